@@ -9,10 +9,15 @@ fusion, batch 256 per GPU, bf16 backbone compute, synthetic 224x224x3 images + 2
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events recorded on the launch stream
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the --steps steps, writes
+--dump-outputs if given, and prints the line (`roofline` null, no `cpu_baseline`).  With --full it also
+measures the rest: `roofline` is measured live with HIP events recorded on the launch stream
 around every kernel of the dominant class (the implicit-GEMM convolution kernel, forward + dgrad);
 `cpu_baseline` times the CPU oracle (a port: the reference's Python never travels to the GPU box) on a
-bounded sample of the same workload.
+bounded sample of the same workload; N > 1 adds rank 0's kernel-class times with the collectives in flight.
+
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR   # last timed step's outputs as DIR/<name>.npy
 """
 import argparse
 import ctypes
@@ -23,6 +28,7 @@ import socket
 import subprocess
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.join(ROOT, "multimodal-model-skin-lesion-classifier_amd")
@@ -270,6 +276,35 @@ def cpu_baseline(batch, seconds=12.0, workload="resnet50-crossattention"):
             "sample": f"{n} fwd+bwd steps of batch {batch} (fp32, torch CPU oracle), {dt:.1f}s"}
 
 
+DUMP_SAMPLE = 4096            # elements kept per parameter / gradient tensor (fixed, seeded by the tensor's name)
+DUMP_BUDGET = 64 << 20        # bytes, all files together
+
+
+def dump_outputs(path, model, logits, loss):
+    """--dump-outputs: what the last timed step handed its caller, as float32 DIR/<name>.npy -- `logits` (the
+    forward's output), and for a train step `loss`, plus `param.<name>` / `grad.<name>` for every parameter after the
+    optimizer step (tensors above DUMP_SAMPLE elements: the same seeded sample of flat indices in every run)."""
+    import numpy as np
+    arrays = {"logits": logits.detach().float().cpu().numpy()}
+    if loss is not None:
+        arrays["loss"] = loss.detach().float().cpu().numpy()
+        for name, p in model.named_parameters():
+            idx = None
+            if p.numel() > DUMP_SAMPLE:   # the coordinates of tests/step_fixtures.py's sample_index
+                g = torch.Generator().manual_seed(zlib.crc32(name.encode()) & 0x7FFFFFFF)
+                idx = torch.randperm(p.numel(), generator=g)[:DUMP_SAMPLE].sort().values.to(p.device)
+            for kind, t in (("param", p), ("grad", p.grad)):
+                if t is not None:
+                    flat = t.detach().reshape(-1)
+                    arrays[f"{kind}.{name}"] = (flat if idx is None else flat[idx]).float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, over the {DUMP_BUDGET} byte budget")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -279,8 +314,13 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--workload", default="resnet50-crossattention", choices=sorted(WORKLOADS))
     ap.add_argument("--infer", action="store_true", help="time the eval-mode forward only (secondary line; BN folded into the convs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline, the per-kernel-class roofline "
+                         "pass and (N > 1) the class times with the collectives in flight")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline pass")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for rehearsals)")
     ap.add_argument("--device", type=int, default=None, help="force every rank onto this device (rehearsal on a 1-GPU box)")
     ap.add_argument("--rehearse", action="store_true",
@@ -334,9 +374,13 @@ def main():
     adam_cls = torch.optim.Adam if os.environ.get("MMSKIN_TORCH_ADAM", "0") == "1" else ArenaAdam
     opt = adam_cls(model.parameters(), lr=5e-5, weight_decay=1e-4, fused=True)
 
+    last = {}   # the logits of the latest step (--dump-outputs)
+
     def infer_step():
         with torch.no_grad():
-            return model(image, meta).sum()
+            logits = model(image, meta)
+            last["logits"] = logits
+            return logits.sum()
 
     # gradient all-reduce queued per encoder segment from inside backward (mmskin/dp.py); MMSKIN_DP_OVERLAP=0: one
     # all-reduce after backward
@@ -353,7 +397,9 @@ def main():
         if args.infer:
             return infer_step()
         opt.zero_grad(set_to_none=True)
-        loss = crit(model(image, meta), label)
+        logits = model(image, meta)
+        last["logits"] = logits.detach()
+        loss = crit(logits, label)
         loss.backward()
         if sync is not None:
             reduced[0] = sync.finish()
@@ -385,9 +431,12 @@ def main():
         dist.all_reduce(tmin, op=dist.ReduceOp.MIN)
         rank_ms = {"min": round(float(tmin) / args.steps * 1e3, 3), "max": round(dt / args.steps * 1e3, 3)}
     loss_val = float(loss.detach())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, last["logits"], None if args.infer else loss)
 
+    want_roofline = args.full and not args.no_roofline and not args.infer
     roofline, plan = None, None
-    if not args.no_roofline and not args.infer:
+    if want_roofline:
         enc = model.image_encoder.features if hasattr(model.image_encoder, "classifier") and hasattr(model.image_encoder.features, "_plans") else model.image_encoder
         plan = next(iter(enc._plans.values())) if hasattr(enc, "_plans") else None
     # N > 1: the kernel-class times of rank 0 WITH the collectives in flight -- every rank runs the same three extra (untimed) steps, rank 0
@@ -409,9 +458,9 @@ def main():
             classes_dp = {CLASS_NAMES[i]: round(ms[i] / 3, 3) for i in range(7)}
     if rank != 0:
         plan = None
-    if plan_missing := (rank == 0 and not args.no_roofline and not args.infer and plan is None):
+    if plan_missing := (rank == 0 and want_roofline and plan is None):
         roofline = {"note": "this workload's image encoder is a composition of HIP ops without a plan executor: no per-class timers"}
-    if rank == 0 and not args.no_roofline and not args.infer and not plan_missing:
+    if rank == 0 and want_roofline and not plan_missing:
         lib = _lib.load()
         lib.mmskin_backbone_profile_enable(plan.handle, 1)
         nprof = 3
@@ -521,7 +570,7 @@ def main():
                          # stream onto the main one) against roofline.classes, the same pass without any collective
                          "class_ms_with_collectives": classes_dp,
                          "backend": args.backend}
-        if world == 1 and not args.no_cpu_baseline and not args.infer:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.infer:
             try:
                 out["cpu_baseline"] = cpu_baseline(32, workload=args.workload)   # batches of 32, not 256: bounded sample
             except ValueError as e:   # the CPU oracle model covers the torchvision backbones + one-hot / tab-transformer metadata only

@@ -6,7 +6,7 @@ O=$R/gpurun_out/r3_secondary
 mkdir -p $O
 cd $R
 for w in densenet169-metablock davit-tiny-gfcam beitv2-large-bert-rgatt; do
-  timeout -k 10 400 python3 bench.py --workload $w --no-cpu-baseline --steps 10 --warmup 2 > $O/bench_$w.json 2> $O/bench_$w.err
+  timeout -k 10 400 python3 bench.py --workload $w --full --no-cpu-baseline --steps 10 --warmup 2 > $O/bench_$w.json 2> $O/bench_$w.err
   tail -c 700 $O/bench_$w.json
 done
 cd /tmp && export TMPDIR=/tmp
