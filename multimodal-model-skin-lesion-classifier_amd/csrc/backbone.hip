@@ -45,7 +45,7 @@ struct Plan : PlanBase {
   int64_t staged_elems = 0;
   // workspace layout (bytes)
   size_t off_img4, off_wf, off_wd, off_stat, off_pool, off_idx, off_scratch[7], off_slab, off_partial,
-      off_coefbwd, off_coefbwd_b, off_dwv, off_red, off_partial_b, off_stat_b, off_red_b;
+      off_coefbwd, off_dwv, off_red, off_partial_b, off_stat_b, off_red_b;
   size_t off_abn_wd = 0, off_abn_bias = 0, off_abn_S = 0, off_abn_cs = 0;   // algebraic BatchNorm backward scratch
   size_t off_abn_wd2 = 0, off_abn_bias2 = 0;                                 // ... of a stride-1 downsample convolution (its folded weights live beside conv3's)
   size_t off_abn_sgx = 0, off_abn_slab2 = 0, off_abn_S2 = 0, off_abn_cs2 = 0;   // two-pass units: main-stream weight-gradient scratch
@@ -204,10 +204,9 @@ int build_plan(Plan& p) {
     b.mask_off = carve(cur, bl.rows() * bl.s.Cout * es / 16);
   }
   for (int i = 0; i < 7; ++i) p.off_scratch[i] = carve(cur, p.maxact_bytes);
-  {   // algebraic BatchNorm backward of the bottlenecks' expanding 1x1 convolutions (bf16 plans; MMSKIN_ABN=0 switches it off,
-      // MMSKIN_ABN_MAXC bounds the input width it takes: the data gradient of wider layers belongs to the pipelined kernel)
-    static const int abn_on = [] { const char* v = getenv("MMSKIN_ABN"); return v ? atoi(v) : 1; }();
-    static const int abn_maxc = [] { const char* v = getenv("MMSKIN_ABN_MAXC"); return v ? atoi(v) : 128; }();
+  {   // algebraic BatchNorm backward of the bottlenecks' expanding 1x1 convolutions (bf16 plans), up to abn_maxc input channels:
+      // the data gradient of wider layers belongs to the pipelined kernel
+    constexpr int abn_maxc = 128;
     size_t wd_max = 0, s_max = 0;
     int cw_max = 0;
     std::vector<int> cand;
@@ -217,7 +216,7 @@ int build_plan(Plan& p) {
       WgradRingPlan rp;
       int sh = 0;
       while ((u.s.Cin << sh) < u.s.Cout) ++sh;
-      if (!abn_on || p.dtype != 1 || !bottleneck || u.s.kh != 1 || u.s.stride != 1 || u.s.Cin > abn_maxc || u.s.Cin % 64 || (u.s.Cin << sh) != u.s.Cout ||
+      if (p.dtype != 1 || !bottleneck || u.s.kh != 1 || u.s.stride != 1 || u.s.Cin > abn_maxc || u.s.Cin % 64 || (u.s.Cin << sh) != u.s.Cout ||
           !wgrad_gram_plan((int)u.rows(), u.s.Cout, u.s.Cin, rp) || rp.gram_tiles != 1)
         continue;
       u.abn = true;
@@ -236,19 +235,17 @@ int build_plan(Plan& p) {
       p.off_abn_cs = carve(cur, (size_t)cw_max * sizeof(float));
       p.off_abn_wd2 = carve(cur, wd_max);
       p.off_abn_bias2 = carve(cur, (size_t)cw_max * sizeof(float));
-      static const int fwd2p_on = [] { const char* v = getenv("MMSKIN_FWD2P"); return v ? atoi(v) : 1; }();
       size_t slab2 = 0;
       for (Block& b : p.blocks) {
         Unit& u = p.units[b.units.back()];
-        if (!fwd2p_on || !u.abn || b.ds >= 0) continue;
+        if (!u.abn || b.ds >= 0) continue;
         u.fwd2p = true;
         size_t sb = wgrad_gram_slab_bytes((int)u.rows(), u.s.Cout, u.s.Cin);
         if (sb > slab2) slab2 = sb;
-        // MMSKIN_FWDG (default 1): the first pass is not the convolution again but the Gram matrix of its INPUT (gram_stats, abn.hip);
-        // the backward pass reuses that matrix and runs g^T y alone
-        static const int fwdg_on = [] { const char* v = getenv("MMSKIN_FWDG"); return v ? atoi(v) : 1; }();
+        // the first pass is not the convolution again but the Gram matrix of its INPUT (gram_stats, abn.hip); the backward pass
+        // reuses that matrix and runs g^T y alone
         WgradRingPlan rg;
-        if (fwdg_on && wgrad_gram_plan((int)u.rows(), 0, u.s.Cin, rg, 2) && rg.gram_tiles == 1 &&
+        if (wgrad_gram_plan((int)u.rows(), 0, u.s.Cin, rg, 2) && rg.gram_tiles == 1 &&
             wgrad_gram_slab_bytes((int)u.rows(), u.s.Cout, u.s.Cin, 1)) {
           u.gram_off = carve(cur, ((size_t)128 + 1) * u.s.Cin * sizeof(float));
           sb = wgrad_gram_slab_bytes((int)u.rows(), 0, u.s.Cin, 2);
@@ -269,7 +266,6 @@ int build_plan(Plan& p) {
   p.off_partial = carve(cur, partial_max);
   p.off_partial_b = carve(cur, partial_max);
   p.off_coefbwd = carve(cur, 3 * (size_t)maxC * sizeof(float));
-  p.off_coefbwd_b = carve(cur, 3 * (size_t)maxC * sizeof(float));   // the downsample branch's own coefficients (its stream in backward)
   p.off_dwv = carve(cur, 64 * 256 * sizeof(float));
   p.off_red = carve(cur, bn_reduce_scratch_bytes(maxC));
   p.off_red_b = carve(cur, bn_reduce_scratch_bytes(maxC));
@@ -340,8 +336,7 @@ int forward_impl(Plan& p, const void* image, const float* norm6, const float* pa
   p.staged_eval_ws = folded_eval ? ws : nullptr;
   // stage weights (stem region needs zeros in its padding taps)
   if (!reuse) HIP_CHECK_RET(hipMemsetAsync(wf + p.units[0].wf_off, 0, 64 * 256 * sizeof(T), st));
-  static const bool side_off_f = [] { const char* v = getenv("MMSKIN_NO_SIDE_STREAM"); return v && atoi(v) != 0; }();
-  const bool use_side = !side_off_f && !p.prof.on;
+  const bool use_side = !p.prof.on;
   if (use_side && (rc = p.side.init())) return rc;
   const bool stage_aside = use_side && training;   // the stem only needs its own weights: the other layers are staged beside it
   const float* fold = (training || p.keep_raw_eval) ? nullptr : buffers;
@@ -502,25 +497,22 @@ int backward_impl(Plan& p, const float* dfeat, const float* params, unsigned cha
   float* partial_b = reinterpret_cast<float*>(ws + p.off_partial_b);
   // BN backward of unit u when `dz` is ALREADY masked and its partial sums (sum dz, sum dz*x) were
   // produced by the epilogue of the dgrad launch that wrote dz: finalize + one apply pass.
-  // on_branch: the downsample branch on its own stream (own coefficient and reduction scratch)
   // dx == nullptr: finalize only (gamma / beta gradients and the coefficients cA, cB, cC) -- the algebraic path folds the apply
   // into its two GEMMs
-  auto bn_backward_fused = [&](Unit& u, const T* dz, const float* part, int nrows, T* dx, bool on_branch = false, const float* sum_dz_x = nullptr) -> int {
+  auto bn_backward_fused = [&](Unit& u, const T* dz, const float* part, int nrows, T* dx, const float* sum_dz_x = nullptr) -> int {
     const int C = u.s.Cout;
     float* coef = reinterpret_cast<float*>(ws + u.coef_off);
     const T* x = reinterpret_cast<const T*>(ws + u.x_off);
-    float* kA = on_branch ? reinterpret_cast<float*>(ws + p.off_coefbwd_b) : cA;
-    float* cB = kA + C; float* cC = kA + 2 * C;
-    hipStream_t bs = on_branch ? p.side.s2 : st;
-    double* red = reinterpret_cast<double*>(ws + (on_branch ? p.off_red_b : p.off_red));
+    float* cB = cA + C; float* cC = cA + 2 * C;
+    double* red = reinterpret_cast<double*>(ws + p.off_red);
     int r;
     p.prof.begin(K_BN_BWD, st);
     struct End { Profiler& pr; hipStream_t s; ~End() { pr.end(s); } } end_guard{p.prof, st};
     if (p.prof.on && dx) p.prof.bytes[K_BN_BWD] += 3.0 * u.rows() * C * sizeof(T);
     if ((r = bn_bwd_finalize(part, nrows, C, (double)u.rows(), params + u.g_off, coef + 2 * C, coef + 3 * C,
-                             grads + u.g_off, grads + u.b_off, kA, cB, cC, red, bs, -1, false, sum_dz_x))) return r;
+                             grads + u.g_off, grads + u.b_off, cA, cB, cC, red, st, -1, false, sum_dz_x))) return r;
     if (!dx) return MMSKIN_OK;
-    return bn_bwd_apply<T>(dz, x, nullptr, coef, coef + C, MASK_NONE, kA, cB, cC, dx, nullptr, u.rows(), C, bs);
+    return bn_bwd_apply<T>(dz, x, nullptr, coef, coef + C, MASK_NONE, cA, cB, cC, dx, nullptr, u.rows(), C, st);
   };
 
   Unit& last = p.units[p.blocks.back().units.back()];
@@ -529,24 +521,19 @@ int backward_impl(Plan& p, const float* dfeat, const float* params, unsigned cha
   if ((rc = avgpool_bwd<T>(dfeat, p.N, last.s.OH() * last.s.OW(), last.s.Cout, g, st))) return rc;
 
   // ---- side stream for the weight-gradient GEMMs (buffers: 0/1 = alternating dX, 2 = downsample dX)
-  static const bool side_off = [] { const char* v = getenv("MMSKIN_NO_SIDE_STREAM"); return v && atoi(v) != 0; }();
-  const bool use_side = !side_off && !p.prof.on;
+  const bool use_side = !p.prof.on;
   if (use_side && (rc = p.side.init())) return rc;
   for (int i = 0; i < 3; ++i) p.side.done_valid[i] = false;
-  // measured: 19.99 / 20.06 ms per step off, 20.05 / 20.12 ms on (same box, profiles/r03_experiments.txt (9)) -- the chip has no idle
-  // resource for the branch to use, the launches only move.  Off by default; kept as an A/B knob.
-  static const bool ds_stream = [] { const char* v = getenv("MMSKIN_BWD_DS_STREAM"); return v && atoi(v) != 0; }();
   T* DX[3] = {S[2], S[6], S[5]};
   // main stream may overwrite buffer i only after the wgrad that reads it has finished
   auto acquire = [&](int i) -> int {
     if (use_side && p.side.done_valid[i]) HIP_CHECK_RET(hipStreamWaitEvent(st, p.side.done[i], 0));
     return MMSKIN_OK;
   };
-  // from: the stream that produced DX[i] (the main stream, or the downsample branch's)
-  auto wgrad_async = [&](Unit& u, int i, const T* uin, hipStream_t from = nullptr) -> int {
+  auto wgrad_async = [&](Unit& u, int i, const T* uin) -> int {
     hipStream_t ws_st = st;
     if (use_side) {
-      HIP_CHECK_RET(hipEventRecord(p.side.ready[i], from ? from : st));
+      HIP_CHECK_RET(hipEventRecord(p.side.ready[i], st));
       HIP_CHECK_RET(hipStreamWaitEvent(p.side.s, p.side.ready[i], 0));
       ws_st = p.side.s;
     }
@@ -566,9 +553,9 @@ int backward_impl(Plan& p, const float* dfeat, const float* params, unsigned cha
   // algebraic path: the weight-gradient stream reads the block-output gradient buffer (S[0] / S[1]) itself; the main stream may write
   // that buffer again (two blocks later) only after that launch has finished
   auto g_index = [&](const T* buf) { return buf == S[0] ? 0 : 1; };
-  auto g_acquire = [&](const T* buf, hipStream_t writer = nullptr) -> int {
+  auto g_acquire = [&](const T* buf) -> int {
     const int i = g_index(buf);
-    if (use_side && p.side.g_done_valid[i]) HIP_CHECK_RET(hipStreamWaitEvent(writer ? writer : st, p.side.g_done[i], 0));
+    if (use_side && p.side.g_done_valid[i]) HIP_CHECK_RET(hipStreamWaitEvent(st, p.side.g_done[i], 0));
     return MMSKIN_OK;
   };
   // dW = cA (.) (g^T y) + cB (.) (W (y^T y)) + cC (x) colsum(y) on the weight-gradient stream
@@ -612,23 +599,13 @@ int backward_impl(Plan& p, const float* dfeat, const float* params, unsigned cha
     T* dZ = S[4];
     T* dXd = DX[2];
     const bool has_ds = b.ds >= 0;
-    // The downsample branch (BatchNorm-backward apply, dgrad) only has to be done when conv1's dgrad takes its result as the
-    // addend: with MMSKIN_BWD_DS_STREAM=1 it runs on its own stream beside conv3 .. conv2 (as in the forward; ~0.9 ms of launches
-    // per ResNet-50 step leave the main chain).  The main stream hands it g + partial_b (d_ready) and takes gin back (d_done).
-    const bool ds_branch = has_ds && use_side && ds_stream && fused_ready;
     const T* dz_final;   // masked gradient of the block output (residual branch addend)
     dxi ^= 1;
     if ((rc = acquire(dxi))) return rc;
-    if (has_ds && !ds_branch && (rc = acquire(2))) return rc;
+    if (has_ds && (rc = acquire(2))) return rc;
     T* dX = DX[dxi];
     const bool abn = fused_ready && ul.abn && sizeof(T) == 2;
     if (fused_ready) {
-      if (ds_branch) {
-        HIP_CHECK_RET(hipEventRecord(p.side.d_ready, st));
-        HIP_CHECK_RET(hipStreamWaitEvent(p.side.s2, p.side.d_ready, 0));
-        if (p.side.done_valid[2]) HIP_CHECK_RET(hipStreamWaitEvent(p.side.s2, p.side.done[2], 0));   // the last wgrad that read dXd
-        if ((rc = bn_backward_fused(p.units[b.ds], g, partial_b, fused_rows, dXd, true))) return rc;
-      }
       const T* uin3 = nu > 1 ? reinterpret_cast<const T*>(ws + p.units[b.units[nu - 2]].y_off) : in;
       const float* sgx = nullptr;
       if (abn && ul.fwd2p) {
@@ -645,7 +622,7 @@ int backward_impl(Plan& p, const float* dfeat, const float* params, unsigned cha
           sgx = reinterpret_cast<const float*>(ws + p.off_abn_sgx);
         }
       }
-      if ((rc = bn_backward_fused(ul, g, partial, fused_rows, abn ? nullptr : dX, false, sgx))) return rc;
+      if ((rc = bn_backward_fused(ul, g, partial, fused_rows, abn ? nullptr : dX, sgx))) return rc;
       if (abn) {   // fold the coefficients into this block's conv3 data-gradient weights; keep a copy for the weight-gradient fix-up
         if constexpr (sizeof(T) == 2) {
           if ((rc = abn_prep(params + ul.w_off, cA, cA + ul.s.Cout, cA + 2 * ul.s.Cout, ul.s.Cout, ul.s.Cin, reinterpret_cast<bf16_t*>(ws + p.off_abn_wd),
@@ -656,7 +633,7 @@ int backward_impl(Plan& p, const float* dfeat, const float* params, unsigned cha
                                                    reinterpret_cast<const float*>(ws + ul.abn_coef_off), ul.s.Cout, ul.s.Cin, grads + ul.w_off, st, gkept))) return rc;
         }
       }
-      if (has_ds && !ds_branch) {
+      if (has_ds) {
         Unit& d = p.units[b.ds];
         const bool abn_d = d.abn && sizeof(T) == 2;
         if ((rc = bn_backward_fused(d, g, partial_b, fused_rows, abn_d ? nullptr : dXd))) return rc;
@@ -699,16 +676,11 @@ int backward_impl(Plan& p, const float* dfeat, const float* params, unsigned cha
       } else {
         const T* addend = dz_final;
         bool ds_addend_compact = false;
-        static const bool ds_compact = [] { const char* v = getenv("MMSKIN_DS_COMPACT"); return !v || atoi(v) != 0; }();
+        static const bool ds_compact = env_knob("MMSKIN_DS_COMPACT", 1) != 0;
         if (has_ds) {
           Unit& d = p.units[b.ds];
-          if ((rc = g_acquire(gin, ds_branch ? p.side.s2 : nullptr))) return rc;
-          if (ds_branch) {
-            if ((rc = wgrad_async(d, 2, in, p.side.s2))) return rc;
-            if ((rc = launch_conv_dgrad<T>(d.s, dXd, wd + d.wd_off, gin, (const T*)nullptr, p.side.s2))) return rc;
-            HIP_CHECK_RET(hipEventRecord(p.side.d_done, p.side.s2));
-            HIP_CHECK_RET(hipStreamWaitEvent(st, p.side.d_done, 0));
-          } else if (fused_ready && d.abn && sizeof(T) == 2) {   // stride-1 downsample convolution on the algebraic path, as conv3 above
+          if ((rc = g_acquire(gin))) return rc;
+          if (fused_ready && d.abn && sizeof(T) == 2) {   // stride-1 downsample convolution on the algebraic path, as conv3 above
             if ((rc = wgrad_abn_async(d, g, in))) return rc;
             DgradFuse fd;
             fd.in2 = in; fd.k2 = d.s.Cin; fd.bias = reinterpret_cast<const float*>(ws + p.off_abn_bias2);
@@ -760,9 +732,7 @@ int backward_impl(Plan& p, const float* dfeat, const float* params, unsigned cha
     float* cB = cA + 64; float* cC = cA + 128;
     int nr = 0;
     p.prof.begin(K_BN_BWD, st);
-    // MMSKIN_STEM_SUMS_POOLED=0: the sums from the conv output and the routed gradient (565 MB read instead of 206 MB)
-    static const bool pooled_sums = [] { const char* v = getenv("MMSKIN_STEM_SUMS_POOLED"); return !v || atoi(v) != 0; }();
-    if (pooled_sums) rc = stem_pool_bwd_sums<T>(g, reinterpret_cast<const T*>(ws + p.off_pool), ws + p.off_idx, x0, c0, c0 + 64, p.N, p.OH0, p.OW0, 64, partial, &nr, st);
+    if (stem_sums_pooled()) rc = stem_pool_bwd_sums<T>(g, reinterpret_cast<const T*>(ws + p.off_pool), ws + p.off_idx, x0, c0, c0 + 64, p.N, p.OH0, p.OW0, 64, partial, &nr, st);
     else rc = stem_pool_bn_bwd_reduce<T>(g, ws + p.off_idx, x0, c0, c0 + 64, p.N, p.OH0, p.OW0, 64, partial, &nr, st);
     if (!rc) rc = bn_bwd_finalize(partial, nr, 64, (double)u0.rows(), params + u0.g_off, c0 + 128, c0 + 192, grads + u0.g_off,
                                   grads + u0.b_off, cA, cB, cC, reinterpret_cast<double*>(ws + p.off_red), st);

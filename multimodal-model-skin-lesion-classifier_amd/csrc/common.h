@@ -6,6 +6,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
+#include <mutex>
+#include <set>
+#include <utility>
 
 typedef uint16_t bf16_t;  // storage type for bf16 activations / staged weights
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
@@ -181,3 +185,25 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Integer value of the environment variable `name`, or `dflt` when it is unset.  The one way the library reads its
+// configuration variables (INTEGRATION.md section 1 lists them); callers cache the result in a function-local static.
+inline int env_knob(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
+
+// Opt `kern` in to `bytes` of dynamic LDS (above the 64 KiB default).  The attribute belongs to the kernel on one device, so it
+// is set once per (kernel, device), under a lock: launchers may run on several host threads and devices at once.
+inline hipError_t opt_in_dynamic_lds(const void* kern, int bytes) {
+  static std::mutex mu;
+  static std::set<std::pair<const void*, int>> done;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  std::lock_guard<std::mutex> lock(mu);
+  if (done.count({kern, dev})) return hipSuccess;
+  e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) done.insert({kern, dev});
+  return e;
+}

@@ -277,12 +277,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_c64_kernel(const C3Args p) {
 template <int FH, int EPI, int FLIP>
 int launch_one(const C3Args& a, hipStream_t st) {
   constexpr int lds = WBYTES + RING * (8 * FH + 2) * PITCH;
-  static bool attr_done = false;
   auto kern = conv3x3_c64_kernel<FH, EPI, FLIP>;
-  if (!attr_done) {
-    HIP_CHECK_RET(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_done = true;
-  }
+  HIP_CHECK_RET(opt_in_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
 #ifdef MMSKIN_ABLATE
   { const char* e = getenv("MMSKIN_C3_ABLATE"); const_cast<C3Args&>(a).ablate = e ? atoi(e) : 0; }
 #endif
@@ -296,8 +292,8 @@ int launch_one(const C3Args& a, hipStream_t st) {
 // MMSKIN_CONV3X3_C64=0 sends these launches back to the tapped kernel (A/B knob).  The shape: 64 -> 64 channels, 3x3 / stride 1 / pad 1,
 // 56 x 56 (FH = 7) rows of whole 4-row tiles, at least 32 images (one workgroup per image must cover a useful part of the chip).
 bool conv3x3_c64_takes(const ConvShape& s, bool bf16) {
-  static const bool on = [] { const char* v = getenv("MMSKIN_CONV3X3_C64"); return !v || atoi(v) != 0; }();
-  static const int min_n = [] { const char* v = getenv("MMSKIN_CONV3X3_C64_MIN_N"); return v ? atoi(v) : 32; }();
+  static const bool on = env_knob("MMSKIN_CONV3X3_C64", 1) != 0;
+  static const int min_n = env_knob("MMSKIN_CONV3X3_C64_MIN_N", 32);
   return on && bf16 && s.Cin == 64 && s.Cout == 64 && s.kh == 3 && s.kw == 3 && s.stride == 1 && s.pad == 1 && s.W == 56 && s.H % 4 == 0 &&
          s.H >= 8 && s.N >= min_n;
 }

@@ -604,13 +604,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (EPI == 6 && WAVES_M * WAVE
   // issued before any of them is consumed, so EG*3 16-byte loads are in flight per lane instead of one
   // dependent load->store chain per row (the fused epilogue was running at ~3 TB/s that way).
   constexpr int NR = BM / ROWS_PER_PASS;
-#ifndef MMSKIN_EPI_ROWS4
-#define MMSKIN_EPI_ROWS4 4
-#endif
-#ifndef MMSKIN_EPI_ROWS7
-#define MMSKIN_EPI_ROWS7 4
-#endif
-  constexpr int EG_MAX = EPI == 6 ? 2 : (EPI == 4 ? MMSKIN_EPI_ROWS4 : (EPI == 7 ? MMSKIN_EPI_ROWS7 : 4));   // profile 6 holds 32 B of fp32 residual per row in flight: two rows keep it at the main loop's register count
+  constexpr int EG_MAX = EPI == 6 ? 2 : 4;   // profile 6 holds 32 B of fp32 residual per row in flight: two rows keep it at the main loop's register count
   // the pipelined kernel has ONE workgroup per CU and nothing else to overlap its epilogue with, while its 112 - 128 accumulator
   // registers are dead by now: half of a thread's 14 / 16 rows in flight at a time (7 / 8 x up to 3 16-byte loads) instead of 2 / 4
   constexpr int EG = PIPE ? NR / 2 : (NR < EG_MAX ? NR : (NR % EG_MAX == 0 ? EG_MAX : 2));
@@ -802,19 +796,14 @@ template <typename T, int BM, int BN, int WMv, int WNv, int EPI, int NST>
 static int launch_cfg(const ConvGemmArgs& a, hipStream_t st) {
   constexpr int NT = 64 * WMv * WNv;
   constexpr int lds = conv_gemm_lds_bytes<BM, BN, T, NST, NT>();
-  static bool attr_done = false;
   auto kern = conv_gemm_kernel<T, BM, BN, WMv, WNv, EPI, NST>;
-  if (!attr_done) {
-    HIP_CHECK_RET(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_done = true;
-  }
+  HIP_CHECK_RET(opt_in_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
   int grid = a.total_mblk * a.nblk_n;
   if (grid == 0) return MMSKIN_OK;
   // Linear GEMMs ({M, 1, 1, K, N} shapes) with a weight matrix larger than an XCD's L2: with column blocks fastest every row block
   // streamed the whole weight through L2 again (BEiT fc1: 1.2 GB of L2 fills per launch for 60 MB of operands,
   // profiles/r03_step_traffic_beitv2-large-bert-rgatt.txt); groups of 8 row blocks keep their A rows resident instead.
-  static const int gm_env = [] { const char* v = getenv("MMSKIN_GEMM_GROUP_M"); return v ? atoi(v) : 8; }();
+  static const int gm_env = env_knob("MMSKIN_GEMM_GROUP_M", 8);
   ConvGemmArgs b = a;
   b.group_m = 0;
   if (gm_env > 1 && a.ncls == 1 && a.IH == 1 && a.IW == 1 && a.nblk_n >= 4 && (size_t)a.Cout * a.wrow * sizeof(T) > ((size_t)2 << 20) &&
@@ -838,24 +827,19 @@ static void finish_classes(ConvGemmArgs& a, int step = CONV_BM) {
   a.bm_step = step;
 }
 
-// ---- selection of the 8-phase pipelined kernel (NST == 8).  MMSKIN_CONV_PIPE=0 switches it off, MMSKIN_CONV_PIPE_MINK (elements of
-// the reduction) is the shortest K it takes, MMSKIN_CONV_PIPE_FORCE=1 takes every eligible launch (tests), MMSKIN_CONV_PIPE_TILE=
-// 256 | 224 | 196 pins the tile rows instead of the tile-count model below.
 static int64_t g_pipe_launches = 0;
 extern "C" int64_t mmskin_conv_pipe_launches(void) { return g_pipe_launches; }
 struct PipeChoice { int bm, step; };
 // Selection of the pipelined kernel (NST == 8).  One 512-thread workgroup per CU: it pays where the reduction is deep enough to
-// amortise a ~8 us prologue + epilogue that nothing overlaps (row-weighted K >= MMSKIN_CONV_PIPE_MINK, default 1024) and the launch
-// has enough tiles to cover most of the chip (>= MMSKIN_CONV_PIPE_MINTILES, default 192); measured per ResNet-50 layer in
-// profiles/r03_experiments.txt.  MMSKIN_CONV_PIPE=0 switches it off, MMSKIN_CONV_PIPE_FORCE=1 takes every eligible launch (tests),
-// MMSKIN_CONV_PIPE_TILE = 256 | 224 | 196 pins the tile rows instead of the tile-count model below.
+// amortise a ~8 us prologue + epilogue that nothing overlaps (row-weighted K >= PIPE_MIN_K) and the launch has enough tiles to cover
+// most of the chip (>= PIPE_MIN_TILES); measured per ResNet-50 layer in profiles/r03_experiments.txt.  MMSKIN_CONV_PIPE_FORCE=1
+// takes every eligible launch (tests), MMSKIN_CONV_PIPE_TILE = 256 | 224 | 196 pins the tile rows instead of the tile-count model below.
+constexpr int PIPE_MIN_K = 1024;
+constexpr int PIPE_MIN_TILES = 192;
 static bool pipe_choose(const ConvGemmArgs& a, bool tr, int prof, bool heavy, PipeChoice* out) {
-  static const int on = [] { const char* v = getenv("MMSKIN_CONV_PIPE"); return v ? atoi(v) : 1; }();
-  static const int force = [] { const char* v = getenv("MMSKIN_CONV_PIPE_FORCE"); return v ? atoi(v) : 0; }();
-  static const int mink = [] { const char* v = getenv("MMSKIN_CONV_PIPE_MINK"); return v ? atoi(v) : 1024; }();
-  static const int mintiles = [] { const char* v = getenv("MMSKIN_CONV_PIPE_MINTILES"); return v ? atoi(v) : 192; }();
-  static const int pin = [] { const char* v = getenv("MMSKIN_CONV_PIPE_TILE"); return v ? atoi(v) : 0; }();
-  if (!on || !a.pipe_ok || a.in2 || a.addend_sub || prof == 7 || a.ep_mask_out || a.ep_mul || !a.out || a.in_bytes == 0 || a.in_bytes > 0xE0000000ull || (heavy && prof == 1) || a.Cout % 256 != 0 ||
+  static const int force = env_knob("MMSKIN_CONV_PIPE_FORCE", 0);
+  static const int pin = env_knob("MMSKIN_CONV_PIPE_TILE", 0);
+  if (!a.pipe_ok || a.in2 || a.addend_sub || prof == 7 || a.ep_mask_out || a.ep_mul || !a.out || a.in_bytes == 0 || a.in_bytes > 0xE0000000ull || (heavy && prof == 1) || a.Cout % 256 != 0 ||
       a.C % 64 != 0 || a.ncls < 1)
     return false;
   if (tr && (heavy || a.addend || a.stat_sum || !a.out_f32)) return false;   // the transformer-residual epilogue's own contract (checked below)
@@ -880,8 +864,8 @@ static bool pipe_choose(const ConvGemmArgs& a, bool tr, int prof, bool heavy, Pi
   if (best >= 1e30) return false;
   // Linear GEMMs ({M, 1, 1, K, N}: no gather, one tap) already pay at K = 768 (BERT-base qkv / fc1 / output.dense: config 5 50.7 -> 50.3 ms);
   // the ResNet convolutions do not below 1024 (profiles/r04_experiments.txt (0))
-  const double mink_eff = (a.IH == 1 && a.IW == 1 && a.ncls == 1 && mink == 1024) ? 768 : mink;
-  return force || (ksum / rsum >= mink_eff && best_tiles >= mintiles);
+  const double mink = (a.IH == 1 && a.IW == 1 && a.ncls == 1) ? 768 : PIPE_MIN_K;
+  return force || (ksum / rsum >= mink && best_tiles >= PIPE_MIN_TILES);
 }
 
 template <typename T>
@@ -901,18 +885,17 @@ static int dispatch_conv_gemm(ConvGemmArgs& a, hipStream_t st) {
   // Single-buffer variant (3-4 workgroups per CU) whenever the launch has enough workgroups to use the
   // extra residency: measured on the ResNet-50 shape mix (scripts/conv_mix.py) it wins for every layer
   // with more than ~2.5 workgroups per CU and loses for the 392-workgroup layer-4 launches.
-  static const int nst1_min_blocks = [] { const char* v = getenv("MMSKIN_CONV_NST1_MINBLOCKS"); return v ? atoi(v) : 640; }();
-  static const int nst1_min_blocks_epi = [] { const char* v = getenv("MMSKIN_CONV_NST1_MINBLOCKS_EPI"); return v ? atoi(v) : 800; }();   // fused-epilogue launches: 168 VGPRs = 3 workgroups/CU = 768 single-buffer slots; a 784-workgroup launch would spill into a second round
+  constexpr int nst1_min_blocks = 640;
+  constexpr int nst1_min_blocks_epi = 800;   // fused-epilogue launches: 168 VGPRs = 3 workgroups/CU = 768 single-buffer slots; a 784-workgroup launch would spill into a second round
   const int bn_sel = (a.Cout % 128 == 0) ? 128 : 64;
   const bool heavy = a.ep_mask_y || a.ep_mask_bits || a.ep_x;   // needs a fused BatchNorm-backward epilogue
   // 256 x 256 tile, 8 waves (one workgroup per CU, half the L2 -> LDS bytes per FLOP): plain GEMM-like launches (one tap class, no
   // statistics, light epilogue) with a deep reduction whose grid still covers the chip -- fc2 / output.dense of the transformer
   // encoders (K = 3072 / 4096: 1.03 - 1.05 PFLOP/s against 0.88 - 0.92 on the 128 x 128 tile; at K <= 1024 the per-tile prologue and
-  // the 2-wave-per-SIMD epilogue cost more than the fill saves: profiles/r02_experiments.txt (9)).  MMSKIN_GEMM_BIG_MINK=0: off.
-  static const int big_min_k = [] { const char* v = getenv("MMSKIN_GEMM_BIG_MINK"); return v ? atoi(v) : 2048; }();
-  static const bool profiles_on = [] { const char* v = getenv("MMSKIN_CONV_EPI_PROFILES"); return !v || atoi(v) != 0; }();
+  // the 2-wave-per-SIMD epilogue cost more than the fill saves: profiles/r02_experiments.txt (9)).
+  constexpr int big_min_k = 2048;
   int prof = 1;
-  if (profiles_on && heavy && !a.ep_mask_y && !a.ep_relu) {
+  if (heavy && !a.ep_mask_y && !a.ep_relu) {
     if (a.ep_x && !a.addend && !a.ep_mask_bits && !a.ep_x2) prof = 3;   // (+ optional bias)
     else if (!a.ep_bias && a.ep_x && a.ep_mask_bits && !a.ep_scale) prof = a.ep_x2 ? 5 : 4;
     else if (!a.ep_bias && !a.ep_x && !a.ep_x2 && a.ep_mask_bits && !a.ep_scale) prof = 7;
@@ -932,7 +915,7 @@ static int dispatch_conv_gemm(ConvGemmArgs& a, hipStream_t st) {
     }
   }
   if constexpr (sizeof(T) == 2) {
-    if (big_min_k > 0 && a.out && !a.ep_mask_out && !a.ep_mul && a.wrow >= big_min_k && a.ncls == 1 && !heavy && !a.stat_sum && !a.addend && a.Cout % 256 == 0 && a.ep_relu != 2 &&
+    if (a.out && !a.ep_mask_out && !a.ep_mul && a.wrow >= big_min_k && a.ncls == 1 && !heavy && !a.stat_sum && !a.addend && a.Cout % 256 == 0 && a.ep_relu != 2 &&
         a.cls[0].mblk_start == 0 && a.cls[0].ntaps == 1 && a.Sy == 1 && a.Sx == 1 && a.OS == 1) {   // plain GEMMs only (what the tests cover)
       const int mb = ceil_div(a.cls[0].rows, 256), nb = a.Cout / 256;
       if (mb * nb >= 224) {
@@ -1080,8 +1063,7 @@ int launch_conv_dgrad(const ConvShape& s, const T* dout, const T* wt_staged, T* 
       if (c.a_dim <= 0 || c.b_dim <= 0) continue;
       // a tap-less class contributes zeros: skip it when accumulating in place
       if (c.ntaps == 0 && addend == din && addend != nullptr) continue;
-      static const bool zf = [] { const char* v = getenv("MMSKIN_DGRAD_ZEROFILL"); return !v || atoi(v) != 0; }();
-      if (zf && c.ntaps == 0 && addend == nullptr && !fuse) { zero_mask |= 1u << (ph * s.stride + pw); continue; }   // plain zero fill
+      if (c.ntaps == 0 && addend == nullptr && !fuse) { zero_mask |= 1u << (ph * s.stride + pw); continue; }   // plain zero fill
       a.cls[a.ncls++] = c;
     }
   if (zero_mask) {

@@ -394,8 +394,7 @@ int dense_backward(DensePlan& p, const float* dfeat, const float* params, unsign
   // Weight-gradient GEMMs only feed the optimizer: they run on the side stream beside the dgrad -> BN-backward
   // chain (one slab, the side stream is in order).  Operand buffers alternate between consecutive layers; the main
   // stream re-acquires a buffer (waits for the wgrad that read it) before overwriting it.
-  static const bool side_off = [] { const char* v = getenv("MMSKIN_NO_SIDE_STREAM"); return v && atoi(v) != 0; }();
-  const bool use_side = !side_off && !p.prof.on;
+  const bool use_side = !p.prof.on;
   if (use_side) {
     if ((rc = p.side.init())) return rc;
     if ((rc = p.init_events())) return rc;
@@ -452,8 +451,7 @@ int dense_backward(DensePlan& p, const float* dfeat, const float* params, unsign
   // Every later layer of a block adds cA*g + cB*x + cC to the channel prefix it consumed, and x (the concatenated activation) is the
   // same tensor for all of them: the x / constant terms are summed as COEFFICIENTS (sB, sC: bn_bwd_finalize adds into them) and
   // applied once, when a channel's gradient is consumed (its own layer's slice, or the block input at the block's end) -- the
-  // per-layer pass then reads g and read-modify-writes dcat only (3 passes over the prefix instead of 4).  MMSKIN_DN_DEFER=0: the old form.
-  static const bool defer = [] { const char* v = getenv("MMSKIN_DN_DEFER"); return !v || atoi(v) != 0; }();
+  // per-layer pass then reads g and read-modify-writes dcat only (3 passes over the prefix instead of 4).
   float* sB_ = reinterpret_cast<float*>(ws + p.off_defer);
   for (int bi = 3; bi >= 0; --bi) {
     DBlock& b = p.blocks[bi];
@@ -461,7 +459,7 @@ int dense_backward(DensePlan& p, const float* dfeat, const float* params, unsign
     T* dcat = reinterpret_cast<T*>(ws + b.dcat_off);
     const double count = (double)b.rows;
     float* sC_ = sB_ + b.Ctot;
-    if (defer) HIP_CHECK_RET(hipMemsetAsync(sB_, 0, 2 * (size_t)b.Ctot * sizeof(float), st));
+    HIP_CHECK_RET(hipMemsetAsync(sB_, 0, 2 * (size_t)b.Ctot * sizeof(float), st));
     for (int li = (int)b.layers.size() - 1; li >= 0; --li) {
       DLayer& l = b.layers[li];
       float* k1 = reinterpret_cast<float*>(ws + l.coef1_off);
@@ -475,11 +473,8 @@ int dense_backward(DensePlan& p, const float* dfeat, const float* params, unsign
       T* sA = sAq[q];
       // gradient of this layer's 32 output channels, padded to the GEMM's 64
       if ((rc = acquire(q))) return rc;
-      if (defer)
-        PROF(K_BN_BWD, 0.0, 3.0 * b.rows * GROWTH * sizeof(T),
-             slice_pack_deferred<T>(dcat + l.Cin, cat + l.Cin, b.Ctot, GROWTH, G_PAD, b.rows, sB_ + l.Cin, sC_ + l.Cin, sB, st));
-      else
-        PROF(K_BN_BWD, 0.0, 2.0 * b.rows * GROWTH * sizeof(T), slice_pack<T>(dcat + l.Cin, b.Ctot, GROWTH, G_PAD, b.rows, nullptr, nullptr, sB, st));
+      PROF(K_BN_BWD, 0.0, 3.0 * b.rows * GROWTH * sizeof(T),
+           slice_pack_deferred<T>(dcat + l.Cin, cat + l.Cin, b.Ctot, GROWTH, G_PAD, b.rows, sB_ + l.Cin, sC_ + l.Cin, sB, st));
       // conv2: weight gradient (first 32 rows are real) and data gradient with norm2's mask + sums fused
       if ((rc = wgrad_async(q, c2, conv_flops(c2) / 2, sB, u, grads + l.w2_off, GROWTH, 0))) return rc;
       DgradFuse f2;
@@ -504,24 +499,18 @@ int dense_backward(DensePlan& p, const float* dfeat, const float* params, unsign
       f1.x = cat; f1.x_pitch = b.Ctot; f1.scale = k1; f1.shift = k1 + l.Cp; f1.partial = partial;
       PROF(K_CONV_DGRAD, conv_flops(c1), conv_bytes(c1, sizeof(T), 1), launch_conv_dgrad<T>(c1, sA, wd + l.wd1, sZ, (const T*)nullptr, st, &f1));
       {
-        float* cB = cA + l.Cp; float* cC = cA + 2 * l.Cp;
         p.prof.begin(K_BN_BWD, st);
-        if (defer) {   // padded channels [Cin, Cp) have gamma = 0: they add zeros to sB / sC
-          rc = bn_bwd_finalize(partial, f1.rows_written, l.Cp, count, k1 + 4 * l.Cp, k1 + 2 * l.Cp, k1 + 3 * l.Cp,
-                               grads + l.n1.g_off, grads + l.n1.b_off, cA, sB_, sC_, red, st, l.Cin, true);
-          if (!rc) rc = slice_accumulate_scaled<T>(dcat, b.Ctot, l.Cin, sZ, l.Cp, cA, b.rows, st);
-        } else {
-          rc = bn_bwd_finalize(partial, f1.rows_written, l.Cp, count, k1 + 4 * l.Cp, k1 + 2 * l.Cp, k1 + 3 * l.Cp,
-                               grads + l.n1.g_off, grads + l.n1.b_off, cA, cB, cC, red, st, l.Cin);
-          if (!rc) rc = slice_bn_bwd_accumulate<T>(dcat, cat, b.Ctot, l.Cin, sZ, l.Cp, cA, cB, cC, b.rows, st);
-        }
+        // padded channels [Cin, Cp) have gamma = 0: they add zeros to sB / sC
+        rc = bn_bwd_finalize(partial, f1.rows_written, l.Cp, count, k1 + 4 * l.Cp, k1 + 2 * l.Cp, k1 + 3 * l.Cp,
+                             grads + l.n1.g_off, grads + l.n1.b_off, cA, sB_, sC_, red, st, l.Cin, true);
+        if (!rc) rc = slice_accumulate_scaled<T>(dcat, b.Ctot, l.Cin, sZ, l.Cp, cA, b.rows, st);
         p.prof.end(st);
-        if (p.prof.on) p.prof.bytes[K_BN_BWD] += (defer ? 3.0 : 4.0) * b.rows * l.Cin * sizeof(T);
+        if (p.prof.on) p.prof.bytes[K_BN_BWD] += 3.0 * b.rows * l.Cin * sizeof(T);
         if (rc) return rc;
       }
     }
-    if (defer)   // the block-input channels [0, C0): every layer of the block consumed them
-      PROF(K_BN_BWD, 0.0, 3.0 * b.rows * b.C0 * sizeof(T), slice_affine_inplace<T>(dcat, cat, b.Ctot, b.C0, b.rows, sB_, sC_, st));
+    // the block-input channels [0, C0): every layer of the block consumed them
+    PROF(K_BN_BWD, 0.0, 3.0 * b.rows * b.C0 * sizeof(T), slice_affine_inplace<T>(dcat, cat, b.Ctot, b.C0, b.rows, sB_, sC_, st));
     if (bi > 0) {
       // transition bi-1: avgpool <- conv 1x1 <- relu <- norm; writes the whole of the previous block's dcat
       DTrans& tr = p.trans[bi - 1];

@@ -37,7 +37,7 @@ struct FlashArgs {
   float scale, drop_p;
   int causal;
   uint64_t seed, offset;
-  int xcd;      // 1: XCD-aware tile order (MMSKIN_FLASH_XCD)
+  int xcd;      // 1: XCD-aware tile order (the launcher always sets it)
   int ablate;   // -DMMSKIN_ABLATE builds only (scripts/flash_ablate.py): bit0 K / V global loads after tile 0, bit1 softmax VALU work, bit2 MFMAs, bit3 K / V LDS stores
 };
 
@@ -54,7 +54,7 @@ __device__ __forceinline__ uint4 load8_bf16(const float* p) {
 }
 __device__ __forceinline__ uint4 load8_bf16(const bf16_t* p) { return *reinterpret_cast<const uint4*>(p); }
 
-// NB = LDS buffers for the K / V tiles (1: two barriers per key tile; 2: one); IO = tensor dtype; DROP: attention-probability dropout compiled in
+// NB = LDS buffers for the K / V tiles (1: two barriers per key tile; 2: one -- the launcher instantiates NB = 2 only); IO = tensor dtype; DROP: attention-probability dropout compiled in
 // (as a run-time test the generator's code kept 24 - 28 more VGPRs live in the launches that never drop: 3 -> 2 waves per SIMD at Dh = 64)
 template <int D, int NB, typename IO, bool DROP>
 __global__ __launch_bounds__(256) void flash_fwd_kernel(const FlashArgs p) {
@@ -484,8 +484,7 @@ __global__ __launch_bounds__(256) void flash_fwd2_kernel(const FlashArgs p) {
 
 template <typename IO>
 static int flash_launch(FlashArgs& a, int Dh, hipStream_t st) {
-  static const int v2 = [] { const char* e = getenv("MMSKIN_FLASH_V2"); return e ? atoi(e) : 1; }();
-  if (v2 && Dh == 64 && !a.bias && a.L <= 1024) {   // 128 query rows per workgroup, in-register softmax (flash_fwd2_kernel); a score bias [H][L][L]
+  if (Dh == 64 && !a.bias && a.L <= 1024) {   // 128 query rows per workgroup, in-register softmax (flash_fwd2_kernel); a score bias [H][L][L]
                                                      // is read per (query, key): with a query per lane its rows are L floats apart -- the kernel above reads it along keys
     if (a.drop_p > 0.f) hipLaunchKernelGGL((flash_fwd2_kernel<IO, true>), dim3(ceil_div(a.L, 128), a.B * a.H), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((flash_fwd2_kernel<IO, false>), dim3(ceil_div(a.L, 128), a.B * a.H), dim3(256), 0, st, a);
@@ -493,11 +492,10 @@ static int flash_launch(FlashArgs& a, int Dh, hipStream_t st) {
     return MMSKIN_OK;
   }
   const dim3 grid(ceil_div(a.L, 64), a.B * a.H);
-  static const int nb = [] { const char* e = getenv("MMSKIN_FLASH_BUFFERS"); return e ? atoi(e) : 2; }();
-#define FA_GO(DV, NBV) do { if (a.drop_p > 0.f) hipLaunchKernelGGL((flash_fwd_kernel<DV, NBV, IO, true>), grid, dim3(256), 0, st, a); \
-                             else hipLaunchKernelGGL((flash_fwd_kernel<DV, NBV, IO, false>), grid, dim3(256), 0, st, a); } while (0)
-  if (Dh == 32) { if (nb == 1) FA_GO(32, 1); else FA_GO(32, 2); }
-  else { if (nb == 1) FA_GO(64, 1); else FA_GO(64, 2); }
+#define FA_GO(DV) do { if (a.drop_p > 0.f) hipLaunchKernelGGL((flash_fwd_kernel<DV, 2, IO, true>), grid, dim3(256), 0, st, a); \
+                        else hipLaunchKernelGGL((flash_fwd_kernel<DV, 2, IO, false>), grid, dim3(256), 0, st, a); } while (0)
+  if (Dh == 32) FA_GO(32);
+  else FA_GO(64);
 #undef FA_GO
   HIP_CHECK_RET(hipGetLastError());
   return MMSKIN_OK;
@@ -525,7 +523,7 @@ int mmskin_flash_attention_forward(const void* q, const void* k, const void* v, 
   a.o_sb = strides12[9]; a.o_sh = strides12[10]; a.o_sl = strides12[11];
   a.scale = scale; a.drop_p = drop_p; a.causal = causal; a.seed = seed; a.offset = offset;
   a.ablate = 0;
-  { static const int xcd = [] { const char* e = getenv("MMSKIN_FLASH_XCD"); return e ? atoi(e) : 1; }(); a.xcd = xcd; }
+  a.xcd = 1;
 #ifdef MMSKIN_ABLATE
   { const char* e = getenv("MMSKIN_FLASH_ABLATE"); a.ablate = e ? atoi(e) : 0; }
 #endif

@@ -564,8 +564,7 @@ static int colsum4(const float* x, float* out, int64_t M, int N, float* part, bf
   return rows_sum(part, g.nbx, N, N, out, nullptr, st);
 }
 static int colsum(const float* x, float* out, int M, int N, hipStream_t st) {
-  static const bool c4 = [] { const char* v = getenv("MMSKIN_COLSUM4"); return !v || atoi(v) != 0; }();
-  if (c4 && N % 4 == 0 && M >= 2048) {
+  if (N % 4 == 0 && M >= 2048) {
     float* part = head_scratch(colsum4_part_bytes(N));
     if (!part) { mmskin_set_error("colsum: scratch allocation failed"); return MMSKIN_ERR_HIP; }
     return colsum4(x, out, M, N, part, nullptr, 0, st);
@@ -1663,15 +1662,9 @@ static int linear_backward_impl(const float* dy, const float* x, const float* w,
       HIP_CHECK_RET(hipGetLastError());
       // dx = g w as a FORWARD 1x1 conv over the transposed weight (w16 [K][N] is its [Cout][Cin] layout): the light epilogue writes
       // fp32 straight into dx -- no bf16 round trip and widening pass (10 us x 57 per DaViT step)
-      static const bool dx_f32 = [] { const char* v = getenv("MMSKIN_LINEAR_DX_F32"); return !v || atoi(v) != 0; }();
-      if (dx_f32) {
-        ConvShape sd = {M, 1, 1, N, K, 1, 1, 1, 0};
-        FwdFuse f; f.out_f32 = dx;
-        if ((rc = launch_conv_fwd<bf16_t>(sd, g16, w16, reinterpret_cast<bf16_t*>(dx), nullptr, nullptr, st, &f))) return rc;
-      } else {
-        if ((rc = launch_conv_dgrad<bf16_t>(s, g16, w16, t16, (const bf16_t*)nullptr, st))) return rc;   // dx in bf16, then widened
-        if ((rc = cvt_to_f32(t16, dx, (int64_t)M * K, st))) return rc;
-      }
+      ConvShape sd = {M, 1, 1, N, K, 1, 1, 1, 0};
+      FwdFuse f; f.out_f32 = dx;
+      if ((rc = launch_conv_fwd<bf16_t>(sd, g16, w16, reinterpret_cast<bf16_t*>(dx), nullptr, nullptr, st, &f))) return rc;
     }
     if (dw) {
       ARG_CHECK(x || x16_kept, "linear_backward: x required for dw");
@@ -1700,8 +1693,7 @@ static int linear_backward_impl(const float* dy, const float* x, const float* w,
     if (db && (rc = colsum(g, db, M, N, st))) return rc;
     return MMSKIN_OK;
   }
-  static const bool one_launch = [] { const char* v = getenv("MMSKIN_LINEAR_BWD_ONE"); return !v || atoi(v) != 0; }();
-  if (one_launch && M < 4096 && (dx || dw || db)) {   // (a longer contraction takes the split-K form of the separate launches)
+  if (M < 4096 && (dx || dw || db)) {   // (a longer contraction takes the split-K form of the separate launches)
     ARG_CHECK((!dx || w) && (!dw || x), "linear_backward: w / x required");
     const int nx_dx = ceil_div(K, LG_T), n_dx = dx ? nx_dx * ceil_div(M, LG_T) : 0;
     const int nx_dw = ceil_div(K, LG_T), n_dw = dw ? nx_dw * ceil_div(N, LG_T) : 0;
@@ -1746,8 +1738,7 @@ int mmskin_linear_backward_keep(const float* dy, const void* x16, const float* w
 int mmskin_layernorm_forward(const float* x, const float* g, const float* b, float* y, float* mean, float* rstd,
                              int M, int N, float eps, int relu, void* stream) {
   ARG_CHECK(x && g && b && y && mean && rstd && M > 0 && N > 0, "layernorm_forward: bad argument");
-  static const bool rows = [] { const char* v = getenv("MMSKIN_LN_ROWS"); return !v || atoi(v) != 0; }();
-  if (rows && ln_rows_ok(N, relu)) {
+  if (ln_rows_ok(N, relu)) {
 #define CALL(NJ, LPR) hipLaunchKernelGGL((layernorm_fwd_rows_kernel<NJ, LPR>), dim3(ceil_div(M, 4 * (64 / LPR))), dim3(256), 0, ST(stream), x, g, b, y, (bf16_t*)nullptr, mean, rstd, M, N, eps)
     LN_ROWS_DISPATCH(N, CALL);
 #undef CALL
@@ -1770,8 +1761,7 @@ int mmskin_layernorm_forward_mixed(const float* x, const float* g, const float* 
 int mmskin_layernorm_backward(const float* dy, const float* x, const float* g, const float* b, const float* mean,
                               const float* rstd, float* dx, float* dg, float* db, int M, int N, int relu, void* stream) {
   ARG_CHECK(dy && x && g && b && mean && rstd && M > 0 && N > 0, "layernorm_backward: bad argument");
-  static const bool rows = [] { const char* v = getenv("MMSKIN_LN_ROWS"); return !v || atoi(v) != 0; }();
-  if (rows && ln_rows_ok(N, relu)) {
+  if (ln_rows_ok(N, relu)) {
     // <= 1024 workgroups; every wave keeps >= 8 rows so its column sums amortise the slot it writes
     const int rpw = N <= 128 ? 2 : 1;
     int G = ceil_div(M, 4 * rpw * 8);
@@ -1935,12 +1925,9 @@ static int attn_rows_fwd_launch(const float* q, const float* k, const float* v, 
 static int attn_rows_bwd_launch(const float* dO, const float* q, const float* k, const float* v, const float* o, const float* lse,
                                 float* dq, float* dk, float* dv, const AttnRowsArgs& a, void* stream) {
   const size_t lds = (size_t)4 * 2 * a.L * (a.L + 1) * sizeof(float);
-  static bool attr_done = false;
-  if (!attr_done) {   // up to 4 waves x 2 tiles x 64 x 65 floats
-    HIP_CHECK_RET(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_rows_bwd_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * 64 * 65 * 4));
-    HIP_CHECK_RET(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_rows_bwd_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * 64 * 65 * 4));
-    attr_done = true;
-  }
+  // up to 4 waves x 2 tiles x 64 x 65 floats
+  HIP_CHECK_RET(opt_in_dynamic_lds(reinterpret_cast<const void*>(attention_rows_bwd_kernel<32>), 4 * 2 * 64 * 65 * 4));
+  HIP_CHECK_RET(opt_in_dynamic_lds(reinterpret_cast<const void*>(attention_rows_bwd_kernel<64>), 4 * 2 * 64 * 65 * 4));
   if (a.Dh == 32) hipLaunchKernelGGL(attention_rows_bwd_kernel<32>, dim3((a.nheads + 3) / 4), dim3(256), lds, ST(stream), q, k, v, o, dO, lse, dq, dk, dv, a);
   else hipLaunchKernelGGL(attention_rows_bwd_kernel<64>, dim3((a.nheads + 3) / 4), dim3(256), lds, ST(stream), q, k, v, o, dO, lse, dq, dk, dv, a);
   HIP_CHECK_RET(hipGetLastError());

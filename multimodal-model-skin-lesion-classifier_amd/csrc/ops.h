@@ -89,6 +89,9 @@ int stem_bn_relu_pool(const T* x, const float* scale, const float* shift, int N,
 // recomputed from the pooled gradient + argmax bytes inside the BatchNorm-backward reduce and apply passes
 // (saves one 411 MB write and two reads of it at batch 256).
 // the same partial sums from the pooled tensors alone (dpool, the pooled forward output ypool): x at a window's argmax is (y - shift) / scale
+// Whether callers take the sums from the pooled side (stem_pool_bwd_sums, default) or from the conv output and the routed gradient
+// (stem_pool_bn_bwd_reduce: 565 MB read instead of 206 MB at batch 256): MMSKIN_STEM_SUMS_POOLED=0 selects the latter, the reference form.
+bool stem_sums_pooled();
 template <typename T>
 int stem_pool_bwd_sums(const T* dpool, const T* ypool, const uint8_t* idx, const T* x, const float* scale, const float* shift, int N, int H, int W,
                        int C, float* partial, int* nrows_out, hipStream_t st);
@@ -137,11 +140,8 @@ int slice_pack(const T* in, int pitch, int C, int Cp, size_t rows, const float* 
 // dst[r*pitch + c] = src[r*srcC + c] for c < C  (dst may point at a channel offset inside a row)
 template <typename T>
 int slice_scatter(const T* src, int srcC, int C, T* dst, int pitch, size_t rows, hipStream_t st);
-// dcat[r*pitch + c] (+)= cA[c]*dz[r*Cp + c] + cB[c]*x[r*pitch + c] + cC[c]   for c < C
-template <typename T>
-int slice_bn_bwd_accumulate(T* dcat, const T* x, int pitch, int C, const T* dz, int Cp, const float* cA,
-                            const float* cB, const float* cC, size_t rows, hipStream_t st);
-// deferred form (DenseNet): the x / constant terms of all consumers of a channel are added once, when its gradient is consumed
+// BatchNorm-backward accumulation dcat[r*pitch + c] += cA[c]*dz[r*Cp + c] + cB[c]*x[r*pitch + c] + cC[c] in deferred form (DenseNet):
+// the x / constant terms of all consumers of a channel are added once, when its gradient is consumed
 template <typename T>
 int slice_accumulate_scaled(T* dcat, int pitch, int C, const T* dz, int Cp, const float* cA, size_t rows, hipStream_t st);
 template <typename T>

@@ -162,7 +162,7 @@ static inline int reduce_groups(int nrows) {
 // MMSKIN_BN_SINGLE_ROWS (default 512): layers 3 - 4 of ResNet-50 at batch 256 leave 98 - 392 partial rows (64 - 256 with the
 // pipelined conv kernel's tiles) -- one 1024-thread finalize launch (16 row lanes x 2 chains) instead of pre-reduction + finalize
 static inline int bn_single_stage_rows() {
-  static const int v = [] { const char* e = getenv("MMSKIN_BN_SINGLE_ROWS"); return e ? atoi(e) : 512; }();
+  static const int v = env_knob("MMSKIN_BN_SINGLE_ROWS", 512);
   return v;
 }
 
@@ -288,10 +288,8 @@ int bn_apply(const T* x, const T* res, const float* scale, const float* shift, c
 #define LAUNCH(R, H) hipLaunchKernelGGL((bn_apply_kernel<T, R, H>), dim3(grid), dim3(EW_BLOCK), 0, st, x, res, scale, shift, rscale, rshift, y, mask_bits, nch, C / EPC, relu_cap)
   if (relu && relu_cap < 0.f) { if (mode == 2) LAUNCH(2, 2); else if (mode == 1) LAUNCH(2, 1); else LAUNCH(2, 0); }
   else if (relu) {
-    static const bool nt = [] { const char* v = getenv("MMSKIN_EW_NT"); return !v || atoi(v) != 0; }();
 #define LAUNCH_NT(R, H) hipLaunchKernelGGL((bn_apply_kernel<T, R, H, true>), dim3(grid), dim3(EW_BLOCK), 0, st, x, res, scale, shift, rscale, rshift, y, mask_bits, nch, C / EPC, relu_cap)
-    if (nt) { if (mode == 2) LAUNCH_NT(1, 2); else if (mode == 1) LAUNCH_NT(1, 1); else LAUNCH_NT(1, 0); }
-    else { if (mode == 2) LAUNCH(1, 2); else if (mode == 1) LAUNCH(1, 1); else LAUNCH(1, 0); }
+    if (mode == 2) LAUNCH_NT(1, 2); else if (mode == 1) LAUNCH_NT(1, 1); else LAUNCH_NT(1, 0);
 #undef LAUNCH_NT
   }
   else { if (mode == 2) LAUNCH(0, 2); else if (mode == 1) LAUNCH(0, 1); else LAUNCH(0, 0); }
@@ -488,13 +486,8 @@ int bn_bwd_finalize(const float* partial, int nrows, int C, double count, const 
     hipLaunchKernelGGL(bn_bwd_finalize_kernel<double>, dim3(ceil_div(C, 64)), dim3(256), 0, st, scratch, G, C, count,
                        gamma, save_mean, save_invstd, dgamma, dbeta, cA, cB, cC, n_grad, acc_bc, sum_dz_x);
   } else if (nrows > 64) {
-    static const int small_blocks = [] { const char* e = getenv("MMSKIN_BNB_SMALL_BLOCKS"); return e ? atoi(e) : 1; }();
-    if (small_blocks)
-      hipLaunchKernelGGL((bn_bwd_finalize_kernel<float, 16, 16>), dim3(ceil_div(C, 16)), dim3(256), 0, st, partial, nrows, C, count,
-                         gamma, save_mean, save_invstd, dgamma, dbeta, cA, cB, cC, n_grad, acc_bc, sum_dz_x);
-    else
-      hipLaunchKernelGGL((bn_bwd_finalize_kernel<float, 16>), dim3(ceil_div(C, 64)), dim3(1024), 0, st, partial, nrows, C, count,
-                         gamma, save_mean, save_invstd, dgamma, dbeta, cA, cB, cC, n_grad, acc_bc, sum_dz_x);
+    hipLaunchKernelGGL((bn_bwd_finalize_kernel<float, 16, 16>), dim3(ceil_div(C, 16)), dim3(256), 0, st, partial, nrows, C, count,
+                       gamma, save_mean, save_invstd, dgamma, dbeta, cA, cB, cC, n_grad, acc_bc, sum_dz_x);
   } else {
     hipLaunchKernelGGL(bn_bwd_finalize_kernel<float>, dim3(ceil_div(C, 64)), dim3(256), 0, st, partial, nrows, C, count,
                        gamma, save_mean, save_invstd, dgamma, dbeta, cA, cB, cC, n_grad, acc_bc, sum_dz_x);
@@ -541,11 +534,9 @@ int bn_bwd_apply(const T* dy, const T* x, const T* ymask, const float* scale, co
   else if (mask_mode == MASK_SILU_X) { if (dz_out) LAUNCH(MASK_SILU_X, true); else LAUNCH(MASK_SILU_X, false); }
   else {
     // nontemporal loads of dz / x (each is read for the last time here; dx stays cacheable: the dgrad and the weight-gradient
-    // GEMM read it next): same-box A/B 20.74 -> 20.43 ms per step (MMSKIN_EW_NT=0/1, profiles/r02_experiments.txt)
-    static const bool nt = [] { const char* v = getenv("MMSKIN_EW_NT"); return !v || atoi(v) != 0; }();
+    // GEMM read it next): same-box A/B 20.74 -> 20.43 ms per step (cacheable / nontemporal, profiles/r02_experiments.txt)
     if (dz_out) LAUNCH(MASK_NONE, true);
-    else if (nt) hipLaunchKernelGGL((bn_bwd_apply_kernel<T, MASK_NONE, false, true>), dim3(grid), dim3(EW_BLOCK), 0, st, dy, x, ymask, scale, shift, cA, cB, cC, dx, dz_out, nch, C / EPC);
-    else LAUNCH(MASK_NONE, false);
+    else hipLaunchKernelGGL((bn_bwd_apply_kernel<T, MASK_NONE, false, true>), dim3(grid), dim3(EW_BLOCK), 0, st, dy, x, ymask, scale, shift, cA, cB, cC, dx, dz_out, nch, C / EPC);
   }
 #undef LAUNCH
   HIP_CHECK_RET(hipGetLastError());
@@ -611,8 +602,7 @@ int stem_pack(const float* img, int N, int H, int W, int Hp, int Wp, T* img4, hi
   ARG_CHECK(Hp >= H + 6 && Wp >= W + 6 && Wp % 2 == 0, "stem_pack: bad padded size");
   ARG_CHECK(Hp <= 65535 && N <= 65535, "stem_pack: grid %d x %d", Hp, N);
   if constexpr (sizeof(T) == 2) {
-    static const bool pack4 = [] { const char* v = getenv("MMSKIN_STEM_PACK4"); return !v || atoi(v) != 0; }();
-    if (pack4 && W % 4 == 0 && (reinterpret_cast<uintptr_t>(img) & 15) == 0) {
+    if (W % 4 == 0 && (reinterpret_cast<uintptr_t>(img) & 15) == 0) {
       hipLaunchKernelGGL(stem_pack4_kernel, dim3(ceil_div(W / 4 + 2, 64), ceil_div(Hp, 4), N), dim3(256), 0, st, img, H, W, Hp, Wp, img4);
       HIP_CHECK_RET(hipGetLastError());
       return MMSKIN_OK;
@@ -836,9 +826,9 @@ int stem_pool_bn_bwd_reduce(const T* dpool, const uint8_t* idx, const T* x, cons
   ColGeom g = col_geom(cells, C, DT<T>::EPC);
   // col_geom aims at ~1000 blocks (25 cells per lane, 12 loads each, two integer divisions per cell): 294 us for the 540 MB the pass
   // reads.  Four cells per lane instead (6 272 blocks at batch 256): the partial rows go through the two-stage reduction like the
-  // dgrad epilogues' (MMSKIN_STEM_REDUCE_CELLS: cells per lane)
-  static const int cells_per_lane = [] { const char* v = getenv("MMSKIN_STEM_REDUCE_CELLS"); return v ? atoi(v) : 4; }();
-  if (cells_per_lane > 0 && (size_t)g.RL * cells_per_lane < (size_t)g.RB) {
+  // dgrad epilogues'
+  constexpr int cells_per_lane = 4;
+  if ((size_t)g.RL * cells_per_lane < (size_t)g.RB) {
     g.RB = g.RL * cells_per_lane;
     g.gx = (int)((cells + g.RB - 1) / g.RB);
   }
@@ -905,6 +895,10 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_sums_kernel(const T* __rest
     }
   }
   block_col_reduce<EPC, 2>(acc, cx, ry, g.CW, g.RL, col, g.CPR, C, partial, red);
+}
+bool stem_sums_pooled() {
+  static const bool on = env_knob("MMSKIN_STEM_SUMS_POOLED", 1) != 0;
+  return on;
 }
 template <typename T>
 int stem_pool_bwd_sums(const T* dpool, const T* ypool, const uint8_t* idx, const T* x, const float* scale, const float* shift, int N, int H, int W,
@@ -1227,37 +1221,7 @@ int slice_scatter(const T* src, int srcC, int C, T* dst, int pitch, size_t rows,
   return MMSKIN_OK;
 }
 
-template <typename T>
-__global__ __launch_bounds__(EW_BLOCK) void slice_bn_bwd_accumulate_kernel(
-    T* __restrict__ dcat, const T* __restrict__ x, int pitch, int CPR, const T* __restrict__ dz, int Cp,
-    const float* __restrict__ cA, const float* __restrict__ cB, const float* __restrict__ cC, size_t nchunks) {
-  constexpr int EPC = DT<T>::EPC;
-  for (size_t i = blockIdx.x * (size_t)EW_BLOCK + threadIdx.x; i < nchunks; i += (size_t)gridDim.x * EW_BLOCK) {
-    const size_t r = i / CPR;
-    const int cc = (int)(i - r * CPR), c0 = cc * EPC;
-    const size_t off = r * pitch + c0;
-    Chunk<T> g, xv, dv;
-    g.load(dcat + off);
-    xv.load(x + off);
-    dv.load(dz + r * Cp + c0);
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) g.v[e] += cA[c0 + e] * dv.v[e] + cB[c0 + e] * xv.v[e] + cC[c0 + e];
-    g.store(dcat + off);
-  }
-}
-template <typename T>
-int slice_bn_bwd_accumulate(T* dcat, const T* x, int pitch, int C, const T* dz, int Cp, const float* cA,
-                            const float* cB, const float* cC, size_t rows, hipStream_t st) {
-  constexpr int EPC = DT<T>::EPC;
-  ARG_CHECK(C % EPC == 0 && Cp % EPC == 0 && pitch % EPC == 0 && C <= Cp && C <= pitch, "slice_bn_bwd_accumulate: C=%d Cp=%d pitch=%d", C, Cp, pitch);
-  const size_t nch = rows * (C / EPC);
-  hipLaunchKernelGGL(slice_bn_bwd_accumulate_kernel<T>, dim3(ew_grid(nch)), dim3(EW_BLOCK), 0, st, dcat, x, pitch,
-                     C / EPC, dz, Cp, cA, cB, cC, nch);
-  HIP_CHECK_RET(hipGetLastError());
-  return MMSKIN_OK;
-}
-
-// Deferred form of the accumulation above (DenseNet: every later layer of a block adds cA*g + cB*x + cC to the prefix it consumed;
+// Deferred BatchNorm-backward accumulation (DenseNet: every later layer of a block adds cA*g + cB*x + cC to the prefix it consumed;
 // x is the SAME for all of them, so sum(cB) * x + sum(cC) is added once, when a channel's gradient is consumed):
 //   slice_accumulate_scaled : dcat[r*pitch + c] += cA[c] * dz[r*Cp + c]                        (no read of x: 3 passes instead of 4)
 //   slice_pack_deferred     : out[r][c < C] = d[r*pitch + c] + sB[c] * x[r*pitch + c] + sC[c], zero for C <= c < Cp
@@ -1511,8 +1475,6 @@ int avgpool2_bwd(const T* dpool, int pitch, int N, int H, int W, int C, T* dx, h
 #define INST_SLICE(T)                                                                                              \
   template int slice_pack<T>(const T*, int, int, int, size_t, const float*, const float*, T*, hipStream_t);       \
   template int slice_scatter<T>(const T*, int, int, T*, int, size_t, hipStream_t);                                \
-  template int slice_bn_bwd_accumulate<T>(T*, const T*, int, int, const T*, int, const float*, const float*,      \
-                                          const float*, size_t, hipStream_t);                                     \
   template int slice_accumulate_scaled<T>(T*, int, int, const T*, int, const float*, size_t, hipStream_t);       \
   template int slice_pack_deferred<T>(const T*, const T*, int, int, int, size_t, const float*, const float*, T*, hipStream_t); \
   template int slice_affine_inplace<T>(T*, const T*, int, int, size_t, const float*, const float*, hipStream_t); \
@@ -2149,7 +2111,7 @@ int dwconv3_wgrad(const T* dout, const T* in, int N, int H, int W, int C, int st
   const int strips = dww_strips(opix);
   const size_t per = (opix + strips - 1) / strips;
   const int CPR = C / EPC, KK = ksize * ksize;
-  static const bool rows_on = [] { const char* v = getenv("MMSKIN_DWW_ROWS"); return !v || atoi(v) != 0; }();
+  static const bool rows_on = env_knob("MMSKIN_DWW_ROWS", 1) != 0;
   ARG_CHECK(!db || (stride == 1 && ksize == 3), "dwconv_wgrad: the bias gradient comes with the 3x3 / stride 1 kernel only");
   if ((rows_on || db) && stride == 1 && ksize == 3) {
     const DwwRowsPlan g = dww_rows_plan(N, H, CPR);

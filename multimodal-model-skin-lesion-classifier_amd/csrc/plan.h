@@ -48,21 +48,12 @@ struct SideStream {
   bool done_valid[3] = {false, false, false};
   hipEvent_t f_ready = nullptr, f_done = nullptr;      // forward: block input ready / downsample branch finished
   hipEvent_t f_staged = nullptr;                       // forward: weights of the residual stages staged (beside the stem)
-  // backward: the downsample branch of a block (BatchNorm-backward apply + dgrad) on a stream of its own, beside conv3 .. conv2
-  hipStream_t s2 = nullptr;
-  hipEvent_t d_ready = nullptr, d_done = nullptr;      // main: block-output gradient + its partial sums ready / s2: branch gradient written
   // algebraic BatchNorm backward (backbone.hip): the weight-gradient stream reads the block-output gradient buffer itself
   hipEvent_t g_ready = nullptr, g_done[2] = {nullptr, nullptr};
   bool g_done_valid[2] = {false, false};
   int init() {
     if (s) return MMSKIN_OK;
-    int least = 0, greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-    const char* v = getenv("MMSKIN_SIDE_PRIORITY");   // "normal" (default) | "high" | "low": no measurable difference
-    int prio = 0;
-    if (v && !strcmp(v, "high")) prio = greatest;
-    if (v && !strcmp(v, "low")) prio = least;
-    HIP_CHECK_RET(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, prio));
+    HIP_CHECK_RET(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));   // normal priority: high / low measured no different
     for (int i = 0; i < 3; ++i) {
       HIP_CHECK_RET(hipEventCreateWithFlags(&ready[i], hipEventDisableTiming));
       HIP_CHECK_RET(hipEventCreateWithFlags(&done[i], hipEventDisableTiming));
@@ -70,9 +61,6 @@ struct SideStream {
     HIP_CHECK_RET(hipEventCreateWithFlags(&f_ready, hipEventDisableTiming));
     HIP_CHECK_RET(hipEventCreateWithFlags(&f_done, hipEventDisableTiming));
     HIP_CHECK_RET(hipEventCreateWithFlags(&f_staged, hipEventDisableTiming));
-    HIP_CHECK_RET(hipStreamCreateWithPriority(&s2, hipStreamNonBlocking, prio));
-    HIP_CHECK_RET(hipEventCreateWithFlags(&d_ready, hipEventDisableTiming));
-    HIP_CHECK_RET(hipEventCreateWithFlags(&d_done, hipEventDisableTiming));
     HIP_CHECK_RET(hipEventCreateWithFlags(&g_ready, hipEventDisableTiming));
     HIP_CHECK_RET(hipEventCreateWithFlags(&g_done[0], hipEventDisableTiming));
     HIP_CHECK_RET(hipEventCreateWithFlags(&g_done[1], hipEventDisableTiming));
@@ -82,11 +70,7 @@ struct SideStream {
     if (!s) return;
     for (int i = 0; i < 3; ++i) { (void)hipEventDestroy(ready[i]); (void)hipEventDestroy(done[i]); }
     (void)hipEventDestroy(f_ready); (void)hipEventDestroy(f_done); (void)hipEventDestroy(f_staged);
-    if (d_ready) (void)hipEventDestroy(d_ready);
-    if (d_done) (void)hipEventDestroy(d_done);
     if (g_ready) { (void)hipEventDestroy(g_ready); (void)hipEventDestroy(g_done[0]); (void)hipEventDestroy(g_done[1]); }
-    if (s2) (void)hipStreamDestroy(s2);
-    s2 = nullptr;
     (void)hipStreamDestroy(s);
     s = nullptr;
   }

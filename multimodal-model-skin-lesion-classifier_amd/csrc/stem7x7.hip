@@ -149,7 +149,7 @@ extern "C" int64_t mmskin_stem7x7_launches(void) { return g_stem7_launches; }
 
 // MMSKIN_STEM7X7=0: the gather-GEMM form for every shape (A/B, tests)
 bool stem7x7_takes(int OH, int OW, int Hp, int Wp) {
-  static const int on = [] { const char* v = getenv("MMSKIN_STEM7X7"); return v ? atoi(v) : 1; }();
+  static const int on = env_knob("MMSKIN_STEM7X7", 1);
   return on && OW == 16 * ST_MF && OH % ST_ROWS == 0 && Hp >= 2 * OH + 5 && Wp >= 2 * OW + 8 && Wp % 2 == 0 && ST_IN_ROWS * Wp * 8 <= ST_IN_LOADS * 256 * 16 &&
          ST_IN_ROWS * Wp * 8 + ST_W_BYTES + ST_ROWS * ST_STAGE <= 80 * 1024;
 }
@@ -158,11 +158,7 @@ int launch_stem7x7_fwd(int N, int OH, int OW, int Hp, int Wp, const bf16_t* img4
                        hipStream_t st) {
   ARG_CHECK(stem7x7_takes(OH, OW, Hp, Wp), "stem7x7: shape OH=%d OW=%d Hp=%d Wp=%d not taken", OH, OW, Hp, Wp);
   const int lds = ST_IN_ROWS * Wp * 8 + ST_W_BYTES + ST_ROWS * ST_STAGE;
-  static bool attr_done = false;
-  if (!attr_done) {
-    HIP_CHECK_RET(hipFuncSetAttribute(reinterpret_cast<const void*>(stem7x7_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-    attr_done = true;
-  }
+  HIP_CHECK_RET(opt_in_dynamic_lds(reinterpret_cast<const void*>(stem7x7_kernel), 80 * 1024));
   ++g_stem7_launches;
   hipLaunchKernelGGL(stem7x7_kernel, dim3(N * (OH / ST_ROWS)), dim3(256), lds, st, img4, wv, out, stat_sum, stat_sq, OH, OW, Hp, Wp);
   HIP_CHECK_RET(hipGetLastError());

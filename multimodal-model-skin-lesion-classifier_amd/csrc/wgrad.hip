@@ -98,7 +98,8 @@ __device__ __forceinline__ void wg_compute(const unsigned char* Xb, const unsign
 // MSF scales the rows staged per barrier: small output tiles stage more pixel rows per step so every
 // barrier-to-barrier interval carries >= 16 MFMAs per wave and 16-32 KB of loads (a 64x64 tile with 32
 // rows per step was latency-bound at 48 TF/s).
-// PF = stages kept in flight in registers (1 or 2).
+// PF = stages kept in flight in registers: 1 (two-deep prefetch measured no faster in isolation and slower inside the training step,
+// 224 VGPRs; the parameter stays so the kernels keep their names).
 // S1: 1x1 / stride 1 / no padding -- the gathered-input row of pixel m is row m: no pixel stepping and no bounds tests in the stage loop
 // (~5 VALU per chunk and stage instead of ~25; a compile-time variant: the same test as a run-time flag cost more than it saved)
 template <typename T, int BO, int BKK, int MSF, int PF, bool S1 = false>
@@ -146,14 +147,12 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs p) {
   const unsigned char* dy_b = reinterpret_cast<const unsigned char*>(p.dy);
   const unsigned char* in_b = reinterpret_cast<const unsigned char*>(p.in);
 
-  // Named staging registers (arrays of uint4 ended up in scratch memory), TWO sets: the kernel was
-  // load-latency bound (ablation: removing the global loads saved 38 %, removing every MFMA 9 % -- the Y
-  // operand is forward activations coming cold from HBM), so stages s+1 AND s+2 are kept in flight while
-  // stage s is multiplied; the loop is unrolled by two so each set has a fixed name.
+  // Named staging registers (arrays of uint4 ended up in scratch memory): the kernel is load-latency bound (ablation: removing the
+  // global loads saved 38 %, removing every MFMA 9 % -- the Y operand is forward activations coming cold from HBM), so stage s+1
+  // is in flight while stage s is multiplied.
   static_assert(NX <= 4 && NY <= 4 && NX != 3 && NY != 3, "staging registers are written out for 1, 2 or 4 chunks per thread");
   const u32x4_t z4 = {0, 0, 0, 0};
   u32x4_t rxA0 = z4, rxA1 = z4, rxA2 = z4, rxA3 = z4, ryA0 = z4, ryA1 = z4, ryA2 = z4, ryA3 = z4;
-  u32x4_t rxB0 = z4, rxB1 = z4, rxB2 = z4, rxB3 = z4, ryB0 = z4, ryB1 = z4, ryB2 = z4, ryB3 = z4;
 #ifdef MMSKIN_ABLATE   // `make ablate` (scripts/ only)
   const int abl = p.ablate;
 #else
@@ -219,35 +218,15 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs p) {
     for (int j = 0; j < FO; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   const int nstage = (m_end - m_begin + MS - 1) / MS;
-  static_assert(PF == 1 || PF == 2, "prefetch depth");
-  if constexpr (PF == 2) {
-    if (nstage > 0) { LOAD_STAGE(A); STORE_STAGE(0, A); }
-    if (nstage > 1) LOAD_STAGE(A);          // stage 1 -> set A
-    if (nstage > 2) LOAD_STAGE(B);          // stage 2 -> set B
+  static_assert(PF == 1, "prefetch depth");
+  if (nstage > 0) { LOAD_STAGE(A); STORE_STAGE(0, A); }
+  __syncthreads();
+  for (int s = 0; s < nstage; ++s) {
+    const int cur = s & 1;
+    if (s + 1 < nstage) LOAD_STAGE(A);    // in flight while this stage is multiplied
+    if (!(abl & 4)) wg_compute<T, BO, BKK, MS>(Xs + cur * X_BYTES, Ys + cur * Y_BYTES, acc, wo, wk, l15, g);
+    if (s + 1 < nstage) STORE_STAGE(cur ^ 1, A);
     __syncthreads();
-    for (int s = 0; s < nstage; s += 2) {
-      // LDS[0] holds stage s, set A holds stage s+1, set B holds stage s+2 (in flight)
-      if (!(abl & 4)) wg_compute<T, BO, BKK, MS>(Xs, Ys, acc, wo, wk, l15, g);
-      if (s + 1 < nstage) STORE_STAGE(1, A);
-      __syncthreads();
-      if (s + 3 < nstage) LOAD_STAGE(A);    // stage s+3
-      if (s + 1 >= nstage) break;
-      // LDS[1] holds stage s+1, set B holds stage s+2, set A holds stage s+3 (in flight)
-      if (!(abl & 4)) wg_compute<T, BO, BKK, MS>(Xs + X_BYTES, Ys + Y_BYTES, acc, wo, wk, l15, g);
-      if (s + 2 < nstage) STORE_STAGE(0, B);
-      __syncthreads();
-      if (s + 4 < nstage) LOAD_STAGE(B);    // stage s+4
-    }
-  } else {
-    if (nstage > 0) { LOAD_STAGE(A); STORE_STAGE(0, A); }
-    __syncthreads();
-    for (int s = 0; s < nstage; ++s) {
-      const int cur = s & 1;
-      if (s + 1 < nstage) LOAD_STAGE(A);    // in flight while this stage is multiplied
-      if (!(abl & 4)) wg_compute<T, BO, BKK, MS>(Xs + cur * X_BYTES, Ys + cur * Y_BYTES, acc, wo, wk, l15, g);
-      if (s + 1 < nstage) STORE_STAGE(cur ^ 1, A);
-      __syncthreads();
-    }
   }
 
   // D[i = k index][j = cout]: lane holds cout = l15, k = g*4 + reg  -> float4 along k in the slab
@@ -360,25 +339,18 @@ __global__ __launch_bounds__(256) void wgrad_reduce4_lanes_kernel(const float4* 
 }
 
 // ------------------------------------------------------------------------------------------ host
-static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 static void wgrad_plan(int M, int Cout, int Ktot, int MS, int& BO, int& BKK, int& nsplit, int& mps, int ntaps = 1) {
   BO = (Cout % 128 == 0) ? 128 : 64;
   BKK = (Ktot % 128 == 0) ? 128 : 64;
-  // 256-wide cout tiles halve the re-reads of the gathered-input operand (env knob for A/B timing)
-  static const int bo256 = [] { const char* v = getenv("MMSKIN_WGRAD_BO256"); return v ? atoi(v) : 0; }();
-  if (bo256 && Cout % 256 == 0 && BKK == 128) BO = 256;
-  MS *= (BO == 256) ? 1 : ((BO + BKK == 128) ? 4 : 2);   // rows per stage (MSF of the kernel)
+  MS *= (BO + BKK == 128) ? 4 : 2;   // rows per stage (MSF of the kernel)
   int tiles = (Cout / BO) * (Ktot / BKK);
   // workgroups to aim for (never exceeded: one extra workgroup costs a whole extra round of 2 x 256 resident slots).
-  // Per-layer sweep on MI355X, isolated and inside the training step (scripts/wgrad_sweep.sh): 1x1 layers and 3x3
+  // Per-layer sweep on MI355X, isolated and inside the training step: 1x1 layers and 3x3
   // layers with >= 64 output tiles are fastest with ONE round (<= 512), the other 3x3 layers with two (<= 1024).
   // An LDS-DMA staging variant of this kernel was measured too and was 10 % slower than the register-staged loop kept here.
-  static const int target_all = env_int("MMSKIN_WGRAD_BLOCKS", 1024);
-  static const int t1 = env_int("MMSKIN_WGRAD_B1", target_all < 512 ? target_all : 512), t3 = env_int("MMSKIN_WGRAD_B3", target_all),
-                   t3big = env_int("MMSKIN_WGRAD_B3BIG", t1);
-  static const int use_floor = env_int("MMSKIN_WGRAD_FLOOR", 1);
-  const int target = ntaps == 1 ? t1 : (tiles >= 64 ? t3big : t3);
-  int want = use_floor ? (target / tiles > 0 ? target / tiles : 1) : ceil_div(target, tiles);
+  constexpr int one_round = 512, two_rounds = 1024;
+  const int target = (ntaps == 1 || tiles >= 64) ? one_round : two_rounds;
+  int want = target / tiles > 0 ? target / tiles : 1;
   int max_split = M / (MS * 4) > 0 ? M / (MS * 4) : 1;
   nsplit = want < max_split ? want : max_split;
   if (nsplit < 1) nsplit = 1;
@@ -396,8 +368,7 @@ static int reduce_slabs(float* slab, int nsplit, int Cout, int Ktot, float* dw, 
   const int total4 = (int)(total / 4);
   const float* src = slab;
   int nsrc = nsplit;
-  static const int one_launch = env_int("MMSKIN_WGRAD_REDUCE_ONE", 1);
-  if (one_launch && nsplit > WG_DIRECT_SPLITS && C_for_layout % 4 == 0) {
+  if (nsplit > WG_DIRECT_SPLITS && C_for_layout % 4 == 0) {
     const int coutv = cout_valid > 0 ? cout_valid : Cout, cv = cin_valid > 0 ? cin_valid : C_for_layout;
     hipLaunchKernelGGL(wgrad_reduce4_lanes_kernel, dim3(ceil_div(total4, 64)), dim3(256), 0, st, reinterpret_cast<const float4*>(slab),
                        dw, nsplit, Cout, C_for_layout, ntaps_for_layout, coutv, cv);
@@ -462,11 +433,7 @@ static int launch_wg(WgradArgs& a, hipStream_t st) {
   a.nblk_o = a.Cout / BO;
   a.nblk_k = a.Ktot / BKK;
   int grid = a.nblk_o * a.nblk_k * a.nsplit;
-  // two-deep prefetch measured no faster in isolation and slower inside the training step (224 VGPRs)
-  static const int pf = [] { const char* v = getenv("MMSKIN_WGRAD_PF"); return v ? atoi(v) : 1; }();
-  static const int s1 = [] { const char* v = getenv("MMSKIN_WGRAD_S1"); return v ? atoi(v) : 1; }();
-  if (pf == 2) hipLaunchKernelGGL((wgrad_kernel<T, BO, BKK, MSF, 2>), dim3(grid), dim3(256), 0, st, a);
-  else if (s1 && a.simple1x1 && sizeof(T) == 2 && BO >= 64 && BKK >= 64 && BO + BKK >= 192) hipLaunchKernelGGL((wgrad_kernel<T, BO, BKK, MSF, 1, true>), dim3(grid), dim3(256), 0, st, a);
+  if (a.simple1x1 && sizeof(T) == 2 && BO >= 64 && BKK >= 64 && BO + BKK >= 192) hipLaunchKernelGGL((wgrad_kernel<T, BO, BKK, MSF, 1, true>), dim3(grid), dim3(256), 0, st, a);
   else hipLaunchKernelGGL((wgrad_kernel<T, BO, BKK, MSF, 1>), dim3(grid), dim3(256), 0, st, a);
   HIP_CHECK_RET(hipGetLastError());
   return MMSKIN_OK;
@@ -494,8 +461,7 @@ static int run_wgrad(WgradArgs& a, float* dw, int C_for_layout, int ntaps_for_la
   { const char* v = getenv("MMSKIN_WGRAD_ABLATE"); a.ablate = v ? atoi(v) : 0; }
 #endif
   int rc;
-  if (BO == 256) rc = launch_wg<T, 256, 128, 1>(a, st);
-  else if (BO == 128 && BKK == 128) rc = launch_wg<T, 128, 128, 2>(a, st);
+  if (BO == 128 && BKK == 128) rc = launch_wg<T, 128, 128, 2>(a, st);
   else if (BO == 128) rc = launch_wg<T, 128, 64, 2>(a, st);
   else if (BKK == 128) rc = launch_wg<T, 64, 128, 2>(a, st);
   else rc = launch_wg<T, 64, 64, 4>(a, st);
@@ -669,8 +635,7 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3_kernel(const Wgrad3Args p) {
 }
 
 static bool wgrad3_plan(const ConvShape& s, Wgrad3Args& a) {
-  static const int enabled = env_int("MMSKIN_WGRAD_3X3", 1);
-  if (!enabled || s.kh != 3 || s.kw != 3 || s.stride != 1 || s.pad != 1) return false;
+  if (s.kh != 3 || s.kw != 3 || s.stride != 1 || s.pad != 1) return false;
   if (s.Cin % 64 || s.Cout % 64 || s.W > 64 || s.W < 1) return false;
   int R = 64 / s.W;
   if (R > s.H) R = s.H;
@@ -681,13 +646,13 @@ static bool wgrad3_plan(const ConvShape& s, Wgrad3Args& a) {
   a.nblk_o = s.Cout / 64; a.nblk_c = s.Cin / 64;
   a.yrows = (R + 2) * (s.W + 2);
   const int tiles = a.nblk_o * a.nblk_c;
-  static const int target = env_int("MMSKIN_WGRAD3_BLOCKS", 512);      // one round of 2 workgroups per CU
+  static const int target = env_knob("MMSKIN_WGRAD3_BLOCKS", 512);      // one round of 2 workgroups per CU
   int ns = target / tiles > 0 ? target / tiles : 1;
   // every split writes a whole 64 x 9 x 64 fp32 tile (147 KB) and the reduction reads it back: a split should multiply at least
   // ~16 stages before it does.  DenseNet's 32-channel conv2 at 14^2 / 7^2 had 4 / 1 stages per split -- 6.2 GB of slab writes and
   // most of 7.9 GB of reduction reads per step (profiles/r03_step_traffic_densenet169-metablock.txt); ResNet-50's 3x3 layers have 28 - 32.
-  static const int min_stages = env_int("MMSKIN_WGRAD3_MIN_STAGES", 16);
-  if (min_stages > 1 && ns > a.total_stages / min_stages) ns = a.total_stages / min_stages > 0 ? a.total_stages / min_stages : 1;
+  constexpr int min_stages = 16;
+  if (ns > a.total_stages / min_stages) ns = a.total_stages / min_stages > 0 ? a.total_stages / min_stages : 1;
   if (ns > a.total_stages) ns = a.total_stages;
   a.stages_per_split = ceil_div(a.total_stages, ns);
   a.nsplit = ceil_div(a.total_stages, a.stages_per_split);
@@ -703,12 +668,7 @@ static size_t wgrad3_slab_bytes(const ConvShape& s) {
 static int launch_wgrad3(const ConvShape& s, Wgrad3Args& a, const bf16_t* dout, const bf16_t* in, float* slab, float* dw,
                          hipStream_t st, int cout_valid, int cin_valid) {
   a.dy = dout; a.in = in; a.slab = slab;
-  static bool attr_done = false;
-  if (!attr_done) {
-    HIP_CHECK_RET(hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad3x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      W3_LDS_BYTES));
-    attr_done = true;
-  }
+  HIP_CHECK_RET(opt_in_dynamic_lds(reinterpret_cast<const void*>(wgrad3x3_kernel), W3_LDS_BYTES));
   hipLaunchKernelGGL(wgrad3x3_kernel, dim3(a.nblk_o * a.nblk_c * a.nsplit), dim3(256), W3_LDS_BYTES, st, a);
   HIP_CHECK_RET(hipGetLastError());
   return reduce_slabs(slab, a.nsplit, s.Cout, 9 * s.Cin, dw, s.Cin, 9, cout_valid, cin_valid, st);

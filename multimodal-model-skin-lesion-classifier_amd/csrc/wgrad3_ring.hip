@@ -279,13 +279,10 @@ __global__ __launch_bounds__(512) void wgrad3_ring_kernel(const Wgrad3RingArgs p
 }
 
 // ------------------------------------------------------------------------------------------ host
-static int w3r_env(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
-
 struct Wgrad3RingPlan { Wgrad3RingArgs a; int wob, g, nyw; };
 
 static bool wgrad3_ring_plan_(const ConvShape& s, Wgrad3RingPlan& pl) {
-  static const int enabled = w3r_env("MMSKIN_WGRAD3_RING", 1);
-  if (!enabled || s.kh != 3 || s.kw != 3 || s.stride != 1 || s.pad != 1) return false;
+  if (s.kh != 3 || s.kw != 3 || s.stride != 1 || s.pad != 1) return false;
   if (s.Cin % 64 || s.Cout % 64 || s.W > 62 || s.W < 1) return false;
   if ((uint64_t)s.N * s.H * s.W * s.Cout * 2 >= 0xE0000000ull || (uint64_t)s.N * s.H * s.W * s.Cin * 2 >= 0xE0000000ull) return false;
   Wgrad3RingArgs& a = pl.a;
@@ -297,19 +294,16 @@ static bool wgrad3_ring_plan_(const ConvShape& s, Wgrad3RingPlan& pl) {
   a.R = R; a.spi = ceil_div(s.H, R);
   a.W2p = W2p; a.yrows = (R + 2) * W2p;
   a.total_stages = s.N * a.spi;
-  // MMSKIN_WGRAD3_WOB=1: two pixel groups on a 64-cout tile for every layer (half the slab bytes per workgroup, the window staged per group)
-  static const int wob_env = w3r_env("MMSKIN_WGRAD3_WOB", 0);
-  pl.wob = wob_env ? wob_env : ((s.Cout % 128 == 0) ? 2 : 1);
-  if (s.Cout % 128) pl.wob = 1;
+  pl.wob = (s.Cout % 128 == 0) ? 2 : 1;
   pl.g = 2 / pl.wob;
   pl.nyw = ceil_div(pl.g * (a.yrows / 8), 8);
   a.nblk_o = s.Cout / (64 * pl.wob); a.nblk_c = s.Cin / 64;
   const int tiles = a.nblk_o * a.nblk_c;
-  static const int target = w3r_env("MMSKIN_WGRAD3_RING_BLOCKS", 256);
+  constexpr int target = 256;   // one 8-wave workgroup per CU
   int ns = target / tiles > 0 ? target / tiles : 1;
   // a split writes a whole tile x 9 taps of fp32 (147 - 295 KB) and the reduction reads it back: at least ~16 stages of work per split
-  static const int min_stages = w3r_env("MMSKIN_WGRAD3_MIN_STAGES", 16);
-  if (min_stages > 1 && ns > a.total_stages / min_stages) ns = a.total_stages / min_stages > 0 ? a.total_stages / min_stages : 1;
+  constexpr int min_stages = 16;
+  if (ns > a.total_stages / min_stages) ns = a.total_stages / min_stages > 0 ? a.total_stages / min_stages : 1;
   if (ns > a.total_stages) ns = a.total_stages;
   a.stages_per_split = ceil_div(ceil_div(a.total_stages, ns), pl.g) * pl.g;   // whole iterations
   a.nsplit = ceil_div(a.total_stages, a.stages_per_split);
@@ -330,11 +324,7 @@ template <int WOB, int G, int NYW, int NIT>
 static int w3r_launch_t(const Wgrad3RingArgs& a, hipStream_t st) {
   constexpr int LDS = NIT * G * (64 * 128 * WOB + W3R_YMAX * 128) + 1024;
   static_assert(LDS <= 160 * 1024, "ring exceeds the LDS");
-  static bool attr_done = false;
-  if (!attr_done) {
-    HIP_CHECK_RET(hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad3_ring_kernel<WOB, G, NYW, NIT>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    attr_done = true;
-  }
+  HIP_CHECK_RET(opt_in_dynamic_lds(reinterpret_cast<const void*>(wgrad3_ring_kernel<WOB, G, NYW, NIT>), LDS));
   hipLaunchKernelGGL((wgrad3_ring_kernel<WOB, G, NYW, NIT>), dim3(a.nblk_o * a.nblk_c * a.nsplit), dim3(512), LDS, st, a);
   HIP_CHECK_RET(hipGetLastError());
   return MMSKIN_OK;

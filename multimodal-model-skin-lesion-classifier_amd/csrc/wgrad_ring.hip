@@ -292,16 +292,14 @@ __global__ __launch_bounds__(512) void wgrad_ring_kernel(const WgradArgs p) {
 }
 
 // ------------------------------------------------------------------------------------------ host
-static int ring_env(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
+constexpr int RING_TARGET_BLOCKS = 256;   // one 8-wave workgroup per CU
 
 bool wgrad_ring_tile(int M, int Cout, int Ktot, WgradRingPlan& r, bool simple) {
-  static const int enabled = ring_env("MMSKIN_WGRAD_RING", 1);
-  if (!enabled || Cout % 64 || Ktot % 64) return false;
+  if (Cout % 64 || Ktot % 64) return false;
   // 1x1 / stride 1 layers: 128 x 128 tiles with two pixel groups wherever they fit -- half the slab bytes per workgroup for 4/3 of the
   // L2 -> LDS fill: l2.c3 56.5 -> 48.6 us, l3.c3 43.7 -> 40.3, l4.c3 41.8 -> 38.6 (profiles/r04_experiments.txt (4)); the gathering
-  // layers (stride-2 1x1, tapped 3x3) lose with it (l4.c2a 97 -> 134 us) and keep the 256 x 128 tile.  MMSKIN_WGRAD_RING_G2=0: off
-  static const int prefer_g2 = ring_env("MMSKIN_WGRAD_RING_G2", 1);
-  if (prefer_g2 && simple && Cout % 128 == 0 && Ktot % 128 == 0) { r.wo = 2; r.wk = 2; }
+  // layers (stride-2 1x1, tapped 3x3) lose with it (l4.c2a 97 -> 134 us) and keep the 256 x 128 tile.
+  if (simple && Cout % 128 == 0 && Ktot % 128 == 0) { r.wo = 2; r.wk = 2; }
   else if (Cout % 256 == 0 && Ktot % 128 == 0) { r.wo = 4; r.wk = 2; }
   else if (Cout % 128 == 0 && Ktot % 256 == 0) { r.wo = 2; r.wk = 4; }
   else if (Cout % 128 == 0 && Ktot % 128 == 0) { r.wo = 2; r.wk = 2; }
@@ -312,8 +310,7 @@ bool wgrad_ring_tile(int M, int Cout, int Ktot, WgradRingPlan& r, bool simple) {
   else return false;
   const int G = 8 / (r.wo * r.wk), step = G * 32;
   const int tiles = (Cout / (64 * r.wo)) * (Ktot / (64 * r.wk));
-  static const int target = ring_env("MMSKIN_WGRAD_RING_BLOCKS", 256);   // one 8-wave workgroup per CU
-  int ns = target / tiles > 0 ? target / tiles : 1;
+  int ns = RING_TARGET_BLOCKS / tiles > 0 ? RING_TARGET_BLOCKS / tiles : 1;
   const int max_split = M / (step * 8) > 0 ? M / (step * 8) : 1;         // at least 8 iterations per workgroup
   if (ns > max_split) ns = max_split;
   r.mps = ceil_div(ceil_div(M, ns), step) * step;
@@ -336,8 +333,7 @@ bool wgrad_gram_plan(int M, int Cout, int Cin, WgradRingPlan& r, int mode) {
   if (Cin % 8 || (uint64_t)M * Cout * 2 >= 0xE0000000ull || (uint64_t)M * Cin * 2 >= 0xE0000000ull) return false;
   r.gram_tiles = mode == 1 ? 0 : ceil_div(Cin, BO);
   const int tiles = (Cout / BO + r.gram_tiles) * (Cin / (64 * r.wk));
-  static const int target = ring_env("MMSKIN_WGRAD_RING_BLOCKS", 256);
-  int ns = target / tiles > 0 ? target / tiles : 1;
+  int ns = RING_TARGET_BLOCKS / tiles > 0 ? RING_TARGET_BLOCKS / tiles : 1;
   const int max_split = M / (step * 8) > 0 ? M / (step * 8) : 1;
   if (ns > max_split) ns = max_split;
   r.mps = ceil_div(ceil_div(M, ns), step) * step;
@@ -445,18 +441,11 @@ static int ring_launch_t(const WgradArgs& a, bool s1, hipStream_t st) {
   constexpr int G = 8 / (WO * WK), LDS = NIT * G * 32 * (64 * WO + 64 * WK) * 2;
   static_assert(LDS <= 160 * 1024, "ring exceeds the LDS");
   const int grid = a.nblk_o * a.nblk_k * a.nsplit;
-  static bool attr_done[2] = {false, false};
   if (s1) {
-    if (!attr_done[1]) {
-      HIP_CHECK_RET(hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_ring_kernel<WO, WK, NIT, true, STAG>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-      attr_done[1] = true;
-    }
+    HIP_CHECK_RET(opt_in_dynamic_lds(reinterpret_cast<const void*>(wgrad_ring_kernel<WO, WK, NIT, true, STAG>), LDS));
     hipLaunchKernelGGL((wgrad_ring_kernel<WO, WK, NIT, true, STAG>), dim3(grid), dim3(512), LDS, st, a);
   } else {
-    if (!attr_done[0]) {
-      HIP_CHECK_RET(hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_ring_kernel<WO, WK, NIT, false, STAG>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-      attr_done[0] = true;
-    }
+    HIP_CHECK_RET(opt_in_dynamic_lds(reinterpret_cast<const void*>(wgrad_ring_kernel<WO, WK, NIT, false, STAG>), LDS));
     hipLaunchKernelGGL((wgrad_ring_kernel<WO, WK, NIT, false, STAG>), dim3(grid), dim3(512), LDS, st, a);
   }
   HIP_CHECK_RET(hipGetLastError());
@@ -473,18 +462,13 @@ int wgrad_ring_launch(WgradArgs& a, const WgradRingPlan& r, hipStream_t st) {
   a.nblk_o = a.nblk_o_main + r.gram_tiles; a.nblk_k = a.Ktot / (64 * r.wk);
   if (!r.gram_tiles) { a.gram_cols = 0; a.colsum = nullptr; }
   ++g_ring_launches;
-  // ring depth: G = 1 tiles move 24 KB per iteration (4 deep = 96 KB), G = 2 tiles 32 - 40 KB (3 deep = 96 - 120 KB)
-  static const int deep = ring_env("MMSKIN_WGRAD_RING_DEEP", 1);
-  // MMSKIN_WGRAD_RING_STAG (default 1): the MFMA-bound tiles (layers 2 - 4) with the two wave halves half an iteration apart
-  static const int stag = ring_env("MMSKIN_WGRAD_RING_STAG", 1);
-  if (stag && r.wo == 4 && r.wk == 2) return ring_launch_t<4, 2, 4, true>(a, r.s1, st);
-  if (stag && r.wo == 2 && r.wk == 4) return ring_launch_t<2, 4, 4, true>(a, r.s1, st);
-  if (stag && r.wo == 2 && r.wk == 2) return ring_launch_t<2, 2, 4, true>(a, r.s1, st);
-  if (r.wo == 4 && r.wk == 2) return deep ? ring_launch_t<4, 2, 4>(a, r.s1, st) : ring_launch_t<4, 2, 3>(a, r.s1, st);
-  if (r.wo == 2 && r.wk == 4) return deep ? ring_launch_t<2, 4, 4>(a, r.s1, st) : ring_launch_t<2, 4, 3>(a, r.s1, st);
-  if (r.wo == 2 && r.wk == 2) return deep ? ring_launch_t<2, 2, 3>(a, r.s1, st) : ring_launch_t<2, 2, 2>(a, r.s1, st);
-  if (r.wo == 4 && r.wk == 1) return deep ? ring_launch_t<4, 1, 3>(a, r.s1, st) : ring_launch_t<4, 1, 2>(a, r.s1, st);
-  if (r.wo == 1 && r.wk == 4) return deep ? ring_launch_t<1, 4, 3>(a, r.s1, st) : ring_launch_t<1, 4, 2>(a, r.s1, st);
+  // ring depth: G = 1 tiles move 24 KB per iteration (4 deep = 96 KB), G = 2 tiles 32 - 40 KB (3 deep = 96 - 120 KB).
+  // The MFMA-bound tiles (layers 2 - 4) run with the two wave halves half an iteration apart (STAG).
+  if (r.wo == 4 && r.wk == 2) return ring_launch_t<4, 2, 4, true>(a, r.s1, st);
+  if (r.wo == 2 && r.wk == 4) return ring_launch_t<2, 4, 4, true>(a, r.s1, st);
+  if (r.wo == 2 && r.wk == 2) return ring_launch_t<2, 2, 4, true>(a, r.s1, st);
+  if (r.wo == 4 && r.wk == 1) return ring_launch_t<4, 1, 3>(a, r.s1, st);
+  if (r.wo == 1 && r.wk == 4) return ring_launch_t<1, 4, 3>(a, r.s1, st);
   if (r.wo == 2 && r.wk == 1) return ring_launch_t<2, 1, 2>(a, r.s1, st);     // 48 KB per iteration (four groups): two deep
   return ring_launch_t<1, 2, 2>(a, r.s1, st);
 }

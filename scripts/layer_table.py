@@ -20,16 +20,13 @@ def resnet50():
 blocks = resnet50()
 stem = ("stem", dict(Mo=N * 112 * 112, Mi=N * 224 * 224, Cin=3, Cout=64, taps=49))
 fwd = [stem]
-import os
-FWD2P = os.environ.get("MMSKIN_FWD2P", "1") != "0" and os.environ.get("MMSKIN_ABN", "1") != "0"
-FWDG = os.environ.get("MMSKIN_FWDG", "1") != "0"
 for u, ds in blocks:
     if ds: fwd.append(ds)
     # two-pass forward (backbone.hip): conv3 of a layer1 / layer2 block without a downsample branch is one conv launch with BatchNorm +
     # residual + ReLU in its epilogue ("c3+bn"); its statistics come from the Gram matrix of its input (a ring-kernel launch, not listed
-    # here).  MMSKIN_FWDG=0: a statistics-only pass of the convolution first (the "c3" row).
-    if FWD2P and not ds and u[2][1]["Cin"] <= 128:
-        fwd += u[:2] + ([u[2]] if not FWDG else []) + [(u[2][0] + "+bn", u[2][1])]
+    # here).
+    if not ds and u[2][1]["Cin"] <= 128:
+        fwd += u[:2] + [(u[2][0] + "+bn", u[2][1])]
     else:
         fwd += u
 bwd = []   # per block, last to first: conv3, conv2, (downsample), conv1 -- the plan's dgrad order

@@ -1,6 +1,6 @@
 """GPU box: time the bf16 Linear GEMM alone (mmskin_linear_forward_ex, bf16 in -> bf16 out, bias + GELU in the epilogue) on the
 BEiT-large / BERT-base shapes of BASELINE configs[4] and check it against a float64 product of the same bf16-rounded operands.
-MMSKIN_GEMM_BIG_MINBLOCKS selects the 256 x 256 tile (0 = off).  usage: linear_bench.py [iters]"""
+usage: linear_bench.py [iters]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "multimodal-model-skin-lesion-classifier_amd")]
@@ -8,7 +8,6 @@ import torch
 from mmskin import ops
 ops.set_linear_dtype("bf16")
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-print("MMSKIN_GEMM_BIG_MINBLOCKS =", os.environ.get("MMSKIN_GEMM_BIG_MINBLOCKS"))
 for name, M, K, N, act in (("beit qkv", 128 * 197, 1024, 3072, 0), ("beit fc1", 128 * 197, 1024, 4096, 2), ("beit fc2", 128 * 197, 4096, 1024, 0),
                            ("beit proj", 128 * 197, 1024, 1024, 0), ("bert qkv", 128 * 512, 768, 2304, 0), ("bert fc1", 128 * 512, 768, 3072, 2),
                            ("bert fc2", 128 * 512, 3072, 768, 0), ("ragged", 1000, 512, 768, 1)):
