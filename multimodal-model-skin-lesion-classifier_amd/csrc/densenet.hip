@@ -17,10 +17,6 @@
 
 namespace {
 
-struct BNRef {
-  int64_t g_off, b_off, rm_off, rv_off;
-};
-
 struct DLayer {
   int Cin, Cp;
   BNRef n1, n2;
@@ -82,15 +78,6 @@ struct DensePlan : PlanBase {
               float* features, bool training, hipStream_t st) override;
   int backward(const float* dfeat, const float* params, unsigned char* ws, float* grads, hipStream_t st) override;
 };
-
-BNRef add_bn(DensePlan& p, const std::string& name, int C) {
-  BNRef r;
-  r.g_off = add_tensor(p.params, p.param_numel, name + ".weight", {C});
-  r.b_off = add_tensor(p.params, p.param_numel, name + ".bias", {C});
-  r.rm_off = add_tensor(p.buffers, p.buffer_numel, name + ".running_mean", {C});
-  r.rv_off = add_tensor(p.buffers, p.buffer_numel, name + ".running_var", {C});
-  return r;
-}
 
 int build_dense_plan(DensePlan& p) {
   const int depths[4] = {6, 12, 32, 32};

@@ -1,13 +1,19 @@
-// EfficientNet-B0 / B7 image-encoder plan executor (torchvision layout: 3x3/2 stem, MBConv stages with squeeze-
-// excitation, SiLU, 3x3 / 5x5 depthwise convolutions, stochastic depth on the residual branches, 1x1 head;
-// `classifier = Identity`).  Replaces `self.image_encoder(image)` for cnn_model_name == "efficientnet-b0" /
-// "efficientnet-b7" (loadImageModelClassifier.py:102-112).
+// Inverted-residual (MBConv) image-encoder plan executor for MobileNet-V2 and EfficientNet-B0 / B7 (torchvision
+// layouts: 3x3/2 stem, inverted-residual stages, 1x1 head, global average pool; `classifier = Identity`).  Replaces
+// `self.image_encoder(image)` for cnn_model_name == "mobilenet-v2" / "efficientnet-b0" / "efficientnet-b7"
+// (loadImageModelClassifier.py:96-112).
 //
-// Same construction as the MobileNet-V2 plan (mobilenet.hip): 1x1 convolutions on the implicit-GEMM kernels with
-// channels padded to 64, depthwise convolutions as HBM-bound elementwise kernels, BatchNorm through the statistics
-// table.  Additions: SiLU (apply / backward-derivative variants of the BatchNorm kernels), squeeze-excitation (global
-// average pool -> two small fp32 Linear layers on the head GEMM -> per-(sample, channel) gate) and row-mode
-// stochastic depth (the per-sample keep/scale mask is handed in by the host each training step).
+// The 1x1 convolutions (97 % of MobileNet-V2's MACs) run on the implicit-GEMM kernels; every activation is kept NHWC
+// with its channel count padded to a multiple of 64 (zero weights / zero BatchNorm gain on the padding, so padded
+// channels stay exactly zero) and the weight-gradient reductions drop the padding.  The 3x3 / 5x5 depthwise
+// convolutions are HBM-bound elementwise-style kernels (ops.hip: dwconv3_*).  BatchNorm uses the shared
+// statistics-table kernels (batch statistics from the conv epilogue / one column pass).
+//
+// The two networks differ in data only, which their builders set: the activation after the BatchNorm (ReLU6 or SiLU:
+// the clamp / SiLU variants of the BatchNorm apply and backward kernels), the depthwise kernel sizes, the BatchNorm
+// eps / momentum, squeeze-excitation behind every depthwise unit (EfficientNet: global average pool -> two small fp32
+// Linear layers on the head GEMM -> per-(sample, channel) gate) and row-mode stochastic depth on the residual
+// branches (EfficientNet: the per-sample keep/scale mask is handed in by the host each training step).
 #include <math.h>
 
 #include "plan.h"
@@ -16,10 +22,7 @@
 namespace {
 
 enum UKind { U_FIRST = 0, U_PW = 1, U_DW = 2 };
-
-struct BNRef {
-  int64_t g_off, b_off, rm_off, rv_off;
-};
+enum Act { ACT_RELU6, ACT_SILU };
 
 struct SEBlock {   // squeeze-excitation behind a depthwise unit
   int C, Cp, Csq;
@@ -29,21 +32,23 @@ struct SEBlock {   // squeeze-excitation behind a depthwise unit
   size_t yse_off;                                     // gated activation (T) -- the project conv's input
 };
 
-struct EUnit {
+struct MBUnit {
   int kind, ksize;
-  int Cin, Cout, Cinp, Coutp;
-  int H, W, stride, OH, OW;
-  bool act;                     // SiLU after the BatchNorm
-  bool res_last, res_first;
+  int Cin, Cout, Cinp, Coutp;   // real / padded channels
+  int H, W, stride, OH, OW;     // input and output spatial size
+  bool act;                     // the plan's activation after the BatchNorm
+  bool res_last;                // last unit of a block with a residual connection: y = bn(x) + block input
+  bool res_first;               // first unit of such a block: its data gradient adds the residual branch's gradient
   int se;                       // index into ses (depthwise units) or -1
-  int sd;                       // residual-block index for stochastic depth (res_last units) or -1
+  int sd;                       // row of the stochastic-depth mask (res_last units) or -1
   int64_t w_off;
   BNRef bn;
-  int64_t wf, wd;
-  size_t x_off, y_off, coef_off, in_off, res_off;
+  int64_t wf, wd;               // staged weights (element offsets; depthwise: [k*k][Cp] inside the forward buffer)
+  size_t x_off, y_off, coef_off;
+  size_t in_off;                // input activation (bytes); block input for res_last's residual = res_off
+  size_t res_off;
 };
 
-inline int pad64(int c) { return (c + 63) / 64 * 64; }
 inline int make_divisible(double v, int divisor = 8) {
   int nv = (int)(v + divisor / 2.0) / divisor * divisor;
   if (nv < divisor) nv = divisor;
@@ -51,19 +56,24 @@ inline int make_divisible(double v, int divisor = 8) {
   return nv;
 }
 
-struct EffPlan : PlanBase {
-  int variant = 0;                  // 0 = B0, 7 = B7
+struct MBPlan : PlanBase {
+  Act act = ACT_RELU6;
   float eps = 1e-5f, mom = 0.1f;
-  std::vector<EUnit> units;
+  std::vector<MBUnit> units;
   std::vector<SEBlock> ses;
-  int n_res = 0;
-  const float* sd_mask = nullptr;   // [n_res][N] keep/scale factors for this training step (null: no stochastic depth)
+  int n_sd = 0;                     // residual blocks with stochastic depth; 0: the plan takes no "sd_mask"
+  const float* sd_mask = nullptr;   // [n_sd][N] keep/scale factors for this training step (null: no stochastic depth)
   int Hp, Wp, stemC;
   size_t off_img8, off_wf, off_wd, off_stat, off_tab, off_partial, off_coefbwd, off_red, off_slab, off_dwv, off_dwpart,
-      off_setmp, off_g[4];
+      off_setmp = 0, off_g[4];
   size_t stat_bytes = 0;
 
+  // the activation's bn_apply cap and BatchNorm-backward mask mode
+  float act_cap() const { return act == ACT_RELU6 ? 6.f : -1.f; }
+  int act_mask() const { return act == ACT_RELU6 ? MASK_FROM_Y6 : MASK_SILU_X; }
+
   int set_pointer(const char* key, const void* ptr) override {
+    if (!n_sd) return PlanBase::set_pointer(key, ptr);
     if (!strcmp(key, "sd_mask")) { sd_mask = reinterpret_cast<const float*>(ptr); return MMSKIN_OK; }
     return MMSKIN_ERR_ARG;
   }
@@ -72,87 +82,33 @@ struct EffPlan : PlanBase {
   int backward(const float* dfeat, const float* params, unsigned char* ws, float* grads, hipStream_t st) override;
 };
 
-BNRef add_bn(EffPlan& p, const std::string& name, int C) {
-  BNRef r;
-  r.g_off = add_tensor(p.params, p.param_numel, name + ".weight", {C});
-  r.b_off = add_tensor(p.params, p.param_numel, name + ".bias", {C});
-  r.rm_off = add_tensor(p.buffers, p.buffer_numel, name + ".running_mean", {C});
-  r.rv_off = add_tensor(p.buffers, p.buffer_numel, name + ".running_var", {C});
-  return r;
+// Registers one conv + BatchNorm unit (torchvision named_parameters() order); returns its index.
+int add_unit(MBPlan& p, int kind, const std::string& conv_name, const std::string& bn_name, int cin, int cout, int h,
+             int w, int stride, int ksize, bool act) {
+  MBUnit u = {};
+  u.kind = kind; u.ksize = ksize; u.Cin = cin; u.Cout = cout; u.Cinp = kind == U_FIRST ? 3 : pad64(cin); u.Coutp = pad64(cout);
+  u.H = h; u.W = w; u.stride = stride; u.se = -1; u.sd = -1;
+  const int pad = ksize / 2;
+  u.OH = kind == U_PW ? h : (h + 2 * pad - ksize) / stride + 1;
+  u.OW = kind == U_PW ? w : (w + 2 * pad - ksize) / stride + 1;
+  u.act = act;
+  if (kind == U_DW) u.w_off = add_tensor(p.params, p.param_numel, conv_name + ".weight", {cout, 1, ksize, ksize});
+  else u.w_off = add_tensor(p.params, p.param_numel, conv_name + ".weight", {cout, cin, kind == U_FIRST ? 3 : 1, kind == U_FIRST ? 3 : 1});
+  u.bn = add_bn(p, bn_name, cout);
+  p.units.push_back(u);
+  return (int)p.units.size() - 1;
 }
 
-int build_eff_plan(EffPlan& p) {
-  const double width = p.variant == 7 ? 2.0 : 1.0, depth = p.variant == 7 ? 3.1 : 1.0;
-  if (p.variant == 7) { p.eps = 1e-3f; p.mom = 0.01f; }   // torchvision: BatchNorm2d(eps=0.001, momentum=0.01) for B5-B7
-  auto adj = [&](int c) { return make_divisible(c * width); };
-  auto add_unit = [&](int kind, const std::string& conv_name, const std::string& bn_name, int cin, int cout, int h, int w,
-                      int stride, int ksize, bool act) -> int {
-    EUnit u = {};
-    u.kind = kind; u.ksize = ksize; u.Cin = cin; u.Cout = cout; u.Cinp = kind == U_FIRST ? 3 : pad64(cin); u.Coutp = pad64(cout);
-    u.H = h; u.W = w; u.stride = stride; u.se = -1; u.sd = -1;
-    const int pad = ksize / 2;
-    u.OH = kind == U_PW ? h : (h + 2 * pad - ksize) / stride + 1;
-    u.OW = kind == U_PW ? w : (w + 2 * pad - ksize) / stride + 1;
-    u.act = act;
-    if (kind == U_DW) u.w_off = add_tensor(p.params, p.param_numel, conv_name + ".weight", {cout, 1, ksize, ksize});
-    else u.w_off = add_tensor(p.params, p.param_numel, conv_name + ".weight", {cout, cin, kind == U_FIRST ? 3 : 1, kind == U_FIRST ? 3 : 1});
-    u.bn = add_bn(p, bn_name, cout);
-    p.units.push_back(u);
-    return (int)p.units.size() - 1;
-  };
-  int h = p.H, w = p.W;
-  p.stemC = adj(32);
-  ARG_CHECK(p.stemC <= 64, "efficientnet: stem width %d", p.stemC);
-  {
-    int i = add_unit(U_FIRST, "features.0.0", "features.0.1", 3, p.stemC, h, w, 2, 3, true);
-    h = p.units[i].OH; w = p.units[i].OW;
-  }
-  // expand, kernel, stride, in, out, layers  (torchvision _efficientnet_conf)
-  const int cfg[7][6] = {{1, 3, 1, 32, 16, 1}, {6, 3, 2, 16, 24, 2}, {6, 5, 2, 24, 40, 2}, {6, 3, 2, 40, 80, 3},
-                         {6, 5, 1, 80, 112, 3}, {6, 5, 2, 112, 192, 4}, {6, 3, 1, 192, 320, 1}};
-  int last_out = 0;
-  for (int si = 0; si < 7; ++si) {
-    const int layers = (int)ceil(cfg[si][5] * depth);
-    for (int li = 0; li < layers; ++li) {
-      const int expand = cfg[si][0], ks = cfg[si][1];
-      const int cout = adj(cfg[si][4]);
-      const int cin = li == 0 ? adj(cfg[si][3]) : cout;
-      const int stride = li == 0 ? cfg[si][2] : 1;
-      const int hidden = make_divisible((double)cin * expand);
-      const bool res = stride == 1 && cin == cout;
-      const std::string base = "features." + std::to_string(si + 1) + "." + std::to_string(li) + ".block.";
-      const size_t first = p.units.size();
-      int k = 0;
-      if (hidden != cin) { add_unit(U_PW, base + "0.0", base + "0.1", cin, hidden, h, w, 1, 1, true); k = 1; }
-      const int di = add_unit(U_DW, base + std::to_string(k) + ".0", base + std::to_string(k) + ".1", hidden, hidden, h, w, stride, ks, true);
-      h = p.units[di].OH; w = p.units[di].OW;
-      SEBlock se = {};
-      se.C = hidden; se.Cp = pad64(hidden); se.Csq = cin / 4 > 1 ? cin / 4 : 1;
-      const std::string sn = base + std::to_string(k + 1);
-      se.w1_off = add_tensor(p.params, p.param_numel, sn + ".fc1.weight", {se.Csq, hidden, 1, 1});
-      se.b1_off = add_tensor(p.params, p.param_numel, sn + ".fc1.bias", {se.Csq});
-      se.w2_off = add_tensor(p.params, p.param_numel, sn + ".fc2.weight", {hidden, se.Csq, 1, 1});
-      se.b2_off = add_tensor(p.params, p.param_numel, sn + ".fc2.bias", {hidden});
-      p.units[di].se = (int)p.ses.size();
-      p.ses.push_back(se);
-      const int pi = add_unit(U_PW, base + std::to_string(k + 2) + ".0", base + std::to_string(k + 2) + ".1", hidden, cout, h, w, 1, 1, false);
-      if (res) { p.units[first].res_first = true; p.units[pi].res_last = true; p.units[pi].sd = p.n_res++; }
-      ARG_CHECK(h >= 1 && w >= 1, "efficientnet: input %dx%d too small", p.H, p.W);
-      last_out = cout;
-    }
-  }
-  const int headC = 4 * last_out;
-  add_unit(U_PW, "features.8.0", "features.8.1", last_out, headC, h, w, 1, 1, true);
-  p.feat_dim = headC;
-  ARG_CHECK(headC % 64 == 0, "efficientnet: head width %d", headC);
-  ARG_CHECK(p.units[0].OH <= 240 && p.units[0].OW <= 240, "efficientnet: input %dx%d too large for the weight-gradient kernel", p.H, p.W);
+// Staged-weight table and workspace carve-up, once the builder has registered every unit.
+int finish_plan(MBPlan& p, const char* arch) {
+  ARG_CHECK(p.units[0].OH <= 240 && p.units[0].OW <= 240, "%s: input %dx%d too large for the weight-gradient kernel", arch, p.H, p.W);
   p.Hp = p.H + 2; p.Wp = (p.W + 4 + 1) / 2 * 2;
 
   // ---- staged weights
-  int64_t wf = 64 * 128, wd = 0;
+  int64_t wf = 64 * 128, wd = 0;   // slot 0: first conv's virtual operand
   p.units[0].wf = 0;
   for (size_t i = 1; i < p.units.size(); ++i) {
-    EUnit& u = p.units[i];
+    MBUnit& u = p.units[i];
     if (u.kind == U_DW) { u.wf = wf; wf += (int64_t)u.ksize * u.ksize * u.Coutp; continue; }
     StageDesc d = {};
     d.src_off = u.w_off; d.Cout = u.Cout; d.Cin = u.Cin; d.taps = 1; d.Cout_pad = u.Coutp; d.Cin_pad = u.Cinp;
@@ -174,7 +130,7 @@ int build_eff_plan(EffPlan& p) {
   int maxCp = 64;
   size_t prev_y = 0, block_in = 0;
   for (size_t i = 0; i < p.units.size(); ++i) {
-    EUnit& u = p.units[i];
+    MBUnit& u = p.units[i];
     const size_t rows = (size_t)p.N * u.OH * u.OW, in_rows = (size_t)p.N * u.H * u.W;
     u.in_off = prev_y;
     if (u.res_first) block_in = prev_y;
@@ -225,16 +181,101 @@ int build_eff_plan(EffPlan& p) {
   p.off_slab = carve(cur, slab);
   p.off_dwv = carve(cur, 64 * 128 * sizeof(float));
   p.off_dwpart = carve(cur, (dwpart > 0 ? dwpart : 1) * sizeof(float));
-  p.off_setmp = carve(cur, (setmp > 0 ? setmp : 1) * sizeof(float));
+  if (setmp) p.off_setmp = carve(cur, setmp * sizeof(float));
   for (int i = 0; i < 4; ++i) p.off_g[i] = carve(cur, maxact * es);
   p.ws_bytes = cur;
   return MMSKIN_OK;
 }
 
+int build_mobilenet_v2(MBPlan& p) {
+  p.act = ACT_RELU6;
+  p.stemC = 32;
+  int h = p.H, w = p.W;
+  {
+    const int i = add_unit(p, U_FIRST, "features.0.0", "features.0.1", 3, p.stemC, h, w, 2, 3, true);
+    h = p.units[i].OH; w = p.units[i].OW;
+  }
+  // expansion, out, layers, stride  (torchvision mobilenet_v2)
+  const int cfg[7][4] = {{1, 16, 1, 1}, {6, 24, 2, 2}, {6, 32, 3, 2}, {6, 64, 4, 2}, {6, 96, 3, 1}, {6, 160, 3, 2}, {6, 320, 1, 1}};
+  int cin = p.stemC, fi = 1;
+  for (const auto& c : cfg) {
+    for (int i = 0; i < c[2]; ++i, ++fi) {
+      const int t = c[0], oup = c[1], stride = i == 0 ? c[3] : 1, hidden = cin * t;
+      const bool res = stride == 1 && cin == oup;
+      const std::string base = "features." + std::to_string(fi) + ".conv.";
+      const size_t first = p.units.size();
+      int k = 0;
+      if (t != 1) { add_unit(p, U_PW, base + "0.0", base + "0.1", cin, hidden, h, w, 1, 1, true); k = 1; }
+      const int di = add_unit(p, U_DW, base + std::to_string(k) + ".0", base + std::to_string(k) + ".1", hidden, hidden, h, w, stride, 3, true);
+      h = p.units[di].OH; w = p.units[di].OW;
+      const int pi = add_unit(p, U_PW, base + std::to_string(k + 1), base + std::to_string(k + 2), hidden, oup, h, w, 1, 1, false);
+      if (res) { p.units[first].res_first = true; p.units[pi].res_last = true; }
+      ARG_CHECK(h >= 1 && w >= 1, "mobilenet-v2: input %dx%d too small", p.H, p.W);
+      cin = oup;
+    }
+  }
+  add_unit(p, U_PW, "features.18.0", "features.18.1", cin, 1280, h, w, 1, 1, true);
+  p.feat_dim = 1280;
+  return finish_plan(p, "mobilenet-v2");
+}
+
+int build_efficientnet(MBPlan& p, int variant) {   // variant 0 = B0, 7 = B7
+  const double width = variant == 7 ? 2.0 : 1.0, depth = variant == 7 ? 3.1 : 1.0;
+  if (variant == 7) { p.eps = 1e-3f; p.mom = 0.01f; }   // torchvision: BatchNorm2d(eps=0.001, momentum=0.01) for B5-B7
+  p.act = ACT_SILU;
+  auto adj = [&](int c) { return make_divisible(c * width); };
+  int h = p.H, w = p.W;
+  p.stemC = adj(32);
+  ARG_CHECK(p.stemC <= 64, "efficientnet: stem width %d", p.stemC);
+  {
+    const int i = add_unit(p, U_FIRST, "features.0.0", "features.0.1", 3, p.stemC, h, w, 2, 3, true);
+    h = p.units[i].OH; w = p.units[i].OW;
+  }
+  // expand, kernel, stride, in, out, layers  (torchvision _efficientnet_conf)
+  const int cfg[7][6] = {{1, 3, 1, 32, 16, 1}, {6, 3, 2, 16, 24, 2}, {6, 5, 2, 24, 40, 2}, {6, 3, 2, 40, 80, 3},
+                         {6, 5, 1, 80, 112, 3}, {6, 5, 2, 112, 192, 4}, {6, 3, 1, 192, 320, 1}};
+  int last_out = 0;
+  for (int si = 0; si < 7; ++si) {
+    const int layers = (int)ceil(cfg[si][5] * depth);
+    for (int li = 0; li < layers; ++li) {
+      const int expand = cfg[si][0], ks = cfg[si][1];
+      const int cout = adj(cfg[si][4]);
+      const int cin = li == 0 ? adj(cfg[si][3]) : cout;
+      const int stride = li == 0 ? cfg[si][2] : 1;
+      const int hidden = make_divisible((double)cin * expand);
+      const bool res = stride == 1 && cin == cout;
+      const std::string base = "features." + std::to_string(si + 1) + "." + std::to_string(li) + ".block.";
+      const size_t first = p.units.size();
+      int k = 0;
+      if (hidden != cin) { add_unit(p, U_PW, base + "0.0", base + "0.1", cin, hidden, h, w, 1, 1, true); k = 1; }
+      const int di = add_unit(p, U_DW, base + std::to_string(k) + ".0", base + std::to_string(k) + ".1", hidden, hidden, h, w, stride, ks, true);
+      h = p.units[di].OH; w = p.units[di].OW;
+      SEBlock se = {};
+      se.C = hidden; se.Cp = pad64(hidden); se.Csq = cin / 4 > 1 ? cin / 4 : 1;
+      const std::string sn = base + std::to_string(k + 1);
+      se.w1_off = add_tensor(p.params, p.param_numel, sn + ".fc1.weight", {se.Csq, hidden, 1, 1});
+      se.b1_off = add_tensor(p.params, p.param_numel, sn + ".fc1.bias", {se.Csq});
+      se.w2_off = add_tensor(p.params, p.param_numel, sn + ".fc2.weight", {hidden, se.Csq, 1, 1});
+      se.b2_off = add_tensor(p.params, p.param_numel, sn + ".fc2.bias", {hidden});
+      p.units[di].se = (int)p.ses.size();
+      p.ses.push_back(se);
+      const int pi = add_unit(p, U_PW, base + std::to_string(k + 2) + ".0", base + std::to_string(k + 2) + ".1", hidden, cout, h, w, 1, 1, false);
+      if (res) { p.units[first].res_first = true; p.units[pi].res_last = true; p.units[pi].sd = p.n_sd++; }
+      ARG_CHECK(h >= 1 && w >= 1, "efficientnet: input %dx%d too small", p.H, p.W);
+      last_out = cout;
+    }
+  }
+  const int headC = 4 * last_out;
+  add_unit(p, U_PW, "features.8.0", "features.8.1", last_out, headC, h, w, 1, 1, true);
+  p.feat_dim = headC;
+  ARG_CHECK(headC % 64 == 0, "efficientnet: head width %d", headC);
+  return finish_plan(p, "efficientnet");
+}
+
 template <typename T>
-int eff_forward(EffPlan& p, const void* image, const float* norm6, const float* params, float* buffers,
-                unsigned char* ws, float* features, bool training, hipStream_t st) {
-  const float eps = p.eps, mom = p.mom;
+int mb_forward(MBPlan& p, const void* image, const float* norm6, const float* params, float* buffers,
+               unsigned char* ws, float* features, bool training, hipStream_t st) {
+  const float eps = p.eps, mom = p.mom, cap = p.act_cap();
   T* wf = reinterpret_cast<T*>(ws + p.off_wf);
   T* wd = reinterpret_cast<T*>(ws + p.off_wd);
   float* stat_sum = reinterpret_cast<float*>(ws + p.off_stat);
@@ -246,7 +287,7 @@ int eff_forward(EffPlan& p, const void* image, const float* norm6, const float* 
   if ((rc = p.ensure_table())) return rc;
   PROF(K_STAGE, 0.0, 0.0, stage_weights<T>(p.table_dev, (int)p.table_host.size(), p.max_stage_elems, params, wf, wd, training, st));
   PROF(K_STAGE, 0.0, 0.0, vgg_stage_first<T>(params + p.units[0].w_off, wf, st, p.stemC));
-  for (EUnit& u : p.units)
+  for (MBUnit& u : p.units)
     if (u.kind == U_DW) PROF(K_STAGE, 0.0, 0.0, dw_stage_weights<T>(params + u.w_off, u.Cout, u.Coutp, wf + u.wf, st, u.ksize));
   for (SEBlock& se : p.ses) {
     PROF(K_STAGE, 0.0, 0.0, pad_matrix(params + se.w1_off, se.Csq, se.C, se.Csq, se.Cp, reinterpret_cast<float*>(ws + se.w1p_off), st));
@@ -256,7 +297,7 @@ int eff_forward(EffPlan& p, const void* image, const float* norm6, const float* 
   T* img8 = reinterpret_cast<T*>(ws + p.off_img8);
   PROF(K_STEM_MISC, 0.0, 0.0, pack_nhwc8<T>(image, norm6, p.N, p.H, p.W, p.Hp, p.Wp, img8, st));
 
-  for (EUnit& u : p.units) {
+  for (MBUnit& u : p.units) {
     const size_t rows = (size_t)p.N * u.OH * u.OW;
     const T* in = reinterpret_cast<const T*>(ws + u.in_off);
     T* x = reinterpret_cast<T*>(ws + u.x_off);
@@ -291,7 +332,7 @@ int eff_forward(EffPlan& p, const void* image, const float* norm6, const float* 
            sd_residual_add<T>(y, res, sd + (size_t)u.sd * p.N, p.N, (size_t)u.OH * u.OW * Cp, y, st));
     } else {
       PROF(K_BN_FWD, 0.0, (res ? 3.0 : 2.0) * rows * Cp * sizeof(T),
-           bn_apply<T>(x, res, k, k + Cp, nullptr, nullptr, y, rows, Cp, u.act, st, nullptr, -1.f));
+           bn_apply<T>(x, res, k, k + Cp, nullptr, nullptr, y, rows, Cp, u.act, st, nullptr, cap));
     }
     if (u.se >= 0) {   // squeeze-excitation on the depthwise output
       SEBlock& se = p.ses[u.se];
@@ -309,12 +350,12 @@ int eff_forward(EffPlan& p, const void* image, const float* norm6, const float* 
       PROF(K_BN_FWD, 0.0, 2.0 * rows * Cp * sizeof(T), se_scale_fwd<T>(y, g, p.N, u.OH * u.OW, Cp, reinterpret_cast<T*>(ws + se.yse_off), st));
     }
   }
-  EUnit& last = p.units.back();
+  MBUnit& last = p.units.back();
   return avgpool_fwd<T>(reinterpret_cast<const T*>(ws + last.y_off), p.N, last.OH * last.OW, last.Coutp, features, st);
 }
 
 template <typename T>
-int eff_backward(EffPlan& p, const float* dfeat, const float* params, unsigned char* ws, float* grads, hipStream_t st) {
+int mb_backward(MBPlan& p, const float* dfeat, const float* params, unsigned char* ws, float* grads, hipStream_t st) {
   T* wf = reinterpret_cast<T*>(ws + p.off_wf);
   T* wd = reinterpret_cast<T*>(ws + p.off_wd);
   float* slab = reinterpret_cast<float*>(ws + p.off_slab);
@@ -323,15 +364,16 @@ int eff_backward(EffPlan& p, const float* dfeat, const float* params, unsigned c
   double* red = reinterpret_cast<double*>(ws + p.off_red);
   float* setmp = reinterpret_cast<float*>(ws + p.off_setmp);
   const float* sd = p.sd_mask;
+  const int act_mask = p.act_mask();
   T* B[4];
   for (int i = 0; i < 4; ++i) B[i] = reinterpret_cast<T*>(ws + p.off_g[i]);
   int rc, cur = 0, reserved = -1;
   auto take = [&](int a, int b) { for (int i = 0; i < 4; ++i) if (i != a && i != b && i != reserved) return i; return -1; };
-  EUnit& last = p.units.back();
+  MBUnit& last = p.units.back();
   if ((rc = avgpool_bwd<T>(dfeat, p.N, last.OH * last.OW, last.Coutp, B[cur], st))) return rc;
 
   for (int ui = (int)p.units.size() - 1; ui >= 0; --ui) {
-    EUnit& u = p.units[ui];
+    MBUnit& u = p.units[ui];
     const size_t rows = (size_t)p.N * u.OH * u.OW;
     const int Cp = u.Coutp, HW = u.OH * u.OW;
     const T* x = reinterpret_cast<const T*>(ws + u.x_off);
@@ -379,9 +421,9 @@ int eff_backward(EffPlan& p, const float* dfeat, const float* params, unsigned c
         cur = nb;
       }
     }
-    // ---- BatchNorm (+ SiLU) backward: dy -> dx
+    // ---- BatchNorm (+ activation) backward: dy -> dx
     const int a = take(cur, -1);
-    const int mode = u.act ? MASK_SILU_X : MASK_NONE;
+    const int mode = u.act ? act_mask : MASK_NONE;
     int nr = 0;
     p.prof.begin(K_BN_BWD, st);
     rc = bn_bwd_reduce<T>(B[cur], x, y, k, k + Cp, mode, rows, Cp, partial, &nr, st);
@@ -392,6 +434,7 @@ int eff_backward(EffPlan& p, const float* dfeat, const float* params, unsigned c
     if (p.prof.on) p.prof.bytes[K_BN_BWD] += 6.0 * rows * Cp * sizeof(T);
     if (rc) return rc;
     const T* dx = B[a];
+    // ---- convolution backward
     if (u.kind == U_FIRST) {
       float* dwv = reinterpret_cast<float*>(ws + p.off_dwv);
       ConvShape s = {p.N, p.H, p.W, 3, 64, 3, 3, 2, 1};
@@ -403,7 +446,7 @@ int eff_backward(EffPlan& p, const float* dfeat, const float* params, unsigned c
     if (u.kind == U_PW) {
       ConvShape s = {p.N, u.H, u.W, u.Cinp, u.Coutp, 1, 1, 1, 0};
       PROF(K_WGRAD, conv_flops(s), conv_bytes(s, sizeof(T)), launch_conv_wgrad<T>(s, dx, in, slab, grads + u.w_off, st, u.Cout, u.Cin));
-      if (u.res_first) {
+      if (u.res_first) {   // add the residual branch's gradient in the epilogue, in place on the buffer that holds it
         b = reserved;
         PROF(K_CONV_DGRAD, conv_flops(s), conv_bytes(s, sizeof(T), 1), launch_conv_dgrad<T>(s, dx, wd + u.wd, B[b], B[b], st));
         reserved = -1;
@@ -427,22 +470,30 @@ int eff_backward(EffPlan& p, const float* dfeat, const float* params, unsigned c
   return MMSKIN_OK;
 }
 
-int EffPlan::forward(const void* image, const float* norm6, const float* params, float* buffers, unsigned char* ws,
-                     float* features, bool training, hipStream_t st) {
-  if (dtype == 1) return eff_forward<bf16_t>(*this, image, norm6, params, buffers, ws, features, training, st);
-  return eff_forward<float>(*this, image, norm6, params, buffers, ws, features, training, st);
+int MBPlan::forward(const void* image, const float* norm6, const float* params, float* buffers, unsigned char* ws,
+                    float* features, bool training, hipStream_t st) {
+  if (dtype == 1) return mb_forward<bf16_t>(*this, image, norm6, params, buffers, ws, features, training, st);
+  return mb_forward<float>(*this, image, norm6, params, buffers, ws, features, training, st);
 }
-int EffPlan::backward(const float* dfeat, const float* params, unsigned char* ws, float* grads, hipStream_t st) {
-  if (dtype == 1) return eff_backward<bf16_t>(*this, dfeat, params, ws, grads, st);
-  return eff_backward<float>(*this, dfeat, params, ws, grads, st);
+int MBPlan::backward(const float* dfeat, const float* params, unsigned char* ws, float* grads, hipStream_t st) {
+  if (dtype == 1) return mb_backward<bf16_t>(*this, dfeat, params, ws, grads, st);
+  return mb_backward<float>(*this, dfeat, params, ws, grads, st);
+}
+
+template <typename Build>
+PlanBase* make_plan(int N, int H, int W, int dtype, int* rc, Build build) {
+  MBPlan* p = new MBPlan();
+  p->N = N; p->H = H; p->W = W; p->dtype = dtype;
+  *rc = build(*p);
+  if (*rc) { delete p; return nullptr; }
+  return p;
 }
 
 }  // namespace
 
+PlanBase* make_mobilenet_plan(int N, int H, int W, int dtype, int* rc) {
+  return make_plan(N, H, W, dtype, rc, build_mobilenet_v2);
+}
 PlanBase* make_efficientnet_plan(int variant, int N, int H, int W, int dtype, int* rc) {
-  EffPlan* p = new EffPlan();
-  p->variant = variant; p->N = N; p->H = H; p->W = W; p->dtype = dtype;
-  *rc = build_eff_plan(*p);
-  if (*rc) { delete p; return nullptr; }
-  return p;
+  return make_plan(N, H, W, dtype, rc, [variant](MBPlan& p) { return build_efficientnet(p, variant); });
 }

@@ -1,4 +1,5 @@
-// Shared scaffolding of the image-encoder plan executors (backbone.hip: ResNet, densenet.hip: DenseNet).
+// Shared scaffolding of the image-encoder plan executors (backbone.hip: ResNet, densenet.hip: DenseNet, vgg.hip: VGG,
+// mbconv.hip: MobileNet-V2 / EfficientNet).
 // A plan is built once per (architecture, batch, H, W, dtype): it fixes the flat parameter / buffer
 // layout (torchvision named_parameters() order), the workspace carve-up and the launch sequence, so
 // that one C-ABI call runs a whole forward or backward on the caller's stream.
@@ -168,6 +169,22 @@ static inline int64_t add_tensor(std::vector<TensorInfo>& v, int64_t& total, con
   v.push_back(t);
   return t.offset;
 }
+
+// One BatchNorm2d's flat offsets: weight, bias (params) and running_mean, running_var (buffers), in torchvision's order.
+struct BNRef {
+  int64_t g_off, b_off, rm_off, rv_off;
+};
+
+static inline BNRef add_bn(PlanBase& p, const std::string& name, int C) {
+  BNRef r;
+  r.g_off = add_tensor(p.params, p.param_numel, name + ".weight", {C});
+  r.b_off = add_tensor(p.params, p.param_numel, name + ".bias", {C});
+  r.rm_off = add_tensor(p.buffers, p.buffer_numel, name + ".running_mean", {C});
+  r.rv_off = add_tensor(p.buffers, p.buffer_numel, name + ".running_var", {C});
+  return r;
+}
+
+static inline int pad64(int c) { return (c + 63) / 64 * 64; }   // channel count padded for the GEMM kernels
 
 static inline size_t carve(size_t& cursor, size_t bytes) {
   size_t o = cursor;

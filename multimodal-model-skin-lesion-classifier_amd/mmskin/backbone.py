@@ -579,7 +579,7 @@ MOBILENET_V2_CFG = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), 
 
 class HipMobileNetV2(_FlatBackbone):
     """torchvision mobilenet_v2 module tree (features.N[.conv.K[.J]]) with `classifier = Identity`
-    (loadImageModelClassifier.py:96-100) -> 1280 features; plan executor csrc/mobilenet.hip."""
+    (loadImageModelClassifier.py:96-100) -> 1280 features; plan executor csrc/mbconv.hip."""
 
     def __init__(self, name="mobilenet-v2", compute_dtype=None):
         super().__init__()
@@ -655,7 +655,7 @@ class _MBConv(nn.Module):
 
 class HipEfficientNet(_FlatBackbone):
     """torchvision efficientnet_b0 / efficientnet_b7 module tree with `classifier = Identity`
-    (loadImageModelClassifier.py:102-112) -> 1280 / 2560 features; plan executor csrc/effnet.hip."""
+    (loadImageModelClassifier.py:102-112) -> 1280 / 2560 features; plan executor csrc/mbconv.hip."""
 
     def __init__(self, name, compute_dtype=None):
         super().__init__()
