@@ -198,7 +198,19 @@ int mmskin_linear_backward_keep(const float* dy, const void* x16, const float* w
 int mmskin_gelu_forward_bf16(const float* z, void* h16, int64_t rows, int cols, int cols_pad, void* stream);
 int mmskin_linear_forward_x16(const void* x16, const float* w, const float* b, const float* res, float* y, int M, int K, int N, int relu,
                               void* stream);                     /* res as above: the block's skip connection in the same pass */
-/* y = LN(x)*g + b over the last dim, optional fused ReLU; mean/rstd [M] saved for backward */
+/* The same MLP with timm's StarReLU (metaformer.py: y = s * relu(z)^2 + b, s and b learnable scalars, device pointers to one float
+ * each) in GELU's place: mmskin_star_relu_forward_bf16 writes h16 = bf16(s * relu(z)^2 + b); the backward of the first Linear applies
+ * 2 s relu(z) inside the pass that converts dh for the bf16 GEMMs and writes dsb[0] = sum dh * relu(z)^2, dsb[1] = sum dh (fixed-order
+ * reductions: bitwise repeatable).  Needs the kept operand of mmskin_linear_forward_keep and N % 4 == 0. */
+int mmskin_star_relu_forward_bf16(const float* z, const float* s, const float* b, void* h16, int64_t rows, int cols, int cols_pad,
+                                  void* stream);
+int mmskin_linear_star_relu_backward_keep(const float* dh, const void* x16, const float* w, const float* z, const float* s, float* dsb,
+                                          float* dx, float* dw, float* db, int M, int K, int N, void* stream);
+/* Elementwise StarReLU for every other shape: y = s * relu(z)^2 + b; backward dz = dy * 2 s relu(z) (dz may be NULL) and dsb as above */
+int mmskin_star_relu_forward(const float* z, const float* s, const float* b, float* y, int64_t n, void* stream);
+int mmskin_star_relu_backward(const float* dy, const float* z, const float* s, float* dz, float* dsb, int64_t n, void* stream);
+/* y = LN(x)*g + b over the last dim, optional fused ReLU; mean/rstd [M] saved for backward.  b may be NULL (a LayerNorm without
+ * bias, timm metaformer's norms): the backward then writes no db.  The same holds for mmskin_layernorm_forward_mixed. */
 int mmskin_layernorm_forward(const float* x, const float* g, const float* b, float* y, float* mean, float* rstd,
                              int M, int N, float eps, int relu, void* stream);
 int mmskin_layernorm_backward(const float* dy, const float* x, const float* g, const float* b, const float* mean,
@@ -365,6 +377,15 @@ int mmskin_conv_pos_enc_forward(const float* x, const float* w, const float* b, 
                                 void* stream);
 int mmskin_conv_pos_enc_backward(const float* dy, const float* x, const float* w, float* w_stage, float* scratch, float* dx, float* dw,
                                  float* db, int N, int H, int W, int C, void* stream);
+/* CAFormer SepConv core (timm metaformer.py SepConv: act1 -> dwconv) on fp32 NHWC z [N, H, W, C], C % 4 == 0:
+ * y = dwconv7x7(s * relu(z)^2 + b, w), w [C, 1, 7, 7], stride 1, pad 3, no bias; s, b: device pointers to one float each.  The backward
+ * reads dy and z once and writes dz (may be NULL), dw [C, 1, 7, 7] (may be NULL) and dsb[0..1] = the gradients of s and b (may be
+ * NULL); its reductions run in a fixed order (bitwise repeatable).  scratch: mmskin_dw7_star_scratch_floats(N, H, W, C) floats. */
+int64_t mmskin_dw7_star_scratch_floats(int N, int H, int W, int C);
+int mmskin_dw7_star_forward(const float* z, const float* w, const float* s, const float* b, float* y, int N, int H, int W, int C,
+                            void* stream);
+int mmskin_dw7_star_backward(const float* dy, const float* z, const float* w, const float* s, const float* b, float* scratch, float* dz,
+                             float* dw, float* dsb, int N, int H, int W, int C, void* stream);
 /* embedding gather for categorical metadata columns: table [ncols, card, E]; ids [B, ncols] int64 */
 int mmskin_embedding_forward(const float* table, const int64_t* ids, float* out, int B, int ncols, int card, int E,
                              void* stream);

@@ -416,7 +416,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
   for (int i = lane; i < N; i += 64) { float d = xr[i] - mu; q += d * d; }
   const float rs = 1.0f / sqrtf(wave_sum(q) / (float)N + eps);
   for (int i = lane; i < N; i += 64) {
-    float v = (xr[i] - mu) * rs * g[i] + b[i];
+    float v = (xr[i] - mu) * rs * g[i] + (b ? b[i] : 0.f);
     if (relu) v = fmaxf(v, 0.f);
     y[(int64_t)row * N + i] = v;
   }
@@ -437,7 +437,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_dx_kernel(const float* __re
   for (int i = lane; i < N; i += 64) {
     float xh = (xr[i] - mu) * rs;
     float d = dr[i];
-    if (relu && !(xh * g[i] + b[i] > 0.f)) d = 0.f;
+    if (relu && !(xh * g[i] + (b ? b[i] : 0.f) > 0.f)) d = 0.f;
     float dg = d * g[i];
     c1 += dg; c2 += dg * xh;
   }
@@ -445,7 +445,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_dx_kernel(const float* __re
   for (int i = lane; i < N; i += 64) {
     float xh = (xr[i] - mu) * rs;
     float d = dr[i];
-    if (relu && !(xh * g[i] + b[i] > 0.f)) d = 0.f;
+    if (relu && !(xh * g[i] + (b ? b[i] : 0.f) > 0.f)) d = 0.f;
     dx[(int64_t)row * N + i] = rs * (d * g[i] - c1 - xh * c2);
   }
 }
@@ -485,12 +485,25 @@ static int rows_sum(const float* part, int R, int ncols, int split, float* out0,
 __device__ __forceinline__ float gelu_grad(float z) {
   return 0.5f * (1.f + erff(z * 0.70710678118654752f)) + z * 0.3989422804014327f * __expf(-0.5f * z * z);
 }
-template <bool CVT, bool GELU = false>
+// STAR: x is the gradient w.r.t. StarReLU(z) = s * relu(z)^2 + b; it is multiplied by 2 s relu(z) on the way in, and the block's sums
+// of x * relu(z)^2 and x (the gradients of s and b) go to star_part[2 * block] -- star_pair_sum adds the blocks in a fixed order.
+template <bool STAR>
+__device__ __forceinline__ float4 star_grad4(float4 v, float4 z, float s2, float& as, float& ab) {
+  if (!STAR) return v;
+  const float rx = fmaxf(z.x, 0.f), ry = fmaxf(z.y, 0.f), rz = fmaxf(z.z, 0.f), rw = fmaxf(z.w, 0.f);
+  as += (v.x * rx * rx + v.y * ry * ry) + (v.z * rz * rz + v.w * rw * rw);
+  ab += (v.x + v.y) + (v.z + v.w);
+  return make_float4(v.x * s2 * rx, v.y * s2 * ry, v.z * s2 * rz, v.w * s2 * rw);
+}
+template <bool CVT, bool GELU = false, bool STAR = false>
 __global__ __launch_bounds__(256) void colsum4_kernel(const float* __restrict__ x, int64_t M, int N, int rows_per_block, int CW, int lanes,
                                                       float* __restrict__ part, bf16_t* __restrict__ out16, int cols_pad,
-                                                      const float* __restrict__ zg = nullptr) {
+                                                      const float* __restrict__ zg = nullptr, const float* __restrict__ star_s = nullptr,
+                                                      float* __restrict__ star_part = nullptr) {
   extern __shared__ float cs_red[];           // [lanes][CW * 4]
   const int cx = threadIdx.x % CW, ly = threadIdx.x / CW;
+  const float s2 = STAR ? 2.f * star_s[0] : 0.f;
+  float st_s = 0.f, st_b = 0.f;
   const int c4 = blockIdx.y * CW + cx, col = c4 * 4;
   const int ncol4 = (CVT ? cols_pad : N) / 4;
   const bool real = col < N;
@@ -507,6 +520,10 @@ __global__ __launch_bounds__(256) void colsum4_kernel(const float* __restrict__ 
         v0.x *= gelu_grad(z0.x); v0.y *= gelu_grad(z0.y); v0.z *= gelu_grad(z0.z); v0.w *= gelu_grad(z0.w);
         v1.x *= gelu_grad(z1.x); v1.y *= gelu_grad(z1.y); v1.z *= gelu_grad(z1.z); v1.w *= gelu_grad(z1.w);
       }
+      if (STAR && real) {
+        v0 = star_grad4<STAR>(v0, *reinterpret_cast<const float4*>(zg + r * N + col), s2, st_s, st_b);
+        v1 = star_grad4<STAR>(v1, *reinterpret_cast<const float4*>(zg + (r + lanes) * N + col), s2, st_s, st_b);
+      }
       a0.x += v0.x; a0.y += v0.y; a0.z += v0.z; a0.w += v0.w;
       a1.x += v1.x; a1.y += v1.y; a1.z += v1.z; a1.w += v1.w;
       if (CVT) {
@@ -521,6 +538,7 @@ __global__ __launch_bounds__(256) void colsum4_kernel(const float* __restrict__ 
         const float4 z0 = *reinterpret_cast<const float4*>(zg + r * N + col);
         v0.x *= gelu_grad(z0.x); v0.y *= gelu_grad(z0.y); v0.z *= gelu_grad(z0.z); v0.w *= gelu_grad(z0.w);
       }
+      if (STAR && real) v0 = star_grad4<STAR>(v0, *reinterpret_cast<const float4*>(zg + r * N + col), s2, st_s, st_b);
       a0.x += v0.x; a0.y += v0.y; a0.z += v0.z; a0.w += v0.w;
       if (CVT) *reinterpret_cast<uint2*>(out16 + r * cols_pad + col) = make_uint2(f32_to_bf16_bits(v0.x) | (f32_to_bf16_bits(v0.y) << 16), f32_to_bf16_bits(v0.z) | (f32_to_bf16_bits(v0.w) << 16));
     }
@@ -534,6 +552,30 @@ __global__ __launch_bounds__(256) void colsum4_kernel(const float* __restrict__ 
       for (int l = 0; l < lanes; ++l) t += cs_red[(size_t)l * CW * 4 + i];
       part[(int64_t)blockIdx.x * N + cc] = t;
     }
+  }
+  if (STAR) {
+    __shared__ float st_red[2][4];
+    st_s = wave_sum(st_s); st_b = wave_sum(st_b);
+    if ((threadIdx.x & 63) == 0) { st_red[0][threadIdx.x >> 6] = st_s; st_red[1][threadIdx.x >> 6] = st_b; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float* o = star_part + 2 * ((int64_t)blockIdx.y * gridDim.x + blockIdx.x);
+      o[0] = (st_red[0][0] + st_red[0][1]) + (st_red[0][2] + st_red[0][3]);
+      o[1] = (st_red[1][0] + st_red[1][1]) + (st_red[1][2] + st_red[1][3]);
+    }
+  }
+}
+// out[0..1] = sum over the nb pairs part[2 i], part[2 i + 1], in a fixed order (one block): the StarReLU scalar gradients
+__global__ __launch_bounds__(256) void star_pair_sum_kernel(const float* __restrict__ part, int nb, float* __restrict__ out) {
+  __shared__ float red[2][4];
+  float a = 0.f, b = 0.f;
+  for (int i = threadIdx.x; i < nb; i += 256) { a += part[2 * i]; b += part[2 * i + 1]; }
+  a = wave_sum(a); b = wave_sum(b);
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    out[0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+    out[1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
   }
 }
 struct Colsum4Plan { int CW, lanes, gy, nbx, rpb; };
@@ -553,10 +595,21 @@ static inline Colsum4Plan colsum4_plan(int64_t M, int ncol4) {
 }
 static inline size_t colsum4_part_bytes(int N) { return (size_t)1024 * N * sizeof(float); }
 // out[N] = column sums of x [M][N]; out16 != null: also the bf16 copy [M][cols_pad].  part: colsum4_part_bytes(N) of scratch.
+// star_s / star_sb (with z_gelu as the StarReLU pre-activation z): the StarReLU derivative instead of GELU's, and star_sb[0..1] = the
+// gradients of its s and b; star_part: 2 * colsum4_blocks floats.
+static inline int colsum4_blocks(int64_t M, int ncol4) { const Colsum4Plan g = colsum4_plan(M, ncol4); return g.nbx * g.gy; }
 static int colsum4(const float* x, float* out, int64_t M, int N, float* part, bf16_t* out16, int cols_pad, hipStream_t st,
-                   const float* z_gelu = nullptr) {
+                   const float* z_gelu = nullptr, const float* star_s = nullptr, float* star_sb = nullptr, float* star_part = nullptr) {
   const Colsum4Plan g = colsum4_plan(M, (out16 ? cols_pad : N) / 4);
   const size_t lds = (size_t)g.lanes * g.CW * 4 * sizeof(float);
+  if (out16 && z_gelu && star_s) {
+    hipLaunchKernelGGL((colsum4_kernel<true, false, true>), dim3(g.nbx, g.gy), dim3(256), lds, st, x, M, N, g.rpb, g.CW, g.lanes, part, out16,
+                       cols_pad, z_gelu, star_s, star_part);
+    HIP_CHECK_RET(hipGetLastError());
+    hipLaunchKernelGGL(star_pair_sum_kernel, dim3(1), dim3(256), 0, st, star_part, g.nbx * g.gy, star_sb);
+    HIP_CHECK_RET(hipGetLastError());
+    return out ? rows_sum(part, g.nbx, N, N, out, nullptr, st) : MMSKIN_OK;
+  }
   if (out16 && z_gelu) hipLaunchKernelGGL((colsum4_kernel<true, true>), dim3(g.nbx, g.gy), dim3(256), lds, st, x, M, N, g.rpb, g.CW, g.lanes, part, out16, cols_pad, z_gelu);
   else if (out16) hipLaunchKernelGGL(colsum4_kernel<true>, dim3(g.nbx, g.gy), dim3(256), lds, st, x, M, N, g.rpb, g.CW, g.lanes, part, out16, cols_pad);
   else hipLaunchKernelGGL(colsum4_kernel<false>, dim3(g.nbx, g.gy), dim3(256), lds, st, x, M, N, g.rpb, g.CW, g.lanes, part, out16, cols_pad);
@@ -593,7 +646,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_gb_kernel(const float* __re
   const int m_end = min(M, ((int)blockIdx.y + 1) * per);
   float sg = 0.f, sb = 0.f;
   if (n < N) {
-    const float gn = g[n], bn = b[n];
+    const float gn = g[n], bn = b ? b[n] : 0.f;
     for (int m = blockIdx.y * per + ry; m < m_end; m += 4) {
       float xh = (x[(int64_t)m * N + n] - mean[m]) * rstd[m];
       float d = dy[(int64_t)m * N + n];
@@ -660,7 +713,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_rows_kernel(const float* __
   for (int j = 0; j < NJ; ++j) {
     const int i = (j * LPR + sl) * 4;
     if (i >= N) continue;
-    const float4 gg = *reinterpret_cast<const float4*>(g + i), bb = *reinterpret_cast<const float4*>(b + i);
+    const float4 gg = *reinterpret_cast<const float4*>(g + i), bb = b ? *reinterpret_cast<const float4*>(b + i) : make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 o = make_float4((v[j].x - mu) * rs * gg.x + bb.x, (v[j].y - mu) * rs * gg.y + bb.y,
                                  (v[j].z - mu) * rs * gg.z + bb.z, (v[j].w - mu) * rs * gg.w + bb.w);
     if (y32) *reinterpret_cast<float4*>(y32 + (int64_t)row * N + i) = o;
@@ -1402,6 +1455,24 @@ __global__ void gelu_to_bf16_kernel(const float* __restrict__ z, bf16_t* __restr
     *reinterpret_cast<uint2*>(h16 + r * cols_pad + c) = o;
   }
 }
+// h16 = bf16(s relu(z)^2 + b) (timm StarReLU), zero pad columns: the operand of the MLP's second Linear
+__global__ void star_relu_to_bf16_kernel(const float* __restrict__ z, const float* __restrict__ sp, const float* __restrict__ bp,
+                                         bf16_t* __restrict__ h16, int64_t rows, int cols, int cols_pad) {
+  const int cpr = cols_pad / 4;
+  const float s = sp[0], b = bp[0];
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < rows * cpr; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / cpr;
+    const int c = (int)(i - r * cpr) * 4;
+    uint2 o = make_uint2(0u, 0u);
+    if (c < cols) {
+      const float4 v = *reinterpret_cast<const float4*>(z + r * cols + c);
+      const float rx = fmaxf(v.x, 0.f), ry = fmaxf(v.y, 0.f), rz = fmaxf(v.z, 0.f), rw = fmaxf(v.w, 0.f);
+      o = make_uint2(f32_to_bf16_bits(s * (rx * rx) + b) | (f32_to_bf16_bits(s * (ry * ry) + b) << 16),
+                     f32_to_bf16_bits(s * (rz * rz) + b) | (f32_to_bf16_bits(s * (rw * rw) + b) << 16));
+    }
+    *reinterpret_cast<uint2*>(h16 + r * cols_pad + c) = o;
+  }
+}
 __global__ void gelu_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, float* __restrict__ dx, int64_t n) {
   EW_LOOP(n) {
     const float v = x[i];
@@ -1509,6 +1580,15 @@ int mmskin_gelu_forward_bf16(const float* z, void* h16, int64_t rows, int cols, 
   HIP_CHECK_RET(hipGetLastError());
   return MMSKIN_OK;
 }
+int mmskin_star_relu_forward_bf16(const float* z, const float* s, const float* b, void* h16, int64_t rows, int cols, int cols_pad, void* stream) {
+  ARG_CHECK(z && s && b && h16 && rows > 0 && cols > 0 && cols % 4 == 0 && cols_pad % 4 == 0 && cols_pad >= cols, "star_relu_forward_bf16: bad argument");
+  const int64_t n = rows * (cols_pad / 4);
+  int64_t blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(star_relu_to_bf16_kernel, dim3((unsigned)(blocks > 1048576 ? 1048576 : blocks)), dim3(256), 0, ST(stream), z, s, b,
+                     reinterpret_cast<bf16_t*>(h16), rows, cols, cols_pad);
+  HIP_CHECK_RET(hipGetLastError());
+  return MMSKIN_OK;
+}
 int mmskin_linear_forward_keep(const float* x, const float* w, const float* b, const float* res, float* y, void* x16_keep, int M, int K,
                                int N, int relu, void* stream) {
   ARG_CHECK(x16_keep && mmskin_linear_x16_pitch(M, K, N) > 0, "linear_forward_keep: no bf16 operand copy for this shape / mode");
@@ -1594,13 +1674,15 @@ int mmskin_linear_lane(const void* x, int x_dtype, const void* w, int w_dtype, c
 }
 
 static int linear_backward_impl(const float* dy, const float* x, const float* w, const float* y_relu, const float* z_gelu, float* dy_scratch,
-                                float* dx, float* dw, float* db, int M, int K, int N, void* stream, const void* x16_kept = nullptr) {
+                                float* dx, float* dw, float* db, int M, int K, int N, void* stream, const void* x16_kept = nullptr,
+                                const float* star_s = nullptr, float* star_sb = nullptr) {
   ARG_CHECK(dy && M > 0 && K > 0 && N > 0, "linear_backward: bad argument");
   ARG_CHECK(!(y_relu && z_gelu), "linear_backward: one activation");
   hipStream_t st = ST(stream);
   const float* g = dy;
   const bool bf16_gemm = linear_bf16() && (linear_big_padded(M, K, N) || linear_big(M, K, N));
   ARG_CHECK(!x16_kept || bf16_gemm, "linear_backward: the kept bf16 operand belongs to the bf16 large-GEMM path (mode changed since the forward?)");
+  ARG_CHECK(!star_s || (bf16_gemm && z_gelu && star_sb), "linear_backward: StarReLU needs the bf16 large-GEMM path, z and the scalar gradients");
   if (z_gelu && !bf16_gemm) {   // no conversion pass to fold the GELU derivative into: its own pass
     ARG_CHECK(dy_scratch, "linear_backward: dy_scratch required with z_gelu");
     hipLaunchKernelGGL(gelu_bwd_kernel, dim3(grid1d((int64_t)M * N)), dim3(256), 0, st, dy, z_gelu, dy_scratch, (int64_t)M * N);
@@ -1619,12 +1701,14 @@ static int linear_backward_impl(const float* dy, const float* x, const float* w,
     ConvShape s = {M, 1, 1, Kp, Np, 1, 1, 1, 0};
     const size_t gb = align_up((size_t)M * Np * 2, 256), xb = align_up((size_t)M * Kp * 2, 256), wb = align_up((size_t)Np * Kp * 2, 256);
     const size_t slb = align_up(conv_wgrad_slab_bytes(s), 256);
-    unsigned char* sc = reinterpret_cast<unsigned char*>(head_scratch(gb + xb + wb + slb + colsum4_part_bytes(N)));
+    const size_t spb = star_s ? align_up((size_t)2 * colsum4_blocks(M, Np / 4) * sizeof(float), 256) : 0;
+    unsigned char* sc = reinterpret_cast<unsigned char*>(head_scratch(gb + xb + wb + slb + spb + colsum4_part_bytes(N)));
     if (!sc) { mmskin_set_error("linear_backward: scratch allocation failed"); return MMSKIN_ERR_HIP; }
     bf16_t* g16 = reinterpret_cast<bf16_t*>(sc); bf16_t* t16 = reinterpret_cast<bf16_t*>(sc + gb); bf16_t* w16 = reinterpret_cast<bf16_t*>(sc + gb + xb);
     float* slab = reinterpret_cast<float*>(sc + gb + xb + wb);
-    if (db || z_gelu) {   // bias gradient (and the GELU derivative) from the pass that converts dy
-      if ((rc = colsum4(g, db, M, N, reinterpret_cast<float*>(sc + gb + xb + wb + slb), g16, Np, st, z_gelu))) return rc;
+    if (db || z_gelu) {   // bias gradient (and the GELU / StarReLU derivative) from the pass that converts dy
+      if ((rc = colsum4(g, db, M, N, reinterpret_cast<float*>(sc + gb + xb + wb + slb + spb), g16, Np, st, z_gelu, star_s, star_sb,
+                        reinterpret_cast<float*>(sc + gb + xb + wb + slb)))) return rc;
       db = nullptr;
     } else if ((rc = cvt_to_bf16_pad(g, g16, M, N, M, Np, st))) return rc;
     if (dx) {
@@ -1648,12 +1732,14 @@ static int linear_backward_impl(const float* dy, const float* x, const float* w,
     ConvShape s = {M, 1, 1, K, N, 1, 1, 1, 0};
     const size_t gb = align_up((size_t)M * N * 2, 256), xb = align_up((size_t)M * K * 2, 256), wb = align_up((size_t)N * K * 2, 256);
     const size_t slb = align_up(conv_wgrad_slab_bytes(s), 256);
-    unsigned char* sc = reinterpret_cast<unsigned char*>(head_scratch(gb + xb + wb + slb + colsum4_part_bytes(N)));
+    const size_t spb = star_s ? align_up((size_t)2 * colsum4_blocks(M, N / 4) * sizeof(float), 256) : 0;
+    unsigned char* sc = reinterpret_cast<unsigned char*>(head_scratch(gb + xb + wb + slb + spb + colsum4_part_bytes(N)));
     if (!sc) { mmskin_set_error("linear_backward: scratch allocation failed"); return MMSKIN_ERR_HIP; }
     bf16_t* g16 = reinterpret_cast<bf16_t*>(sc); bf16_t* t16 = reinterpret_cast<bf16_t*>(sc + gb); bf16_t* w16 = reinterpret_cast<bf16_t*>(sc + gb + xb);
     float* slab = reinterpret_cast<float*>(sc + gb + xb + wb);
-    if (db || z_gelu) {   // bias gradient (and the GELU derivative) from the pass that converts dy
-      if ((rc = colsum4(g, db, M, N, reinterpret_cast<float*>(sc + gb + xb + wb + slb), g16, N, st, z_gelu))) return rc;
+    if (db || z_gelu) {   // bias gradient (and the GELU / StarReLU derivative) from the pass that converts dy
+      if ((rc = colsum4(g, db, M, N, reinterpret_cast<float*>(sc + gb + xb + wb + slb + spb), g16, N, st, z_gelu, star_s, star_sb,
+                        reinterpret_cast<float*>(sc + gb + xb + wb + slb)))) return rc;
       db = nullptr;
     } else if ((rc = cvt_to_bf16(g, g16, (int64_t)M * N, st))) return rc;
     if (dx) {
@@ -1735,9 +1821,18 @@ int mmskin_linear_backward_keep(const float* dy, const void* x16, const float* w
   return linear_backward_impl(dy, nullptr, w, y_relu, z_gelu, dy_scratch, dx, dw, db, M, K, N, stream, x16);
 }
 
+// Backward of h = StarReLU(x w^T) = s relu(z)^2 + b given dh, the kept bf16 operand and z [M][N]: 2 s relu(z) is applied inside the pass
+// that converts dh for the bf16 GEMMs, and the same pass leaves the gradients of s and b in dsb[0..1] (fixed-order block sums).
+int mmskin_linear_star_relu_backward_keep(const float* dh, const void* x16, const float* w, const float* z, const float* s, float* dsb,
+                                          float* dx, float* dw, float* db, int M, int K, int N, void* stream) {
+  ARG_CHECK(x16 && z && s && dsb, "linear_star_relu_backward_keep: x16, z, s and dsb required");
+  ARG_CHECK(N % 4 == 0, "linear_star_relu_backward_keep: N=%d (needs N %% 4 == 0)", N);
+  return linear_backward_impl(dh, nullptr, w, nullptr, z, nullptr, dx, dw, db, M, K, N, stream, x16, s, dsb);
+}
+
 int mmskin_layernorm_forward(const float* x, const float* g, const float* b, float* y, float* mean, float* rstd,
                              int M, int N, float eps, int relu, void* stream) {
-  ARG_CHECK(x && g && b && y && mean && rstd && M > 0 && N > 0, "layernorm_forward: bad argument");
+  ARG_CHECK(x && g && y && mean && rstd && M > 0 && N > 0, "layernorm_forward: bad argument");
   if (ln_rows_ok(N, relu)) {
 #define CALL(NJ, LPR) hipLaunchKernelGGL((layernorm_fwd_rows_kernel<NJ, LPR>), dim3(ceil_div(M, 4 * (64 / LPR))), dim3(256), 0, ST(stream), x, g, b, y, (bf16_t*)nullptr, mean, rstd, M, N, eps)
     LN_ROWS_DISPATCH(N, CALL);
@@ -1750,7 +1845,7 @@ int mmskin_layernorm_forward(const float* x, const float* g, const float* b, flo
 }
 int mmskin_layernorm_forward_mixed(const float* x, const float* g, const float* b, float* y_f32, void* y_bf16, int M, int N,
                                    float eps, void* stream) {
-  ARG_CHECK(x && g && b && (y_f32 || y_bf16) && M > 0 && N > 0, "layernorm_forward_mixed: bad argument");
+  ARG_CHECK(x && g && (y_f32 || y_bf16) && M > 0 && N > 0, "layernorm_forward_mixed: bad argument");
   ARG_CHECK(N % 4 == 0 && N <= 2048, "layernorm_forward_mixed: N=%d (needs N %% 4 == 0 and N <= 2048)", N);
 #define CALL(NJ, LPR) hipLaunchKernelGGL((layernorm_fwd_rows_kernel<NJ, LPR>), dim3(ceil_div(M, 4 * (64 / LPR))), dim3(256), 0, ST(stream), x, g, b, y_f32, reinterpret_cast<bf16_t*>(y_bf16), (float*)nullptr, (float*)nullptr, M, N, eps)
   LN_ROWS_DISPATCH(N, CALL);
@@ -1760,7 +1855,8 @@ int mmskin_layernorm_forward_mixed(const float* x, const float* g, const float* 
 }
 int mmskin_layernorm_backward(const float* dy, const float* x, const float* g, const float* b, const float* mean,
                               const float* rstd, float* dx, float* dg, float* db, int M, int N, int relu, void* stream) {
-  ARG_CHECK(dy && x && g && b && mean && rstd && M > 0 && N > 0, "layernorm_backward: bad argument");
+  ARG_CHECK(dy && x && g && mean && rstd && M > 0 && N > 0, "layernorm_backward: bad argument");
+  if (!b) db = nullptr;     // a LayerNorm without bias has no bias gradient
   if (ln_rows_ok(N, relu)) {
     // <= 1024 workgroups; every wave keeps >= 8 rows so its column sums amortise the slot it writes
     const int rpw = N <= 128 ? 2 : 1;
@@ -2063,6 +2159,48 @@ int mmskin_gelu_forward(const float* x, float* y, int64_t n, void* stream) { EW_
 int mmskin_gelu_tanh_forward(const float* x, float* y, int64_t n, void* stream) { EW_LAUNCH(gelu_tanh_fwd_kernel, n, x, y, n); }
 int mmskin_gelu_tanh_backward(const float* dy, const float* x, float* dx, int64_t n, void* stream) {
   EW_LAUNCH(gelu_tanh_bwd_kernel, n, dy, x, dx, n);
+}
+// StarReLU (timm metaformer.py): y = s relu(z)^2 + b with learnable scalars s, b (device pointers).  Backward: dz = dy 2 s relu(z) and
+// dsb[0..1] = (sum dy relu(z)^2, sum dy) -- per-block partials over a grid fixed by n, then one block adds them in a fixed order.
+__global__ void star_relu_fwd_kernel(const float* __restrict__ z, const float* __restrict__ sp, const float* __restrict__ bp,
+                                     float* __restrict__ y, int64_t n) {
+  const float s = sp[0], b = bp[0];
+  EW_LOOP(n) { const float r = fmaxf(z[i], 0.f); y[i] = s * (r * r) + b; }
+}
+constexpr int STAR_EW_BLOCKS = 1024;
+__global__ __launch_bounds__(256) void star_relu_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ z, const float* __restrict__ sp,
+                                                            float* __restrict__ dz, float* __restrict__ part, int64_t n) {
+  __shared__ float red[2][4];
+  const float s2 = 2.f * sp[0];
+  float as = 0.f, ab = 0.f;
+  EW_LOOP(n) {
+    const float g = dy[i], r = fmaxf(z[i], 0.f);
+    as += g * r * r; ab += g;
+    if (dz) dz[i] = g * s2 * r;
+  }
+  as = wave_sum(as); ab = wave_sum(ab);
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = as; red[1][threadIdx.x >> 6] = ab; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    part[2 * blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+    part[2 * blockIdx.x + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+  }
+}
+int mmskin_star_relu_forward(const float* z, const float* s, const float* b, float* y, int64_t n, void* stream) {
+  ARG_CHECK(z && s && b && y && n > 0, "star_relu_forward: bad argument");
+  EW_LAUNCH(star_relu_fwd_kernel, n, z, s, b, y, n);
+}
+int mmskin_star_relu_backward(const float* dy, const float* z, const float* s, float* dz, float* dsb, int64_t n, void* stream) {
+  ARG_CHECK(dy && z && s && dsb && n > 0, "star_relu_backward: bad argument");
+  int64_t nb = (n + 255) / 256;
+  if (nb > STAR_EW_BLOCKS) nb = STAR_EW_BLOCKS;
+  float* part = head_scratch((size_t)2 * nb * sizeof(float));
+  if (!part) { mmskin_set_error("star_relu_backward: scratch allocation failed"); return MMSKIN_ERR_HIP; }
+  hipLaunchKernelGGL(star_relu_bwd_kernel, dim3((unsigned)nb), dim3(256), 0, ST(stream), dy, z, s, dz, part, n);
+  HIP_CHECK_RET(hipGetLastError());
+  hipLaunchKernelGGL(star_pair_sum_kernel, dim3(1), dim3(256), 0, ST(stream), part, (int)nb, dsb);
+  HIP_CHECK_RET(hipGetLastError());
+  return MMSKIN_OK;
 }
 int mmskin_gelu_backward(const float* dy, const float* x, float* dx, int64_t n, void* stream) {
   EW_LAUNCH(gelu_bwd_kernel, n, dy, x, dx, n);

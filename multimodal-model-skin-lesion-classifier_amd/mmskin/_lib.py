@@ -141,6 +141,13 @@ _SIGNATURES = {
     "mmskin_metadata_encode": (_i, [_P, _i, _P, _i, _P, _i, _P, _P, _f, _P, _i, _P]),
     "mmskin_pool_gap_forward": (_i, [_P] * 3 + [_i] * 5 + [_P]),
     "mmskin_pool_gap_backward": (_i, [_P] * 3 + [_i] * 5 + [_P]),
+    "mmskin_star_relu_forward_bf16": (_i, [_P] * 4 + [_i64, _i, _i, _P]),
+    "mmskin_linear_star_relu_backward_keep": (_i, [_P] * 9 + [_i] * 3 + [_P]),
+    "mmskin_star_relu_forward": (_i, [_P] * 4 + [_i64, _P]),
+    "mmskin_star_relu_backward": (_i, [_P] * 5 + [_i64, _P]),
+    "mmskin_dw7_star_scratch_floats": (_i64, [_i] * 4),
+    "mmskin_dw7_star_forward": (_i, [_P] * 5 + [_i] * 4 + [_P]),
+    "mmskin_dw7_star_backward": (_i, [_P] * 9 + [_i] * 4 + [_P]),
 }
 
 

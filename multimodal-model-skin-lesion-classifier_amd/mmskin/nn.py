@@ -32,6 +32,23 @@ class HipLayerNorm(nn.LayerNorm):
         return ops.layernorm(x, self.weight, self.bias, self.eps, self.fuse_relu)
 
 
+class HipLayerNormNoBias(nn.Module):
+    """nn.LayerNorm over the last dim with a weight and no bias (timm LayerNormNoBias / LayerNorm2dNoBias applied to token rows):
+    registers `weight` only, so the state_dict has no `bias` key."""
+
+    def __init__(self, normalized_shape, eps=1e-5):
+        super().__init__()
+        self.normalized_shape = (normalized_shape,) if isinstance(normalized_shape, int) else tuple(normalized_shape)
+        self.eps = eps
+        self.weight = nn.Parameter(torch.ones(self.normalized_shape))
+
+    def forward(self, x):
+        return ops.layernorm(x, self.weight, None, self.eps)
+
+    def extra_repr(self):
+        return f"{self.normalized_shape}, eps={self.eps}, bias=False"
+
+
 class FusedAway(nn.Module):
     """Placeholder that keeps nn.Sequential indices (=> state_dict keys) identical to the reference
     where an activation was fused into the preceding HIP kernel."""

@@ -244,7 +244,7 @@ def linear(x, w, b=None, relu=False, out_dtype=None, residual=None):
 
 @no_second_order
 class LayerNormFn(torch.autograd.Function):
-    """nn.LayerNorm over the last dim, optional fused ReLU."""
+    """nn.LayerNorm over the last dim, optional fused ReLU; b may be None (a LayerNorm without bias: no bias gradient)."""
 
     @staticmethod
     def forward(ctx, x, g, b, eps, relu):
@@ -269,14 +269,14 @@ class LayerNormFn(torch.autograd.Function):
         dy2 = _f32c(dy).reshape(M, N)
         dx = torch.empty_like(x2) if ctx.needs_input_grad[0] else None
         dg = torch.empty_like(g) if ctx.needs_input_grad[1] else None
-        db = torch.empty_like(b) if ctx.needs_input_grad[2] else None
+        db = torch.empty_like(b) if b is not None and ctx.needs_input_grad[2] else None
         call("mmskin_layernorm_backward", ptr(dy2), ptr(x2), ptr(g), ptr(b), ptr(mean), ptr(rstd), ptr(dx), ptr(dg),
              ptr(db), M, N, int(ctx.relu), stream())
         return (dx.reshape(ctx.xshape) if dx is not None else None), dg, db, None, None
 
 
 def layernorm(x, g, b, eps=1e-5, relu=False, out_dtype=None, keep_f32=False):
-    """nn.LayerNorm.  out_dtype=torch.bfloat16 (inference lane): the result as a bf16 tensor -- and with keep_f32 also the fp32
+    """nn.LayerNorm (b=None: without bias).  out_dtype=torch.bfloat16 (inference lane): the result as a bf16 tensor -- and with keep_f32 also the fp32
     one (post-LN residual streams), returned as (fp32, bf16) -- from one pass over the row."""
     N = x.shape[-1]
     if out_dtype == torch.bfloat16 and not relu and N % 4 == 0 and N <= 2048 and not _needs_grad(x, g, b):
@@ -284,7 +284,7 @@ def layernorm(x, g, b, eps=1e-5, relu=False, out_dtype=None, keep_f32=False):
         x2 = _f32c(x).reshape(-1, N)
         y16 = torch.empty(x2.shape, device=x.device, dtype=torch.bfloat16)
         y32 = torch.empty_like(x2) if keep_f32 else None
-        call("mmskin_layernorm_forward_mixed", ptr(x2), ptr(_f32c(g)), ptr(_f32c(b)), ptr(y32), ptr(y16), x2.shape[0], N, float(eps), stream())
+        call("mmskin_layernorm_forward_mixed", ptr(x2), ptr(_f32c(g)), ptr(None if b is None else _f32c(b)), ptr(y32), ptr(y16), x2.shape[0], N, float(eps), stream())
         return (y32.reshape(x.shape), y16.reshape(x.shape)) if keep_f32 else y16.reshape(x.shape)
     y = LayerNormFn.apply(x, g, b, eps, relu)
     return (y, y) if keep_f32 else y
@@ -1183,9 +1183,12 @@ class MlpFn(torch.autograd.Function):
         return (dx.reshape(ctx.xshape) if dx is not None else None), dw1, db1, dw2, db2, dres, None, None
 
 
-def mlp(x, w1, b1, w2, b2, residual=None):
-    """[residual +] fc2(gelu(fc1(x))).  With gradients, fp32 tensors on the GPU and both Linears on the bf16-operand large-GEMM path:
-    MlpFn (no fp32 gelu(z), kept bf16 operands, residual added by the output pass); otherwise linear_gelu, linear and add."""
+def mlp(x, w1, b1, w2, b2, residual=None, star_relu=None):
+    """[residual +] fc2(act(fc1(x))), act = exact GELU (default) or, with star_relu=(scale, bias), timm's StarReLU
+    scale * relu(z)^2 + bias.  With gradients, fp32 tensors on the GPU and both Linears on the bf16-operand large-GEMM path:
+    MlpFn / StarMlpFn (no fp32 act(z), kept bf16 operands, residual added by the output pass); otherwise the separate ops."""
+    if star_relu is not None:
+        return _star_mlp(x, w1, b1, w2, b2, residual, *star_relu)
     if (_needs_grad(x, w1, b1, w2, b2) and x.is_cuda and x.dtype == torch.float32 and w1.dtype == torch.float32 and w2.dtype == torch.float32
             and w1.requires_grad and w2.requires_grad and (residual is None or residual.dtype == torch.float32)):
         M = x.numel() // x.shape[-1]
@@ -1195,6 +1198,132 @@ def mlp(x, w1, b1, w2, b2, residual=None):
         if p1 and p2:
             return MlpFn.apply(x, w1, b1, w2, b2, residual, p1, p2)
     return linear(linear_gelu(x, w1, b1), w2, b2, residual=residual)
+
+
+@no_second_order
+class StarMlpFn(torch.autograd.Function):
+    """[res +] fc2(s * relu(fc1(x))^2 + b) with gradients on the bf16-operand large-GEMM path (MlpFn with timm's StarReLU): the hidden
+    activation exists as the pre-activation z (fp32) and as the bf16 operand of fc2 only.  The backward of fc1 applies 2 s relu(z) in
+    the pass that converts dh and returns the gradients of s and b from the same pass."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, s, sb, res, p1, p2):
+        _need_gpu(x, "mlp")
+        x2 = _f32c(x).reshape(-1, x.shape[-1])
+        w1, w2, s, sb = _f32c(w1), _f32c(w2), _f32c(s), _f32c(sb)
+        M, K = x2.shape
+        Hd, N = w1.shape[0], w2.shape[0]
+        z = torch.empty((M, Hd), device=x.device, dtype=torch.float32)
+        x16 = torch.empty((M, p1), device=x.device, dtype=torch.bfloat16)
+        call("mmskin_linear_forward_keep", ptr(x2), ptr(w1), ptr(b1), None, ptr(z), ptr(x16), M, K, Hd, 0, stream())
+        h16 = torch.empty((M, p2), device=x.device, dtype=torch.bfloat16)
+        call("mmskin_star_relu_forward_bf16", ptr(z), ptr(s), ptr(sb), ptr(h16), M, Hd, p2, stream())
+        y = torch.empty((M, N), device=x.device, dtype=torch.float32)
+        r2 = _f32c(res).reshape(M, N) if res is not None else None
+        call("mmskin_linear_forward_x16", ptr(h16), ptr(w2), ptr(b2), ptr(r2), ptr(y), M, Hd, N, 0, stream())
+        ctx.save_for_backward(x16, w1, z, h16, w2, s)
+        ctx.dims = (M, K, Hd, N)
+        ctx.bias = (b1 is not None, b2 is not None)
+        ctx.xshape = x.shape
+        ctx.res_shape = None if res is None else res.shape
+        return y.reshape(*x.shape[:-1], N)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x16, w1, z, h16, w2, s = ctx.saved_tensors
+        M, K, Hd, N = ctx.dims
+        dy2 = _f32c(dy).reshape(M, N)
+        ng = ctx.needs_input_grad
+        dev = dy.device
+        dh = torch.empty((M, Hd), device=dev, dtype=torch.float32)
+        dw2 = torch.empty_like(w2) if ng[3] else None
+        db2 = torch.empty(N, device=dev, dtype=torch.float32) if ctx.bias[1] and ng[4] else None
+        call("mmskin_linear_backward_keep", ptr(dy2), ptr(h16), ptr(w2), None, None, None, ptr(dh), ptr(dw2), ptr(db2), M, Hd, N, stream())
+        dx = torch.empty((M, K), device=dev, dtype=torch.float32) if ng[0] else None
+        dw1 = torch.empty_like(w1) if ng[1] else None
+        db1 = torch.empty(Hd, device=dev, dtype=torch.float32) if ctx.bias[0] and ng[2] else None
+        dsb = torch.empty(2, device=dev, dtype=torch.float32)
+        call("mmskin_linear_star_relu_backward_keep", ptr(dh), ptr(x16), ptr(w1), ptr(z), ptr(s), ptr(dsb), ptr(dx), ptr(dw1), ptr(db1),
+             M, K, Hd, stream())
+        dres = dy2.reshape(ctx.res_shape) if ctx.res_shape is not None and ng[7] else None
+        ds = dsb[0:1].reshape(s.shape) if ng[5] else None
+        dsbias = dsb[1:2].reshape(s.shape) if ng[6] else None
+        return (dx.reshape(ctx.xshape) if dx is not None else None), dw1, db1, dw2, db2, ds, dsbias, dres, None, None
+
+
+@no_second_order
+class StarReluFn(torch.autograd.Function):
+    """timm StarReLU: s * relu(z)^2 + b, s and b one-element tensors; the backward returns their gradients from the pass that writes dz
+    (fixed-order reductions)."""
+
+    @staticmethod
+    def forward(ctx, z, s, b):
+        _need_gpu(z, "star_relu")
+        z, s, b = _f32c(z), _f32c(s), _f32c(b)
+        y = torch.empty_like(z)
+        call("mmskin_star_relu_forward", ptr(z), ptr(s), ptr(b), ptr(y), z.numel(), stream())
+        ctx.save_for_backward(z, s)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        z, s = ctx.saved_tensors
+        dy = _f32c(dy)
+        dz = torch.empty_like(z) if ctx.needs_input_grad[0] else None
+        dsb = torch.empty(2, device=dy.device, dtype=torch.float32)
+        call("mmskin_star_relu_backward", ptr(dy), ptr(z), ptr(s), ptr(dz), ptr(dsb), z.numel(), stream())
+        return dz, dsb[0:1].reshape(s.shape), dsb[1:2].reshape(s.shape)
+
+
+star_relu = StarReluFn.apply
+
+
+def _star_mlp(x, w1, b1, w2, b2, residual, s, sb):
+    if (_needs_grad(x, w1, b1, w2, b2, s, sb) and x.is_cuda and x.dtype == torch.float32 and w1.dtype == torch.float32
+            and w2.dtype == torch.float32 and w1.requires_grad and w2.requires_grad and w1.shape[0] % 4 == 0
+            and (residual is None or residual.dtype == torch.float32)):
+        M = x.numel() // x.shape[-1]
+        lib = _lib.load()
+        p1 = lib.mmskin_linear_x16_pitch(M, x.shape[-1], w1.shape[0])
+        p2 = lib.mmskin_linear_x16_pitch(M, w1.shape[0], w2.shape[0])
+        if p1 and p2:
+            return StarMlpFn.apply(x, w1, b1, w2, b2, s, sb, residual, p1, p2)
+    return linear(star_relu(linear(x, w1, b1), s, sb), w2, b2, residual=residual)
+
+
+@no_second_order
+class Dw7StarFn(torch.autograd.Function):
+    """CAFormer SepConv core on NHWC fp32: dwconv7x7(s * relu(z)^2 + b, w), z [N, H, W, C], w [C, 1, 7, 7] (stride 1, pad 3, no bias).
+    The StarReLU is applied as z is staged (act(z) is never written); the backward reads dy and z once for dz, dw and the gradients of
+    s and b (fixed-order reductions over per-workgroup partials in a scratch buffer)."""
+
+    @staticmethod
+    def forward(ctx, z, w, s, b):
+        _need_gpu(z, "dw7_star")
+        z, w, s, b = _f32c(z), _f32c(w), _f32c(s), _f32c(b)
+        N, H, W, C = z.shape
+        y = torch.empty_like(z)
+        call("mmskin_dw7_star_forward", ptr(z), ptr(w), ptr(s), ptr(b), ptr(y), N, H, W, C, stream())
+        ctx.save_for_backward(z, w, s, b)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        z, w, s, b = ctx.saved_tensors
+        N, H, W, C = z.shape
+        dy = _f32c(dy)
+        ng = ctx.needs_input_grad
+        scratch = torch.empty(_lib.load().mmskin_dw7_star_scratch_floats(N, H, W, C), device=dy.device, dtype=torch.float32)
+        dz = torch.empty_like(z) if ng[0] else None
+        dw = torch.empty_like(w) if ng[1] else None
+        dsb = torch.empty(2, device=dy.device, dtype=torch.float32) if ng[2] or ng[3] else None
+        call("mmskin_dw7_star_backward", ptr(dy), ptr(z), ptr(w), ptr(s), ptr(b), ptr(scratch), ptr(dz), ptr(dw), ptr(dsb), N, H, W, C, stream())
+        ds = dsb[0:1].reshape(s.shape) if ng[2] else None
+        db = dsb[1:2].reshape(b.shape) if ng[3] else None
+        return dz, dw, ds, db
+
+
+dw7_star = Dw7StarFn.apply
 
 
 def linear_gelu(x, w, b=None, out_dtype=None):

@@ -2,7 +2,8 @@
 
 Same static-method API, argument meaning, return values and error strings as the reference's
 ``loadModels``.  Image backbones with a gfx950 plan: ``custom-cnn``, ``resnet-18``, ``resnet-50``,
-``densenet169``, ``vgg16``, ``mobilenet-v2``, ``efficientnet-b0/b7``.
+``densenet169``, ``vgg16``, ``mobilenet-v2``, ``efficientnet-b0/b7``, and the timm encoders ``beitv2_*``, ``vit_*``,
+``davit_*`` and ``caformer_*``.
 Weights are randomly initialised (torchvision layout and init); pretrained checkpoints are loaded by
 the caller with ``load_state_dict`` -- there is no network access from this package.
 """
@@ -76,7 +77,7 @@ class loadModels:
                     p.requires_grad = True
             else:
                 loadModels.set_backbone_train_mode(model, backbone_train_mode)
-        elif cnn_model_name.startswith(("beitv2_", "vit_", "davit_")):
+        elif cnn_model_name.startswith(("beitv2_", "vit_", "davit_", "caformer_")):
             # the reference's generic timm branch (:117-152): create_model(name) + reset_classifier(0), F = num_features,
             # "partial" unfreezes the last block
             if cnn_model_name.startswith("beitv2_"):
@@ -85,6 +86,9 @@ class loadModels:
             elif cnn_model_name.startswith("davit_"):
                 from hip_davit import HipDaVit
                 model = HipDaVit(cnn_model_name)
+            elif cnn_model_name.startswith("caformer_"):
+                from hip_caformer import HipCAFormer
+                model = HipCAFormer(cnn_model_name)
             else:
                 from hip_vit import HipVisionTransformer
                 model = HipVisionTransformer(cnn_model_name)
