@@ -19,17 +19,6 @@ void mmskin_set_error(const char* fmt, ...) {
 
 namespace {
 
-struct Carver {
-  unsigned char* base;
-  size_t cur = 0;
-  explicit Carver(void* p) : base((unsigned char*)p) {}
-  template <typename U> U* take(size_t count) {
-    size_t o = cur;
-    cur = align_up(cur + count * sizeof(U), 256);
-    return reinterpret_cast<U*>(base + o);
-  }
-};
-
 __global__ void coef_from_saved_kernel(int C, const float* gamma, const float* beta, const float* mean,
                                        const float* invstd, float* scale, float* shift) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;

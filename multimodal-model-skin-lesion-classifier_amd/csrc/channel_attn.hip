@@ -26,8 +26,6 @@
 
 #include "common.h"
 
-#define ST(s) ((hipStream_t)(s))
-
 namespace {
 
 typedef float f32x16_t __attribute__((ext_vector_type(16)));

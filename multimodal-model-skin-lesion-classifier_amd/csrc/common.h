@@ -183,8 +183,35 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
 }
 
+// 64-lane wavefront reductions: every lane ends with the result
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+static inline int pad64(int c) { return (c + 63) / 64 * 64; }   // channel count / Linear width padded for the GEMM kernels
+#define ST(s) ((hipStream_t)(s))   // the C ABI carries streams as void*
+
+// Hands out consecutive regions of one buffer, each starting on a 256-byte boundary; `cur` is the byte count taken so far.  Run on a
+// null base it only sizes the layout, so the function that carves a workspace also answers how large it must be.
+struct Carver {
+  unsigned char* base;
+  size_t cur = 0;
+  explicit Carver(void* p) : base((unsigned char*)p) {}
+  template <typename U> U* take(size_t count) {
+    size_t o = cur;
+    cur = align_up(cur + count * sizeof(U), 256);
+    return reinterpret_cast<U*>(base + o);
+  }
+};
 
 // Integer value of the environment variable `name`, or `dflt` when it is unset.  The one way the library reads its
 // configuration variables (INTEGRATION.md section 1 lists them); callers cache the result in a function-local static.

@@ -16,8 +16,6 @@
 #include "../../include/mmskin.h"
 #include "common.h"
 
-#define ST(s) ((hipStream_t)(s))
-
 namespace {
 
 constexpr int TH = 8, TW = 16;                  // output tile
@@ -65,12 +63,6 @@ __device__ __forceinline__ void stage(const float* __restrict__ src, int n, int 
     }
     *reinterpret_cast<float4*>(lds + p * CC + q * 4) = v;
   }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 __global__ __launch_bounds__(256) void dw7_star_fwd_kernel(const float* __restrict__ z, const float* __restrict__ w, const float* __restrict__ sp,

@@ -184,8 +184,6 @@ static inline BNRef add_bn(PlanBase& p, const std::string& name, int C) {
   return r;
 }
 
-static inline int pad64(int c) { return (c + 63) / 64 * 64; }   // channel count padded for the GEMM kernels
-
 static inline size_t carve(size_t& cursor, size_t bytes) {
   size_t o = cursor;
   cursor = align_up(cursor + bytes, 256);

@@ -1124,7 +1124,7 @@ class LinearGeluFn(torch.autograd.Function):
         dx = torch.empty((M, K), device=dh.device, dtype=torch.float32) if need_x else None
         dw = torch.empty_like(w) if need_w else None
         db = torch.empty(N, device=dh.device, dtype=torch.float32) if need_b else None
-        # off the bf16-operand large-GEMM path (head.hip: linear_big / linear_big_padded) the C side applies gelu'(z) in a pass of its own
+        # off the bf16-operand large-GEMM path (linear.hip: linear_path) the C side applies gelu'(z) in a pass of its own
         # (mmskin_linear_x16_pitch(M, K, N) > 0 IS that predicate, asked of the library instead of re-derived here: ADVICE r03)
         fused = _lib.load().mmskin_linear_x16_pitch(M, K, N) > 0
         scratch = None if fused else torch.empty_like(dh2)

@@ -6,8 +6,8 @@ Same module tree as transformers' `BertModel` (embeddings.{word,position,token_t
 encoder.layer.N.attention.self.{query,key,value}, attention.output.{dense,LayerNorm}, intermediate.dense,
 output.{dense,LayerNorm}, pooler.dense), so a HuggingFace state_dict loads with strict=True.  Weights are randomly
 initialised (normal(0, 0.02), as HF); this package never downloads.  Arithmetic: Linear layers on the exact-f32
-implicit-GEMM kernels (batch x tokens rows), attention through strided batched GEMMs + a row-softmax kernel, LayerNorm /
-GELU / dropout / embedding kernels from head.hip.
+implicit-GEMM kernels (batch x tokens rows, linear.hip), attention through strided batched GEMMs (linear.hip) + a row-softmax
+kernel, LayerNorm / GELU / dropout / embedding kernels from head.hip.
 """
 import os
 import sys

@@ -2,7 +2,7 @@
 to the fp32 oracle models: the yardstick the bf16 gradient-parity tests hold the HIP path against, exactly as
 tests/test_gpu_model.py holds the bf16 ResNet step against a bf16-storage emulation.
 
-What the HIP path rounds in that mode (csrc/head.hip, mmskin_linear_forward / _backward): a Linear over >= 2048 rows whose widths are
+What the HIP path rounds in that mode (csrc/linear.hip, mmskin_linear_forward / _backward): a Linear over >= 2048 rows whose widths are
 multiples of 8 (>= 32) runs on the bf16 MFMA GEMM kernels -- forward  y = bf16(x) bf16(W)^T + b  with fp32 accumulation and an fp32
 result (rounded to bf16 before the bias when a width is not a multiple of 64: the zero-padded operand path); backward  dx = bf16( bf16(dy) bf16(W) ),  dW = bf16(dy)^T bf16(x)  (fp32 result),  db = sum dy (fp32).  Patch-embedding
 convolutions (kernel = stride, no padding) are that Linear on im2col columns.  Everything else -- LayerNorm, softmax attention with
