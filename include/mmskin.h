@@ -386,6 +386,29 @@ int mmskin_dw7_star_forward(const float* z, const float* w, const float* s, cons
                             void* stream);
 int mmskin_dw7_star_backward(const float* dy, const float* z, const float* w, const float* s, const float* b, float* scratch, float* dz,
                              float* dw, float* dsb, int N, int H, int W, int C, void* stream);
+/* CoaT factorized attention with convolutional relative position encoding (timm coat.py FactorAttnConvRelPosEnc.forward with its
+ * ConvRelPosEnc) on the token-major packed output of a fused qkv Linear, fp32: qkv [B, N, 3, 8, Ch], N = 1 + H * W (token 0 = class token),
+ * Ch in {8, 16, 32, 40, 64} -> att [B, N, 8 * Ch]:  att = Ch^-0.5 * q (softmax_N(k)^T v) + q_img . (dwconv(v_img) + bias), heads 0-1 through
+ * w3 [2Ch, 1, 3, 3], heads 2-4 through w5 [3Ch, 1, 5, 5], heads 5-7 through w7 [3Ch, 1, 7, 7] ("same" padding); the class row gets no
+ * convolution term.  The forward also writes F [B * 8, Ch, Ch] = softmax(k)^T v and stats [B * 8, 2, Ch] (column maximum and exp-sum of k)
+ * for the backward, which writes d(qkv) in the packed layout and the six convolution gradients (every element written).  All reductions run
+ * in a fixed order (bitwise repeatable).  scratch: mmskin_factor_attention_scratch_floats(B, H, W, Ch, backward) floats. */
+int64_t mmskin_factor_attention_scratch_floats(int B, int H, int W, int Ch, int backward);
+int mmskin_factor_attention_forward(const float* qkv, const float* w3, const float* b3, const float* w5, const float* b5, const float* w7,
+                                    const float* b7, float* att, float* F, float* stats, float* scratch, int B, int H, int W, int Ch,
+                                    void* stream);
+int mmskin_factor_attention_backward(const float* dO, const float* qkv, const float* w3, const float* b3, const float* w5, const float* b5,
+                                     const float* w7, const float* b7, const float* F, const float* stats, float* dqkv, float* dw3,
+                                     float* db3, float* dw5, float* db5, float* dw7, float* db7, float* scratch, int B, int H, int W,
+                                     int Ch, void* stream);
+/* CoaT's convolutional position encoding (timm coat.py ConvPosEnc.forward) on a token tensor with a class token, fp32 x [B, 1 + H * W, C]:
+ * the class row passes through, image rows y = x + dwconv3(x, w) + b on the H x W grid (w [C, 1, 3, 3]) -- no slice / concat copies.
+ * backward: dx = dy + dgrad(dy) on the image rows, dy on the class row; dw, db (each may be NULL) through
+ * mmskin_conv_pos_enc_tokens_scratch_floats(B, H, W, C) floats of scratch, summed in a fixed order. */
+int64_t mmskin_conv_pos_enc_tokens_scratch_floats(int B, int H, int W, int C);
+int mmskin_conv_pos_enc_tokens_forward(const float* x, const float* w, const float* b, float* y, int B, int H, int W, int C, void* stream);
+int mmskin_conv_pos_enc_tokens_backward(const float* dy, const float* x, const float* w, float* scratch, float* dx, float* dw, float* db, int B,
+                                        int H, int W, int C, void* stream);
 /* embedding gather for categorical metadata columns: table [ncols, card, E]; ids [B, ncols] int64 */
 int mmskin_embedding_forward(const float* table, const int64_t* ids, float* out, int B, int ncols, int card, int E,
                              void* stream);

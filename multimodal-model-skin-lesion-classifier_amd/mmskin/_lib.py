@@ -109,6 +109,12 @@ _SIGNATURES = {
     "mmskin_dwconv3_backward": (_i, [_P] * 7 + [_i] * 4 + [_P]),
     "mmskin_conv_pos_enc_forward": (_i, [_P] * 5 + [_i] * 4 + [_P]),
     "mmskin_conv_pos_enc_backward": (_i, [_P] * 8 + [_i] * 4 + [_P]),
+    "mmskin_factor_attention_scratch_floats": (_i64, [_i] * 5),
+    "mmskin_factor_attention_forward": (_i, [_P] * 11 + [_i] * 4 + [_P]),
+    "mmskin_factor_attention_backward": (_i, [_P] * 18 + [_i] * 4 + [_P]),
+    "mmskin_conv_pos_enc_tokens_scratch_floats": (_i64, [_i] * 4),
+    "mmskin_conv_pos_enc_tokens_forward": (_i, [_P] * 4 + [_i] * 4 + [_P]),
+    "mmskin_conv_pos_enc_tokens_backward": (_i, [_P] * 7 + [_i] * 4 + [_P]),
     "mmskin_scale_add_forward": (_i, [_P] * 4 + [_i64, _i, _P]),
     "mmskin_scale_mul": (_i, [_P] * 3 + [_i64, _i, _i, _P]),
     "mmskin_token_mean_forward": (_i, [_P, _P, _i, _i, _i, _i, _P]),

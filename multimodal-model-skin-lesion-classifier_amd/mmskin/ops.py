@@ -1061,6 +1061,100 @@ conv_pos_enc = ConvPosEncFn.apply
 
 
 @no_second_order
+class ConvPosEncTokensFn(torch.autograd.Function):
+    """timm coat.py ConvPosEnc.forward on a token tensor with a class token, fp32 x [B, 1 + H * W, C]: the class row passes through, the
+    image rows get x + dwconv3(x, w) + b on the H x W grid -- one kernel, no slice / concat copies; dw and db from one pass over dy."""
+
+    @staticmethod
+    def forward(ctx, x, H, W, w, b):
+        _need_gpu(x, "conv_pos_enc_tokens")
+        x, w, b = _f32c(x), _f32c(w), _f32c(b)
+        B, N, C = x.shape
+        if N != 1 + H * W:
+            raise _lib.MMSkinError(f"mmskin.conv_pos_enc_tokens: {N} tokens are not 1 + {H} * {W}")
+        y = torch.empty_like(x)
+        call("mmskin_conv_pos_enc_tokens_forward", ptr(x), ptr(w), ptr(b), ptr(y), B, H, W, C, stream())
+        ctx.save_for_backward(x, w)
+        ctx.hw = (int(H), int(W))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        B, N, C = x.shape
+        H, W = ctx.hw
+        dy = _f32c(dy)
+        need_w = ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dw = torch.empty_like(w) if ctx.needs_input_grad[3] else None
+        db = torch.empty(C, device=x.device, dtype=torch.float32) if ctx.needs_input_grad[4] else None
+        scratch = None
+        if need_w:
+            scratch = torch.empty(_lib.load().mmskin_conv_pos_enc_tokens_scratch_floats(B, H, W, C), device=x.device, dtype=torch.float32)
+        call("mmskin_conv_pos_enc_tokens_backward", ptr(dy), ptr(x), ptr(w), ptr(scratch), ptr(dx), ptr(dw), ptr(db), B, H, W, C, stream())
+        return dx, None, None, dw, db
+
+
+def conv_pos_enc_tokens(x, H, W, w, b):
+    return ConvPosEncTokensFn.apply(x, H, W, w, b)
+
+
+FACTOR_ATTENTION_WIDTHS = (8, 16, 32, 40, 64)
+
+
+@no_second_order
+class FactorAttentionFn(torch.autograd.Function):
+    """CoaT factorized attention with convolutional relative position encoding (timm coat.py FactorAttnConvRelPosEnc.forward) on the packed
+    qkv of a fused Linear, qkv [B, 1 + H * W, 3, 8, Ch] -> [B, 1 + H * W, 8 * Ch] (token-major, what the output projection reads):
+    Ch^-0.5 * q (softmax_tokens(k)^T v) + q_img * (dwconv(v_img) + bias) with the 3x3 / 5x5 / 7x7 windows on heads 0-1 / 2-4 / 5-7.
+    No permute / contiguous copies; the backward writes d(qkv) in the packed layout and recomputes the softmax and the convolution."""
+
+    @staticmethod
+    def forward(ctx, qkv, H, W, w3, w5, w7, b3, b5, b7):
+        _need_gpu(qkv, "factor_attention")
+        qkv = _f32c(qkv)
+        B, N, three, heads, Ch = qkv.shape
+        if three != 3 or heads != 8 or Ch not in FACTOR_ATTENTION_WIDTHS or N != 1 + H * W:
+            raise _lib.MMSkinError(f"mmskin.factor_attention: qkv {tuple(qkv.shape)} is not [B, 1 + {H} * {W}, 3, 8, Ch in {FACTOR_ATTENTION_WIDTHS}]")
+        ws = [_f32c(t) for t in (w3, b3, w5, b5, w7, b7)]
+        for t, k, n in zip(ws[0::2], (3, 5, 7), (2, 3, 3)):
+            if tuple(t.shape) != (n * Ch, 1, k, k):
+                raise _lib.MMSkinError(f"mmskin.factor_attention: window-{k} weight {tuple(t.shape)}, expected {(n * Ch, 1, k, k)}")
+        for t, n in zip(ws[1::2], (2, 3, 3)):
+            if tuple(t.shape) != (n * Ch,):
+                raise _lib.MMSkinError(f"mmskin.factor_attention: bias {tuple(t.shape)}, expected {(n * Ch,)}")
+        att = torch.empty((B, N, 8 * Ch), device=qkv.device, dtype=torch.float32)
+        F = torch.empty((B * 8, Ch, Ch), device=qkv.device, dtype=torch.float32)
+        stats = torch.empty((B * 8, 2, Ch), device=qkv.device, dtype=torch.float32)
+        scratch = torch.empty(_lib.load().mmskin_factor_attention_scratch_floats(B, H, W, Ch, 0), device=qkv.device, dtype=torch.float32)
+        call("mmskin_factor_attention_forward", ptr(qkv), *[ptr(t) for t in ws], ptr(att), ptr(F), ptr(stats), ptr(scratch), B, H, W, Ch, stream())
+        ctx.save_for_backward(qkv, F, stats, *ws)
+        ctx.hw = (int(H), int(W))
+        return att
+
+    @staticmethod
+    def backward(ctx, dO):
+        qkv, F, stats, *ws = ctx.saved_tensors
+        B, N, three, heads, Ch = qkv.shape
+        H, W = ctx.hw
+        dO = _f32c(dO)
+        dqkv = torch.empty_like(qkv)
+        dws = [torch.empty_like(t) for t in ws]
+        scratch = torch.empty(_lib.load().mmskin_factor_attention_scratch_floats(B, H, W, Ch, 1), device=qkv.device, dtype=torch.float32)
+        call("mmskin_factor_attention_backward", ptr(dO), ptr(qkv), *[ptr(t) for t in ws], ptr(F), ptr(stats), ptr(dqkv), *[ptr(t) for t in dws],
+             ptr(scratch), B, H, W, Ch, stream())
+        dw3, db3, dw5, db5, dw7, db7 = dws
+        return dqkv, None, None, dw3, dw5, dw7, db3, db5, db7
+
+
+def factor_attention(qkv, H, W, crpe_weights, crpe_biases):
+    """qkv [B, 1 + H * W, 3, 8, Ch]; crpe_weights / crpe_biases: the three conv_list weights (window 3, 5, 7) and biases."""
+    w3, w5, w7 = crpe_weights
+    b3, b5, b7 = crpe_biases
+    return FactorAttentionFn.apply(qkv, H, W, w3, w5, w7, b3, b5, b7)
+
+
+@no_second_order
 class GeluFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
