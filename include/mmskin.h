@@ -188,6 +188,15 @@ int mmskin_linear_gelu_backward(const float* dh, const float* x, const float* w,
  * output of a fused ReLU or pre-activation of a following GELU, at most one, as in mmskin_linear_backward / _gelu_backward).
  * Same arithmetic as mmskin_linear_forward / _backward: the kept copy is the tensor the scratch conversion would have produced. */
 int mmskin_linear_x16_pitch(int M, int K, int N);
+/* Which GEMM route a Linear of M rows, K inputs and N outputs takes in the current operand mode (mmskin_set_linear_dtype), forward and
+ * backward alike; -1 for a non-positive dimension.  Tests assert it so that a case keeps covering the route it was written for:
+ *   MMSKIN_LINEAR_SMALL        the strided exact-f32 MFMA GEMM of linear.hip (any shape; M < 2048 or a width off the classes below)
+ *   MMSKIN_LINEAR_BIG_F32      fp32 mode, M >= 2048, K and N multiples of 64: the exact-f32 implicit-GEMM conv kernels as a 1x1 conv
+ *   MMSKIN_LINEAR_BIG_BF16     bf16 mode, same shape class: bf16 operands, fp32 accumulation
+ *   MMSKIN_LINEAR_PADDED_BF16  bf16 mode, M >= 2048, K and N multiples of 8 and >= 32, not both multiples of 64: bf16 operands
+ *                              zero-padded to 64-multiple widths */
+enum { MMSKIN_LINEAR_SMALL = 0, MMSKIN_LINEAR_BIG_F32 = 1, MMSKIN_LINEAR_BIG_BF16 = 2, MMSKIN_LINEAR_PADDED_BF16 = 3 };
+int mmskin_linear_route(int M, int K, int N);
 int mmskin_linear_forward_keep(const float* x, const float* w, const float* b, const float* res, float* y, void* x16_keep, int M, int K,
                                int N, int relu, void* stream);   /* res (optional, fp32 [M][N]): y = res + act(x w^T + b) */
 int mmskin_linear_backward_keep(const float* dy, const void* x16, const float* w, const float* y_relu, const float* z_gelu, float* dy_scratch,

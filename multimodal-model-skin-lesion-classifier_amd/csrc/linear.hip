@@ -226,19 +226,26 @@ static inline bool linear_bf16() {
   if (g_linear_dtype < 0) { const char* e = getenv("MMSKIN_LINEAR_DTYPE"); g_linear_dtype = (e && !strcmp(e, "bf16")) ? 1 : 0; }
   return g_linear_dtype == 1;
 }
-__global__ void f32_to_bf16_kernel(const float* __restrict__ in, bf16_t* __restrict__ out, int64_t n4) {
+// n elements: n / 4 four-element chunks, then the n % 4 elements behind them one by one (block 0); nothing at or past n is touched
+__global__ void f32_to_bf16_kernel(const float* __restrict__ in, bf16_t* __restrict__ out, int64_t n) {
+  const int64_t n4 = n / 4;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
     const float4 v = reinterpret_cast<const float4*>(in)[i];
     reinterpret_cast<uint2*>(out)[i] = make_uint2(f32_to_bf16_bits(v.x) | (f32_to_bf16_bits(v.y) << 16),
                                                   f32_to_bf16_bits(v.z) | (f32_to_bf16_bits(v.w) << 16));
   }
+  const int64_t t = 4 * n4 + threadIdx.x;
+  if (blockIdx.x == 0 && t < n) out[t] = (bf16_t)f32_to_bf16_bits(in[t]);
 }
-__global__ void bf16_to_f32_kernel(const bf16_t* __restrict__ in, float* __restrict__ out, int64_t n4) {
+__global__ void bf16_to_f32_kernel(const bf16_t* __restrict__ in, float* __restrict__ out, int64_t n) {
+  const int64_t n4 = n / 4;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
     const uint2 v = reinterpret_cast<const uint2*>(in)[i];
     reinterpret_cast<float4*>(out)[i] = make_float4(bf16_bits_to_f32(v.x & 0xffffu), bf16_bits_to_f32(v.x >> 16),
                                                     bf16_bits_to_f32(v.y & 0xffffu), bf16_bits_to_f32(v.y >> 16));
   }
+  const int64_t t = 4 * n4 + threadIdx.x;
+  if (blockIdx.x == 0 && t < n) out[t] = bf16_bits_to_f32(in[t]);
 }
 // out[k][n] (bf16) = in[n][k] (fp32)
 __global__ void transpose_f32_to_bf16_kernel(const float* __restrict__ in, bf16_t* __restrict__ out, int rows, int cols) {
@@ -261,8 +268,9 @@ __global__ void transpose_f32_to_bf16_kernel(const float* __restrict__ in, bf16_
     HIP_CHECK_RET(hipGetLastError());                                                            \
     return MMSKIN_OK;                                                                            \
   } while (0)
-static int cvt_to_bf16(const float* in, bf16_t* out, int64_t n, hipStream_t st) { WIDE_LAUNCH(f32_to_bf16_kernel, n / 4, in, out, n / 4); }
-static int cvt_to_f32(const bf16_t* in, float* out, int64_t n, hipStream_t st) { WIDE_LAUNCH(bf16_to_f32_kernel, n / 4, in, out, n / 4); }
+// flat conversions of n > 0 elements (any n: the kernels finish the n % 4 tail; n < 4 is still one block)
+static int cvt_to_bf16(const float* in, bf16_t* out, int64_t n, hipStream_t st) { WIDE_LAUNCH(f32_to_bf16_kernel, (n + 3) / 4, in, out, n); }
+static int cvt_to_f32(const bf16_t* in, float* out, int64_t n, hipStream_t st) { WIDE_LAUNCH(bf16_to_f32_kernel, (n + 3) / 4, in, out, n); }
 
 // ---- Linear layers whose widths are not multiples of 64 (DaViT's 96 / 288-wide first stage over 200 704 tokens) on the bf16 GEMM
 // kernels: operands are converted into zero-padded bf16 copies (the conversion pass exists anyway), the GEMM runs on the padded
@@ -842,6 +850,12 @@ int mmskin_linear_forward(const float* x, const float* w, const float* b, float*
 }
 // Row pitch (elements) of the bf16 operand copy the current mode's large-GEMM path makes of an [M][K] input, 0 when this shape / mode
 // does not take that path (then there is nothing to keep).
+// The route linear_path gives M x K x N in the current mode (MMSKIN_LINEAR_* in mmskin.h mirror LinearPath), -1 on a bad shape
+int mmskin_linear_route(int M, int K, int N) {
+  static_assert(LIN_SMALL == MMSKIN_LINEAR_SMALL && LIN_BIG_F32 == MMSKIN_LINEAR_BIG_F32 && LIN_BIG_BF16 == MMSKIN_LINEAR_BIG_BF16 &&
+                LIN_PADDED_BF16 == MMSKIN_LINEAR_PADDED_BF16, "mmskin.h documents the LinearPath values");
+  return (M > 0 && K > 0 && N > 0) ? (int)linear_path(M, K, N) : -1;
+}
 int mmskin_linear_x16_pitch(int M, int K, int N) {
   const LinearPath path = (M > 0 && K > 0 && N > 0) ? linear_path(M, K, N) : LIN_SMALL;
   return path == LIN_PADDED_BF16 ? pad64(K) : path == LIN_BIG_BF16 ? K : 0;

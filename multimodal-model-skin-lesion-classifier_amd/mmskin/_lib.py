@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(os.path.dirname(_HERE), "libmmskin_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "mmskin.h")
 
 F32, BF16 = 0, 1
+LINEAR_SMALL, LINEAR_BIG_F32, LINEAR_BIG_BF16, LINEAR_PADDED_BF16 = 0, 1, 2, 3   # mmskin_linear_route (MMSKIN_LINEAR_* in mmskin.h)
 
 _lib = None
 
@@ -80,6 +81,7 @@ _SIGNATURES = {
     "mmskin_linear_backward": (_i, [_P] * 8 + [_i] * 3 + [_P]),
     "mmskin_linear_gelu_backward": (_i, [_P] * 8 + [_i] * 3 + [_P]),
     "mmskin_linear_x16_pitch": (_i, [_i, _i, _i]),
+    "mmskin_linear_route": (_i, [_i, _i, _i]),
     "mmskin_linear_forward_keep": (_i, [_P] * 6 + [_i] * 4 + [_P]),
     "mmskin_linear_backward_keep": (_i, [_P] * 9 + [_i] * 3 + [_P]),
     "mmskin_gelu_forward_bf16": (_i, [_P, _P, _i64, _i, _i, _P]),
