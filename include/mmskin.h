@@ -448,6 +448,56 @@ int mmskin_metadata_encode(const int32_t* codes, int n_cat, const int32_t* col_o
                            int n_num, const float* mean, const float* scale, float nan_fill, float* out, int batch, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Training-time image augmentation (skinLesionDatasets.py:74-113, the A.Compose of the train transform) as ONE fused kernel
+ * on the raw uint8 NHWC batch: Rotate(limit 45, BORDER_REFLECT) -> HorizontalFlip -> VerticalFlip -> GaussianBlur ->
+ * CoarseDropout(fill 0) -> HueSaturationValue -> RandomBrightnessContrast(brightness_by_max), each stage skipped per sample
+ * when its flag is off; Normalize + ToTensor then run inside mmskin_backbone_forward_u8.  The random draws happen on the host
+ * (mmskin.preprocess.TrainAugment.sample); the kernel is a pure function of (src, table).  One record per sample, 160 bytes:
+ *   minv[6]    float64  the INVERTED 2x3 matrix warpAffine uses, row major: src_x = minv[0]*x + minv[1]*y + minv[2],
+ *                       src_y = minv[3]*x + minv[4]*y + minv[5] (getRotationMatrix2D about (W/2-0.5, H/2-0.5), inverted in
+ *                       float64 on the host); read only when MMSKIN_AUG_ROTATE is set
+ *   flags      uint32   MMSKIN_AUG_* bits, one per stage
+ *   ksize      int32    GaussianBlur kernel size: 1 (no blur), 3, 5 or 7
+ *   taps[4]    uint16   8-bit fixed-point Gaussian taps, taps[j] = weight at distance j from the centre (0 beyond ksize/2);
+ *                       taps[0] + 2*(taps[1] + taps[2] + taps[3]) = 256
+ *   hue, sat, val int32 floor() of the HueSaturationValue shifts: hue in [0, 180) (already reduced mod 180), sat / val in
+ *                       [-255, 255]; H -> (H + hue) mod 180, S / V -> clip(x + shift, 0, 255)
+ *   alpha, beta255 float32  RandomBrightnessContrast LUT: clip(float32(i) * alpha + beta255, 0, 255) truncated,
+ *                       beta255 = float32(beta * 255); the multiply and the add each round to float32
+ *   n_holes    int32    0..MMSKIN_AUG_MAX_HOLES CoarseDropout rectangles in use
+ *   holes[8][4] int16   x1, y1, x2, y2 (half open, clipped to the image by the kernel), set to 0
+ *   reserved[2] uint32  zero
+ * Rotate is warpAffine's 8-bit INTER_LINEAR path (10-bit fixed-point row / column terms rounded to the 1/32 grid, 15-bit
+ * weights summing to 32768, (sum + 2^14) >> 15); the flips evaluate that same formula at the flipped destination index;
+ * GaussianBlur is separable with BORDER_REFLECT_101 and rounds half up once, after the vertical pass.
+ * params_host is the table, N records in host memory: the call validates it (ksize, n_holes, taps, hue) and then uploads
+ * exactly those bytes on `stream` into params_scratch, N records of device memory that the caller only provides (its
+ * previous content is ignored; it must stay allocated until the kernel has run, in stream order).  The host table may be
+ * reused as soon as the call returns.  Errors: H or W < 1 (or > 16384), N < 1 (or > 65535), ksize outside {1, 3, 5, 7}, n_holes outside
+ * 0..MMSKIN_AUG_MAX_HOLES, taps that do not sum to 256, src == dst. */
+#define MMSKIN_AUG_ROTATE 1u
+#define MMSKIN_AUG_HFLIP 2u
+#define MMSKIN_AUG_VFLIP 4u
+#define MMSKIN_AUG_BLUR 8u
+#define MMSKIN_AUG_DROPOUT 16u
+#define MMSKIN_AUG_HSV 32u
+#define MMSKIN_AUG_BC 64u
+#define MMSKIN_AUG_MAX_HOLES 8
+typedef struct mmskin_augment_params {
+  double minv[6];
+  uint32_t flags;
+  int32_t ksize;
+  uint16_t taps[4];
+  int32_t hue, sat, val;
+  float alpha, beta255;
+  int32_t n_holes;
+  int16_t holes[MMSKIN_AUG_MAX_HOLES][4];
+  uint32_t reserved[2];
+} mmskin_augment_params;
+int mmskin_train_augment_u8(const uint8_t* src_nhwc, int N, int H, int W, const mmskin_augment_params* params_host,
+                            mmskin_augment_params* params_scratch, uint8_t* dst_nhwc, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * `custom-cnn` image encoder pieces (loadImageModelClassifier.py:50-60): small direct kernels for
  * shapes the MFMA implicit GEMM does not cover (Cin=3, Cout=16).  NCHW fp32. */
 int mmskin_direct_conv2d_forward(const float* x, const float* w, const float* b, float* y, int N, int Cin, int H, int W,

@@ -229,6 +229,10 @@ class _FlatBackbone(nn.Module):
     # (H, W) or None.  When set, uint8 NHWC batches of another size go through the GPU A.Resize kernel first (the val / test
     # transform of skinLesionDatasets.py:116-120: Resize -> Normalize -> ToTensor, all on the device)
     resize_to = None
+    # mmskin.preprocess.TrainAugment or None.  When set, uint8 NHWC batches seen in training mode go through the fused GPU
+    # augmentation kernel (the train transform of skinLesionDatasets.py:74-113) after the optional resize; eval mode and
+    # float inputs are untouched
+    train_augment = None
 
     def _init_flat(self, compute_dtype):
         self.compute_dtype = (compute_dtype or default_compute_dtype()).lower()
@@ -382,6 +386,8 @@ class _FlatBackbone(nn.Module):
         if self.resize_to is not None and image.dtype == torch.uint8:
             from .preprocess import resize_u8
             image = resize_u8(image, self.resize_to)
+        if self.train_augment is not None and self.training and image.dtype == torch.uint8:
+            image = self.train_augment(image)
         tail = self._hooked_features_tail()
         if tail is not None:
             return self._forward_with_features_hooks(image, tail)
