@@ -498,6 +498,28 @@ int mmskin_train_augment_u8(const uint8_t* src_nhwc, int N, int H, int W, const 
                             mmskin_augment_params* params_scratch, uint8_t* dst_nhwc, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Score-CAM (interpretability/ScoreCam.py:62-155), forward only.  fmap is the hooked feature map of ONE image, fp32
+ * [C, fh, fw]; image is fp32 [3, H, W].  cam_c = min-max normalised torch.nn.Upsample(size=(H, W), mode='bilinear')
+ * (align_corners=False) of channel c: src = max((dst + 0.5) * (in / out) - 0.5, 0), i0 = min(floor(src), in - 1),
+ * i1 = min(i0 + 1, in - 1), value f0 + l * (f1 - f0) along x, then along y (weights 1 - l and l in the form that keeps a
+ * constant channel exactly constant); a flat channel (max == min) gives an all-zero cam.  The normalised maps
+ * are never stored: every kernel recomputes them from fmap, every multiply and add rounded to fp32 on its own.
+ *   minmax   minmax[c] = (min, max) of the UPSAMPLED map of channel c, [C, 2]
+ *   mask     out[j, ch, y, x] = image[ch, y, x] * cam_{c0 + j}[y, x] for j < n and 0 for n <= j < n_pad, fp32 NCHW
+ *            [n_pad, 3, H, W]: the masked inputs of one chunk of channels, the ragged last chunk padded to the batch shape
+ *   combine  heat[y, x] = sum_c scores[c] * cam_c[y, x] accumulated in fp32 in ascending channel order, ReLU, then
+ *            (heat - min) / (max - min) over the [H, W] map.  The last division has no zero guard (ScoreCam.py:154): a flat
+ *            combined map comes back as NaN.  channel_block: channels staged through LDS per round, 0 = as many as fit
+ * minmax must come from mmskin_scorecam_minmax with the same fmap and sizes.  Errors (nothing is launched): an extent < 1,
+ * H < fh or W < fw, n < 1, n > n_pad, c0 < 0 or c0 + n > C; MMSKIN_ERR_UNSUPPORTED for a feature map of more than 12272
+ * samples per channel (the LDS tile). */
+int mmskin_scorecam_minmax(const float* fmap, int C, int fh, int fw, int H, int W, float* minmax, void* stream);
+int mmskin_scorecam_mask(const float* fmap, const float* minmax, const float* image, int C, int fh, int fw, int H, int W, int c0,
+                         int n, int n_pad, float* out, void* stream);
+int mmskin_scorecam_combine(const float* fmap, const float* minmax, const float* scores, int C, int fh, int fw, int H, int W,
+                            int channel_block, float* heat, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * `custom-cnn` image encoder pieces (loadImageModelClassifier.py:50-60): small direct kernels for
  * shapes the MFMA implicit GEMM does not cover (Cin=3, Cout=16).  NCHW fp32. */
 int mmskin_direct_conv2d_forward(const float* x, const float* w, const float* b, float* y, int N, int Cin, int H, int W,

@@ -229,6 +229,8 @@ def linear_lane(x, ws, b=None, act=0, gamma=None, residual=None, drop_p=0.0, tra
 def linear(x, w, b=None, relu=False, out_dtype=None, residual=None):
     """nn.Linear (+ ReLU).  residual: y = residual + x @ w.T + b -- added in the pass that writes y when the bf16-operand large-GEMM
     path takes the shape (a transformer block's skip connection), by ops.add otherwise."""
+    if w.numel() != w.shape[0] * x.shape[-1]:      # the kernels take K from x alone: a wrong width would read past w
+        raise _lib.MMSkinError(f"linear: input of width {x.shape[-1]} for a weight of shape {tuple(w.shape)}")
     if x.dtype == torch.bfloat16 or out_dtype == torch.bfloat16:
         y = linear_lane(x, w, b, 1 if relu else 0, out_dtype=out_dtype)
         return y if residual is None else add(y, residual.reshape(y.shape))
@@ -1549,3 +1551,49 @@ class PoolGapFn(torch.autograd.Function):
 
 
 pool_gap = PoolGapFn.apply
+
+
+# ---------------------------------------------------------------------------------------------- Score-CAM (forward only)
+def _scorecam_dims(fmap, size):
+    _need_gpu(fmap, "scorecam")
+    if fmap.dim() != 3 or fmap.dtype != torch.float32 or not fmap.is_contiguous():
+        raise _lib.MMSkinError(f"scorecam: the feature map must be a contiguous fp32 [C, fh, fw] tensor, got {tuple(fmap.shape)} {fmap.dtype}")
+    return tuple(fmap.shape) + (int(size[0]), int(size[1]))
+
+
+def scorecam_minmax(fmap, size):
+    """(min, max) of every channel of fmap [C, fh, fw] after the bilinear upsample to size = (H, W) -> [C, 2]."""
+    C, fh, fw, H, W = _scorecam_dims(fmap, size)
+    out = torch.empty((C, 2), device=fmap.device, dtype=torch.float32)
+    call("mmskin_scorecam_minmax", ptr(fmap), C, fh, fw, H, W, ptr(out), stream())
+    return out
+
+
+def scorecam_mask(fmap, minmax, image, c0, n, n_pad, out=None):
+    """Masked inputs of channels c0 .. c0 + n: image [3, H, W] times each channel's normalised upsampled map -> [n_pad, 3, H, W],
+    rows n .. n_pad zero.  `out` (same shape, fp32, contiguous) is overwritten when given."""
+    _need_gpu(image, "scorecam_mask")
+    if image.dim() != 3 or image.shape[0] != 3 or image.dtype != torch.float32 or not image.is_contiguous():
+        raise _lib.MMSkinError(f"scorecam_mask: the image must be a contiguous fp32 [3, H, W] tensor, got {tuple(image.shape)} {image.dtype}")
+    C, fh, fw, H, W = _scorecam_dims(fmap, image.shape[1:])
+    if tuple(minmax.shape) != (C, 2) or minmax.dtype != torch.float32 or not minmax.is_contiguous():
+        raise _lib.MMSkinError("scorecam_mask: minmax must be the [C, 2] fp32 result of scorecam_minmax")
+    if out is None:
+        out = torch.empty((max(int(n_pad), 0), 3, H, W), device=fmap.device, dtype=torch.float32)
+    elif tuple(out.shape) != (n_pad, 3, H, W) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise _lib.MMSkinError(f"scorecam_mask: out must be a contiguous fp32 {(n_pad, 3, H, W)} tensor")
+    call("mmskin_scorecam_mask", ptr(fmap), ptr(minmax), ptr(image), C, fh, fw, H, W, int(c0), int(n), int(n_pad), ptr(out), stream())
+    return out
+
+
+def scorecam_combine(fmap, minmax, scores, size, channel_block=0):
+    """Heat map [H, W]: sum of scores[c] * normalised upsampled channel c (fp32, ascending c), ReLU, min-max normalised.  A flat
+    combined map comes back as NaN, as in the reference (no zero guard on the last division)."""
+    C, fh, fw, H, W = _scorecam_dims(fmap, size)
+    if tuple(minmax.shape) != (C, 2) or minmax.dtype != torch.float32 or not minmax.is_contiguous():
+        raise _lib.MMSkinError("scorecam_combine: minmax must be the [C, 2] fp32 result of scorecam_minmax")
+    if tuple(scores.shape) != (C,) or scores.dtype != torch.float32 or not scores.is_contiguous() or not scores.is_cuda:
+        raise _lib.MMSkinError(f"scorecam_combine: scores must be a contiguous fp32 [{C}] device tensor")
+    heat = torch.empty((H, W), device=fmap.device, dtype=torch.float32)
+    call("mmskin_scorecam_combine", ptr(fmap), ptr(minmax), ptr(scores), C, fh, fw, H, W, int(channel_block), ptr(heat), stream())
+    return heat
