@@ -50,7 +50,10 @@ int mmskin_backbone_feature_dim(mmskin_backbone_t h);
 int mmskin_backbone_feature_hw(mmskin_backbone_t h, int* out_h, int* out_w);
 /* Introspection for parity tests: where unit `index` (conv+BN, in parameter order) keeps its raw conv
  * output x, its post-activation output y and its BN coefficient vectors inside the workspace.
- * info12 = {x_off, y_off, coef_off (bytes), rows, Cout, OH, OW, Cin, H, W, pool_off, scratch0_off}. */
+ * info12 = {x_off, y_off, coef_off (bytes), rows, Cout, OH, OW, Cin, H, W, pool_off, scratch0_off}.
+ * MobileNet-V2 / EfficientNet plans report the same twelve fields with the real (unpadded) Cout / Cin, the unit's input
+ * activation offset in place of pool_off and the first gradient buffer in place of scratch0_off; a depthwise unit is the one
+ * whose named weight has shape [C][1][k][k]. */
 int mmskin_backbone_num_units(mmskin_backbone_t h);
 int mmskin_backbone_unit_info(mmskin_backbone_t h, int index, char* name, int name_cap, int64_t* info12);
 /* Per-kernel-class timing with HIP events recorded on the launch stream (off by default).  Classes:
@@ -158,6 +161,42 @@ int mmskin_batchnorm_forward(const float* x, const float* gamma, const float* be
 int mmskin_batchnorm_backward(const float* dy, const float* x, const float* gamma, const float* beta,
                               const float* save_mean, const float* save_invstd, float* dx, float* dgamma, float* dbeta,
                               int N, int C, int H, int W, int relu, int dtype, void* workspace, void* stream);
+/* ---- The MBConv family op by op (MobileNet-V2 / EfficientNet plans, torchvision MBConv / InvertedResidual): each entry launches what
+ * the plan launches for one unit, on NCHW fp32 tensors, with NHWC `dtype` copies inside the workspace.
+ *
+ * Depthwise k x k convolution, k in {3, 5}, stride in {1, 2}, padding k / 2.  x [N][C][H][W] with C the PADDED channel count (a multiple
+ * of 8; the plan uses multiples of 64), w and dw [c_valid][1][k][k]: channels >= c_valid get zero weights, as the plan stages them, so y
+ * and dx are zero there whatever x / dy hold.  dx or dw may be NULL. */
+int64_t mmskin_dwconv2d_workspace_bytes(int N, int C, int H, int W, int ksize, int stride);
+int mmskin_dwconv2d_forward(const float* x, const float* w, float* y, int N, int C, int H, int W, int ksize, int stride, int c_valid,
+                            int dtype, void* workspace, void* stream);
+int mmskin_dwconv2d_backward(const float* dy, const float* x, const float* w, float* dx, float* dw, int N, int C, int H, int W, int ksize,
+                             int stride, int c_valid, int dtype, void* workspace, void* stream);
+/* training-mode BatchNorm2d + the plans' activations: y = act(bn(x) + res), act 0 none, 1 ReLU, 2 ReLU6, 3 SiLU; res may be NULL.
+ * Backward takes the y the forward returned (ReLU / ReLU6 mask from it: 0 < y, y < 6 on the STORED value) and returns dx, dgamma, dbeta
+ * and, with has_residual, dres = the masked dy (may be NULL).  SiLU behind a residual has no backward (MMSKIN_ERR_UNSUPPORTED): the
+ * kernel recomputes the SiLU argument from x alone, and the plans' residual units carry no activation. */
+int64_t mmskin_batchnorm_act_workspace_bytes(int N, int C, int H, int W);
+int mmskin_batchnorm_act_forward(const float* x, const float* res, const float* gamma, const float* beta, float* running_mean,
+                                 float* running_var, float* y, float* save_mean, float* save_invstd, int N, int C, int H, int W, float eps,
+                                 float momentum, int act, int dtype, void* workspace, void* stream);
+int mmskin_batchnorm_act_backward(const float* dy, const float* x, const float* y, const float* gamma, const float* beta,
+                                  const float* save_mean, const float* save_invstd, float* dx, float* dres, float* dgamma, float* dbeta,
+                                  int N, int C, int H, int W, int act, int has_residual, int dtype, void* workspace, void* stream);
+/* Squeeze-excitation (torchvision SqueezeExcitation: y * sigmoid(fc2(silu(fc1(mean_hw y))))): y, y_se, dy_se, dy are [N][Cp][HW] with
+ * Cp = C rounded up to 64 (the plan keeps the padding channels of y at zero); w1 [Csq][C], b1 [Csq], w2 [C][Csq], b2 [C] and their
+ * gradients are unpadded.  The backward recomputes the forward's small activations. */
+int64_t mmskin_se_workspace_bytes(int N, int Cp, int Csq, int HW);
+int mmskin_se_forward(const float* y, const float* w1, const float* b1, const float* w2, const float* b2, float* y_se, int N, int C, int Cp,
+                      int Csq, int HW, int dtype, void* workspace, void* stream);
+int mmskin_se_backward(const float* dy_se, const float* y, const float* w1, const float* b1, const float* w2, const float* b2, float* dy,
+                       float* dw1, float* db1, float* dw2, float* db2, int N, int C, int Cp, int Csq, int HW, int dtype, void* workspace,
+                       void* stream);
+/* Row-mode stochastic depth on [N][per_sample] (per_sample a multiple of 8): y = branch * mask[n] + res;  out = dy * mask[n] */
+int64_t mmskin_sd_workspace_bytes(int N, int64_t per_sample);
+int mmskin_sd_forward(const float* branch, const float* res, const float* mask, float* y, int N, int64_t per_sample, int dtype,
+                      void* workspace, void* stream);
+int mmskin_sd_backward(const float* dy, const float* mask, float* out, int N, int64_t per_sample, int dtype, void* workspace, void* stream);
 /* the ResNet stem: conv7x7/2 (OIHW [64,3,7,7]) -> BN(train) -> ReLU -> maxpool3x3/2; y [N,64,PH,PW] */
 int64_t mmskin_stem_workspace_bytes(int N, int H, int W);
 int mmskin_stem_forward(const float* x, const float* w, const float* gamma, const float* beta, float* y, int N, int H,

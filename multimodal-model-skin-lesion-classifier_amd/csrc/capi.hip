@@ -7,6 +7,7 @@
 #include "../../include/mmskin.h"
 #include "conv.h"
 #include "ops.h"
+#include "plan.h"
 
 static thread_local char g_err[1024] = "";
 
@@ -213,6 +214,178 @@ int stem_bwd_op(const float* dy, const float* x, const float* w, const float* ga
                                       g.OW, 64, s.dx0, st))) return rc;
   if ((rc = launch_stem_conv_wgrad<T>(N, g.OH, g.OW, g.Hp, g.Wp, s.dx0, s.img4, s.slab, s.dwv, st))) return rc;
   return stem_wgrad_unpack(s.dwv, dw, st);
+}
+
+// ---- MBConv family (mbconv.hip's launches, op by op): depthwise k x k, BatchNorm + ReLU6 / SiLU, squeeze-excitation, stochastic depth
+template <typename T>
+struct DwWs {
+  T *xh, *yh, *wst, *dxh; float* partial; size_t total; int OH, OW;
+  DwWs(void* ws, int N, int C, int H, int W, int k, int stride) {
+    const int pad = k / 2;
+    OH = (H + 2 * pad - k) / stride + 1; OW = (W + 2 * pad - k) / stride + 1;
+    Carver c(ws);
+    xh = c.take<T>((size_t)N * H * W * C);
+    yh = c.take<T>((size_t)N * OH * OW * C);
+    wst = c.take<T>((size_t)k * k * C);
+    dxh = c.take<T>((size_t)N * H * W * C);
+    partial = c.take<float>(dwconv3_wgrad_partial_floats(N, H, W, C, stride, k));   // the sizing finish_plan uses
+    total = c.cur;
+  }
+};
+
+template <typename T>
+int dw_fwd_op(const float* x, const float* w, float* y, int N, int C, int H, int W, int k, int stride, int Cv, void* ws, hipStream_t st) {
+  DwWs<T> s(ws, N, C, H, W, k, stride);
+  int rc;
+  if ((rc = nchw_to_nhwc<T>(x, N, C, H, W, s.xh, st))) return rc;
+  if ((rc = dw_stage_weights<T>(w, Cv, C, s.wst, st, k))) return rc;
+  if ((rc = dwconv3_fwd<T>(s.xh, s.wst, N, H, W, C, stride, s.yh, st, k))) return rc;
+  return nhwc_to_nchw<T>(s.yh, N, C, s.OH, s.OW, y, st);
+}
+
+template <typename T>
+int dw_bwd_op(const float* dy, const float* x, const float* w, float* dx, float* dw, int N, int C, int H, int W, int k, int stride,
+              int Cv, void* ws, hipStream_t st) {
+  DwWs<T> s(ws, N, C, H, W, k, stride);
+  int rc;
+  if ((rc = nchw_to_nhwc<T>(dy, N, C, s.OH, s.OW, s.yh, st))) return rc;
+  if (dx) {
+    if ((rc = dw_stage_weights<T>(w, Cv, C, s.wst, st, k))) return rc;
+    if ((rc = dwconv3_dgrad<T>(s.yh, s.wst, N, H, W, C, stride, s.dxh, st, k))) return rc;
+    if ((rc = nhwc_to_nchw<T>(s.dxh, N, C, H, W, dx, st))) return rc;
+  }
+  if (dw) {
+    if ((rc = nchw_to_nhwc<T>(x, N, C, H, W, s.xh, st))) return rc;
+    if ((rc = dwconv3_wgrad<T>(s.yh, s.xh, N, H, W, C, stride, s.partial, dw, Cv, st, k))) return rc;
+  }
+  return MMSKIN_OK;
+}
+
+template <typename T>
+struct BnActWs {
+  T *xh, *yh, *rh, *dyh, *dxh, *dzh; float *ssum, *ssq, *tab, *coef, *partial; size_t total;
+  BnActWs(void* ws, size_t rows, int C) {
+    Carver c(ws);
+    xh = c.take<T>(rows * C); yh = c.take<T>(rows * C); rh = c.take<T>(rows * C);
+    dyh = c.take<T>(rows * C); dxh = c.take<T>(rows * C); dzh = c.take<T>(rows * C);
+    ssum = c.take<float>((size_t)column_stats_rows(rows, C) * C);
+    ssq = c.take<float>((size_t)column_stats_rows(rows, C) * C);
+    tab = c.take<float>(2 * (size_t)C);
+    coef = c.take<float>(5 * (size_t)C);
+    partial = c.take<float>((size_t)bn_bwd_partial_rows(rows, C) * 2 * C);
+    total = c.cur;
+  }
+};
+// act 0 none, 1 ReLU, 2 ReLU6, 3 SiLU -> bn_apply's (relu, cap) and the BatchNorm-backward mask mode (2 / 3: MBPlan::act_cap / act_mask)
+inline float act_cap(int act) { return act == 2 ? 6.f : act == 3 ? -1.f : 0.f; }
+inline int act_mask(int act) { return act == 1 ? MASK_FROM_Y : act == 2 ? MASK_FROM_Y6 : act == 3 ? MASK_SILU_X : MASK_NONE; }
+
+template <typename T>
+int bn_act_fwd_op(const float* x, const float* res, const float* gamma, const float* beta, float* rm, float* rv, float* y, float* save_mean,
+                  float* save_invstd, int N, int C, int H, int W, float eps, float mom, int act, void* ws, hipStream_t st) {
+  const size_t rows = (size_t)N * H * W;
+  BnActWs<T> s(ws, rows, C);
+  int rc, nr = 0;
+  if ((rc = nchw_to_nhwc<T>(x, N, C, H, W, s.xh, st))) return rc;
+  if (res && (rc = nchw_to_nhwc<T>(res, N, C, H, W, s.rh, st))) return rc;
+  // the plan's sequence behind a depthwise conv: column sums -> statistics table -> coefficient vectors -> apply
+  if ((rc = column_stats<T>(s.xh, rows, C, s.ssum, s.ssq, &nr, st))) return rc;
+  if ((rc = bn_table_finalize(s.ssum, s.ssq, nr, C, C, (double)rows, s.tab, s.tab + C, nullptr, st))) return rc;
+  if ((rc = bn_coef_from_table(s.tab, s.tab + C, C, C, gamma, beta, eps, mom, (double)rows, rm, rv, true, s.coef, st))) return rc;
+  HIP_CHECK_RET(hipMemcpyAsync(save_mean, s.coef + 2 * C, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
+  HIP_CHECK_RET(hipMemcpyAsync(save_invstd, s.coef + 3 * C, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
+  if ((rc = bn_apply<T>(s.xh, res ? s.rh : nullptr, s.coef, s.coef + C, nullptr, nullptr, s.yh, rows, C, act != 0, st, nullptr, act_cap(act)))) return rc;
+  return nhwc_to_nchw<T>(s.yh, N, C, H, W, y, st);
+}
+
+template <typename T>
+int bn_act_bwd_op(const float* dy, const float* x, const float* y, const float* gamma, const float* beta, const float* save_mean,
+                  const float* save_invstd, float* dx, float* dres, float* dgamma, float* dbeta, int N, int C, int H, int W, int act,
+                  void* ws, hipStream_t st) {
+  const size_t rows = (size_t)N * H * W;
+  BnActWs<T> s(ws, rows, C);
+  int rc, nr = 0;
+  if ((rc = nchw_to_nhwc<T>(x, N, C, H, W, s.xh, st))) return rc;
+  if ((rc = nchw_to_nhwc<T>(y, N, C, H, W, s.yh, st))) return rc;   // the forward's stored y: exact in T, MASK_FROM_Y6 reads it
+  if ((rc = nchw_to_nhwc<T>(dy, N, C, H, W, s.dyh, st))) return rc;
+  hipLaunchKernelGGL(coef_from_saved_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, st, C, gamma, beta, save_mean, save_invstd, s.coef,
+                     s.coef + C);
+  HIP_CHECK_RET(hipGetLastError());
+  const int mode = act_mask(act);
+  float *cA = s.coef + 2 * C, *cB = s.coef + 3 * C, *cC = s.coef + 4 * C;
+  if ((rc = bn_bwd_reduce<T>(s.dyh, s.xh, s.yh, s.coef, s.coef + C, mode, rows, C, s.partial, &nr, st))) return rc;
+  if ((rc = bn_bwd_finalize(s.partial, nr, C, (double)rows, gamma, save_mean, save_invstd, dgamma, dbeta, cA, cB, cC, nullptr, st))) return rc;
+  if ((rc = bn_bwd_apply<T>(s.dyh, s.xh, s.yh, s.coef, s.coef + C, mode, cA, cB, cC, s.dxh, dres ? s.dzh : (T*)nullptr, rows, C, st))) return rc;
+  if (dres && (rc = nhwc_to_nchw<T>(s.dzh, N, C, H, W, dres, st))) return rc;   // the residual's gradient is the masked dy
+  return nhwc_to_nchw<T>(s.dxh, N, C, H, W, dx, st);
+}
+
+template <typename T>
+struct SeWs {
+  T *yh, *yseh, *dyh, *dxh; float *w1p, *w2p, *b2p, *s, *z1, *a1, *z2, *g, *tmp; size_t total;
+  SeWs(void* ws, int N, int Cp, int Csq, int HW) {
+    Carver c(ws);
+    const size_t act = (size_t)N * HW * Cp;
+    yh = c.take<T>(act); yseh = c.take<T>(act); dyh = c.take<T>(act); dxh = c.take<T>(act);
+    w1p = c.take<float>((size_t)Csq * Cp); w2p = c.take<float>((size_t)Cp * Csq); b2p = c.take<float>(Cp);
+    s = c.take<float>((size_t)N * Cp); z1 = c.take<float>((size_t)N * Csq); a1 = c.take<float>((size_t)N * Csq);
+    z2 = c.take<float>((size_t)N * Cp); g = c.take<float>((size_t)N * Cp);
+    tmp = c.take<float>(se_backward_tmp_floats(N, Cp, Csq));
+    total = c.cur;
+  }
+  SEArgs args(int N, int HW, int C, int Cp, int Csq, const float* b1) const {
+    SEArgs a;
+    a.N = N; a.HW = HW; a.C = C; a.Cp = Cp; a.Csq = Csq;
+    a.w1p = w1p; a.b1 = b1; a.w2p = w2p; a.b2p = b2p;
+    a.s = s; a.z1 = z1; a.a1 = a1; a.z2 = z2; a.g = g;
+    return a;
+  }
+};
+
+// y [N][Cp][HW] -> NHWC T, the three padded parameter copies (the plan's staging), then the plan's forward chain
+template <typename T>
+int se_fwd_core(SeWs<T>& s, const float* y, const float* w1, const float* b1, const float* w2, const float* b2, int N, int C, int Cp,
+                int Csq, int HW, hipStream_t st) {
+  int rc;
+  if ((rc = nchw_to_nhwc<T>(y, N, Cp, HW, 1, s.yh, st))) return rc;
+  if ((rc = pad_matrix(w1, Csq, C, Csq, Cp, s.w1p, st))) return rc;
+  if ((rc = pad_matrix(w2, C, Csq, Cp, Csq, s.w2p, st))) return rc;
+  if ((rc = pad_matrix(b2, 1, C, 1, Cp, s.b2p, st))) return rc;
+  return se_forward<T>(s.args(N, HW, C, Cp, Csq, b1), s.yh, s.yseh, nullptr, st);
+}
+
+template <typename T>
+int se_fwd_op(const float* y, const float* w1, const float* b1, const float* w2, const float* b2, float* yse, int N, int C, int Cp, int Csq,
+              int HW, void* ws, hipStream_t st) {
+  SeWs<T> s(ws, N, Cp, Csq, HW);
+  int rc;
+  if ((rc = se_fwd_core<T>(s, y, w1, b1, w2, b2, N, C, Cp, Csq, HW, st))) return rc;
+  return nhwc_to_nchw<T>(s.yseh, N, Cp, HW, 1, yse, st);
+}
+
+template <typename T>
+int se_bwd_op(const float* dyse, const float* y, const float* w1, const float* b1, const float* w2, const float* b2, float* dy, float* dw1,
+              float* db1, float* dw2, float* db2, int N, int C, int Cp, int Csq, int HW, void* ws, hipStream_t st) {
+  SeWs<T> s(ws, N, Cp, Csq, HW);
+  int rc;
+  if ((rc = se_fwd_core<T>(s, y, w1, b1, w2, b2, N, C, Cp, Csq, HW, st))) return rc;   // the activations backward reads
+  if ((rc = nchw_to_nhwc<T>(dyse, N, Cp, HW, 1, s.dyh, st))) return rc;
+  if ((rc = se_backward<T>(s.args(N, HW, C, Cp, Csq, b1), s.dyh, s.yh, s.tmp, dw1, db1, dw2, db2, s.dxh, nullptr, st))) return rc;
+  return nhwc_to_nchw<T>(s.dxh, N, Cp, HW, 1, dy, st);
+}
+
+// flat [N][per_sample] fp32 <-> T (the converters with H = W = 1 are plain element-type conversions)
+template <typename T>
+int sd_op(const float* a, const float* res, const float* mask, float* out, int N, int64_t per, void* ws, hipStream_t st) {
+  Carver c(ws);
+  T* ah = c.take<T>((size_t)N * per); T* rh = c.take<T>((size_t)N * per); T* oh = c.take<T>((size_t)N * per);
+  int rc;
+  if ((rc = nchw_to_nhwc<T>(a, N, (int)per, 1, 1, ah, st))) return rc;
+  if (res) {
+    if ((rc = nchw_to_nhwc<T>(res, N, (int)per, 1, 1, rh, st))) return rc;
+    if ((rc = sd_residual_add<T>(ah, rh, mask, N, (size_t)per, oh, st))) return rc;
+  } else if ((rc = sd_row_scale<T>(ah, mask, N, (size_t)per, oh, st))) return rc;
+  return nhwc_to_nchw<T>(oh, N, (int)per, 1, 1, out, st);
 }
 
 }  // namespace
@@ -536,6 +709,102 @@ int mmskin_conv_pos_enc_backward(const float* dy, const float* x, const float* w
   if (dx && (rc = dwconv3_dgrad<float>(dy, w_stage, N, H, W, C, 1, dx, st, 3, true))) return rc;
   if (dw && (rc = dwconv3_wgrad<float>(dy, x, N, H, W, C, 1, scratch, dw, C, st, 3, db))) return rc;
   return MMSKIN_OK;
+}
+
+/* ---- MBConv family, op by op (MobileNet-V2 / EfficientNet: csrc/mbconv.hip).  NCHW fp32 at the boundary, NHWC `dtype` inside the
+ * workspace; every entry launches what the plan launches for the same unit. */
+#define DW_ARGS_OK (N > 0 && C > 0 && C % 8 == 0 && H > 0 && W > 0 && (ksize == 3 || ksize == 5) && (stride == 1 || stride == 2) && \
+                    c_valid >= 1 && c_valid <= C)
+int64_t mmskin_dwconv2d_workspace_bytes(int N, int C, int H, int W, int ksize, int stride) {
+  if (!(N > 0 && C > 0 && H > 0 && W > 0 && (ksize == 3 || ksize == 5) && (stride == 1 || stride == 2))) return -1;
+  DwWs<float> s(nullptr, N, C, H, W, ksize, stride);
+  return (int64_t)s.total + 4096;
+}
+int mmskin_dwconv2d_forward(const float* x, const float* w, float* y, int N, int C, int H, int W, int ksize, int stride, int c_valid,
+                            int dtype, void* workspace, void* stream) {
+  ARG_CHECK(x && w && y && workspace && DW_ARGS_OK, "dwconv2d_forward: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype, dw_fwd_op<float>(x, w, y, N, C, H, W, ksize, stride, c_valid, workspace, st),
+           dw_fwd_op<bf16_t>(x, w, y, N, C, H, W, ksize, stride, c_valid, workspace, st));
+}
+int mmskin_dwconv2d_backward(const float* dy, const float* x, const float* w, float* dx, float* dw, int N, int C, int H, int W, int ksize,
+                             int stride, int c_valid, int dtype, void* workspace, void* stream) {
+  ARG_CHECK(dy && x && w && workspace && DW_ARGS_OK, "dwconv2d_backward: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype, dw_bwd_op<float>(dy, x, w, dx, dw, N, C, H, W, ksize, stride, c_valid, workspace, st),
+           dw_bwd_op<bf16_t>(dy, x, w, dx, dw, N, C, H, W, ksize, stride, c_valid, workspace, st));
+}
+#undef DW_ARGS_OK
+
+int64_t mmskin_batchnorm_act_workspace_bytes(int N, int C, int H, int W) {
+  if (!(N > 0 && C > 0 && H > 0 && W > 0)) return -1;
+  BnActWs<float> s(nullptr, (size_t)N * H * W, C);
+  return (int64_t)s.total + 4096;
+}
+int mmskin_batchnorm_act_forward(const float* x, const float* res, const float* gamma, const float* beta, float* running_mean,
+                                 float* running_var, float* y, float* save_mean, float* save_invstd, int N, int C, int H, int W, float eps,
+                                 float momentum, int act, int dtype, void* workspace, void* stream) {
+  ARG_CHECK(x && gamma && beta && running_mean && running_var && y && save_mean && save_invstd && workspace && N > 0 && C > 0 && C % 8 == 0 &&
+            H > 0 && W > 0 && act >= 0 && act <= 3, "batchnorm_act_forward: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype,
+           bn_act_fwd_op<float>(x, res, gamma, beta, running_mean, running_var, y, save_mean, save_invstd, N, C, H, W, eps, momentum, act, workspace, st),
+           bn_act_fwd_op<bf16_t>(x, res, gamma, beta, running_mean, running_var, y, save_mean, save_invstd, N, C, H, W, eps, momentum, act, workspace, st));
+}
+int mmskin_batchnorm_act_backward(const float* dy, const float* x, const float* y, const float* gamma, const float* beta,
+                                  const float* save_mean, const float* save_invstd, float* dx, float* dres, float* dgamma, float* dbeta,
+                                  int N, int C, int H, int W, int act, int has_residual, int dtype, void* workspace, void* stream) {
+  ARG_CHECK(dy && x && y && gamma && beta && save_mean && save_invstd && dx && workspace && N > 0 && C > 0 && C % 8 == 0 && H > 0 && W > 0 &&
+            act >= 0 && act <= 3 && (has_residual || !dres), "batchnorm_act_backward: bad argument");
+  if (act == 3 && has_residual) {   // MASK_SILU_X recomputes the SiLU argument from x alone; the plan's residual units carry no activation
+    mmskin_set_error("batchnorm_act_backward: SiLU behind a residual has no backward kernel");
+    return MMSKIN_ERR_UNSUPPORTED;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype,
+           bn_act_bwd_op<float>(dy, x, y, gamma, beta, save_mean, save_invstd, dx, dres, dgamma, dbeta, N, C, H, W, act, workspace, st),
+           bn_act_bwd_op<bf16_t>(dy, x, y, gamma, beta, save_mean, save_invstd, dx, dres, dgamma, dbeta, N, C, H, W, act, workspace, st));
+}
+
+#define SE_ARGS_OK (N > 0 && C > 0 && Cp == pad64(C) && Csq > 0 && HW > 0)
+int64_t mmskin_se_workspace_bytes(int N, int Cp, int Csq, int HW) {
+  if (!(N > 0 && Cp > 0 && Csq > 0 && HW > 0)) return -1;
+  SeWs<float> s(nullptr, N, Cp, Csq, HW);
+  return (int64_t)s.total + 4096;
+}
+int mmskin_se_forward(const float* y, const float* w1, const float* b1, const float* w2, const float* b2, float* y_se, int N, int C, int Cp,
+                      int Csq, int HW, int dtype, void* workspace, void* stream) {
+  ARG_CHECK(y && w1 && b1 && w2 && b2 && y_se && workspace && SE_ARGS_OK, "se_forward: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype, se_fwd_op<float>(y, w1, b1, w2, b2, y_se, N, C, Cp, Csq, HW, workspace, st),
+           se_fwd_op<bf16_t>(y, w1, b1, w2, b2, y_se, N, C, Cp, Csq, HW, workspace, st));
+}
+int mmskin_se_backward(const float* dy_se, const float* y, const float* w1, const float* b1, const float* w2, const float* b2, float* dy,
+                       float* dw1, float* db1, float* dw2, float* db2, int N, int C, int Cp, int Csq, int HW, int dtype, void* workspace,
+                       void* stream) {
+  ARG_CHECK(dy_se && y && w1 && b1 && w2 && b2 && dy && dw1 && db1 && dw2 && db2 && workspace && SE_ARGS_OK, "se_backward: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype, se_bwd_op<float>(dy_se, y, w1, b1, w2, b2, dy, dw1, db1, dw2, db2, N, C, Cp, Csq, HW, workspace, st),
+           se_bwd_op<bf16_t>(dy_se, y, w1, b1, w2, b2, dy, dw1, db1, dw2, db2, N, C, Cp, Csq, HW, workspace, st));
+}
+#undef SE_ARGS_OK
+
+int64_t mmskin_sd_workspace_bytes(int N, int64_t per_sample) {
+  if (!(N > 0 && per_sample > 0)) return -1;
+  return (int64_t)(3 * align_up((size_t)N * per_sample * 4, 256) + 4096);
+}
+int mmskin_sd_forward(const float* branch, const float* res, const float* mask, float* y, int N, int64_t per_sample, int dtype,
+                      void* workspace, void* stream) {
+  ARG_CHECK(branch && res && mask && y && workspace && N > 0 && per_sample > 0 && per_sample % 8 == 0 && per_sample < (1ll << 31),
+            "sd_forward: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype, sd_op<float>(branch, res, mask, y, N, per_sample, workspace, st), sd_op<bf16_t>(branch, res, mask, y, N, per_sample, workspace, st));
+}
+int mmskin_sd_backward(const float* dy, const float* mask, float* out, int N, int64_t per_sample, int dtype, void* workspace, void* stream) {
+  ARG_CHECK(dy && mask && out && workspace && N > 0 && per_sample > 0 && per_sample % 8 == 0 && per_sample < (1ll << 31),
+            "sd_backward: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype, sd_op<float>(dy, nullptr, mask, out, N, per_sample, workspace, st), sd_op<bf16_t>(dy, nullptr, mask, out, N, per_sample, workspace, st));
 }
 
 }  // extern "C"

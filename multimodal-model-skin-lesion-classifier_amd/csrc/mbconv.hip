@@ -80,7 +80,21 @@ struct MBPlan : PlanBase {
   int forward(const void* image, const float* norm6, const float* params, float* buffers, unsigned char* ws,
               float* features, bool training, hipStream_t st) override;
   int backward(const float* dfeat, const float* params, unsigned char* ws, float* grads, hipStream_t st) override;
+  int num_units() const override { return (int)units.size(); }
+  int unit_info(int index, std::string* name, int64_t* info12) const override;
 };
+
+// The twelve fields of the ResNet plan's unit_info; channel counts are the real (unpadded) ones, the two plan-wide offsets are
+// this plan's analogues: the unit's input activation and the first gradient buffer.
+int MBPlan::unit_info(int index, std::string* name, int64_t* info12) const {
+  const MBUnit& u = units[index];
+  for (const TensorInfo& t : params)
+    if (t.offset == u.w_off && name) *name = t.name;
+  const int64_t v[12] = {(int64_t)u.x_off, (int64_t)u.y_off, (int64_t)u.coef_off, (int64_t)N * u.OH * u.OW, u.Cout,
+                         u.OH, u.OW, u.Cin, u.H, u.W, (int64_t)u.in_off, (int64_t)off_g[0]};
+  for (int i = 0; i < 12; ++i) info12[i] = v[i];
+  return MMSKIN_OK;
+}
 
 // Registers one conv + BatchNorm unit (torchvision named_parameters() order); returns its index.
 int add_unit(MBPlan& p, int kind, const std::string& conv_name, const std::string& bn_name, int cin, int cout, int h,
@@ -152,7 +166,7 @@ int finish_plan(MBPlan& p, const char* arch) {
       se.g_off = carve(cur, (size_t)p.N * se.Cp * 4);
       prev_y = se.yse_off;
       // backward temporaries: dgate/dz2 [N][Cp] x2, da1/dz1 [N][Csq] x2, ds [N][Cp], dW1p, dW2p, db2p
-      size_t t = (size_t)3 * p.N * se.Cp + (size_t)2 * p.N * se.Csq + (size_t)2 * se.Csq * se.Cp + se.Cp + (size_t)p.N * se.Csq;
+      size_t t = se_backward_tmp_floats(p.N, se.Cp, se.Csq);
       if (t > setmp) setmp = t;
     }
     if (rows * u.Coutp > maxact) maxact = rows * u.Coutp;
@@ -272,6 +286,17 @@ int build_efficientnet(MBPlan& p, int variant) {   // variant 0 = B0, 7 = B7
   return finish_plan(p, "efficientnet");
 }
 
+inline SEArgs se_args(const MBPlan& p, const SEBlock& se, unsigned char* ws, const float* params, int HW) {
+  SEArgs a;
+  a.N = p.N; a.HW = HW; a.C = se.C; a.Cp = se.Cp; a.Csq = se.Csq;
+  a.w1p = reinterpret_cast<const float*>(ws + se.w1p_off); a.b1 = params + se.b1_off;
+  a.w2p = reinterpret_cast<const float*>(ws + se.w2p_off); a.b2p = reinterpret_cast<const float*>(ws + se.b2p_off);
+  a.s = reinterpret_cast<float*>(ws + se.s_off); a.z1 = reinterpret_cast<float*>(ws + se.z1_off);
+  a.a1 = reinterpret_cast<float*>(ws + se.a1_off); a.z2 = reinterpret_cast<float*>(ws + se.z2_off);
+  a.g = reinterpret_cast<float*>(ws + se.g_off);
+  return a;
+}
+
 template <typename T>
 int mb_forward(MBPlan& p, const void* image, const float* norm6, const float* params, float* buffers,
                unsigned char* ws, float* features, bool training, hipStream_t st) {
@@ -336,18 +361,7 @@ int mb_forward(MBPlan& p, const void* image, const float* norm6, const float* pa
     }
     if (u.se >= 0) {   // squeeze-excitation on the depthwise output
       SEBlock& se = p.ses[u.se];
-      float* s = reinterpret_cast<float*>(ws + se.s_off);
-      float* z1 = reinterpret_cast<float*>(ws + se.z1_off);
-      float* a1 = reinterpret_cast<float*>(ws + se.a1_off);
-      float* z2 = reinterpret_cast<float*>(ws + se.z2_off);
-      float* g = reinterpret_cast<float*>(ws + se.g_off);
-      if ((rc = gap_reduce<T>(y, nullptr, p.N, u.OH * u.OW, Cp, 1.f / (float)(u.OH * u.OW), s, st))) return rc;
-      if ((rc = mmskin_linear_forward(s, reinterpret_cast<const float*>(ws + se.w1p_off), params + se.b1_off, z1, p.N, Cp, se.Csq, 0, st))) return rc;
-      if ((rc = ew_act_fwd(z1, a1, (int64_t)p.N * se.Csq, 0, st))) return rc;
-      if ((rc = mmskin_linear_forward(a1, reinterpret_cast<const float*>(ws + se.w2p_off), reinterpret_cast<const float*>(ws + se.b2p_off),
-                                      z2, p.N, se.Csq, Cp, 0, st))) return rc;
-      if ((rc = ew_act_fwd(z2, g, (int64_t)p.N * Cp, 1, st))) return rc;
-      PROF(K_BN_FWD, 0.0, 2.0 * rows * Cp * sizeof(T), se_scale_fwd<T>(y, g, p.N, u.OH * u.OW, Cp, reinterpret_cast<T*>(ws + se.yse_off), st));
+      if ((rc = se_forward<T>(se_args(p, se, ws, params, u.OH * u.OW), y, reinterpret_cast<T*>(ws + se.yse_off), &p.prof, st))) return rc;
     }
   }
   MBUnit& last = p.units.back();
@@ -384,33 +398,9 @@ int mb_backward(MBPlan& p, const float* dfeat, const float* params, unsigned cha
     if (u.se >= 0) {
       // ---- squeeze-excitation backward: B[cur] = d(y_se) -> d(y_dw) = dyse * g + ds / HW
       SEBlock& se = p.ses[u.se];
-      const float* s = reinterpret_cast<const float*>(ws + se.s_off);
-      const float* z1 = reinterpret_cast<const float*>(ws + se.z1_off);
-      const float* a1 = reinterpret_cast<const float*>(ws + se.a1_off);
-      const float* z2 = reinterpret_cast<const float*>(ws + se.z2_off);
-      const float* g = reinterpret_cast<const float*>(ws + se.g_off);
-      float* t = setmp;
-      float* dgate = t; t += (size_t)p.N * Cp;
-      float* dz2 = t; t += (size_t)p.N * Cp;
-      float* ds = t; t += (size_t)p.N * Cp;
-      float* da1 = t; t += (size_t)p.N * se.Csq;
-      float* dz1 = t; t += (size_t)p.N * se.Csq;
-      float* dw1p = t; t += (size_t)se.Csq * Cp;
-      float* dw2p = t; t += (size_t)Cp * se.Csq;
-      float* db2p = t; t += Cp;
-      if ((rc = gap_reduce<T>(B[cur], y, p.N, HW, Cp, 1.f, dgate, st))) return rc;
-      if ((rc = ew_act_bwd(dgate, z2, dz2, (int64_t)p.N * Cp, 1, st))) return rc;
-      if ((rc = mmskin_linear_backward(dz2, a1, reinterpret_cast<const float*>(ws + se.w2p_off), nullptr, nullptr, da1, dw2p, db2p,
-                                       p.N, se.Csq, Cp, st))) return rc;
-      if ((rc = ew_act_bwd(da1, z1, dz1, (int64_t)p.N * se.Csq, 0, st))) return rc;
-      if ((rc = mmskin_linear_backward(dz1, s, reinterpret_cast<const float*>(ws + se.w1p_off), nullptr, nullptr, ds, dw1p,
-                                       grads + se.b1_off, p.N, Cp, se.Csq, st))) return rc;
-      HIP_CHECK_RET(hipMemcpy2DAsync(grads + se.w1_off, (size_t)se.C * 4, dw1p, (size_t)Cp * 4, (size_t)se.C * 4, se.Csq,
-                                     hipMemcpyDeviceToDevice, st));
-      HIP_CHECK_RET(hipMemcpyAsync(grads + se.w2_off, dw2p, (size_t)se.C * se.Csq * 4, hipMemcpyDeviceToDevice, st));
-      HIP_CHECK_RET(hipMemcpyAsync(grads + se.b2_off, db2p, (size_t)se.C * 4, hipMemcpyDeviceToDevice, st));
       const int nb = take(cur, -1);
-      PROF(K_BN_BWD, 0.0, 2.0 * rows * Cp * sizeof(T), se_dx<T>(B[cur], g, ds, p.N, HW, Cp, B[nb], st));
+      if ((rc = se_backward<T>(se_args(p, se, ws, params, HW), B[cur], y, setmp, grads + se.w1_off, grads + se.b1_off, grads + se.w2_off,
+                               grads + se.b2_off, B[nb], &p.prof, st))) return rc;
       cur = nb;
     }
     if (u.res_last) {
@@ -490,6 +480,62 @@ PlanBase* make_plan(int N, int H, int W, int dtype, int* rc, Build build) {
 }
 
 }  // namespace
+
+// Profiled launch for the two functions below, which have a Profiler pointer instead of a plan
+#define SE_PROF(bytes_, call_)                                   \
+  do {                                                          \
+    if (prof) prof->begin(cls, st);                             \
+    rc = (call_);                                               \
+    if (prof) { prof->end(st); if (prof->on) prof->bytes[cls] += (bytes_); } \
+    if (rc) return rc;                                          \
+  } while (0)
+
+template <typename T>
+int se_forward(const SEArgs& a, const T* y, T* yse, Profiler* prof, hipStream_t st) {
+  const int cls = K_BN_FWD;
+  const size_t rows = (size_t)a.N * a.HW;
+  int rc;
+  if ((rc = gap_reduce<T>(y, nullptr, a.N, a.HW, a.Cp, 1.f / (float)a.HW, a.s, st))) return rc;
+  if ((rc = mmskin_linear_forward(a.s, a.w1p, a.b1, a.z1, a.N, a.Cp, a.Csq, 0, st))) return rc;
+  if ((rc = ew_act_fwd(a.z1, a.a1, (int64_t)a.N * a.Csq, 0, st))) return rc;
+  if ((rc = mmskin_linear_forward(a.a1, a.w2p, a.b2p, a.z2, a.N, a.Csq, a.Cp, 0, st))) return rc;
+  if ((rc = ew_act_fwd(a.z2, a.g, (int64_t)a.N * a.Cp, 1, st))) return rc;
+  SE_PROF(2.0 * rows * a.Cp * sizeof(T), se_scale_fwd<T>(y, a.g, a.N, a.HW, a.Cp, yse, st));
+  return MMSKIN_OK;
+}
+
+template <typename T>
+int se_backward(const SEArgs& a, const T* dyse, const T* y, float* tmp, float* dW1, float* db1, float* dW2, float* db2, T* dy,
+                Profiler* prof, hipStream_t st) {
+  const int cls = K_BN_BWD;
+  const size_t rows = (size_t)a.N * a.HW;
+  const int N = a.N, Cp = a.Cp, Csq = a.Csq;
+  int rc;
+  float* t = tmp;
+  float* dgate = t; t += (size_t)N * Cp;
+  float* dz2 = t; t += (size_t)N * Cp;
+  float* ds = t; t += (size_t)N * Cp;
+  float* da1 = t; t += (size_t)N * Csq;
+  float* dz1 = t; t += (size_t)N * Csq;
+  float* dw1p = t; t += (size_t)Csq * Cp;
+  float* dw2p = t; t += (size_t)Cp * Csq;
+  float* db2p = t; t += Cp;
+  if ((rc = gap_reduce<T>(dyse, y, N, a.HW, Cp, 1.f, dgate, st))) return rc;
+  if ((rc = ew_act_bwd(dgate, a.z2, dz2, (int64_t)N * Cp, 1, st))) return rc;
+  if ((rc = mmskin_linear_backward(dz2, a.a1, a.w2p, nullptr, nullptr, da1, dw2p, db2p, N, Csq, Cp, st))) return rc;
+  if ((rc = ew_act_bwd(da1, a.z1, dz1, (int64_t)N * Csq, 0, st))) return rc;
+  if ((rc = mmskin_linear_backward(dz1, a.s, a.w1p, nullptr, nullptr, ds, dw1p, db1, N, Cp, Csq, st))) return rc;
+  HIP_CHECK_RET(hipMemcpy2DAsync(dW1, (size_t)a.C * 4, dw1p, (size_t)Cp * 4, (size_t)a.C * 4, Csq, hipMemcpyDeviceToDevice, st));
+  HIP_CHECK_RET(hipMemcpyAsync(dW2, dw2p, (size_t)a.C * Csq * 4, hipMemcpyDeviceToDevice, st));
+  HIP_CHECK_RET(hipMemcpyAsync(db2, db2p, (size_t)a.C * 4, hipMemcpyDeviceToDevice, st));
+  SE_PROF(2.0 * rows * Cp * sizeof(T), se_dx<T>(dyse, a.g, ds, N, a.HW, Cp, dy, st));
+  return MMSKIN_OK;
+}
+#undef SE_PROF
+template int se_forward<float>(const SEArgs&, const float*, float*, Profiler*, hipStream_t);
+template int se_forward<bf16_t>(const SEArgs&, const bf16_t*, bf16_t*, Profiler*, hipStream_t);
+template int se_backward<float>(const SEArgs&, const float*, const float*, float*, float*, float*, float*, float*, float*, Profiler*, hipStream_t);
+template int se_backward<bf16_t>(const SEArgs&, const bf16_t*, const bf16_t*, float*, float*, float*, float*, float*, bf16_t*, Profiler*, hipStream_t);
 
 PlanBase* make_mobilenet_plan(int N, int H, int W, int dtype, int* rc) {
   return make_plan(N, H, W, dtype, rc, build_mobilenet_v2);

@@ -209,6 +209,28 @@ static inline double conv_bytes(const ConvShape& s, size_t es, int extra_in_shap
   return (in * (1 + extra_in_shaped) + out) * es + (double)s.Cout * s.Cin * s.kh * s.kw * es;
 }
 
+// ---- squeeze-excitation (mbconv.hip): the chain the MBConv plan runs behind a depthwise unit, shared with the op-level entry
+// points mmskin_se_* so that a test of the chain runs the plan's own launches.  Channels are padded to Cp = pad64(C).
+struct SEArgs {
+  int N, HW, C, Cp, Csq;
+  const float* w1p;   // fc1 weight padded to [Csq][Cp]
+  const float* b1;    // fc1 bias [Csq]
+  const float* w2p;   // fc2 weight padded to [Cp][Csq]
+  const float* b2p;   // fc2 bias padded to [Cp]
+  float *s, *z1, *a1, *z2, *g;   // fp32 activations kept for backward: [N][Cp], [N][Csq], [N][Csq], [N][Cp], [N][Cp]
+};
+// floats of backward temporaries: dgate / dz2 / ds [N][Cp] x3, da1 / dz1 [N][Csq] x2, dW1p, dW2p, db2p (+ [N][Csq] slack)
+static inline size_t se_backward_tmp_floats(int N, int Cp, int Csq) {
+  return (size_t)3 * N * Cp + (size_t)2 * N * Csq + (size_t)2 * Csq * Cp + Cp + (size_t)N * Csq;
+}
+// yse = y * sigmoid(fc2(silu(fc1(mean_hw y))))          (prof may be null)
+template <typename T>
+int se_forward(const SEArgs& a, const T* y, T* yse, Profiler* prof, hipStream_t st);
+// dyse -> dy = dyse * g + ds / HW, and the unpadded parameter gradients dW1 [Csq][C], db1 [Csq], dW2 [C][Csq], db2 [C]
+template <typename T>
+int se_backward(const SEArgs& a, const T* dyse, const T* y, float* tmp, float* dW1, float* db1, float* dW2, float* db2, T* dy,
+                Profiler* prof, hipStream_t st);
+
 // plan factories (create() needs no GPU); return nullptr and set *rc on failure
 PlanBase* make_resnet_plan(int arch, int N, int H, int W, int dtype, int* rc);
 PlanBase* make_densenet_plan(int N, int H, int W, int dtype, bool feature_map, int* rc);

@@ -74,6 +74,18 @@ _SIGNATURES = {
     "mmskin_batchnorm_workspace_bytes": (_i64, [_i] * 4),
     "mmskin_batchnorm_forward": (_i, [_P] * 8 + [_i] * 4 + [_f, _f, _i, _i, _P, _P]),
     "mmskin_batchnorm_backward": (_i, [_P] * 9 + [_i] * 6 + [_P, _P]),
+    "mmskin_dwconv2d_workspace_bytes": (_i64, [_i] * 6),
+    "mmskin_dwconv2d_forward": (_i, [_P] * 3 + [_i] * 8 + [_P, _P]),
+    "mmskin_dwconv2d_backward": (_i, [_P] * 5 + [_i] * 8 + [_P, _P]),
+    "mmskin_batchnorm_act_workspace_bytes": (_i64, [_i] * 4),
+    "mmskin_batchnorm_act_forward": (_i, [_P] * 9 + [_i] * 4 + [_f, _f, _i, _i, _P, _P]),
+    "mmskin_batchnorm_act_backward": (_i, [_P] * 11 + [_i] * 7 + [_P, _P]),
+    "mmskin_se_workspace_bytes": (_i64, [_i] * 4),
+    "mmskin_se_forward": (_i, [_P] * 6 + [_i] * 6 + [_P, _P]),
+    "mmskin_se_backward": (_i, [_P] * 11 + [_i] * 6 + [_P, _P]),
+    "mmskin_sd_workspace_bytes": (_i64, [_i, _i64]),
+    "mmskin_sd_forward": (_i, [_P] * 4 + [_i, _i64, _i, _P, _P]),
+    "mmskin_sd_backward": (_i, [_P] * 3 + [_i, _i64, _i, _P, _P]),
     "mmskin_stem_workspace_bytes": (_i64, [_i] * 3),
     "mmskin_stem_forward": (_i, [_P] * 5 + [_i] * 3 + [_f, _i, _P, _P]),
     "mmskin_stem_backward": (_i, [_P] * 8 + [_i] * 3 + [_f, _i, _P, _P]),
