@@ -4,6 +4,8 @@
 #include <stdarg.h>
 #include <string.h>
 
+#include <algorithm>
+
 #include "../../include/mmskin.h"
 #include "conv.h"
 #include "ops.h"
@@ -42,91 +44,144 @@ int stage_one(const float* w, int Cout, int Cin, int taps, bool stem, T* wfwd, T
   return stage_weights<T>(table_dev, 1, Cout * Cin * taps, w, wfwd, wdgrad, wdgrad != nullptr, st);
 }
 
+// Op-level workspaces: one layout struct per op family.  Its constructor carves the regions; on a null base it only sizes them, and
+// ws_bytes() is how every mmskin_*_workspace_bytes asks.  The size functions take no dtype, so they size with T = float: each take of the
+// bf16_t instantiation is no larger and Carver's alignment is monotone, so every bf16 region ends at or before its float counterpart.
+template <class Ws, class... A>
+int64_t ws_bytes(A... a) { return (int64_t)Ws(nullptr, a...).total; }
+
+// the weight-gradient slab of the shapes the weight-gradient kernels take (the others are rejected at launch and need none)
+inline size_t conv_slab_floats(const ConvShape& s) {
+  return (s.Cout % 64 == 0 && (s.Cin * s.kh * s.kw) % 64 == 0) ? conv_wgrad_slab_bytes(s) / sizeof(float) : 0;
+}
+
+template <typename T>
+struct ConvWs {
+  StageDesc* table; T *xh, *wf, *yh, *wd, *dxh; float* slab; size_t total;   // yh: NHWC output (forward) or dy (backward)
+  ConvWs(void* ws, const ConvShape& s) {
+    Carver c(ws);
+    const size_t in = (size_t)s.N * s.H * s.W * s.Cin, wgt = (size_t)s.Cout * s.Cin * s.kh * s.kw;
+    table = c.take<StageDesc>(1);
+    xh = c.take<T>(in); wf = c.take<T>(wgt); yh = c.take<T>((size_t)s.N * s.OH() * s.OW() * s.Cout);
+    wd = c.take<T>(wgt); dxh = c.take<T>(in); slab = c.take<float>(conv_slab_floats(s));
+    total = c.cur;
+  }
+};
+// the weight-gradient timer writes an fp32 dw, which ConvWs<bf16_t>'s weight regions are too small for
+template <typename T>
+struct WgradTimeWs {
+  T *xh, *yh; float *dw, *slab; size_t total;
+  WgradTimeWs(void* ws, const ConvShape& s) {
+    Carver c(ws);
+    xh = c.take<T>((size_t)s.N * s.H * s.W * s.Cin); yh = c.take<T>((size_t)s.N * s.OH() * s.OW() * s.Cout);
+    dw = c.take<float>((size_t)s.Cout * s.Cin * s.kh * s.kw); slab = c.take<float>(conv_slab_floats(s));
+    total = c.cur;
+  }
+};
+
 template <typename T>
 int conv_fwd_op(const float* x, const float* w, float* y, const ConvShape& s, void* ws, hipStream_t st) {
-  Carver c(ws);
-  StageDesc* table = c.take<StageDesc>(1);
-  T* xh = c.take<T>((size_t)s.N * s.H * s.W * s.Cin);
-  T* wf = c.take<T>((size_t)s.Cout * s.Cin * s.kh * s.kw);
-  T* yh = c.take<T>((size_t)s.N * s.OH() * s.OW() * s.Cout);
+  ConvWs<T> c(ws, s);
   int rc;
-  if ((rc = nchw_to_nhwc<T>(x, s.N, s.Cin, s.H, s.W, xh, st))) return rc;
-  if ((rc = stage_one<T>(w, s.Cout, s.Cin, s.kh * s.kw, false, wf, (T*)nullptr, table, st))) return rc;
-  if ((rc = launch_conv_fwd<T>(s, xh, wf, yh, nullptr, nullptr, st))) return rc;
-  return nhwc_to_nchw<T>(yh, s.N, s.Cout, s.OH(), s.OW(), y, st);
+  if ((rc = nchw_to_nhwc<T>(x, s.N, s.Cin, s.H, s.W, c.xh, st))) return rc;
+  if ((rc = stage_one<T>(w, s.Cout, s.Cin, s.kh * s.kw, false, c.wf, (T*)nullptr, c.table, st))) return rc;
+  if ((rc = launch_conv_fwd<T>(s, c.xh, c.wf, c.yh, nullptr, nullptr, st))) return rc;
+  return nhwc_to_nchw<T>(c.yh, s.N, s.Cout, s.OH(), s.OW(), y, st);
 }
 
 template <typename T>
 int conv_bwd_op(const float* dy, const float* x, const float* w, float* dx, float* dw, const ConvShape& s, void* ws,
                 hipStream_t st) {
-  Carver c(ws);
-  StageDesc* table = c.take<StageDesc>(1);
-  T* xh = c.take<T>((size_t)s.N * s.H * s.W * s.Cin);
-  T* wf = c.take<T>((size_t)s.Cout * s.Cin * s.kh * s.kw);
-  T* yh = c.take<T>((size_t)s.N * s.OH() * s.OW() * s.Cout);  // dy in NHWC
-  T* wd = c.take<T>((size_t)s.Cout * s.Cin * s.kh * s.kw);
-  T* dxh = c.take<T>((size_t)s.N * s.H * s.W * s.Cin);
-  float* slab = c.take<float>(conv_wgrad_slab_bytes(s) / sizeof(float));
+  ConvWs<T> c(ws, s);
   int rc;
-  if ((rc = nchw_to_nhwc<T>(dy, s.N, s.Cout, s.OH(), s.OW(), yh, st))) return rc;
+  if ((rc = nchw_to_nhwc<T>(dy, s.N, s.Cout, s.OH(), s.OW(), c.yh, st))) return rc;
   if (dx) {
-    if ((rc = stage_one<T>(w, s.Cout, s.Cin, s.kh * s.kw, false, wf, wd, table, st))) return rc;
-    if ((rc = launch_conv_dgrad<T>(s, yh, wd, dxh, (const T*)nullptr, st))) return rc;
-    if ((rc = nhwc_to_nchw<T>(dxh, s.N, s.Cin, s.H, s.W, dx, st))) return rc;
+    if ((rc = stage_one<T>(w, s.Cout, s.Cin, s.kh * s.kw, false, c.wf, c.wd, c.table, st))) return rc;
+    if ((rc = launch_conv_dgrad<T>(s, c.yh, c.wd, c.dxh, (const T*)nullptr, st))) return rc;
+    if ((rc = nhwc_to_nchw<T>(c.dxh, s.N, s.Cin, s.H, s.W, dx, st))) return rc;
   }
   if (dw) {
-    if ((rc = nchw_to_nhwc<T>(x, s.N, s.Cin, s.H, s.W, xh, st))) return rc;
-    if ((rc = launch_conv_wgrad<T>(s, yh, xh, slab, dw, st))) return rc;
+    if ((rc = nchw_to_nhwc<T>(x, s.N, s.Cin, s.H, s.W, c.xh, st))) return rc;
+    if ((rc = launch_conv_wgrad<T>(s, c.yh, c.xh, c.slab, dw, st))) return rc;
   }
   return MMSKIN_OK;
 }
 
+// Average microseconds per launch of `run` (0 = launched) on stream st: three warm-up launches, then `iters` between an event pair.
+// -1.0 when a launch or an event call fails; both events are destroyed on every path.
+template <class F>
+static double time_launches(F run, int iters, hipStream_t st) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  float ms = 0.f;
+  bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+  for (int i = 0; ok && i < 3; ++i) ok = run() == 0;
+  ok = ok && hipEventRecord(e0, st) == hipSuccess;
+  for (int i = 0; ok && i < iters; ++i) ok = run() == 0;
+  ok = ok && hipEventRecord(e1, st) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  return ok ? (double)ms * 1e3 / iters : -1.0;
+}
+enum { TIME_FWD, TIME_DGRAD, TIME_WGRAD };
+template <typename T>
+double conv_time(int op, const ConvShape& s, int iters, void* ws, hipStream_t st) {
+  ConvWs<T> c(ws, s);
+  WgradTimeWs<T> g(ws, s);
+  if (op == TIME_FWD) return time_launches([&] { return launch_conv_fwd<T>(s, c.xh, c.wf, c.yh, nullptr, nullptr, st); }, iters, st);
+  if (op == TIME_DGRAD) return time_launches([&] { return launch_conv_dgrad<T>(s, c.yh, c.wd, c.dxh, (const T*)nullptr, st); }, iters, st);
+  return time_launches([&] { return launch_conv_wgrad<T>(s, g.yh, g.xh, g.slab, g.dw, st); }, iters, st);
+}
+
+template <typename T>
+struct BnWs {
+  T *xh, *yh, *dxh; float *ssum, *ssq, *partial, *coef; size_t total;   // yh: y (forward) or dy (backward)
+  BnWs(void* ws, int N, int C, int H, int W) {
+    Carver c(ws);
+    const size_t rows = (size_t)N * H * W;
+    xh = c.take<T>(rows * C); yh = c.take<T>(rows * C); dxh = c.take<T>(rows * C);
+    ssum = c.take<float>((size_t)column_stats_rows(rows, C) * C);
+    ssq = c.take<float>((size_t)column_stats_rows(rows, C) * C);
+    partial = c.take<float>((size_t)bn_bwd_partial_rows(rows, C) * 2 * C);
+    coef = c.take<float>(5 * (size_t)C);   // forward: scale, shift; backward: + cA, cB, cC
+    total = c.cur;
+  }
+};
+
 template <typename T>
 int bn_fwd_op(const float* x, const float* gamma, const float* beta, float* rm, float* rv, float* y, float* save_mean,
               float* save_invstd, int N, int C, int H, int W, float eps, float mom, int relu, void* ws, hipStream_t st) {
-  Carver c(ws);
+  BnWs<T> s(ws, N, C, H, W);
   const size_t rows = (size_t)N * H * W;
-  T* xh = c.take<T>(rows * C);
-  T* yh = c.take<T>(rows * C);
-  float* ssum = c.take<float>((size_t)column_stats_rows(rows, C) * C);
-  float* ssq = c.take<float>((size_t)column_stats_rows(rows, C) * C);
-  float* coef = c.take<float>(2 * (size_t)C);
   int rc, nr = 0;
-  if ((rc = nchw_to_nhwc<T>(x, N, C, H, W, xh, st))) return rc;
-  if ((rc = column_stats<T>(xh, rows, C, ssum, ssq, &nr, st))) return rc;
-  if ((rc = bn_finalize(ssum, ssq, nr, C, (double)rows, gamma, beta, eps, mom, rm, rv, coef, coef + C, save_mean,
+  if ((rc = nchw_to_nhwc<T>(x, N, C, H, W, s.xh, st))) return rc;
+  if ((rc = column_stats<T>(s.xh, rows, C, s.ssum, s.ssq, &nr, st))) return rc;
+  if ((rc = bn_finalize(s.ssum, s.ssq, nr, C, (double)rows, gamma, beta, eps, mom, rm, rv, s.coef, s.coef + C, save_mean,
                         save_invstd, nullptr, st))) return rc;
-  if ((rc = bn_apply<T>(xh, nullptr, coef, coef + C, nullptr, nullptr, yh, rows, C, relu != 0, st))) return rc;
-  return nhwc_to_nchw<T>(yh, N, C, H, W, y, st);
+  if ((rc = bn_apply<T>(s.xh, nullptr, s.coef, s.coef + C, nullptr, nullptr, s.yh, rows, C, relu != 0, st))) return rc;
+  return nhwc_to_nchw<T>(s.yh, N, C, H, W, y, st);
 }
 
 template <typename T>
 int bn_bwd_op(const float* dy, const float* x, const float* gamma, const float* beta, const float* save_mean,
               const float* save_invstd, float* dx, float* dgamma, float* dbeta, int N, int C, int H, int W, int relu,
               void* ws, hipStream_t st) {
-  Carver c(ws);
+  BnWs<T> s(ws, N, C, H, W);
   const size_t rows = (size_t)N * H * W;
-  T* xh = c.take<T>(rows * C);
-  T* dyh = c.take<T>(rows * C);
-  float* partial = c.take<float>((size_t)bn_bwd_partial_rows(rows, C) * 2 * C);
-  float* tail = c.take<float>((size_t)bn_bwd_partial_rows(rows, C) * C);  // keep layout equal to bn_fwd_op's
-  (void)tail;
-  float* coef = c.take<float>(5 * (size_t)C);
-  T* dxh = c.take<T>(rows * C);
+  float* coef = s.coef;
   int rc;
-  if ((rc = nchw_to_nhwc<T>(x, N, C, H, W, xh, st))) return rc;
-  if ((rc = nchw_to_nhwc<T>(dy, N, C, H, W, dyh, st))) return rc;
+  if ((rc = nchw_to_nhwc<T>(x, N, C, H, W, s.xh, st))) return rc;
+  if ((rc = nchw_to_nhwc<T>(dy, N, C, H, W, s.yh, st))) return rc;
   hipLaunchKernelGGL(coef_from_saved_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, st, C, gamma, beta, save_mean,
                      save_invstd, coef, coef + C);
   HIP_CHECK_RET(hipGetLastError());
   const int mode = relu ? MASK_FROM_X : MASK_NONE;
   int nr = 0;
-  if ((rc = bn_bwd_reduce<T>(dyh, xh, nullptr, coef, coef + C, mode, rows, C, partial, &nr, st))) return rc;
-  if ((rc = bn_bwd_finalize(partial, nr, C, (double)rows, gamma, save_mean, save_invstd,
+  if ((rc = bn_bwd_reduce<T>(s.yh, s.xh, nullptr, coef, coef + C, mode, rows, C, s.partial, &nr, st))) return rc;
+  if ((rc = bn_bwd_finalize(s.partial, nr, C, (double)rows, gamma, save_mean, save_invstd,
                             dgamma, dbeta, coef + 2 * C, coef + 3 * C, coef + 4 * C, nullptr, st))) return rc;
-  if ((rc = bn_bwd_apply<T>(dyh, xh, nullptr, coef, coef + C, mode, coef + 2 * C, coef + 3 * C, coef + 4 * C, dxh,
+  if ((rc = bn_bwd_apply<T>(s.yh, s.xh, nullptr, coef, coef + C, mode, coef + 2 * C, coef + 3 * C, coef + 4 * C, s.dxh,
                             (T*)nullptr, rows, C, st))) return rc;
-  return nhwc_to_nchw<T>(dxh, N, C, H, W, dx, st);
+  return nhwc_to_nchw<T>(s.dxh, N, C, H, W, dx, st);
 }
 
 struct StemGeom {
@@ -264,8 +319,9 @@ int dw_bwd_op(const float* dy, const float* x, const float* w, float* dx, float*
 template <typename T>
 struct BnActWs {
   T *xh, *yh, *rh, *dyh, *dxh, *dzh; float *ssum, *ssq, *tab, *coef, *partial; size_t total;
-  BnActWs(void* ws, size_t rows, int C) {
+  BnActWs(void* ws, int N, int C, int H, int W) {
     Carver c(ws);
+    const size_t rows = (size_t)N * H * W;
     xh = c.take<T>(rows * C); yh = c.take<T>(rows * C); rh = c.take<T>(rows * C);
     dyh = c.take<T>(rows * C); dxh = c.take<T>(rows * C); dzh = c.take<T>(rows * C);
     ssum = c.take<float>((size_t)column_stats_rows(rows, C) * C);
@@ -284,7 +340,7 @@ template <typename T>
 int bn_act_fwd_op(const float* x, const float* res, const float* gamma, const float* beta, float* rm, float* rv, float* y, float* save_mean,
                   float* save_invstd, int N, int C, int H, int W, float eps, float mom, int act, void* ws, hipStream_t st) {
   const size_t rows = (size_t)N * H * W;
-  BnActWs<T> s(ws, rows, C);
+  BnActWs<T> s(ws, N, C, H, W);
   int rc, nr = 0;
   if ((rc = nchw_to_nhwc<T>(x, N, C, H, W, s.xh, st))) return rc;
   if (res && (rc = nchw_to_nhwc<T>(res, N, C, H, W, s.rh, st))) return rc;
@@ -303,7 +359,7 @@ int bn_act_bwd_op(const float* dy, const float* x, const float* y, const float* 
                   const float* save_invstd, float* dx, float* dres, float* dgamma, float* dbeta, int N, int C, int H, int W, int act,
                   void* ws, hipStream_t st) {
   const size_t rows = (size_t)N * H * W;
-  BnActWs<T> s(ws, rows, C);
+  BnActWs<T> s(ws, N, C, H, W);
   int rc, nr = 0;
   if ((rc = nchw_to_nhwc<T>(x, N, C, H, W, s.xh, st))) return rc;
   if ((rc = nchw_to_nhwc<T>(y, N, C, H, W, s.yh, st))) return rc;   // the forward's stored y: exact in T, MASK_FROM_Y6 reads it
@@ -376,17 +432,51 @@ int se_bwd_op(const float* dyse, const float* y, const float* w1, const float* b
 
 // flat [N][per_sample] fp32 <-> T (the converters with H = W = 1 are plain element-type conversions)
 template <typename T>
+struct SdWs {
+  T *ah, *rh, *oh; size_t total;
+  SdWs(void* ws, int N, int64_t per) {
+    Carver c(ws);
+    ah = c.take<T>((size_t)N * per); rh = c.take<T>((size_t)N * per); oh = c.take<T>((size_t)N * per);
+    total = c.cur;
+  }
+};
+template <typename T>
 int sd_op(const float* a, const float* res, const float* mask, float* out, int N, int64_t per, void* ws, hipStream_t st) {
-  Carver c(ws);
-  T* ah = c.take<T>((size_t)N * per); T* rh = c.take<T>((size_t)N * per); T* oh = c.take<T>((size_t)N * per);
+  SdWs<T> s(ws, N, per);
   int rc;
-  if ((rc = nchw_to_nhwc<T>(a, N, (int)per, 1, 1, ah, st))) return rc;
+  if ((rc = nchw_to_nhwc<T>(a, N, (int)per, 1, 1, s.ah, st))) return rc;
   if (res) {
-    if ((rc = nchw_to_nhwc<T>(res, N, (int)per, 1, 1, rh, st))) return rc;
-    if ((rc = sd_residual_add<T>(ah, rh, mask, N, (size_t)per, oh, st))) return rc;
-  } else if ((rc = sd_row_scale<T>(ah, mask, N, (size_t)per, oh, st))) return rc;
-  return nhwc_to_nchw<T>(oh, N, (int)per, 1, 1, out, st);
+    if ((rc = nchw_to_nhwc<T>(res, N, (int)per, 1, 1, s.rh, st))) return rc;
+    if ((rc = sd_residual_add<T>(s.ah, s.rh, mask, N, (size_t)per, s.oh, st))) return rc;
+  } else if ((rc = sd_row_scale<T>(s.ah, mask, N, (size_t)per, s.oh, st))) return rc;
+  return nhwc_to_nchw<T>(s.oh, N, (int)per, 1, 1, out, st);
 }
+
+// algebraic BatchNorm backward of an expanding 1x1 convolution (abn_backward_impl); the slab serves whichever Gram launch mode runs
+struct AbnWs {
+  bf16_t *gh, *yh, *dyh, *wd; float *bias, *coef, *S, *cs, *gram, *slab; size_t total;
+  AbnWs(void* ws, int N, int Cw, int C4, int H, int W) {
+    Carver c(ws);
+    const size_t M = (size_t)N * H * W;
+    gh = c.take<bf16_t>(M * C4); yh = c.take<bf16_t>(M * Cw); dyh = c.take<bf16_t>(M * Cw);
+    wd = c.take<bf16_t>((size_t)Cw * (C4 + Cw)); bias = c.take<float>(Cw); coef = c.take<float>(3 * (size_t)C4);
+    S = c.take<float>(((size_t)C4 + 256) * Cw); cs = c.take<float>(256); gram = c.take<float>((size_t)256 * Cw);
+    size_t sb = 0;
+    for (int mode = 0; mode < 3; ++mode) sb = std::max(sb, wgrad_gram_slab_bytes((int)M, mode == 2 ? 0 : C4, Cw, mode));
+    slab = c.take<float>(sb / sizeof(float));
+    total = c.cur;
+  }
+};
+struct GramStatsWs {
+  bf16_t* yh; float *gram, *cs, *slab; size_t total;
+  GramStatsWs(void* ws, int N, int Cw, int C4, int H, int W) {
+    Carver c(ws);
+    const size_t M = (size_t)N * H * W;
+    yh = c.take<bf16_t>(M * Cw); gram = c.take<float>((size_t)256 * Cw); cs = c.take<float>(256);
+    slab = c.take<float>(wgrad_gram_slab_bytes((int)M, 0, Cw, 2) / sizeof(float));
+    total = c.cur;
+  }
+};
 
 }  // namespace
 
@@ -397,10 +487,7 @@ int mmskin_version(void) { return 100; }
 
 int64_t mmskin_conv2d_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad) {
   ConvShape s = {N, H, W, Cin, Cout, kh, kw, stride, pad};
-  size_t in = (size_t)N * H * W * Cin * 4, out = (size_t)N * s.OH() * s.OW() * Cout * 4;
-  size_t wgt = (size_t)Cout * Cin * kh * kw * 4;
-  size_t slab = (Cout % 64 == 0 && (Cin * kh * kw) % 64 == 0) ? conv_wgrad_slab_bytes(s) : 0;
-  return (int64_t)(2 * in + out + 2 * wgt + slab + 16 * 256);
+  return std::max(ws_bytes<ConvWs<float>>(s), ws_bytes<WgradTimeWs<float>>(s));   // the ops, dgrad_fused and the three timers
 }
 
 #define DISPATCH(dtype, call_f32, call_bf16)                            \
@@ -444,23 +531,17 @@ int mmskin_conv2d_dgrad_fused(const float* dy, const float* w, const float* xc, 
   ARG_CHECK(dy && w && xc && scale && shift && dz && partial && rows_written && workspace, "conv2d_dgrad_fused: null argument");
   ConvShape s = {N, H, W, Cin, Cout, kh, kw, stride, pad};
   hipStream_t st = (hipStream_t)stream;
-  Carver c(workspace);
   typedef bf16_t T;
-  StageDesc* table = c.take<StageDesc>(1);
-  T* xh = c.take<T>((size_t)N * H * W * Cin);
-  T* wf = c.take<T>((size_t)Cout * Cin * kh * kw);
-  T* yh = c.take<T>((size_t)N * s.OH() * s.OW() * Cout);
-  T* wd = c.take<T>((size_t)Cout * Cin * kh * kw);
-  T* dxh = c.take<T>((size_t)N * H * W * Cin);
+  ConvWs<T> c(workspace, s);
   int rc;
-  if ((rc = nchw_to_nhwc<T>(dy, N, Cout, s.OH(), s.OW(), yh, st))) return rc;
-  if ((rc = nchw_to_nhwc<T>(xc, N, Cin, H, W, xh, st))) return rc;
-  if ((rc = stage_one<T>(w, Cout, Cin, kh * kw, false, wf, wd, table, st))) return rc;
+  if ((rc = nchw_to_nhwc<T>(dy, N, Cout, s.OH(), s.OW(), c.yh, st))) return rc;
+  if ((rc = nchw_to_nhwc<T>(xc, N, Cin, H, W, c.xh, st))) return rc;
+  if ((rc = stage_one<T>(w, Cout, Cin, kh * kw, false, c.wf, c.wd, c.table, st))) return rc;
   DgradFuse f;
-  f.x = xh; f.scale = scale; f.shift = shift; f.partial = partial;
-  if ((rc = launch_conv_dgrad<T>(s, yh, wd, dxh, (const T*)nullptr, st, &f))) return rc;
+  f.x = c.xh; f.scale = scale; f.shift = shift; f.partial = partial;
+  if ((rc = launch_conv_dgrad<T>(s, c.yh, c.wd, c.dxh, (const T*)nullptr, st, &f))) return rc;
   *rows_written = f.rows_written;
-  return nhwc_to_nchw<T>(dxh, N, Cin, H, W, dz, st);
+  return nhwc_to_nchw<T>(c.dxh, N, Cin, H, W, dz, st);
 }
 
 /* timing helper: runs the forward conv kernel `iters` times on NHWC buffers already resident in the
@@ -468,100 +549,44 @@ int mmskin_conv2d_dgrad_fused(const float* dy, const float* w, const float* xc, 
 double mmskin_conv2d_time(int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int dtype,
                           int iters, void* workspace, void* stream) {
   ConvShape s = {N, H, W, Cin, Cout, kh, kw, stride, pad};
-  hipStream_t st = (hipStream_t)stream;
-  Carver c(workspace);
-  size_t es = dtype == MMSKIN_BF16 ? 2 : 4;
-  unsigned char* xh = c.take<unsigned char>((size_t)N * H * W * Cin * es);
-  unsigned char* wf = c.take<unsigned char>((size_t)Cout * Cin * kh * kw * es);
-  unsigned char* yh = c.take<unsigned char>((size_t)N * s.OH() * s.OW() * Cout * es);
-  hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1.0;
-  auto run = [&]() -> int {
-    if (dtype == MMSKIN_BF16) return launch_conv_fwd<bf16_t>(s, (bf16_t*)xh, (bf16_t*)wf, (bf16_t*)yh, nullptr, nullptr, st);
-    return launch_conv_fwd<float>(s, (float*)xh, (float*)wf, (float*)yh, nullptr, nullptr, st);
-  };
-  for (int i = 0; i < 3; ++i) if (run()) return -1.0;
-  (void)hipEventRecord(e0, st);
-  for (int i = 0; i < iters; ++i) if (run()) return -1.0;
-  (void)hipEventRecord(e1, st);
-  (void)hipEventSynchronize(e1);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  return (double)ms * 1e3 / iters;
+  return dtype == MMSKIN_BF16 ? conv_time<bf16_t>(TIME_FWD, s, iters, workspace, ST(stream)) : conv_time<float>(TIME_FWD, s, iters, workspace, ST(stream));
 }
 
 /* same for the data-gradient launch (no fused epilogue; stride-2 layers run as parity classes) */
 double mmskin_conv2d_dgrad_time(int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int dtype,
                                 int iters, void* workspace, void* stream) {
   ConvShape s = {N, H, W, Cin, Cout, kh, kw, stride, pad};
-  hipStream_t st = (hipStream_t)stream;
-  Carver c(workspace);
-  size_t es = dtype == MMSKIN_BF16 ? 2 : 4;
-  unsigned char* xh = c.take<unsigned char>((size_t)N * H * W * Cin * es);
-  unsigned char* wt = c.take<unsigned char>((size_t)Cout * Cin * kh * kw * es);
-  unsigned char* yh = c.take<unsigned char>((size_t)N * s.OH() * s.OW() * Cout * es);
-  hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1.0;
-  auto run = [&]() -> int {
-    if (dtype == MMSKIN_BF16) return launch_conv_dgrad<bf16_t>(s, (bf16_t*)yh, (bf16_t*)wt, (bf16_t*)xh, (const bf16_t*)nullptr, st);
-    return launch_conv_dgrad<float>(s, (float*)yh, (float*)wt, (float*)xh, (const float*)nullptr, st);
-  };
-  for (int i = 0; i < 3; ++i) if (run()) return -1.0;
-  (void)hipEventRecord(e0, st);
-  for (int i = 0; i < iters; ++i) if (run()) return -1.0;
-  (void)hipEventRecord(e1, st);
-  (void)hipEventSynchronize(e1);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  return (double)ms * 1e3 / iters;
+  return dtype == MMSKIN_BF16 ? conv_time<bf16_t>(TIME_DGRAD, s, iters, workspace, ST(stream)) : conv_time<float>(TIME_DGRAD, s, iters, workspace, ST(stream));
 }
 
 /* Algebraic BatchNorm backward of an expanding 1x1 convolution (abn.hip), op level: g [N,C4,H,W] is the (masked) gradient of the
  * BatchNorm output, y [N,Cw,H,W] the convolution's input, w [C4,Cw] its weight, cA / cB / cC [C4] the BatchNorm-backward coefficients
  * (dz = cA g + cB x + cC, x = conv(y)).  Returns dy = dz W [N,Cw,H,W] and dw = dz^T y [C4,Cw] without forming dz or x. */
 int64_t mmskin_abn_workspace_bytes(int N, int Cw, int C4, int H, int W) {
-  const size_t M = (size_t)N * H * W;
-  size_t b = 4096 + M * C4 * 2 + 2 * M * Cw * 2 + (size_t)Cw * (C4 + Cw) * 2 + 4 * (size_t)Cw + 12 * (size_t)C4;
-  b += 2 * wgrad_gram_slab_bytes((int)M, C4, Cw) + wgrad_gram_slab_bytes((int)M, 0, Cw, 2) + ((size_t)C4 + 512) * Cw * 4 + 32 * 256;
-  return (int64_t)b;
+  return std::max(ws_bytes<AbnWs>(N, Cw, C4, H, W), ws_bytes<GramStatsWs>(N, Cw, C4, H, W));   // serves mmskin_conv1x1_gram_stats too
 }
 static int abn_backward_impl(const float* g, const float* y, const float* w, const float* cA, const float* cB, const float* cC, int N, int Cw,
                              int C4, int H, int W, float* dy, float* dw, void* workspace, hipStream_t st, bool kept_gram) {
-  Carver c(workspace);
   const size_t M = (size_t)N * H * W;
   ARG_CHECK(wgrad_gram_slab_bytes((int)M, C4, Cw) > 0 && (!kept_gram || (wgrad_gram_slab_bytes((int)M, C4, Cw, 1) > 0 && wgrad_gram_slab_bytes((int)M, 0, Cw, 2) > 0)),
             "abn_backward: shape C4=%d Cw=%d unsupported", C4, Cw);
-  bf16_t* gh = c.take<bf16_t>(M * C4);
-  bf16_t* yh = c.take<bf16_t>(M * Cw);
-  bf16_t* dyh = c.take<bf16_t>(M * Cw);
-  bf16_t* wd = c.take<bf16_t>((size_t)Cw * (C4 + Cw));
-  float* bias = c.take<float>(Cw);
-  float* coef = c.take<float>(3 * (size_t)C4);
-  float* S = c.take<float>(((size_t)C4 + 256) * Cw);
-  float* cs = c.take<float>(256);
-  float* gram = c.take<float>((size_t)256 * Cw);
-  size_t sb = wgrad_gram_slab_bytes((int)M, C4, Cw);
-  if (wgrad_gram_slab_bytes((int)M, C4, Cw, 1) > sb) sb = wgrad_gram_slab_bytes((int)M, C4, Cw, 1);
-  if (wgrad_gram_slab_bytes((int)M, 0, Cw, 2) > sb) sb = wgrad_gram_slab_bytes((int)M, 0, Cw, 2);
-  float* slab = c.take<float>(sb / sizeof(float));
+  AbnWs a(workspace, N, Cw, C4, H, W);
   int rc;
-  if ((rc = nchw_to_nhwc<bf16_t>(g, N, C4, H, W, gh, st))) return rc;
-  if ((rc = nchw_to_nhwc<bf16_t>(y, N, Cw, H, W, yh, st))) return rc;
-  if ((rc = abn_prep(w, cA, cB, cC, C4, Cw, wd, bias, coef, st))) return rc;
+  if ((rc = nchw_to_nhwc<bf16_t>(g, N, C4, H, W, a.gh, st))) return rc;
+  if ((rc = nchw_to_nhwc<bf16_t>(y, N, Cw, H, W, a.yh, st))) return rc;
+  if ((rc = abn_prep(w, cA, cB, cC, C4, Cw, a.wd, a.bias, a.coef, st))) return rc;
   ConvShape s = {N, H, W, Cw, C4, 1, 1, 1, 0};
   DgradFuse f;
-  f.in2 = yh; f.k2 = Cw; f.bias = bias;
-  if ((rc = launch_conv_dgrad<bf16_t>(s, gh, wd, dyh, (const bf16_t*)nullptr, st, &f))) return rc;
-  if ((rc = nhwc_to_nchw<bf16_t>(dyh, N, Cw, H, W, dy, st))) return rc;
+  f.in2 = a.yh; f.k2 = Cw; f.bias = a.bias;
+  if ((rc = launch_conv_dgrad<bf16_t>(s, a.gh, a.wd, a.dyh, (const bf16_t*)nullptr, st, &f))) return rc;
+  if ((rc = nhwc_to_nchw<bf16_t>(a.dyh, N, Cw, H, W, dy, st))) return rc;
   if (kept_gram) {   // the two-pass forward's order: y^T y + colsum(y) first (forward), g^T y alone later
-    if ((rc = launch_wgrad_gram(N, H, W, Cw, C4, nullptr, yh, slab, gram, cs, st, 2))) return rc;
-    if ((rc = launch_wgrad_gram(N, H, W, Cw, C4, gh, yh, slab, S, nullptr, st, 1))) return rc;
-    return abn_wgrad_finalize(S, cs, w, coef, C4, Cw, dw, st, gram);
+    if ((rc = launch_wgrad_gram(N, H, W, Cw, C4, nullptr, a.yh, a.slab, a.gram, a.cs, st, 2))) return rc;
+    if ((rc = launch_wgrad_gram(N, H, W, Cw, C4, a.gh, a.yh, a.slab, a.S, nullptr, st, 1))) return rc;
+    return abn_wgrad_finalize(a.S, a.cs, w, a.coef, C4, Cw, dw, st, a.gram);
   }
-  if ((rc = launch_wgrad_gram(N, H, W, Cw, C4, gh, yh, slab, S, cs, st))) return rc;
-  return abn_wgrad_finalize(S, cs, w, coef, C4, Cw, dw, st);
+  if ((rc = launch_wgrad_gram(N, H, W, Cw, C4, a.gh, a.yh, a.slab, a.S, a.cs, st))) return rc;
+  return abn_wgrad_finalize(a.S, a.cs, w, a.coef, C4, Cw, dw, st);
 }
 int mmskin_abn_backward(const float* g, const float* y, const float* w, const float* cA, const float* cB, const float* cC, int N, int Cw,
                         int C4, int H, int W, float* dy, float* dw, void* workspace, void* stream) {
@@ -578,50 +603,23 @@ int mmskin_abn_backward_kept_gram(const float* g, const float* y, const float* w
 int mmskin_conv1x1_gram_stats(const float* y, const float* w, int N, int Cw, int C4, int H, int W, float* stat_sum, float* stat_sq,
                               void* workspace, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  Carver c(workspace);
-  const size_t M = (size_t)N * H * W;
-  ARG_CHECK(wgrad_gram_slab_bytes((int)M, 0, Cw, 2) > 0, "conv1x1_gram_stats: Cw=%d unsupported", Cw);
-  bf16_t* yh = c.take<bf16_t>(M * Cw);
-  float* gram = c.take<float>((size_t)256 * Cw);
-  float* cs = c.take<float>(256);
-  float* slab = c.take<float>(wgrad_gram_slab_bytes((int)M, 0, Cw, 2) / sizeof(float));
+  ARG_CHECK(wgrad_gram_slab_bytes(N * H * W, 0, Cw, 2) > 0, "conv1x1_gram_stats: Cw=%d unsupported", Cw);
+  GramStatsWs a(workspace, N, Cw, C4, H, W);
   int rc;
-  if ((rc = nchw_to_nhwc<bf16_t>(y, N, Cw, H, W, yh, st))) return rc;
-  if ((rc = launch_wgrad_gram(N, H, W, Cw, C4, nullptr, yh, slab, gram, cs, st, 2))) return rc;
-  return gram_stats(gram, cs, w, C4, Cw, stat_sum, stat_sq, st);
+  if ((rc = nchw_to_nhwc<bf16_t>(y, N, Cw, H, W, a.yh, st))) return rc;
+  if ((rc = launch_wgrad_gram(N, H, W, Cw, C4, nullptr, a.yh, a.slab, a.gram, a.cs, st, 2))) return rc;
+  return gram_stats(a.gram, a.cs, w, C4, Cw, stat_sum, stat_sq, st);
 }
 
 /* same for the weight-gradient kernel (+ its slab reduction) */
 double mmskin_conv2d_wgrad_time(int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int dtype,
                                 int iters, void* workspace, void* stream) {
   ConvShape s = {N, H, W, Cin, Cout, kh, kw, stride, pad};
-  hipStream_t st = (hipStream_t)stream;
-  Carver c(workspace);
-  size_t es = dtype == MMSKIN_BF16 ? 2 : 4;
-  unsigned char* xh = c.take<unsigned char>((size_t)N * H * W * Cin * es);
-  unsigned char* yh = c.take<unsigned char>((size_t)N * s.OH() * s.OW() * Cout * es);
-  float* dw = c.take<float>((size_t)Cout * Cin * kh * kw);
-  float* slab = c.take<float>(conv_wgrad_slab_bytes(s) / sizeof(float));
-  hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1.0;
-  auto run = [&]() -> int {
-    if (dtype == MMSKIN_BF16) return launch_conv_wgrad<bf16_t>(s, (bf16_t*)yh, (bf16_t*)xh, slab, dw, st);
-    return launch_conv_wgrad<float>(s, (float*)yh, (float*)xh, slab, dw, st);
-  };
-  for (int i = 0; i < 3; ++i) if (run()) return -1.0;
-  (void)hipEventRecord(e0, st);
-  for (int i = 0; i < iters; ++i) if (run()) return -1.0;
-  (void)hipEventRecord(e1, st);
-  (void)hipEventSynchronize(e1);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  return (double)ms * 1e3 / iters;
+  return dtype == MMSKIN_BF16 ? conv_time<bf16_t>(TIME_WGRAD, s, iters, workspace, ST(stream)) : conv_time<float>(TIME_WGRAD, s, iters, workspace, ST(stream));
 }
 
 int64_t mmskin_batchnorm_workspace_bytes(int N, int C, int H, int W) {
-  size_t rows = (size_t)N * H * W;
-  return (int64_t)(3 * rows * C * 4 + (size_t)bn_bwd_partial_rows(rows, C) * 3 * C * 4 + 8 * (size_t)C * 4 + 16 * 256);
+  return ws_bytes<BnWs<float>>(N, C, H, W);
 }
 
 int mmskin_batchnorm_forward(const float* x, const float* gamma, const float* beta, float* running_mean,
@@ -645,8 +643,7 @@ int mmskin_batchnorm_backward(const float* dy, const float* x, const float* gamm
 }
 
 int64_t mmskin_stem_workspace_bytes(int N, int H, int W) {
-  StemWs<float> s(nullptr, N, H, W);
-  return (int64_t)s.total + 4096;
+  return ws_bytes<StemWs<float>>(N, H, W);
 }
 
 int mmskin_stem_forward(const float* x, const float* w, const float* gamma, const float* beta, float* y, int N, int H,
@@ -717,8 +714,7 @@ int mmskin_conv_pos_enc_backward(const float* dy, const float* x, const float* w
                     c_valid >= 1 && c_valid <= C)
 int64_t mmskin_dwconv2d_workspace_bytes(int N, int C, int H, int W, int ksize, int stride) {
   if (!(N > 0 && C > 0 && H > 0 && W > 0 && (ksize == 3 || ksize == 5) && (stride == 1 || stride == 2))) return -1;
-  DwWs<float> s(nullptr, N, C, H, W, ksize, stride);
-  return (int64_t)s.total + 4096;
+  return ws_bytes<DwWs<float>>(N, C, H, W, ksize, stride);
 }
 int mmskin_dwconv2d_forward(const float* x, const float* w, float* y, int N, int C, int H, int W, int ksize, int stride, int c_valid,
                             int dtype, void* workspace, void* stream) {
@@ -738,8 +734,7 @@ int mmskin_dwconv2d_backward(const float* dy, const float* x, const float* w, fl
 
 int64_t mmskin_batchnorm_act_workspace_bytes(int N, int C, int H, int W) {
   if (!(N > 0 && C > 0 && H > 0 && W > 0)) return -1;
-  BnActWs<float> s(nullptr, (size_t)N * H * W, C);
-  return (int64_t)s.total + 4096;
+  return ws_bytes<BnActWs<float>>(N, C, H, W);
 }
 int mmskin_batchnorm_act_forward(const float* x, const float* res, const float* gamma, const float* beta, float* running_mean,
                                  float* running_var, float* y, float* save_mean, float* save_invstd, int N, int C, int H, int W, float eps,
@@ -769,8 +764,7 @@ int mmskin_batchnorm_act_backward(const float* dy, const float* x, const float* 
 #define SE_ARGS_OK (N > 0 && C > 0 && Cp == pad64(C) && Csq > 0 && HW > 0)
 int64_t mmskin_se_workspace_bytes(int N, int Cp, int Csq, int HW) {
   if (!(N > 0 && Cp > 0 && Csq > 0 && HW > 0)) return -1;
-  SeWs<float> s(nullptr, N, Cp, Csq, HW);
-  return (int64_t)s.total + 4096;
+  return ws_bytes<SeWs<float>>(N, Cp, Csq, HW);
 }
 int mmskin_se_forward(const float* y, const float* w1, const float* b1, const float* w2, const float* b2, float* y_se, int N, int C, int Cp,
                       int Csq, int HW, int dtype, void* workspace, void* stream) {
@@ -791,7 +785,7 @@ int mmskin_se_backward(const float* dy_se, const float* y, const float* w1, cons
 
 int64_t mmskin_sd_workspace_bytes(int N, int64_t per_sample) {
   if (!(N > 0 && per_sample > 0)) return -1;
-  return (int64_t)(3 * align_up((size_t)N * per_sample * 4, 256) + 4096);
+  return ws_bytes<SdWs<float>>(N, per_sample);
 }
 int mmskin_sd_forward(const float* branch, const float* res, const float* mask, float* y, int N, int64_t per_sample, int dtype,
                       void* workspace, void* stream) {

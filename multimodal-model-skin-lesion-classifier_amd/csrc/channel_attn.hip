@@ -203,12 +203,19 @@ __global__ __launch_bounds__(256) void channel_attn_bwd_kernel(const float* __re
   }
 }
 
+// The scratch of mmskin_channel_attention_* in floats: one region at offset 0, the 32 x 32 partial products per (batch, group, chunk) that
+// chan_outer_kernel writes when the tokens span more than one chunk.
+struct ChanScratch {
+  int nchunk; int64_t total;
+  ChanScratch(int B, int G, int N) : nchunk((N + CHAN_CHUNK - 1) / CHAN_CHUNK) { total = nchunk > 1 ? (int64_t)B * G * nchunk * 1024 : 0; }
+};
+
 int chan_args(ChanArgs& a, int B, int G, int N, int Dh, int64_t q_tok, int64_t q_b, int64_t o_tok, int64_t o_b, float scale, const char* what) {
   ARG_CHECK(B > 0 && G > 0 && N > 0 && Dh == 32, "%s: needs 32 channels per group (B=%d G=%d N=%d Dh=%d)", what, B, G, N, Dh);
   ARG_CHECK((int64_t)B * G < (int64_t)1 << 30, "%s: too many (batch, group) pairs", what);
   ARG_CHECK(q_tok % 4 == 0 && q_b % 4 == 0 && o_tok % 4 == 0 && o_b % 4 == 0, "%s: strides must keep rows 16-byte aligned", what);
   a.q_tok = q_tok; a.q_b = q_b; a.o_tok = o_tok; a.o_b = o_b; a.G = G; a.N = N; a.scale = scale;
-  a.nchunk = (N + CHAN_CHUNK - 1) / CHAN_CHUNK;
+  a.nchunk = ChanScratch(B, G, N).nchunk;
   return MMSKIN_OK;
 }
 
@@ -216,10 +223,7 @@ int chan_args(ChanArgs& a, int B, int G, int N, int Dh, int64_t q_tok, int64_t q
 
 extern "C" {
 
-int64_t mmskin_channel_attention_scratch_floats(int B, int G, int N) {
-  const int64_t nchunk = (N + CHAN_CHUNK - 1) / CHAN_CHUNK;
-  return nchunk > 1 ? (int64_t)B * G * nchunk * 1024 : 0;
-}
+int64_t mmskin_channel_attention_scratch_floats(int B, int G, int N) { return ChanScratch(B, G, N).total; }
 
 int mmskin_channel_attention_forward(const float* q, const float* k, const float* v, float* x, float* attn, float* scratch, int B, int G,
                                      int N, int Dh, int64_t q_tok, int64_t q_b, int64_t o_tok, int64_t o_b, float scale, void* stream) {

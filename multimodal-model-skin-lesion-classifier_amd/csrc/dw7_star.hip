@@ -209,14 +209,22 @@ __global__ __launch_bounds__(256) void dw7_scalar_finalize_kernel(const float* _
   }
 }
 
+// The backward's scratch as float offsets (packed): per-group weight-gradient partials, then the (ds, db) pairs per group and chunk.
+struct Dw7Scratch {
+  int64_t part_w = 0, part_sb, total;
+  explicit Dw7Scratch(const Geo& g, int C) {
+    part_sb = (int64_t)g.G * 49 * C;
+    total = part_sb + 2 * (int64_t)g.G * g.chunks;
+  }
+};
+
 }  // namespace
 
 extern "C" {
 
 int64_t mmskin_dw7_star_scratch_floats(int N, int H, int W, int C) {
   if (N <= 0 || H <= 0 || W <= 0 || C <= 0) return 0;
-  const Geo g = geo(N, H, W, C);
-  return (int64_t)g.G * 49 * C + 2 * (int64_t)g.G * g.chunks;
+  return Dw7Scratch(geo(N, H, W, C), C).total;
 }
 
 int mmskin_dw7_star_forward(const float* z, const float* w, const float* s, const float* b, float* y, int N, int H, int W, int C,
@@ -236,8 +244,8 @@ int mmskin_dw7_star_backward(const float* dy, const float* z, const float* w, co
   ARG_CHECK(dy && z && w && s && b && scratch && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "dw7_star_backward: bad argument");
   const Geo g = geo(N, H, W, C);
   ARG_CHECK(g.chunks <= 65535, "dw7_star_backward: shape too large");
-  float* part_w = scratch;
-  float* part_sb = scratch + (int64_t)g.G * 49 * C;
+  const Dw7Scratch lay(g, C);
+  float *part_w = scratch + lay.part_w, *part_sb = scratch + lay.part_sb;
   HIP_CHECK_RET(opt_in_dynamic_lds((const void*)dw7_star_bwd_kernel, LDS_BYTES));
   hipLaunchKernelGGL(dw7_star_bwd_kernel, dim3(g.G, g.chunks), dim3(256), LDS_BYTES, ST(stream), dy, z, w, s, b, dz, part_w, part_sb, H, W,
                      C, g.tx, g.tiles, g.ntiles);

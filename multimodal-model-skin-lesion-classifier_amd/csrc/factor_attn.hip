@@ -495,20 +495,26 @@ int fa_reduce(const float* a, int64_t a_tok, int64_t a_b, const float* b, int64_
   return MMSKIN_OK;
 }
 
+// The scratch of mmskin_factor_attention_*, as float offsets (packed): the reduction partials of both directions, then the backward's dF
+// and its position-encoding weight-gradient partials.  mmskin_factor_attention_scratch_floats returns `total`.
+struct FaScratch {
+  int64_t part = 0, dF, wpart, total;
+  FaScratch(int B, int H, int W, int Ch, bool backward) {
+    int64_t per; int ns;
+    fa_strips((int64_t)B * H * W, per, ns);
+    dF = (int64_t)B * FA_HEADS * fa_nchunk(1 + H * W) * fa_part_stride(Ch);
+    wpart = dF + (int64_t)B * FA_HEADS * Ch * Ch;
+    total = backward ? wpart + (int64_t)ns * 50 * FA_HEADS * Ch : dF;
+  }
+};
+
 }  // namespace
 
 extern "C" {
 
 int64_t mmskin_factor_attention_scratch_floats(int B, int H, int W, int Ch, int backward) {
   if (B <= 0 || H <= 0 || W <= 0 || Ch <= 0) return 0;
-  const int N = 1 + H * W;
-  int64_t n = (int64_t)B * FA_HEADS * fa_nchunk(N) * fa_part_stride(Ch);
-  if (backward) {
-    int64_t per; int ns;
-    fa_strips((int64_t)B * H * W, per, ns);
-    n += (int64_t)B * FA_HEADS * Ch * Ch + (int64_t)ns * 50 * FA_HEADS * Ch;
-  }
-  return n;
+  return FaScratch(B, H, W, Ch, backward != 0).total;
 }
 
 int mmskin_factor_attention_forward(const float* qkv, const float* w3, const float* b3, const float* w5, const float* b5, const float* w7,
@@ -522,8 +528,9 @@ int mmskin_factor_attention_forward(const float* qkv, const float* w3, const flo
   a.w[0] = w3; a.w[1] = w5; a.w[2] = w7; a.bias[0] = b3; a.bias[1] = b5; a.bias[2] = b7;
   const int64_t tok = 3 * (int64_t)a.C, bs = (int64_t)a.N * tok;
   hipStream_t st = ST(stream);
-  if ((rc = fa_reduce<true>(qkv + a.C, tok, bs, qkv + 2 * a.C, tok, bs, scratch, B, a.N, Ch, st))) return rc;
-  hipLaunchKernelGGL(fa_combine_fwd_kernel, dim3(B * FA_HEADS), dim3(256), 0, st, scratch, fa_nchunk(a.N), Ch, F, stats);
+  float* part = scratch + FaScratch(B, H, W, Ch, false).part;
+  if ((rc = fa_reduce<true>(qkv + a.C, tok, bs, qkv + 2 * a.C, tok, bs, part, B, a.N, Ch, st))) return rc;
+  hipLaunchKernelGGL(fa_combine_fwd_kernel, dim3(B * FA_HEADS), dim3(256), 0, st, part, fa_nchunk(a.N), Ch, F, stats);
   const int tiles = a.tiles_x * ((H + a.TH - 1) / a.TH);
   hipLaunchKernelGGL(fa_apply_fwd_kernel, dim3(tiles, B, FA_HEADS / a.HG), dim3(256), 0, st, qkv, F, att, a);
   HIP_CHECK_RET(hipGetLastError());
@@ -544,9 +551,8 @@ int mmskin_factor_attention_backward(const float* dO, const float* qkv, const fl
   const int C = a.C;
   const int64_t tok = 3 * (int64_t)C, bs = (int64_t)a.N * tok, obs = (int64_t)a.N * C;
   hipStream_t st = ST(stream);
-  float* part = scratch;
-  float* dF = part + (int64_t)B * FA_HEADS * fa_nchunk(a.N) * fa_part_stride(Ch);
-  float* wpart = dF + (int64_t)B * FA_HEADS * Ch * Ch;
+  const FaScratch lay(B, H, W, Ch, true);
+  float *part = scratch + lay.part, *dF = scratch + lay.dF, *wpart = scratch + lay.wpart;
   if ((rc = fa_reduce<false>(qkv, tok, bs, dO, C, obs, part, B, a.N, Ch, st))) return rc;          // sum_n q[n]^T dO[n]
   hipLaunchKernelGGL(fa_combine_bwd_kernel, dim3(B * FA_HEADS), dim3(256), 0, st, part, fa_nchunk(a.N), Ch, a.scale, dF);
   int64_t per; int ns;
