@@ -5,6 +5,7 @@ the HIP kernels on torch's current stream through ctypes and keeps what the
 matching backward entry point needs.  No arithmetic happens in PyTorch here.
 """
 import ctypes
+import weakref
 
 import torch
 
@@ -26,6 +27,45 @@ def _f32c(t):
     return t.contiguous()
 
 
+def _needs_grad(*ts):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
+
+
+# ---------------------------------------------------------------------------------------------- the Linear family (csrc/linear.hip)
+# Everything that drives csrc/linear.hip, in dependency order: the operand mode, LinearFn and its row-block sibling, the inference
+# lane, linear(), the activations of the transformer MLPs, LinearGeluFn, and the fused MLP.  The route of a shape is linear.hip's
+# decision (linear_path); the wrappers ask it (mmskin_linear_x16_pitch) instead of re-deriving it.
+def set_linear_dtype(name):
+    """'fp32' (exact-f32 MFMA, default) or 'bf16' (bf16 operands, fp32 accumulate) for the large Linear GEMMs."""
+    call("mmskin_set_linear_dtype", {"fp32": _lib.F32, "float32": _lib.F32, "bf16": _lib.BF16, "bfloat16": _lib.BF16}[name.lower()])
+
+
+def get_linear_dtype():
+    return "bf16" if _lib.load().mmskin_get_linear_dtype() == 1 else "fp32"
+
+
+def _linear_forward(x, w, b, res, act, want_keep):
+    """The forward LinearFn and LinearGeluFn share: y = [res +] act(x @ w.T + b) over the rows of x.  want_keep: ask the library for the
+    pitch of the bf16 operand copy of x -- non-zero on the bf16-operand large-GEMM path only -- and have the GEMM that consumes that copy
+    leave it behind (the fused residual exists on that path alone).  Returns (xs, w, y, kept): xs is the kept bf16 copy when `kept`,
+    the fp32 rows of x otherwise -- what a weight gradient needs."""
+    x2 = _f32c(x).reshape(-1, x.shape[-1])
+    w = _f32c(w)
+    M, K = x2.shape
+    N = w.shape[0]
+    y = torch.empty((M, N), device=x.device, dtype=torch.float32)
+    pitch = _lib.load().mmskin_linear_x16_pitch(M, K, N) if want_keep else 0
+    if res is not None and (not pitch or act):
+        raise RuntimeError("linear: the fused residual needs the bf16-operand large-GEMM path and no ReLU")
+    if not pitch:
+        call("mmskin_linear_forward", ptr(x2), ptr(w), ptr(b), ptr(y), M, K, N, int(act), stream())
+        return x2, w, y, False
+    x16 = torch.empty((M, pitch), device=x.device, dtype=torch.bfloat16)
+    r2 = _f32c(res).reshape(M, N) if res is not None else None
+    call("mmskin_linear_forward_keep", ptr(x2), ptr(w), ptr(b), ptr(r2), ptr(y), ptr(x16), M, K, N, int(act), stream())
+    return x16, w, y, True
+
+
 @no_second_order
 class LinearFn(torch.autograd.Function):
     """y = [res +] x @ w.T + b, optional fused ReLU (nn.Linear [+ nn.ReLU] [+ the block's residual add]).  When the bf16-operand
@@ -35,29 +75,15 @@ class LinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, relu, res=None):
         _need_gpu(x, "linear")
-        x2 = _f32c(x).reshape(-1, x.shape[-1])
-        w = _f32c(w)
-        M, K = x2.shape
-        N = w.shape[0]
-        y = torch.empty((M, N), device=x.device, dtype=torch.float32)
         need_w = ctx.needs_input_grad[1]
-        pitch = _lib.load().mmskin_linear_x16_pitch(M, K, N) if (need_w or res is not None) else 0
-        if res is not None and (not pitch or relu):
-            raise RuntimeError("linear: the fused residual needs the bf16-operand large-GEMM path and no ReLU")
-        if pitch:
-            x16 = torch.empty((M, pitch), device=x.device, dtype=torch.bfloat16)
-            r2 = _f32c(res).reshape(M, N) if res is not None else None
-            call("mmskin_linear_forward_keep", ptr(x2), ptr(w), ptr(b), ptr(r2), ptr(y), ptr(x16), M, K, N, int(relu), stream())
-            ctx.save_for_backward(x16 if need_w else None, w, y if relu else None)
-        else:
-            call("mmskin_linear_forward", ptr(x2), ptr(w), ptr(b), ptr(y), M, K, N, int(relu), stream())
-            ctx.save_for_backward(x2 if need_w else None, w, y if relu else None)
-        ctx.kept = bool(pitch) and need_w
-        ctx.mk = (M, K)
+        xs, w, y, kept = _linear_forward(x, w, b, res, relu, need_w or res is not None)
+        ctx.save_for_backward(xs if need_w else None, w, y if relu else None)
+        ctx.kept = kept and need_w
+        ctx.mk = (y.shape[0], x.shape[-1])
         ctx.has_bias = b is not None
         ctx.xshape = x.shape
         ctx.res_shape = None if res is None else res.shape
-        return y.reshape(*x.shape[:-1], N)
+        return y.reshape(*x.shape[:-1], w.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
@@ -127,6 +153,17 @@ def linear_rows(x, w, b, r0, r1):
     return LinearRowsFn.apply(x, w, b, r0, r1)
 
 
+def _dtype_code(t):
+    """the C ABI's dtype code of a tensor or of a torch dtype (bf16, or fp32 for everything else)"""
+    return _lib.BF16 if getattr(t, "dtype", t) == torch.bfloat16 else _lib.F32
+
+
+def _rows_f32_or_bf16(x):
+    """x as contiguous rows [M, K] in a dtype the lane entry points read: bf16 and fp32 as they are, anything else widened to fp32"""
+    x2 = x.reshape(-1, x.shape[-1]).contiguous()
+    return x2 if x2.dtype in (torch.float32, torch.bfloat16) else x2.float()
+
+
 def lane_dtype(x, module=None, *tensors):
     """torch.bfloat16 when the INFERENCE LANE applies to a layer -- bf16-operand mode and no gradient flows through it (input,
     the module's parameters and `tensors` all without grad, or grad mode off): activations are then handed between the layer's
@@ -143,16 +180,13 @@ def _linear_ex(x, w, b, act, out_dtype):
     _need_gpu(x, "linear")
     if _needs_grad(x, w, b):
         raise _lib.MMSkinError("mmskin.linear: bf16 activations are an inference-lane feature (no gradient may flow through them)")
-    x2 = x.reshape(-1, x.shape[-1]).contiguous()
-    if x2.dtype not in (torch.float32, torch.bfloat16):
-        x2 = x2.float()
+    x2 = _rows_f32_or_bf16(x)
     w = _f32c(w)
     M, K = x2.shape
     N = w.shape[0]
     od = out_dtype or torch.float32
     y = torch.empty((M, N), device=x.device, dtype=od)
-    call("mmskin_linear_forward_ex", ptr(x2), _lib.BF16 if x2.dtype == torch.bfloat16 else _lib.F32, ptr(w), ptr(b), ptr(y),
-         _lib.BF16 if od == torch.bfloat16 else _lib.F32, M, K, N, int(act), stream())
+    call("mmskin_linear_forward_ex", ptr(x2), _dtype_code(x2), ptr(w), ptr(b), ptr(y), _dtype_code(od), M, K, N, int(act), stream())
     return y.reshape(*x.shape[:-1], N)
 
 
@@ -163,7 +197,6 @@ def frozen_bf16(*ws):
     """bf16 copy of one weight (or of several stacked along dim 0: the q / k / v projections of a BERT layer as ONE [3E, E] operand)
     that no gradient flows into, converted once and reused until a source tensor changes (its version counter moves: optimizer
     step, load_state_dict, .copy_) or is replaced.  Saves the per-step fp32 -> bf16 pass over every frozen encoder weight."""
-    import weakref
     key = tuple(w.data_ptr() for w in ws)
     vers = tuple(w._version for w in ws)
     hit = _frozen_cache.get(key)
@@ -212,17 +245,15 @@ def linear_lane(x, ws, b=None, act=0, gamma=None, residual=None, drop_p=0.0, tra
         if gamma is not None:
             return scale_add(residual if residual is not None else torch.zeros_like(h), h, gamma)
         return add(h, residual) if residual is not None else h
-    x2 = x.reshape(-1, K).contiguous()
-    if x2.dtype not in (torch.float32, torch.bfloat16):
-        x2 = x2.float()
+    x2 = _rows_f32_or_bf16(x)
     M = x2.shape[0]
     od = torch.float32 if tail else (out_dtype or torch.float32)
     y = torch.empty((M, N), device=x.device, dtype=od)
     res = None if residual is None else _f32c(residual).reshape(M, N)
     seed, offset = _dropout_state(p, M * N)
-    call("mmskin_linear_lane", ptr(x2), _lib.BF16 if x2.dtype == torch.bfloat16 else _lib.F32, ptr(frozen_bf16(*ws)), _lib.BF16,
+    call("mmskin_linear_lane", ptr(x2), _dtype_code(x2), ptr(frozen_bf16(*ws)), _lib.BF16,
          ptr(None if b is None else _f32c(b)), ptr(None if gamma is None else _f32c(gamma)), ptr(res), p, int(seed), int(offset),
-         ptr(y), _lib.BF16 if od == torch.bfloat16 else _lib.F32, M, K, N, int(act), stream())
+         ptr(y), _dtype_code(od), M, K, N, int(act), stream())
     return y.reshape(*x.shape[:-1], N)
 
 
@@ -242,6 +273,204 @@ def linear(x, w, b=None, relu=False, out_dtype=None, residual=None):
         y = LinearFn.apply(x, w, b, relu)
         return add(y, residual.reshape(y.shape))
     return LinearFn.apply(x, w, b, relu)
+
+
+def _gelu_fn(cls_name, what):
+    """The autograd Function of a GELU flavour, what = 'gelu' (exact) / 'gelu_tanh': its two entry points are mmskin_<what>_forward
+    (x, y, n) and mmskin_<what>_backward (dy, x, dx, n)."""
+    fwd, bwd = f"mmskin_{what}_forward", f"mmskin_{what}_backward"
+
+    class Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x):
+            _need_gpu(x, what)
+            x = _f32c(x)
+            y = torch.empty_like(x)
+            call(fwd, ptr(x), ptr(y), x.numel(), stream())
+            ctx.save_for_backward(x)
+            return y
+
+        @staticmethod
+        def backward(ctx, dy):
+            (x,) = ctx.saved_tensors
+            dy = _f32c(dy)
+            dx = torch.empty_like(x)
+            call(bwd, ptr(dy), ptr(x), ptr(dx), x.numel(), stream())
+            return dx
+
+    Fn.__name__ = Fn.__qualname__ = cls_name
+    return no_second_order(Fn)
+
+
+GeluFn, GeluTanhFn = _gelu_fn("GeluFn", "gelu"), _gelu_fn("GeluTanhFn", "gelu_tanh")
+gelu, gelu_tanh = GeluFn.apply, GeluTanhFn.apply
+
+
+def _split_dsb(dsb, s, b, need_s, need_b):
+    """The (d scale, d bias) pair a StarReLU backward pass wrote, as gradients shaped like the two one-element parameters; None where
+    none is needed."""
+    return (dsb[0:1].reshape(s.shape) if need_s else None), (dsb[1:2].reshape(b.shape) if need_b else None)
+
+
+@no_second_order
+class StarReluFn(torch.autograd.Function):
+    """timm StarReLU: s * relu(z)^2 + b, s and b one-element tensors; the backward returns their gradients from the pass that writes dz
+    (fixed-order reductions)."""
+
+    @staticmethod
+    def forward(ctx, z, s, b):
+        _need_gpu(z, "star_relu")
+        z, s, b = _f32c(z), _f32c(s), _f32c(b)
+        y = torch.empty_like(z)
+        call("mmskin_star_relu_forward", ptr(z), ptr(s), ptr(b), ptr(y), z.numel(), stream())
+        ctx.save_for_backward(z, s)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        z, s = ctx.saved_tensors
+        dy = _f32c(dy)
+        dz = torch.empty_like(z) if ctx.needs_input_grad[0] else None
+        dsb = torch.empty(2, device=dy.device, dtype=torch.float32)
+        call("mmskin_star_relu_backward", ptr(dy), ptr(z), ptr(s), ptr(dz), ptr(dsb), z.numel(), stream())
+        return (dz,) + _split_dsb(dsb, s, s, True, True)
+
+
+star_relu = StarReluFn.apply
+
+
+@no_second_order
+class LinearGeluFn(torch.autograd.Function):
+    """h = gelu(x @ w.T + b) with gradients (first half of a transformer MLP).  Forward: Linear, then GELU (the pre-activation z is kept
+    for the backward); backward: ONE C call -- gelu'(z) is applied inside the pass that converts dh for the bf16 GEMMs and sums it for
+    db (mmskin_linear_gelu_backward), so d(z) is never written in fp32.  The bf16 operand copy of x is kept as in LinearFn."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        _need_gpu(x, "linear_gelu")
+        need_w = ctx.needs_input_grad[1]
+        xs, w, z, ctx.kept = _linear_forward(x, w, b, None, 0, need_w)
+        ctx.save_for_backward(xs if need_w else None, w, z)
+        h = torch.empty_like(z)
+        call("mmskin_gelu_forward", ptr(z), ptr(h), z.numel(), stream())
+        ctx.mk = (z.shape[0], x.shape[-1])
+        ctx.has_bias = b is not None
+        ctx.xshape = x.shape
+        return h.reshape(*x.shape[:-1], w.shape[0])
+
+    @staticmethod
+    def backward(ctx, dh):
+        xs, w, z = ctx.saved_tensors
+        M, K = ctx.mk
+        N = w.shape[0]
+        dh2 = _f32c(dh).reshape(M, N)
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        dx = torch.empty((M, K), device=dh.device, dtype=torch.float32) if need_x else None
+        dw = torch.empty_like(w) if need_w else None
+        db = torch.empty(N, device=dh.device, dtype=torch.float32) if need_b else None
+        # off the bf16-operand large-GEMM path (linear.hip: linear_path) the C side applies gelu'(z) in a pass of its own
+        # (mmskin_linear_x16_pitch(M, K, N) > 0 IS that predicate, asked of the library instead of re-derived here: ADVICE r03)
+        fused = _lib.load().mmskin_linear_x16_pitch(M, K, N) > 0
+        scratch = None if fused else torch.empty_like(dh2)
+        if ctx.kept:
+            call("mmskin_linear_backward_keep", ptr(dh2), ptr(xs), ptr(w), None, ptr(z), ptr(scratch), ptr(dx), ptr(dw), ptr(db), M, K, N, stream())
+        else:
+            call("mmskin_linear_gelu_backward", ptr(dh2), ptr(xs), ptr(w), ptr(z), ptr(scratch), ptr(dx), ptr(dw), ptr(db), M, K, N, stream())
+        return (dx.reshape(ctx.xshape) if need_x else None), dw, db
+
+
+def linear_gelu(x, w, b=None, out_dtype=None):
+    """gelu(x @ w.T + b) -- the first half of a transformer MLP.  Without gradients (frozen encoders, inference) bias and the
+    exact GELU run in the GEMM epilogue (one launch, the pre-activation never reaches memory); with gradients the two ops
+    stay separate because GELU's backward needs the pre-activation."""
+    if _needs_grad(x, w, b):
+        if x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32:
+            return LinearGeluFn.apply(x, w, b)
+        return gelu(linear(x, w, b))
+    if x.dtype == torch.bfloat16 or out_dtype == torch.bfloat16:
+        return linear_lane(x, w, b, 2, out_dtype=out_dtype)
+    with torch.no_grad():
+        return LinearFn.apply(x, w, b, 2)
+
+
+@no_second_order
+class MlpFn(torch.autograd.Function):
+    """[res +] fc2(act(fc1(x))) with gradients (timm Mlp.forward and the block's skip connection) on the bf16-operand large-GEMM path;
+    act is the exact GELU (s and sb None) or timm's StarReLU s * relu(z)^2 + sb.  The hidden activation exists only as the
+    pre-activation z (fp32, for the derivative) and as the bf16 operand of fc2 -- act(z) is never written in fp32; the residual is
+    added in the pass that writes the output.  Backward: two C calls (fc2's, then fc1's with act'(z) inside the pass that converts dh
+    -- for StarReLU the gradients of s and sb come from that pass too), each on the bf16 operand copy kept from the forward."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, s, sb, res, p1, p2):
+        _need_gpu(x, "mlp")
+        x2 = _f32c(x).reshape(-1, x.shape[-1])
+        w1, w2 = _f32c(w1), _f32c(w2)
+        M, K = x2.shape
+        Hd, N = w1.shape[0], w2.shape[0]
+        z = torch.empty((M, Hd), device=x.device, dtype=torch.float32)
+        x16 = torch.empty((M, p1), device=x.device, dtype=torch.bfloat16)
+        call("mmskin_linear_forward_keep", ptr(x2), ptr(w1), ptr(b1), None, ptr(z), ptr(x16), M, K, Hd, 0, stream())
+        h16 = torch.empty((M, p2), device=x.device, dtype=torch.bfloat16)
+        if s is None:
+            call("mmskin_gelu_forward_bf16", ptr(z), ptr(h16), M, Hd, p2, stream())
+        else:
+            s, sb = _f32c(s), _f32c(sb)
+            call("mmskin_star_relu_forward_bf16", ptr(z), ptr(s), ptr(sb), ptr(h16), M, Hd, p2, stream())
+        y = torch.empty((M, N), device=x.device, dtype=torch.float32)
+        r2 = _f32c(res).reshape(M, N) if res is not None else None
+        call("mmskin_linear_forward_x16", ptr(h16), ptr(w2), ptr(b2), ptr(r2), ptr(y), M, Hd, N, 0, stream())
+        ctx.save_for_backward(x16, w1, z, h16, w2, s)
+        ctx.dims = (M, K, Hd, N)
+        ctx.bias = (b1 is not None, b2 is not None)
+        ctx.xshape = x.shape
+        ctx.res_shape = None if res is None else res.shape
+        return y.reshape(*x.shape[:-1], N)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x16, w1, z, h16, w2, s = ctx.saved_tensors
+        M, K, Hd, N = ctx.dims
+        dy2 = _f32c(dy).reshape(M, N)
+        ng = ctx.needs_input_grad
+        dev = dy.device
+        dh = torch.empty((M, Hd), device=dev, dtype=torch.float32)
+        dw2 = torch.empty_like(w2) if ng[3] else None
+        db2 = torch.empty(N, device=dev, dtype=torch.float32) if ctx.bias[1] and ng[4] else None
+        call("mmskin_linear_backward_keep", ptr(dy2), ptr(h16), ptr(w2), None, None, None, ptr(dh), ptr(dw2), ptr(db2), M, Hd, N, stream())
+        dx = torch.empty((M, K), device=dev, dtype=torch.float32) if ng[0] else None
+        dw1 = torch.empty_like(w1) if ng[1] else None
+        db1 = torch.empty(Hd, device=dev, dtype=torch.float32) if ctx.bias[0] and ng[2] else None
+        if s is None:
+            call("mmskin_linear_backward_keep", ptr(dh), ptr(x16), ptr(w1), None, ptr(z), None, ptr(dx), ptr(dw1), ptr(db1), M, K, Hd, stream())
+            ds = dsbias = None
+        else:
+            dsb = torch.empty(2, device=dev, dtype=torch.float32)
+            call("mmskin_linear_star_relu_backward_keep", ptr(dh), ptr(x16), ptr(w1), ptr(z), ptr(s), ptr(dsb), ptr(dx), ptr(dw1), ptr(db1),
+                 M, K, Hd, stream())
+            ds, dsbias = _split_dsb(dsb, s, s, ng[5], ng[6])
+        dres = dy2.reshape(ctx.res_shape) if ctx.res_shape is not None and ng[7] else None
+        return (dx.reshape(ctx.xshape) if dx is not None else None), dw1, db1, dw2, db2, ds, dsbias, dres, None, None
+
+
+def mlp(x, w1, b1, w2, b2, residual=None, star_relu=None):
+    """[residual +] fc2(act(fc1(x))), act = exact GELU (default) or, with star_relu=(scale, bias), timm's StarReLU
+    scale * relu(z)^2 + bias.  With gradients, fp32 tensors on the GPU and both Linears on the bf16-operand large-GEMM path: MlpFn
+    (no fp32 act(z), kept bf16 operands, residual added by the output pass; its StarReLU kernels take hidden widths that are multiples
+    of 4); otherwise the separate ops."""
+    s, sb = star_relu if star_relu is not None else (None, None)
+    if (_needs_grad(x, w1, b1, w2, b2, s, sb) and x.is_cuda and x.dtype == torch.float32 and w1.dtype == torch.float32 and w2.dtype == torch.float32
+            and w1.requires_grad and w2.requires_grad and (s is None or w1.shape[0] % 4 == 0)
+            and (residual is None or residual.dtype == torch.float32)):
+        M = x.numel() // x.shape[-1]
+        lib = _lib.load()
+        p1 = lib.mmskin_linear_x16_pitch(M, x.shape[-1], w1.shape[0])
+        p2 = lib.mmskin_linear_x16_pitch(M, w1.shape[0], w2.shape[0])
+        if p1 and p2:
+            return MlpFn.apply(x, w1, b1, w2, b2, s, sb, residual, p1, p2)
+    if s is None:
+        return linear(linear_gelu(x, w1, b1), w2, b2, residual=residual)
+    return linear(StarReluFn.apply(linear(x, w1, b1), s, sb), w2, b2, residual=residual)
 
 
 @no_second_order
@@ -705,10 +934,6 @@ class LongAttentionFn(torch.autograd.Function):
         return dq, dk, dv, None, None, None, None, dbias, None
 
 
-def _needs_grad(*ts):
-    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
-
-
 def _flash_ok(q, k, v, mask_add, bias, bh):
     """The fused bf16 attention kernel (csrc/flash_attn.hip) serves bf16-operand mode whenever no gradient has to flow
     through the attention (frozen encoders -- the reference's default `frozen_weights` -- and inference); trainable blocks
@@ -733,7 +958,7 @@ def _flash_forward(q, k, v, out, dims, strides, mask_add, bias, causal, p, seed,
     bs = _f32c(bias) if bias is not None else None
     call("mmskin_flash_attention_forward", ptr(q), ptr(k), ptr(v), ptr(m) if m is not None else None,
          ptr(bs) if bs is not None else None, ptr(out), None, B, H, L, Dh, st,
-         _lib.BF16 if q.dtype == torch.bfloat16 else _lib.F32, 1.0 / Dh ** 0.5, int(causal), float(p), int(seed), int(offset), stream())
+         _dtype_code(q), 1.0 / Dh ** 0.5, int(causal), float(p), int(seed), int(offset), stream())
     return out
 
 
@@ -955,15 +1180,6 @@ class TokenMeanFn(torch.autograd.Function):
 token_mean = TokenMeanFn.apply
 
 
-def set_linear_dtype(name):
-    """'fp32' (exact-f32 MFMA, default) or 'bf16' (bf16 operands, fp32 accumulate) for the large Linear GEMMs."""
-    call("mmskin_set_linear_dtype", {"fp32": _lib.F32, "float32": _lib.F32, "bf16": _lib.BF16, "bfloat16": _lib.BF16}[name.lower()])
-
-
-def get_linear_dtype():
-    return "bf16" if _lib.load().mmskin_get_linear_dtype() == 1 else "fp32"
-
-
 @no_second_order
 class PatchColsFn(torch.autograd.Function):
     """im2col for the patch-embedding GEMMs: x [N, C, H, W] (channels_last=False) or [N, H, W, C] (True), fp32 ->
@@ -1157,237 +1373,6 @@ def factor_attention(qkv, H, W, crpe_weights, crpe_biases):
 
 
 @no_second_order
-class GeluFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x):
-        _need_gpu(x, "gelu")
-        x = _f32c(x)
-        y = torch.empty_like(x)
-        call("mmskin_gelu_forward", ptr(x), ptr(y), x.numel(), stream())
-        ctx.save_for_backward(x)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        (x,) = ctx.saved_tensors
-        dy = _f32c(dy)
-        dx = torch.empty_like(x)
-        call("mmskin_gelu_backward", ptr(dy), ptr(x), ptr(dx), x.numel(), stream())
-        return dx
-
-
-gelu = GeluFn.apply
-
-
-@no_second_order
-class LinearGeluFn(torch.autograd.Function):
-    """h = gelu(x @ w.T + b) with gradients (first half of a transformer MLP).  Forward: Linear, then GELU (the pre-activation z is kept
-    for the backward); backward: ONE C call -- gelu'(z) is applied inside the pass that converts dh for the bf16 GEMMs and sums it for
-    db (mmskin_linear_gelu_backward), so d(z) is never written in fp32.  The bf16 operand copy of x is kept as in LinearFn."""
-
-    @staticmethod
-    def forward(ctx, x, w, b):
-        _need_gpu(x, "linear_gelu")
-        x2 = _f32c(x).reshape(-1, x.shape[-1])
-        w = _f32c(w)
-        M, K = x2.shape
-        N = w.shape[0]
-        z = torch.empty((M, N), device=x.device, dtype=torch.float32)
-        need_w = ctx.needs_input_grad[1]
-        pitch = _lib.load().mmskin_linear_x16_pitch(M, K, N) if need_w else 0
-        if pitch:
-            x16 = torch.empty((M, pitch), device=x.device, dtype=torch.bfloat16)
-            call("mmskin_linear_forward_keep", ptr(x2), ptr(w), ptr(b), None, ptr(z), ptr(x16), M, K, N, 0, stream())
-            ctx.save_for_backward(x16, w, z)
-        else:
-            call("mmskin_linear_forward", ptr(x2), ptr(w), ptr(b), ptr(z), M, K, N, 0, stream())
-            ctx.save_for_backward(x2 if need_w else None, w, z)
-        h = torch.empty_like(z)
-        call("mmskin_gelu_forward", ptr(z), ptr(h), z.numel(), stream())
-        ctx.kept = bool(pitch)
-        ctx.mk = (M, K)
-        ctx.has_bias = b is not None
-        ctx.xshape = x.shape
-        return h.reshape(*x.shape[:-1], N)
-
-    @staticmethod
-    def backward(ctx, dh):
-        xs, w, z = ctx.saved_tensors
-        M, K = ctx.mk
-        N = w.shape[0]
-        dh2 = _f32c(dh).reshape(M, N)
-        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
-        dx = torch.empty((M, K), device=dh.device, dtype=torch.float32) if need_x else None
-        dw = torch.empty_like(w) if need_w else None
-        db = torch.empty(N, device=dh.device, dtype=torch.float32) if need_b else None
-        # off the bf16-operand large-GEMM path (linear.hip: linear_path) the C side applies gelu'(z) in a pass of its own
-        # (mmskin_linear_x16_pitch(M, K, N) > 0 IS that predicate, asked of the library instead of re-derived here: ADVICE r03)
-        fused = _lib.load().mmskin_linear_x16_pitch(M, K, N) > 0
-        scratch = None if fused else torch.empty_like(dh2)
-        if ctx.kept:
-            call("mmskin_linear_backward_keep", ptr(dh2), ptr(xs), ptr(w), None, ptr(z), ptr(scratch), ptr(dx), ptr(dw), ptr(db), M, K, N, stream())
-        else:
-            call("mmskin_linear_gelu_backward", ptr(dh2), ptr(xs), ptr(w), ptr(z), ptr(scratch), ptr(dx), ptr(dw), ptr(db), M, K, N, stream())
-        return (dx.reshape(ctx.xshape) if need_x else None), dw, db
-
-
-@no_second_order
-class MlpFn(torch.autograd.Function):
-    """[res +] fc2(gelu(fc1(x))) with gradients (timm Mlp.forward and the block's skip connection) on the bf16-operand large-GEMM path:
-    the hidden activation exists only as the pre-activation z (fp32, for GELU's derivative) and as the bf16 operand of fc2 -- gelu(z)
-    is never written in fp32; the residual is added in the pass that writes the output.  Backward: two C calls (fc2's, then fc1's with
-    gelu'(z) inside the conversion pass), each on the bf16 operand copy kept from the forward."""
-
-    @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, res, p1, p2):
-        _need_gpu(x, "mlp")
-        x2 = _f32c(x).reshape(-1, x.shape[-1])
-        w1, w2 = _f32c(w1), _f32c(w2)
-        M, K = x2.shape
-        Hd, N = w1.shape[0], w2.shape[0]
-        z = torch.empty((M, Hd), device=x.device, dtype=torch.float32)
-        x16 = torch.empty((M, p1), device=x.device, dtype=torch.bfloat16)
-        call("mmskin_linear_forward_keep", ptr(x2), ptr(w1), ptr(b1), None, ptr(z), ptr(x16), M, K, Hd, 0, stream())
-        h16 = torch.empty((M, p2), device=x.device, dtype=torch.bfloat16)
-        call("mmskin_gelu_forward_bf16", ptr(z), ptr(h16), M, Hd, p2, stream())
-        y = torch.empty((M, N), device=x.device, dtype=torch.float32)
-        r2 = _f32c(res).reshape(M, N) if res is not None else None
-        call("mmskin_linear_forward_x16", ptr(h16), ptr(w2), ptr(b2), ptr(r2), ptr(y), M, Hd, N, 0, stream())
-        ctx.save_for_backward(x16, w1, z, h16, w2)
-        ctx.dims = (M, K, Hd, N)
-        ctx.bias = (b1 is not None, b2 is not None)
-        ctx.xshape = x.shape
-        ctx.res_shape = None if res is None else res.shape
-        return y.reshape(*x.shape[:-1], N)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x16, w1, z, h16, w2 = ctx.saved_tensors
-        M, K, Hd, N = ctx.dims
-        dy2 = _f32c(dy).reshape(M, N)
-        ng = ctx.needs_input_grad
-        dev = dy.device
-        dh = torch.empty((M, Hd), device=dev, dtype=torch.float32)
-        dw2 = torch.empty_like(w2) if ng[3] else None
-        db2 = torch.empty(N, device=dev, dtype=torch.float32) if ctx.bias[1] and ng[4] else None
-        call("mmskin_linear_backward_keep", ptr(dy2), ptr(h16), ptr(w2), None, None, None, ptr(dh), ptr(dw2), ptr(db2), M, Hd, N, stream())
-        dx = torch.empty((M, K), device=dev, dtype=torch.float32) if ng[0] else None
-        dw1 = torch.empty_like(w1) if ng[1] else None
-        db1 = torch.empty(Hd, device=dev, dtype=torch.float32) if ctx.bias[0] and ng[2] else None
-        call("mmskin_linear_backward_keep", ptr(dh), ptr(x16), ptr(w1), None, ptr(z), None, ptr(dx), ptr(dw1), ptr(db1), M, K, Hd, stream())
-        dres = dy2.reshape(ctx.res_shape) if ctx.res_shape is not None and ng[5] else None
-        return (dx.reshape(ctx.xshape) if dx is not None else None), dw1, db1, dw2, db2, dres, None, None
-
-
-def mlp(x, w1, b1, w2, b2, residual=None, star_relu=None):
-    """[residual +] fc2(act(fc1(x))), act = exact GELU (default) or, with star_relu=(scale, bias), timm's StarReLU
-    scale * relu(z)^2 + bias.  With gradients, fp32 tensors on the GPU and both Linears on the bf16-operand large-GEMM path:
-    MlpFn / StarMlpFn (no fp32 act(z), kept bf16 operands, residual added by the output pass); otherwise the separate ops."""
-    if star_relu is not None:
-        return _star_mlp(x, w1, b1, w2, b2, residual, *star_relu)
-    if (_needs_grad(x, w1, b1, w2, b2) and x.is_cuda and x.dtype == torch.float32 and w1.dtype == torch.float32 and w2.dtype == torch.float32
-            and w1.requires_grad and w2.requires_grad and (residual is None or residual.dtype == torch.float32)):
-        M = x.numel() // x.shape[-1]
-        lib = _lib.load()
-        p1 = lib.mmskin_linear_x16_pitch(M, x.shape[-1], w1.shape[0])
-        p2 = lib.mmskin_linear_x16_pitch(M, w1.shape[0], w2.shape[0])
-        if p1 and p2:
-            return MlpFn.apply(x, w1, b1, w2, b2, residual, p1, p2)
-    return linear(linear_gelu(x, w1, b1), w2, b2, residual=residual)
-
-
-@no_second_order
-class StarMlpFn(torch.autograd.Function):
-    """[res +] fc2(s * relu(fc1(x))^2 + b) with gradients on the bf16-operand large-GEMM path (MlpFn with timm's StarReLU): the hidden
-    activation exists as the pre-activation z (fp32) and as the bf16 operand of fc2 only.  The backward of fc1 applies 2 s relu(z) in
-    the pass that converts dh and returns the gradients of s and b from the same pass."""
-
-    @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, s, sb, res, p1, p2):
-        _need_gpu(x, "mlp")
-        x2 = _f32c(x).reshape(-1, x.shape[-1])
-        w1, w2, s, sb = _f32c(w1), _f32c(w2), _f32c(s), _f32c(sb)
-        M, K = x2.shape
-        Hd, N = w1.shape[0], w2.shape[0]
-        z = torch.empty((M, Hd), device=x.device, dtype=torch.float32)
-        x16 = torch.empty((M, p1), device=x.device, dtype=torch.bfloat16)
-        call("mmskin_linear_forward_keep", ptr(x2), ptr(w1), ptr(b1), None, ptr(z), ptr(x16), M, K, Hd, 0, stream())
-        h16 = torch.empty((M, p2), device=x.device, dtype=torch.bfloat16)
-        call("mmskin_star_relu_forward_bf16", ptr(z), ptr(s), ptr(sb), ptr(h16), M, Hd, p2, stream())
-        y = torch.empty((M, N), device=x.device, dtype=torch.float32)
-        r2 = _f32c(res).reshape(M, N) if res is not None else None
-        call("mmskin_linear_forward_x16", ptr(h16), ptr(w2), ptr(b2), ptr(r2), ptr(y), M, Hd, N, 0, stream())
-        ctx.save_for_backward(x16, w1, z, h16, w2, s)
-        ctx.dims = (M, K, Hd, N)
-        ctx.bias = (b1 is not None, b2 is not None)
-        ctx.xshape = x.shape
-        ctx.res_shape = None if res is None else res.shape
-        return y.reshape(*x.shape[:-1], N)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x16, w1, z, h16, w2, s = ctx.saved_tensors
-        M, K, Hd, N = ctx.dims
-        dy2 = _f32c(dy).reshape(M, N)
-        ng = ctx.needs_input_grad
-        dev = dy.device
-        dh = torch.empty((M, Hd), device=dev, dtype=torch.float32)
-        dw2 = torch.empty_like(w2) if ng[3] else None
-        db2 = torch.empty(N, device=dev, dtype=torch.float32) if ctx.bias[1] and ng[4] else None
-        call("mmskin_linear_backward_keep", ptr(dy2), ptr(h16), ptr(w2), None, None, None, ptr(dh), ptr(dw2), ptr(db2), M, Hd, N, stream())
-        dx = torch.empty((M, K), device=dev, dtype=torch.float32) if ng[0] else None
-        dw1 = torch.empty_like(w1) if ng[1] else None
-        db1 = torch.empty(Hd, device=dev, dtype=torch.float32) if ctx.bias[0] and ng[2] else None
-        dsb = torch.empty(2, device=dev, dtype=torch.float32)
-        call("mmskin_linear_star_relu_backward_keep", ptr(dh), ptr(x16), ptr(w1), ptr(z), ptr(s), ptr(dsb), ptr(dx), ptr(dw1), ptr(db1),
-             M, K, Hd, stream())
-        dres = dy2.reshape(ctx.res_shape) if ctx.res_shape is not None and ng[7] else None
-        ds = dsb[0:1].reshape(s.shape) if ng[5] else None
-        dsbias = dsb[1:2].reshape(s.shape) if ng[6] else None
-        return (dx.reshape(ctx.xshape) if dx is not None else None), dw1, db1, dw2, db2, ds, dsbias, dres, None, None
-
-
-@no_second_order
-class StarReluFn(torch.autograd.Function):
-    """timm StarReLU: s * relu(z)^2 + b, s and b one-element tensors; the backward returns their gradients from the pass that writes dz
-    (fixed-order reductions)."""
-
-    @staticmethod
-    def forward(ctx, z, s, b):
-        _need_gpu(z, "star_relu")
-        z, s, b = _f32c(z), _f32c(s), _f32c(b)
-        y = torch.empty_like(z)
-        call("mmskin_star_relu_forward", ptr(z), ptr(s), ptr(b), ptr(y), z.numel(), stream())
-        ctx.save_for_backward(z, s)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        z, s = ctx.saved_tensors
-        dy = _f32c(dy)
-        dz = torch.empty_like(z) if ctx.needs_input_grad[0] else None
-        dsb = torch.empty(2, device=dy.device, dtype=torch.float32)
-        call("mmskin_star_relu_backward", ptr(dy), ptr(z), ptr(s), ptr(dz), ptr(dsb), z.numel(), stream())
-        return dz, dsb[0:1].reshape(s.shape), dsb[1:2].reshape(s.shape)
-
-
-star_relu = StarReluFn.apply
-
-
-def _star_mlp(x, w1, b1, w2, b2, residual, s, sb):
-    if (_needs_grad(x, w1, b1, w2, b2, s, sb) and x.is_cuda and x.dtype == torch.float32 and w1.dtype == torch.float32
-            and w2.dtype == torch.float32 and w1.requires_grad and w2.requires_grad and w1.shape[0] % 4 == 0
-            and (residual is None or residual.dtype == torch.float32)):
-        M = x.numel() // x.shape[-1]
-        lib = _lib.load()
-        p1 = lib.mmskin_linear_x16_pitch(M, x.shape[-1], w1.shape[0])
-        p2 = lib.mmskin_linear_x16_pitch(M, w1.shape[0], w2.shape[0])
-        if p1 and p2:
-            return StarMlpFn.apply(x, w1, b1, w2, b2, s, sb, residual, p1, p2)
-    return linear(star_relu(linear(x, w1, b1), s, sb), w2, b2, residual=residual)
-
-
-@no_second_order
 class Dw7StarFn(torch.autograd.Function):
     """CAFormer SepConv core on NHWC fp32: dwconv7x7(s * relu(z)^2 + b, w), z [N, H, W, C], w [C, 1, 7, 7] (stride 1, pad 3, no bias).
     The StarReLU is applied as z is staged (act(z) is never written); the backward reads dy and z once for dz, dw and the gradients of
@@ -1414,49 +1399,10 @@ class Dw7StarFn(torch.autograd.Function):
         dw = torch.empty_like(w) if ng[1] else None
         dsb = torch.empty(2, device=dy.device, dtype=torch.float32) if ng[2] or ng[3] else None
         call("mmskin_dw7_star_backward", ptr(dy), ptr(z), ptr(w), ptr(s), ptr(b), ptr(scratch), ptr(dz), ptr(dw), ptr(dsb), N, H, W, C, stream())
-        ds = dsb[0:1].reshape(s.shape) if ng[2] else None
-        db = dsb[1:2].reshape(b.shape) if ng[3] else None
-        return dz, dw, ds, db
+        return (dz, dw) + _split_dsb(dsb, s, b, ng[2], ng[3])
 
 
 dw7_star = Dw7StarFn.apply
-
-
-def linear_gelu(x, w, b=None, out_dtype=None):
-    """gelu(x @ w.T + b) -- the first half of a transformer MLP.  Without gradients (frozen encoders, inference) bias and the
-    exact GELU run in the GEMM epilogue (one launch, the pre-activation never reaches memory); with gradients the two ops
-    stay separate because GELU's backward needs the pre-activation."""
-    if _needs_grad(x, w, b):
-        if x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32:
-            return LinearGeluFn.apply(x, w, b)
-        return gelu(linear(x, w, b))
-    if x.dtype == torch.bfloat16 or out_dtype == torch.bfloat16:
-        return linear_lane(x, w, b, 2, out_dtype=out_dtype)
-    with torch.no_grad():
-        return LinearFn.apply(x, w, b, 2)
-
-
-@no_second_order
-class GeluTanhFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x):
-        _need_gpu(x, "gelu_tanh")
-        x = _f32c(x)
-        y = torch.empty_like(x)
-        call("mmskin_gelu_tanh_forward", ptr(x), ptr(y), x.numel(), stream())
-        ctx.save_for_backward(x)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        (x,) = ctx.saved_tensors
-        dy = _f32c(dy)
-        dx = torch.empty_like(x)
-        call("mmskin_gelu_tanh_backward", ptr(dy), ptr(x), ptr(dx), x.numel(), stream())
-        return dx
-
-
-gelu_tanh = GeluTanhFn.apply
 
 
 @no_second_order

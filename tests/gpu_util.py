@@ -1,7 +1,7 @@
 """Helpers for the -m gpu parity tests: call the C ABI with torch CUDA tensors."""
 import torch
 
-from mmskin import _lib
+from mmskin import _lib, ops
 from mmskin._lib import call, ptr, stream
 
 DEV = "cuda:0"
@@ -10,6 +10,20 @@ DT = {"fp32": _lib.F32, "bf16": _lib.BF16}
 
 def ws(nbytes):
     return torch.empty(int(nbytes), dtype=torch.uint8, device=DEV)
+
+
+class linear_mode:
+    """with linear_mode("bf16"): ...  -- the Linear operand mode (ops.set_linear_dtype) for the block, the previous one restored after it"""
+
+    def __init__(self, mode):
+        self.mode = mode
+
+    def __enter__(self):
+        self.prev = ops.get_linear_dtype()
+        ops.set_linear_dtype(self.mode)
+
+    def __exit__(self, *exc):
+        ops.set_linear_dtype(self.prev)
 
 
 def rel_err(got, want):

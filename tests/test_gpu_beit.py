@@ -7,7 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_util import DEV, rel_err
+from gpu_util import DEV, linear_mode, rel_err
 from oracle.altmodels import OracleBeit
 from oracle.detinit import det_init_, det_tensor
 
@@ -43,7 +43,6 @@ def test_beit_bf16_operand_mode_gradients_vs_emulation():
     inside the 1.5 x slack): per-parameter gradient distance /
     cosine to the fp32 oracle, bounded by the CPU bf16-operand emulation of the oracle (tests/bf16_emulation.py)."""
     from bf16_emulation import assert_grads_not_worse_than_emulation, bf16_operand_emulation, grad_distance_report
-    from mmskin import ops
     from models.hip_beit import HipBeit
     x = det_tensor("beit.xb", (12, 3, 224, 224))
     w = det_tensor("beit.wb", (12, 64))
@@ -62,12 +61,8 @@ def test_beit_bf16_operand_mode_gradients_vs_emulation():
     hip = HipBeit("beitv2_tiny_test", init_values=0.5)
     hip.load_state_dict(cpu.state_dict(), strict=True)
     hip = hip.to(DEV)
-    prev = ops.get_linear_dtype()
-    try:
-        ops.set_linear_dtype("bf16")
+    with linear_mode("bf16"):
         f_hip, g_hip = run(hip, DEV)
-    finally:
-        ops.set_linear_dtype(prev)
     assert rel_err(f_emu, f_ref) > 1e-4
     assert rel_err(f_hip, f_ref) <= 1.5 * rel_err(f_emu, f_ref) + 1e-3, (rel_err(f_hip, f_ref), rel_err(f_emu, f_ref))
     rows = grad_distance_report(g_ref, g_hip, g_emu)

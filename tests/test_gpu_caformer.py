@@ -5,7 +5,7 @@ import torch
 import torch.nn.functional as F
 
 from caformer_oracle import OracleCAFormer, bf16_attention
-from gpu_util import DEV, rel_err
+from gpu_util import DEV, linear_mode, rel_err
 from helpers import disable_dropout
 from oracle.detinit import det_init_, det_inputs, det_tensor
 
@@ -71,7 +71,7 @@ def _star_mlp_reference(x, w1, w2, s, b, res):
 @pytest.mark.parametrize("mode,rows,tol", [("bf16", 4096, 5e-2), ("fp32", 4096, 1e-4), ("bf16", 200, 1e-4)])
 @pytest.mark.parametrize("sb", [(1.0, 0.0), (-0.15, 0.1)])
 def test_star_relu_mlp(mode, rows, tol, sb):
-    """bf16 mode at 4096 rows takes the kept-operand path (StarMlpFn); fp32 mode and 200 rows the elementwise StarReLU fallback."""
+    """bf16 mode at 4096 rows takes the kept-operand path (MlpFn with StarReLU); fp32 mode and 200 rows the elementwise StarReLU fallback."""
     from mmskin import ops
     D = 128
     x = det_tensor(f"smlp.x.{rows}", (rows, D))
@@ -82,15 +82,11 @@ def test_star_relu_mlp(mode, rows, tol, sb):
     s, b = torch.tensor([sb[0]]), torch.tensor([sb[1]])
     y_ref, leaves_ref = _star_mlp_reference(x, w1, w2, s, b, res)
     y_ref.backward(dy.double())
-    prev = ops.get_linear_dtype()
-    try:
-        ops.set_linear_dtype(mode)
+    with linear_mode(mode):
         leaves = [t.to(DEV).requires_grad_() for t in (x, w1, w2, s, b)]
         y = ops.mlp(leaves[0], leaves[1], None, leaves[2], None, residual=res.to(DEV), star_relu=(leaves[3], leaves[4]))
         y.backward(dy.to(DEV))
         torch.cuda.synchronize()
-    finally:
-        ops.set_linear_dtype(prev)
     assert _max_rel(y.detach().cpu(), y_ref) < tol
     for got, want in zip(leaves, leaves_ref):
         assert rel_err(got.grad.cpu().double(), want.grad) < tol, (got.shape, rel_err(got.grad.cpu().double(), want.grad))
@@ -189,19 +185,14 @@ def test_caformer_b36_forward_backward():
 
 def test_caformer_s18_bf16_operand_mode_vs_emulation():
     from bf16_emulation import assert_grads_not_worse_than_emulation, bf16_operand_emulation, grad_distance_report
-    from mmskin import ops
     cpu, hip = _pair("caformer_s18")
     x, w = det_tensor("caf.xb", (4, 3, 224, 224)), det_tensor("caf.wb", (4, 512))
     f_ref, g_ref = _run(cpu, x, w, "cpu")
     emu = det_init_(OracleCAFormer("caformer_s18"))
     with bf16_operand_emulation(), bf16_attention():
         f_emu, g_emu = _run(emu, x, w, "cpu")
-    prev = ops.get_linear_dtype()
-    try:
-        ops.set_linear_dtype("bf16")
+    with linear_mode("bf16"):
         f_hip, g_hip = _run(hip, x, w, DEV)
-    finally:
-        ops.set_linear_dtype(prev)
     assert rel_err(f_emu, f_ref) > 1e-4
     assert rel_err(f_hip, f_ref) <= 1.5 * rel_err(f_emu, f_ref) + 1e-3, (rel_err(f_hip, f_ref), rel_err(f_emu, f_ref))
     # The StarReLU scalars' gradients are sums over 10^5 - 10^6 terms that largely cancel: the bf16 roundings of the gradient flowing
@@ -226,7 +217,6 @@ def test_caformer_s18_input_160x192():
 @pytest.mark.parametrize("mode", ["fp32", "bf16"])
 def test_caformer_s18_frozen_no_grad(mode):
     from bf16_emulation import bf16_operand_emulation
-    from mmskin import ops
     from models.loadImageModelClassifier import loadModels
     cpu = det_init_(OracleCAFormer("caformer_s18")).eval()
     hip, _ = loadModels.loadModelImageEncoder("caformer_s18", 512, "frozen_weights")
@@ -238,12 +228,8 @@ def test_caformer_s18_frozen_no_grad(mode):
         if mode == "bf16":
             with bf16_operand_emulation(), bf16_attention():
                 f_emu = cpu(x)
-        prev = ops.get_linear_dtype()
-        try:
-            ops.set_linear_dtype(mode)
+        with linear_mode(mode):
             f_hip = hip(x.to(DEV)).cpu()
-        finally:
-            ops.set_linear_dtype(prev)
     if mode == "fp32":
         assert rel_err(f_hip, f_ref) < 5e-4, rel_err(f_hip, f_ref)
     else:   # the no-gradient fused bf16 attention rounds more than the emulation models (3.4x its distance measured): bound 4x

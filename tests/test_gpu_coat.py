@@ -7,7 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from coat_oracle import OracleCoaT
-from gpu_util import DEV, rel_err
+from gpu_util import DEV, linear_mode, rel_err
 from helpers import disable_dropout
 from oracle.detinit import det_init_, det_inputs, det_tensor
 
@@ -172,19 +172,14 @@ def test_coat_lite_matches_oracle(name, B, hw):
 
 def test_coat_lite_tiny_bf16_operand_mode_vs_emulation():
     from bf16_emulation import assert_grads_not_worse_than_emulation, bf16_operand_emulation, grad_distance_report
-    from mmskin import ops
     cpu, hip = _pair("coat_lite_tiny")
     x, w = det_tensor("coat.xb", (2, 3, 224, 224)), det_tensor("coat.wb", (2, 320))
     f_ref, g_ref = _run(cpu, x, w, "cpu")
     emu = det_init_(OracleCoaT("coat_lite_tiny"))
     with bf16_operand_emulation():
         f_emu, g_emu = _run(emu, x, w, "cpu")
-    prev = ops.get_linear_dtype()
-    try:
-        ops.set_linear_dtype("bf16")
+    with linear_mode("bf16"):
         f_hip, g_hip = _run(hip, x, w, DEV)
-    finally:
-        ops.set_linear_dtype(prev)
     print(f"bf16: rel_err hip {rel_err(f_hip, f_ref):.3e}, emulation {rel_err(f_emu, f_ref):.3e}")
     assert rel_err(f_emu, f_ref) > 1e-4
     assert rel_err(f_hip, f_ref) <= 1.5 * rel_err(f_emu, f_ref) + 1e-3, (rel_err(f_hip, f_ref), rel_err(f_emu, f_ref))
@@ -198,7 +193,6 @@ def test_coat_lite_tiny_bf16_operand_mode_vs_emulation():
 @pytest.mark.parametrize("mode", ["fp32", "bf16"])
 def test_coat_lite_small_frozen_no_grad(mode):
     from bf16_emulation import bf16_operand_emulation
-    from mmskin import ops
     from models.loadImageModelClassifier import loadModels
     cpu = det_init_(OracleCoaT("coat_lite_small")).eval()
     hip, dim = loadModels.loadModelImageEncoder("coat_lite_small.in1k", 512, "frozen_weights")
@@ -210,12 +204,8 @@ def test_coat_lite_small_frozen_no_grad(mode):
         if mode == "bf16":
             with bf16_operand_emulation():
                 f_emu = cpu(x)
-        prev = ops.get_linear_dtype()
-        try:
-            ops.set_linear_dtype(mode)
+        with linear_mode(mode):
             f_hip = hip(x.to(DEV)).cpu()
-        finally:
-            ops.set_linear_dtype(prev)
     assert f_hip.shape == (2, 512) and dim == 512
     if mode == "fp32":
         assert rel_err(f_hip, f_ref) < 5e-4, rel_err(f_hip, f_ref)

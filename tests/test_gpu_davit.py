@@ -5,7 +5,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_util import DEV, rel_err
+from gpu_util import DEV, linear_mode, rel_err
 from helpers import SMALL, disable_dropout
 from oracle.altmodels import OracleDaVit
 from oracle.detinit import det_init_, det_inputs, det_tensor
@@ -45,7 +45,6 @@ def test_davit_bf16_operand_mode_gradients_vs_emulation():
     gradient to the fp32 oracle's, bounded by the CPU bf16-operand emulation of the oracle (tests/bf16_emulation.py: the same
     operand roundings, torch's summation order) -- at most 1.5 x its distance (+2e-3), cosine no more than 0.02 below its."""
     from bf16_emulation import assert_grads_not_worse_than_emulation, bf16_operand_emulation, grad_distance_report
-    from mmskin import ops
     from models.hip_davit import HipDaVit
     x = det_tensor("davit.xb", (4, 3, 224, 224))
     w = det_tensor("davit.wb", (4, 768))
@@ -64,12 +63,8 @@ def test_davit_bf16_operand_mode_gradients_vs_emulation():
     hip = HipDaVit("davit_tiny.msft_in1k")
     hip.load_state_dict(cpu.state_dict(), strict=True)
     hip = hip.to(DEV)
-    prev = ops.get_linear_dtype()
-    try:
-        ops.set_linear_dtype("bf16")
+    with linear_mode("bf16"):
         f_hip, g_hip = run(hip, DEV)
-    finally:
-        ops.set_linear_dtype(prev)
     assert rel_err(f_emu, f_ref) > 1e-4                       # the emulation really rounds something at this size
     assert rel_err(f_hip, f_ref) <= 1.5 * rel_err(f_emu, f_ref) + 1e-3, (rel_err(f_hip, f_ref), rel_err(f_emu, f_ref))
     rows = grad_distance_report(g_ref, g_hip, g_emu)

@@ -11,7 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_util import DEV
+from gpu_util import DEV, linear_mode
 from mmskin import ops
 
 pytestmark = pytest.mark.gpu
@@ -150,14 +150,10 @@ def test_linear_gelu_backward_in_one_call(mode, M, K, N):
     dh = torch.randn(M, N, generator=g)
     xr, wr, br = (t.double().requires_grad_(True) for t in (x, w, b))
     F.gelu(F.linear(xr, wr, br)).backward(dh.double())
-    prev = ops.get_linear_dtype()
-    ops.set_linear_dtype(mode)
-    try:
+    with linear_mode(mode):
         xd, wd, bd = (t.to(DEV).requires_grad_(True) for t in (x, w, b))
         h = ops.linear_gelu(xd, wd, bd)
         h.backward(dh.to(DEV))
-    finally:
-        ops.set_linear_dtype(prev)
     ref = F.gelu(F.linear(x.double(), w.double(), b.double()))
     for got, want in ((h, ref), (xd.grad, xr.grad), (wd.grad, wr.grad), (bd.grad, br.grad)):
         got, want = got.detach().cpu().double(), want.detach()
@@ -181,14 +177,10 @@ def test_mlp_fc1_gelu_fc2(mode, M, C):
     ref = [t.double().requires_grad_(True) for t in (x, w1, b1, w2, b2)]
     y_ref = F.linear(F.gelu(F.linear(ref[0], ref[1], ref[2])), ref[3], ref[4])
     y_ref.backward(dy.double())
-    prev = ops.get_linear_dtype()
-    ops.set_linear_dtype(mode)
-    try:
+    with linear_mode(mode):
         dev = [t.to(DEV).requires_grad_(True) for t in (x, w1, b1, w2, b2)]
         y = ops.mlp(*dev)
         y.backward(dy.to(DEV))
-    finally:
-        ops.set_linear_dtype(prev)
     pairs = [(y, y_ref)] + [(d.grad, r.grad) for d, r in zip(dev, ref)]
     for got, want in pairs:
         got, want = got.detach().cpu().double(), want.detach()
@@ -210,9 +202,7 @@ def test_linear_and_mlp_with_fused_residual(mode, M, K):
     w1 = torch.randn(4 * K, K, generator=g) / K ** 0.5; b1 = torch.randn(4 * K, generator=g) * 0.1
     w2 = torch.randn(K, 4 * K, generator=g) / (4 * K) ** 0.5; b2 = torch.randn(K, generator=g) * 0.1
     dy = torch.randn(M, K, generator=g)
-    prev = ops.get_linear_dtype()
-    ops.set_linear_dtype(mode)
-    try:
+    with linear_mode(mode):
         for case in ("linear", "mlp"):
             rx, rr = x.double().requires_grad_(True), res.double().requires_grad_(True)
             dx_, dr_ = x.to(DEV).requires_grad_(True), res.to(DEV).requires_grad_(True)
@@ -229,5 +219,3 @@ def test_linear_and_mlp_with_fused_residual(mode, M, K):
                     assert (got - want).abs().max().item() <= 1e-4 * max(1.0, want.abs().max().item()), case
                 else:
                     assert ((got - want).norm() / want.norm()).item() < 2e-2, case
-    finally:
-        ops.set_linear_dtype(prev)

@@ -8,17 +8,10 @@ import math
 import pytest
 import torch
 
-from gpu_util import DEV, rel_err
+from gpu_util import DEV, linear_mode, rel_err
 from mmskin import ops
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(autouse=True)
-def _restore_mode():
-    prev = ops.get_linear_dtype()
-    yield
-    ops.set_linear_dtype(prev)
 
 
 def _inputs(B, H, L, D, seed):
@@ -75,10 +68,10 @@ def test_flash_forward_matches_unfused_and_torch(B, H, L, D, kind):
     want = _torch_ref(q, k, v, mask, bias, causal)
     dev = lambda t: None if t is None else t.to(DEV)
     with torch.no_grad():
-        ops.set_linear_dtype("fp32")
-        unfused = ops.attention(dev(q), dev(k), dev(v), mask_add=dev(mask), bias=dev(bias), causal=causal).cpu()
-        ops.set_linear_dtype("bf16")
-        fused = ops.attention(dev(q), dev(k), dev(v), mask_add=dev(mask), bias=dev(bias), causal=causal).cpu()
+        with linear_mode("fp32"):
+            unfused = ops.attention(dev(q), dev(k), dev(v), mask_add=dev(mask), bias=dev(bias), causal=causal).cpu()
+        with linear_mode("bf16"):
+            fused = ops.attention(dev(q), dev(k), dev(v), mask_add=dev(mask), bias=dev(bias), causal=causal).cpu()
     assert rel_err(unfused, want) < 1e-4
     assert torch.isfinite(fused).all()
     emu = _torch_ref(q, k, v, mask, bias, causal, bf16=True)
@@ -99,10 +92,10 @@ def test_flash_fully_masked_row_is_the_uniform_average_like_torch():
     assert rel_err(want[1], v[1].mean(1, keepdim=True).expand_as(want[1])) < 1e-5      # the reference IS the uniform average
     dev = lambda t: t.to(DEV)
     with torch.no_grad():
-        ops.set_linear_dtype("fp32")
-        unfused = ops.attention(dev(q), dev(k), dev(v), mask_add=dev(mask)).cpu()
-        ops.set_linear_dtype("bf16")
-        fused = ops.attention(dev(q), dev(k), dev(v), mask_add=dev(mask)).cpu()
+        with linear_mode("fp32"):
+            unfused = ops.attention(dev(q), dev(k), dev(v), mask_add=dev(mask)).cpu()
+        with linear_mode("bf16"):
+            fused = ops.attention(dev(q), dev(k), dev(v), mask_add=dev(mask)).cpu()
     assert rel_err(unfused, want) < 1e-4
     assert rel_err(fused[1], want[1]) < 2e-2 and rel_err(fused[0], want[0]) < 6e-2
 
@@ -115,8 +108,7 @@ def test_flash_grid_limit_falls_back_instead_of_raising():
     qkv = torch.randn(B, L, 3, H, D, generator=g)
     want = _torch_ref(*(qkv[:8, :, i].permute(0, 2, 1, 3) for i in range(3))).permute(0, 2, 1, 3)
     qd = qkv.to(DEV)
-    with torch.no_grad():
-        ops.set_linear_dtype("bf16")
+    with linear_mode("bf16"), torch.no_grad():
         assert not ops._flash_ok(qd[:, :, 0], qd[:, :, 1], qd[:, :, 2], None, None, B * H)
         got = ops.attention_packed(qd)
         small = ops.attention_packed(qd[:8].contiguous())       # 24 (batch, head) pairs: the fused kernel
@@ -127,9 +119,8 @@ def test_flash_grid_limit_falls_back_instead_of_raising():
 
 def test_flash_rejects_a_misshapen_bias_or_mask():
     q, k, v = (t.to(DEV) for t in _inputs(2, 2, 70, 64, 4))
-    ops.set_linear_dtype("bf16")
     from mmskin import _lib
-    with torch.no_grad():
+    with linear_mode("bf16"), torch.no_grad():
         with pytest.raises(_lib.MMSkinError):
             ops.attention(q, k, v, bias=torch.zeros(2, 70, 69, device=DEV))
         with pytest.raises(_lib.MMSkinError):
@@ -158,15 +149,15 @@ def test_flash_dropout_drops_the_same_elements_as_the_unfused_path():
     outs = {}
     with torch.no_grad():
         for mode in ("fp32", "bf16"):
-            ops.set_linear_dtype(mode)
+            with linear_mode(mode):
+                torch.manual_seed(1234)
+                ops._dropout_counter[0] = 1000                 # same generator position for both calls
+                outs[mode] = ops.attention(q, k, v, 0.3, True).cpu()
+        with linear_mode("bf16"):
             torch.manual_seed(1234)
-            ops._dropout_counter[0] = 1000                 # same generator position for both calls
-            outs[mode] = ops.attention(q, k, v, 0.3, True).cpu()
-        ops.set_linear_dtype("bf16")
-        torch.manual_seed(1234)
-        ops._dropout_counter[0] = 77777
-        other = ops.attention(q, k, v, 0.3, True).cpu()
-        nodrop = ops.attention(q, k, v, 0.0, True).cpu()
+            ops._dropout_counter[0] = 77777
+            other = ops.attention(q, k, v, 0.3, True).cpu()
+            nodrop = ops.attention(q, k, v, 0.0, True).cpu()
     assert rel_err(outs["bf16"], outs["fp32"]) < 6e-2      # identical mask, bf16 operands
     assert rel_err(other, outs["fp32"]) > 0.2               # another generator position gives another mask
     assert rel_err(nodrop, outs["fp32"]) > 0.2
@@ -200,10 +191,10 @@ def test_flash_backward_matches_fp64_autograd_and_the_unfused_path(B, H, L, D, k
     want = _attn_grads(lambda a, b_, c, bb: _torch_ref64(a, b_, c, mask, bb, causal), q.double(), k.double(), v.double(), w.double(),
                        bias.double() if bias is not None else None)
     dev = lambda t: None if t is None else t.to(DEV)
-    ops.set_linear_dtype("bf16")
-    fused = _attn_grads(lambda a, b_, c, bb: ops.attention(a, b_, c, mask_add=dev(mask), bias=bb, causal=causal), dev(q), dev(k), dev(v), dev(w), dev(bias))
-    monkeypatch.setenv("MMSKIN_FLASH_BWD", "0")
-    unfused = _attn_grads(lambda a, b_, c, bb: ops.attention(a, b_, c, mask_add=dev(mask), bias=bb, causal=causal), dev(q), dev(k), dev(v), dev(w), dev(bias))
+    with linear_mode("bf16"):
+        fused = _attn_grads(lambda a, b_, c, bb: ops.attention(a, b_, c, mask_add=dev(mask), bias=bb, causal=causal), dev(q), dev(k), dev(v), dev(w), dev(bias))
+        monkeypatch.setenv("MMSKIN_FLASH_BWD", "0")
+        unfused = _attn_grads(lambda a, b_, c, bb: ops.attention(a, b_, c, mask_add=dev(mask), bias=bb, causal=causal), dev(q), dev(k), dev(v), dev(w), dev(bias))
     for name, gf, gu, gw in zip(("dq", "dk", "dv", "dbias"), fused, unfused, want):
         assert torch.isfinite(gf).all(), name
         assert rel_err(gu, gw) < 2e-3, (name, "unfused", rel_err(gu, gw))
@@ -236,17 +227,16 @@ def test_flash_backward_regenerates_the_forward_dropout_mask(monkeypatch):
     B, H, L, D = 2, 2, 200, 64
     q, k, v = (t.to(DEV) for t in _inputs(B, H, L, D, 11))
     w = torch.randn(B, H, L, D, generator=torch.Generator().manual_seed(4)).to(DEV)
-    ops.set_linear_dtype("bf16")
+    with linear_mode("bf16"):
+        def grads(pos):
+            torch.manual_seed(99)
+            ops._dropout_counter[0] = pos
+            return _attn_grads(lambda a, b_, c, bb: ops.attention(a, b_, c, 0.25, True), q, k, v, w, None)
 
-    def grads(pos):
-        torch.manual_seed(99)
-        ops._dropout_counter[0] = pos
-        return _attn_grads(lambda a, b_, c, bb: ops.attention(a, b_, c, 0.25, True), q, k, v, w, None)
-
-    fused = grads(4096)
-    other = grads(123456)
-    monkeypatch.setenv("MMSKIN_FLASH_BWD", "0")
-    unfused = grads(4096)
+        fused = grads(4096)
+        other = grads(123456)
+        monkeypatch.setenv("MMSKIN_FLASH_BWD", "0")
+        unfused = grads(4096)
     for name, gf, gu, go in zip(("dq", "dk", "dv"), fused, unfused, other):
         assert rel_err(gf, gu) < 6e-2, (name, rel_err(gf, gu))
         assert rel_err(go, gu) > 0.2, name
@@ -260,20 +250,20 @@ def test_flash_reads_a_fused_qkv_tensor_in_place():
     want = _torch_ref(*(qkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))).permute(0, 2, 1, 3)
     qd = qkv.to(DEV)
     with torch.no_grad():
-        ops.set_linear_dtype("bf16")
-        got = ops.attention_blhd(qd[:, :, 0], qd[:, :, 1], qd[:, :, 2])
+        with linear_mode("bf16"):
+            got = ops.attention_blhd(qd[:, :, 0], qd[:, :, 1], qd[:, :, 2])
         assert got.shape == (B, L, H, D) and got.is_contiguous()
         assert rel_err(got.cpu(), want) < 6e-2
-        ops.set_linear_dtype("fp32")                                        # unfused fallback of the same entry
-        assert rel_err(ops.attention_blhd(qd[:, :, 0], qd[:, :, 1], qd[:, :, 2]).cpu(), want) < 1e-4
+        with linear_mode("fp32"):       # unfused fallback of the same entry
+            assert rel_err(ops.attention_blhd(qd[:, :, 0], qd[:, :, 1], qd[:, :, 2]).cpu(), want) < 1e-4
 
 
 def test_trainable_attention_keeps_the_differentiable_path():
     """Gradients must keep flowing: with requires_grad inputs bf16 mode uses the unfused ops (which save the probabilities)."""
-    ops.set_linear_dtype("bf16")
-    q, k, v = (t.to(DEV).requires_grad_(True) for t in _inputs(1, 2, 70, 64, 3))
-    o = ops.attention(q, k, v)
-    o.sum().backward()
+    with linear_mode("bf16"):
+        q, k, v = (t.to(DEV).requires_grad_(True) for t in _inputs(1, 2, 70, 64, 3))
+        o = ops.attention(q, k, v)
+        o.sum().backward()
     assert q.grad is not None and torch.isfinite(q.grad).all() and float(q.grad.abs().max()) > 0
 
 
@@ -285,15 +275,14 @@ def test_linear_gelu_epilogue(M, K, N):
     x, w, b = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) / K ** 0.5, torch.randn(N, generator=g)
     want = torch.nn.functional.gelu(x.double() @ w.double().T + b.double()).float()
     for mode, tol in (("fp32", 1e-4), ("bf16", 3e-2)):
-        ops.set_linear_dtype(mode)
-        with torch.no_grad():
+        with linear_mode(mode), torch.no_grad():
             fused = ops.linear_gelu(x.to(DEV), w.to(DEV), b.to(DEV)).cpu()
             pair = ops.gelu(ops.linear(x.to(DEV), w.to(DEV), b.to(DEV))).cpu()
         assert rel_err(fused, want) < tol, (mode, rel_err(fused, want))
         assert rel_err(fused, pair) < (1e-5 if mode == "fp32" else 1e-2)     # bf16: the unfused pair rounds the pre-activation to bf16 too
-    ops.set_linear_dtype("fp32")
-    xg = x.to(DEV).requires_grad_(True)
-    ops.linear_gelu(xg, w.to(DEV), b.to(DEV)).sum().backward()
+    with linear_mode("fp32"):
+        xg = x.to(DEV).requires_grad_(True)
+        ops.linear_gelu(xg, w.to(DEV), b.to(DEV)).sum().backward()
     xr = x.clone().requires_grad_(True)
     torch.nn.functional.gelu(xr @ w.T + b).sum().backward()
     assert rel_err(xg.grad.cpu(), xr.grad) < 1e-3
@@ -302,37 +291,37 @@ def test_linear_gelu_epilogue(M, K, N):
 def test_flash_bf16_tensors_and_lane_ops():
     """The inference lane's bf16 tensors: attention on bf16 q / k / v views (bf16 out), Linear with bf16 in / out and LayerNorm with a
     bf16 (and fp32) result -- each against fp64 math on the values those tensors actually hold."""
-    ops.set_linear_dtype("bf16")
-    B, L, H, D = 2, 197, 4, 64
-    g = torch.Generator().manual_seed(11)
-    qkv = torch.randn(B, L, 3, H, D, generator=g).bfloat16()
-    want = _torch_ref(*(qkv[:, :, i].float().permute(0, 2, 1, 3) for i in range(3))).permute(0, 2, 1, 3)
-    qd = qkv.to(DEV)
-    with torch.no_grad():
-        got = ops.attention_blhd(qd[:, :, 0], qd[:, :, 1], qd[:, :, 2])
-    assert got.dtype == torch.bfloat16 and got.shape == (B, L, H, D)
-    assert rel_err(got.float().cpu(), want) < 3e-2
-    # Linear: bf16 in -> bf16 out with GELU, bf16 in -> fp32 out, small shape through the fallback
-    for M, K, N in ((4096, 256, 512), (96, 64, 40)):
-        x = torch.randn(M, K, generator=g).bfloat16()
-        w, b = torch.randn(N, K, generator=g) / K ** 0.5, torch.randn(N, generator=g)
-        ref = x.double() @ w.double().T + b.double()
+    with linear_mode("bf16"):
+        B, L, H, D = 2, 197, 4, 64
+        g = torch.Generator().manual_seed(11)
+        qkv = torch.randn(B, L, 3, H, D, generator=g).bfloat16()
+        want = _torch_ref(*(qkv[:, :, i].float().permute(0, 2, 1, 3) for i in range(3))).permute(0, 2, 1, 3)
+        qd = qkv.to(DEV)
         with torch.no_grad():
-            y32 = ops.linear(x.to(DEV), w.to(DEV), b.to(DEV))
-            y16 = ops.linear_gelu(x.to(DEV), w.to(DEV), b.to(DEV), out_dtype=torch.bfloat16)
-        assert y32.dtype == torch.float32 and y16.dtype == torch.bfloat16
-        assert rel_err(y32.cpu(), ref.float()) < 2e-2
-        assert rel_err(y16.float().cpu(), torch.nn.functional.gelu(ref).float()) < 3e-2
-    # LayerNorm: one pass, fp32 + bf16 results
-    x = torch.randn(300, 768, generator=g)
-    gam, bet = torch.rand(768, generator=g) + 0.5, torch.randn(768, generator=g)
-    ref = torch.nn.functional.layer_norm(x.double(), (768,), gam.double(), bet.double(), 1e-6).float()
-    with torch.no_grad():
-        y32, y16 = ops.layernorm(x.to(DEV), gam.to(DEV), bet.to(DEV), 1e-6, out_dtype=torch.bfloat16, keep_f32=True)
-    assert rel_err(y32.cpu(), ref) < 1e-5 and y16.dtype == torch.bfloat16 and rel_err(y16.float().cpu(), ref) < 2.5e-2   # 2^-9 of |y| <= 4
-    # a gradient-carrying input is refused on the lane instead of silently detached
-    with pytest.raises(Exception):
-        ops.linear(x.to(DEV).bfloat16().requires_grad_(True), w.to(DEV)[:, :768] if w.shape[1] >= 768 else torch.randn(8, 768, device=DEV))
+            got = ops.attention_blhd(qd[:, :, 0], qd[:, :, 1], qd[:, :, 2])
+        assert got.dtype == torch.bfloat16 and got.shape == (B, L, H, D)
+        assert rel_err(got.float().cpu(), want) < 3e-2
+        # Linear: bf16 in -> bf16 out with GELU, bf16 in -> fp32 out, small shape through the fallback
+        for M, K, N in ((4096, 256, 512), (96, 64, 40)):
+            x = torch.randn(M, K, generator=g).bfloat16()
+            w, b = torch.randn(N, K, generator=g) / K ** 0.5, torch.randn(N, generator=g)
+            ref = x.double() @ w.double().T + b.double()
+            with torch.no_grad():
+                y32 = ops.linear(x.to(DEV), w.to(DEV), b.to(DEV))
+                y16 = ops.linear_gelu(x.to(DEV), w.to(DEV), b.to(DEV), out_dtype=torch.bfloat16)
+            assert y32.dtype == torch.float32 and y16.dtype == torch.bfloat16
+            assert rel_err(y32.cpu(), ref.float()) < 2e-2
+            assert rel_err(y16.float().cpu(), torch.nn.functional.gelu(ref).float()) < 3e-2
+        # LayerNorm: one pass, fp32 + bf16 results
+        x = torch.randn(300, 768, generator=g)
+        gam, bet = torch.rand(768, generator=g) + 0.5, torch.randn(768, generator=g)
+        ref = torch.nn.functional.layer_norm(x.double(), (768,), gam.double(), bet.double(), 1e-6).float()
+        with torch.no_grad():
+            y32, y16 = ops.layernorm(x.to(DEV), gam.to(DEV), bet.to(DEV), 1e-6, out_dtype=torch.bfloat16, keep_f32=True)
+        assert rel_err(y32.cpu(), ref) < 1e-5 and y16.dtype == torch.bfloat16 and rel_err(y16.float().cpu(), ref) < 2.5e-2   # 2^-9 of |y| <= 4
+        # a gradient-carrying input is refused on the lane instead of silently detached
+        with pytest.raises(Exception):
+            ops.linear(x.to(DEV).bfloat16().requires_grad_(True), w.to(DEV)[:, :768] if w.shape[1] >= 768 else torch.randn(8, 768, device=DEV))
 
 
 def test_bert_bf16_lane_matches_transformers():
@@ -351,10 +340,10 @@ def test_bert_bf16_lane_matches_transformers():
     mask = torch.ones(6, 512, dtype=torch.long); mask[1, 300:] = 0; mask[4, 17:] = 0
     with torch.no_grad():
         want = hf(input_ids=ids, attention_mask=mask).last_hidden_state[:, 0]
-        ops.set_linear_dtype("bf16")
-        got = hip(input_ids=ids.to(DEV), attention_mask=mask.to(DEV)).last_hidden_state[:, 0].cpu()
-        ops.set_linear_dtype("fp32")
-        exact = hip(input_ids=ids.to(DEV), attention_mask=mask.to(DEV)).last_hidden_state[:, 0].cpu()
+        with linear_mode("bf16"):
+            got = hip(input_ids=ids.to(DEV), attention_mask=mask.to(DEV)).last_hidden_state[:, 0].cpu()
+        with linear_mode("fp32"):
+            exact = hip(input_ids=ids.to(DEV), attention_mask=mask.to(DEV)).last_hidden_state[:, 0].cpu()
     assert rel_err(exact, want) < 5e-4
     assert rel_err(got, want) < 5e-2, rel_err(got, want)
 
@@ -364,47 +353,47 @@ def test_linear_lane_fused_tail_matches_separate_ops():
     ops (Linear on the lane -> dropout op -> scale_add): identical dropout mask (same generator, same element index), bf16-rounded
     GEMM result in both, so the two agree to fp32 rounding; stacked weights = one GEMM over the concatenation; the cached bf16
     weight follows in-place updates of its source; shapes off the fused path are composed from the separate ops."""
-    ops.set_linear_dtype("bf16")
-    g = torch.Generator().manual_seed(21)
-    M, K, N = 4096 + 40, 256, 384                       # ragged last row block
-    x = torch.randn(M, K, generator=g).bfloat16().to(DEV)
-    w = (torch.randn(N, K, generator=g) / K ** 0.5).to(DEV)
-    b, gam = torch.randn(N, generator=g).to(DEV), (torch.rand(N, generator=g) + 0.5).to(DEV)
-    res = torch.randn(M, N, generator=g).to(DEV)
-    with torch.no_grad():
-        for act, p, use_g, use_r in ((0, 0.0, True, True), (2, 0.0, False, True), (0, 0.1, False, True), (1, 0.25, True, True), (0, 0.1, False, False)):
-            state = list(ops._dropout_counter)
-            y = ops.linear_lane(x, w, b, act, gam if use_g else None, res if use_r else None, p, True)
-            ops._dropout_counter[:] = state               # replay the same dropout call for the separate ops
-            h = ops.linear_lane(x, w, b, act)                                  # fp32 out, plain epilogue
-            if p > 0:
-                h = ops.dropout(h, p, True)
-            want = h * (gam if use_g else 1.0) + (res if use_r else 0.0)
-            assert y.dtype == torch.float32 and y.shape == (M, N)
-            assert rel_err(y.cpu(), want.cpu()) < 1e-6, (act, p, use_g, use_r, rel_err(y.cpu(), want.cpu()))
-            if p > 0 and act == 0:
-                assert abs(float((h == 0).float().mean()) - p) < 0.01
-        # against fp64 math on the bf16 operands
-        ref = res.double().cpu() + gam.double().cpu() * (x.double().cpu() @ w.bfloat16().double().cpu().T + b.double().cpu())
-        assert rel_err(ops.linear_lane(x, w, b, 0, gam, res).cpu(), ref.float()) < 2e-2
-        # stacked weights: one GEMM over the concatenation
-        w2 = (torch.randn(128, K, generator=g) / K ** 0.5).to(DEV)
-        b2 = torch.randn(N + 128, generator=g).to(DEV)
-        ys = ops.linear_lane(x, (w, w2), b2, out_dtype=torch.bfloat16)
-        yc = ops.linear_lane(x, torch.cat([w, w2]), b2, out_dtype=torch.bfloat16)
-        assert ys.dtype == torch.bfloat16 and torch.equal(ys, yc)
-        # the cache follows an in-place update of the source weight
-        y0 = ops.linear_lane(x, w, b)
-        w.mul_(2.0)
-        y1 = ops.linear_lane(x, w, b)
-        assert rel_err((y1 - b).cpu(), (2.0 * (y0 - b)).cpu()) < 1e-2
-        # off the fused path (few rows; N not a multiple of 128 with a tail): composed from the separate ops
-        xs = torch.randn(96, 64, generator=g).to(DEV)
-        ws, rs = torch.randn(40, 64, generator=g).to(DEV), torch.randn(96, 40, generator=g).to(DEV)
-        ysm = ops.linear_lane(xs, ws, None, 0, None, rs)
-        assert rel_err(ysm.cpu(), (xs @ ws.T + rs).cpu()) < 2e-2
-    with pytest.raises(Exception):
-        ops.linear_lane(x.float().requires_grad_(True), w, b)
+    with linear_mode("bf16"):
+        g = torch.Generator().manual_seed(21)
+        M, K, N = 4096 + 40, 256, 384                       # ragged last row block
+        x = torch.randn(M, K, generator=g).bfloat16().to(DEV)
+        w = (torch.randn(N, K, generator=g) / K ** 0.5).to(DEV)
+        b, gam = torch.randn(N, generator=g).to(DEV), (torch.rand(N, generator=g) + 0.5).to(DEV)
+        res = torch.randn(M, N, generator=g).to(DEV)
+        with torch.no_grad():
+            for act, p, use_g, use_r in ((0, 0.0, True, True), (2, 0.0, False, True), (0, 0.1, False, True), (1, 0.25, True, True), (0, 0.1, False, False)):
+                state = list(ops._dropout_counter)
+                y = ops.linear_lane(x, w, b, act, gam if use_g else None, res if use_r else None, p, True)
+                ops._dropout_counter[:] = state               # replay the same dropout call for the separate ops
+                h = ops.linear_lane(x, w, b, act)                                  # fp32 out, plain epilogue
+                if p > 0:
+                    h = ops.dropout(h, p, True)
+                want = h * (gam if use_g else 1.0) + (res if use_r else 0.0)
+                assert y.dtype == torch.float32 and y.shape == (M, N)
+                assert rel_err(y.cpu(), want.cpu()) < 1e-6, (act, p, use_g, use_r, rel_err(y.cpu(), want.cpu()))
+                if p > 0 and act == 0:
+                    assert abs(float((h == 0).float().mean()) - p) < 0.01
+            # against fp64 math on the bf16 operands
+            ref = res.double().cpu() + gam.double().cpu() * (x.double().cpu() @ w.bfloat16().double().cpu().T + b.double().cpu())
+            assert rel_err(ops.linear_lane(x, w, b, 0, gam, res).cpu(), ref.float()) < 2e-2
+            # stacked weights: one GEMM over the concatenation
+            w2 = (torch.randn(128, K, generator=g) / K ** 0.5).to(DEV)
+            b2 = torch.randn(N + 128, generator=g).to(DEV)
+            ys = ops.linear_lane(x, (w, w2), b2, out_dtype=torch.bfloat16)
+            yc = ops.linear_lane(x, torch.cat([w, w2]), b2, out_dtype=torch.bfloat16)
+            assert ys.dtype == torch.bfloat16 and torch.equal(ys, yc)
+            # the cache follows an in-place update of the source weight
+            y0 = ops.linear_lane(x, w, b)
+            w.mul_(2.0)
+            y1 = ops.linear_lane(x, w, b)
+            assert rel_err((y1 - b).cpu(), (2.0 * (y0 - b)).cpu()) < 1e-2
+            # off the fused path (few rows; N not a multiple of 128 with a tail): composed from the separate ops
+            xs = torch.randn(96, 64, generator=g).to(DEV)
+            ws, rs = torch.randn(40, 64, generator=g).to(DEV), torch.randn(96, 40, generator=g).to(DEV)
+            ysm = ops.linear_lane(xs, ws, None, 0, None, rs)
+            assert rel_err(ysm.cpu(), (xs @ ws.T + rs).cpu()) < 2e-2
+        with pytest.raises(Exception):
+            ops.linear_lane(x.float().requires_grad_(True), w, b)
 
 
 @pytest.mark.parametrize("B,H,L,Dh,p", [(3, 3, 49, 32, 0.0), (2, 2, 64, 64, 0.0), (5, 1, 7, 32, 0.0), (2, 3, 49, 32, 0.2)])
@@ -461,21 +450,21 @@ def test_linear_bf16_padded_widths(M, K, N):
     """bf16-operand Linear with widths that are not multiples of 64 (DaViT stage 1: 96 / 288): zero-padded bf16 operand copies on the
     MFMA GEMM kernels, un-padded while widening -- forward (+ bias, ReLU) and dx / dw / db against float64 math on the bf16-rounded
     operands (the pad columns must contribute exact zeros)."""
-    ops.set_linear_dtype("bf16")
-    g = torch.Generator().manual_seed(M + K)
-    x, w, b = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) / K ** 0.5, torch.randn(N, generator=g)
-    dy = torch.randn(M, N, generator=g)
-    xr, wr = x.bfloat16().double(), w.bfloat16().double()
-    for relu in (False, True):
-        xd, wd, bd = x.to(DEV).requires_grad_(True), w.to(DEV).requires_grad_(True), b.to(DEV).requires_grad_(True)
-        y = ops.linear(xd, wd, bd, relu)
-        y.backward(dy.to(DEV))
-        ref = xr @ wr.T + b.double()
-        gg = dy.double() * ((y.detach().cpu() > 0) if relu else 1.0)     # the ReLU mask the backward really used (sign flips next to 0 are rounding)
-        if relu:
-            ref = ref.clamp_min(0)
-        assert rel_err(y.detach().cpu(), ref.float()) < 2.5e-2     # the GEMM result is staged in bf16 before bias / ReLU: 2^-9 of |y| <= 4
-        gr = gg.bfloat16().double()                      # the gradient operand is rounded to bf16 as well
-        assert rel_err(xd.grad.cpu(), (gr @ wr).float()) < 2e-2
-        assert rel_err(wd.grad.cpu(), (gr.T @ xr).float()) < 2e-2
-        assert rel_err(bd.grad.cpu(), gg.sum(0).float()) < 1e-4
+    with linear_mode("bf16"):
+        g = torch.Generator().manual_seed(M + K)
+        x, w, b = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) / K ** 0.5, torch.randn(N, generator=g)
+        dy = torch.randn(M, N, generator=g)
+        xr, wr = x.bfloat16().double(), w.bfloat16().double()
+        for relu in (False, True):
+            xd, wd, bd = x.to(DEV).requires_grad_(True), w.to(DEV).requires_grad_(True), b.to(DEV).requires_grad_(True)
+            y = ops.linear(xd, wd, bd, relu)
+            y.backward(dy.to(DEV))
+            ref = xr @ wr.T + b.double()
+            gg = dy.double() * ((y.detach().cpu() > 0) if relu else 1.0)     # the ReLU mask the backward really used (sign flips next to 0 are rounding)
+            if relu:
+                ref = ref.clamp_min(0)
+            assert rel_err(y.detach().cpu(), ref.float()) < 2.5e-2     # the GEMM result is staged in bf16 before bias / ReLU: 2^-9 of |y| <= 4
+            gr = gg.bfloat16().double()                      # the gradient operand is rounded to bf16 as well
+            assert rel_err(xd.grad.cpu(), (gr @ wr).float()) < 2e-2
+            assert rel_err(wd.grad.cpu(), (gr.T @ xr).float()) < 2e-2
+            assert rel_err(bd.grad.cpu(), gg.sum(0).float()) < 1e-4

@@ -12,7 +12,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_util import DEV, rel_err
+from gpu_util import DEV, linear_mode, rel_err
 from helpers import SMALL, disable_dropout
 from mmskin import ops
 from models import multimodalIntraInterModal as M
@@ -74,9 +74,7 @@ def test_config4_davit_tabtransformer_gfcam_b64(mode):
     """configs[3]: davit_tiny.msft_in1k + tab-transformer + gfcam at the per-GPU batch 64 (512 over DP=8); the image
     encoder's eval features of four samples against the oracle restatement (timm absent: parity unpinned)."""
     from oracle.altmodels import OracleDaVit
-    prev = ops.get_linear_dtype()
-    ops.set_linear_dtype(mode)
-    try:
+    with linear_mode(mode):
         kw = dict(SMALL, cnn_model_name="davit_tiny.msft_in1k", text_model_name="tab-transformer", attention_mecanism="gfcam",
                   vocab_size=86, common_dim=512, text_encoder_dim_output=512, unfreeze_weights="unfrozen_weights", device=DEV)
         model = M.MultimodalModel(**kw)
@@ -94,8 +92,6 @@ def test_config4_davit_tabtransformer_gfcam_b64(mode):
             want = ref(img[pick])
         err = rel_err(feats[pick], want)
         assert err < (5e-4 if mode == "fp32" else 3e-2), (mode, err)                  # bf16 operands: ~2^-8 per GEMM over 20 layers
-    finally:
-        ops.set_linear_dtype(prev)
 
 
 @pytest.mark.parametrize("mode", ["fp32", "bf16"])
@@ -103,9 +99,7 @@ def test_config5_beitv2_large_bert_rgatt_b128(mode):
     """configs[4]: beitv2_large_patch16_224 + bert-base-uncased (512 tokens) + the RG-ATT string at the per-GPU batch 128
     (1024 over DP=8), last-block fine-tuning ('partial'); BEiT-large eval features of two samples against the oracle."""
     from oracle.altmodels import OracleBeit
-    prev = ops.get_linear_dtype()
-    ops.set_linear_dtype(mode)
-    try:
+    with linear_mode(mode):
         model = M.MultimodalModel(num_classes=6, num_heads=8, device=DEV, cnn_model_name="beitv2_large_patch16_224",
                                   text_model_name="bert-base-uncased", common_dim=512, vocab_size=20, unfreeze_weights="partial",
                                   attention_mecanism="att-intramodal+residual+cross-attention-metadados", n=2)
@@ -129,8 +123,6 @@ def test_config5_beitv2_large_bert_rgatt_b128(mode):
         assert err < (1e-3 if mode == "fp32" else 3e-2), (mode, err)
         live = [n for n, p in model.named_parameters() if p.grad is not None and n.startswith("image_encoder")]
         assert live and all(n.startswith("image_encoder.blocks.23.") or n.startswith("image_encoder.fc_norm") for n in live)
-    finally:
-        ops.set_linear_dtype(prev)
 
 
 def test_patch_cols_matches_unfold():

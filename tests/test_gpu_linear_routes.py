@@ -29,7 +29,7 @@ import itertools
 import pytest
 import torch
 
-from gpu_util import DEV, rel_err
+from gpu_util import DEV, linear_mode, rel_err
 from linear_route_cases import BIG_BF16, BIG_F32, PADDED, ROUTE_CASES, SMALL, case_id, make_inputs, reference
 from mmskin import _lib, ops
 from mmskin._lib import call, ptr, stream
@@ -85,18 +85,6 @@ def check(label, got, want, metric, tol):
     err = rel_err(got, want) if metric == "max" else l2_err(got, want)
     print(f"{label}: {metric} {err:.3e} (bound {tol:.1e})")
     assert err < tol, f"{label}: {metric} error {err:.3e} >= {tol:.1e}"
-
-
-class linear_mode:
-    def __init__(self, mode):
-        self.mode = mode
-
-    def __enter__(self):
-        self.prev = ops.get_linear_dtype()
-        ops.set_linear_dtype(self.mode)
-
-    def __exit__(self, *exc):
-        ops.set_linear_dtype(self.prev)
 
 
 def assert_route(M, K, N, route):
