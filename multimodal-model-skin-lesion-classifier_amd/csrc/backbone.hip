@@ -18,7 +18,7 @@ struct Unit {  // conv + batch-norm
   int64_t rm_off, rv_off;        // flat buffer offsets
   int64_t wf_off, wd_off;        // staged weight element offsets
   size_t x_off;                  // raw conv output (bytes in workspace)
-  size_t y_off;                  // post-activation output (bytes); for the last unit of a block = block output
+  size_t y_off = 0;              // post-activation output (bytes); for the last unit of a block = block output (stem: none, its output is the pooled map)
   size_t coef_off;               // floats: scale, shift, mean, invstd (4*Cout)
   bool abn = false;              // algebraic BatchNorm backward (abn.hip): expanding 1x1 conv3 of a bottleneck, bf16 plans
   size_t gram_off = 0;           // two-pass unit with Gram statistics: y^T y [128][Cin] + colsum(y) [Cin] of its input, forward -> backward
@@ -37,9 +37,13 @@ struct Block {
   int seg_done = -1;   // gradient segment that is complete once this block's backward has been enqueued
 };
 
+// side-stream slots of backward: 0 / 1 = the alternating dX buffers, 2 = the downsample branch's dX, 3 / 4 = the block-output gradient
+// buffers S[0] / S[1] (algebraic path: the weight-gradient stream reads them itself)
+constexpr int SIDE_SLOTS = 5;
+
 struct Plan : PlanBase {
   int arch;
-  int Hp, Wp, OH0, OW0, PH, PW;
+  StemGeom sg;
   std::vector<Unit> units;
   std::vector<Block> blocks;
   int64_t staged_elems = 0;
@@ -79,16 +83,10 @@ int build_plan(Plan& p) {
   const int* depths = bottleneck ? depths50 : depths18;
   const int expansion = bottleneck ? 4 : 1;
   // stem
-  ConvShape s0 = {p.N, p.H, p.W, 3, 64, 7, 7, 2, 3};
-  int u0 = add_unit(p, "conv1", "bn1", s0);
+  p.sg = StemGeom(p.N, p.H, p.W);
+  int u0 = add_unit(p, "conv1", "bn1", p.sg.conv());
   p.units[u0].stem = true;
-  p.OH0 = s0.OH(); p.OW0 = s0.OW();
-  p.Hp = 2 * p.OH0 + 8; p.Wp = 2 * p.OW0 + 8;
-  if (p.Hp < p.H + 6) p.Hp = p.H + 6;
-  if (p.Wp < p.W + 6) p.Wp = p.W + 6;
-  p.Wp = (p.Wp + 1) / 2 * 2;
-  p.PH = (p.OH0 + 2 - 3) / 2 + 1; p.PW = (p.OW0 + 2 - 3) / 2 + 1;
-  int cin = 64, h = p.PH, w = p.PW;
+  int cin = 64, h = p.sg.PH, w = p.sg.PW;
   const int widths[4] = {64, 128, 256, 512};
   std::vector<int64_t> seg_starts;   // first parameter of layer2, layer3, layer4
   for (int li = 0; li < 4; ++li) {
@@ -155,10 +153,10 @@ int build_plan(Plan& p) {
   // ---- workspace layout
   const size_t es = p.esz();
   size_t cur = 0;
-  p.off_img4 = carve(cur, (size_t)p.N * p.Hp * p.Wp * 4 * es);
+  p.off_img4 = carve(cur, (size_t)p.N * p.sg.Hp * p.sg.Wp * 4 * es);
   p.off_wf = carve(cur, (size_t)wf * es);
   p.off_wd = carve(cur, (size_t)wd * es);
-  size_t stat_rows_max = 0, maxact = 0, slab_max = stem_wgrad_slab_bytes(p.N, p.OH0, p.OW0), partial_max = 0;
+  size_t stat_rows_max = 0, maxact = 0, slab_max = stem_wgrad_slab_bytes(p.N, p.sg.OH, p.sg.OW), partial_max = 0;
   int maxC = 64;
   for (Unit& u : p.units) {
     size_t rows = u.rows();
@@ -189,8 +187,8 @@ int build_plan(Plan& p) {
     d.bn_g_off = u.g_off; d.bn_b_off = u.b_off; d.bn_rm_off = u.rm_off; d.bn_rv_off = u.rv_off;
     d.coef_off = (int64_t)u.coef_off;
   }
-  p.off_pool = carve(cur, (size_t)p.N * p.PH * p.PW * 64 * es);
-  p.off_idx = carve(cur, (size_t)p.N * p.PH * p.PW * 64);
+  p.off_pool = carve(cur, p.sg.pooled() * 64 * es);
+  p.off_idx = carve(cur, p.sg.pooled() * 64);
   // post-activation outputs
   size_t prev = p.off_pool;
   for (Block& b : p.blocks) {
@@ -273,6 +271,27 @@ int build_plan(Plan& p) {
   return MMSKIN_OK;
 }
 
+template <typename T>
+StemBufs<T> stem_bufs(const Plan& p, unsigned char* ws) {
+  const Unit& u0 = p.units[0];
+  StemBufs<T> b;
+  b.img4 = reinterpret_cast<T*>(ws + p.off_img4);
+  b.wv = reinterpret_cast<const T*>(ws + p.off_wf) + u0.wf_off;
+  b.x0 = reinterpret_cast<T*>(ws + u0.x_off);
+  b.pool = reinterpret_cast<T*>(ws + p.off_pool);
+  b.idx = ws + p.off_idx;
+  b.coef = reinterpret_cast<float*>(ws + u0.coef_off);
+  b.ssum = reinterpret_cast<float*>(ws + p.off_stat);
+  b.ssq = reinterpret_cast<float*>(ws + p.off_stat + p.stat_bytes);
+  b.red = reinterpret_cast<double*>(ws + p.off_red);
+  b.coefbwd = reinterpret_cast<float*>(ws + p.off_coefbwd);
+  b.partial = reinterpret_cast<float*>(ws + p.off_partial);
+  b.dx0 = reinterpret_cast<T*>(ws + p.off_scratch[3]);
+  b.slab = reinterpret_cast<float*>(ws + p.off_slab);
+  b.dwv = reinterpret_cast<float*>(ws + p.off_dwv);
+  return b;
+}
+
 // Inference: eval-mode BatchNorm is folded into the convolutions -- the staged weights carry gamma/sqrt(var+eps)
 // (stage_weights above), the conv epilogue adds the shift, the residual and the ReLU, so no BatchNorm pass and
 // no raw conv output exists (loadImageModelClassifier.py backbones under model.eval(): model_metrics.py:50-62).
@@ -284,18 +303,9 @@ int forward_eval(Plan& p, const void* image, const float* norm6, const float* pa
   int rc, maxC = 64;
   for (const Unit& u : p.units) maxC = u.s.Cout > maxC ? u.s.Cout : maxC;
   if (!reuse_table) PROF(K_BN_FWD, 0.0, 0.0, bn_eval_table(p.table_dev, (int)p.units.size(), maxC, params, buffers, ws, eps, st));
-  auto shift_of = [&](const Unit& u) { return reinterpret_cast<const float*>(ws + u.coef_off) + u.s.Cout; };
-  // stem: the 7x7 conv keeps its own BN + ReLU + max-pool kernel (one pass over the largest activation)
-  Unit& u0 = p.units[0];
-  T* img4 = reinterpret_cast<T*>(ws + p.off_img4);
-  if (norm6) PROF(K_STEM_MISC, 0.0, 0.0, stem_pack_u8<T>((const uint8_t*)image, p.N, p.H, p.W, p.Hp, p.Wp, norm6, img4, st));
-  else PROF(K_STEM_MISC, 0.0, 0.0, stem_pack<T>((const float*)image, p.N, p.H, p.W, p.Hp, p.Wp, img4, st));
-  T* x0 = reinterpret_cast<T*>(ws + u0.x_off);
-  PROF(K_CONV_FWD, conv_flops(u0.s), conv_bytes(u0.s, sizeof(T)),
-       launch_stem_conv_fwd<T>(p.N, p.OH0, p.OW0, p.Hp, p.Wp, img4, wf + u0.wf_off, x0, nullptr, nullptr, st));
-  const float* c0 = reinterpret_cast<const float*>(ws + u0.coef_off);
-  T* pool = reinterpret_cast<T*>(ws + p.off_pool);
-  PROF(K_STEM_MISC, 0.0, 0.0, stem_bn_relu_pool<T>(x0, c0, c0 + 64, p.N, p.OH0, p.OW0, 64, pool, ws + p.off_idx, st));
+  auto shift_of = [&](const Unit& u) { return BnCoef(reinterpret_cast<float*>(ws + u.coef_off), u.s.Cout).shift; };
+  // stem: the 7x7 conv keeps its own BN + ReLU + max-pool kernel; its coefficients are in the table above
+  if ((rc = stem_forward<T>(stem_bufs<T>(p, ws), p.sg, image, norm6, StemBn(), &p.prof, st))) return rc;
   for (Block& b : p.blocks) {
     const T* in = reinterpret_cast<const T*>(ws + b.in_off);
     const T* cur = in;
@@ -337,7 +347,7 @@ int forward_impl(Plan& p, const void* image, const float* norm6, const float* pa
   // stage weights (stem region needs zeros in its padding taps)
   if (!reuse) HIP_CHECK_RET(hipMemsetAsync(wf + p.units[0].wf_off, 0, 64 * 256 * sizeof(T), st));
   const bool use_side = !p.prof.on;
-  if (use_side && (rc = p.side.init())) return rc;
+  if (use_side && (rc = p.side.init(SIDE_SLOTS))) return rc;
   const bool stage_aside = use_side && training;   // the stem only needs its own weights: the other layers are staged beside it
   const float* fold = (training || p.keep_raw_eval) ? nullptr : buffers;
   if (stage_aside) {
@@ -353,15 +363,13 @@ int forward_impl(Plan& p, const void* image, const float* norm6, const float* pa
   if (folded_eval) return forward_eval<T>(p, image, norm6, params, buffers, ws, features, st, reuse);
 
   auto bn_coeffs_on = [&](Unit& u, int stat_rows, float* ssum, float* ssq, double* red, hipStream_t s2) -> int {
-    float* coef = reinterpret_cast<float*>(ws + u.coef_off);
     const int C = u.s.Cout;
-    p.prof.begin(K_BN_FWD, s2);
-    struct End { Profiler& pr; hipStream_t s; ~End() { pr.end(s); } } end_guard{p.prof, s2};
+    const BnCoef k(reinterpret_cast<float*>(ws + u.coef_off), C);
+    ProfScope scope(&p.prof, K_BN_FWD, s2, 0.0, 0.0);
     if (training)
       return bn_finalize(ssum, ssq, stat_rows, C, (double)u.rows(), params + u.g_off, params + u.b_off, eps,
-                         mom, buffers + u.rm_off, buffers + u.rv_off, coef, coef + C, coef + 2 * C, coef + 3 * C, red, s2);
-    return bn_eval_coeffs(C, params + u.g_off, params + u.b_off, buffers + u.rm_off, buffers + u.rv_off, eps, coef,
-                          coef + C, s2);
+                         mom, buffers + u.rm_off, buffers + u.rv_off, k.scale, k.shift, k.mean, k.invstd, red, s2);
+    return bn_eval_coeffs(C, params + u.g_off, params + u.b_off, buffers + u.rm_off, buffers + u.rv_off, eps, k.scale, k.shift, s2);
   };
   auto bn_coeffs = [&](Unit& u, int stat_rows) -> int {
     return bn_coeffs_on(u, stat_rows, stat_sum, stat_sq, reinterpret_cast<double*>(ws + p.off_red), st);
@@ -371,18 +379,10 @@ int forward_impl(Plan& p, const void* image, const float* norm6, const float* pa
 
   // ---- stem
   Unit& u0 = p.units[0];
-  T* img4 = reinterpret_cast<T*>(ws + p.off_img4);
-  if (norm6) PROF(K_STEM_MISC, 0.0, 0.0, stem_pack_u8<T>((const uint8_t*)image, p.N, p.H, p.W, p.Hp, p.Wp, norm6, img4, st));
-  else PROF(K_STEM_MISC, 0.0, 0.0, stem_pack<T>((const float*)image, p.N, p.H, p.W, p.Hp, p.Wp, img4, st));
-  T* x0 = reinterpret_cast<T*>(ws + u0.x_off);
-  int stem_rows = 0;
-  PROF(K_CONV_FWD, conv_flops(u0.s), conv_bytes(u0.s, sizeof(T)),
-       launch_stem_conv_fwd<T>(p.N, p.OH0, p.OW0, p.Hp, p.Wp, img4, wf + u0.wf_off, x0,
-                               training ? stat_sum : nullptr, training ? stat_sq : nullptr, st, &stem_rows));
-  if ((rc = bn_coeffs(u0, stem_rows))) return rc;
-  float* c0 = reinterpret_cast<float*>(ws + u0.coef_off);
-  T* pool = reinterpret_cast<T*>(ws + p.off_pool);
-  PROF(K_STEM_MISC, 0.0, 0.0, stem_bn_relu_pool<T>(x0, c0, c0 + 64, p.N, p.OH0, p.OW0, 64, pool, ws + p.off_idx, st));
+  StemBn bn0;
+  bn0.gamma = params + u0.g_off; bn0.beta = params + u0.b_off; bn0.rm = buffers + u0.rm_off; bn0.rv = buffers + u0.rv_off;
+  bn0.eps = eps; bn0.mom = mom; bn0.batch_stats = training;
+  if ((rc = stem_forward<T>(stem_bufs<T>(p, ws), p.sg, image, norm6, bn0, &p.prof, st))) return rc;
 
   // ---- residual stages
   if (stage_aside) HIP_CHECK_RET(hipStreamWaitEvent(st, p.side.f_staged, 0));
@@ -424,10 +424,9 @@ int forward_impl(Plan& p, const void* image, const float* norm6, const float* pa
           float* gcs = gm + (size_t)128 * u.s.Cin;
           PROF(K_BN_FWD, 0.0, (double)u.rows() * u.s.Cin * sizeof(T),
                launch_wgrad_gram(u.s.N, u.s.OH(), u.s.OW(), u.s.Cin, u.s.Cout, nullptr, cur, reinterpret_cast<float*>(ws + p.off_abn_slab2), gm, gcs, st, 2));
-          float* cf = reinterpret_cast<float*>(ws + u.coef_off);
-          const int Cq = u.s.Cout;
-          PROF(K_BN_FWD, 0.0, 0.0, gram_stats_finalize(gm, gcs, params + u.w_off, Cq, u.s.Cin, (double)u.rows(), params + u.g_off, params + u.b_off, eps, mom,
-                                                       buffers + u.rm_off, buffers + u.rv_off, cf, cf + Cq, cf + 2 * Cq, cf + 3 * Cq, st));
+          const BnCoef kq(reinterpret_cast<float*>(ws + u.coef_off), u.s.Cout);
+          PROF(K_BN_FWD, 0.0, 0.0, gram_stats_finalize(gm, gcs, params + u.w_off, u.s.Cout, u.s.Cin, (double)u.rows(), params + u.g_off, params + u.b_off, eps, mom,
+                                                       buffers + u.rm_off, buffers + u.rv_off, kq.scale, kq.shift, kq.mean, kq.invstd, st));
           nrows_u = -1;   // coefficients done
         }
       } else {
@@ -436,27 +435,27 @@ int forward_impl(Plan& p, const void* image, const float* norm6, const float* pa
                                 training ? stat_sq : nullptr, st, nullptr, &nrows_u));
       }
       if (nrows_u >= 0 && (rc = bn_coeffs(u, nrows_u))) return rc;
-      float* coef = reinterpret_cast<float*>(ws + u.coef_off);
       const int C = u.s.Cout;
+      const BnCoef k(reinterpret_cast<float*>(ws + u.coef_off), C);
       if (two_pass) {
         // second pass: the conv again with scale * acc + shift + identity + ReLU (+ the mask byte) in its epilogue -- the raw output
         // (the block's widest tensor) is neither written nor read: 2T + 2t bytes instead of 4T + t, and the normalisation multiplies the
         // fp32 accumulator, not a bf16-rounded copy of it
-        FwdFuse f2; f2.mul = coef; f2.bias = coef + C; f2.addend = in; f2.relu = true; f2.mask_out = ws + b.mask_off;
+        FwdFuse f2; f2.mul = k.scale; f2.bias = k.shift; f2.addend = in; f2.relu = true; f2.mask_out = ws + b.mask_off;
         // (class accounting: the recomputed MACs are overhead, not algorithmic work -- the layer's FLOPs were counted with the first pass)
         PROF(K_CONV_FWD, gram_pass ? conv_flops(u.s) : 0.0, conv_bytes(u.s, sizeof(T), 0) + (double)u.rows() * C * sizeof(T), launch_conv_fwd<T>(u.s, cur, wf + u.wf_off, y, nullptr, nullptr, st, &f2));
       } else if (i + 1 < nu) {
-        PROF(K_BN_FWD, 0.0, 2.0 * u.rows() * C * sizeof(T), bn_apply<T>(x, nullptr, coef, coef + C, nullptr, nullptr, y, u.rows(), C, true, st));
+        PROF(K_BN_FWD, 0.0, 2.0 * u.rows() * C * sizeof(T), bn_apply<T>(x, nullptr, k.scale, k.shift, nullptr, nullptr, y, u.rows(), C, true, st));
       } else if (b.ds >= 0) {
         Unit& d = p.units[b.ds];
-        float* dc = reinterpret_cast<float*>(ws + d.coef_off);
+        const BnCoef kd(reinterpret_cast<float*>(ws + d.coef_off), C);
         if (use_side) HIP_CHECK_RET(hipStreamWaitEvent(st, p.side.f_done, 0));
         PROF(K_BN_FWD, 0.0, 3.0 * u.rows() * C * sizeof(T),
-             bn_apply<T>(x, reinterpret_cast<const T*>(ws + d.x_off), coef, coef + C, dc, dc + C, y, u.rows(), C, true, st,
+             bn_apply<T>(x, reinterpret_cast<const T*>(ws + d.x_off), k.scale, k.shift, kd.scale, kd.shift, y, u.rows(), C, true, st,
                          training ? ws + b.mask_off : nullptr));
       } else {
         PROF(K_BN_FWD, 0.0, 3.0 * u.rows() * C * sizeof(T),
-             bn_apply<T>(x, in, coef, coef + C, nullptr, nullptr, y, u.rows(), C, true, st, training ? ws + b.mask_off : nullptr));
+             bn_apply<T>(x, in, k.scale, k.shift, nullptr, nullptr, y, u.rows(), C, true, st, training ? ws + b.mask_off : nullptr));
       }
       cur = y;
     }
@@ -477,21 +476,13 @@ int backward_impl(Plan& p, const float* dfeat, const float* params, unsigned cha
   for (int i = 0; i < 7; ++i) S[i] = reinterpret_cast<T*>(ws + p.off_scratch[i]);
   int rc;
 
+  double* red = reinterpret_cast<double*>(ws + p.off_red);
+  const auto coef_of = [&](const Unit& u) { return BnCoef(reinterpret_cast<float*>(ws + u.coef_off), u.s.Cout); };
   // BN backward of unit u given dy: fills dx (and optionally dz)
-  auto bn_backward = [&](Unit& u, const T* dy, const T* ymask, int mode, T* dx, T* dz) -> int {
-    const int C = u.s.Cout;
-    float* coef = reinterpret_cast<float*>(ws + u.coef_off);
-    const T* x = reinterpret_cast<const T*>(ws + u.x_off);
-    float* cB = cA + C; float* cC = cA + 2 * C;
-    int r, nr = 0;
-    p.prof.begin(K_BN_BWD, st);
-    struct End { Profiler& pr; hipStream_t s; ~End() { pr.end(s); } } end_guard{p.prof, st};
-    if (p.prof.on) p.prof.bytes[K_BN_BWD] += (mode == MASK_FROM_Y ? 7.0 : 5.0) * u.rows() * C * sizeof(T);
-    if ((r = bn_bwd_reduce<T>(dy, x, ymask, coef, coef + C, mode, u.rows(), C, partial, &nr, st))) return r;
-    if ((r = bn_bwd_finalize(partial, nr, C, (double)u.rows(), params + u.g_off,
-                             coef + 2 * C, coef + 3 * C, grads + u.g_off, grads + u.b_off, cA, cB, cC,
-                             reinterpret_cast<double*>(ws + p.off_red), st))) return r;
-    return bn_bwd_apply<T>(dy, x, ymask, coef, coef + C, mode, cA, cB, cC, dx, dz, u.rows(), C, st);
+  auto bn_bwd = [&](Unit& u, const T* dy, const T* ymask, int mode, T* dx, T* dz) -> int {
+    return bn_backward<T>(dy, reinterpret_cast<const T*>(ws + u.x_off), ymask, mode, u.rows(), u.s.Cout, coef_of(u), params + u.g_off,
+                          grads + u.g_off, grads + u.b_off, BnBwdCoef(cA, u.s.Cout), partial, red, dx, dz, &p.prof,
+                          (mode == MASK_FROM_Y ? 7.0 : 5.0) * u.rows() * u.s.Cout * sizeof(T), st);
   };
 
   float* partial_b = reinterpret_cast<float*>(ws + p.off_partial_b);
@@ -499,20 +490,10 @@ int backward_impl(Plan& p, const float* dfeat, const float* params, unsigned cha
   // produced by the epilogue of the dgrad launch that wrote dz: finalize + one apply pass.
   // dx == nullptr: finalize only (gamma / beta gradients and the coefficients cA, cB, cC) -- the algebraic path folds the apply
   // into its two GEMMs
-  auto bn_backward_fused = [&](Unit& u, const T* dz, const float* part, int nrows, T* dx, const float* sum_dz_x = nullptr) -> int {
-    const int C = u.s.Cout;
-    float* coef = reinterpret_cast<float*>(ws + u.coef_off);
-    const T* x = reinterpret_cast<const T*>(ws + u.x_off);
-    float* cB = cA + C; float* cC = cA + 2 * C;
-    double* red = reinterpret_cast<double*>(ws + p.off_red);
-    int r;
-    p.prof.begin(K_BN_BWD, st);
-    struct End { Profiler& pr; hipStream_t s; ~End() { pr.end(s); } } end_guard{p.prof, st};
-    if (p.prof.on && dx) p.prof.bytes[K_BN_BWD] += 3.0 * u.rows() * C * sizeof(T);
-    if ((r = bn_bwd_finalize(part, nrows, C, (double)u.rows(), params + u.g_off, coef + 2 * C, coef + 3 * C,
-                             grads + u.g_off, grads + u.b_off, cA, cB, cC, red, st, -1, false, sum_dz_x))) return r;
-    if (!dx) return MMSKIN_OK;
-    return bn_bwd_apply<T>(dz, x, nullptr, coef, coef + C, MASK_NONE, cA, cB, cC, dx, nullptr, u.rows(), C, st);
+  auto bn_bwd_fused = [&](Unit& u, const T* dz, const float* part, int nrows, T* dx, const float* sum_dz_x = nullptr) -> int {
+    return bn_backward_from_sums<T>(dz, reinterpret_cast<const T*>(ws + u.x_off), part, nrows, u.rows(), u.s.Cout, coef_of(u), params + u.g_off,
+                                    grads + u.g_off, grads + u.b_off, BnBwdCoef(cA, u.s.Cout), red, dx, &p.prof,
+                                    dx ? 3.0 * u.rows() * u.s.Cout * sizeof(T) : 0.0, st, -1, false, sum_dz_x);
   };
 
   Unit& last = p.units[p.blocks.back().units.back()];
@@ -520,68 +501,33 @@ int backward_impl(Plan& p, const float* dfeat, const float* params, unsigned cha
   T* gin = S[1];
   if ((rc = avgpool_bwd<T>(dfeat, p.N, last.s.OH() * last.s.OW(), last.s.Cout, g, st))) return rc;
 
-  // ---- side stream for the weight-gradient GEMMs (buffers: 0/1 = alternating dX, 2 = downsample dX)
+  // ---- side stream for the weight-gradient GEMMs
   const bool use_side = !p.prof.on;
-  if (use_side && (rc = p.side.init())) return rc;
-  for (int i = 0; i < 3; ++i) p.side.done_valid[i] = false;
+  if (use_side && (rc = p.side.init(SIDE_SLOTS))) return rc;
+  p.side.begin_backward();
   T* DX[3] = {S[2], S[6], S[5]};
-  // main stream may overwrite buffer i only after the wgrad that reads it has finished
-  auto acquire = [&](int i) -> int {
-    if (use_side && p.side.done_valid[i]) HIP_CHECK_RET(hipStreamWaitEvent(st, p.side.done[i], 0));
-    return MMSKIN_OK;
-  };
+  auto acquire = [&](int i) { return p.side.acquire(i, st, use_side); };
   auto wgrad_async = [&](Unit& u, int i, const T* uin) -> int {
-    hipStream_t ws_st = st;
-    if (use_side) {
-      HIP_CHECK_RET(hipEventRecord(p.side.ready[i], st));
-      HIP_CHECK_RET(hipStreamWaitEvent(p.side.s, p.side.ready[i], 0));
-      ws_st = p.side.s;
-    }
-    p.prof.begin(K_WGRAD, st);
-    int r = launch_conv_wgrad<T>(u.s, DX[i], uin, slab, grads + u.w_off, ws_st);
-    p.prof.end(st);
-    if (p.prof.on) { p.prof.flops[K_WGRAD] += conv_flops(u.s); p.prof.bytes[K_WGRAD] += conv_bytes(u.s, sizeof(T)); }
-    if (r) return r;
-    if (use_side) {
-      HIP_CHECK_RET(hipEventRecord(p.side.done[i], p.side.s));
-      p.side.done_valid[i] = true;
-    }
-    return MMSKIN_OK;
+    return p.side.run(i, st, use_side, [&](hipStream_t wst) {
+      ProfScope scope(&p.prof, K_WGRAD, wst, conv_flops(u.s), conv_bytes(u.s, sizeof(T)));
+      return launch_conv_wgrad<T>(u.s, DX[i], uin, slab, grads + u.w_off, wst);
+    });
   };
   int dxi = 0;   // index of the buffer holding the current dX
-  for (int i = 0; i < 2; ++i) p.side.g_done_valid[i] = false;
-  // algebraic path: the weight-gradient stream reads the block-output gradient buffer (S[0] / S[1]) itself; the main stream may write
-  // that buffer again (two blocks later) only after that launch has finished
-  auto g_index = [&](const T* buf) { return buf == S[0] ? 0 : 1; };
-  auto g_acquire = [&](const T* buf) -> int {
-    const int i = g_index(buf);
-    if (use_side && p.side.g_done_valid[i]) HIP_CHECK_RET(hipStreamWaitEvent(st, p.side.g_done[i], 0));
-    return MMSKIN_OK;
-  };
+  // algebraic path: the main stream may write S[0] / S[1] again (two blocks later) only after the launch reading it has finished
+  auto g_slot = [&](const T* buf) { return buf == S[0] ? 3 : 4; };
+  auto g_acquire = [&](const T* buf) { return acquire(g_slot(buf)); };
   // dW = cA (.) (g^T y) + cB (.) (W (y^T y)) + cC (x) colsum(y) on the weight-gradient stream
   auto wgrad_abn_async = [&](Unit& u, const T* gbuf, const T* uin) -> int {
     if constexpr (sizeof(T) == 2) {
-      hipStream_t ws_st = st;
-      if (use_side) {
-        HIP_CHECK_RET(hipEventRecord(p.side.g_ready, st));
-        HIP_CHECK_RET(hipStreamWaitEvent(p.side.s, p.side.g_ready, 0));
-        ws_st = p.side.s;
-      }
-      float* S_out = reinterpret_cast<float*>(ws + p.off_abn_S);
-      float* cs_out = reinterpret_cast<float*>(ws + p.off_abn_cs);
-      p.prof.begin(K_WGRAD, st);
-      int r = launch_wgrad_gram(u.s.N, u.s.OH(), u.s.OW(), u.s.Cin, u.s.Cout, gbuf, uin, slab, S_out, cs_out, ws_st);
-      if (!r) r = abn_wgrad_finalize(S_out, cs_out, params + u.w_off, reinterpret_cast<const float*>(ws + u.abn_coef_off), u.s.Cout, u.s.Cin,
-                                     grads + u.w_off, ws_st);
-      p.prof.end(st);
-      if (p.prof.on) { p.prof.flops[K_WGRAD] += conv_flops(u.s); p.prof.bytes[K_WGRAD] += conv_bytes(u.s, sizeof(T)); }
-      if (r) return r;
-      if (use_side) {
-        const int gi = g_index(gbuf);
-        HIP_CHECK_RET(hipEventRecord(p.side.g_done[gi], p.side.s));
-        p.side.g_done_valid[gi] = true;
-      }
-      return MMSKIN_OK;
+      return p.side.run(g_slot(gbuf), st, use_side, [&](hipStream_t wst) {
+        float* S_out = reinterpret_cast<float*>(ws + p.off_abn_S);
+        float* cs_out = reinterpret_cast<float*>(ws + p.off_abn_cs);
+        ProfScope scope(&p.prof, K_WGRAD, wst, conv_flops(u.s), conv_bytes(u.s, sizeof(T)));
+        if (int r = launch_wgrad_gram(u.s.N, u.s.OH(), u.s.OW(), u.s.Cin, u.s.Cout, gbuf, uin, slab, S_out, cs_out, wst)) return r;
+        return abn_wgrad_finalize(S_out, cs_out, params + u.w_off, reinterpret_cast<const float*>(ws + u.abn_coef_off), u.s.Cout, u.s.Cin,
+                                  grads + u.w_off, wst);
+      });
     } else {
       return MMSKIN_ERR_UNSUPPORTED;
     }
@@ -622,10 +568,11 @@ int backward_impl(Plan& p, const float* dfeat, const float* params, unsigned cha
           sgx = reinterpret_cast<const float*>(ws + p.off_abn_sgx);
         }
       }
-      if ((rc = bn_backward_fused(ul, g, partial, fused_rows, abn ? nullptr : dX, sgx))) return rc;
+      if ((rc = bn_bwd_fused(ul, g, partial, fused_rows, abn ? nullptr : dX, sgx))) return rc;
       if (abn) {   // fold the coefficients into this block's conv3 data-gradient weights; keep a copy for the weight-gradient fix-up
         if constexpr (sizeof(T) == 2) {
-          if ((rc = abn_prep(params + ul.w_off, cA, cA + ul.s.Cout, cA + 2 * ul.s.Cout, ul.s.Cout, ul.s.Cin, reinterpret_cast<bf16_t*>(ws + p.off_abn_wd),
+          const BnBwdCoef c(cA, ul.s.Cout);
+          if ((rc = abn_prep(params + ul.w_off, c.cA, c.cB, c.cC, ul.s.Cout, ul.s.Cin, reinterpret_cast<bf16_t*>(ws + p.off_abn_wd),
                              reinterpret_cast<float*>(ws + p.off_abn_bias), reinterpret_cast<float*>(ws + ul.abn_coef_off), st))) return rc;
           const float* gkept = ul.gram_off ? reinterpret_cast<const float*>(ws + ul.gram_off) : nullptr;   // y^T y | colsum(y) from the forward pass
           if (ul.fwd2p && (rc = abn_wgrad_finalize(reinterpret_cast<const float*>(ws + p.off_abn_S2),
@@ -636,19 +583,20 @@ int backward_impl(Plan& p, const float* dfeat, const float* params, unsigned cha
       if (has_ds) {
         Unit& d = p.units[b.ds];
         const bool abn_d = d.abn && sizeof(T) == 2;
-        if ((rc = bn_backward_fused(d, g, partial_b, fused_rows, abn_d ? nullptr : dXd))) return rc;
+        if ((rc = bn_bwd_fused(d, g, partial_b, fused_rows, abn_d ? nullptr : dXd))) return rc;
         if (abn_d) {
           if constexpr (sizeof(T) == 2) {
-            if ((rc = abn_prep(params + d.w_off, cA, cA + d.s.Cout, cA + 2 * d.s.Cout, d.s.Cout, d.s.Cin, reinterpret_cast<bf16_t*>(ws + p.off_abn_wd2),
+            const BnBwdCoef c(cA, d.s.Cout);
+            if ((rc = abn_prep(params + d.w_off, c.cA, c.cB, c.cC, d.s.Cout, d.s.Cin, reinterpret_cast<bf16_t*>(ws + p.off_abn_wd2),
                                reinterpret_cast<float*>(ws + p.off_abn_bias2), reinterpret_cast<float*>(ws + d.abn_coef_off), st))) return rc;
           }
         }
       }
       dz_final = g;
     } else {
-      if ((rc = bn_backward(ul, g, out, MASK_FROM_Y, dX, has_ds ? nullptr : dZ))) return rc;
+      if ((rc = bn_bwd(ul, g, out, MASK_FROM_Y, dX, has_ds ? nullptr : dZ))) return rc;
       if (has_ds)
-        if ((rc = bn_backward(p.units[b.ds], g, out, MASK_FROM_Y, dXd, nullptr))) return rc;
+        if ((rc = bn_bwd(p.units[b.ds], g, out, MASK_FROM_Y, dXd, nullptr))) return rc;
       dz_final = dZ;
     }
     for (int i = nu - 1; i >= 0; --i) {
@@ -661,9 +609,8 @@ int backward_impl(Plan& p, const float* dfeat, const float* params, unsigned cha
         // dgrad writes the gradient of unit i-1's ReLU output; its epilogue applies that ReLU's mask and
         // accumulates unit i-1's BN-backward sums, so the stand-alone reduce pass is gone.
         Unit& up = p.units[b.units[i - 1]];
-        float* cup = reinterpret_cast<float*>(ws + up.coef_off);
         DgradFuse f;
-        f.x = ws + up.x_off; f.scale = cup; f.shift = cup + up.s.Cout; f.partial = partial;
+        f.x = ws + up.x_off; f.scale = coef_of(up).scale; f.shift = coef_of(up).shift; f.partial = partial;
         if (abn_u) {   // dY = [g | y] [cA (.) W ; Q] + r: no dz in memory
           f.in2 = uin; f.k2 = u.s.Cin; f.bias = reinterpret_cast<const float*>(ws + p.off_abn_bias);
           PROF(K_CONV_DGRAD, conv_flops(u.s), conv_bytes(u.s, sizeof(T), 1), launch_conv_dgrad<T>(u.s, g, reinterpret_cast<const T*>(ws + p.off_abn_wd), dY, (const T*)nullptr, st, &f));
@@ -672,7 +619,7 @@ int backward_impl(Plan& p, const float* dfeat, const float* params, unsigned cha
         dxi ^= 1;                              // the next dX goes to the other buffer: wgrad(u) may still read this one
         if ((rc = acquire(dxi))) return rc;
         dX = DX[dxi];
-        if ((rc = bn_backward_fused(up, dY, partial, f.rows_written, dX))) return rc;
+        if ((rc = bn_bwd_fused(up, dY, partial, f.rows_written, dX))) return rc;
       } else {
         const T* addend = dz_final;
         bool ds_addend_compact = false;
@@ -725,39 +672,11 @@ int backward_impl(Plan& p, const float* dfeat, const float* params, unsigned cha
   // weight-gradient GEMMs are still reading (dX ring, forward activations) or writing (slab), so it runs on the main
   // stream BESIDE the tail of layer1's wgrads; the stem's own wgrad needs the slab and queues behind them on the side stream.
   Unit& u0 = p.units[0];
-  T* dx0 = S[3];
-  {   // max-pool + ReLU + BatchNorm backward without materialising the full-resolution pooled gradient
-    float* c0 = reinterpret_cast<float*>(ws + u0.coef_off);
-    const T* x0 = reinterpret_cast<const T*>(ws + u0.x_off);
-    float* cB = cA + 64; float* cC = cA + 128;
-    int nr = 0;
-    p.prof.begin(K_BN_BWD, st);
-    if (stem_sums_pooled()) rc = stem_pool_bwd_sums<T>(g, reinterpret_cast<const T*>(ws + p.off_pool), ws + p.off_idx, x0, c0, c0 + 64, p.N, p.OH0, p.OW0, 64, partial, &nr, st);
-    else rc = stem_pool_bn_bwd_reduce<T>(g, ws + p.off_idx, x0, c0, c0 + 64, p.N, p.OH0, p.OW0, 64, partial, &nr, st);
-    if (!rc) rc = bn_bwd_finalize(partial, nr, 64, (double)u0.rows(), params + u0.g_off, c0 + 128, c0 + 192, grads + u0.g_off,
-                                  grads + u0.b_off, cA, cB, cC, reinterpret_cast<double*>(ws + p.off_red), st);
-    if (!rc) rc = stem_pool_bn_bwd_apply<T>(g, ws + p.off_idx, x0, c0, c0 + 64, cA, cB, cC, p.N, p.OH0, p.OW0, 64, dx0, st);
-    p.prof.end(st);
-    if (p.prof.on) p.prof.bytes[K_BN_BWD] += 3.5 * u0.rows() * 64 * sizeof(T);
-    if (rc) return rc;
-  }
-  float* dwv = reinterpret_cast<float*>(ws + p.off_dwv);
-  hipStream_t wst = st;
-  if (use_side) {
-    HIP_CHECK_RET(hipEventRecord(p.side.ready[0], st));
-    HIP_CHECK_RET(hipStreamWaitEvent(p.side.s, p.side.ready[0], 0));
-    wst = p.side.s;
-  }
-  p.prof.begin(K_WGRAD, st);
-  rc = launch_stem_conv_wgrad<T>(p.N, p.OH0, p.OW0, p.Hp, p.Wp, dx0, reinterpret_cast<const T*>(ws + p.off_img4), slab, dwv, wst);
-  p.prof.end(st);
-  if (p.prof.on) p.prof.flops[K_WGRAD] += conv_flops(u0.s);
-  if (rc) return rc;
-  if ((rc = stem_wgrad_unpack(dwv, grads + u0.w_off, wst))) return rc;
-  if (use_side) {   // final join: everything the side stream was given has finished before backward's last event
-    HIP_CHECK_RET(hipEventRecord(p.side.done[0], p.side.s));
-    HIP_CHECK_RET(hipStreamWaitEvent(st, p.side.done[0], 0));
-  }
+  const StemBufs<T> sb = stem_bufs<T>(p, ws);   // dx0 = S[3]
+  if ((rc = stem_backward<T>(sb, p.sg, g, params + u0.g_off, grads + u0.g_off, grads + u0.b_off, stem_sums_pooled(), &p.prof,
+                             3.5 * u0.rows() * 64 * sizeof(T), st))) return rc;
+  if ((rc = p.side.run(0, st, use_side, [&](hipStream_t wst) { return stem_wgrad<T>(sb, p.sg, grads + u0.w_off, &p.prof, wst); }))) return rc;
+  if ((rc = acquire(0))) return rc;   // final join: everything the side stream was given has finished before backward's last event
   return p.segment_done((int)p.segments.size() - 1, st, false);
 }
 

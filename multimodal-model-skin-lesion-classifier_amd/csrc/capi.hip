@@ -134,7 +134,7 @@ double conv_time(int op, const ConvShape& s, int iters, void* ws, hipStream_t st
 
 template <typename T>
 struct BnWs {
-  T *xh, *yh, *dxh; float *ssum, *ssq, *partial, *coef; size_t total;   // yh: y (forward) or dy (backward)
+  T *xh, *yh, *dxh; float *ssum, *ssq, *partial, *coef, *coefbwd; size_t total;   // yh: y (forward) or dy (backward)
   BnWs(void* ws, int N, int C, int H, int W) {
     Carver c(ws);
     const size_t rows = (size_t)N * H * W;
@@ -142,7 +142,8 @@ struct BnWs {
     ssum = c.take<float>((size_t)column_stats_rows(rows, C) * C);
     ssq = c.take<float>((size_t)column_stats_rows(rows, C) * C);
     partial = c.take<float>((size_t)bn_bwd_partial_rows(rows, C) * 2 * C);
-    coef = c.take<float>(5 * (size_t)C);   // forward: scale, shift; backward: + cA, cB, cC
+    coef = c.take<float>(5 * (size_t)C);   // scale | shift, and behind them (backward) cA | cB | cC
+    coefbwd = BnCoef(coef, C).mean;           // ... which start where a five-slot block keeps mean
     total = c.cur;
   }
 };
@@ -155,10 +156,20 @@ int bn_fwd_op(const float* x, const float* gamma, const float* beta, float* rm, 
   int rc, nr = 0;
   if ((rc = nchw_to_nhwc<T>(x, N, C, H, W, s.xh, st))) return rc;
   if ((rc = column_stats<T>(s.xh, rows, C, s.ssum, s.ssq, &nr, st))) return rc;
-  if ((rc = bn_finalize(s.ssum, s.ssq, nr, C, (double)rows, gamma, beta, eps, mom, rm, rv, s.coef, s.coef + C, save_mean,
+  const BnCoef k(s.coef, C);
+  if ((rc = bn_finalize(s.ssum, s.ssq, nr, C, (double)rows, gamma, beta, eps, mom, rm, rv, k.scale, k.shift, save_mean,
                         save_invstd, nullptr, st))) return rc;
-  if ((rc = bn_apply<T>(s.xh, nullptr, s.coef, s.coef + C, nullptr, nullptr, s.yh, rows, C, relu != 0, st))) return rc;
+  if ((rc = bn_apply<T>(s.xh, nullptr, k.scale, k.shift, nullptr, nullptr, s.yh, rows, C, relu != 0, st))) return rc;
   return nhwc_to_nchw<T>(s.yh, N, C, H, W, y, st);
+}
+
+// k.scale | k.shift rebuilt in the op's workspace from the statistics the caller saved, which k.mean / k.invstd then point at
+inline int coef_from_saved(BnCoef& k, int C, const float* gamma, const float* beta, const float* save_mean, const float* save_invstd,
+                           hipStream_t st) {
+  hipLaunchKernelGGL(coef_from_saved_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, st, C, gamma, beta, save_mean, save_invstd, k.scale, k.shift);
+  HIP_CHECK_RET(hipGetLastError());
+  k.mean = const_cast<float*>(save_mean); k.invstd = const_cast<float*>(save_invstd);   // read only from here on
+  return MMSKIN_OK;
 }
 
 template <typename T>
@@ -167,108 +178,74 @@ int bn_bwd_op(const float* dy, const float* x, const float* gamma, const float* 
               void* ws, hipStream_t st) {
   BnWs<T> s(ws, N, C, H, W);
   const size_t rows = (size_t)N * H * W;
-  float* coef = s.coef;
+  BnCoef k(s.coef, C);
   int rc;
   if ((rc = nchw_to_nhwc<T>(x, N, C, H, W, s.xh, st))) return rc;
   if ((rc = nchw_to_nhwc<T>(dy, N, C, H, W, s.yh, st))) return rc;
-  hipLaunchKernelGGL(coef_from_saved_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, st, C, gamma, beta, save_mean,
-                     save_invstd, coef, coef + C);
-  HIP_CHECK_RET(hipGetLastError());
-  const int mode = relu ? MASK_FROM_X : MASK_NONE;
-  int nr = 0;
-  if ((rc = bn_bwd_reduce<T>(s.yh, s.xh, nullptr, coef, coef + C, mode, rows, C, s.partial, &nr, st))) return rc;
-  if ((rc = bn_bwd_finalize(s.partial, nr, C, (double)rows, gamma, save_mean, save_invstd,
-                            dgamma, dbeta, coef + 2 * C, coef + 3 * C, coef + 4 * C, nullptr, st))) return rc;
-  if ((rc = bn_bwd_apply<T>(s.yh, s.xh, nullptr, coef, coef + C, mode, coef + 2 * C, coef + 3 * C, coef + 4 * C, s.dxh,
-                            (T*)nullptr, rows, C, st))) return rc;
+  if ((rc = coef_from_saved(k, C, gamma, beta, save_mean, save_invstd, st))) return rc;
+  if ((rc = bn_backward<T>(s.yh, s.xh, nullptr, relu ? MASK_FROM_X : MASK_NONE, rows, C, k, gamma, dgamma, dbeta, BnBwdCoef(s.coefbwd, C),
+                           s.partial, nullptr, s.dxh, nullptr, nullptr, 0.0, st))) return rc;
   return nhwc_to_nchw<T>(s.dxh, N, C, H, W, dx, st);
 }
 
-struct StemGeom {
-  int OH, OW, Hp, Wp, PH, PW;
-  StemGeom(int H, int W) {
-    OH = (H + 6 - 7) / 2 + 1; OW = (W + 6 - 7) / 2 + 1;
-    Hp = 2 * OH + 8; Wp = 2 * OW + 8;
-    if (Hp < H + 6) Hp = H + 6;
-    if (Wp < W + 6) Wp = W + 6;
-    Wp = (Wp + 1) / 2 * 2;
-    PH = (OH + 2 - 3) / 2 + 1; PW = (OW + 2 - 3) / 2 + 1;
-  }
-};
-
 template <typename T>
 struct StemWs {
-  StageDesc* table; T* img4; T* wv; T* x0; T* pool; uint8_t* idx; float* ssum; float* ssq; float* coef;
-  T* dpool; T* dyfull; T* dx0; float* partial; float* slab; float* dwv; double* red;
-  StemWs(void* ws, int N, int H, int W) {
-    StemGeom g(H, W);
+  StageDesc* table; T* wv; T* dpool; StemBufs<T> b; size_t total;
+  StemWs(void* ws, const StemGeom& g) {
     Carver c(ws);
-    const size_t rows = (size_t)N * g.OH * g.OW;
     table = c.take<StageDesc>(1);
-    img4 = c.take<T>((size_t)N * g.Hp * g.Wp * 4);
-    wv = c.take<T>(64 * 256);
-    x0 = c.take<T>(rows * 64);
-    pool = c.take<T>((size_t)N * g.PH * g.PW * 64);
-    idx = c.take<uint8_t>((size_t)N * g.PH * g.PW * 64);
-    ssum = c.take<float>((size_t)stem_conv_stat_rows(N, g.OH, g.OW) * 64);
-    ssq = c.take<float>((size_t)stem_conv_stat_rows(N, g.OH, g.OW) * 64);
-    coef = c.take<float>(7 * 64);
-    dpool = c.take<T>((size_t)N * g.PH * g.PW * 64);
-    dyfull = c.take<T>(rows * 64);
-    dx0 = c.take<T>(rows * 64);
-    partial = c.take<float>((size_t)bn_bwd_partial_rows(rows, 64) * 2 * 64);
-    slab = c.take<float>(stem_wgrad_slab_bytes(N, g.OH, g.OW) / sizeof(float));
-    dwv = c.take<float>(64 * 256);
-    red = c.take<double>(2 * 64 * 64);
+    b.img4 = c.take<T>((size_t)g.N * g.Hp * g.Wp * 4);
+    b.wv = wv = c.take<T>(64 * 256);
+    b.x0 = c.take<T>(g.rows() * 64);
+    b.pool = c.take<T>(g.pooled() * 64);
+    b.idx = c.take<uint8_t>(g.pooled() * 64);
+    b.ssum = c.take<float>((size_t)stem_conv_stat_rows(g.N, g.OH, g.OW) * 64);
+    b.ssq = c.take<float>((size_t)stem_conv_stat_rows(g.N, g.OH, g.OW) * 64);
+    b.coef = c.take<float>(7 * 64);   // scale | shift | mean | invstd, and behind them cA | cB | cC
+    b.coefbwd = BnCoef(b.coef, 64).gamma;
+    dpool = c.take<T>(g.pooled() * 64);
+    c.take<T>(g.rows() * 64);   // (a second full-resolution gradient nothing writes: keeps mmskin_stem_workspace_bytes what it was)
+    b.dx0 = c.take<T>(g.rows() * 64);
+    b.partial = c.take<float>((size_t)bn_bwd_partial_rows(g.rows(), 64) * 2 * 64);
+    b.slab = c.take<float>(stem_wgrad_slab_bytes(g.N, g.OH, g.OW) / sizeof(float));
+    b.dwv = c.take<float>(64 * 256);
+    b.red = c.take<double>(2 * 64 * 64);
     total = c.cur;
   }
-  size_t total;
 };
 
+// pack, stage the weights, then the plans' training forward (batch statistics, no running buffers)
 template <typename T>
-int stem_fwd_core(StemWs<T>& s, const float* x, const float* w, const float* gamma, const float* beta, int N, int H,
-                  int W, float eps, hipStream_t st) {
-  StemGeom g(H, W);
+int stem_fwd_core(StemWs<T>& s, const StemGeom& g, const float* x, const float* w, const float* gamma, const float* beta, float eps,
+                  hipStream_t st) {
   int rc;
-  if ((rc = stem_pack<T>(x, N, H, W, g.Hp, g.Wp, s.img4, st))) return rc;
+  if ((rc = stem_pack<T>(x, g.N, g.H, g.W, g.Hp, g.Wp, s.b.img4, st))) return rc;
   if ((rc = stage_one<T>(w, 64, 3, 49, true, s.wv, (T*)nullptr, s.table, st))) return rc;
-  int stem_rows = 0;
-  if ((rc = launch_stem_conv_fwd<T>(N, g.OH, g.OW, g.Hp, g.Wp, s.img4, s.wv, s.x0, s.ssum, s.ssq, st, &stem_rows))) return rc;
-  if ((rc = bn_finalize(s.ssum, s.ssq, stem_rows, 64, (double)N * g.OH * g.OW, gamma, beta, eps,
-                        0.1f, nullptr, nullptr, s.coef, s.coef + 64, s.coef + 128, s.coef + 192, s.red, st))) return rc;
-  return stem_bn_relu_pool<T>(s.x0, s.coef, s.coef + 64, N, g.OH, g.OW, 64, s.pool, s.idx, st);
+  StemBn bn;
+  bn.gamma = gamma; bn.beta = beta; bn.eps = eps; bn.batch_stats = true;
+  return stem_forward<T>(s.b, g, nullptr, nullptr, bn, nullptr, st);
 }
 
 template <typename T>
 int stem_fwd_op(const float* x, const float* w, const float* gamma, const float* beta, float* y, int N, int H,
                        int W, float eps, void* ws, hipStream_t st) {
-  StemWs<T> s(ws, N, H, W);
-  StemGeom g(H, W);
+  const StemGeom g(N, H, W);
+  StemWs<T> s(ws, g);
   int rc;
-  if ((rc = stem_fwd_core<T>(s, x, w, gamma, beta, N, H, W, eps, st))) return rc;
-  return nhwc_to_nchw<T>(s.pool, N, 64, g.PH, g.PW, y, st);
+  if ((rc = stem_fwd_core<T>(s, g, x, w, gamma, beta, eps, st))) return rc;
+  return nhwc_to_nchw<T>(s.b.pool, N, 64, g.PH, g.PW, y, st);
 }
 
 template <typename T>
 int stem_bwd_op(const float* dy, const float* x, const float* w, const float* gamma, const float* beta,
                        float* dw, float* dgamma, float* dbeta, int N, int H, int W, float eps, void* ws, hipStream_t st) {
-  StemWs<T> s(ws, N, H, W);
-  StemGeom g(H, W);
-  const size_t rows = (size_t)N * g.OH * g.OW;
+  const StemGeom g(N, H, W);
+  StemWs<T> s(ws, g);
   int rc;
-  if ((rc = stem_fwd_core<T>(s, x, w, gamma, beta, N, H, W, eps, st))) return rc;
+  if ((rc = stem_fwd_core<T>(s, g, x, w, gamma, beta, eps, st))) return rc;
   if ((rc = nchw_to_nhwc<T>(dy, N, 64, g.PH, g.PW, s.dpool, st))) return rc;
-  // the plans' fused path: max-pool + ReLU + BatchNorm backward on pooled cells, no full-resolution pooled gradient
-  int nr = 0;
-  if (stem_sums_pooled()) rc = stem_pool_bwd_sums<T>(s.dpool, s.pool, s.idx, s.x0, s.coef, s.coef + 64, N, g.OH, g.OW, 64, s.partial, &nr, st);
-  else rc = stem_pool_bn_bwd_reduce<T>(s.dpool, s.idx, s.x0, s.coef, s.coef + 64, N, g.OH, g.OW, 64, s.partial, &nr, st);
-  if (rc) return rc;
-  if ((rc = bn_bwd_finalize(s.partial, nr, 64, (double)rows, gamma, s.coef + 128, s.coef + 192,
-                            dgamma, dbeta, s.coef + 256, s.coef + 320, s.coef + 384, s.red, st))) return rc;
-  if ((rc = stem_pool_bn_bwd_apply<T>(s.dpool, s.idx, s.x0, s.coef, s.coef + 64, s.coef + 256, s.coef + 320, s.coef + 384, N, g.OH,
-                                      g.OW, 64, s.dx0, st))) return rc;
-  if ((rc = launch_stem_conv_wgrad<T>(N, g.OH, g.OW, g.Hp, g.Wp, s.dx0, s.img4, s.slab, s.dwv, st))) return rc;
-  return stem_wgrad_unpack(s.dwv, dw, st);
+  if ((rc = stem_backward<T>(s.b, g, s.dpool, gamma, dgamma, dbeta, stem_sums_pooled(), nullptr, 0.0, st))) return rc;
+  return stem_wgrad<T>(s.b, g, dw, nullptr, st);
 }
 
 // ---- MBConv family (mbconv.hip's launches, op by op): depthwise k x k, BatchNorm + ReLU6 / SiLU, squeeze-excitation, stochastic depth
@@ -318,7 +295,7 @@ int dw_bwd_op(const float* dy, const float* x, const float* w, float* dx, float*
 
 template <typename T>
 struct BnActWs {
-  T *xh, *yh, *rh, *dyh, *dxh, *dzh; float *ssum, *ssq, *tab, *coef, *partial; size_t total;
+  T *xh, *yh, *rh, *dyh, *dxh, *dzh; float *ssum, *ssq, *tab, *coef, *coefbwd, *partial; size_t total;
   BnActWs(void* ws, int N, int C, int H, int W) {
     Carver c(ws);
     const size_t rows = (size_t)N * H * W;
@@ -327,7 +304,8 @@ struct BnActWs {
     ssum = c.take<float>((size_t)column_stats_rows(rows, C) * C);
     ssq = c.take<float>((size_t)column_stats_rows(rows, C) * C);
     tab = c.take<float>(2 * (size_t)C);
-    coef = c.take<float>(5 * (size_t)C);
+    coef = c.take<float>(5 * (size_t)C);   // forward: all five slots; backward: scale | shift | cA | cB | cC
+    coefbwd = BnCoef(coef, C).mean;
     partial = c.take<float>((size_t)bn_bwd_partial_rows(rows, C) * 2 * C);
     total = c.cur;
   }
@@ -347,10 +325,11 @@ int bn_act_fwd_op(const float* x, const float* res, const float* gamma, const fl
   // the plan's sequence behind a depthwise conv: column sums -> statistics table -> coefficient vectors -> apply
   if ((rc = column_stats<T>(s.xh, rows, C, s.ssum, s.ssq, &nr, st))) return rc;
   if ((rc = bn_table_finalize(s.ssum, s.ssq, nr, C, C, (double)rows, s.tab, s.tab + C, nullptr, st))) return rc;
+  const BnCoef k(s.coef, C);
   if ((rc = bn_coef_from_table(s.tab, s.tab + C, C, C, gamma, beta, eps, mom, (double)rows, rm, rv, true, s.coef, st))) return rc;
-  HIP_CHECK_RET(hipMemcpyAsync(save_mean, s.coef + 2 * C, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
-  HIP_CHECK_RET(hipMemcpyAsync(save_invstd, s.coef + 3 * C, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
-  if ((rc = bn_apply<T>(s.xh, res ? s.rh : nullptr, s.coef, s.coef + C, nullptr, nullptr, s.yh, rows, C, act != 0, st, nullptr, act_cap(act)))) return rc;
+  HIP_CHECK_RET(hipMemcpyAsync(save_mean, k.mean, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
+  HIP_CHECK_RET(hipMemcpyAsync(save_invstd, k.invstd, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
+  if ((rc = bn_apply<T>(s.xh, res ? s.rh : nullptr, k.scale, k.shift, nullptr, nullptr, s.yh, rows, C, act != 0, st, nullptr, act_cap(act)))) return rc;
   return nhwc_to_nchw<T>(s.yh, N, C, H, W, y, st);
 }
 
@@ -360,18 +339,14 @@ int bn_act_bwd_op(const float* dy, const float* x, const float* y, const float* 
                   void* ws, hipStream_t st) {
   const size_t rows = (size_t)N * H * W;
   BnActWs<T> s(ws, N, C, H, W);
-  int rc, nr = 0;
+  BnCoef k(s.coef, C);
+  int rc;
   if ((rc = nchw_to_nhwc<T>(x, N, C, H, W, s.xh, st))) return rc;
   if ((rc = nchw_to_nhwc<T>(y, N, C, H, W, s.yh, st))) return rc;   // the forward's stored y: exact in T, MASK_FROM_Y6 reads it
   if ((rc = nchw_to_nhwc<T>(dy, N, C, H, W, s.dyh, st))) return rc;
-  hipLaunchKernelGGL(coef_from_saved_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, st, C, gamma, beta, save_mean, save_invstd, s.coef,
-                     s.coef + C);
-  HIP_CHECK_RET(hipGetLastError());
-  const int mode = act_mask(act);
-  float *cA = s.coef + 2 * C, *cB = s.coef + 3 * C, *cC = s.coef + 4 * C;
-  if ((rc = bn_bwd_reduce<T>(s.dyh, s.xh, s.yh, s.coef, s.coef + C, mode, rows, C, s.partial, &nr, st))) return rc;
-  if ((rc = bn_bwd_finalize(s.partial, nr, C, (double)rows, gamma, save_mean, save_invstd, dgamma, dbeta, cA, cB, cC, nullptr, st))) return rc;
-  if ((rc = bn_bwd_apply<T>(s.dyh, s.xh, s.yh, s.coef, s.coef + C, mode, cA, cB, cC, s.dxh, dres ? s.dzh : (T*)nullptr, rows, C, st))) return rc;
+  if ((rc = coef_from_saved(k, C, gamma, beta, save_mean, save_invstd, st))) return rc;
+  if ((rc = bn_backward<T>(s.dyh, s.xh, s.yh, act_mask(act), rows, C, k, gamma, dgamma, dbeta, BnBwdCoef(s.coefbwd, C), s.partial, nullptr,
+                           s.dxh, dres ? s.dzh : (T*)nullptr, nullptr, 0.0, st))) return rc;
   if (dres && (rc = nhwc_to_nchw<T>(s.dzh, N, C, H, W, dres, st))) return rc;   // the residual's gradient is the masked dy
   return nhwc_to_nchw<T>(s.dxh, N, C, H, W, dx, st);
 }
@@ -643,7 +618,7 @@ int mmskin_batchnorm_backward(const float* dy, const float* x, const float* gamm
 }
 
 int64_t mmskin_stem_workspace_bytes(int N, int H, int W) {
-  return ws_bytes<StemWs<float>>(N, H, W);
+  return ws_bytes<StemWs<float>>(StemGeom(N, H, W));
 }
 
 int mmskin_stem_forward(const float* x, const float* w, const float* gamma, const float* beta, float* y, int N, int H,

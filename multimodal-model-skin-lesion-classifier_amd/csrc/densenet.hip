@@ -45,7 +45,7 @@ constexpr int GROWTH = 32, BOTTLE = 128, G_PAD = 64;
 
 struct DensePlan : PlanBase {
   bool fmap = false;   // "densenet169-features": output = norm5 feature map [N][C][H/32][W/32] fp32 (MDNet), no ReLU / pool
-  int Hp, Wp, OH0, OW0, PH, PW;
+  StemGeom sg;
   // stem
   int64_t w0_off; BNRef n0; int64_t wf0;
   size_t x0_off, coef0_off, off_pool, off_idx, off_img4;
@@ -55,24 +55,9 @@ struct DensePlan : PlanBase {
   size_t off_wf, off_wd, off_stat, off_partial, off_coefbwd, off_defer, off_dwv, off_red, off_slab;
   size_t off_sB, off_sB2, off_sU, off_sA, off_sA2, off_sX, off_sZ, off_sC;
   size_t stat_bytes = 0;
-  // weight-gradient GEMMs on the side stream: slots 0/1 = conv2 operand (sB) of even/odd layers, 2/3 = conv1
+  // weight-gradient GEMMs on the side stream (SideStream slots): 0/1 = conv2 operand (sB) of even/odd layers, 2/3 = conv1
   // operand (sA) of even/odd layers, 4 = transition operand (sC)
-  hipEvent_t ev_ready[5] = {}, ev_done[5] = {};
-  bool ev_valid[5] = {};
-  ~DensePlan() override {
-    for (int i = 0; i < 5; ++i) {
-      if (ev_ready[i]) (void)hipEventDestroy(ev_ready[i]);
-      if (ev_done[i]) (void)hipEventDestroy(ev_done[i]);
-    }
-  }
-  int init_events() {
-    if (ev_ready[0]) return MMSKIN_OK;
-    for (int i = 0; i < 5; ++i) {
-      HIP_CHECK_RET(hipEventCreateWithFlags(&ev_ready[i], hipEventDisableTiming));
-      HIP_CHECK_RET(hipEventCreateWithFlags(&ev_done[i], hipEventDisableTiming));
-    }
-    return MMSKIN_OK;
-  }
+  static constexpr int SIDE_SLOTS = 5;
 
   int forward(const void* image, const float* norm6, const float* params, float* buffers, unsigned char* ws,
               float* features, bool training, hipStream_t st) override;
@@ -85,14 +70,8 @@ int build_dense_plan(DensePlan& p) {
   const std::string pre = p.fmap ? "" : "features.";
   p.w0_off = add_tensor(p.params, p.param_numel, pre + "conv0.weight", {64, 3, 7, 7});
   p.n0 = add_bn(p, pre + "norm0", 64);
-  ConvShape s0 = {p.N, p.H, p.W, 3, 64, 7, 7, 2, 3};
-  p.OH0 = s0.OH(); p.OW0 = s0.OW();
-  p.Hp = 2 * p.OH0 + 8; p.Wp = 2 * p.OW0 + 8;
-  if (p.Hp < p.H + 6) p.Hp = p.H + 6;
-  if (p.Wp < p.W + 6) p.Wp = p.W + 6;
-  p.Wp = (p.Wp + 1) / 2 * 2;
-  p.PH = (p.OH0 + 2 - 3) / 2 + 1; p.PW = (p.OW0 + 2 - 3) / 2 + 1;
-  int c = 64, h = p.PH, w = p.PW;
+  p.sg = StemGeom(p.N, p.H, p.W);
+  int c = 64, h = p.sg.PH, w = p.sg.PW;
   for (int bi = 0; bi < 4; ++bi) {
     ARG_CHECK(h >= 1 && w >= 1, "densenet169: input %dx%d too small", p.H, p.W);
     DBlock b;
@@ -154,18 +133,18 @@ int build_dense_plan(DensePlan& p) {
   // ---- workspace
   const size_t es = p.esz();
   size_t cur = 0;
-  p.off_img4 = carve(cur, (size_t)p.N * p.Hp * p.Wp * 4 * es);
+  p.off_img4 = carve(cur, (size_t)p.N * p.sg.Hp * p.sg.Wp * 4 * es);
   p.off_wf = carve(cur, (size_t)wf * es);
   p.off_wd = carve(cur, (size_t)wd * es);
-  const size_t rows0 = (size_t)p.N * p.OH0 * p.OW0;
+  const size_t rows0 = p.sg.rows();
   p.x0_off = carve(cur, rows0 * 64 * es);
   p.coef0_off = carve(cur, 4 * 64 * sizeof(float));
-  p.off_pool = carve(cur, (size_t)p.N * p.PH * p.PW * 64 * es);
-  p.off_idx = carve(cur, (size_t)p.N * p.PH * p.PW * 64);
+  p.off_pool = carve(cur, p.sg.pooled() * 64 * es);
+  p.off_idx = carve(cur, p.sg.pooled() * 64);
 
-  size_t stat_floats = (size_t)stem_conv_stat_rows(p.N, p.OH0, p.OW0) * 64;
+  size_t stat_floats = (size_t)stem_conv_stat_rows(p.N, p.sg.OH, p.sg.OW) * 64;
   size_t partial_bytes = (size_t)bn_bwd_partial_rows(rows0, 64) * 2 * 64 * sizeof(float);
-  size_t slab = stem_wgrad_slab_bytes(p.N, p.OH0, p.OW0);
+  size_t slab = stem_wgrad_slab_bytes(p.N, p.sg.OH, p.sg.OW);
   size_t small_elems = 0, big_elems = rows0 * 64;
   int maxC = BOTTLE;
   auto need_stat = [&](size_t floats) { if (floats > stat_floats) stat_floats = floats; };
@@ -240,6 +219,26 @@ int build_dense_plan(DensePlan& p) {
 }
 
 template <typename T>
+StemBufs<T> stem_bufs(const DensePlan& p, unsigned char* ws) {
+  StemBufs<T> b;
+  b.img4 = reinterpret_cast<T*>(ws + p.off_img4);
+  b.wv = reinterpret_cast<const T*>(ws + p.off_wf) + p.wf0;
+  b.x0 = reinterpret_cast<T*>(ws + p.x0_off);
+  b.pool = reinterpret_cast<T*>(ws + p.off_pool);
+  b.idx = ws + p.off_idx;
+  b.coef = reinterpret_cast<float*>(ws + p.coef0_off);
+  b.ssum = reinterpret_cast<float*>(ws + p.off_stat);
+  b.ssq = reinterpret_cast<float*>(ws + p.off_stat + p.stat_bytes);
+  b.red = reinterpret_cast<double*>(ws + p.off_red);
+  b.coefbwd = reinterpret_cast<float*>(ws + p.off_coefbwd);
+  b.partial = reinterpret_cast<float*>(ws + p.off_partial);
+  b.dx0 = reinterpret_cast<T*>(ws + p.off_sX);
+  b.slab = reinterpret_cast<float*>(ws + p.off_slab);
+  b.dwv = reinterpret_cast<float*>(ws + p.off_dwv);
+  return b;
+}
+
+template <typename T>
 int dense_forward(DensePlan& p, const void* image, const float* norm6, const float* params, float* buffers,
                   unsigned char* ws, float* features, bool training, hipStream_t st) {
   const float eps = 1e-5f, mom = 0.1f;
@@ -259,33 +258,17 @@ int dense_forward(DensePlan& p, const void* image, const float* norm6, const flo
   auto table_from_slice = [&](DBlock& b, int c0, int C) -> int {
     float* tab = reinterpret_cast<float*>(ws + b.tab_off);
     int nr = 0, r;
-    p.prof.begin(K_BN_FWD, st);
-    struct End { Profiler& pr; hipStream_t s; ~End() { pr.end(s); } } end_guard{p.prof, st};
-    if (p.prof.on) p.prof.bytes[K_BN_FWD] += (double)b.rows * C * sizeof(T);
+    ProfScope scope(&p.prof, K_BN_FWD, st, 0.0, (double)b.rows * C * sizeof(T));
     if ((r = slice_stats<T>(reinterpret_cast<const T*>(ws + b.cat_off) + c0, b.Ctot, C, b.rows, stat_sum, stat_sum + C, &nr, st))) return r;
     return bn_table_finalize(stat_sum, stat_sum + C, nr, 2 * C, C, (double)b.rows, tab + c0, tab + b.Ctot + c0, red, st);
   };
 
   // ---- stem: conv0 (7x7 s2) -> norm0 -> relu -> maxpool 3x3 s2
-  T* img4 = reinterpret_cast<T*>(ws + p.off_img4);
-  if (norm6) PROF(K_STEM_MISC, 0.0, 0.0, stem_pack_u8<T>((const uint8_t*)image, p.N, p.H, p.W, p.Hp, p.Wp, norm6, img4, st));
-  else PROF(K_STEM_MISC, 0.0, 0.0, stem_pack<T>((const float*)image, p.N, p.H, p.W, p.Hp, p.Wp, img4, st));
-  T* x0 = reinterpret_cast<T*>(ws + p.x0_off);
-  ConvShape s0 = {p.N, p.H, p.W, 3, 64, 7, 7, 2, 3};
-  int stem_rows = 0;
-  PROF(K_CONV_FWD, conv_flops(s0), conv_bytes(s0, sizeof(T)),
-       launch_stem_conv_fwd<T>(p.N, p.OH0, p.OW0, p.Hp, p.Wp, img4, wf + p.wf0, x0, training ? stat_sum : nullptr,
-                               training ? stat_sq : nullptr, st, &stem_rows));
-  float* c0 = reinterpret_cast<float*>(ws + p.coef0_off);
-  if (training) {
-    PROF(K_BN_FWD, 0.0, 0.0, bn_finalize(stat_sum, stat_sq, stem_rows, 64, (double)p.N * p.OH0 * p.OW0,
-                     params + p.n0.g_off, params + p.n0.b_off, eps, mom, buffers + p.n0.rm_off, buffers + p.n0.rv_off,
-                     c0, c0 + 64, c0 + 128, c0 + 192, red, st));
-  } else {
-    PROF(K_BN_FWD, 0.0, 0.0, bn_eval_coeffs(64, params + p.n0.g_off, params + p.n0.b_off, buffers + p.n0.rm_off, buffers + p.n0.rv_off, eps, c0, c0 + 64, st));
-  }
-  T* pool = reinterpret_cast<T*>(ws + p.off_pool);
-  PROF(K_STEM_MISC, 0.0, 0.0, stem_bn_relu_pool<T>(x0, c0, c0 + 64, p.N, p.OH0, p.OW0, 64, pool, ws + p.off_idx, st));
+  StemBn bn0;
+  bn0.gamma = params + p.n0.g_off; bn0.beta = params + p.n0.b_off; bn0.rm = buffers + p.n0.rm_off; bn0.rv = buffers + p.n0.rv_off;
+  bn0.eps = eps; bn0.mom = mom; bn0.batch_stats = training;
+  if ((rc = stem_forward<T>(stem_bufs<T>(p, ws), p.sg, image, norm6, bn0, &p.prof, st))) return rc;
+  const T* pool = reinterpret_cast<const T*>(ws + p.off_pool);
   {
     DBlock& b = p.blocks[0];
     PROF(K_STEM_MISC, 0.0, 0.0, slice_scatter<T>(pool, 64, 64, reinterpret_cast<T*>(ws + b.cat_off), b.Ctot, b.rows, st));
@@ -300,20 +283,19 @@ int dense_forward(DensePlan& p, const void* image, const float* norm6, const flo
     float* tab = reinterpret_cast<float*>(ws + b.tab_off);
     const double count = (double)b.rows;
     for (DLayer& l : b.layers) {
-      float* k1 = reinterpret_cast<float*>(ws + l.coef1_off);
-      float* k2 = reinterpret_cast<float*>(ws + l.coef2_off);
+      const BnCoef k1(reinterpret_cast<float*>(ws + l.coef1_off), l.Cp), k2(reinterpret_cast<float*>(ws + l.coef2_off), BOTTLE);
       T* t = reinterpret_cast<T*>(ws + l.t_off);
       T* a = reinterpret_cast<T*>(ws + l.a_off);
       T* u = reinterpret_cast<T*>(ws + l.u_off);
       // norm1 + relu over the channel prefix -> compact padded operand
       PROF(K_BN_FWD, 0.0, 0.0, bn_coef_from_table(tab, tab + b.Ctot, l.Cin, l.Cp, params + l.n1.g_off, params + l.n1.b_off, eps, mom,
-                         count, buffers + l.n1.rm_off, buffers + l.n1.rv_off, training, k1, st));
+                         count, buffers + l.n1.rm_off, buffers + l.n1.rv_off, training, k1.scale, st));
       PROF(K_BN_FWD, 0.0, (double)b.rows * (l.Cin + l.Cp) * sizeof(T),
-           slice_pack<T>(cat, b.Ctot, l.Cin, l.Cp, b.rows, k1, k1 + l.Cp, t, st));
+           slice_pack<T>(cat, b.Ctot, l.Cin, l.Cp, b.rows, k1.scale, k1.shift, t, st));
       // conv1 1x1 -> norm2 -> relu
       ConvShape c1 = {p.N, b.H, b.W, l.Cp, BOTTLE, 1, 1, 1, 0};
       if (!training) {   // norm2 folded: u = relu(conv1'(t) + shift2) straight from the conv epilogue
-        FwdFuse f; f.bias = k2 + BOTTLE; f.relu = true;
+        FwdFuse f; f.bias = k2.shift; f.relu = true;
         PROF(K_CONV_FWD, conv_flops(c1), conv_bytes(c1, sizeof(T)), launch_conv_fwd<T>(c1, t, wf + l.wf1, u, nullptr, nullptr, st, &f));
       } else {
       PROF(K_CONV_FWD, conv_flops(c1), conv_bytes(c1, sizeof(T)),
@@ -321,9 +303,9 @@ int dense_forward(DensePlan& p, const void* image, const float* norm6, const flo
       }
       if (training) {
         PROF(K_BN_FWD, 0.0, 0.0, bn_finalize(stat_sum, stat_sq, conv_fwd_stat_rows(c1), BOTTLE, count, params + l.n2.g_off, params + l.n2.b_off, eps, mom,
-                         buffers + l.n2.rm_off, buffers + l.n2.rv_off, k2, k2 + BOTTLE, k2 + 2 * BOTTLE, k2 + 3 * BOTTLE, red, st));
+                         buffers + l.n2.rm_off, buffers + l.n2.rv_off, k2.scale, k2.shift, k2.mean, k2.invstd, red, st));
         PROF(K_BN_FWD, 0.0, 2.0 * b.rows * BOTTLE * sizeof(T),
-             bn_apply<T>(a, nullptr, k2, k2 + BOTTLE, nullptr, nullptr, u, b.rows, BOTTLE, true, st));
+             bn_apply<T>(a, nullptr, k2.scale, k2.shift, nullptr, nullptr, u, b.rows, BOTTLE, true, st));
       }
       // conv2 3x3 (32 outputs padded to 64) -> new cat channels + their batch statistics
       ConvShape c2 = {p.N, b.H, b.W, BOTTLE, G_PAD, 3, 3, 1, 1};
@@ -337,11 +319,11 @@ int dense_forward(DensePlan& p, const void* image, const float* norm6, const flo
       // transition: norm -> relu -> conv 1x1 (C -> C/2) -> avgpool 2x2 into the next block's cat prefix
       DTrans& t = p.trans[bi];
       DBlock& nb = p.blocks[bi + 1];
-      float* k = reinterpret_cast<float*>(ws + t.coef_off);
+      const BnCoef k(reinterpret_cast<float*>(ws + t.coef_off), t.C);
       T* tt = reinterpret_cast<T*>(ws + t.tt_off);
       PROF(K_BN_FWD, 0.0, 0.0, bn_coef_from_table(tab, tab + b.Ctot, t.C, t.C, params + t.n.g_off, params + t.n.b_off, eps, mom, count,
-                         buffers + t.n.rm_off, buffers + t.n.rv_off, training, k, st));
-      PROF(K_BN_FWD, 0.0, 2.0 * b.rows * t.C * sizeof(T), bn_apply<T>(cat, nullptr, k, k + t.C, nullptr, nullptr, tt, b.rows, t.C, true, st));
+                         buffers + t.n.rm_off, buffers + t.n.rv_off, training, k.scale, st));
+      PROF(K_BN_FWD, 0.0, 2.0 * b.rows * t.C * sizeof(T), bn_apply<T>(cat, nullptr, k.scale, k.shift, nullptr, nullptr, tt, b.rows, t.C, true, st));
       ConvShape ct = {p.N, b.H, b.W, t.C, t.C / 2, 1, 1, 1, 0};
       PROF(K_CONV_FWD, conv_flops(ct), conv_bytes(ct, sizeof(T)), launch_conv_fwd<T>(ct, tt, wf + t.wf, sC, nullptr, nullptr, st));
       PROF(K_STEM_MISC, 0.0, 0.0, avgpool2_fwd<T>(sC, p.N, b.H, b.W, t.C / 2, reinterpret_cast<T*>(ws + nb.cat_off), nb.Ctot, st));
@@ -350,14 +332,14 @@ int dense_forward(DensePlan& p, const void* image, const float* norm6, const flo
   }
   // ---- norm5 -> relu -> global average pool
   DBlock& lb = p.blocks[3];
-  float* k5 = reinterpret_cast<float*>(ws + p.coef5_off);
+  const int C5 = lb.Ctot;
+  const BnCoef k5(reinterpret_cast<float*>(ws + p.coef5_off), C5);
   float* tab = reinterpret_cast<float*>(ws + lb.tab_off);
   T* y5 = reinterpret_cast<T*>(ws + p.y5_off);
-  const int C5 = lb.Ctot;
   PROF(K_BN_FWD, 0.0, 0.0, bn_coef_from_table(tab, tab + C5, C5, C5, params + p.n5.g_off, params + p.n5.b_off, eps, mom, (double)lb.rows,
-                     buffers + p.n5.rm_off, buffers + p.n5.rv_off, training, k5, st));
+                     buffers + p.n5.rm_off, buffers + p.n5.rv_off, training, k5.scale, st));
   PROF(K_BN_FWD, 0.0, 2.0 * lb.rows * C5 * sizeof(T),
-       bn_apply<T>(reinterpret_cast<const T*>(ws + lb.cat_off), nullptr, k5, k5 + C5, nullptr, nullptr, y5, lb.rows, C5, !p.fmap, st));
+       bn_apply<T>(reinterpret_cast<const T*>(ws + lb.cat_off), nullptr, k5.scale, k5.shift, nullptr, nullptr, y5, lb.rows, C5, !p.fmap, st));
   if (p.fmap) return nhwc_to_nchw<T>(y5, p.N, C5, lb.H, lb.W, features, st);
   return avgpool_fwd<T>(y5, p.N, lb.H * lb.W, C5, features, st);
 }
@@ -382,33 +364,14 @@ int dense_backward(DensePlan& p, const float* dfeat, const float* params, unsign
   // chain (one slab, the side stream is in order).  Operand buffers alternate between consecutive layers; the main
   // stream re-acquires a buffer (waits for the wgrad that read it) before overwriting it.
   const bool use_side = !p.prof.on;
-  if (use_side) {
-    if ((rc = p.side.init())) return rc;
-    if ((rc = p.init_events())) return rc;
-  }
-  for (int i = 0; i < 5; ++i) p.ev_valid[i] = false;
-  auto acquire = [&](int slot) -> int {
-    if (use_side && p.ev_valid[slot]) HIP_CHECK_RET(hipStreamWaitEvent(st, p.ev_done[slot], 0));
-    return MMSKIN_OK;
-  };
-  auto wgrad_async = [&](int slot, const ConvShape& cs, double flops, const T* dout, const T* in, float* dw, int cov,
-                         int civ) -> int {
-    hipStream_t wst = st;
-    if (use_side) {
-      HIP_CHECK_RET(hipEventRecord(p.ev_ready[slot], st));
-      HIP_CHECK_RET(hipStreamWaitEvent(p.side.s, p.ev_ready[slot], 0));
-      wst = p.side.s;
-    }
-    p.prof.begin(K_WGRAD, st);
-    int r = launch_conv_wgrad<T>(cs, dout, in, slab, dw, wst, cov, civ);
-    p.prof.end(st);
-    if (p.prof.on) { p.prof.flops[K_WGRAD] += flops; p.prof.bytes[K_WGRAD] += conv_bytes(cs, sizeof(T)); }
-    if (r) return r;
-    if (use_side) {
-      HIP_CHECK_RET(hipEventRecord(p.ev_done[slot], p.side.s));
-      p.ev_valid[slot] = true;
-    }
-    return MMSKIN_OK;
+  if (use_side && (rc = p.side.init(DensePlan::SIDE_SLOTS))) return rc;
+  p.side.begin_backward();
+  auto acquire = [&](int slot) { return p.side.acquire(slot, st, use_side); };
+  auto wgrad_async = [&](int slot, const ConvShape& cs, double flops, const T* dout, const T* in, float* dw, int cov, int civ) -> int {
+    return p.side.run(slot, st, use_side, [&](hipStream_t wst) {
+      ProfScope scope(&p.prof, K_WGRAD, wst, flops, conv_bytes(cs, sizeof(T)));
+      return launch_conv_wgrad<T>(cs, dout, in, slab, dw, wst, cov, civ);
+    });
   };
   int layer_no = 0;
 
@@ -416,23 +379,15 @@ int dense_backward(DensePlan& p, const float* dfeat, const float* params, unsign
   {
     DBlock& lb = p.blocks[3];
     const int C5 = lb.Ctot;
-    float* k5 = reinterpret_cast<float*>(ws + p.coef5_off);
     const T* x = reinterpret_cast<const T*>(ws + lb.cat_off);
     const T* y5 = reinterpret_cast<const T*>(ws + p.y5_off);
-    float* cB = cA + C5; float* cC = cA + 2 * C5;
-    int nr = 0;
-    const int mode = p.fmap ? MASK_NONE : MASK_FROM_Y;
     if (p.fmap) rc = nchw_to_nhwc<T>(dfeat, p.N, C5, lb.H, lb.W, sZ, st);
     else rc = avgpool_bwd<T>(dfeat, p.N, lb.H * lb.W, C5, sZ, st);
     if (rc) return rc;
-    p.prof.begin(K_BN_BWD, st);
-    rc = bn_bwd_reduce<T>(sZ, x, y5, k5, k5 + C5, mode, lb.rows, C5, partial, &nr, st);
-    if (!rc) rc = bn_bwd_finalize(partial, nr, C5, (double)lb.rows, params + p.n5.g_off, k5 + 2 * C5, k5 + 3 * C5,
-                                  grads + p.n5.g_off, grads + p.n5.b_off, cA, cB, cC, red, st);
-    if (!rc) rc = bn_bwd_apply<T>(sZ, x, y5, k5, k5 + C5, mode, cA, cB, cC, reinterpret_cast<T*>(ws + lb.dcat_off),
-                                  nullptr, lb.rows, C5, st);
-    p.prof.end(st);
-    if (rc) return rc;
+    // (profiler: norm5's bytes are not counted -- an omission, kept)
+    if ((rc = bn_backward<T>(sZ, x, y5, p.fmap ? MASK_NONE : MASK_FROM_Y, lb.rows, C5, BnCoef(reinterpret_cast<float*>(ws + p.coef5_off), C5),
+                             params + p.n5.g_off, grads + p.n5.g_off, grads + p.n5.b_off, BnBwdCoef(cA, C5), partial, red,
+                             reinterpret_cast<T*>(ws + lb.dcat_off), nullptr, &p.prof, 0.0, st))) return rc;
   }
 
   // Every later layer of a block adds cA*g + cB*x + cC to the channel prefix it consumed, and x (the concatenated activation) is the
@@ -449,8 +404,7 @@ int dense_backward(DensePlan& p, const float* dfeat, const float* params, unsign
     HIP_CHECK_RET(hipMemsetAsync(sB_, 0, 2 * (size_t)b.Ctot * sizeof(float), st));
     for (int li = (int)b.layers.size() - 1; li >= 0; --li) {
       DLayer& l = b.layers[li];
-      float* k1 = reinterpret_cast<float*>(ws + l.coef1_off);
-      float* k2 = reinterpret_cast<float*>(ws + l.coef2_off);
+      const BnCoef k1(reinterpret_cast<float*>(ws + l.coef1_off), l.Cp), k2(reinterpret_cast<float*>(ws + l.coef2_off), BOTTLE);
       const T* t = reinterpret_cast<const T*>(ws + l.t_off);
       const T* a = reinterpret_cast<const T*>(ws + l.a_off);
       const T* u = reinterpret_cast<const T*>(ws + l.u_off);
@@ -465,35 +419,26 @@ int dense_backward(DensePlan& p, const float* dfeat, const float* params, unsign
       // conv2: weight gradient (first 32 rows are real) and data gradient with norm2's mask + sums fused
       if ((rc = wgrad_async(q, c2, conv_flops(c2) / 2, sB, u, grads + l.w2_off, GROWTH, 0))) return rc;
       DgradFuse f2;
-      f2.x = a; f2.scale = k2; f2.shift = k2 + BOTTLE; f2.partial = partial;
+      f2.x = a; f2.scale = k2.scale; f2.shift = k2.shift; f2.partial = partial;
       PROF(K_CONV_DGRAD, conv_flops(c2) / 2, conv_bytes(c2, sizeof(T), 1), launch_conv_dgrad<T>(c2, sB, wd + l.wd2, sU, (const T*)nullptr, st, &f2));
-      {
-        float* cB = cA + BOTTLE; float* cC = cA + 2 * BOTTLE;
-        p.prof.begin(K_BN_BWD, st);
-        if ((rc = acquire(2 + q))) return rc;
-        rc = bn_bwd_finalize(partial, f2.rows_written, BOTTLE, count, params + l.n2.g_off, k2 + 2 * BOTTLE, k2 + 3 * BOTTLE,
-                             grads + l.n2.g_off, grads + l.n2.b_off, cA, cB, cC, red, st);
-        if (!rc) rc = bn_bwd_apply<T>(sU, a, nullptr, k2, k2 + BOTTLE, MASK_NONE, cA, cB, cC, sA, nullptr, b.rows, BOTTLE, st);
-        p.prof.end(st);
-        if (p.prof.on) p.prof.bytes[K_BN_BWD] += 3.0 * b.rows * BOTTLE * sizeof(T);
-        if (rc) return rc;
-      }
+      if ((rc = acquire(2 + q))) return rc;
+      if ((rc = bn_backward_from_sums<T>(sU, a, partial, f2.rows_written, b.rows, BOTTLE, k2, params + l.n2.g_off, grads + l.n2.g_off,
+                                         grads + l.n2.b_off, BnBwdCoef(cA, BOTTLE), red, sA, &p.prof, 3.0 * b.rows * BOTTLE * sizeof(T), st)))
+        return rc;
       // conv1: weight gradient, padded input channels dropped by the reduction
       if ((rc = wgrad_async(2 + q, c1, conv_flops(c1), sA, t, grads + l.w1_off, 0, l.Cin))) return rc;
       // conv1 data gradient with norm1's mask + sums fused: the epilogue reads the raw channel prefix straight from
       // cat (row pitch Ctot); padded channels [Cin, Cp) have scale = shift = 0, so their mask is false
       DgradFuse f1;
-      f1.x = cat; f1.x_pitch = b.Ctot; f1.scale = k1; f1.shift = k1 + l.Cp; f1.partial = partial;
+      f1.x = cat; f1.x_pitch = b.Ctot; f1.scale = k1.scale; f1.shift = k1.shift; f1.partial = partial;
       PROF(K_CONV_DGRAD, conv_flops(c1), conv_bytes(c1, sizeof(T), 1), launch_conv_dgrad<T>(c1, sA, wd + l.wd1, sZ, (const T*)nullptr, st, &f1));
       {
-        p.prof.begin(K_BN_BWD, st);
-        // padded channels [Cin, Cp) have gamma = 0: they add zeros to sB / sC
-        rc = bn_bwd_finalize(partial, f1.rows_written, l.Cp, count, k1 + 4 * l.Cp, k1 + 2 * l.Cp, k1 + 3 * l.Cp,
-                             grads + l.n1.g_off, grads + l.n1.b_off, cA, sB_, sC_, red, st, l.Cin, true);
-        if (!rc) rc = slice_accumulate_scaled<T>(dcat, b.Ctot, l.Cin, sZ, l.Cp, cA, b.rows, st);
-        p.prof.end(st);
-        if (p.prof.on) p.prof.bytes[K_BN_BWD] += 3.0 * b.rows * l.Cin * sizeof(T);
-        if (rc) return rc;
+        // norm1: cB / cC are added to the block's running sums (padded channels [Cin, Cp) have gamma = 0: they add zeros), and the
+        // apply pass is the scaled accumulation into dcat -- a finalize of its own, not bn_backward_from_sums
+        ProfScope scope(&p.prof, K_BN_BWD, st, 0.0, 3.0 * b.rows * l.Cin * sizeof(T));
+        if ((rc = bn_bwd_finalize(partial, f1.rows_written, l.Cp, count, k1.gamma, k1.mean, k1.invstd, grads + l.n1.g_off, grads + l.n1.b_off,
+                                  cA, sB_, sC_, red, st, l.Cin, true))) return rc;
+        if ((rc = slice_accumulate_scaled<T>(dcat, b.Ctot, l.Cin, sZ, l.Cp, cA, b.rows, st))) return rc;
       }
     }
     // the block-input channels [0, C0): every layer of the block consumed them
@@ -502,7 +447,7 @@ int dense_backward(DensePlan& p, const float* dfeat, const float* params, unsign
       // transition bi-1: avgpool <- conv 1x1 <- relu <- norm; writes the whole of the previous block's dcat
       DTrans& tr = p.trans[bi - 1];
       DBlock& pb = p.blocks[bi - 1];
-      float* k = reinterpret_cast<float*>(ws + tr.coef_off);
+      const BnCoef k(reinterpret_cast<float*>(ws + tr.coef_off), tr.C);
       const T* tt = reinterpret_cast<const T*>(ws + tr.tt_off);
       const T* pcat = reinterpret_cast<const T*>(ws + pb.cat_off);
       ConvShape ct = {p.N, pb.H, pb.W, tr.C, tr.C / 2, 1, 1, 1, 0};
@@ -510,46 +455,28 @@ int dense_backward(DensePlan& p, const float* dfeat, const float* params, unsign
       PROF(K_STEM_MISC, 0.0, 0.0, avgpool2_bwd<T>(dcat, b.Ctot, p.N, pb.H, pb.W, tr.C / 2, sC, st));
       if ((rc = wgrad_async(4, ct, conv_flops(ct), sC, tt, grads + tr.w_off, 0, 0))) return rc;
       DgradFuse f;
-      f.x = pcat; f.scale = k; f.shift = k + tr.C; f.partial = partial;
+      f.x = pcat; f.scale = k.scale; f.shift = k.shift; f.partial = partial;
       PROF(K_CONV_DGRAD, conv_flops(ct), conv_bytes(ct, sizeof(T), 1), launch_conv_dgrad<T>(ct, sC, wd + tr.wd, sZ, (const T*)nullptr, st, &f));
-      float* cB = cA + tr.C; float* cC = cA + 2 * tr.C;
-      p.prof.begin(K_BN_BWD, st);
-      rc = bn_bwd_finalize(partial, f.rows_written, tr.C, (double)pb.rows, params + tr.n.g_off, k + 2 * tr.C, k + 3 * tr.C,
-                           grads + tr.n.g_off, grads + tr.n.b_off, cA, cB, cC, red, st);
-      if (!rc) rc = bn_bwd_apply<T>(sZ, pcat, nullptr, k, k + tr.C, MASK_NONE, cA, cB, cC, reinterpret_cast<T*>(ws + pb.dcat_off),
-                                    nullptr, pb.rows, tr.C, st);
-      p.prof.end(st);
-      if (p.prof.on) p.prof.bytes[K_BN_BWD] += 3.0 * pb.rows * tr.C * sizeof(T);
-      if (rc) return rc;
+      if ((rc = bn_backward_from_sums<T>(sZ, pcat, partial, f.rows_written, pb.rows, tr.C, k, params + tr.n.g_off, grads + tr.n.g_off,
+                                         grads + tr.n.b_off, BnBwdCoef(cA, tr.C), red, reinterpret_cast<T*>(ws + pb.dcat_off), &p.prof,
+                                         3.0 * pb.rows * tr.C * sizeof(T), st))) return rc;
     }
   }
 
   // join: the stem reuses the slab and scratch buffers the side stream has been working on
-  for (int i = 0; i < 5; ++i)
+  for (int i = 0; i < DensePlan::SIDE_SLOTS; ++i)
     if ((rc = acquire(i))) return rc;
 
   // ---- stem: maxpool <- relu <- norm0 <- conv0
   {
     T* sB = sBq[0];
     DBlock& b = p.blocks[0];
-    const size_t rows0 = (size_t)p.N * p.OH0 * p.OW0;
-    float* c0 = reinterpret_cast<float*>(ws + p.coef0_off);
-    const T* x0 = reinterpret_cast<const T*>(ws + p.x0_off);
-    float* cB = cA + 64; float* cC = cA + 128;
-    int nr = 0;
+    const StemBufs<T> sb = stem_bufs<T>(p, ws);   // dx0 = sX
     PROF(K_STEM_MISC, 0.0, 0.0, slice_pack<T>(reinterpret_cast<const T*>(ws + b.dcat_off), b.Ctot, 64, 64, b.rows, nullptr, nullptr, sB, st));
-    p.prof.begin(K_BN_BWD, st);   // max-pool + ReLU + BatchNorm backward straight from the pooled gradient
-    rc = stem_pool_bn_bwd_reduce<T>(sB, ws + p.off_idx, x0, c0, c0 + 64, p.N, p.OH0, p.OW0, 64, partial, &nr, st);
-    if (!rc) rc = bn_bwd_finalize(partial, nr, 64, (double)rows0, params + p.n0.g_off, c0 + 128, c0 + 192, grads + p.n0.g_off,
-                                  grads + p.n0.b_off, cA, cB, cC, red, st);
-    if (!rc) rc = stem_pool_bn_bwd_apply<T>(sB, ws + p.off_idx, x0, c0, c0 + 64, cA, cB, cC, p.N, p.OH0, p.OW0, 64, sX, st);
-    p.prof.end(st);
-    if (rc) return rc;
-    float* dwv = reinterpret_cast<float*>(ws + p.off_dwv);
-    ConvShape s0 = {p.N, p.H, p.W, 3, 64, 7, 7, 2, 3};
-    PROF(K_WGRAD, conv_flops(s0), 0.0,
-         launch_stem_conv_wgrad<T>(p.N, p.OH0, p.OW0, p.Hp, p.Wp, sX, reinterpret_cast<const T*>(ws + p.off_img4), slab, dwv, st));
-    return stem_wgrad_unpack(dwv, grads + p.w0_off, st);
+    // sums_pooled = false: the routed form whatever stem_sums_pooled() says -- inherited behaviour, not a decision.
+    // (profiler: the stem's BatchNorm-backward bytes are not counted -- an omission, kept)
+    if ((rc = stem_backward<T>(sb, p.sg, sB, params + p.n0.g_off, grads + p.n0.g_off, grads + p.n0.b_off, false, &p.prof, 0.0, st))) return rc;
+    return stem_wgrad<T>(sb, p.sg, grads + p.w0_off, &p.prof, st);
   }
 }
 

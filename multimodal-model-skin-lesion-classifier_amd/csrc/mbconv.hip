@@ -327,8 +327,8 @@ int mb_forward(MBPlan& p, const void* image, const float* norm6, const float* pa
     const T* in = reinterpret_cast<const T*>(ws + u.in_off);
     T* x = reinterpret_cast<T*>(ws + u.x_off);
     T* y = reinterpret_cast<T*>(ws + u.y_off);
-    float* k = reinterpret_cast<float*>(ws + u.coef_off);
     const int Cp = u.Coutp;
+    const BnCoef k(reinterpret_cast<float*>(ws + u.coef_off), Cp);
     int nrows = 0;
     if (u.kind == U_FIRST) {
       ConvShape s = {p.N, p.H, p.W, 3, 64, 3, 3, 2, 1};
@@ -349,15 +349,15 @@ int mb_forward(MBPlan& p, const void* image, const float* norm6, const float* pa
     if (training)
       PROF(K_BN_FWD, 0.0, 0.0, bn_table_finalize(stat_sum, stat_sq, nrows, Cp, Cp, (double)rows, tab, tab + Cp, red, st));
     PROF(K_BN_FWD, 0.0, 0.0, bn_coef_from_table(tab, tab + Cp, u.Cout, Cp, params + u.bn.g_off, params + u.bn.b_off, eps, mom,
-                       (double)rows, buffers + u.bn.rm_off, buffers + u.bn.rv_off, training, k, st));
+                       (double)rows, buffers + u.bn.rm_off, buffers + u.bn.rv_off, training, k.scale, st));
     const T* res = u.res_last ? reinterpret_cast<const T*>(ws + u.res_off) : nullptr;
     if (res && sd) {   // stochastic depth: y = bn(x) * mask[n] + block input
-      PROF(K_BN_FWD, 0.0, 2.0 * rows * Cp * sizeof(T), bn_apply<T>(x, nullptr, k, k + Cp, nullptr, nullptr, y, rows, Cp, false, st));
+      PROF(K_BN_FWD, 0.0, 2.0 * rows * Cp * sizeof(T), bn_apply<T>(x, nullptr, k.scale, k.shift, nullptr, nullptr, y, rows, Cp, false, st));
       PROF(K_BN_FWD, 0.0, 3.0 * rows * Cp * sizeof(T),
            sd_residual_add<T>(y, res, sd + (size_t)u.sd * p.N, p.N, (size_t)u.OH * u.OW * Cp, y, st));
     } else {
       PROF(K_BN_FWD, 0.0, (res ? 3.0 : 2.0) * rows * Cp * sizeof(T),
-           bn_apply<T>(x, res, k, k + Cp, nullptr, nullptr, y, rows, Cp, u.act, st, nullptr, cap));
+           bn_apply<T>(x, res, k.scale, k.shift, nullptr, nullptr, y, rows, Cp, u.act, st, nullptr, cap));
     }
     if (u.se >= 0) {   // squeeze-excitation on the depthwise output
       SEBlock& se = p.ses[u.se];
@@ -393,8 +393,6 @@ int mb_backward(MBPlan& p, const float* dfeat, const float* params, unsigned cha
     const T* x = reinterpret_cast<const T*>(ws + u.x_off);
     const T* y = reinterpret_cast<const T*>(ws + u.y_off);
     const T* in = reinterpret_cast<const T*>(ws + u.in_off);
-    float* k = reinterpret_cast<float*>(ws + u.coef_off);
-    float* cB = cA + Cp; float* cC = cA + 2 * Cp;
     if (u.se >= 0) {
       // ---- squeeze-excitation backward: B[cur] = d(y_se) -> d(y_dw) = dyse * g + ds / HW
       SEBlock& se = p.ses[u.se];
@@ -413,16 +411,9 @@ int mb_backward(MBPlan& p, const float* dfeat, const float* params, unsigned cha
     }
     // ---- BatchNorm (+ activation) backward: dy -> dx
     const int a = take(cur, -1);
-    const int mode = u.act ? act_mask : MASK_NONE;
-    int nr = 0;
-    p.prof.begin(K_BN_BWD, st);
-    rc = bn_bwd_reduce<T>(B[cur], x, y, k, k + Cp, mode, rows, Cp, partial, &nr, st);
-    if (!rc) rc = bn_bwd_finalize(partial, nr, Cp, (double)rows, k + 4 * Cp, k + 2 * Cp, k + 3 * Cp, grads + u.bn.g_off,
-                                  grads + u.bn.b_off, cA, cB, cC, red, st, u.Cout);
-    if (!rc) rc = bn_bwd_apply<T>(B[cur], x, y, k, k + Cp, mode, cA, cB, cC, B[a], nullptr, rows, Cp, st);
-    p.prof.end(st);
-    if (p.prof.on) p.prof.bytes[K_BN_BWD] += 6.0 * rows * Cp * sizeof(T);
-    if (rc) return rc;
+    const BnCoef k(reinterpret_cast<float*>(ws + u.coef_off), Cp);   // gamma: the copy zero-padded to Cp channels
+    if ((rc = bn_backward<T>(B[cur], x, y, u.act ? act_mask : MASK_NONE, rows, Cp, k, k.gamma, grads + u.bn.g_off, grads + u.bn.b_off,
+                             BnBwdCoef(cA, Cp), partial, red, B[a], nullptr, &p.prof, 6.0 * rows * Cp * sizeof(T), st, u.Cout))) return rc;
     const T* dx = B[a];
     // ---- convolution backward
     if (u.kind == U_FIRST) {
@@ -481,15 +472,6 @@ PlanBase* make_plan(int N, int H, int W, int dtype, int* rc, Build build) {
 
 }  // namespace
 
-// Profiled launch for the two functions below, which have a Profiler pointer instead of a plan
-#define SE_PROF(bytes_, call_)                                   \
-  do {                                                          \
-    if (prof) prof->begin(cls, st);                             \
-    rc = (call_);                                               \
-    if (prof) { prof->end(st); if (prof->on) prof->bytes[cls] += (bytes_); } \
-    if (rc) return rc;                                          \
-  } while (0)
-
 template <typename T>
 int se_forward(const SEArgs& a, const T* y, T* yse, Profiler* prof, hipStream_t st) {
   const int cls = K_BN_FWD;
@@ -500,7 +482,7 @@ int se_forward(const SEArgs& a, const T* y, T* yse, Profiler* prof, hipStream_t 
   if ((rc = ew_act_fwd(a.z1, a.a1, (int64_t)a.N * a.Csq, 0, st))) return rc;
   if ((rc = mmskin_linear_forward(a.a1, a.w2p, a.b2p, a.z2, a.N, a.Csq, a.Cp, 0, st))) return rc;
   if ((rc = ew_act_fwd(a.z2, a.g, (int64_t)a.N * a.Cp, 1, st))) return rc;
-  SE_PROF(2.0 * rows * a.Cp * sizeof(T), se_scale_fwd<T>(y, a.g, a.N, a.HW, a.Cp, yse, st));
+  PROF_AT(prof, cls, 0.0, 2.0 * rows * a.Cp * sizeof(T), se_scale_fwd<T>(y, a.g, a.N, a.HW, a.Cp, yse, st));
   return MMSKIN_OK;
 }
 
@@ -528,10 +510,9 @@ int se_backward(const SEArgs& a, const T* dyse, const T* y, float* tmp, float* d
   HIP_CHECK_RET(hipMemcpy2DAsync(dW1, (size_t)a.C * 4, dw1p, (size_t)Cp * 4, (size_t)a.C * 4, Csq, hipMemcpyDeviceToDevice, st));
   HIP_CHECK_RET(hipMemcpyAsync(dW2, dw2p, (size_t)a.C * Csq * 4, hipMemcpyDeviceToDevice, st));
   HIP_CHECK_RET(hipMemcpyAsync(db2, db2p, (size_t)a.C * 4, hipMemcpyDeviceToDevice, st));
-  SE_PROF(2.0 * rows * Cp * sizeof(T), se_dx<T>(dyse, a.g, ds, N, a.HW, Cp, dy, st));
+  PROF_AT(prof, cls, 0.0, 2.0 * rows * Cp * sizeof(T), se_dx<T>(dyse, a.g, ds, N, a.HW, Cp, dy, st));
   return MMSKIN_OK;
 }
-#undef SE_PROF
 template int se_forward<float>(const SEArgs&, const float*, float*, Profiler*, hipStream_t);
 template int se_forward<bf16_t>(const SEArgs&, const bf16_t*, bf16_t*, Profiler*, hipStream_t);
 template int se_backward<float>(const SEArgs&, const float*, const float*, float*, float*, float*, float*, float*, float*, Profiler*, hipStream_t);

@@ -80,6 +80,7 @@ int stem_pack(const float* img, int N, int H, int W, int Hp, int Wp, T* img4, hi
 template <typename T>
 int stem_pack_u8(const uint8_t* img_nhwc, int N, int H, int W, int Hp, int Wp, const float* norm6, T* img4,
                  hipStream_t st);
+static inline int pool3s2_out(int n) { return (n + 2 - 3) / 2 + 1; }   // max-pool 3x3 / stride 2 / pad 1 output extent
 // y = maxpool3x3s2p1(relu(x*scale+shift)); idx = argmax tap (first max, row-major), 0..8
 template <typename T>
 int stem_bn_relu_pool(const T* x, const float* scale, const float* shift, int N, int H, int W, int C,

@@ -708,7 +708,7 @@ __global__ __launch_bounds__(256) void stem_bn_relu_pool_kernel(const T* __restr
 template <typename T>
 int stem_bn_relu_pool(const T* x, const float* scale, const float* shift, int N, int H, int W, int C, T* y,
                       uint8_t* idx, hipStream_t st) {
-  int PH = (H + 2 - 3) / 2 + 1, PW = (W + 2 - 3) / 2 + 1;
+  int PH = pool3s2_out(H), PW = pool3s2_out(W);
   ARG_CHECK(PH <= 65535 && N <= 65535, "stem_bn_relu_pool: grid %dx%d", PH, N);
   hipLaunchKernelGGL(stem_bn_relu_pool_kernel<T>, dim3(ceil_div(PW * (C / DT<T>::EPC), 256), PH, N), dim3(256), 0, st, x, scale,
                      shift, N, H, W, C, PH, PW, y, idx);
@@ -820,7 +820,7 @@ template <typename T>
 int stem_pool_bn_bwd_reduce(const T* dpool, const uint8_t* idx, const T* x, const float* scale, const float* shift, int N,
                             int H, int W, int C, float* partial, int* nrows_out, hipStream_t st) {
   ARG_CHECK(C % DT<T>::EPC == 0, "stem_pool_bn_bwd_reduce: C=%d", C);
-  const int PH = (H + 2 - 3) / 2 + 1, PW = (W + 2 - 3) / 2 + 1;
+  const int PH = pool3s2_out(H), PW = pool3s2_out(W);
   const size_t cells = (size_t)N * PH * PW;
   ARG_CHECK(cells < ((size_t)1 << 32), "stem_pool_bn_bwd_reduce: %zu cells", cells);
   ColGeom g = col_geom(cells, C, DT<T>::EPC);
@@ -904,7 +904,7 @@ template <typename T>
 int stem_pool_bwd_sums(const T* dpool, const T* ypool, const uint8_t* idx, const T* x, const float* scale, const float* shift, int N, int H, int W,
                        int C, float* partial, int* nrows_out, hipStream_t st) {
   ARG_CHECK(C % DT<T>::EPC == 0, "stem_pool_bwd_sums: C=%d", C);
-  const int PH = (H + 2 - 3) / 2 + 1, PW = (W + 2 - 3) / 2 + 1;
+  const int PH = pool3s2_out(H), PW = pool3s2_out(W);
   const size_t cells = (size_t)N * PH * PW;
   ARG_CHECK(cells < ((size_t)1 << 32), "stem_pool_bwd_sums: %zu cells", cells);
   ColGeom g = col_geom(cells, C, DT<T>::EPC);
@@ -943,7 +943,7 @@ template <typename T>
 int stem_pool_bn_bwd_apply(const T* dpool, const uint8_t* idx, const T* x, const float* scale, const float* shift,
                            const float* cA, const float* cB, const float* cC, int N, int H, int W, int C, T* dx, hipStream_t st) {
   ARG_CHECK(C % DT<T>::EPC == 0, "stem_pool_bn_bwd_apply: C=%d", C);
-  const int PH = (H + 2 - 3) / 2 + 1, PW = (W + 2 - 3) / 2 + 1;
+  const int PH = pool3s2_out(H), PW = pool3s2_out(W);
   ARG_CHECK(PH <= 65535 && N <= 65535, "stem_pool_bn_bwd_apply: grid %dx%d", PH, N);
   hipLaunchKernelGGL(stem_pool_bn_bwd_apply_kernel<T>, dim3(ceil_div(PW * (C / DT<T>::EPC), 256), PH, N), dim3(256), 0, st, dpool, idx,
                      x, scale, shift, cA, cB, cC, H, W, C, PH, PW, dx);

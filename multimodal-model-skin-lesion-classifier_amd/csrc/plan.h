@@ -42,38 +42,61 @@ struct Profiler {
 
 // Weight-gradient GEMMs only feed the optimizer, so they run on a second HIP stream beside the
 // dgrad -> BN-backward chain of the main stream (fills launch tails and latency-bound phases).
+// A slot stands for one operand buffer the main stream writes and a side-stream launch reads: the hand-off is run(), and the
+// main stream calls acquire() before it writes that buffer again.
 struct SideStream {
   hipStream_t s = nullptr;
-  hipEvent_t ready[3] = {nullptr, nullptr, nullptr};   // main: buffer i holds a fresh dX
-  hipEvent_t done[3] = {nullptr, nullptr, nullptr};    // side: the wgrad reading buffer i has finished
-  bool done_valid[3] = {false, false, false};
+  struct Slot {
+    hipEvent_t ready = nullptr;   // main: the buffer holds a fresh operand
+    hipEvent_t done = nullptr;    // side: the launch reading the buffer has finished
+    bool done_valid = false;
+  };
+  std::vector<Slot> slots;
   hipEvent_t f_ready = nullptr, f_done = nullptr;      // forward: block input ready / downsample branch finished
   hipEvent_t f_staged = nullptr;                       // forward: weights of the residual stages staged (beside the stem)
-  // algebraic BatchNorm backward (backbone.hip): the weight-gradient stream reads the block-output gradient buffer itself
-  hipEvent_t g_ready = nullptr, g_done[2] = {nullptr, nullptr};
-  bool g_done_valid[2] = {false, false};
-  int init() {
+  int init(int nslots) {
     if (s) return MMSKIN_OK;
     HIP_CHECK_RET(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));   // normal priority: high / low measured no different
-    for (int i = 0; i < 3; ++i) {
-      HIP_CHECK_RET(hipEventCreateWithFlags(&ready[i], hipEventDisableTiming));
-      HIP_CHECK_RET(hipEventCreateWithFlags(&done[i], hipEventDisableTiming));
+    slots.resize(nslots);
+    for (Slot& x : slots) {
+      HIP_CHECK_RET(hipEventCreateWithFlags(&x.ready, hipEventDisableTiming));
+      HIP_CHECK_RET(hipEventCreateWithFlags(&x.done, hipEventDisableTiming));
     }
     HIP_CHECK_RET(hipEventCreateWithFlags(&f_ready, hipEventDisableTiming));
     HIP_CHECK_RET(hipEventCreateWithFlags(&f_done, hipEventDisableTiming));
     HIP_CHECK_RET(hipEventCreateWithFlags(&f_staged, hipEventDisableTiming));
-    HIP_CHECK_RET(hipEventCreateWithFlags(&g_ready, hipEventDisableTiming));
-    HIP_CHECK_RET(hipEventCreateWithFlags(&g_done[0], hipEventDisableTiming));
-    HIP_CHECK_RET(hipEventCreateWithFlags(&g_done[1], hipEventDisableTiming));
     return MMSKIN_OK;
   }
   void destroy() {
     if (!s) return;
-    for (int i = 0; i < 3; ++i) { (void)hipEventDestroy(ready[i]); (void)hipEventDestroy(done[i]); }
-    (void)hipEventDestroy(f_ready); (void)hipEventDestroy(f_done); (void)hipEventDestroy(f_staged);
-    if (g_ready) { (void)hipEventDestroy(g_ready); (void)hipEventDestroy(g_done[0]); (void)hipEventDestroy(g_done[1]); }
+    for (Slot& x : slots) {
+      if (x.ready) (void)hipEventDestroy(x.ready);
+      if (x.done) (void)hipEventDestroy(x.done);
+    }
+    if (f_ready) (void)hipEventDestroy(f_ready);
+    if (f_done) (void)hipEventDestroy(f_done);
+    if (f_staged) (void)hipEventDestroy(f_staged);
     (void)hipStreamDestroy(s);
     s = nullptr;
+  }
+  void begin_backward() { for (Slot& x : slots) x.done_valid = false; }   // nothing of the previous backward is pending
+  // main may overwrite the slot's buffer only after the side-stream launch that reads it has finished
+  int acquire(int slot, hipStream_t main, bool use_side) {
+    if (use_side && slots[slot].done_valid) HIP_CHECK_RET(hipStreamWaitEvent(main, slots[slot].done, 0));
+    return MMSKIN_OK;
+  }
+  // launch(stream) reads the slot's buffer: on the side stream behind everything main has enqueued so far, or (use_side off: the
+  // profiled path) on main itself
+  template <class F>
+  int run(int slot, hipStream_t main, bool use_side, F launch) {
+    if (!use_side) return launch(main);
+    Slot& x = slots[slot];
+    HIP_CHECK_RET(hipEventRecord(x.ready, main));
+    HIP_CHECK_RET(hipStreamWaitEvent(s, x.ready, 0));
+    if (int rc = launch(s)) return rc;
+    HIP_CHECK_RET(hipEventRecord(x.done, s));
+    x.done_valid = true;
+    return MMSKIN_OK;
   }
 };
 
@@ -190,14 +213,31 @@ static inline size_t carve(size_t& cursor, size_t bytes) {
   return o;
 }
 
-#define PROF(cls_, flops_, bytes_, call_)                      \
+// One profiler event pair around `call_` on stream `st`, its FLOPs / bytes added to class cls_; returns from the enclosing function
+// (which has `int rc` and `hipStream_t st`) when the call fails.  prof_ may be null (op-level callers).
+#define PROF_AT(prof_, cls_, flops_, bytes_, call_)            \
   do {                                                        \
-    p.prof.begin((cls_), st);                                 \
+    Profiler* pr_ = (prof_);                                  \
+    if (pr_) pr_->begin((cls_), st);                          \
     rc = (call_);                                             \
-    p.prof.end(st);                                           \
-    if (p.prof.on) { p.prof.flops[(cls_)] += (flops_); p.prof.bytes[(cls_)] += (bytes_); } \
+    if (pr_) pr_->end(st);                                    \
+    if (pr_ && pr_->on) { pr_->flops[(cls_)] += (flops_); pr_->bytes[(cls_)] += (bytes_); } \
     if (rc) return rc;                                        \
   } while (0)
+#define PROF(cls_, flops_, bytes_, call_) PROF_AT(&p.prof, cls_, flops_, bytes_, call_)
+// The same pair around a group of launches: opened here, closed when the scope is left on any path.
+struct ProfScope {
+  Profiler* pr;
+  hipStream_t st;
+  ProfScope(Profiler* prof, int cls, hipStream_t stream, double flops, double bytes) : pr(prof), st(stream) {
+    if (!pr) return;
+    pr->begin(cls, st);
+    if (pr->on) { pr->flops[cls] += flops; pr->bytes[cls] += bytes; }
+  }
+  ~ProfScope() { if (pr) pr->end(st); }
+  ProfScope(const ProfScope&) = delete;
+  ProfScope& operator=(const ProfScope&) = delete;
+};
 
 static inline double conv_flops(const ConvShape& s) {
   return 2.0 * s.N * s.OH() * s.OW() * (double)s.Cout * s.Cin * s.kh * s.kw;
@@ -207,6 +247,134 @@ static inline double conv_flops(const ConvShape& s) {
 static inline double conv_bytes(const ConvShape& s, size_t es, int extra_in_shaped = 0) {
   double in = (double)s.N * s.H * s.W * s.Cin, out = (double)s.N * s.OH() * s.OW() * s.Cout;
   return (in * (1 + extra_in_shaped) + out) * es + (double)s.Cout * s.Cin * s.kh * s.kw * es;
+}
+
+// ---- BatchNorm coefficient blocks.  Forward: scale | shift | mean | invstd | gamma, C floats each, written by bn_finalize (the first
+// four), bn_eval_coeffs / bn_eval_table (the first two) or bn_coef_from_table (all five: gamma is the copy zero-padded to C channels).
+// A view over a block of only two or four slots simply does not touch the later members.
+struct BnCoef {
+  float *scale, *shift, *mean, *invstd, *gamma;
+  BnCoef(float* base, int C) : scale(base), shift(scale + C), mean(shift + C), invstd(mean + C), gamma(invstd + C) {}
+};
+// Backward: dx = cA * dz + cB * x + cC, written by bn_bwd_finalize
+struct BnBwdCoef {
+  float *cA, *cB, *cC;
+  BnBwdCoef(float* base, int C) : cA(base), cB(cA + C), cC(cB + C) {}
+};
+
+// BatchNorm backward when the masked gradient dz already exists and its partial sums (sum dz, sum dz * x) came from the epilogue of the
+// launch that wrote it: finalize (gamma / beta gradients for channels < n_grad, and c) + one apply pass dx = cA dz + cB x + cC.
+// dx == nullptr: finalize only.  accumulate_bc / sum_dz_x: as bn_bwd_finalize.  One profiler pair (prof may be null) with the
+// caller's byte count.
+template <typename T>
+int bn_backward_from_sums(const T* dz, const T* x, const float* partial, int nrows, size_t rows, int C, const BnCoef& k, const float* gamma,
+                          float* dgamma, float* dbeta, const BnBwdCoef& c, double* red, T* dx, Profiler* prof, double prof_bytes,
+                          hipStream_t st, int n_grad = -1, bool accumulate_bc = false, const float* sum_dz_x = nullptr) {
+  ProfScope scope(prof, K_BN_BWD, st, 0.0, prof_bytes);
+  if (int rc = bn_bwd_finalize(partial, nrows, C, (double)rows, gamma, k.mean, k.invstd, dgamma, dbeta, c.cA, c.cB, c.cC, red, st, n_grad,
+                               accumulate_bc, sum_dz_x)) return rc;
+  if (!dx) return MMSKIN_OK;
+  return bn_bwd_apply<T>(dz, x, nullptr, k.scale, k.shift, MASK_NONE, c.cA, c.cB, c.cC, dx, nullptr, rows, C, st);
+}
+// BatchNorm (+ activation mask `mode` from x or ymask) backward from dy: reduce -> finalize -> apply; fills dx and, when given, dz (the
+// masked dy).  One profiler pair with the caller's byte count.
+template <typename T>
+int bn_backward(const T* dy, const T* x, const T* ymask, int mode, size_t rows, int C, const BnCoef& k, const float* gamma, float* dgamma,
+                float* dbeta, const BnBwdCoef& c, float* partial, double* red, T* dx, T* dz, Profiler* prof, double prof_bytes,
+                hipStream_t st, int n_grad = -1) {
+  ProfScope scope(prof, K_BN_BWD, st, 0.0, prof_bytes);
+  int nr = 0;
+  if (int rc = bn_bwd_reduce<T>(dy, x, ymask, k.scale, k.shift, mode, rows, C, partial, &nr, st)) return rc;
+  if (int rc = bn_bwd_finalize(partial, nr, C, (double)rows, gamma, k.mean, k.invstd, dgamma, dbeta, c.cA, c.cB, c.cC, red, st, n_grad)) return rc;
+  return bn_bwd_apply<T>(dy, x, ymask, k.scale, k.shift, mode, c.cA, c.cB, c.cC, dx, dz, rows, C, st);
+}
+
+// ---- the 7x7 / stride 2 stem of ResNet and DenseNet: conv -> BatchNorm -> ReLU -> max-pool 3x3 / stride 2, 64 channels
+struct StemGeom {
+  int N, H, W;
+  int OH, OW;   // conv output
+  int Hp, Wp;   // zero-padded NHWC4 image the conv kernels read (stem_pack): 3 px top / left border, even width
+  int PH, PW;   // pooled output
+  StemGeom(int n = 0, int h = 0, int w = 0) : N(n), H(h), W(w) {
+    OH = (H + 6 - 7) / 2 + 1; OW = (W + 6 - 7) / 2 + 1;
+    Hp = 2 * OH + 8; Wp = 2 * OW + 8;
+    if (Hp < H + 6) Hp = H + 6;
+    if (Wp < W + 6) Wp = W + 6;
+    Wp = (Wp + 1) / 2 * 2;
+    PH = pool3s2_out(OH); PW = pool3s2_out(OW);
+  }
+  size_t rows() const { return (size_t)N * OH * OW; }
+  size_t pooled() const { return (size_t)N * PH * PW; }
+  ConvShape conv() const { return ConvShape{N, H, W, 3, 64, 7, 7, 2, 3}; }
+};
+// The stem's buffers: the plans fill it from their workspace offsets, the op-level entry points from their carve.
+template <typename T>
+struct StemBufs {
+  T* img4 = nullptr;         // packed image [N][Hp][Wp][4]
+  const T* wv = nullptr;     // staged weights (64 x 256, zero padding taps)
+  T* x0 = nullptr;           // raw conv output [rows][64]
+  T* pool = nullptr;         // pooled activation [pooled][64]
+  uint8_t* idx = nullptr;    // argmax tap of every pooled element
+  float* coef = nullptr;     // BnCoef block (4 slots)
+  float *ssum = nullptr, *ssq = nullptr;   // batch-statistics slabs of the conv epilogue
+  double* red = nullptr;     // reduction scratch of the finalize kernels
+  // backward
+  float* coefbwd = nullptr;  // BnBwdCoef block
+  float* partial = nullptr;  // BatchNorm-backward partial sums
+  T* dx0 = nullptr;          // gradient of the raw conv output [rows][64]
+  float *slab = nullptr, *dwv = nullptr;   // weight-gradient slab, and the gradient in the staged (64 x 256) layout
+};
+// Where the stem's BatchNorm coefficients come from
+struct StemBn {
+  const float *gamma = nullptr, *beta = nullptr;   // both null: coef already holds scale | shift (folded eval: bn_eval_table wrote them)
+  float *rm = nullptr, *rv = nullptr;              // running statistics: updated (batch_stats; may be null) or read
+  float eps = 1e-5f, mom = 0.1f;
+  bool batch_stats = false;                        // training: statistics of this batch from the conv epilogue
+};
+// image: fp32 NCHW, uint8 NHWC with norm6 (PlanBase::forward), or null when b.img4 is packed already
+template <typename T>
+int stem_forward(const StemBufs<T>& b, const StemGeom& g, const void* image, const float* norm6, const StemBn& bn, Profiler* prof,
+                 hipStream_t st) {
+  int rc, stat_rows = 0;
+  if (image && norm6) PROF_AT(prof, K_STEM_MISC, 0.0, 0.0, stem_pack_u8<T>((const uint8_t*)image, g.N, g.H, g.W, g.Hp, g.Wp, norm6, b.img4, st));
+  else if (image) PROF_AT(prof, K_STEM_MISC, 0.0, 0.0, stem_pack<T>((const float*)image, g.N, g.H, g.W, g.Hp, g.Wp, b.img4, st));
+  const ConvShape s = g.conv();
+  const BnCoef k(b.coef, 64);
+  PROF_AT(prof, K_CONV_FWD, conv_flops(s), conv_bytes(s, sizeof(T)),
+          launch_stem_conv_fwd<T>(g.N, g.OH, g.OW, g.Hp, g.Wp, b.img4, b.wv, b.x0, bn.batch_stats ? b.ssum : nullptr,
+                                  bn.batch_stats ? b.ssq : nullptr, st, &stat_rows));
+  if (bn.batch_stats)
+    PROF_AT(prof, K_BN_FWD, 0.0, 0.0, bn_finalize(b.ssum, b.ssq, stat_rows, 64, (double)g.rows(), bn.gamma, bn.beta, bn.eps, bn.mom, bn.rm, bn.rv,
+                                                  k.scale, k.shift, k.mean, k.invstd, b.red, st));
+  else if (bn.gamma)
+    PROF_AT(prof, K_BN_FWD, 0.0, 0.0, bn_eval_coeffs(64, bn.gamma, bn.beta, bn.rm, bn.rv, bn.eps, k.scale, k.shift, st));
+  // one pass over the largest activation: BatchNorm + ReLU + max-pool
+  PROF_AT(prof, K_STEM_MISC, 0.0, 0.0, stem_bn_relu_pool<T>(b.x0, k.scale, k.shift, g.N, g.OH, g.OW, 64, b.pool, b.idx, st));
+  return MMSKIN_OK;
+}
+// dpool (gradient of the pooled activation) -> b.dx0 and dgamma / dbeta: max-pool + ReLU + BatchNorm backward without materialising the
+// full-resolution pooled gradient.  sums_pooled (callers: stem_sums_pooled()): the partial sums come from the pooled tensors alone
+// instead of the conv output and the routed gradient.  One profiler pair with the caller's byte count.
+template <typename T>
+int stem_backward(const StemBufs<T>& b, const StemGeom& g, const T* dpool, const float* gamma, float* dgamma, float* dbeta, bool sums_pooled,
+                  Profiler* prof, double prof_bytes, hipStream_t st) {
+  const BnCoef k(b.coef, 64);
+  const BnBwdCoef c(b.coefbwd, 64);
+  ProfScope scope(prof, K_BN_BWD, st, 0.0, prof_bytes);
+  int rc, nr = 0;
+  if (sums_pooled) rc = stem_pool_bwd_sums<T>(dpool, b.pool, b.idx, b.x0, k.scale, k.shift, g.N, g.OH, g.OW, 64, b.partial, &nr, st);
+  else rc = stem_pool_bn_bwd_reduce<T>(dpool, b.idx, b.x0, k.scale, k.shift, g.N, g.OH, g.OW, 64, b.partial, &nr, st);
+  if (rc) return rc;
+  if ((rc = bn_backward_from_sums<T>(nullptr, nullptr, b.partial, nr, g.rows(), 64, k, gamma, dgamma, dbeta, c, b.red, nullptr, nullptr, 0.0, st)))
+    return rc;
+  return stem_pool_bn_bwd_apply<T>(dpool, b.idx, b.x0, k.scale, k.shift, c.cA, c.cB, c.cC, g.N, g.OH, g.OW, 64, b.dx0, st);
+}
+// b.dx0, b.img4 -> dw [64][3][7][7], on the stream the caller picks (SideStream::run: it needs the slab)
+template <typename T>
+int stem_wgrad(const StemBufs<T>& b, const StemGeom& g, float* dw, Profiler* prof, hipStream_t st) {
+  int rc;
+  PROF_AT(prof, K_WGRAD, conv_flops(g.conv()), 0.0, launch_stem_conv_wgrad<T>(g.N, g.OH, g.OW, g.Hp, g.Wp, b.dx0, b.img4, b.slab, b.dwv, st));
+  return stem_wgrad_unpack(b.dwv, dw, st);
 }
 
 // ---- squeeze-excitation (mbconv.hip): the chain the MBConv plan runs behind a depthwise unit, shared with the op-level entry

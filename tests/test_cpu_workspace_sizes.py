@@ -5,7 +5,12 @@ host arithmetic over the layout struct that the op itself carves, csrc/capi.hip 
   formulas returned before the layouts were written once: any change would move an allocation or an offset.
 * mmskin_*_workspace_bytes serve the op-by-op tests.  They are a carve now, so there is no second formula to compare with; what can be
   checked without one: a positive multiple of the carver's 256-byte alignment, not smaller for a larger batch, and not smaller than the
-  tensors the op must hold (counted here from the shapes alone, fp32 elements unless the op is bf16-only)."""
+  tensors the op must hold (counted here from the shapes alone, fp32 elements unless the op is bf16-only).
+* mmskin_backbone_create needs no device either: the carve-up of every plan (workspace bytes, parameter and buffer counts, and the
+  twelve unit_info fields of the first and last unit where a plan reports units) is pinned to the values of commit a9b9008, before the
+  stem geometry and the side-stream slots were each written once."""
+import ctypes
+
 import pytest
 
 from mbconv_cases import BN_SHAPES, DW_CASES, SE_SHAPES, out_hw, pad64
@@ -113,3 +118,62 @@ def test_one_abn_workspace_serves_both_entry_points():
     lib = _lib.load()
     for N, Cw, C4, H, W in [(2, 64, 256, 14, 14), (3, 128, 512, 9, 11), (256, 64, 256, 56, 56)]:
         assert lib.mmskin_abn_workspace_bytes(N, Cw, C4, H, W) >= 2 * N * H * W * Cw + 4 * (256 * Cw + 256)
+
+
+# ---- plan carve-ups: (arch, (N, H, W), dtype) -> (workspace bytes, param numel, buffer numel, units, (info12 of the first unit, of the last))
+# None: not pinned -- the ResNet stem unit has no post-activation buffer (its output is the pooled map), and its y_off field was
+# uninitialised memory in the library these values were recorded from
+PLAN_PINS = {
+    ('resnet-18', (2, 64, 64), 'fp32'): (106652672, 11176512, 9600, 20, ((89508864, None, 89507840, 2048, 64, 32, 32, 3, 64, 64, 91206656, 92384256), (91190272, 92366848, 91182080, 8, 512, 2, 2, 512, 2, 2, 91206656, 92384256))),
+    ('resnet-18', (2, 64, 64), 'bf16'): (58688512, 11176512, 9600, 20, ((44763136, None, 44762112, 2048, 64, 32, 32, 3, 64, 64, 45649920, 46255104), (45641728, 46246400, 45633536, 8, 512, 2, 2, 512, 2, 2, 45649920, 46255104))),
+    ('resnet-18', (3, 96, 128), 'fp32'): (129973248, 11176512, 9600, 20, ((90079232, None, 90078208, 9216, 64, 48, 64, 3, 96, 128, 97454080, 102753280), (97380352, 102674944, 97372160, 36, 512, 3, 4, 512, 3, 4, 97454080, 102753280))),
+    ('resnet-18', (3, 96, 128), 'bf16'): (70488064, 11176512, 9600, 20, ((45076992, None, 45075968, 9216, 64, 48, 64, 3, 96, 128, 48802304, 51525632), (48765440, 51486464, 48757248, 36, 512, 3, 4, 512, 3, 4, 48802304, 51525632))),
+    ('resnet-50', (2, 64, 64), 'fp32'): (219206656, 23508032, 53120, 53, ((187829248, None, 187828224, 2048, 64, 32, 32, 3, 64, 64, 195511296, 201651200), (195445760, 201581568, 195412992, 8, 2048, 2, 2, 512, 2, 2, 195511296, 201651200))),
+    ('resnet-50', (2, 64, 64), 'bf16'): (118606848, 23508032, 53120, 53, ((93931520, None, 93930496, 2048, 64, 32, 32, 3, 64, 64, 97984512, 101070848), (97951744, 101036032, 97918976, 8, 2048, 2, 2, 512, 2, 2, 97984512, 101070848))),
+    ('resnet-50', (3, 96, 128), 'fp32'): (279924736, 23508032, 53120, 53, ((188383232, None, 188382208, 9216, 64, 48, 64, 3, 96, 128, 221468672, 249098240), (221173760, 248784896, 221140992, 36, 2048, 3, 4, 512, 3, 4, 221468672, 249098240))),
+    ('resnet-50', (3, 96, 128), 'bf16'): (149650944, 23508032, 53120, 53, ((94228992, None, 94227968, 9216, 64, 48, 64, 3, 96, 128, 110983680, 124872192), (110836224, 124715520, 110803456, 36, 2048, 3, 4, 512, 3, 4, 110983680, 124872192))),
+    ('densenet169', (2, 64, 64), 'fp32'): (151677696, 12484480, 158400, 0, ()),
+    ('densenet169', (2, 64, 64), 'bf16'): (79245056, 12484480, 158400, 0, ()),
+    ('densenet169', (3, 96, 128), 'fp32'): (230309632, 12484480, 158400, 0, ()),
+    ('densenet169', (3, 96, 128), 'bf16'): (121615616, 12484480, 158400, 0, ()),
+    ('densenet169-features', (2, 64, 64), 'fp32'): (151677696, 12484480, 158400, 0, ()),
+    ('densenet169-features', (2, 64, 64), 'bf16'): (79245056, 12484480, 158400, 0, ()),
+    ('densenet169-features', (3, 96, 128), 'fp32'): (230309632, 12484480, 158400, 0, ()),
+    ('densenet169-features', (3, 96, 128), 'bf16'): (121615616, 12484480, 158400, 0, ()),
+    ('vgg16-features', (2, 64, 64), 'fp32'): (142340608, 14714688, 0, 0, ()),
+    ('vgg16-features', (2, 64, 64), 'bf16'): (76325120, 14714688, 0, 0, ()),
+    ('vgg16-features', (3, 96, 128), 'fp32'): (264321792, 14714688, 0, 0, ()),
+    ('vgg16-features', (3, 96, 128), 'bf16'): (173257216, 14714688, 0, 0, ()),
+    ('mobilenet-v2', (2, 64, 64), 'fp32'): (40450048, 2223872, 34112, 52, ((20440064, 20964352, 21488640, 2048, 32, 32, 32, 3, 64, 64, 0, 36255744), (32996864, 33037824, 33078784, 8, 1280, 2, 2, 320, 2, 2, 32980224, 36255744))),
+    ('mobilenet-v2', (2, 64, 64), 'bf16'): (21978624, 2223872, 34112, 52, ((10220032, 10482176, 10744320, 2048, 32, 32, 32, 3, 64, 64, 0, 19881472), (16663552, 16684032, 16704512, 8, 1280, 2, 2, 320, 2, 2, 16652032, 19881472))),
+    ('mobilenet-v2', (3, 96, 128), 'fp32'): (102373120, 2223872, 34112, 52, ((21394688, 23753984, 26113280, 9216, 32, 48, 64, 3, 96, 128, 0, 83498752), (76744448, 76928768, 77113088, 36, 1280, 3, 4, 320, 3, 4, 76691968, 83498752))),
+    ('mobilenet-v2', (3, 96, 128), 'bf16'): (54544640, 2223872, 34112, 52, ((10697472, 11877120, 13056768, 9216, 32, 48, 64, 3, 96, 128, 0, 45107456), (38537472, 38629632, 38721792, 36, 1280, 3, 4, 320, 3, 4, 38508032, 45107456))),
+    ('efficientnet-b0', (2, 64, 64), 'fp32'): (54398720, 4007548, 42016, 49, ((28730368, 29254656, 29778944, 2048, 32, 32, 32, 3, 64, 64, 0, 50204416), (46383104, 46424064, 46465024, 8, 1280, 2, 2, 320, 2, 2, 46366464, 50204416))),
+    ('efficientnet-b0', (2, 64, 64), 'bf16'): (30691584, 4007548, 42016, 49, ((14365184, 14627328, 14889472, 2048, 32, 32, 32, 3, 64, 64, 0, 28594432), (24814080, 24834560, 24855040, 8, 1280, 2, 2, 320, 2, 2, 24802560, 28594432))),
+    ('efficientnet-b0', (3, 96, 128), 'fp32'): (124082176, 4007548, 42016, 49, ((29684992, 32044288, 34403584, 9216, 32, 48, 64, 3, 96, 128, 0, 105207808), (97880320, 98064640, 98248960, 36, 1280, 3, 4, 320, 3, 4, 97827840, 105207808))),
+    ('efficientnet-b0', (3, 96, 128), 'bf16'): (67201024, 4007548, 42016, 49, ((14842624, 16022272, 17201920, 9216, 32, 48, 64, 3, 96, 128, 0, 57763840), (50620672, 50712832, 50804992, 36, 1280, 3, 4, 320, 3, 4, 50591232, 57763840))),
+    ('efficientnet-b7', (2, 64, 64), 'fp32'): (572389632, 63786960, 310720, 163, ((422388736, 422913024, 423437312, 2048, 64, 32, 32, 3, 64, 64, 0, 566098176), (546476544, 546558464, 546640384, 8, 2560, 2, 2, 640, 2, 2, 546443264, 566098176))),
+    ('efficientnet-b7', (2, 64, 64), 'bf16'): (322325248, 63786960, 310720, 163, ((211194368, 211456512, 211718656, 2048, 64, 32, 32, 3, 64, 64, 0, 319179520), (299639808, 299680768, 299721728, 8, 2560, 2, 2, 640, 2, 2, 299616768, 319179520))),
+    ('efficientnet-b7', (3, 96, 128), 'fp32'): (847353856, 63786960, 310720, 163, ((423343360, 425702656, 428061952, 9216, 64, 48, 64, 3, 96, 128, 0, 819042304), (797800192, 798168832, 798537472, 36, 2560, 3, 4, 640, 3, 4, 797695232, 819042304))),
+    ('efficientnet-b7', (3, 96, 128), 'bf16'): (460767232, 63786960, 310720, 163, ((211671808, 212851456, 214031104, 9216, 64, 48, 64, 3, 96, 128, 0, 446611456), (425737984, 425922304, 426106624, 36, 2560, 3, 4, 640, 3, 4, 425679104, 446611456))),
+}
+
+
+@pytest.mark.parametrize("key", list(PLAN_PINS), ids=lambda k: "%s-%s-%s" % (k[0], "x".join(map(str, k[1])), k[2]))
+def test_plan_carve_is_what_it_was(key):
+    arch, shape, dtype = key
+    ws_bytes, params, buffers, units, infos = PLAN_PINS[key]
+    lib = _lib.load()
+    h = ctypes.c_void_p()
+    _lib.check(lib.mmskin_backbone_create(arch.encode(), *shape, {"fp32": _lib.F32, "bf16": _lib.BF16}[dtype], ctypes.byref(h)))
+    try:
+        assert lib.mmskin_backbone_workspace_bytes(h) == ws_bytes
+        assert lib.mmskin_backbone_param_numel(h) == params
+        assert lib.mmskin_backbone_buffer_numel(h) == buffers
+        assert lib.mmskin_backbone_num_units(h) == units
+        for index, want in zip((0, units - 1), infos):
+            info = (ctypes.c_int64 * 12)()
+            _lib.check(lib.mmskin_backbone_unit_info(h, index, None, 0, info))
+            assert [g for g, w in zip(info, want) if w is not None] == [w for w in want if w is not None], (index, list(info))
+    finally:
+        lib.mmskin_backbone_destroy(h)
