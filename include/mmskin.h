@@ -559,6 +559,76 @@ int mmskin_scorecam_combine(const float* fmap, const float* minmax, const float*
                             int channel_block, float* heat, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Metadata-sensitivity sweeps (interpretability/flip_rate.py:164-256, inference_all_folds.py:116-140,
+ * analyze_prediction_uncertainty.py:166-272): the image is encoded once, the fusion head runs on V metadata variants of the
+ * batch (mmskin.sweep.MetadataSweep); these are the kernels before and after the head.
+ *
+ * metadata_variants: mutate + one-hot + standardise, fused.  codes, col_offset, onehot_width, numeric, mean, scale, nan_fill
+ * are the inputs of mmskin_metadata_encode.  Columns are numbered categorical first: 0 .. n_cat - 1 are the columns of
+ * `codes`, n_cat .. n_cat + n_num - 1 those of `numeric`.  The variant table holds V records of 32 bytes, one mutation of one
+ * column each:
+ *   op        int32    MMSKIN_META_*:
+ *                        NONE        identity (the baseline is variant 0 by convention); column, a, b, value are ignored
+ *                        CAT_SET     code = a
+ *                        CAT_TOGGLE  code = (code == a) ? b : a    (the reference's `not bool(x)`, its gender swap and its
+ *                                    FACE / FOREARM rule, flip_rate.py:167-181, each with the right (a, b))
+ *                        NUM_ADD     raw value + `value`, before filling and scaling; NaN stays NaN and is then filled,
+ *                                    as float('nan') + 5 followed by fillna(-1)
+ *                        NUM_SET     raw value = `value`
+ *   column    int32    the mutated column, numbered as above
+ *   a, b      int32    category codes of that column, -1 .. count - 1 (-1 = a value unseen at fit time: an all-zero block)
+ *   value     float32  operand of NUM_ADD / NUM_SET
+ *   reserved[3] uint32 zero
+ * mask (optional, device) uint8 [V][batch][n_cat + n_num], applied AFTER the record's op: non-zero blanks the cell -- a
+ * numeric becomes missing (-> nan_fill), a categorical takes missing_code[column] (device int32 [n_cat]: the code of the
+ * column's "EMPTY" category, or -1 when that value was not seen at fit time, which encodes as an all-zero block like
+ * handle_unknown='ignore').  out fp32 [V][batch][out_width]: columns [0, onehot_width + n_num) as mmskin_metadata_encode
+ * writes them (the same (x - mean) / scale: an unmutated, unmasked variant equals its output bit for bit), zeros beyond;
+ * a smaller out_width truncates (the reference pads or cuts to the checkpoint's vocab_size, inference_all_folds.py:105-112).
+ * A pure function of its inputs, no atomics, every output element written exactly once (no pre-zeroing).
+ * variants_host is the table in host memory and col_offset_host a host copy of col_offset: the call validates the table
+ * against them and then uploads exactly those bytes on `stream` into variants_scratch, V records of device memory that the
+ * caller only provides (it must stay allocated until the kernel has run, in stream order).  Errors (nothing is launched):
+ * V, batch or out_width < 1, no column at all, an unknown op, a column outside [0, n_cat + n_num), a CAT_* op on a numeric
+ * column or a NUM_* op on a categorical one, a code outside -1 .. count - 1 of its column.
+ *
+ * sweep_reduce: logits in, answers out, nothing to the host.  logits [V][batch][C], fp32 (logits_dtype 0) or bf16 (1, what
+ * the head delivers on the inference lane); base fp32 [batch][C], the baseline logits; labels int32 [batch] or NULL.
+ * Per (v, b):
+ *   probs   fp32 [V][batch][C]  soft-max of the logits, exp(x - max) / sum (NULL: not written)
+ *   pred    int32 [V][batch]    FIRST index of the maximum LOGIT (the reference takes the argmax of the fp32 soft-max; the two
+ *                               differ only where rounding in exp makes two probabilities equal although the logits differ)
+ *   margin  fp32 [V][batch]     top-1 minus top-2 logit
+ *   stats   fp32 [V][batch][4]  on p = clip(probs, 1e-12, 1) / sum (safe_probs) of the variant and q of the baseline:
+ *                               entropy -sum p ln p (nats), KL(p || q), JS(p, q) = KL(p || m) / 2 + KL(q || m) / 2 with
+ *                               m = (p + q) / 2, and p[base_pred] - q[base_pred]
+ * Counters, ADDED TO so that several batches accumulate (the caller zeroes them once): flips int32 [V] (pred != base_pred),
+ * transitions int32 [V][C][C] indexed [base_pred][pred], and with labels confusion int32 [V][C][C] indexed [label][pred].
+ * Each workgroup counts into an LDS histogram and issues one integer atomic add per non-zero cell: the result does not
+ * depend on launch order.  labels live on the device, so they are not inspected on the host: a row whose label is outside
+ * [0, C) is skipped in `confusion` only.  2 <= C <= 64 (one class per lane), anything else is MMSKIN_ERR_UNSUPPORTED;
+ * V or batch < 1 and null arguments are errors.  Nothing is launched on an error. */
+#define MMSKIN_META_NONE 0
+#define MMSKIN_META_CAT_SET 1
+#define MMSKIN_META_CAT_TOGGLE 2
+#define MMSKIN_META_NUM_ADD 3
+#define MMSKIN_META_NUM_SET 4
+typedef struct mmskin_meta_variant {
+  int32_t op;
+  int32_t column;
+  int32_t a, b;
+  float value;
+  uint32_t reserved[3];
+} mmskin_meta_variant;
+int mmskin_metadata_variants(const int32_t* codes, int n_cat, const int32_t* col_offset, const int32_t* col_offset_host,
+                             int onehot_width, const float* numeric, int n_num, const float* mean, const float* scale,
+                             float nan_fill, const mmskin_meta_variant* variants_host, mmskin_meta_variant* variants_scratch, int V,
+                             const uint8_t* mask, const int32_t* missing_code, float* out, int batch, int out_width, void* stream);
+int mmskin_sweep_reduce(const void* logits, int logits_dtype, const float* base, const int32_t* labels, int V, int batch, int C,
+                        float* probs, int32_t* pred, float* margin, float* stats, int32_t* flips, int32_t* transitions,
+                        int32_t* confusion, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * `custom-cnn` image encoder pieces (loadImageModelClassifier.py:50-60): small direct kernels for
  * shapes the MFMA implicit GEMM does not cover (Cin=3, Cout=16).  NCHW fp32. */
 int mmskin_direct_conv2d_forward(const float* x, const float* w, const float* b, float* y, int N, int Cin, int H, int W,

@@ -7,6 +7,7 @@ matching backward entry point needs.  No arithmetic happens in PyTorch here.
 import ctypes
 import weakref
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1543,3 +1544,78 @@ def scorecam_combine(fmap, minmax, scores, size, channel_block=0):
     heat = torch.empty((H, W), device=fmap.device, dtype=torch.float32)
     call("mmskin_scorecam_combine", ptr(fmap), ptr(minmax), ptr(scores), C, fh, fw, H, W, int(channel_block), ptr(heat), stream())
     return heat
+
+
+# ---------------------------------------------------------------------------------------------- metadata sweeps (forward only)
+META_NONE, META_CAT_SET, META_CAT_TOGGLE, META_NUM_ADD, META_NUM_SET = 0, 1, 2, 3, 4          # MMSKIN_META_* of mmskin.h
+# one record per variant: struct mmskin_meta_variant of include/mmskin.h (32 bytes)
+META_VARIANT_DTYPE = np.dtype([("op", "<i4"), ("column", "<i4"), ("a", "<i4"), ("b", "<i4"), ("value", "<f4"), ("reserved", "<u4", (3,))])
+assert META_VARIANT_DTYPE.itemsize == 32
+
+
+def _dev_tensor(t, dtype, shape, what):
+    if t is None or not t.is_cuda or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous {str(dtype).replace('torch.', '')} {tuple(shape)} device tensor, got "
+                         f"{None if t is None else (t.dtype, tuple(t.shape), str(t.device))}")
+    return t
+
+
+def metadata_variants(codes, numeric, col_offset, mean, scale, nan_fill, table, out_width, mask=None, missing_code=None, out=None):
+    """The V mutated, encoded metadata batches [V, B, out_width] of one batch, in one kernel (mmskin_metadata_variants).
+    codes int32 [B, n_cat] and numeric fp32 [B, n_num] on the device; col_offset a HOST int32 array [n_cat + 1]; mean / scale fp32
+    [n_num] on the device; table a numpy array of META_VARIANT_DTYPE records (validated by the library); mask uint8
+    [V, B, n_cat + n_num] and missing_code int32 [n_cat] on the device, or None."""
+    _need_gpu(codes, "metadata_variants")
+    table = np.ascontiguousarray(table)
+    if table.dtype != META_VARIANT_DTYPE or table.ndim != 1:
+        raise ValueError("metadata_variants: table must be a 1-D array of META_VARIANT_DTYPE records")
+    V, (B, n_cat), n_num = len(table), codes.shape, numeric.shape[1]
+    dev = codes.device
+    _dev_tensor(codes, torch.int32, (B, n_cat), "metadata_variants: codes")
+    _dev_tensor(numeric, torch.float32, (B, n_num), "metadata_variants: numeric")
+    off_host = np.ascontiguousarray(col_offset, dtype=np.int32)
+    if off_host.shape != (n_cat + 1,):
+        raise ValueError(f"metadata_variants: col_offset must have {n_cat + 1} entries, got {off_host.shape}")
+    if n_num:
+        _dev_tensor(mean, torch.float32, (n_num,), "metadata_variants: mean")
+        _dev_tensor(scale, torch.float32, (n_num,), "metadata_variants: scale")
+    if mask is not None:
+        _dev_tensor(mask, torch.uint8, (V, B, n_cat + n_num), "metadata_variants: mask")
+        if n_cat:
+            _dev_tensor(missing_code, torch.int32, (n_cat,), "metadata_variants: missing_code")
+    out_width = int(out_width)
+    if out is None:
+        out = torch.empty((V, B, max(out_width, 0)), device=dev, dtype=torch.float32)
+    else:
+        _dev_tensor(out, torch.float32, (V, B, out_width), "metadata_variants: out")
+    off_dev = torch.from_numpy(off_host).to(dev)
+    scratch = torch.empty(max(table.nbytes, 1), dtype=torch.uint8, device=dev)      # the library uploads the table into it
+    call("mmskin_metadata_variants", ptr(codes), n_cat, ptr(off_dev), ctypes.c_void_p(off_host.ctypes.data), int(off_host[-1]),
+         ptr(numeric), n_num, ptr(mean) if n_num else None, ptr(scale) if n_num else None, float(nan_fill),
+         ctypes.c_void_p(table.ctypes.data), ptr(scratch), V, ptr(mask), ptr(missing_code) if mask is not None and n_cat else None,
+         ptr(out), B, out_width, stream())
+    return out
+
+
+def sweep_reduce(logits, base, flips, transitions, confusion=None, labels=None, want_probs=True):
+    """logits [V, B, C] (fp32 or bf16) against the baseline logits base fp32 [B, C] -> (probs or None, pred, margin, stats) per
+    (v, b); the flip / transition (/ confusion, with labels int32 [B]) counts are ADDED to the int32 device counters flips [V],
+    transitions [V, C, C], confusion [V, C, C] (mmskin_sweep_reduce)."""
+    _need_gpu(logits, "sweep_reduce")
+    if logits.dim() != 3 or logits.dtype not in (torch.float32, torch.bfloat16) or not logits.is_contiguous():
+        raise ValueError(f"sweep_reduce: logits must be a contiguous fp32 or bf16 [V, B, C] tensor, got {logits.dtype} {tuple(logits.shape)}")
+    V, B, C = logits.shape
+    dev = logits.device
+    _dev_tensor(base, torch.float32, (B, C), "sweep_reduce: base")
+    _dev_tensor(flips, torch.int32, (V,), "sweep_reduce: flips")
+    _dev_tensor(transitions, torch.int32, (V, C, C), "sweep_reduce: transitions")
+    if labels is not None:
+        _dev_tensor(labels, torch.int32, (B,), "sweep_reduce: labels")
+        _dev_tensor(confusion, torch.int32, (V, C, C), "sweep_reduce: confusion")
+    probs = torch.empty((V, B, C), device=dev, dtype=torch.float32) if want_probs else None
+    pred = torch.empty((V, B), device=dev, dtype=torch.int32)
+    margin = torch.empty((V, B), device=dev, dtype=torch.float32)
+    stats = torch.empty((V, B, 4), device=dev, dtype=torch.float32)
+    call("mmskin_sweep_reduce", ptr(logits), _dtype_code(logits), ptr(base), ptr(labels), V, B, C, ptr(probs), ptr(pred), ptr(margin),
+         ptr(stats), ptr(flips), ptr(transitions), ptr(confusion) if labels is not None else None, stream())
+    return probs, pred, margin, stats

@@ -116,11 +116,20 @@ class MultimodalModel(nn.Module):
         attention_mask = text_metadata["attention_mask"].squeeze(1).to(self.device)
         return self.text_encoder(input_ids=input_ids, attention_mask=attention_mask).last_hidden_state[:, 0, :]
 
-    def forward(self, image, text_metadata):
-        mech = self.attention_mecanism
+    def encode_image(self, image):
+        """The image half of forward: img_feat [B, cnn_dim_output], computed before anything looks at the metadata."""
         img_feat = self.image_encoder(image.to(self.device))
         if img_feat.dim() == 4:
             img_feat = img_feat.mean(dim=(-2, -1))
+        return img_feat
+
+    def forward(self, image, text_metadata):
+        return self.fuse(self.encode_image(image), text_metadata)
+
+    def fuse(self, img_feat, text_metadata):
+        """The fusion half of forward: img_feat [R, cnn_dim_output] + metadata of R rows -> logits [R, num_classes].  R is any
+        row count (mmskin.sweep tiles one batch's img_feat over its metadata variants)."""
+        mech = self.attention_mecanism
         needs_meta = mech not in ("no-metadata", "no-metadata-without-mlp")
         if mech == "no-metadata-without-mlp":
             return self.fc_visual_only(img_feat)
