@@ -629,6 +629,47 @@ int mmskin_sweep_reduce(const void* logits, int logits_dtype, const float* base,
                         int32_t* confusion, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The criterion (csrc/criterion.hip): one forward and one backward launch for three kinds of loss on logits [B][C], row-major,
+ * fp32 (logits_dtype 0) or bf16 (1); all arithmetic fp32.  1 <= B <= 2^20, 2 <= C <= 1024.  With m = max z_i,
+ * ls = ln sum exp(z_i - m), ce = ls - (z_i[y] - m), p = softmax(z_i):
+ *   CE     torch nn.CrossEntropyLoss(weight=w)     row value w[y] ce;  `mean` = sum w[y] ce / sum w[y] over the valid rows
+ *   FOCAL  the reference's models/focalLoss.py     row value (1 - pt)^gamma (alpha[y] ce), pt = exp(-ce), 1 - pt formed as
+ *                                                  -expm1(-ce);  `mean` = the plain mean over B.  gamma is 0 (then the factor is
+ *                                                  skipped: the result IS CE, bit for bit) or >= 1
+ *   SOFT   models/softtargetsCrossEntropy.py       row value -sum_c t[c] (z[c] - m - ls) w[c], targets fp32 [B][C]; `mean` over
+ *                                                  B only, as the reference
+ * targets: int64 [B] labels (CE, FOCAL), read in place and never inspected on the host: a label outside [0, C) -- torch's
+ * ignore_index -100 included -- gives no loss, no gradient and does not count in CE's `mean` (all rows ignored: nan, as torch).
+ * weight: fp32 [C] (w / alpha) or NULL for all ones.  loss: fp32, one value, or [B] for MMSKIN_REDUCE_NONE.  loss is fp32 also
+ * for bf16 logits.
+ * scratch: mmskin_criterion_scratch_floats(B, C, kind) floats (-1 for a shape out of range), not initialised by the caller.
+ * The forward leaves the rows' (m, ls), the per-workgroup partial sums and the divisor of `mean` there; the backward reads
+ * them, so the buffer lives until the backward has run.  ticket: one int32 that is ZERO before the first call and that the
+ * kernel leaves zero; calls that share it must be ordered on one stream.  The batch reduction has a fixed order (64-row
+ * partials, then a tree in the workgroup that arrives last): forward and backward are bitwise repeatable.
+ * meter (optional): a caller-zeroed block { double loss_sum; int64 rows; int32 confusion[C][C]; }.  The forward adds, from one
+ * thread after the reduction, rows = the valid rows of the batch (SOFT: B) and loss_sum = rows x the batch's `mean` loss --
+ * the sum of the row values, except for CE under class weights -- whatever `reduction` is; and with labels it adds 1 to
+ * confusion[y][first arg-max of the logits] per valid row (integer atomics).  probs_out (optional) fp32 [B][C]: the soft-max.
+ * backward: dloss is one device float, or [B] for MMSKIN_REDUCE_NONE; dlogits [B][C] in the logits' dtype, every element
+ * written:  CE g w[y] (p_j - [j = y]) with g = dloss / sum w[y] for `mean`;  FOCAL g alpha[y] (gamma (1 - pt)^(gamma - 1) pt ce
+ * + (1 - pt)^gamma) (p_j - [j = y]), g = dloss / B for `mean`;  SOFT (dloss / B) (p_j sum_c t[c] w[c] - t[j] w[j]).  targets
+ * and weight get no gradient.  Errors (MMSKIN_ERR_ARG, nothing launched, no GPU needed): B or C out of range, an unknown dtype,
+ * kind or reduction, SOFT with a reduction other than `mean`, FOCAL with 0 < gamma < 1 or gamma < 0, a null argument. */
+#define MMSKIN_CRITERION_CE 0
+#define MMSKIN_CRITERION_FOCAL 1
+#define MMSKIN_CRITERION_SOFT 2
+#define MMSKIN_REDUCE_NONE 0
+#define MMSKIN_REDUCE_SUM 1
+#define MMSKIN_REDUCE_MEAN 2
+int64_t mmskin_criterion_scratch_floats(int B, int C, int kind);
+int mmskin_criterion_forward(const void* logits, int logits_dtype, const void* targets, const float* weight, int kind, int reduction,
+                             float gamma, int B, int C, float* loss, float* scratch, int32_t* ticket, void* meter, float* probs_out,
+                             void* stream);
+int mmskin_criterion_backward(const void* logits, int logits_dtype, const void* targets, const float* weight, int kind, int reduction,
+                              float gamma, int B, int C, const float* dloss, const float* scratch, void* dlogits, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * `custom-cnn` image encoder pieces (loadImageModelClassifier.py:50-60): small direct kernels for
  * shapes the MFMA implicit GEMM does not cover (Cin=3, Cout=16).  NCHW fp32. */
 int mmskin_direct_conv2d_forward(const float* x, const float* w, const float* b, float* y, int N, int Cin, int H, int W,

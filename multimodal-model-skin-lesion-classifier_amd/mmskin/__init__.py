@@ -5,6 +5,7 @@ Layout:
   mmskin/    ctypes binding, autograd wrappers, parameter-holder modules, DP helper
   models/    drop-in modules with the reference's file / class names
 """
-from . import _lib  # noqa: F401
+from . import _lib, criterion  # noqa: F401
+from .criterion import CrossEntropyLoss, EpochMeter, FocalLoss, SoftTargetCrossEntropy  # noqa: F401
 
-__all__ = ["_lib"]
+__all__ = ["_lib", "criterion", "CrossEntropyLoss", "FocalLoss", "SoftTargetCrossEntropy", "EpochMeter"]

@@ -165,7 +165,10 @@ _SIGNATURES = {
     "mmskin_scorecam_combine": (_i, [_P] * 3 + [_i] * 6 + [_P, _P]),
     "mmskin_metadata_variants": (_i, [_P, _i, _P, _P, _i, _P, _i, _P, _P, _f, _P, _P, _i, _P, _P, _P, _i, _i, _P]),
     "mmskin_sweep_reduce": (_i, [_P, _i, _P, _P, _i, _i, _i] + [_P] * 7 + [_P]),
-    "mmskin_pool_gap_forward": (_i, [_P] * 3 + [_i] * 5 + [_P]),
+    "mmskin_criterion_scratch_floats": (_i64, [_i, _i, _i]),
+    "mmskin_criterion_forward": (_i, [_P, _i, _P, _P, _i, _i, _f, _i, _i] + [_P] * 6),
+    "mmskin_criterion_backward": (_i, [_P, _i, _P, _P, _i, _i, _f, _i, _i] + [_P] * 4),
+    "mmskin_pool_gap_forward":(_i, [_P] * 3 + [_i] * 5 + [_P]),
     "mmskin_pool_gap_backward": (_i, [_P] * 3 + [_i] * 5 + [_P]),
     "mmskin_star_relu_forward_bf16": (_i, [_P] * 4 + [_i64, _i, _i, _P]),
     "mmskin_linear_star_relu_backward_keep": (_i, [_P] * 9 + [_i] * 3 + [_P]),
