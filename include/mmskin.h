@@ -197,6 +197,46 @@ int64_t mmskin_sd_workspace_bytes(int N, int64_t per_sample);
 int mmskin_sd_forward(const float* branch, const float* res, const float* mask, float* y, int N, int64_t per_sample, int dtype,
                       void* workspace, void* stream);
 int mmskin_sd_backward(const float* dy, const float* mask, float* out, int N, int64_t per_sample, int dtype, void* workspace, void* stream);
+/* DenseNet / VGG plan kernels, op by op (csrc/densenet.hip, csrc/vgg.hip): the same conventions (NCHW fp32 at the boundary, NHWC `dtype`
+ * inside the caller's workspace).  The dense-block and transition entries run the functions the plan runs; their backward entries run the
+ * training forward first, so they take the forward's inputs.
+ * Dense block of L layers (growth 32, bottleneck 128) on x [N,C0,H,W], C0 a multiple of 32.  params (mmskin_dense_block_param_numel floats),
+ * per layer in torchvision order: norm1.weight | norm1.bias [Cin], conv1.weight [128,Cin], norm2.weight | norm2.bias [128],
+ * conv2.weight [32,128,3,3], Cin = C0 + 32 i.  buffers per layer: norm1.running_mean | running_var [Cin], norm2.running_mean |
+ * running_var [128] (training: updated; eval: read, norm2 folded into conv1).  cat [N,C0+32L,H,W]; table (training, may be null):
+ * mean [C0+32L] | biased var [C0+32L] of every cat channel.  Backward: dcat [N,C0+32L,H,W] -> dx [N,C0,H,W], grads laid out as params. */
+int64_t mmskin_dense_block_workspace_bytes(int N, int C0, int L, int H, int W);
+int64_t mmskin_dense_block_param_numel(int C0, int L);
+int mmskin_dense_block_forward(const float* x, const float* params, float* buffers, float* cat, float* table, int N, int C0, int L, int H, int W,
+                               int training, int dtype, void* workspace, void* stream);
+int mmskin_dense_block_backward(const float* dcat, const float* x, const float* params, float* dx, float* grads, int N, int C0, int L, int H,
+                                int W, int dtype, void* workspace, void* stream);
+/* Transition norm -> ReLU -> conv1x1 (C -> C/2) -> avgpool 2x2 of x [N,C,H,W] (C a multiple of 128, H, W >= 2) with the block's table
+ * (mean [C] | var [C]) into the first C/2 channels of dst [N,Cdst,H/2,W/2] (Cdst >= C/2, a multiple of 8; the other channels are kept).
+ * params: norm.weight | norm.bias [C], conv.weight [C/2,C]; buffers: running_mean | running_var [C]; conv_out (may be null) [N,C/2,H,W]:
+ * the stored convolution output the pool read.  Backward: dnext [N,Cdst,H/2,W/2]
+ * (the next block's gradient; channels >= C/2 are not read) -> dx [N,C,H,W], grads laid out as params; dconv_out (may be null)
+ * [N,C/2,H,W]: the gradient of the convolution output as the un-pooling kernel stored it. */
+int64_t mmskin_dense_transition_workspace_bytes(int N, int C, int H, int W, int Cdst);
+int mmskin_dense_transition_forward(const float* x, const float* table, const float* params, float* buffers, float* dst, float* conv_out, int N,
+                                    int C, int H, int W, int Cdst, int training, int dtype, void* workspace, void* stream);
+int mmskin_dense_transition_backward(const float* dnext, const float* x, const float* table, const float* params, float* dx, float* grads,
+                                     float* dconv_out, int N, int C, int H, int W, int Cdst, int dtype, void* workspace, void* stream);
+/* mean and biased variance of channels [c0, c0+C) of x [rows][pitch] (slice_stats + bn_table_finalize); C, c0, pitch multiples of 8 */
+int64_t mmskin_slice_stats_workspace_bytes(int64_t rows, int pitch, int c0, int C);
+int mmskin_slice_stats(const float* x, int64_t rows, int pitch, int c0, int C, float* mean, float* var, int dtype, void* workspace, void* stream);
+/* VGG: 2x2 / stride 2 max-pool (floor) of a post-ReLU map y [N,C,H,W] (C a multiple of 8, H, W >= 2): pooled [N,C,H/2,W/2] and idx, the
+ * argmax tap 0..3 (first maximum, row-major in the window) as bytes in the kernel's layout [N,H/2,W/2,C].  Backward: dz [N,C,H,W] =
+ * dpool at each window's argmax where y > 0, else 0. */
+int64_t mmskin_maxpool2_relu_workspace_bytes(int N, int C, int H, int W);
+int mmskin_maxpool2_relu_forward(const float* y, float* pooled, unsigned char* idx, int N, int C, int H, int W, int dtype, void* workspace,
+                                 void* stream);
+int mmskin_maxpool2_relu_backward(const float* dpool, const float* y, float* dz, int N, int C, int H, int W, int dtype, void* workspace,
+                                  void* stream);
+/* VGG: AdaptiveAvgPool2d(7) of x [N,C,H,W] -> out [N,C,7,7] (fp32), and dout [N,C,7,7] -> dx [N,C,H,W] */
+int64_t mmskin_adaptive_avgpool_workspace_bytes(int N, int C, int H, int W);
+int mmskin_adaptive_avgpool_forward(const float* x, float* out, int N, int C, int H, int W, int dtype, void* workspace, void* stream);
+int mmskin_adaptive_avgpool_backward(const float* dout, float* dx, int N, int C, int H, int W, int dtype, void* workspace, void* stream);
 /* the ResNet stem: conv7x7/2 (OIHW [64,3,7,7]) -> BN(train) -> ReLU -> maxpool3x3/2; y [N,64,PH,PW] */
 int64_t mmskin_stem_workspace_bytes(int N, int H, int W);
 int mmskin_stem_forward(const float* x, const float* w, const float* gamma, const float* beta, float* y, int N, int H,

@@ -453,6 +453,312 @@ struct GramStatsWs {
   }
 };
 
+// ---- DenseNet / VGG plan kernels, op by op (densenet.hip's block and transition bodies, vgg.hip's pools)
+// several stage descriptors at once (the table lives in the workspace; the host copy must outlive the transfer)
+inline int upload_table(const std::vector<StageDesc>& host, StageDesc* dev, hipStream_t st) {
+  HIP_CHECK_RET(hipMemcpyAsync(dev, host.data(), host.size() * sizeof(StageDesc), hipMemcpyHostToDevice, st));
+  HIP_CHECK_RET(hipStreamSynchronize(st));
+  return MMSKIN_OK;
+}
+
+// One dense block of L layers on its own: the plan's DBlock with offsets into this carve.  Flat parameters per layer, torchvision order:
+// norm1.weight | norm1.bias [Cin], conv1.weight [128][Cin], norm2.weight | norm2.bias [128], conv2.weight [32][128][3][3]; flat buffers
+// per layer: norm1.running_mean | running_var [Cin], norm2.running_mean | running_var [128].  es: element size of the compute dtype.
+struct DenseBlockWs {
+  DBlock b;
+  std::vector<StageDesc> table;
+  int max_stage_elems = 0;
+  int64_t param_numel = 0, buffer_numel = 0, wf_elems = 0;
+  size_t table_off, xh_off, wf_off, wd_off, stat_off, stat_bytes, partial_off, coefbwd_off, defer_off, red_off, slab_off, sB_off[2], sU_off,
+      sA_off[2], sZ_off, rbuf_off, total;
+  DenseBlockWs(int N, int C0, int L, int H, int W, size_t es) {
+    b.H = H; b.W = W; b.C0 = C0; b.Ctot = C0 + DENSE_GROWTH * L; b.rows = (size_t)N * H * W;
+    auto bn = [&](int C) {
+      BNRef r;
+      r.g_off = param_numel; r.b_off = param_numel + C; param_numel += 2 * C;
+      r.rm_off = buffer_numel; r.rv_off = buffer_numel + C; buffer_numel += 2 * C;
+      return r;
+    };
+    int64_t wf = 0, wd = 0;
+    for (int i = 0; i < L; ++i) {
+      DLayer l = {};
+      dense_layer_geom(l, C0, i);
+      l.n1 = bn(l.Cin);
+      l.w1_off = param_numel; param_numel += (int64_t)DENSE_BOTTLE * l.Cin;
+      l.n2 = bn(DENSE_BOTTLE);
+      l.w2_off = param_numel; param_numel += (int64_t)DENSE_GROWTH * DENSE_BOTTLE * 9;
+      dense_stage_layer(l, table, wf, wd, max_stage_elems);
+      b.layers.push_back(l);
+    }
+    wf_elems = wf;
+    size_t cur = 0;
+    table_off = carve(cur, table.size() * sizeof(StageDesc));
+    xh_off = carve(cur, b.rows * C0 * es);
+    wf_off = carve(cur, (size_t)wf * es);
+    wd_off = carve(cur, (size_t)wf * es);
+    b.cat_off = carve(cur, b.rows * b.Ctot * es);
+    b.dcat_off = carve(cur, b.rows * b.Ctot * es);
+    b.tab_off = carve(cur, 2 * (size_t)b.Ctot * sizeof(float));
+    size_t stat_floats = (size_t)column_stats_rows(b.rows, C0) * 2 * C0, partial = 0, slab = 0, big = b.rows * b.Ctot;
+    int maxC = std::max(DENSE_BOTTLE, b.Ctot);
+    for (DLayer& l : b.layers) {
+      l.t_off = carve(cur, b.rows * l.Cp * es);
+      l.a_off = carve(cur, b.rows * DENSE_BOTTLE * es);
+      l.u_off = carve(cur, b.rows * DENSE_BOTTLE * es);
+      l.coef1_off = carve(cur, 5 * (size_t)l.Cp * sizeof(float));
+      l.coef2_off = carve(cur, 4 * (size_t)DENSE_BOTTLE * sizeof(float));
+      dense_fold_norm2(l, table);
+      dense_layer_needs(N, H, W, b.rows, l, stat_floats, partial, slab);
+      big = std::max(big, b.rows * l.Cp);
+      maxC = std::max(maxC, l.Cp);
+    }
+    stat_bytes = align_up(stat_floats * sizeof(float), 256);
+    stat_off = carve(cur, 2 * stat_bytes);
+    partial_off = carve(cur, partial);
+    coefbwd_off = carve(cur, 3 * (size_t)maxC * sizeof(float));
+    defer_off = carve(cur, 2 * (size_t)maxC * sizeof(float));
+    red_off = carve(cur, bn_reduce_scratch_bytes(maxC));
+    slab_off = carve(cur, slab);
+    for (int q = 0; q < 2; ++q) sB_off[q] = carve(cur, b.rows * DENSE_G_PAD * es);
+    sU_off = carve(cur, b.rows * DENSE_BOTTLE * es);
+    for (int q = 0; q < 2; ++q) sA_off[q] = carve(cur, b.rows * DENSE_BOTTLE * es);
+    sZ_off = carve(cur, big * es);
+    rbuf_off = carve(cur, (size_t)buffer_numel * sizeof(float));   // the backward entry's forward pass updates these, not the caller's
+    total = cur;
+  }
+  template <typename T>
+  DenseRun<T> run(int N, unsigned char* ws, const float* params, float* buffers, float* grads) const {
+    DenseRun<T> r;
+    r.N = N; r.ws = ws; r.params = params; r.buffers = buffers; r.grads = grads;
+    r.wf = reinterpret_cast<T*>(ws + wf_off); r.wd = reinterpret_cast<T*>(ws + wd_off);
+    r.stat_sum = reinterpret_cast<float*>(ws + stat_off); r.stat_sq = reinterpret_cast<float*>(ws + stat_off + stat_bytes);
+    r.red = reinterpret_cast<double*>(ws + red_off);
+    for (int q = 0; q < 2; ++q) { r.sBq[q] = reinterpret_cast<T*>(ws + sB_off[q]); r.sAq[q] = reinterpret_cast<T*>(ws + sA_off[q]); }
+    r.sU = reinterpret_cast<T*>(ws + sU_off); r.sZ = reinterpret_cast<T*>(ws + sZ_off);
+    r.slab = reinterpret_cast<float*>(ws + slab_off); r.partial = reinterpret_cast<float*>(ws + partial_off);
+    r.cA = reinterpret_cast<float*>(ws + coefbwd_off); r.defer = reinterpret_cast<float*>(ws + defer_off);
+    return r;
+  }
+};
+
+// x -> cat prefix, staged weights, the input slice's statistics, then the plan's block body
+template <typename T>
+int dense_block_fwd_core(DenseBlockWs& w, DenseRun<T>& r, const float* x, int N, bool training, hipStream_t st) {
+  unsigned char* ws = r.ws;
+  DBlock& b = w.b;
+  StageDesc* table = reinterpret_cast<StageDesc*>(ws + w.table_off);
+  T* xh = reinterpret_cast<T*>(ws + w.xh_off);
+  int rc;
+  if ((rc = upload_table(w.table, table, st))) return rc;
+  if ((rc = nchw_to_nhwc<T>(x, N, b.C0, b.H, b.W, xh, st))) return rc;
+  if ((rc = slice_scatter<T>(xh, b.C0, b.C0, reinterpret_cast<T*>(ws + b.cat_off), b.Ctot, b.rows, st))) return rc;
+  if ((rc = stage_weights<T>(table, (int)w.table.size(), w.max_stage_elems, r.params, r.wf, r.wd, training, st, training ? nullptr : r.buffers, 1e-5f))) return rc;
+  if (!training && (rc = bn_eval_table(table, (int)w.table.size(), DENSE_BOTTLE, r.params, r.buffers, ws, 1e-5f, st))) return rc;
+  if (training && (rc = dense_table_from_slice<T>(r, b, 0, b.C0, st))) return rc;
+  return dense_block_forward<T>(r, b, training, st);
+}
+template <typename T>
+int dense_block_fwd_op(const float* x, const float* params, float* buffers, float* cat, float* table_out, int N, int C0, int L, int H, int W,
+                       bool training, void* wsp, hipStream_t st) {
+  DenseBlockWs w(N, C0, L, H, W, sizeof(T));
+  unsigned char* ws = (unsigned char*)wsp;
+  DenseRun<T> r = w.run<T>(N, ws, params, buffers, nullptr);
+  int rc;
+  if ((rc = dense_block_fwd_core<T>(w, r, x, N, training, st))) return rc;
+  if (training && table_out) HIP_CHECK_RET(hipMemcpyAsync(table_out, ws + w.b.tab_off, 2 * (size_t)w.b.Ctot * sizeof(float), hipMemcpyDeviceToDevice, st));
+  return nhwc_to_nchw<T>(reinterpret_cast<const T*>(ws + w.b.cat_off), N, w.b.Ctot, H, W, cat, st);
+}
+template <typename T>
+int dense_block_bwd_op(const float* dcat, const float* x, const float* params, float* dx, float* grads, int N, int C0, int L, int H, int W,
+                       void* wsp, hipStream_t st) {
+  DenseBlockWs w(N, C0, L, H, W, sizeof(T));
+  unsigned char* ws = (unsigned char*)wsp;
+  float* rbuf = reinterpret_cast<float*>(ws + w.rbuf_off);
+  DenseRun<T> r = w.run<T>(N, ws, params, rbuf, grads);
+  int rc;
+  HIP_CHECK_RET(hipMemsetAsync(rbuf, 0, (size_t)w.buffer_numel * sizeof(float), st));
+  if ((rc = dense_block_fwd_core<T>(w, r, x, N, true, st))) return rc;   // the activations and coefficients backward reads
+  T* dc = reinterpret_cast<T*>(ws + w.b.dcat_off);
+  T* xh = reinterpret_cast<T*>(ws + w.xh_off);
+  if ((rc = nchw_to_nhwc<T>(dcat, N, w.b.Ctot, H, W, dc, st))) return rc;
+  if ((rc = dense_block_backward<T>(r, w.b, st))) return rc;
+  if ((rc = slice_pack<T>(dc, w.b.Ctot, C0, C0, w.b.rows, nullptr, nullptr, xh, st))) return rc;
+  return nhwc_to_nchw<T>(xh, N, C0, H, W, dx, st);
+}
+
+// One transition on its own: block geometry with Ctot = C (the transition reads the whole concatenated activation).  Flat parameters:
+// norm.weight | norm.bias [C], conv.weight [C/2][C]; flat buffers: running_mean | running_var [C].
+struct DenseTransWs {
+  DBlock b;
+  DTrans t;
+  StageDesc desc;
+  int PH, PW;
+  size_t table_off, wf_off, wd_off, sC_off, dst_off, sZ_off, partial_off, coefbwd_off, red_off, slab_off, rbuf_off, total;
+  DenseTransWs(int N, int C, int H, int W, int Cdst, size_t es) {
+    b.H = H; b.W = W; b.C0 = C; b.Ctot = C; b.rows = (size_t)N * H * W;
+    PH = H / 2; PW = W / 2;
+    t = DTrans();
+    t.C = C;
+    t.n.g_off = 0; t.n.b_off = C; t.n.rm_off = 0; t.n.rv_off = C;
+    t.w_off = 2 * (int64_t)C; t.wf = 0; t.wd = 0;
+    {
+      std::vector<StageDesc> one;
+      int64_t wf = 0, wd = 0;
+      int max_elems = 0;
+      dense_stage(one, t.w_off, C / 2, C, 1, C / 2, C, wf, wd, max_elems, t.wf, t.wd);   // as build_dense_plan stages a transition
+      desc = one[0];
+    }
+    const ConvShape ct = {N, H, W, C, C / 2, 1, 1, 1, 0};
+    size_t cur = 0;
+    table_off = carve(cur, sizeof(StageDesc));
+    wf_off = carve(cur, (size_t)C / 2 * C * es);
+    wd_off = carve(cur, (size_t)C / 2 * C * es);
+    b.cat_off = carve(cur, b.rows * C * es);
+    b.dcat_off = carve(cur, b.rows * C * es);
+    b.tab_off = carve(cur, 2 * (size_t)C * sizeof(float));
+    t.tt_off = carve(cur, b.rows * C * es);
+    t.coef_off = carve(cur, 5 * (size_t)C * sizeof(float));
+    sC_off = carve(cur, b.rows * (C / 2) * es);
+    dst_off = carve(cur, (size_t)N * PH * PW * Cdst * es);
+    sZ_off = carve(cur, b.rows * C * es);
+    partial_off = carve(cur, dense_partial_bytes(b.rows, C));
+    coefbwd_off = carve(cur, 3 * (size_t)C * sizeof(float));
+    red_off = carve(cur, bn_reduce_scratch_bytes(C));
+    slab_off = carve(cur, conv_wgrad_slab_bytes(ct));
+    rbuf_off = carve(cur, 2 * (size_t)C * sizeof(float));
+    total = cur;
+  }
+  template <typename T>
+  DenseRun<T> run(int N, unsigned char* ws, const float* params, float* buffers, float* grads) const {
+    DenseRun<T> r;
+    r.N = N; r.ws = ws; r.params = params; r.buffers = buffers; r.grads = grads;
+    r.wf = reinterpret_cast<T*>(ws + wf_off); r.wd = reinterpret_cast<T*>(ws + wd_off);
+    r.red = reinterpret_cast<double*>(ws + red_off);
+    r.sZ = reinterpret_cast<T*>(ws + sZ_off); r.sC = reinterpret_cast<T*>(ws + sC_off);
+    r.slab = reinterpret_cast<float*>(ws + slab_off); r.partial = reinterpret_cast<float*>(ws + partial_off);
+    r.cA = reinterpret_cast<float*>(ws + coefbwd_off);
+    return r;
+  }
+};
+// x and the block's table into the carve, staged weight, the caller's destination rows, then the plan's transition body
+template <typename T>
+int dense_trans_fwd_core(DenseTransWs& w, DenseRun<T>& r, const float* x, const float* table, const float* dst_in, int N, int Cdst, bool training,
+                         hipStream_t st) {
+  unsigned char* ws = r.ws;
+  StageDesc* tdev = reinterpret_cast<StageDesc*>(ws + w.table_off);
+  T* dst = reinterpret_cast<T*>(ws + w.dst_off);
+  int rc;
+  HIP_CHECK_RET(hipMemcpyAsync(tdev, &w.desc, sizeof(StageDesc), hipMemcpyHostToDevice, st));
+  HIP_CHECK_RET(hipStreamSynchronize(st));
+  HIP_CHECK_RET(hipMemcpyAsync(ws + w.b.tab_off, table, 2 * (size_t)w.t.C * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if ((rc = nchw_to_nhwc<T>(x, N, w.t.C, w.b.H, w.b.W, reinterpret_cast<T*>(ws + w.b.cat_off), st))) return rc;
+  if (dst_in && (rc = nchw_to_nhwc<T>(dst_in, N, Cdst, w.PH, w.PW, dst, st))) return rc;
+  if ((rc = stage_weights<T>(tdev, 1, w.t.C / 2 * w.t.C, r.params, r.wf, r.wd, true, st))) return rc;
+  return dense_transition_forward<T>(r, w.b, w.t, dst, Cdst, training, st);
+}
+template <typename T>
+int dense_trans_fwd_op(const float* x, const float* table, const float* params, float* buffers, float* dst, float* conv_out, int N, int C, int H,
+                       int W, int Cdst, bool training, void* wsp, hipStream_t st) {
+  DenseTransWs w(N, C, H, W, Cdst, sizeof(T));
+  unsigned char* ws = (unsigned char*)wsp;
+  DenseRun<T> r = w.run<T>(N, ws, params, buffers, nullptr);
+  int rc;
+  if ((rc = dense_trans_fwd_core<T>(w, r, x, table, dst, N, Cdst, training, st))) return rc;
+  if (conv_out && (rc = nhwc_to_nchw<T>(r.sC, N, C / 2, H, W, conv_out, st))) return rc;   // the stored conv output the pool read
+  return nhwc_to_nchw<T>(reinterpret_cast<const T*>(ws + w.dst_off), N, Cdst, w.PH, w.PW, dst, st);
+}
+template <typename T>
+int dense_trans_bwd_op(const float* dnext, const float* x, const float* table, const float* params, float* dx, float* grads, float* dconv_out,
+                       int N, int C, int H, int W, int Cdst, void* wsp, hipStream_t st) {
+  DenseTransWs w(N, C, H, W, Cdst, sizeof(T));
+  unsigned char* ws = (unsigned char*)wsp;
+  float* rbuf = reinterpret_cast<float*>(ws + w.rbuf_off);
+  DenseRun<T> r = w.run<T>(N, ws, params, rbuf, grads);
+  T* dst = reinterpret_cast<T*>(ws + w.dst_off);
+  int rc;
+  HIP_CHECK_RET(hipMemsetAsync(rbuf, 0, 2 * (size_t)C * sizeof(float), st));
+  if ((rc = dense_trans_fwd_core<T>(w, r, x, table, nullptr, N, Cdst, true, st))) return rc;   // tt and the coefficients backward reads
+  if ((rc = nchw_to_nhwc<T>(dnext, N, Cdst, w.PH, w.PW, dst, st))) return rc;                  // the next block's dcat, pitch Cdst
+  if ((rc = dense_transition_backward<T>(r, w.b, w.t, dst, Cdst, st))) return rc;
+  if (dconv_out && (rc = nhwc_to_nchw<T>(r.sC, N, C / 2, H, W, dconv_out, st))) return rc;   // what avgpool2_bwd stored: the conv output's gradient
+  return nhwc_to_nchw<T>(reinterpret_cast<const T*>(ws + w.b.dcat_off), N, C, H, W, dx, st);
+}
+
+// slice_stats + bn_table_finalize on channels [c0, c0 + C) of a [rows][pitch] matrix (table_from_slice's pair)
+template <typename T>
+struct SliceStatsWs {
+  T* xh; float* stat; double* red; size_t total;
+  SliceStatsWs(void* ws, int64_t rows, int pitch, int C) {
+    Carver c(ws);
+    xh = c.take<T>((size_t)rows * pitch);
+    stat = c.take<float>((size_t)column_stats_rows((size_t)rows, C) * 2 * C);
+    red = c.take<double>(bn_reduce_scratch_bytes(C) / sizeof(double));
+    total = c.cur;
+  }
+};
+template <typename T>
+int slice_stats_op(const float* x, int64_t rows, int pitch, int c0, int C, float* mean, float* var, void* ws, hipStream_t st) {
+  SliceStatsWs<T> s(ws, rows, pitch, C);
+  int rc, nr = 0;
+  if ((rc = nchw_to_nhwc<T>(x, (int)rows, pitch, 1, 1, s.xh, st))) return rc;
+  if ((rc = slice_stats<T>(s.xh + c0, pitch, C, (size_t)rows, s.stat, s.stat + C, &nr, st))) return rc;
+  return bn_table_finalize(s.stat, s.stat + C, nr, 2 * C, C, (double)rows, mean, var, s.red, st);
+}
+
+// VGG: 2x2 max-pool of a post-ReLU map with its argmax bytes, and the fused un-pool + ReLU mask
+template <typename T>
+struct MaxpoolWs {
+  T *yh, *ph, *dph, *dzh; uint8_t* idx; size_t total; int PH, PW;
+  MaxpoolWs(void* ws, int N, int C, int H, int W) {
+    PH = H / 2; PW = W / 2;
+    Carver c(ws);
+    const size_t rows = (size_t)N * H * W, prows = (size_t)N * PH * PW;
+    yh = c.take<T>(rows * C); ph = c.take<T>(prows * C); idx = c.take<uint8_t>(prows * C);
+    dph = c.take<T>(prows * C); dzh = c.take<T>(rows * C);
+    total = c.cur;
+  }
+};
+template <typename T>
+int maxpool_fwd_op(const float* y, float* pooled, uint8_t* idx, int N, int C, int H, int W, void* ws, hipStream_t st) {
+  MaxpoolWs<T> s(ws, N, C, H, W);
+  int rc;
+  if ((rc = nchw_to_nhwc<T>(y, N, C, H, W, s.yh, st))) return rc;
+  if ((rc = maxpool2_fwd<T>(s.yh, N, H, W, C, s.ph, s.idx, st))) return rc;
+  if (idx) HIP_CHECK_RET(hipMemcpyAsync(idx, s.idx, (size_t)N * s.PH * s.PW * C, hipMemcpyDeviceToDevice, st));
+  return pooled ? nhwc_to_nchw<T>(s.ph, N, C, s.PH, s.PW, pooled, st) : MMSKIN_OK;
+}
+template <typename T>
+int maxpool_bwd_op(const float* dpool, const float* y, float* dz, int N, int C, int H, int W, void* ws, hipStream_t st) {
+  MaxpoolWs<T> s(ws, N, C, H, W);
+  int rc;
+  if ((rc = maxpool_fwd_op<T>(y, nullptr, nullptr, N, C, H, W, ws, st))) return rc;   // the argmax bytes backward reads
+  if ((rc = nchw_to_nhwc<T>(dpool, N, C, s.PH, s.PW, s.dph, st))) return rc;
+  if ((rc = maxpool2_bwd_relu<T>(s.dph, s.idx, s.yh, N, H, W, C, s.dzh, st))) return rc;
+  return nhwc_to_nchw<T>(s.dzh, N, C, H, W, dz, st);
+}
+
+template <typename T>
+struct AdaptivePoolWs {
+  T *xh, *dxh; size_t total;
+  AdaptivePoolWs(void* ws, int N, int C, int H, int W) {
+    Carver c(ws);
+    xh = c.take<T>((size_t)N * H * W * C); dxh = c.take<T>((size_t)N * H * W * C);
+    total = c.cur;
+  }
+};
+template <typename T>
+int adaptive_fwd_op(const float* x, float* out, int N, int C, int H, int W, void* ws, hipStream_t st) {
+  AdaptivePoolWs<T> s(ws, N, C, H, W);
+  if (int rc = nchw_to_nhwc<T>(x, N, C, H, W, s.xh, st)) return rc;
+  return adaptive_avgpool_fwd<T>(s.xh, N, H, W, C, 7, 7, out, st);
+}
+template <typename T>
+int adaptive_bwd_op(const float* dout, float* dx, int N, int C, int H, int W, void* ws, hipStream_t st) {
+  AdaptivePoolWs<T> s(ws, N, C, H, W);
+  if (int rc = adaptive_avgpool_bwd<T>(dout, N, H, W, C, 7, 7, s.dxh, st)) return rc;
+  return nhwc_to_nchw<T>(s.dxh, N, C, H, W, dx, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -775,5 +1081,107 @@ int mmskin_sd_backward(const float* dy, const float* mask, float* out, int N, in
   hipStream_t st = (hipStream_t)stream;
   DISPATCH(dtype, sd_op<float>(dy, nullptr, mask, out, N, per_sample, workspace, st), sd_op<bf16_t>(dy, nullptr, mask, out, N, per_sample, workspace, st));
 }
+
+/* ---- DenseNet / VGG plan kernels, op by op (csrc/densenet.hip, csrc/vgg.hip).  Same conventions as the MBConv entries; the dense-block
+ * and transition entries call the functions the plan calls (dense_block_forward / _backward, dense_transition_forward / _backward), with
+ * the weight-gradient GEMMs on the caller's stream as in a profiled plan run.  The backward entries run the training forward first. */
+#define DENSE_BLOCK_OK (N > 0 && C0 > 0 && C0 % 32 == 0 && L >= 1 && L <= 64 && H > 0 && W > 0)
+int64_t mmskin_dense_block_workspace_bytes(int N, int C0, int L, int H, int W) {
+  if (!DENSE_BLOCK_OK) return -1;
+  return (int64_t)DenseBlockWs(N, C0, L, H, W, sizeof(float)).total;
+}
+int64_t mmskin_dense_block_param_numel(int C0, int L) {
+  if (!(C0 > 0 && C0 % 32 == 0 && L >= 1 && L <= 64)) return -1;
+  return DenseBlockWs(1, C0, L, 1, 1, sizeof(float)).param_numel;
+}
+int mmskin_dense_block_forward(const float* x, const float* params, float* buffers, float* cat, float* table, int N, int C0, int L, int H, int W,
+                               int training, int dtype, void* workspace, void* stream) {
+  ARG_CHECK(x && params && buffers && cat && workspace && DENSE_BLOCK_OK, "dense_block_forward: bad argument (C0 = %d must be a multiple of 32)", C0);
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype, dense_block_fwd_op<float>(x, params, buffers, cat, table, N, C0, L, H, W, training != 0, workspace, st),
+           dense_block_fwd_op<bf16_t>(x, params, buffers, cat, table, N, C0, L, H, W, training != 0, workspace, st));
+}
+int mmskin_dense_block_backward(const float* dcat, const float* x, const float* params, float* dx, float* grads, int N, int C0, int L, int H,
+                                int W, int dtype, void* workspace, void* stream) {
+  ARG_CHECK(dcat && x && params && dx && grads && workspace && DENSE_BLOCK_OK, "dense_block_backward: bad argument (C0 = %d must be a multiple of 32)", C0);
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype, dense_block_bwd_op<float>(dcat, x, params, dx, grads, N, C0, L, H, W, workspace, st),
+           dense_block_bwd_op<bf16_t>(dcat, x, params, dx, grads, N, C0, L, H, W, workspace, st));
+}
+#undef DENSE_BLOCK_OK
+
+#define DENSE_TRANS_OK (N > 0 && C > 0 && C % 128 == 0 && H >= 2 && W >= 2 && Cdst >= C / 2 && Cdst % 8 == 0)
+int64_t mmskin_dense_transition_workspace_bytes(int N, int C, int H, int W, int Cdst) {
+  if (!DENSE_TRANS_OK) return -1;
+  return (int64_t)DenseTransWs(N, C, H, W, Cdst, sizeof(float)).total;
+}
+int mmskin_dense_transition_forward(const float* x, const float* table, const float* params, float* buffers, float* dst, float* conv_out, int N,
+                                    int C, int H, int W, int Cdst, int training, int dtype, void* workspace, void* stream) {
+  ARG_CHECK(x && table && params && buffers && dst && workspace && DENSE_TRANS_OK,
+            "dense_transition_forward: bad argument (C = %d a multiple of 128, map %dx%d at least 2x2, pitch %d >= C/2)", C, H, W, Cdst);
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype, dense_trans_fwd_op<float>(x, table, params, buffers, dst, conv_out, N, C, H, W, Cdst, training != 0, workspace, st),
+           dense_trans_fwd_op<bf16_t>(x, table, params, buffers, dst, conv_out, N, C, H, W, Cdst, training != 0, workspace, st));
+}
+int mmskin_dense_transition_backward(const float* dnext, const float* x, const float* table, const float* params, float* dx, float* grads,
+                                     float* dconv_out, int N, int C, int H, int W, int Cdst, int dtype, void* workspace, void* stream) {
+  ARG_CHECK(dnext && x && table && params && dx && grads && workspace && DENSE_TRANS_OK,
+            "dense_transition_backward: bad argument (C = %d a multiple of 128, map %dx%d at least 2x2, pitch %d >= C/2)", C, H, W, Cdst);
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype, dense_trans_bwd_op<float>(dnext, x, table, params, dx, grads, dconv_out, N, C, H, W, Cdst, workspace, st),
+           dense_trans_bwd_op<bf16_t>(dnext, x, table, params, dx, grads, dconv_out, N, C, H, W, Cdst, workspace, st));
+}
+#undef DENSE_TRANS_OK
+
+#define SLICE_OK (rows > 0 && rows < (1ll << 31) && rows * pitch < (1ll << 31) && C > 0 && C % 8 == 0 && pitch % 8 == 0 && c0 >= 0 && c0 % 8 == 0 && c0 + C <= pitch)
+int64_t mmskin_slice_stats_workspace_bytes(int64_t rows, int pitch, int c0, int C) {
+  if (!SLICE_OK) return -1;
+  return ws_bytes<SliceStatsWs<float>>(rows, pitch, C);
+}
+int mmskin_slice_stats(const float* x, int64_t rows, int pitch, int c0, int C, float* mean, float* var, int dtype, void* workspace, void* stream) {
+  ARG_CHECK(x && mean && var && workspace && SLICE_OK, "slice_stats: bad argument (C = %d, c0 = %d, pitch = %d: multiples of 8, c0 + C <= pitch)", C, c0, pitch);
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype, slice_stats_op<float>(x, rows, pitch, c0, C, mean, var, workspace, st),
+           slice_stats_op<bf16_t>(x, rows, pitch, c0, C, mean, var, workspace, st));
+}
+#undef SLICE_OK
+
+#define POOL2_OK (N > 0 && C > 0 && C % 8 == 0 && H >= 2 && W >= 2)
+int64_t mmskin_maxpool2_relu_workspace_bytes(int N, int C, int H, int W) {
+  if (!POOL2_OK) return -1;
+  return ws_bytes<MaxpoolWs<float>>(N, C, H, W);
+}
+/* idx: the argmax tap (0..3, row-major inside the window) of every pooled element, in the kernel's layout [N][H/2][W/2][C] */
+int mmskin_maxpool2_relu_forward(const float* y, float* pooled, unsigned char* idx, int N, int C, int H, int W, int dtype, void* workspace,
+                                 void* stream) {
+  ARG_CHECK(y && pooled && idx && workspace && POOL2_OK, "maxpool2_relu_forward: bad argument (C = %d a multiple of 8, map %dx%d at least 2x2)", C, H, W);
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype, maxpool_fwd_op<float>(y, pooled, idx, N, C, H, W, workspace, st), maxpool_fwd_op<bf16_t>(y, pooled, idx, N, C, H, W, workspace, st));
+}
+int mmskin_maxpool2_relu_backward(const float* dpool, const float* y, float* dz, int N, int C, int H, int W, int dtype, void* workspace,
+                                  void* stream) {
+  ARG_CHECK(dpool && y && dz && workspace && POOL2_OK, "maxpool2_relu_backward: bad argument (C = %d a multiple of 8, map %dx%d at least 2x2)", C, H, W);
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype, maxpool_bwd_op<float>(dpool, y, dz, N, C, H, W, workspace, st), maxpool_bwd_op<bf16_t>(dpool, y, dz, N, C, H, W, workspace, st));
+}
+#undef POOL2_OK
+
+#define APOOL_OK (N > 0 && C > 0 && H > 0 && W > 0)
+int64_t mmskin_adaptive_avgpool_workspace_bytes(int N, int C, int H, int W) {
+  if (!APOOL_OK) return -1;
+  return ws_bytes<AdaptivePoolWs<float>>(N, C, H, W);
+}
+/* AdaptiveAvgPool2d(7): x [N][C][H][W] -> out [N][C][7][7] (fp32, as the plan writes its features), and its backward */
+int mmskin_adaptive_avgpool_forward(const float* x, float* out, int N, int C, int H, int W, int dtype, void* workspace, void* stream) {
+  ARG_CHECK(x && out && workspace && APOOL_OK, "adaptive_avgpool_forward: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype, adaptive_fwd_op<float>(x, out, N, C, H, W, workspace, st), adaptive_fwd_op<bf16_t>(x, out, N, C, H, W, workspace, st));
+}
+int mmskin_adaptive_avgpool_backward(const float* dout, float* dx, int N, int C, int H, int W, int dtype, void* workspace, void* stream) {
+  ARG_CHECK(dout && dx && workspace && APOOL_OK, "adaptive_avgpool_backward: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype, adaptive_bwd_op<float>(dout, dx, N, C, H, W, workspace, st), adaptive_bwd_op<bf16_t>(dout, dx, N, C, H, W, workspace, st));
+}
+#undef APOOL_OK
 
 }  // extern "C"

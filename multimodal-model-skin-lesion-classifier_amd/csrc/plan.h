@@ -399,6 +399,113 @@ template <typename T>
 int se_backward(const SEArgs& a, const T* dyse, const T* y, float* tmp, float* dW1, float* db1, float* dW2, float* db2, T* dy,
                 Profiler* prof, hipStream_t st);
 
+// ---- DenseNet (densenet.hip): one dense block and one transition, shared with the op-level entry points mmskin_dense_* so that a
+// test of a block runs the plan's own launches.  Offsets are bytes into the workspace (activations, coefficients), elements into the
+// flat parameter / buffer / gradient arrays (BNRef, w*_off) and elements into the staged-weight buffers (wf*, wd*).
+constexpr int DENSE_GROWTH = 32, DENSE_BOTTLE = 128, DENSE_G_PAD = 64;
+struct DLayer {
+  int Cin, Cp;
+  BNRef n1, n2;
+  int64_t w1_off, w2_off;        // flat param offsets
+  int64_t wf1, wd1, wf2, wd2;    // staged element offsets
+  size_t t_off, a_off, u_off;    // saved activations (bytes)
+  size_t coef1_off, coef2_off;   // floats: 5*Cp | 4*128
+  int tab1;                      // stage-table index of conv1 (norm2 folds into it for inference)
+};
+struct DBlock {
+  int H, W, C0, Ctot;
+  size_t rows;
+  std::vector<DLayer> layers;
+  size_t cat_off, dcat_off, tab_off;   // tab: mean[Ctot] | var[Ctot]
+};
+struct DTrans {
+  int C;
+  BNRef n;
+  int64_t w_off, wf, wd;
+  size_t tt_off, coef_off;   // coef: 5*C floats
+};
+// The geometry every carve of a dense layer shares (build_dense_plan and the op-level carves of capi.hip call these, so they cannot drift):
+inline void dense_layer_geom(DLayer& l, int c0, int i) {   // layer i of a block whose input has c0 channels; operands padded to 64
+  l.Cin = c0 + DENSE_GROWTH * i;
+  l.Cp = (l.Cin + 63) / 64 * 64;
+}
+// one staged weight appended to `table`; wf / wd are the running element cursors of the forward / data-gradient staging buffers
+inline void dense_stage(std::vector<StageDesc>& table, int64_t src, int Cout, int Cin, int taps, int Cop, int Cip, int64_t& wf, int64_t& wd,
+                        int& max_stage_elems, int64_t& wf_off, int64_t& wd_off) {
+  StageDesc d = {};
+  d.src_off = src; d.Cout = Cout; d.Cin = Cin; d.taps = taps; d.Cout_pad = Cop; d.Cin_pad = Cip;
+  wf_off = wf; wd_off = wd;
+  d.fwd_off = wf; d.dgrad_off = wd;
+  const int64_t n = (int64_t)Cop * Cip * taps;
+  wf += n; wd += n;
+  if (n > max_stage_elems) max_stage_elems = (int)n;
+  table.push_back(d);
+}
+inline void dense_stage_layer(DLayer& l, std::vector<StageDesc>& table, int64_t& wf, int64_t& wd, int& max_stage_elems) {
+  l.tab1 = (int)table.size();
+  dense_stage(table, l.w1_off, DENSE_BOTTLE, l.Cin, 1, DENSE_BOTTLE, l.Cp, wf, wd, max_stage_elems, l.wf1, l.wd1);
+  dense_stage(table, l.w2_off, DENSE_GROWTH, DENSE_BOTTLE, 9, DENSE_G_PAD, DENSE_BOTTLE, wf, wd, max_stage_elems, l.wf2, l.wd2);
+}
+// inference: conv1 carries norm2's scale, its epilogue adds shift + ReLU (coef2_off must be carved)
+inline void dense_fold_norm2(const DLayer& l, std::vector<StageDesc>& table) {
+  StageDesc& d = table[l.tab1];
+  d.has_bn = 1;
+  d.bn_g_off = l.n2.g_off; d.bn_b_off = l.n2.b_off; d.bn_rm_off = l.n2.rm_off; d.bn_rv_off = l.n2.rv_off;
+  d.coef_off = (int64_t)l.coef2_off;
+}
+// bytes of BatchNorm-backward partial sums for `rows` rows of C channels: the stand-alone reduce's rows or a fused dgrad epilogue's
+inline size_t dense_partial_bytes(size_t rows, int C) {
+  size_t a = (size_t)bn_bwd_partial_rows(rows, C) * 2 * C * sizeof(float);
+  size_t b = ((rows + 127) / 128 + 4) * 2 * (size_t)C * sizeof(float);
+  return a > b ? a : b;
+}
+// what one layer asks of the shared scratch regions: statistics floats, partial bytes, weight-gradient slab bytes (maxima kept)
+inline void dense_layer_needs(int N, int H, int W, size_t rows, const DLayer& l, size_t& stat_floats, size_t& partial_bytes, size_t& slab) {
+  ConvShape c1 = {N, H, W, l.Cp, DENSE_BOTTLE, 1, 1, 1, 0}, c2 = {N, H, W, DENSE_BOTTLE, DENSE_G_PAD, 3, 3, 1, 1};
+  auto up = [](size_t& m, size_t v) { if (v > m) m = v; };
+  up(stat_floats, (size_t)conv_fwd_stat_rows(c1) * DENSE_BOTTLE);
+  up(stat_floats, (size_t)conv_fwd_stat_rows(c2) * DENSE_G_PAD);
+  up(partial_bytes, dense_partial_bytes(rows, l.Cp));
+  up(partial_bytes, dense_partial_bytes(rows, DENSE_BOTTLE));
+  up(slab, conv_wgrad_slab_bytes(c1));
+  up(slab, conv_wgrad_slab_bytes(c2));
+}
+// What a block / transition runs on: the plan fills it from its workspace offsets, the op-level entry points from their carve.
+template <typename T>
+struct DenseRun {
+  int N = 0;
+  Profiler* prof = nullptr;        // may be null (op-level callers)
+  unsigned char* ws = nullptr;
+  const float* params = nullptr;
+  float* buffers = nullptr;        // running statistics (forward)
+  float* grads = nullptr;          // backward
+  T *wf = nullptr, *wd = nullptr;  // staged weights
+  float *stat_sum = nullptr, *stat_sq = nullptr;   // batch-statistics slabs
+  double* red = nullptr;
+  T* sBq[2] = {nullptr, nullptr};  // conv2 output / gradient, padded to 64 channels (forward uses [0]); alternate between layers
+  T* sAq[2] = {nullptr, nullptr};  // gradient of conv1's output
+  T *sU = nullptr, *sZ = nullptr, *sC = nullptr;   // gradient of u; of the padded prefix t; the transition conv's output / its gradient
+  float *slab = nullptr, *partial = nullptr, *cA = nullptr, *defer = nullptr;
+  SideStream* side = nullptr;      // null: the weight-gradient GEMMs run on the caller's stream
+  bool use_side = false;
+  int layer_no = 0;                // layers seen by this backward (picks the alternating operand buffers)
+};
+// batch statistics of cat channels [c0, c0+C) of block b -> its mean/var table
+template <typename T>
+int dense_table_from_slice(DenseRun<T>& r, const DBlock& b, int c0, int C, hipStream_t st);
+// every layer of block b on the block input already in cat[:, :C0] (training: its table entries written too)
+template <typename T>
+int dense_block_forward(DenseRun<T>& r, DBlock& b, bool training, hipStream_t st);
+// norm -> relu -> conv 1x1 (C -> C/2) -> avgpool 2x2 of block b's cat into the channel prefix of dst rows of dst_pitch channels
+template <typename T>
+int dense_transition_forward(DenseRun<T>& r, DBlock& b, DTrans& t, T* dst, int dst_pitch, bool training, hipStream_t st);
+// dcat of block b (whole concatenated output's gradient) -> parameter gradients, dcat[:, :C0] = gradient of the block input
+template <typename T>
+int dense_block_backward(DenseRun<T>& r, DBlock& b, hipStream_t st);
+// gradient of the next block's cat prefix (rows of pitch_next channels) -> the whole of block pb's dcat, and the transition's gradients
+template <typename T>
+int dense_transition_backward(DenseRun<T>& r, DBlock& pb, DTrans& tr, const T* dcat_next, int pitch_next, hipStream_t st);
+
 // plan factories (create() needs no GPU); return nullptr and set *rc on failure
 PlanBase* make_resnet_plan(int arch, int N, int H, int W, int dtype, int* rc);
 PlanBase* make_densenet_plan(int N, int H, int W, int dtype, bool feature_map, int* rc);

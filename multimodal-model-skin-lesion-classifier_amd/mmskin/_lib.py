@@ -86,6 +86,21 @@ _SIGNATURES = {
     "mmskin_sd_workspace_bytes": (_i64, [_i, _i64]),
     "mmskin_sd_forward": (_i, [_P] * 4 + [_i, _i64, _i, _P, _P]),
     "mmskin_sd_backward": (_i, [_P] * 3 + [_i, _i64, _i, _P, _P]),
+    "mmskin_dense_block_workspace_bytes": (_i64, [_i] * 5),
+    "mmskin_dense_block_param_numel": (_i64, [_i] * 2),
+    "mmskin_dense_block_forward": (_i, [_P] * 5 + [_i] * 7 + [_P, _P]),
+    "mmskin_dense_block_backward": (_i, [_P] * 5 + [_i] * 6 + [_P, _P]),
+    "mmskin_dense_transition_workspace_bytes": (_i64, [_i] * 5),
+    "mmskin_dense_transition_forward": (_i, [_P] * 6 + [_i] * 7 + [_P, _P]),
+    "mmskin_dense_transition_backward": (_i, [_P] * 7 + [_i] * 6 + [_P, _P]),
+    "mmskin_slice_stats_workspace_bytes": (_i64, [_i64, _i, _i, _i]),
+    "mmskin_slice_stats": (_i, [_P, _i64, _i, _i, _i, _P, _P, _i, _P, _P]),
+    "mmskin_maxpool2_relu_workspace_bytes": (_i64, [_i] * 4),
+    "mmskin_maxpool2_relu_forward": (_i, [_P] * 3 + [_i] * 5 + [_P, _P]),
+    "mmskin_maxpool2_relu_backward": (_i, [_P] * 3 + [_i] * 5 + [_P, _P]),
+    "mmskin_adaptive_avgpool_workspace_bytes": (_i64, [_i] * 4),
+    "mmskin_adaptive_avgpool_forward": (_i, [_P] * 2 + [_i] * 5 + [_P, _P]),
+    "mmskin_adaptive_avgpool_backward": (_i, [_P] * 2 + [_i] * 5 + [_P, _P]),
     "mmskin_stem_workspace_bytes": (_i64, [_i] * 3),
     "mmskin_stem_forward": (_i, [_P] * 5 + [_i] * 3 + [_f, _i, _P, _P]),
     "mmskin_stem_backward": (_i, [_P] * 8 + [_i] * 3 + [_f, _i, _P, _P]),

@@ -13,6 +13,7 @@ import ctypes
 
 import pytest
 
+from densenet_cases import ADAPTIVE_CASES, BLOCK_CASES, MAXPOOL_CASES, SLICE_CASES, TRANS_CASES
 from mbconv_cases import BN_SHAPES, DW_CASES, SE_SHAPES, out_hw, pad64
 from mmskin import _lib
 
@@ -85,6 +86,32 @@ def _sd(N, per):
     return "mmskin_sd_workspace_bytes", (N, per), 4 * 3 * N * per                                 # branch, residual, result
 
 
+def _dense_block(c):
+    rows, ctot = c.N * c.H * c.W, c.C0 + 32 * c.L
+    acts = sum(pad64(c.C0 + 32 * i) + 2 * 128 for i in range(c.L))                                # t, a, u of every layer
+    weights = sum(128 * pad64(c.C0 + 32 * i) + 64 * 128 * 9 for i in range(c.L))                  # staged forward and data-gradient copies
+    return "mmskin_dense_block_workspace_bytes", (c.N, c.C0, c.L, c.H, c.W), 4 * (rows * (2 * ctot + acts) + 2 * weights)
+
+
+def _dense_transition(c):
+    rows, prows = c.N * c.H * c.W, c.N * (c.H // 2) * (c.W // 2)
+    # x, its gradient, relu(norm(x)) and the data gradient; the conv output; the destination rows; both staged weights
+    return "mmskin_dense_transition_workspace_bytes", (c.N, c.C, c.H, c.W, c.pitch), 4 * (4 * rows * c.C + rows * c.C // 2 + prows * c.pitch + c.C * c.C)
+
+
+def _slice_stats(c):
+    return "mmskin_slice_stats_workspace_bytes", (c.rows, c.pitch, c.c0, c.C), 4 * c.rows * c.pitch
+
+
+def _maxpool(N, C, H, W):
+    prows = N * (H // 2) * (W // 2)
+    return "mmskin_maxpool2_relu_workspace_bytes", (N, C, H, W), 4 * (2 * N * H * W * C + 2 * prows * C) + prows * C   # y, dz, pooled, dpool; argmax bytes
+
+
+def _adaptive(N, C, H, W):
+    return "mmskin_adaptive_avgpool_workspace_bytes", (N, C, H, W), 4 * 2 * N * H * W * C          # x, dx
+
+
 ROWS = (
     # tests/test_gpu_kernels.py CONV_CASES, the two shapes of tests/test_gpu_workspace_bounds.py and the rejected 3-channel shape
     [_conv(*c) for c in [(2, 64, 14, 14, 64, 1, 1, 0), (2, 64, 14, 14, 256, 1, 1, 0), (2, 256, 9, 11, 128, 1, 1, 0), (3, 64, 12, 12, 64, 3, 1, 1),
@@ -98,6 +125,11 @@ ROWS = (
     + [_bn_act(*c) for c in BN_SHAPES]
     + [_se(*c) for c in SE_SHAPES]
     + [_sd(*c) for c in [(5, 7 * 7 * 64), (4, 256)]]
+    + [_dense_block(c) for c in BLOCK_CASES]
+    + [_dense_transition(c) for c in TRANS_CASES]
+    + [_slice_stats(c) for c in SLICE_CASES if c.dtype == "fp32"]
+    + [_maxpool(*c) for c in MAXPOOL_CASES]
+    + [_adaptive(*c) for c in ADAPTIVE_CASES]
 )
 
 

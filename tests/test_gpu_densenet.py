@@ -2,8 +2,9 @@
 plan executor vs the CPU oracle (oracle/backbones.py::OracleDenseNet169, torchvision layout -- parity
 unpinned against torchvision itself, which is absent; state_dict names and shapes follow it).
 
-Op-level: the channel-slice kernels the concatenating plan adds.  Backbone level: features, BN running
-statistics and every parameter gradient.  Model level: the config-3 wiring end to end."""
+Backbone level: features, BN running statistics and every parameter gradient.  Model level: the config-3 wiring end to
+end.  The op-level tests of the kernels and host chains the concatenating plan adds (channel slices, deferred BatchNorm
+backward, transitions) live in tests/test_gpu_densenet_ops.py."""
 import os
 
 import pytest

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from gpu_util import DEV, DT
+from densenet_cases import BLOCK_CASES, TRANS_CASES, block_reference, trans_reference
 from mbconv_cases import BN_SHAPES, DW_CASES, SE_SHAPES, out_hw, pad64
 from mmskin import _lib
 from mmskin._lib import call, ptr, stream
@@ -173,6 +174,78 @@ def stochastic_depth_case(dtype):
     return _lib.load().mmskin_sd_workspace_bytes(N, per), run
 
 
+def dense_block_case(dtype):
+    c = BLOCK_CASES[0]                                        # the row with a padded layer: every region of the layout, two operand parities
+    r = block_reference(c)
+    x, dcat, params = r["x"].to(DEV), r["dcat"].to(DEV), r["params"].to(DEV)
+    ctot = c.C0 + 32 * c.L
+    nbuf = sum(2 * (c.C0 + 32 * i) + 256 for i in range(c.L))
+    shape = (c.N, c.C0, c.L, c.H, c.W)
+
+    def run(wsp):
+        bufs = torch.ones(nbuf, device=DEV)
+        cat, table, dx, grads = _new(c.N, ctot, c.H, c.W), _new(2 * ctot), _new(c.N, c.C0, c.H, c.W), _new(params.numel())
+        call("mmskin_dense_block_forward", ptr(x), ptr(params), ptr(bufs), ptr(cat), ptr(table), *shape, 1, DT[dtype], ptr(wsp), stream())
+        call("mmskin_dense_block_backward", ptr(dcat), ptr(x), ptr(params), ptr(dx), ptr(grads), *shape, DT[dtype], ptr(wsp), stream())
+        return cat, table, bufs, dx, grads
+    return _lib.load().mmskin_dense_block_workspace_bytes(*shape), run
+
+
+def dense_transition_case(dtype):
+    c = TRANS_CASES[0]                                        # odd map, destination wider than C/2
+    r = trans_reference(c)
+    x, dnext, params, table = (r[k].to(DEV) for k in ("x", "dnext", "params", "table"))
+    shape = (c.N, c.C, c.H, c.W, c.pitch)
+
+    def run(wsp):
+        bufs = torch.ones(2 * c.C, device=DEV)
+        dst = torch.full((c.N, c.pitch, c.H // 2, c.W // 2), -3.0, device=DEV)
+        conv, dx, grads = _new(c.N, c.C // 2, c.H, c.W), _new(c.N, c.C, c.H, c.W), _new(params.numel())
+        call("mmskin_dense_transition_forward", ptr(x), ptr(table), ptr(params), ptr(bufs), ptr(dst), ptr(conv), *shape, 1, DT[dtype], ptr(wsp), stream())
+        call("mmskin_dense_transition_backward", ptr(dnext), ptr(x), ptr(table), ptr(params), ptr(dx), ptr(grads), None, *shape, DT[dtype], ptr(wsp), stream())
+        return dst, conv, bufs, dx, grads
+    return _lib.load().mmskin_dense_transition_workspace_bytes(*shape), run
+
+
+def slice_stats_case(dtype):
+    rows, pitch, c0, C = 70, 160, 32, 64
+    g = torch.Generator().manual_seed(13)
+    x = _rand(g, rows, pitch)
+
+    def run(wsp):
+        mean, var = _new(C), _new(C)
+        call("mmskin_slice_stats", ptr(x), rows, pitch, c0, C, ptr(mean), ptr(var), DT[dtype], ptr(wsp), stream())
+        return mean, var
+    return _lib.load().mmskin_slice_stats_workspace_bytes(rows, pitch, c0, C), run
+
+
+def maxpool_case(dtype):
+    N, C, H, W = 1, 64, 7, 5
+    g = torch.Generator().manual_seed(14)
+    y, dpool = torch.relu(_rand(g, N, C, H, W)), _rand(g, N, C, H // 2, W // 2)
+
+    def run(wsp):
+        pooled, dz = _new(N, C, H // 2, W // 2), _new(N, C, H, W)
+        idx = torch.empty(N, H // 2, W // 2, C, dtype=torch.uint8, device=DEV)
+        call("mmskin_maxpool2_relu_forward", ptr(y), ptr(pooled), ptr(idx), N, C, H, W, DT[dtype], ptr(wsp), stream())
+        call("mmskin_maxpool2_relu_backward", ptr(dpool), ptr(y), ptr(dz), N, C, H, W, DT[dtype], ptr(wsp), stream())
+        return pooled, dz
+    return _lib.load().mmskin_maxpool2_relu_workspace_bytes(N, C, H, W), run
+
+
+def adaptive_case(dtype):
+    N, C, H, W = 1, 24, 10, 9
+    g = torch.Generator().manual_seed(15)
+    x, dout = _rand(g, N, C, H, W), _rand(g, N, C, 7, 7)
+
+    def run(wsp):
+        out, dx = _new(N, C, 7, 7), _new(N, C, H, W)
+        call("mmskin_adaptive_avgpool_forward", ptr(x), ptr(out), N, C, H, W, DT[dtype], ptr(wsp), stream())
+        call("mmskin_adaptive_avgpool_backward", ptr(dout), ptr(dx), N, C, H, W, DT[dtype], ptr(wsp), stream())
+        return out, dx
+    return _lib.load().mmskin_adaptive_avgpool_workspace_bytes(N, C, H, W), run
+
+
 BOTH = ("fp32", "bf16")
 CASES = (
     [(f"conv2d_k3s1-{d}", lambda d=d: conv_case(3, 1, 1, d)) for d in BOTH]
@@ -185,6 +258,11 @@ CASES = (
     + [(f"batchnorm_act-{d}", lambda d=d: batchnorm_act_case(d)) for d in BOTH]
     + [(f"squeeze_excitation-{d}", lambda d=d: se_case(d)) for d in BOTH]
     + [(f"stochastic_depth-{d}", lambda d=d: stochastic_depth_case(d)) for d in BOTH]
+    + [(f"dense_block-{d}", lambda d=d: dense_block_case(d)) for d in BOTH]
+    + [(f"dense_transition-{d}", lambda d=d: dense_transition_case(d)) for d in BOTH]
+    + [(f"slice_stats-{d}", lambda d=d: slice_stats_case(d)) for d in BOTH]
+    + [(f"maxpool2-{d}", lambda d=d: maxpool_case(d)) for d in BOTH]
+    + [(f"adaptive_avgpool-{d}", lambda d=d: adaptive_case(d)) for d in BOTH]
 )
 
 
