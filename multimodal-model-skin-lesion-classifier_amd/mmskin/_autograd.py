@@ -2,11 +2,15 @@
 differentiation through an op must fail loudly instead of treating the first-order gradient as a constant (which is what
 torch does, silently, for a custom Function whose backward is opaque).  The reference never needs it -- its Grad-CAM++
 (src/services/XAI/models/cam.py:38-43) calls autograd.grad(..., create_graph=True) and then only squares / cubes the
-first-order gradients -- so first-order results under create_graph=True stay exact and free."""
+first-order gradients -- so first-order results under create_graph=True stay exact and free.
+
+Below that: what ops.py and attention.py both need and neither owns -- the tensor checks every Function opens with, the Linear operand
+mode and the dropout counter."""
 import functools
 
 import torch
 
+from . import _lib
 from ._lib import MMSkinError
 
 
@@ -49,3 +53,40 @@ def no_second_order(cls):
     cls.forward = staticmethod(forward)
     cls.backward = staticmethod(backward)
     return cls
+
+
+def _need_gpu(t, what):
+    if not t.is_cuda:
+        raise _lib.MMSkinError(
+            f"mmskin.{what}: tensors must live on a HIP device (got {t.device}); the MI355X path has "
+            "no CPU fallback")
+
+
+def _f32c(t):
+    if t.dtype != torch.float32:
+        t = t.float()
+    return t.contiguous()
+
+
+def _needs_grad(*ts):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
+
+
+def _dtype_code(t):
+    """the C ABI's dtype code of a tensor or of a torch dtype (bf16, or fp32 for everything else)"""
+    return _lib.BF16 if getattr(t, "dtype", t) == torch.bfloat16 else _lib.F32
+
+
+def get_linear_dtype():
+    return "bf16" if _lib.load().mmskin_get_linear_dtype() == 1 else "fp32"
+
+
+_dropout_counter = [0]
+
+
+def _dropout_state(p, n):
+    if p <= 0.0:
+        return 0, 0
+    off = _dropout_counter[0]          # this call consumes counters [off, off + n): ranges of successive calls never overlap
+    _dropout_counter[0] += n
+    return torch.initial_seed() & 0xFFFFFFFFFFFFFFFF, off

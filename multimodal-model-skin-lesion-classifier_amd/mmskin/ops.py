@@ -11,25 +11,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._autograd import no_second_order
+from ._autograd import (_dropout_counter, _dropout_state, _dtype_code, _f32c, _need_gpu, _needs_grad, get_linear_dtype,  # noqa: F401
+                        no_second_order)
 from ._lib import call, ptr, stream
-
-
-def _need_gpu(t, what):
-    if not t.is_cuda:
-        raise _lib.MMSkinError(
-            f"mmskin.{what}: tensors must live on a HIP device (got {t.device}); the MI355X path has "
-            "no CPU fallback")
-
-
-def _f32c(t):
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.contiguous()
-
-
-def _needs_grad(*ts):
-    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
+from .attention import (LongAttentionFn, _bmm, attention, attention_blhd, attention_packed, attention_route,  # noqa: F401
+                        channel_attention, channel_attention_ok, window_attention, window_attention_ok)
 
 
 # ---------------------------------------------------------------------------------------------- the Linear family (csrc/linear.hip)
@@ -39,10 +25,6 @@ def _needs_grad(*ts):
 def set_linear_dtype(name):
     """'fp32' (exact-f32 MFMA, default) or 'bf16' (bf16 operands, fp32 accumulate) for the large Linear GEMMs."""
     call("mmskin_set_linear_dtype", {"fp32": _lib.F32, "float32": _lib.F32, "bf16": _lib.BF16, "bfloat16": _lib.BF16}[name.lower()])
-
-
-def get_linear_dtype():
-    return "bf16" if _lib.load().mmskin_get_linear_dtype() == 1 else "fp32"
 
 
 def _linear_forward(x, w, b, res, act, want_keep):
@@ -152,11 +134,6 @@ def linear_rows(x, w, b, r0, r1):
     if x.dtype != torch.float32 or not x.is_cuda:
         return linear(x, w[r0:r1], b[r0:r1] if b is not None else None)
     return LinearRowsFn.apply(x, w, b, r0, r1)
-
-
-def _dtype_code(t):
-    """the C ABI's dtype code of a tensor or of a torch dtype (bf16, or fp32 for everything else)"""
-    return _lib.BF16 if getattr(t, "dtype", t) == torch.bfloat16 else _lib.F32
 
 
 def _rows_f32_or_bf16(x):
@@ -621,9 +598,6 @@ class DropoutFn(torch.autograd.Function):
         return dx, None, None, None
 
 
-_dropout_counter = [0]
-
-
 def dropout(x, p, training):
     if not training or p <= 0.0:
         return x
@@ -656,421 +630,6 @@ class Concat2Fn(torch.autograd.Function):
 
 
 concat2 = Concat2Fn.apply
-
-
-@no_second_order
-class AttentionFn(torch.autograd.Function):
-    """softmax(q k^T / sqrt(Dh)) v on [B, H, L, Dh] tensors; optional dropout on the probabilities."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, drop_p, seed, offset):
-        _need_gpu(q, "attention")
-        q, k, v = _f32c(q), _f32c(k), _f32c(v)
-        B, H, L, Dh = q.shape
-        o = torch.empty_like(q)
-        ctx.rng = (float(drop_p), int(seed), int(offset))
-        ctx.rows = _rows_ok(L, Dh)
-        if ctx.rows:   # one wave per head, row log-sum-exp instead of the [B, H, L, L] probabilities
-            lse = torch.empty((B, H, L), device=q.device, dtype=torch.float32)
-            st = _i64x3(H * L * Dh, L * Dh, Dh)
-            call("mmskin_attention_rows_forward", ptr(q), ptr(k), ptr(v), ptr(o), ptr(lse), B, H, L, Dh, st, st, Dh ** -0.5, *ctx.rng, stream())
-            ctx.save_for_backward(q, k, v, o, lse)
-            return o
-        p = torch.empty((B, H, L, L), device=q.device, dtype=torch.float32)
-        call("mmskin_attention_forward", ptr(q), ptr(k), ptr(v), ptr(o), ptr(p), B, H, L, Dh, float(drop_p), int(seed),
-             int(offset), stream())
-        ctx.save_for_backward(q, k, v, p)
-        return o
-
-    @staticmethod
-    def backward(ctx, dO):
-        dO = _f32c(dO)
-        if ctx.rows:
-            q, k, v, o, lse = ctx.saved_tensors
-            B, H, L, Dh = q.shape
-            dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-            st = _i64x3(H * L * Dh, L * Dh, Dh)
-            call("mmskin_attention_rows_backward", ptr(dO), ptr(q), ptr(k), ptr(v), ptr(o), ptr(lse), ptr(dq), ptr(dk), ptr(dv), B, H, L, Dh,
-                 st, st, Dh ** -0.5, *ctx.rng, stream())
-            return dq, dk, dv, None, None, None
-        q, k, v, p = ctx.saved_tensors
-        B, H, L, Dh = q.shape
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        call("mmskin_attention_backward", ptr(dO), ptr(q), ptr(k), ptr(v), ptr(p), ptr(dq), ptr(dk), ptr(dv), B, H, L,
-             Dh, *ctx.rng, stream())
-        return dq, dk, dv, None, None, None
-
-
-def _rows_ok(L, Dh):
-    """shapes of the one-wave-per-head attention kernels (mmskin_attention_rows_*)"""
-    return L <= 64 and Dh in (32, 64)
-
-
-def _i64x3(a, b, c):
-    import ctypes
-    return (ctypes.c_int64 * 3)(int(a), int(b), int(c))
-
-
-@no_second_order
-class AttentionPackedFn(torch.autograd.Function):
-    """softmax(q k^T / sqrt(Dh)) v straight on the packed [B, L, 3, H, Dh] output of a fused qkv Linear -> [B, L, H, Dh] (token-major,
-    what the output projection reads); the backward writes d(qkv) in the packed layout.  No permute / contiguous copies in either
-    direction (timm Attention.forward / DaViT WindowAttention with gradients: window attention of 49 tokens, Dh 32)."""
-
-    @staticmethod
-    def forward(ctx, qkv, drop_p, seed, offset):
-        _need_gpu(qkv, "attention_packed")
-        qkv = _f32c(qkv)
-        B, L, three, H, Dh = qkv.shape
-        o = torch.empty((B, L, H, Dh), device=qkv.device, dtype=torch.float32)
-        lse = torch.empty((B, H, L), device=qkv.device, dtype=torch.float32)
-        ctx.rng = (float(drop_p), int(seed), int(offset))
-        step = H * Dh * 4
-        qs, os_ = _i64x3(L * 3 * H * Dh, Dh, 3 * H * Dh), _i64x3(L * H * Dh, Dh, H * Dh)
-        base = qkv.data_ptr()
-        import ctypes
-        call("mmskin_attention_rows_forward", ctypes.c_void_p(base), ctypes.c_void_p(base + step), ctypes.c_void_p(base + 2 * step), ptr(o),
-             ptr(lse), B, H, L, Dh, qs, os_, Dh ** -0.5, *ctx.rng, stream())
-        ctx.save_for_backward(qkv, o, lse)
-        return o
-
-    @staticmethod
-    def backward(ctx, dO):
-        import ctypes
-        qkv, o, lse = ctx.saved_tensors
-        B, L, three, H, Dh = qkv.shape
-        dO = _f32c(dO)
-        dqkv = torch.empty_like(qkv)
-        step = H * Dh * 4
-        qs, os_ = _i64x3(L * 3 * H * Dh, Dh, 3 * H * Dh), _i64x3(L * H * Dh, Dh, H * Dh)
-        base, dbase = qkv.data_ptr(), dqkv.data_ptr()
-        call("mmskin_attention_rows_backward", ptr(dO), ctypes.c_void_p(base), ctypes.c_void_p(base + step), ctypes.c_void_p(base + 2 * step),
-             ptr(o), ptr(lse), ctypes.c_void_p(dbase), ctypes.c_void_p(dbase + step), ctypes.c_void_p(dbase + 2 * step), B, H, L, Dh,
-             qs, os_, Dh ** -0.5, *ctx.rng, stream())
-        return dqkv, None, None, None
-
-
-@no_second_order
-class WindowAttentionFn(torch.autograd.Function):
-    """Window attention on the packed qkv of an image-major token grid, qkv [B, Hp, Wp, 3, H, Dh] -> [B, Hp, Wp, H, Dh]: every ws x ws
-    window attends over its own tokens where they sit (mmskin_window_attention_*), so timm's window_partition / window_reverse
-    (davit.py SpatialBlock.forward) cost no copy in either direction."""
-
-    @staticmethod
-    def forward(ctx, qkv, ws, drop_p, seed, offset):
-        import ctypes
-        _need_gpu(qkv, "window_attention")
-        qkv = _f32c(qkv)
-        B, Hp, Wp, three, H, Dh = qkv.shape
-        nwy, nwx = Hp // ws, Wp // ws
-        o = torch.empty((B, Hp, Wp, H, Dh), device=qkv.device, dtype=torch.float32)
-        lse = torch.empty((B * nwy * nwx, H, ws * ws), device=qkv.device, dtype=torch.float32)
-        ctx.rng = (float(drop_p), int(seed), int(offset))
-        ctx.geom = (B, nwy, nwx, ws, H, Dh)
-        step = H * Dh * 4
-        base = qkv.data_ptr()
-        call("mmskin_window_attention_forward", ctypes.c_void_p(base), ctypes.c_void_p(base + step), ctypes.c_void_p(base + 2 * step), ptr(o),
-             ptr(lse), B, nwy, nwx, ws, H, Dh, 3 * H * Dh, Dh, H * Dh, Dh, Dh ** -0.5, *ctx.rng, stream())
-        ctx.save_for_backward(qkv, o, lse)
-        return o
-
-    @staticmethod
-    def backward(ctx, dO):
-        import ctypes
-        qkv, o, lse = ctx.saved_tensors
-        B, nwy, nwx, ws, H, Dh = ctx.geom
-        dO = _f32c(dO)
-        dqkv = torch.empty_like(qkv)
-        step = H * Dh * 4
-        base, dbase = qkv.data_ptr(), dqkv.data_ptr()
-        call("mmskin_window_attention_backward", ptr(dO), ctypes.c_void_p(base), ctypes.c_void_p(base + step), ctypes.c_void_p(base + 2 * step),
-             ptr(o), ptr(lse), ctypes.c_void_p(dbase), ctypes.c_void_p(dbase + step), ctypes.c_void_p(dbase + 2 * step), B, nwy, nwx, ws, H, Dh,
-             3 * H * Dh, Dh, H * Dh, Dh, Dh ** -0.5, *ctx.rng, stream())
-        return dqkv, None, None, None, None
-
-
-def window_attention_ok(qkv, ws):
-    """shapes mmskin_window_attention_* takes: fp32 packed qkv [B, Hp, Wp, 3, H, Dh] on the GPU, Hp / Wp multiples of ws, ws*ws <= 64, Dh 32 / 64"""
-    return (qkv.is_cuda and qkv.dtype == torch.float32 and qkv.dim() == 6 and qkv.shape[3] == 3 and qkv.is_contiguous()
-            and qkv.shape[1] % ws == 0 and qkv.shape[2] % ws == 0 and _rows_ok(ws * ws, qkv.shape[5]))
-
-
-def window_attention(qkv, ws, dropout_p=0.0, training=False):
-    """softmax(q k^T / sqrt(Dh)) v inside every ws x ws window of the token grid; qkv [B, Hp, Wp, 3, H, Dh] -> [B, Hp, Wp, H, Dh]."""
-    B, Hp, Wp, _, H, Dh = qkv.shape
-    p = dropout_p if training else 0.0
-    nw = B * (Hp // ws) * (Wp // ws)
-    seed, offset = _dropout_state(p, nw * H * (ws * ws) ** 2)
-    return WindowAttentionFn.apply(qkv, ws, p, seed, offset)
-
-
-@no_second_order
-class ChannelAttentionFn(torch.autograd.Function):
-    """DaViT channel attention on the packed qkv of a fused Linear, qkv [B, N, 3, G, 32] -> [B, N, G, 32] (token-major, what the output
-    projection reads): A = softmax(scale q^T k) over each group's 32 channels, x = (A v^T)^T (timm davit.py ChannelAttention.forward).
-    No permute / contiguous copies; the backward writes d(qkv) in the packed layout."""
-
-    @staticmethod
-    def forward(ctx, qkv, scale):
-        import ctypes
-        _need_gpu(qkv, "channel_attention")
-        qkv = _f32c(qkv)
-        B, N, three, G, Dh = qkv.shape
-        x = torch.empty((B, N, G, Dh), device=qkv.device, dtype=torch.float32)
-        attn = torch.empty((B * G, Dh, Dh), device=qkv.device, dtype=torch.float32)
-        step = G * Dh * 4
-        base = qkv.data_ptr()
-        ctx.scale = float(scale)
-        ns = _lib.load().mmskin_channel_attention_scratch_floats(B, G, N)
-        scratch = torch.empty(ns, device=qkv.device, dtype=torch.float32) if ns else None
-        call("mmskin_channel_attention_forward", ctypes.c_void_p(base), ctypes.c_void_p(base + step), ctypes.c_void_p(base + 2 * step), ptr(x),
-             ptr(attn), ptr(scratch) if scratch is not None else None, B, G, N, Dh, 3 * G * Dh, N * 3 * G * Dh, G * Dh, N * G * Dh, ctx.scale, stream())
-        ctx.save_for_backward(qkv, attn)
-        return x
-
-    @staticmethod
-    def backward(ctx, dO):
-        import ctypes
-        qkv, attn = ctx.saved_tensors
-        B, N, three, G, Dh = qkv.shape
-        dO = _f32c(dO)
-        dqkv = torch.empty_like(qkv)
-        step = G * Dh * 4
-        base, dbase = qkv.data_ptr(), dqkv.data_ptr()
-        ns = _lib.load().mmskin_channel_attention_scratch_floats(B, G, N)
-        scratch = torch.empty(ns, device=qkv.device, dtype=torch.float32) if ns else None
-        call("mmskin_channel_attention_backward", ptr(dO), ctypes.c_void_p(base), ctypes.c_void_p(base + step), ctypes.c_void_p(base + 2 * step),
-             ptr(attn), ctypes.c_void_p(dbase), ctypes.c_void_p(dbase + step), ctypes.c_void_p(dbase + 2 * step),
-             ptr(scratch) if scratch is not None else None, B, G, N, Dh,
-             3 * G * Dh, N * 3 * G * Dh, G * Dh, N * G * Dh, ctx.scale, stream())
-        return dqkv, None
-
-
-def channel_attention_ok(qkv):
-    """shapes mmskin_channel_attention_* takes: fp32 packed qkv [B, N, 3, G, 32] on the GPU"""
-    return qkv.is_cuda and qkv.dtype == torch.float32 and qkv.dim() == 5 and qkv.shape[2] == 3 and qkv.shape[4] == 32 and qkv.is_contiguous()
-
-
-def channel_attention(qkv, scale):
-    return ChannelAttentionFn.apply(qkv, scale)
-
-
-def attention_packed(qkv, dropout_p=0.0, training=False, mask_add=None, bias=None, causal=False):
-    """Attention on the packed output of a fused qkv Linear, qkv [B, L, 3, H, Dh] -> [B, L, H, Dh].  Picks, in order: the fused bf16
-    kernel (inference lane), the one-wave-per-head fp32 kernels reading the packed tensor in place (L <= 64, Dh 32 / 64, no mask /
-    bias: window attention with gradients), else attention_blhd on the three views."""
-    B, L, _, H, Dh = qkv.shape
-    q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
-    if (qkv.is_cuda and qkv.dtype == torch.float32 and mask_add is None and bias is None and not causal and _rows_ok(L, Dh)
-            and not _flash_ok(q, k, v, mask_add, bias, B * H) and qkv.is_contiguous()):
-        p = dropout_p if training else 0.0
-        seed, offset = _dropout_state(p, B * H * L * L)
-        return AttentionPackedFn.apply(qkv, p, seed, offset)
-    return attention_blhd(q, k, v, dropout_p, training, mask_add, bias, causal)
-
-
-def _bmm(a, b, c, batch, M, N, K, sam, sak, sab, sbn, sbk, sbb, ldc, scb):
-    call("mmskin_bmm", ptr(a), ptr(b), ptr(c), batch, M, N, K, sam, sak, sab, sbn, sbk, sbb, ldc, scb, stream())
-
-
-@no_second_order
-class LongAttentionFn(torch.autograd.Function):
-    """softmax(q k^T / sqrt(Dh) + mask) v for sequences whose score matrix does not fit one workgroup's LDS
-    (BERT: L = 512): strided batched GEMMs + a row-softmax kernel, the probabilities kept for backward.
-    q, k, v [B, H, L, Dh]; mask_add [B, L] additive key mask or None; dropout on the probabilities when drop_p > 0."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, mask_add, drop_p, seed, offset, bias=None, causal=False):
-        _need_gpu(q, "attention")
-        q, k, v = _f32c(q), _f32c(k), _f32c(v)
-        B, H, L, Dh = q.shape
-        BH = B * H
-        scores = torch.empty((B, H, L, L), device=q.device, dtype=torch.float32)
-        _bmm(q, k, scores, BH, L, L, Dh, Dh, 1, L * Dh, Dh, 1, L * Dh, L, L * L)
-        probs = torch.empty_like(scores)
-        m = _f32c(mask_add) if mask_add is not None else None
-        bs = _f32c(bias) if bias is not None else None                              # [H, L, L], shared by the batch
-        call("mmskin_softmax_forward", ptr(scores), ptr(m) if m is not None else None, ptr(bs) if bs is not None else None,
-             ptr(probs), BH * L, L, H * L, 1.0 / Dh ** 0.5, int(causal), stream())
-        ctx.has_bias = bias is not None
-        del scores
-        dmask = None
-        pd = probs
-        if drop_p > 0.0:
-            pd = torch.empty_like(probs)
-            dmask = torch.empty(probs.shape, device=q.device, dtype=torch.uint8)
-            call("mmskin_attn_dropout_forward", ptr(probs), ptr(pd), ptr(dmask), probs.numel(), L, float(drop_p), int(seed), int(offset), stream())
-        o = torch.empty_like(q)
-        _bmm(pd, v, o, BH, L, Dh, L, L, 1, L * L, 1, Dh, L * Dh, Dh, L * Dh)          # o[i][d] = sum_j pd[i][j] v[j][d]
-        ctx.save_for_backward(q, k, v, probs, pd if drop_p > 0.0 else None, dmask)
-        ctx.drop_p = float(drop_p)
-        return o
-
-    @staticmethod
-    def backward(ctx, dO):
-        q, k, v, probs, pd, dmask = ctx.saved_tensors
-        B, H, L, Dh = q.shape
-        BH = B * H
-        dO = _f32c(dO)
-        pdrop = pd if pd is not None else probs
-        dv = torch.empty_like(v)
-        _bmm(pdrop, dO, dv, BH, L, Dh, L, 1, L, L * L, 1, Dh, L * Dh, Dh, L * Dh)        # dv[j][d] = sum_i pd[i][j] dO[i][d]
-        dp = torch.empty_like(probs)
-        _bmm(dO, v, dp, BH, L, L, Dh, Dh, 1, L * Dh, Dh, 1, L * Dh, L, L * L)           # dp[i][j] = sum_d dO[i][d] v[j][d]
-        if dmask is not None:
-            dp2 = torch.empty_like(dp)
-            call("mmskin_dropout_backward", ptr(dp), ptr(dmask), ptr(dp2), dp.numel(), ctx.drop_p, stream())
-            dp = dp2
-        ds = torch.empty_like(dp)
-        call("mmskin_softmax_backward", ptr(dp), ptr(probs), ptr(ds), BH * L, L, 1.0 / Dh ** 0.5, stream())
-        del dp
-        dq, dk = torch.empty_like(q), torch.empty_like(k)
-        _bmm(ds, k, dq, BH, L, Dh, L, L, 1, L * L, 1, Dh, L * Dh, Dh, L * Dh)            # dq[i][d] = sum_j ds[i][j] k[j][d]
-        _bmm(ds, q, dk, BH, L, Dh, L, 1, L, L * L, 1, Dh, L * Dh, Dh, L * Dh)            # dk[j][d] = sum_i ds[i][j] q[i][d]
-        dbias = None
-        if ctx.has_bias and ctx.needs_input_grad[7]:       # d/d(bias) = d/d(scaled scores) summed over the batch = ds / scale
-            dbias = torch.empty((H, L, L), device=q.device, dtype=torch.float32)
-            call("mmskin_colsum", ptr(ds), ptr(dbias), B, H * L * L, stream())
-            dbias.mul_(Dh ** 0.5)
-        return dq, dk, dv, None, None, None, None, dbias, None
-
-
-def _flash_ok(q, k, v, mask_add, bias, bh):
-    """The fused bf16 attention kernel (csrc/flash_attn.hip) serves bf16-operand mode whenever no gradient has to flow
-    through the attention (frozen encoders -- the reference's default `frozen_weights` -- and inference); trainable blocks
-    keep the unfused path, which saves the probabilities for its backward."""
-    if not (get_linear_dtype() == "bf16" and q.shape[-1] in (32, 64) and q.is_cuda and q.shape == k.shape == v.shape
-            and q.dtype == k.dtype == v.dtype and q.dtype in (torch.float32, torch.bfloat16)
-            and not _needs_grad(q, k, v, bias) and all(t.stride(-1) == 1 for t in (q, k, v))):
-        return False
-    # the kernel's grid is (query tiles, batch * heads): batch * heads <= 65535 (flash_attn.hip ARG_CHECK); larger launches (DaViT
-    # window attention on >= 342 images: 64 windows x 3 heads each) take the rows / unfused path instead of raising
-    return bh <= 65535
-
-
-def _flash_forward(q, k, v, out, dims, strides, mask_add, bias, causal, p, seed, offset):
-    B, H, L, Dh = dims
-    if bias is not None and tuple(bias.shape) != (H, L, L):
-        raise _lib.MMSkinError(f"mmskin.attention: bias must be [H, L, L] = {(H, L, L)}, got {tuple(bias.shape)}")
-    if mask_add is not None and tuple(mask_add.shape) != (B, L):
-        raise _lib.MMSkinError(f"mmskin.attention: mask_add must be [B, L] = {(B, L)}, got {tuple(mask_add.shape)}")
-    st = (ctypes.c_int64 * 12)(*strides)
-    m = _f32c(mask_add) if mask_add is not None else None
-    bs = _f32c(bias) if bias is not None else None
-    call("mmskin_flash_attention_forward", ptr(q), ptr(k), ptr(v), ptr(m) if m is not None else None,
-         ptr(bs) if bs is not None else None, ptr(out), None, B, H, L, Dh, st,
-         _dtype_code(q), 1.0 / Dh ** 0.5, int(causal), float(p), int(seed), int(offset), stream())
-    return out
-
-
-def _flash_train_ok(q, k, v, bias, bh):
-    """Trainable attention on the fused kernels (forward with the row log-sum-exp kept, backward recomputing the probabilities:
-    csrc/flash_attn_bwd.hip) -- bf16-operand mode, gradients required, head dim 32 / 64, more than 64 tokens (shorter sequences have
-    the one-wave-per-head fp32 kernels).  MMSKIN_FLASH_BWD=0 keeps the unfused fp32 chain."""
-    import os
-    return (get_linear_dtype() == "bf16" and os.environ.get("MMSKIN_FLASH_BWD", "1") != "0" and q.is_cuda and q.shape[-1] in (32, 64)
-            and q.shape == k.shape == v.shape and q.shape[-2] > 64 and bh <= 65535 and _needs_grad(q, k, v, bias))
-
-
-@no_second_order
-class FlashAttnFn(torch.autograd.Function):
-    """softmax(q k^T / sqrt(Dh) + bias + mask) v with gradients, fused: q, k, v [B, H, L, Dh] fp32 (rounded to bf16 operands inside),
-    mask_add [B, L] or None, bias [H, L, L] or None (its gradient is the sum of dS over the batch), dropout on the probabilities."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, mask_add, bias, causal, p, seed, offset):
-        q, k, v = _f32c(q), _f32c(k), _f32c(v)
-        B, H, L, Dh = q.shape
-        out = torch.empty_like(q)
-        lse = torch.empty((B, H, L), device=q.device, dtype=torch.float32)
-        if bias is not None and tuple(bias.shape) != (H, L, L):
-            raise _lib.MMSkinError(f"mmskin.attention: bias must be [H, L, L] = {(H, L, L)}, got {tuple(bias.shape)}")
-        if mask_add is not None and tuple(mask_add.shape) != (B, L):
-            raise _lib.MMSkinError(f"mmskin.attention: mask_add must be [B, L] = {(B, L)}, got {tuple(mask_add.shape)}")
-        m = _f32c(mask_add) if mask_add is not None else None
-        bs = _f32c(bias) if bias is not None else None
-        st = (ctypes.c_int64 * 12)(*([q.stride(0), q.stride(1), q.stride(2)] * 4))
-        call("mmskin_flash_attention_forward", ptr(q), ptr(k), ptr(v), ptr(m) if m is not None else None, ptr(bs) if bs is not None else None,
-             ptr(out), ptr(lse), B, H, L, Dh, st, _lib.F32, 1.0 / Dh ** 0.5, int(causal), float(p), int(seed), int(offset), stream())
-        ctx.save_for_backward(q, k, v, out, lse, m, bs)
-        ctx.cfg = (bool(causal), float(p), int(seed), int(offset))
-        return out
-
-    @staticmethod
-    def backward(ctx, dO):
-        q, k, v, out, lse, m, bs = ctx.saved_tensors
-        causal, p, seed, offset = ctx.cfg
-        B, H, L, Dh = q.shape
-        dO = _f32c(dO)
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
-        delta = torch.empty((B, H, L), device=q.device, dtype=torch.float32)
-        bT = bs.transpose(1, 2).contiguous() if bs is not None else None
-        ds = torch.empty((B, H, L, L), device=q.device, dtype=torch.float32) if bs is not None and ctx.needs_input_grad[4] else None
-        st = (ctypes.c_int64 * 15)(*([q.stride(0), q.stride(1), q.stride(2)] * 5))
-        call("mmskin_flash_attention_backward", ptr(q), ptr(k), ptr(v), ptr(out), ptr(dO), ptr(lse), ptr(m) if m is not None else None,
-             ptr(bs) if bs is not None else None, ptr(bT) if bT is not None else None, ptr(delta), ptr(dq), ptr(dk), ptr(dv),
-             ptr(ds) if ds is not None else None, B, H, L, Dh, st, 1.0 / Dh ** 0.5, int(causal), p, seed, offset, stream())
-        dbias = None
-        if ds is not None:       # d(bias) = dS summed over the batch (deterministic column sum, as the unfused path does)
-            dbias = torch.empty((H, L, L), device=q.device, dtype=torch.float32)
-            call("mmskin_colsum", ptr(ds), ptr(dbias), B, H * L * L, stream())
-        return dq, dk, dv, None, dbias, None, None, None, None
-
-
-def _dropout_state(p, n):
-    if p <= 0.0:
-        return 0, 0
-    off = _dropout_counter[0]          # this call consumes counters [off, off + n): ranges of successive calls never overlap
-    _dropout_counter[0] += n
-    return torch.initial_seed() & 0xFFFFFFFFFFFFFFFF, off
-
-
-def attention_blhd(q, k, v, dropout_p=0.0, training=False, mask_add=None, bias=None, causal=False):
-    """Attention on token-major views: q, k, v [B, L, H, Dh] (any strides with a contiguous last dim, e.g. slices of the
-    [B, L, 3, H, Dh] output of a fused qkv Linear) -> [B, L, H, Dh] contiguous.  In bf16-operand mode without gradients this
-    is ONE fused kernel reading the qkv tensor in place; otherwise the views are permuted into the [B, H, L, Dh] ops."""
-    B, L, H, Dh = q.shape
-    p = dropout_p if training else 0.0
-    per16 = 16 // q.element_size()
-    if _flash_ok(q, k, v, mask_add, bias, B * H) and all(t.data_ptr() % 16 == 0 and all(s % per16 == 0 for s in t.stride()[:3])
-                                                   for t in (q, k, v)):
-        seed, offset = _dropout_state(p, B * H * L * L)
-        out = torch.empty((B, L, H, Dh), device=q.device, dtype=q.dtype)
-        strides = []
-        for t in (q, k, v, out):
-            strides += [t.stride(0), t.stride(2), t.stride(1)]        # (batch, head, token)
-        return _flash_forward(q, k, v, out, (B, H, L, Dh), strides, mask_add, bias, causal, p, seed, offset)
-    if q.dtype == torch.bfloat16:     # bf16 views only exist on the inference lane; off the fused kernel's shapes go through fp32
-        q, k, v = q.float(), k.float(), v.float()
-    o = attention(q.permute(0, 2, 1, 3).contiguous(), k.permute(0, 2, 1, 3).contiguous(), v.permute(0, 2, 1, 3).contiguous(),
-                  dropout_p, training, mask_add, bias, causal)
-    return o.permute(0, 2, 1, 3).contiguous()
-
-
-def attention(q, k, v, dropout_p=0.0, training=False, mask_add=None, bias=None, causal=False):
-    B, H, L, _ = q.shape
-    p = dropout_p if training else 0.0
-    if _flash_train_ok(q, k, v, bias, B * H):
-        seed, offset = _dropout_state(p, B * H * L * L)
-        return FlashAttnFn.apply(q, k, v, mask_add, bias, causal, p, seed, offset)
-    if _flash_ok(q, k, v, mask_add, bias, B * H):
-        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        seed, offset = _dropout_state(p, B * H * L * L)
-        out = torch.empty_like(q)
-        strides = []
-        for t in (q, k, v, out):
-            strides += [t.stride(0), t.stride(1), t.stride(2)]
-        return _flash_forward(q, k, v, out, tuple(q.shape), strides, mask_add, bias, causal, p, seed, offset)
-    seed = offset = 0
-    if p > 0.0:
-        seed, offset = _dropout_state(p, B * H * L * L)
-    # the one-workgroup-per-head kernel keeps L x L scores in LDS and walks the feature dimension serially: long sequences
-    # and long feature dimensions (DaViT's channel attention: feature = tokens) go through the batched-GEMM path
-    if mask_add is not None or bias is not None or causal or L * L * 4 > 64 * 1024 or q.shape[3] > 256:
-        return LongAttentionFn.apply(q, k, v, mask_add, p, seed, offset, bias, causal)
-    if p <= 0.0:
-        return AttentionFn.apply(q, k, v, 0.0, 0, 0)
-    return AttentionFn.apply(q, k, v, p, seed, offset)
 
 
 @no_second_order

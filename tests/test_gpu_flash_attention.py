@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from gpu_util import DEV, linear_mode, rel_err
-from mmskin import ops
+from mmskin import attention, ops
 
 pytestmark = pytest.mark.gpu
 
@@ -109,7 +109,7 @@ def test_flash_grid_limit_falls_back_instead_of_raising():
     want = _torch_ref(*(qkv[:8, :, i].permute(0, 2, 1, 3) for i in range(3))).permute(0, 2, 1, 3)
     qd = qkv.to(DEV)
     with linear_mode("bf16"), torch.no_grad():
-        assert not ops._flash_ok(qd[:, :, 0], qd[:, :, 1], qd[:, :, 2], None, None, B * H)
+        assert attention._route("packed", B, H, L, D, qd, None, None, None, None, False)[0] != attention.FLASH
         got = ops.attention_packed(qd)
         small = ops.attention_packed(qd[:8].contiguous())       # 24 (batch, head) pairs: the fused kernel
     assert got.shape == (B, L, H, D)
