@@ -224,6 +224,12 @@ int mmskin_dense_transition_backward(const float* dnext, const float* x, const f
                                      float* dconv_out, int N, int C, int H, int W, int Cdst, int dtype, void* workspace, void* stream);
 /* mean and biased variance of channels [c0, c0+C) of x [rows][pitch] (slice_stats + bn_table_finalize); C, c0, pitch multiples of 8 */
 int64_t mmskin_slice_stats_workspace_bytes(int64_t rows, int pitch, int c0, int C);
+/* The fp64 reduction scratch of the BatchNorm / bias finalize kernels (host arithmetic, no launch; for tests).  Above
+ * MMSKIN_BN_SINGLE_ROWS partial rows a finalize first reduces each slab to at most 64 rows of doubles: a slab whose rows are cols_total
+ * floats apart needs mmskin_col_reduce_scratch_doubles(cols_total) = 64 * cols_total doubles.  mmskin_col_reduce_scratch_check is the
+ * check every finalize makes before that stage writes: 0 when `slabs` slabs of nrows x cols_total fit in `doubles`, else MMSKIN_ERR_ARG. */
+int64_t mmskin_col_reduce_scratch_doubles(int64_t cols_total);
+int mmskin_col_reduce_scratch_check(int slabs, int nrows, int cols_total, int64_t doubles);
 int mmskin_slice_stats(const float* x, int64_t rows, int pitch, int c0, int C, float* mean, float* var, int dtype, void* workspace, void* stream);
 /* VGG: 2x2 / stride 2 max-pool (floor) of a post-ReLU map y [N,C,H,W] (C a multiple of 8, H, W >= 2): pooled [N,C,H/2,W/2] and idx, the
  * argmax tap 0..3 (first maximum, row-major in the window) as bytes in the kernel's layout [N,H/2,W/2,C].  Backward: dz [N,C,H,W] =

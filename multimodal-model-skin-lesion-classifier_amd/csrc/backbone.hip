@@ -50,6 +50,7 @@ struct Plan : PlanBase {
   // workspace layout (bytes)
   size_t off_img4, off_wf, off_wd, off_stat, off_pool, off_idx, off_scratch[7], off_slab, off_partial,
       off_coefbwd, off_dwv, off_red, off_partial_b, off_stat_b, off_red_b;
+  int red_C = 0;   // channels both reduction scratches were carved for (bn_reduce_scratch)
   size_t off_abn_wd = 0, off_abn_bias = 0, off_abn_S = 0, off_abn_cs = 0;   // algebraic BatchNorm backward scratch
   size_t off_abn_wd2 = 0, off_abn_bias2 = 0;                                 // ... of a stride-1 downsample convolution (its folded weights live beside conv3's)
   size_t off_abn_sgx = 0, off_abn_slab2 = 0, off_abn_S2 = 0, off_abn_cs2 = 0;   // two-pass units: main-stream weight-gradient scratch
@@ -265,8 +266,9 @@ int build_plan(Plan& p) {
   p.off_partial_b = carve(cur, partial_max);
   p.off_coefbwd = carve(cur, 3 * (size_t)maxC * sizeof(float));
   p.off_dwv = carve(cur, 64 * 256 * sizeof(float));
-  p.off_red = carve(cur, bn_reduce_scratch_bytes(maxC));
-  p.off_red_b = carve(cur, bn_reduce_scratch_bytes(maxC));
+  p.red_C = maxC;
+  p.off_red = carve(cur, bn_reduce_scratch_bytes(p.red_C));
+  p.off_red_b = carve(cur, bn_reduce_scratch_bytes(p.red_C));
   p.ws_bytes = cur;
   return MMSKIN_OK;
 }
@@ -283,7 +285,7 @@ StemBufs<T> stem_bufs(const Plan& p, unsigned char* ws) {
   b.coef = reinterpret_cast<float*>(ws + u0.coef_off);
   b.ssum = reinterpret_cast<float*>(ws + p.off_stat);
   b.ssq = reinterpret_cast<float*>(ws + p.off_stat + p.stat_bytes);
-  b.red = reinterpret_cast<double*>(ws + p.off_red);
+  b.red = bn_reduce_scratch(ws + p.off_red, p.red_C);
   b.coefbwd = reinterpret_cast<float*>(ws + p.off_coefbwd);
   b.partial = reinterpret_cast<float*>(ws + p.off_partial);
   b.dx0 = reinterpret_cast<T*>(ws + p.off_scratch[3]);
@@ -362,7 +364,7 @@ int forward_impl(Plan& p, const void* image, const float* norm6, const float* pa
   }
   if (folded_eval) return forward_eval<T>(p, image, norm6, params, buffers, ws, features, st, reuse);
 
-  auto bn_coeffs_on = [&](Unit& u, int stat_rows, float* ssum, float* ssq, double* red, hipStream_t s2) -> int {
+  auto bn_coeffs_on = [&](Unit& u, int stat_rows, float* ssum, float* ssq, ColScratch red, hipStream_t s2) -> int {
     const int C = u.s.Cout;
     const BnCoef k(reinterpret_cast<float*>(ws + u.coef_off), C);
     ProfScope scope(&p.prof, K_BN_FWD, s2, 0.0, 0.0);
@@ -372,7 +374,7 @@ int forward_impl(Plan& p, const void* image, const float* norm6, const float* pa
     return bn_eval_coeffs(C, params + u.g_off, params + u.b_off, buffers + u.rm_off, buffers + u.rv_off, eps, k.scale, k.shift, s2);
   };
   auto bn_coeffs = [&](Unit& u, int stat_rows) -> int {
-    return bn_coeffs_on(u, stat_rows, stat_sum, stat_sq, reinterpret_cast<double*>(ws + p.off_red), st);
+    return bn_coeffs_on(u, stat_rows, stat_sum, stat_sq, bn_reduce_scratch(ws + p.off_red, p.red_C), st);
   };
   float* stat_b_sum = reinterpret_cast<float*>(ws + p.off_stat_b);
   float* stat_b_sq = reinterpret_cast<float*>(ws + p.off_stat_b + p.stat_bytes);
@@ -401,7 +403,7 @@ int forward_impl(Plan& p, const void* image, const float* norm6, const float* pa
         if ((rc = launch_conv_fwd<T>(d.s, in, wf + d.wf_off, reinterpret_cast<T*>(ws + d.x_off),
                                      training ? stat_b_sum : nullptr, training ? stat_b_sq : nullptr, p.side.s, nullptr, &nrows_d))) return rc;
         if ((rc = bn_coeffs_on(d, nrows_d, stat_b_sum, stat_b_sq,
-                               reinterpret_cast<double*>(ws + p.off_red_b), p.side.s))) return rc;
+                               bn_reduce_scratch(ws + p.off_red_b, p.red_C), p.side.s))) return rc;
         HIP_CHECK_RET(hipEventRecord(p.side.f_done, p.side.s));
       } else {
         int nrows_d = 0;
@@ -476,7 +478,7 @@ int backward_impl(Plan& p, const float* dfeat, const float* params, unsigned cha
   for (int i = 0; i < 7; ++i) S[i] = reinterpret_cast<T*>(ws + p.off_scratch[i]);
   int rc;
 
-  double* red = reinterpret_cast<double*>(ws + p.off_red);
+  const ColScratch red = bn_reduce_scratch(ws + p.off_red, p.red_C);
   const auto coef_of = [&](const Unit& u) { return BnCoef(reinterpret_cast<float*>(ws + u.coef_off), u.s.Cout); };
   // BN backward of unit u given dy: fills dx (and optionally dz)
   auto bn_bwd = [&](Unit& u, const T* dy, const T* ymask, int mode, T* dx, T* dz) -> int {

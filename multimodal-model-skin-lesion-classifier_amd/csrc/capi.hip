@@ -134,7 +134,7 @@ double conv_time(int op, const ConvShape& s, int iters, void* ws, hipStream_t st
 
 template <typename T>
 struct BnWs {
-  T *xh, *yh, *dxh; float *ssum, *ssq, *partial, *coef, *coefbwd; size_t total;   // yh: y (forward) or dy (backward)
+  T *xh, *yh, *dxh; float *ssum, *ssq, *partial, *coef, *coefbwd; ColScratch red; size_t total;   // yh: y (forward) or dy (backward)
   BnWs(void* ws, int N, int C, int H, int W) {
     Carver c(ws);
     const size_t rows = (size_t)N * H * W;
@@ -144,6 +144,7 @@ struct BnWs {
     partial = c.take<float>((size_t)bn_bwd_partial_rows(rows, C) * 2 * C);
     coef = c.take<float>(5 * (size_t)C);   // scale | shift, and behind them (backward) cA | cB | cC
     coefbwd = BnCoef(coef, C).mean;           // ... which start where a five-slot block keeps mean
+    red = bn_reduce_scratch(c.take<double>(bn_reduce_scratch_bytes(C) / sizeof(double)), C);
     total = c.cur;
   }
 };
@@ -158,7 +159,7 @@ int bn_fwd_op(const float* x, const float* gamma, const float* beta, float* rm, 
   if ((rc = column_stats<T>(s.xh, rows, C, s.ssum, s.ssq, &nr, st))) return rc;
   const BnCoef k(s.coef, C);
   if ((rc = bn_finalize(s.ssum, s.ssq, nr, C, (double)rows, gamma, beta, eps, mom, rm, rv, k.scale, k.shift, save_mean,
-                        save_invstd, nullptr, st))) return rc;
+                        save_invstd, s.red, st))) return rc;
   if ((rc = bn_apply<T>(s.xh, nullptr, k.scale, k.shift, nullptr, nullptr, s.yh, rows, C, relu != 0, st))) return rc;
   return nhwc_to_nchw<T>(s.yh, N, C, H, W, y, st);
 }
@@ -184,7 +185,7 @@ int bn_bwd_op(const float* dy, const float* x, const float* gamma, const float* 
   if ((rc = nchw_to_nhwc<T>(dy, N, C, H, W, s.yh, st))) return rc;
   if ((rc = coef_from_saved(k, C, gamma, beta, save_mean, save_invstd, st))) return rc;
   if ((rc = bn_backward<T>(s.yh, s.xh, nullptr, relu ? MASK_FROM_X : MASK_NONE, rows, C, k, gamma, dgamma, dbeta, BnBwdCoef(s.coefbwd, C),
-                           s.partial, nullptr, s.dxh, nullptr, nullptr, 0.0, st))) return rc;
+                           s.partial, s.red, s.dxh, nullptr, nullptr, 0.0, st))) return rc;
   return nhwc_to_nchw<T>(s.dxh, N, C, H, W, dx, st);
 }
 
@@ -209,7 +210,7 @@ struct StemWs {
     b.partial = c.take<float>((size_t)bn_bwd_partial_rows(g.rows(), 64) * 2 * 64);
     b.slab = c.take<float>(stem_wgrad_slab_bytes(g.N, g.OH, g.OW) / sizeof(float));
     b.dwv = c.take<float>(64 * 256);
-    b.red = c.take<double>(2 * 64 * 64);
+    b.red = bn_reduce_scratch(c.take<double>(bn_reduce_scratch_bytes(64) / sizeof(double)), 64);
     total = c.cur;
   }
 };
@@ -295,7 +296,7 @@ int dw_bwd_op(const float* dy, const float* x, const float* w, float* dx, float*
 
 template <typename T>
 struct BnActWs {
-  T *xh, *yh, *rh, *dyh, *dxh, *dzh; float *ssum, *ssq, *tab, *coef, *coefbwd, *partial; size_t total;
+  T *xh, *yh, *rh, *dyh, *dxh, *dzh; float *ssum, *ssq, *tab, *coef, *coefbwd, *partial; ColScratch red; size_t total;
   BnActWs(void* ws, int N, int C, int H, int W) {
     Carver c(ws);
     const size_t rows = (size_t)N * H * W;
@@ -307,6 +308,7 @@ struct BnActWs {
     coef = c.take<float>(5 * (size_t)C);   // forward: all five slots; backward: scale | shift | cA | cB | cC
     coefbwd = BnCoef(coef, C).mean;
     partial = c.take<float>((size_t)bn_bwd_partial_rows(rows, C) * 2 * C);
+    red = bn_reduce_scratch(c.take<double>(bn_reduce_scratch_bytes(C) / sizeof(double)), C);
     total = c.cur;
   }
 };
@@ -324,7 +326,7 @@ int bn_act_fwd_op(const float* x, const float* res, const float* gamma, const fl
   if (res && (rc = nchw_to_nhwc<T>(res, N, C, H, W, s.rh, st))) return rc;
   // the plan's sequence behind a depthwise conv: column sums -> statistics table -> coefficient vectors -> apply
   if ((rc = column_stats<T>(s.xh, rows, C, s.ssum, s.ssq, &nr, st))) return rc;
-  if ((rc = bn_table_finalize(s.ssum, s.ssq, nr, C, C, (double)rows, s.tab, s.tab + C, nullptr, st))) return rc;
+  if ((rc = bn_table_finalize(s.ssum, s.ssq, nr, C, C, (double)rows, s.tab, s.tab + C, s.red, st))) return rc;
   const BnCoef k(s.coef, C);
   if ((rc = bn_coef_from_table(s.tab, s.tab + C, C, C, gamma, beta, eps, mom, (double)rows, rm, rv, true, s.coef, st))) return rc;
   HIP_CHECK_RET(hipMemcpyAsync(save_mean, k.mean, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
@@ -345,7 +347,7 @@ int bn_act_bwd_op(const float* dy, const float* x, const float* y, const float* 
   if ((rc = nchw_to_nhwc<T>(y, N, C, H, W, s.yh, st))) return rc;   // the forward's stored y: exact in T, MASK_FROM_Y6 reads it
   if ((rc = nchw_to_nhwc<T>(dy, N, C, H, W, s.dyh, st))) return rc;
   if ((rc = coef_from_saved(k, C, gamma, beta, save_mean, save_invstd, st))) return rc;
-  if ((rc = bn_backward<T>(s.dyh, s.xh, s.yh, act_mask(act), rows, C, k, gamma, dgamma, dbeta, BnBwdCoef(s.coefbwd, C), s.partial, nullptr,
+  if ((rc = bn_backward<T>(s.dyh, s.xh, s.yh, act_mask(act), rows, C, k, gamma, dgamma, dbeta, BnBwdCoef(s.coefbwd, C), s.partial, s.red,
                            s.dxh, dres ? s.dzh : (T*)nullptr, nullptr, 0.0, st))) return rc;
   if (dres && (rc = nhwc_to_nchw<T>(s.dzh, N, C, H, W, dres, st))) return rc;   // the residual's gradient is the masked dy
   return nhwc_to_nchw<T>(s.dxh, N, C, H, W, dx, st);
@@ -468,6 +470,7 @@ struct DenseBlockWs {
   DBlock b;
   std::vector<StageDesc> table;
   int max_stage_elems = 0;
+  int red_C = 0;   // channels the reduction scratch was carved for (bn_reduce_scratch)
   int64_t param_numel = 0, buffer_numel = 0, wf_elems = 0;
   size_t table_off, xh_off, wf_off, wd_off, stat_off, stat_bytes, partial_off, coefbwd_off, defer_off, red_off, slab_off, sB_off[2], sU_off,
       sA_off[2], sZ_off, rbuf_off, total;
@@ -517,7 +520,8 @@ struct DenseBlockWs {
     partial_off = carve(cur, partial);
     coefbwd_off = carve(cur, 3 * (size_t)maxC * sizeof(float));
     defer_off = carve(cur, 2 * (size_t)maxC * sizeof(float));
-    red_off = carve(cur, bn_reduce_scratch_bytes(maxC));
+    red_C = maxC;
+    red_off = carve(cur, bn_reduce_scratch_bytes(red_C));
     slab_off = carve(cur, slab);
     for (int q = 0; q < 2; ++q) sB_off[q] = carve(cur, b.rows * DENSE_G_PAD * es);
     sU_off = carve(cur, b.rows * DENSE_BOTTLE * es);
@@ -532,7 +536,7 @@ struct DenseBlockWs {
     r.N = N; r.ws = ws; r.params = params; r.buffers = buffers; r.grads = grads;
     r.wf = reinterpret_cast<T*>(ws + wf_off); r.wd = reinterpret_cast<T*>(ws + wd_off);
     r.stat_sum = reinterpret_cast<float*>(ws + stat_off); r.stat_sq = reinterpret_cast<float*>(ws + stat_off + stat_bytes);
-    r.red = reinterpret_cast<double*>(ws + red_off);
+    r.red = bn_reduce_scratch(ws + red_off, red_C);
     for (int q = 0; q < 2; ++q) { r.sBq[q] = reinterpret_cast<T*>(ws + sB_off[q]); r.sAq[q] = reinterpret_cast<T*>(ws + sA_off[q]); }
     r.sU = reinterpret_cast<T*>(ws + sU_off); r.sZ = reinterpret_cast<T*>(ws + sZ_off);
     r.slab = reinterpret_cast<float*>(ws + slab_off); r.partial = reinterpret_cast<float*>(ws + partial_off);
@@ -593,6 +597,7 @@ struct DenseTransWs {
   DTrans t;
   StageDesc desc;
   int PH, PW;
+  int red_C = 0;   // channels the reduction scratch was carved for (bn_reduce_scratch)
   size_t table_off, wf_off, wd_off, sC_off, dst_off, sZ_off, partial_off, coefbwd_off, red_off, slab_off, rbuf_off, total;
   DenseTransWs(int N, int C, int H, int W, int Cdst, size_t es) {
     b.H = H; b.W = W; b.C0 = C; b.Ctot = C; b.rows = (size_t)N * H * W;
@@ -623,7 +628,8 @@ struct DenseTransWs {
     sZ_off = carve(cur, b.rows * C * es);
     partial_off = carve(cur, dense_partial_bytes(b.rows, C));
     coefbwd_off = carve(cur, 3 * (size_t)C * sizeof(float));
-    red_off = carve(cur, bn_reduce_scratch_bytes(C));
+    red_C = C;
+    red_off = carve(cur, bn_reduce_scratch_bytes(red_C));
     slab_off = carve(cur, conv_wgrad_slab_bytes(ct));
     rbuf_off = carve(cur, 2 * (size_t)C * sizeof(float));
     total = cur;
@@ -633,7 +639,7 @@ struct DenseTransWs {
     DenseRun<T> r;
     r.N = N; r.ws = ws; r.params = params; r.buffers = buffers; r.grads = grads;
     r.wf = reinterpret_cast<T*>(ws + wf_off); r.wd = reinterpret_cast<T*>(ws + wd_off);
-    r.red = reinterpret_cast<double*>(ws + red_off);
+    r.red = bn_reduce_scratch(ws + red_off, red_C);
     r.sZ = reinterpret_cast<T*>(ws + sZ_off); r.sC = reinterpret_cast<T*>(ws + sC_off);
     r.slab = reinterpret_cast<float*>(ws + slab_off); r.partial = reinterpret_cast<float*>(ws + partial_off);
     r.cA = reinterpret_cast<float*>(ws + coefbwd_off);
@@ -687,12 +693,12 @@ int dense_trans_bwd_op(const float* dnext, const float* x, const float* table, c
 // slice_stats + bn_table_finalize on channels [c0, c0 + C) of a [rows][pitch] matrix (table_from_slice's pair)
 template <typename T>
 struct SliceStatsWs {
-  T* xh; float* stat; double* red; size_t total;
+  T* xh; float* stat; ColScratch red; size_t total;
   SliceStatsWs(void* ws, int64_t rows, int pitch, int C) {
     Carver c(ws);
     xh = c.take<T>((size_t)rows * pitch);
     stat = c.take<float>((size_t)column_stats_rows((size_t)rows, C) * 2 * C);
-    red = c.take<double>(bn_reduce_scratch_bytes(C) / sizeof(double));
+    red = bn_reduce_scratch(c.take<double>(bn_reduce_scratch_bytes(C) / sizeof(double)), C);
     total = c.cur;
   }
 };
@@ -1134,6 +1140,10 @@ int mmskin_dense_transition_backward(const float* dnext, const float* x, const f
 #undef DENSE_TRANS_OK
 
 #define SLICE_OK (rows > 0 && rows < (1ll << 31) && rows * pitch < (1ll << 31) && C > 0 && C % 8 == 0 && pitch % 8 == 0 && c0 >= 0 && c0 % 8 == 0 && c0 + C <= pitch)
+int64_t mmskin_col_reduce_scratch_doubles(int64_t cols_total) { return cols_total < 0 ? -1 : (int64_t)col_reduce_scratch_doubles((size_t)cols_total); }
+int mmskin_col_reduce_scratch_check(int slabs, int nrows, int cols_total, int64_t doubles) {
+  return col_reduce_scratch_check(slabs, nrows, cols_total, doubles < 0 ? 0 : (size_t)doubles);
+}
 int64_t mmskin_slice_stats_workspace_bytes(int64_t rows, int pitch, int c0, int C) {
   if (!SLICE_OK) return -1;
   return ws_bytes<SliceStatsWs<float>>(rows, pitch, C);

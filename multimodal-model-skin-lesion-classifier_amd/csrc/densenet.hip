@@ -29,6 +29,7 @@ struct DensePlan : PlanBase {
   DTrans trans[3];
   BNRef n5; size_t coef5_off, y5_off;
   size_t off_wf, off_wd, off_stat, off_partial, off_coefbwd, off_defer, off_dwv, off_red, off_slab;
+  int red_C = 0;   // channels the reduction scratch was carved for (bn_reduce_scratch)
   size_t off_sB, off_sB2, off_sU, off_sA, off_sA2, off_sX, off_sZ, off_sC;
   size_t stat_bytes = 0;
   // weight-gradient GEMMs on the side stream (SideStream slots): 0/1 = conv2 operand (sB) of even/odd layers, 2/3 = conv1
@@ -157,7 +158,8 @@ int build_dense_plan(DensePlan& p) {
   p.off_coefbwd = carve(cur, 3 * (size_t)maxC * sizeof(float));
   p.off_defer = carve(cur, 2 * (size_t)maxC * sizeof(float));   // per block: running sums of the consumers' cB / cC (backward)
   p.off_dwv = carve(cur, 64 * 256 * sizeof(float));
-  p.off_red = carve(cur, bn_reduce_scratch_bytes(maxC));
+  p.red_C = maxC;
+  p.off_red = carve(cur, bn_reduce_scratch_bytes(p.red_C));
   p.off_slab = carve(cur, slab);
   p.off_sB = carve(cur, p.blocks[0].rows * G_PAD * es);
   p.off_sB2 = carve(cur, p.blocks[0].rows * G_PAD * es);
@@ -182,7 +184,7 @@ StemBufs<T> stem_bufs(const DensePlan& p, unsigned char* ws) {
   b.coef = reinterpret_cast<float*>(ws + p.coef0_off);
   b.ssum = reinterpret_cast<float*>(ws + p.off_stat);
   b.ssq = reinterpret_cast<float*>(ws + p.off_stat + p.stat_bytes);
-  b.red = reinterpret_cast<double*>(ws + p.off_red);
+  b.red = bn_reduce_scratch(ws + p.off_red, p.red_C);
   b.coefbwd = reinterpret_cast<float*>(ws + p.off_coefbwd);
   b.partial = reinterpret_cast<float*>(ws + p.off_partial);
   b.dx0 = reinterpret_cast<T*>(ws + p.off_sX);
@@ -199,7 +201,7 @@ DenseRun<T> dense_run(DensePlan& p, const float* params, float* buffers, float* 
   r.wd = reinterpret_cast<T*>(ws + p.off_wd);
   r.stat_sum = reinterpret_cast<float*>(ws + p.off_stat);
   r.stat_sq = reinterpret_cast<float*>(ws + p.off_stat + p.stat_bytes);
-  r.red = reinterpret_cast<double*>(ws + p.off_red);
+  r.red = bn_reduce_scratch(ws + p.off_red, p.red_C);
   r.sBq[0] = reinterpret_cast<T*>(ws + p.off_sB); r.sBq[1] = reinterpret_cast<T*>(ws + p.off_sB2);
   r.sAq[0] = reinterpret_cast<T*>(ws + p.off_sA); r.sAq[1] = reinterpret_cast<T*>(ws + p.off_sA2);
   r.sU = reinterpret_cast<T*>(ws + p.off_sU);
@@ -231,7 +233,7 @@ int dense_block_forward(DenseRun<T>& r, DBlock& b, bool training, hipStream_t st
   float* buffers = r.buffers;
   T* wf = r.wf;
   float *stat_sum = r.stat_sum, *stat_sq = r.stat_sq;
-  double* red = r.red;
+  const ColScratch red = r.red;
   T* sB = r.sBq[0];
   int rc;
   T* cat = reinterpret_cast<T*>(ws + b.cat_off);
@@ -318,7 +320,7 @@ int dense_block_backward(DenseRun<T>& r, DBlock& b, hipStream_t st) {
   float* grads = r.grads;
   T* wd = r.wd;
   float *partial = r.partial, *cA = r.cA;
-  double* red = r.red;
+  const ColScratch red = r.red;
   T *sU = r.sU, *sZ = r.sZ;
   int rc;
   float* sB_ = r.defer;

@@ -66,6 +66,7 @@ struct MBPlan : PlanBase {
   int Hp, Wp, stemC;
   size_t off_img8, off_wf, off_wd, off_stat, off_tab, off_partial, off_coefbwd, off_red, off_slab, off_dwv, off_dwpart,
       off_setmp = 0, off_g[4];
+  int red_C = 0;   // channels the reduction scratch was carved for (bn_reduce_scratch)
   size_t stat_bytes = 0;
 
   // the activation's bn_apply cap and BatchNorm-backward mask mode
@@ -191,7 +192,8 @@ int finish_plan(MBPlan& p, const char* arch) {
   p.off_tab = carve(cur, 2 * (size_t)maxCp * sizeof(float));
   p.off_partial = carve(cur, partial);
   p.off_coefbwd = carve(cur, 3 * (size_t)maxCp * sizeof(float));
-  p.off_red = carve(cur, bn_reduce_scratch_bytes(maxCp));
+  p.red_C = maxCp;
+  p.off_red = carve(cur, bn_reduce_scratch_bytes(p.red_C));
   p.off_slab = carve(cur, slab);
   p.off_dwv = carve(cur, 64 * 128 * sizeof(float));
   p.off_dwpart = carve(cur, (dwpart > 0 ? dwpart : 1) * sizeof(float));
@@ -306,7 +308,7 @@ int mb_forward(MBPlan& p, const void* image, const float* norm6, const float* pa
   float* stat_sum = reinterpret_cast<float*>(ws + p.off_stat);
   float* stat_sq = reinterpret_cast<float*>(ws + p.off_stat + p.stat_bytes);
   float* tab = reinterpret_cast<float*>(ws + p.off_tab);
-  double* red = reinterpret_cast<double*>(ws + p.off_red);
+  const ColScratch red = bn_reduce_scratch(ws + p.off_red, p.red_C);
   const float* sd = training ? p.sd_mask : nullptr;
   int rc;
   if ((rc = p.ensure_table())) return rc;
@@ -375,7 +377,7 @@ int mb_backward(MBPlan& p, const float* dfeat, const float* params, unsigned cha
   float* slab = reinterpret_cast<float*>(ws + p.off_slab);
   float* partial = reinterpret_cast<float*>(ws + p.off_partial);
   float* cA = reinterpret_cast<float*>(ws + p.off_coefbwd);
-  double* red = reinterpret_cast<double*>(ws + p.off_red);
+  const ColScratch red = bn_reduce_scratch(ws + p.off_red, p.red_C);
   float* setmp = reinterpret_cast<float*>(ws + p.off_setmp);
   const float* sd = p.sd_mask;
   const int act_mask = p.act_mask();

@@ -26,13 +26,26 @@ __device__ __forceinline__ void bn_fwd_coeffs(int c, double s, double q, double 
   }
 }
 #endif
+// ---- scratch of the four finalize entries (bn_finalize, bn_bwd_finalize, bn_table_finalize, bias_grad_finalize; one reducer, bn.hip).
+// Above MMSKIN_BN_SINGLE_ROWS partial rows they first reduce their slab(s) to at most 64 fp64 rows in `p`: a slab whose rows are
+// cols_total floats apart needs col_reduce_scratch_doubles(cols_total) doubles, two split slabs twice that.  The entries check what they
+// are about to write against `doubles`.  The default -- no scratch -- is legal and means "reduce in a single stage whatever the row count".
+static inline size_t col_reduce_scratch_doubles(size_t cols_total) { return 64 * cols_total; }
+// MMSKIN_OK when the first stage's output for `slabs` slabs of nrows partial rows x cols_total columns fits in `doubles`, else MMSKIN_ERR_ARG:
+// the check the entries make before that stage writes (no launch)
+int col_reduce_scratch_check(int slabs, int nrows, int cols_total, size_t doubles);
+struct ColScratch {
+  double* p = nullptr;
+  size_t doubles = 0;   // capacity of p
+};
+// what every plan and op carves for a BatchNorm of up to C channels: two slabs of C columns, or one interleaved [row][2][C] slab
+static inline size_t bn_reduce_scratch_bytes(int C) { return col_reduce_scratch_doubles(2 * (size_t)C) * sizeof(double); }
+static inline ColScratch bn_reduce_scratch(void* carved, int C) { return ColScratch{static_cast<double*>(carved), col_reduce_scratch_doubles(2 * (size_t)C)}; }
 // Reduce conv-epilogue partials [nrows][C] -> batch mean/var -> scale/shift (+ running stats).
 int bn_finalize(const float* stat_sum, const float* stat_sq, int nrows, int C, double count,
                 const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
                 float* running_var, float* scale, float* shift, float* save_mean, float* save_invstd,
-                double* scratch, hipStream_t st);
-// scratch for the two finalize calls: 2 * 64 * C doubles (may be null: single-stage reduction)
-static inline size_t bn_reduce_scratch_bytes(int C) { return (size_t)2 * 64 * C * sizeof(double); }
+                ColScratch scratch, hipStream_t st);
 // in[nrows][cols] -> out[G][cols] (and in1 -> out[G..2G) when given)
 template <typename OUT>
 int partial_reduce(const float* in0, const float* in1, int nrows, int cols, int G, OUT* out, hipStream_t st);
@@ -62,7 +75,7 @@ int bn_bwd_reduce(const T* dy, const T* x, const T* ymask, const float* scale, c
 // n_grad (default C): dgamma / dbeta are written for channels < n_grad only (zero-padded channel tails)
 int bn_bwd_finalize(const float* partial, int nrows, int C, double count, const float* gamma,
                     const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta,
-                    float* cA, float* cB, float* cC, double* scratch, hipStream_t st, int n_grad = -1,
+                    float* cA, float* cB, float* cC, ColScratch scratch, hipStream_t st, int n_grad = -1,
                     bool accumulate_bc = false,    // accumulate_bc: cB / cC are ADDED to (running sums over the consumers of one input)
                     const float* sum_dz_x = nullptr);   // [C]: use this as sum dz*x instead of the partial rows' second half (abn.hip, second phase)
 // dx = cA*dz + cB*x + cC ; optionally also writes dz (masked dy) to dz_out
@@ -153,9 +166,9 @@ int slice_affine_inplace(T* d, const T* x, int pitch, int C, size_t rows, const 
 template <typename T>
 int slice_stats(const T* x, int pitch, int C, size_t rows, float* stat_sum, float* stat_sq, int* nrows_out,
                 hipStream_t st);
-// partial slabs [nrows][stride] (first C columns used) -> batch mean / biased variance
+// partial slabs [nrows][stride] (first C columns used; stat_sq = stat_sum + C with stride = 2 * C: slice_stats' interleaved slab) -> batch mean / biased variance
 int bn_table_finalize(const float* stat_sum, const float* stat_sq, int nrows, int stride, int C, double count,
-                      float* mean, float* var, double* scratch, hipStream_t st);
+                      float* mean, float* var, ColScratch scratch, hipStream_t st);
 // BatchNorm coefficients for a consumer of table channels [0, C): coef = scale|shift|mean|invstd|gamma,
 // each Cp long with zeros beyond C.  training: batch stats from the table (+ running-stat update);
 // eval: running stats.
@@ -188,7 +201,7 @@ int adaptive_avgpool_fwd(const T* x, int N, int H, int W, int C, int OH, int OW,
 template <typename T>
 int adaptive_avgpool_bwd(const float* dout_nchw, int N, int H, int W, int C, int OH, int OW, T* dx, hipStream_t st);
 // db[c] = sum over rows of partial[r*stride + c]   (conv bias gradient from dgrad-epilogue / column_stats partials)
-int bias_grad_finalize(const float* partial, int nrows, int stride, int C, float* db, double* scratch, hipStream_t st);
+int bias_grad_finalize(const float* partial, int nrows, int stride, int C, float* db, ColScratch scratch, hipStream_t st);
 
 // Grad-CAM: dx[n][c][hw] (NCHW fp32) = dfeat[n][c] / HW * (y[n][hw][c] > 0) * scale[c]  -- the gradient of the pooled
 // features w.r.t. the raw output of the last conv under eval-mode BatchNorm (y = relu(x*scale + shift + skip), NHWC T)

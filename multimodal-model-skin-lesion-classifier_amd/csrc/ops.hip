@@ -1,547 +1,10 @@
-// HBM-bound NHWC kernels (see ops.h).  Replaces the ATen batch_norm / relu / add / max_pool2d /
-// adaptive_avg_pool2d forward+backward kernels the reference reaches through torchvision's ResNet
-// (multimodalIntraInterModal.py:167).
+// HBM-bound NHWC kernels (see ops.h) other than BatchNorm and its column reductions, which are in bn.hip: stem packing + max-pool,
+// global average pool, weight staging, layout converters, channel slices, the VGG pieces, depthwise convolution, squeeze-excitation.
+// Replaces the ATen relu / add / max_pool2d / adaptive_avg_pool2d forward+backward kernels the reference reaches through torchvision's
+// ResNet (multimodalIntraInterModal.py:167).
 #include <stdlib.h>
 
-#include "ops.h"
-
-#define EW_BLOCK 256
-static inline int ew_grid(size_t work_items) {
-  size_t b = (work_items + EW_BLOCK - 1) / EW_BLOCK;
-  // One 16-byte chunk per thread, no grid-stride cap in practice: on MI355X a 2-reads-1-write pass over 1.2 GB ran at
-  // 4.9 TB/s with 4 096 workgroups and 5.9 TB/s with 65 536 (scripts/bench/membench.hip) -- many short workgroups
-  // keep more loads in flight than few long-running ones.
-  if (b > (size_t)1 << 20) b = (size_t)1 << 20;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
-// ------------------------------------------------------------------ column reduction geometry
-struct ColGeom {
-  int CPR;   // 16-byte chunks per row
-  int CW;    // chunk columns per block
-  int RL;    // row lanes per block
-  int RB;    // rows per block
-  int gx, gy;
-};
-static ColGeom col_geom(size_t rows, int C, int EPC) {
-  ColGeom g;
-  g.CPR = C / EPC;
-  g.CW = g.CPR >= 256 ? 256 : g.CPR;
-  g.RL = 256 / g.CW;
-  size_t rb = (rows + 1023) / 1024;
-  if (rb < (size_t)g.RL * 4) rb = (size_t)g.RL * 4;
-  rb = (rb + g.RL - 1) / g.RL * g.RL;
-  g.RB = (int)rb;
-  g.gx = (int)((rows + rb - 1) / rb);
-  g.gy = (g.CPR + g.CW - 1) / g.CW;
-  return g;
-}
-
-// Reduce NQ per-thread EPC-wide accumulators over the row lanes of a block and write them to
-// partial[(blockIdx.x*NQ + q)*C + channel].
-template <int EPC, int NQ>
-__device__ __forceinline__ void block_col_reduce(float (&acc)[NQ][EPC], int cx, int ry, int CW, int RL,
-                                                 int col, int CPR, int C, float* partial, float* red) {
-  // red: [NQ][RL][CW*EPC]
-  const bool active = ry < RL;
-  if (active) {
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) red[(q * RL + ry) * CW * EPC + cx * EPC + e] = acc[q][e];
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < NQ * CW * EPC; i += blockDim.x) {
-    int q = i / (CW * EPC), ce = i - q * CW * EPC;
-    int ch = blockIdx.y * CW * EPC + ce;
-    if (ch < C) {
-      float s = 0.f;
-      for (int r = 0; r < RL; ++r) s += red[(q * RL + r) * CW * EPC + ce];
-      partial[((size_t)blockIdx.x * NQ + q) * C + ch] = s;
-    }
-  }
-}
-
-// ------------------------------------------------------------------ row-partial pre-reduction
-// in[nrows][cols] -> out[G][cols]: group g sums rows [g*per, (g+1)*per).  Conv epilogues / wgrad splits
-// leave up to ~25k partial rows; reducing them in one finalize block per 64 channels was latency-bound
-// (200 us per BatchNorm), so a wide first stage brings the row count down to <= 64 first.
-template <typename OUT>
-__global__ __launch_bounds__(512) void partial_reduce_kernel(const float* __restrict__ in0,
-                                                             const float* __restrict__ in1, int nrows, int cols,
-                                                             int G, OUT* __restrict__ out) {
-  __shared__ OUT red[8][64];
-  const float* in = blockIdx.z ? in1 : in0;
-  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + cx;
-  const int per = (nrows + G - 1) / G;
-  const int r0 = blockIdx.y * per;
-  const int r1 = min(nrows, r0 + per);
-  OUT a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-  if (c < cols) {
-    int r = r0 + ry;
-    for (; r + 24 < r1; r += 32) {
-      a0 += (OUT)in[(size_t)r * cols + c];
-      a1 += (OUT)in[(size_t)(r + 8) * cols + c];
-      a2 += (OUT)in[(size_t)(r + 16) * cols + c];
-      a3 += (OUT)in[(size_t)(r + 24) * cols + c];
-    }
-    for (; r < r1; r += 8) a0 += (OUT)in[(size_t)r * cols + c];
-  }
-  red[ry][cx] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  if (ry == 0 && c < cols) {
-    OUT s = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s += red[i][cx];
-    out[((size_t)blockIdx.z * G + blockIdx.y) * cols + c] = s;
-  }
-}
-
-// float4 variant for wide matrices (wgrad split slabs): 64 threads cover 256 columns, 8 row lanes
-__global__ __launch_bounds__(512) void partial_reduce4_kernel(const float* __restrict__ in, int nrows, int cols,
-                                                              int G, float* __restrict__ out) {
-  __shared__ float4 red[8][64];
-  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
-  const int c = (blockIdx.x * 64 + cx) * 4;
-  const int per = (nrows + G - 1) / G;
-  const int r0 = blockIdx.y * per;
-  const int r1 = min(nrows, r0 + per);
-  float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
-  if (c < cols) {
-    int r = r0 + ry;
-    for (; r + 8 < r1; r += 16) {
-      float4 u = *reinterpret_cast<const float4*>(in + (size_t)r * cols + c);
-      float4 v = *reinterpret_cast<const float4*>(in + (size_t)(r + 8) * cols + c);
-      a0.x += u.x; a0.y += u.y; a0.z += u.z; a0.w += u.w;
-      a1.x += v.x; a1.y += v.y; a1.z += v.z; a1.w += v.w;
-    }
-    for (; r < r1; r += 8) {
-      float4 u = *reinterpret_cast<const float4*>(in + (size_t)r * cols + c);
-      a0.x += u.x; a0.y += u.y; a0.z += u.z; a0.w += u.w;
-    }
-  }
-  red[ry][cx] = make_float4(a0.x + a1.x, a0.y + a1.y, a0.z + a1.z, a0.w + a1.w);
-  __syncthreads();
-  if (ry == 0 && c < cols) {
-    float4 s = red[0][cx];
-#pragma unroll
-    for (int i = 1; i < 8; ++i) { s.x += red[i][cx].x; s.y += red[i][cx].y; s.z += red[i][cx].z; s.w += red[i][cx].w; }
-    *reinterpret_cast<float4*>(out + (size_t)blockIdx.y * cols + c) = s;
-  }
-}
-
-template <typename OUT>
-int partial_reduce(const float* in0, const float* in1, int nrows, int cols, int G, OUT* out, hipStream_t st) {
-  if constexpr (sizeof(OUT) == 4) {
-    if (!in1 && cols % 4 == 0) {
-      hipLaunchKernelGGL(partial_reduce4_kernel, dim3(ceil_div(cols, 256), G), dim3(512), 0, st, in0, nrows, cols, G,
-                         reinterpret_cast<float*>(out));
-      HIP_CHECK_RET(hipGetLastError());
-      return MMSKIN_OK;
-    }
-  }
-  hipLaunchKernelGGL(partial_reduce_kernel<OUT>, dim3(ceil_div(cols, 64), G, in1 ? 2 : 1), dim3(512), 0, st, in0, in1,
-                     nrows, cols, G, out);
-  HIP_CHECK_RET(hipGetLastError());
-  return MMSKIN_OK;
-}
-template int partial_reduce<float>(const float*, const float*, int, int, int, float*, hipStream_t);
-template int partial_reduce<double>(const float*, const float*, int, int, int, double*, hipStream_t);
-
-static inline int reduce_groups(int nrows) {
-  int g = (nrows + 31) / 32;
-  return g > 64 ? 64 : (g < 1 ? 1 : g);
-}
-
-// partial-row counts up to this are reduced by the finalize kernel itself (one launch instead of two)
-#ifndef BN_SINGLE_STAGE_ROWS
-#define BN_SINGLE_STAGE_ROWS bn_single_stage_rows()
-#endif
-// MMSKIN_BN_SINGLE_ROWS (default 512): layers 3 - 4 of ResNet-50 at batch 256 leave 98 - 392 partial rows (64 - 256 with the
-// pipelined conv kernel's tiles) -- one 1024-thread finalize launch (16 row lanes x 2 chains) instead of pre-reduction + finalize
-static inline int bn_single_stage_rows() {
-  static const int v = env_knob("MMSKIN_BN_SINGLE_ROWS", 512);
-  return v;
-}
-
-// ------------------------------------------------------------------ BN forward
-template <typename IN, int RL = 4>
-__global__ __launch_bounds__(64 * RL) void bn_finalize_kernel(const IN* __restrict__ ssum, const IN* __restrict__ ssq, int nrows,
-                                   int C, double count, const float* __restrict__ gamma,
-                                   const float* __restrict__ beta, float eps, float momentum,
-                                   float* running_mean, float* running_var, float* scale, float* shift,
-                                   float* save_mean, float* save_invstd) {
-  __shared__ double red[2][RL][64];
-  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + cx;
-  double s = 0.0, q = 0.0;
-  if (c < C) {
-    int r = ry;
-    double s1 = 0.0, q1 = 0.0, s2 = 0.0, q2 = 0.0, s3 = 0.0, q3 = 0.0;
-    for (; r + 3 * RL < nrows; r += 4 * RL) {     // four independent chains per lane (eight loads in flight)
-      s += (double)ssum[(size_t)r * C + c]; q += (double)ssq[(size_t)r * C + c];
-      s1 += (double)ssum[(size_t)(r + RL) * C + c]; q1 += (double)ssq[(size_t)(r + RL) * C + c];
-      s2 += (double)ssum[(size_t)(r + 2 * RL) * C + c]; q2 += (double)ssq[(size_t)(r + 2 * RL) * C + c];
-      s3 += (double)ssum[(size_t)(r + 3 * RL) * C + c]; q3 += (double)ssq[(size_t)(r + 3 * RL) * C + c];
-    }
-    for (; r < nrows; r += RL) { s += (double)ssum[(size_t)r * C + c]; q += (double)ssq[(size_t)r * C + c]; }
-    s = (s + s1) + (s2 + s3); q = (q + q1) + (q2 + q3);
-  }
-  red[0][ry][cx] = s; red[1][ry][cx] = q;
-  __syncthreads();
-  if (ry == 0 && c < C) {
-    s = 0.0; q = 0.0;
-#pragma unroll
-    for (int i = 0; i < RL; ++i) { s += red[0][i][cx]; q += red[1][i][cx]; }
-    bn_fwd_coeffs(c, s, q, count, gamma, beta, eps, momentum, running_mean, running_var, scale, shift, save_mean, save_invstd);
-  }
-}
-
-int bn_finalize(const float* stat_sum, const float* stat_sq, int nrows, int C, double count,
-                const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
-                float* running_var, float* scale, float* shift, float* save_mean, float* save_invstd,
-                double* scratch, hipStream_t st) {
-  if (scratch && nrows > BN_SINGLE_STAGE_ROWS) {   // (both stages in one launch behind a ticket per column block: +1.3 ms per step, profiles/r04_experiments.txt (11))
-    const int G = reduce_groups(nrows);
-    int rc = partial_reduce<double>(stat_sum, stat_sq, nrows, C, G, scratch, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(bn_finalize_kernel<double>, dim3(ceil_div(C, 64)), dim3(256), 0, st, scratch,
-                       scratch + (size_t)G * C, G, C, count, gamma, beta, eps, momentum, running_mean, running_var,
-                       scale, shift, save_mean, save_invstd);
-  } else if (nrows > 64) {   // up to BN_SINGLE_STAGE_ROWS partial rows in ONE launch: 16 row lanes x 2 chains each
-    hipLaunchKernelGGL((bn_finalize_kernel<float, 16>), dim3(ceil_div(C, 64)), dim3(1024), 0, st, stat_sum, stat_sq, nrows,
-                       C, count, gamma, beta, eps, momentum, running_mean, running_var, scale, shift, save_mean,
-                       save_invstd);
-  } else {
-    hipLaunchKernelGGL(bn_finalize_kernel<float>, dim3(ceil_div(C, 64)), dim3(256), 0, st, stat_sum, stat_sq, nrows,
-                       C, count, gamma, beta, eps, momentum, running_mean, running_var, scale, shift, save_mean,
-                       save_invstd);
-  }
-  HIP_CHECK_RET(hipGetLastError());
-  return MMSKIN_OK;
-}
-
-__global__ void bn_eval_coeffs_kernel(int C, const float* gamma, const float* beta, const float* rm,
-                                      const float* rv, float eps, float* scale, float* shift) {
-  int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c < C) {
-    float sc = gamma[c] / sqrtf(rv[c] + eps);
-    scale[c] = sc;
-    shift[c] = beta[c] - rm[c] * sc;
-  }
-}
-int bn_eval_coeffs(int C, const float* gamma, const float* beta, const float* running_mean,
-                   const float* running_var, float eps, float* scale, float* shift, hipStream_t st) {
-  hipLaunchKernelGGL(bn_eval_coeffs_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, st, C, gamma, beta,
-                     running_mean, running_var, eps, scale, shift);
-  HIP_CHECK_RET(hipGetLastError());
-  return MMSKIN_OK;
-}
-
-template <typename T, int RELU, int RES, bool NT = false>  // RELU: 0 none, 1 relu / capped relu, 2 SiLU; RES: 0 none, 1 plain residual, 2 residual*rscale + rshift
-__global__ __launch_bounds__(EW_BLOCK) void bn_apply_kernel(const T* __restrict__ x, const T* __restrict__ res,
-                                                            const float* __restrict__ scale,
-                                                            const float* __restrict__ shift,
-                                                            const float* __restrict__ rscale,
-                                                            const float* __restrict__ rshift, T* __restrict__ y,
-                                                            uint8_t* __restrict__ mask_bits, size_t nchunks, int CPR,
-                                                            float relu_cap) {
-  constexpr int EPC = DT<T>::EPC;
-  for (size_t i = blockIdx.x * (size_t)EW_BLOCK + threadIdx.x; i < nchunks; i += (size_t)gridDim.x * EW_BLOCK) {
-    int c0 = (int)(i % CPR) * EPC;
-    Chunk<T> v;
-    if (NT) v.load_nt(x + i * EPC); else v.load(x + i * EPC);     // the raw conv output is read once more only in backward
-    Chunk<T> r;
-    if (RES) { if (NT) r.load_nt(res + i * EPC); else r.load(res + i * EPC); }
-    uint32_t bits = 0;
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) {
-      float t = v.v[e] * scale[c0 + e] + shift[c0 + e];
-      if (RES == 1) t += r.v[e];
-      if (RES == 2) t += r.v[e] * rscale[c0 + e] + rshift[c0 + e];
-      // SiLU is its own instantiation: as a run-time branch its exp + divide were if-converted into the ReLU path
-      // and made the (HBM-bound) pass VALU-bound -- 3x slower BatchNorm-apply on every backbone
-      if (RELU == 2) t = t / (1.f + __expf(-t));
-      else if (RELU == 1) { t = fmaxf(t, 0.f); if (relu_cap > 0.f) t = fminf(t, relu_cap); }
-      v.v[e] = t;
-      bits |= (from_f32<T>(t) != 0 && t > 0.f ? 1u : 0u) << e;   // bit = (stored y > 0)
-    }
-    v.store(y + i * EPC);
-    if (mask_bits) mask_bits[i] = (uint8_t)bits;   // one byte per 16-byte chunk: the ReLU mask for backward
-  }
-}
-
-template <typename T>
-int bn_apply(const T* x, const T* res, const float* scale, const float* shift, const float* rscale,
-             const float* rshift, T* y, size_t rows, int C, bool relu, hipStream_t st, uint8_t* mask_bits,
-             float relu_cap) {
-  constexpr int EPC = DT<T>::EPC;
-  ARG_CHECK(C % EPC == 0, "bn_apply: C=%d", C);
-  size_t nch = rows * (C / EPC);
-  int grid = ew_grid(nch);
-  int mode = res ? (rscale ? 2 : 1) : 0;
-#ifdef MMSKIN_ABLATE   // `make ablate` only: upper bound of folding the plain BN + ReLU apply into its consumers (wrong results, valid timing)
-  { static const int abl = [] { const char* v = getenv("MMSKIN_BN_ABLATE"); return v ? atoi(v) : 0; }(); if ((abl & 1) && mode == 0 && relu) return MMSKIN_OK; }
-#endif
-#define LAUNCH(R, H) hipLaunchKernelGGL((bn_apply_kernel<T, R, H>), dim3(grid), dim3(EW_BLOCK), 0, st, x, res, scale, shift, rscale, rshift, y, mask_bits, nch, C / EPC, relu_cap)
-  if (relu && relu_cap < 0.f) { if (mode == 2) LAUNCH(2, 2); else if (mode == 1) LAUNCH(2, 1); else LAUNCH(2, 0); }
-  else if (relu) {
-#define LAUNCH_NT(R, H) hipLaunchKernelGGL((bn_apply_kernel<T, R, H, true>), dim3(grid), dim3(EW_BLOCK), 0, st, x, res, scale, shift, rscale, rshift, y, mask_bits, nch, C / EPC, relu_cap)
-    if (mode == 2) LAUNCH_NT(1, 2); else if (mode == 1) LAUNCH_NT(1, 1); else LAUNCH_NT(1, 0);
-#undef LAUNCH_NT
-  }
-  else { if (mode == 2) LAUNCH(0, 2); else if (mode == 1) LAUNCH(0, 1); else LAUNCH(0, 0); }
-#undef LAUNCH
-  HIP_CHECK_RET(hipGetLastError());
-  return MMSKIN_OK;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void column_stats_kernel(const T* __restrict__ x, size_t rows, int C,
-                                                           ColGeom g, float* partial_sum, float* partial_sq) {
-  constexpr int EPC = DT<T>::EPC;
-  __shared__ float red[2 * 256 * EPC];
-  const int cx = threadIdx.x % g.CW, ry = threadIdx.x / g.CW;
-  const int col = blockIdx.y * g.CW + cx;
-  float acc[2][EPC];
-#pragma unroll
-  for (int e = 0; e < EPC; ++e) { acc[0][e] = 0.f; acc[1][e] = 0.f; }
-  if (ry < g.RL && col < g.CPR) {
-    size_t r_end = (size_t)(blockIdx.x + 1) * g.RB;
-    if (r_end > rows) r_end = rows;
-    for (size_t r = (size_t)blockIdx.x * g.RB + ry; r < r_end; r += g.RL) {
-      Chunk<T> v;
-      v.load(x + (r * g.CPR + col) * EPC);
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) { acc[0][e] += v.v[e]; acc[1][e] += v.v[e] * v.v[e]; }
-    }
-  }
-  // two quantities into two separate slabs: reuse the NQ=1 reducer twice
-  float a1[1][EPC], a2[1][EPC];
-#pragma unroll
-  for (int e = 0; e < EPC; ++e) { a1[0][e] = acc[0][e]; a2[0][e] = acc[1][e]; }
-  block_col_reduce<EPC, 1>(a1, cx, ry, g.CW, g.RL, col, g.CPR, C, partial_sum, red);
-  __syncthreads();
-  block_col_reduce<EPC, 1>(a2, cx, ry, g.CW, g.RL, col, g.CPR, C, partial_sq, red);
-}
-
-int column_stats_rows(size_t rows, int C) {
-  ColGeom a = col_geom(rows, C, 4), b = col_geom(rows, C, 8);
-  return a.gx > b.gx ? a.gx : b.gx;
-}
-template <typename T>
-int column_stats(const T* x, size_t rows, int C, float* stat_sum, float* stat_sq, int* nrows_out,
-                 hipStream_t st) {
-  ARG_CHECK(C % DT<T>::EPC == 0, "column_stats: C=%d", C);
-  ColGeom g = col_geom(rows, C, DT<T>::EPC);
-  hipLaunchKernelGGL(column_stats_kernel<T>, dim3(g.gx, g.gy), dim3(256), 0, st, x, rows, C, g, stat_sum, stat_sq);
-  HIP_CHECK_RET(hipGetLastError());
-  *nrows_out = g.gx;
-  return MMSKIN_OK;
-}
-
-// ------------------------------------------------------------------ BN backward
-template <typename T, int MODE>
-__device__ __forceinline__ void masked_dy(Chunk<T>& dz, const Chunk<T>& xv, const T* ymask, size_t off,
-                                          const float* scale, const float* shift, int c0) {
-  constexpr int EPC = DT<T>::EPC;
-  if (MODE == MASK_FROM_X) {
-#pragma unroll
-    for (int e = 0; e < EPC; ++e)
-      if (!(xv.v[e] * scale[c0 + e] + shift[c0 + e] > 0.f)) dz.v[e] = 0.f;
-  } else if (MODE == MASK_FROM_Y) {
-    Chunk<T> yv;
-    yv.load(ymask + off);
-#pragma unroll
-    for (int e = 0; e < EPC; ++e)
-      if (!(yv.v[e] > 0.f)) dz.v[e] = 0.f;
-  } else if (MODE == MASK_FROM_Y6) {
-    Chunk<T> yv;
-    yv.load(ymask + off);
-#pragma unroll
-    for (int e = 0; e < EPC; ++e)
-      if (!(yv.v[e] > 0.f && yv.v[e] < 6.f)) dz.v[e] = 0.f;
-  } else if (MODE == MASK_SILU_X) {
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) {
-      const float t = xv.v[e] * scale[c0 + e] + shift[c0 + e];
-      const float sg = 1.f / (1.f + __expf(-t));
-      dz.v[e] *= sg * (1.f + t * (1.f - sg));
-    }
-  }
-}
-
-template <typename T, int MODE>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict__ dy, const T* __restrict__ x,
-                                                            const T* __restrict__ ymask,
-                                                            const float* __restrict__ scale,
-                                                            const float* __restrict__ shift, size_t rows, int C,
-                                                            ColGeom g, float* partial) {
-  constexpr int EPC = DT<T>::EPC;
-  __shared__ float red[2 * 256 * EPC];
-  const int cx = threadIdx.x % g.CW, ry = threadIdx.x / g.CW;
-  const int col = blockIdx.y * g.CW + cx;
-  float acc[2][EPC];
-#pragma unroll
-  for (int e = 0; e < EPC; ++e) { acc[0][e] = 0.f; acc[1][e] = 0.f; }
-  if (ry < g.RL && col < g.CPR) {
-    size_t r_end = (size_t)(blockIdx.x + 1) * g.RB;
-    if (r_end > rows) r_end = rows;
-    const int c0 = col * EPC;
-    for (size_t r = (size_t)blockIdx.x * g.RB + ry; r < r_end; r += g.RL) {
-      size_t off = (r * g.CPR + col) * EPC;
-      Chunk<T> dz, xv;
-      dz.load(dy + off);
-      xv.load(x + off);
-      masked_dy<T, MODE>(dz, xv, ymask, off, scale, shift, c0);
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) { acc[0][e] += dz.v[e]; acc[1][e] += dz.v[e] * xv.v[e]; }
-    }
-  }
-  block_col_reduce<EPC, 2>(acc, cx, ry, g.CW, g.RL, col, g.CPR, C, partial, red);
-}
-
-int bn_bwd_partial_rows(size_t rows, int C) { return column_stats_rows(rows, C); }
-
-template <typename T>
-int bn_bwd_reduce(const T* dy, const T* x, const T* ymask, const float* scale, const float* shift,
-                  int mask_mode, size_t rows, int C, float* partial, int* nrows_out, hipStream_t st) {
-  ARG_CHECK(C % DT<T>::EPC == 0, "bn_bwd_reduce: C=%d", C);
-  ColGeom g = col_geom(rows, C, DT<T>::EPC);
-#define LAUNCH(M) hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, M>), dim3(g.gx, g.gy), dim3(256), 0, st, dy, x, ymask, scale, shift, rows, C, g, partial)
-  if (mask_mode == MASK_FROM_X) LAUNCH(MASK_FROM_X);
-  else if (mask_mode == MASK_FROM_Y) LAUNCH(MASK_FROM_Y);
-  else if (mask_mode == MASK_FROM_Y6) LAUNCH(MASK_FROM_Y6);
-  else if (mask_mode == MASK_SILU_X) LAUNCH(MASK_SILU_X);
-  else LAUNCH(MASK_NONE);
-#undef LAUNCH
-  HIP_CHECK_RET(hipGetLastError());
-  *nrows_out = g.gx;
-  return MMSKIN_OK;
-}
-
-// channel c's BatchNorm-backward coefficients (dz = cA g + cB x + cC) and parameter gradients from s1 = sum dz, s2 = sum dz x
-__device__ __forceinline__ void bn_bwd_coeffs(int c, double s1, double s2, double count, const float* __restrict__ gamma, const float* __restrict__ mean,
-                                              const float* __restrict__ invstd, float* dgamma, float* dbeta, float* cA, float* cB, float* cC, int n_grad,
-                                              int acc_bc, const float* __restrict__ s2_override) {
-  if (s2_override) s2 = (double)s2_override[c];
-  double mu = mean[c], is = invstd[c], g = gamma ? gamma[c] : 1.0;
-  double dg = is * (s2 - mu * s1);   // sum dz * xhat
-  if (dgamma && c < n_grad) dgamma[c] = (float)dg;
-  if (dbeta && c < n_grad) dbeta[c] = (float)s1;
-  double A = g * is;
-  cA[c] = (float)A;
-  const float vb = (float)(-A * is * dg / count), vc = (float)(A * (-s1 / count + mu * is * dg / count));
-  if (acc_bc) { cB[c] += vb; cC[c] += vc; }   // running sums over the consumers of a shared input (DenseNet's deferred x / constant terms)
-  else { cB[c] = vb; cC[c] = vc; }
-}
-// CB columns x RL row lanes per block.  CB = 16 (256 threads, 4 KB of LDS) is the backward pass's form: a block that small fits on a CU
-// beside a weight-gradient ring workgroup of the other stream (208 VGPRs x 8 waves, 121 - 132 KB of LDS), where the 1024-thread form
-// waited for a ring workgroup to retire -- i.e. for the whole weight-gradient launch (profiles/r04_experiments.txt (8)).
-template <typename IN, int RL = 4, int CB = 64>
-__global__ __launch_bounds__(CB * RL) void bn_bwd_finalize_kernel(const IN* __restrict__ partial, int nrows, int C, double count,
-                                       const float* __restrict__ gamma, const float* __restrict__ mean,
-                                       const float* __restrict__ invstd, float* dgamma, float* dbeta,
-                                       float* cA, float* cB, float* cC, int n_grad, int acc_bc, const float* __restrict__ s2_override = nullptr) {
-  __shared__ double red[2][RL][CB];
-  const int cx = threadIdx.x % CB, ry = threadIdx.x / CB;
-  const int c = blockIdx.x * CB + cx;
-  double s1 = 0.0, s2 = 0.0;
-  if (c < C) {
-    int r = ry;
-    double t1 = 0.0, t2 = 0.0, u1 = 0.0, u2 = 0.0, v1 = 0.0, v2 = 0.0;
-    for (; r + 3 * RL < nrows; r += 4 * RL) {     // four independent chains per lane (eight loads in flight)
-      s1 += (double)partial[((size_t)r * 2) * C + c];
-      s2 += (double)partial[((size_t)r * 2 + 1) * C + c];
-      t1 += (double)partial[((size_t)(r + RL) * 2) * C + c];
-      t2 += (double)partial[((size_t)(r + RL) * 2 + 1) * C + c];
-      u1 += (double)partial[((size_t)(r + 2 * RL) * 2) * C + c];
-      u2 += (double)partial[((size_t)(r + 2 * RL) * 2 + 1) * C + c];
-      v1 += (double)partial[((size_t)(r + 3 * RL) * 2) * C + c];
-      v2 += (double)partial[((size_t)(r + 3 * RL) * 2 + 1) * C + c];
-    }
-    for (; r < nrows; r += RL) { s1 += (double)partial[((size_t)r * 2) * C + c]; s2 += (double)partial[((size_t)r * 2 + 1) * C + c]; }
-    s1 = (s1 + t1) + (u1 + v1); s2 = (s2 + t2) + (u2 + v2);
-  }
-  red[0][ry][cx] = s1; red[1][ry][cx] = s2;
-  __syncthreads();
-  if (ry == 0 && c < C) {
-    s1 = 0.0; s2 = 0.0;
-#pragma unroll
-    for (int i = 0; i < RL; ++i) { s1 += red[0][i][cx]; s2 += red[1][i][cx]; }
-    bn_bwd_coeffs(c, s1, s2, count, gamma, mean, invstd, dgamma, dbeta, cA, cB, cC, n_grad, acc_bc, s2_override);
-  }
-}
-int bn_bwd_finalize(const float* partial, int nrows, int C, double count, const float* gamma,
-                    const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta,
-                    float* cA, float* cB, float* cC, double* scratch, hipStream_t st, int n_grad, bool accumulate_bc, const float* sum_dz_x) {
-  if (n_grad < 0) n_grad = C;
-  const int acc_bc = accumulate_bc ? 1 : 0;
-  if (scratch && nrows > BN_SINGLE_STAGE_ROWS) {
-    const int G = reduce_groups(nrows);
-    int rc = partial_reduce<double>(partial, nullptr, nrows, 2 * C, G, scratch, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel<double>, dim3(ceil_div(C, 64)), dim3(256), 0, st, scratch, G, C, count,
-                       gamma, save_mean, save_invstd, dgamma, dbeta, cA, cB, cC, n_grad, acc_bc, sum_dz_x);
-  } else if (nrows > 64) {
-    hipLaunchKernelGGL((bn_bwd_finalize_kernel<float, 16, 16>), dim3(ceil_div(C, 16)), dim3(256), 0, st, partial, nrows, C, count,
-                       gamma, save_mean, save_invstd, dgamma, dbeta, cA, cB, cC, n_grad, acc_bc, sum_dz_x);
-  } else {
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel<float>, dim3(ceil_div(C, 64)), dim3(256), 0, st, partial, nrows, C, count,
-                       gamma, save_mean, save_invstd, dgamma, dbeta, cA, cB, cC, n_grad, acc_bc, sum_dz_x);
-  }
-  HIP_CHECK_RET(hipGetLastError());
-  return MMSKIN_OK;
-}
-
-template <typename T, int MODE, bool WRITE_DZ, bool NT = false>
-__global__ __launch_bounds__(EW_BLOCK) void bn_bwd_apply_kernel(
-    const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ ymask,
-    const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ cA,
-    const float* __restrict__ cB, const float* __restrict__ cC, T* __restrict__ dx, T* __restrict__ dz_out,
-    size_t nchunks, int CPR) {
-  constexpr int EPC = DT<T>::EPC;
-  for (size_t i = blockIdx.x * (size_t)EW_BLOCK + threadIdx.x; i < nchunks; i += (size_t)gridDim.x * EW_BLOCK) {
-    const int c0 = (int)(i % CPR) * EPC;
-    const size_t off = i * EPC;
-    Chunk<T> dz, xv;
-    if (NT) { dz.load_nt(dy + off); xv.load_nt(x + off); } else { dz.load(dy + off); xv.load(x + off); }
-    masked_dy<T, MODE>(dz, xv, ymask, off, scale, shift, c0);
-    if (WRITE_DZ) dz.store(dz_out + off);
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) xv.v[e] = cA[c0 + e] * dz.v[e] + cB[c0 + e] * xv.v[e] + cC[c0 + e];
-    xv.store(dx + off);
-  }
-}
-
-template <typename T>
-int bn_bwd_apply(const T* dy, const T* x, const T* ymask, const float* scale, const float* shift,
-                 int mask_mode, const float* cA, const float* cB, const float* cC, T* dx, T* dz_out,
-                 size_t rows, int C, hipStream_t st) {
-  constexpr int EPC = DT<T>::EPC;
-  ARG_CHECK(C % EPC == 0, "bn_bwd_apply: C=%d", C);
-  size_t nch = rows * (C / EPC);
-  int grid = ew_grid(nch);
-#ifdef MMSKIN_ABLATE   // `make ablate` only: upper bound of folding the BN-backward apply into the dgrad / weight-gradient operand loads
-  { static const int abl = [] { const char* v = getenv("MMSKIN_BN_ABLATE"); return v ? atoi(v) : 0; }(); if ((abl & 2) && mask_mode == MASK_NONE && !dz_out) return MMSKIN_OK; }
-#endif
-#define LAUNCH(M, W) hipLaunchKernelGGL((bn_bwd_apply_kernel<T, M, W>), dim3(grid), dim3(EW_BLOCK), 0, st, dy, x, ymask, scale, shift, cA, cB, cC, dx, dz_out, nch, C / EPC)
-  if (mask_mode == MASK_FROM_X) { if (dz_out) LAUNCH(MASK_FROM_X, true); else LAUNCH(MASK_FROM_X, false); }
-  else if (mask_mode == MASK_FROM_Y) { if (dz_out) LAUNCH(MASK_FROM_Y, true); else LAUNCH(MASK_FROM_Y, false); }
-  else if (mask_mode == MASK_FROM_Y6) { if (dz_out) LAUNCH(MASK_FROM_Y6, true); else LAUNCH(MASK_FROM_Y6, false); }
-  else if (mask_mode == MASK_SILU_X) { if (dz_out) LAUNCH(MASK_SILU_X, true); else LAUNCH(MASK_SILU_X, false); }
-  else {
-    // nontemporal loads of dz / x (each is read for the last time here; dx stays cacheable: the dgrad and the weight-gradient
-    // GEMM read it next): same-box A/B 20.74 -> 20.43 ms per step (cacheable / nontemporal, profiles/r02_experiments.txt)
-    if (dz_out) LAUNCH(MASK_NONE, true);
-    else hipLaunchKernelGGL((bn_bwd_apply_kernel<T, MASK_NONE, false, true>), dim3(grid), dim3(EW_BLOCK), 0, st, dy, x, ymask, scale, shift, cA, cB, cC, dx, dz_out, nch, C / EPC);
-  }
-#undef LAUNCH
-  HIP_CHECK_RET(hipGetLastError());
-  return MMSKIN_OK;
-}
+#include "ops_internal.h"
 
 // ------------------------------------------------------------------ stem
 template <typename T>
@@ -1070,24 +533,6 @@ int stage_weights(const StageDesc* table_dev, int nlayers, int max_elems, const 
   return MMSKIN_OK;
 }
 
-__global__ void bn_eval_table_kernel(const StageDesc* __restrict__ table, const float* __restrict__ params,
-                                     const float* __restrict__ buffers, unsigned char* ws, float eps) {
-  const StageDesc d = table[blockIdx.y];
-  if (!d.has_bn) return;
-  float* coef = reinterpret_cast<float*>(ws + d.coef_off);
-  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < d.Cout; c += gridDim.x * blockDim.x) {
-    float sc = params[d.bn_g_off + c] / sqrtf(buffers[d.bn_rv_off + c] + eps);
-    coef[c] = sc;
-    coef[d.Cout + c] = params[d.bn_b_off + c] - buffers[d.bn_rm_off + c] * sc;
-  }
-}
-int bn_eval_table(const StageDesc* table_dev, int nlayers, int maxC, const float* params, const float* buffers,
-                  unsigned char* ws, float eps, hipStream_t st) {
-  hipLaunchKernelGGL(bn_eval_table_kernel, dim3(ceil_div(maxC, 256), nlayers), dim3(256), 0, st, table_dev, params, buffers, ws, eps);
-  HIP_CHECK_RET(hipGetLastError());
-  return MMSKIN_OK;
-}
-
 __global__ void stem_wgrad_unpack_kernel(const float* __restrict__ dwv, float* __restrict__ dw) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;  // over 64*3*7*7
   if (i < 64 * 147) {
@@ -1142,10 +587,6 @@ int nhwc_to_nchw(const T* src, int N, int C, int H, int W, float* dst, hipStream
 }
 
 #define INST(T)                                                                                               \
-  template int bn_apply<T>(const T*, const T*, const float*, const float*, const float*, const float*, T*, size_t, int, bool, hipStream_t, uint8_t*, float); \
-  template int column_stats<T>(const T*, size_t, int, float*, float*, int*, hipStream_t);                       \
-  template int bn_bwd_reduce<T>(const T*, const T*, const T*, const float*, const float*, int, size_t, int, float*, int*, hipStream_t); \
-  template int bn_bwd_apply<T>(const T*, const T*, const T*, const float*, const float*, int, const float*, const float*, const float*, T*, T*, size_t, int, hipStream_t); \
   template int stem_pack<T>(const float*, int, int, int, int, int, T*, hipStream_t);                            \
   template int stem_pack_u8<T>(const uint8_t*, int, int, int, int, int, const float*, T*, hipStream_t);        \
   template int stem_bn_relu_pool<T>(const T*, const float*, const float*, int, int, int, int, T*, uint8_t*, hipStream_t); \
@@ -1297,119 +738,6 @@ int slice_affine_inplace(T* d, const T* x, int pitch, int C, size_t rows, const 
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void slice_stats_kernel(const T* __restrict__ x, int pitch, size_t rows, int C,
-                                                          ColGeom g, float* partial_sum, float* partial_sq) {
-  constexpr int EPC = DT<T>::EPC;
-  __shared__ float red[2 * 256 * EPC];
-  const int cx = threadIdx.x % g.CW, ry = threadIdx.x / g.CW;
-  const int col = blockIdx.y * g.CW + cx;
-  float acc[2][EPC];
-#pragma unroll
-  for (int e = 0; e < EPC; ++e) { acc[0][e] = 0.f; acc[1][e] = 0.f; }
-  if (ry < g.RL && col < g.CPR) {
-    size_t r_end = (size_t)(blockIdx.x + 1) * g.RB;
-    if (r_end > rows) r_end = rows;
-    for (size_t r = (size_t)blockIdx.x * g.RB + ry; r < r_end; r += g.RL) {
-      Chunk<T> v;
-      v.load(x + r * pitch + (size_t)col * EPC);
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) { acc[0][e] += v.v[e]; acc[1][e] += v.v[e] * v.v[e]; }
-    }
-  }
-  block_col_reduce<EPC, 2>(acc, cx, ry, g.CW, g.RL, col, g.CPR, C, partial_sum, red);
-}
-// NOTE: partial layout here is the interleaved [row][2][C] of block_col_reduce<.,2>; stat_sum points at
-// it and stat_sq is unused by the kernel -- bn_table_finalize is told through stride / offsets.
-template <typename T>
-int slice_stats(const T* x, int pitch, int C, size_t rows, float* stat_sum, float* stat_sq, int* nrows_out,
-                hipStream_t st) {
-  ARG_CHECK(C % DT<T>::EPC == 0 && pitch % DT<T>::EPC == 0, "slice_stats: C=%d pitch=%d", C, pitch);
-  ARG_CHECK(stat_sq == stat_sum + C, "slice_stats: stat_sq must be stat_sum + C (interleaved [row][2][C] slab)");
-  ColGeom g = col_geom(rows, C, DT<T>::EPC);
-  hipLaunchKernelGGL(slice_stats_kernel<T>, dim3(g.gx, g.gy), dim3(256), 0, st, x, pitch, rows, C, g, stat_sum, stat_sq);
-  HIP_CHECK_RET(hipGetLastError());
-  *nrows_out = g.gx;
-  return MMSKIN_OK;
-}
-
-template <typename IN>
-__global__ __launch_bounds__(1024) void bn_table_finalize_kernel(const IN* __restrict__ ssum, const IN* __restrict__ ssq, int nrows, int stride,
-                                         int C, double count, float* __restrict__ mean, float* __restrict__ var) {
-  // 64 columns x 16 row lanes (a DenseNet growth slice has 32 channels: with 4 lanes one workgroup walked up to 512 rows in 18 us)
-  __shared__ double red[2][16][64];
-  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + cx;
-  double s = 0.0, q = 0.0;
-  if (c < C)
-    for (int r = ry; r < nrows; r += 16) { s += (double)ssum[(size_t)r * stride + c]; q += (double)ssq[(size_t)r * stride + c]; }
-  red[0][ry][cx] = s; red[1][ry][cx] = q;
-  __syncthreads();
-  if (ry == 0 && c < C) {
-    s = 0.0; q = 0.0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) { s += red[0][k][cx]; q += red[1][k][cx]; }
-    double m = s / count, v = q / count - m * m;
-    mean[c] = (float)m;
-    var[c] = (float)(v < 0.0 ? 0.0 : v);
-  }
-}
-int bn_table_finalize(const float* stat_sum, const float* stat_sq, int nrows, int stride, int C, double count,
-                      float* mean, float* var, double* scratch, hipStream_t st) {
-  const bool interleaved = stat_sq == stat_sum + C && stride == 2 * C;   // slice_stats slab
-  if (scratch && nrows > BN_SINGLE_STAGE_ROWS) {
-    const int G = reduce_groups(nrows);
-    int rc;
-    if (interleaved) {
-      if ((rc = partial_reduce<double>(stat_sum, nullptr, nrows, stride, G, scratch, st))) return rc;
-      hipLaunchKernelGGL(bn_table_finalize_kernel<double>, dim3(ceil_div(C, 64)), dim3(1024), 0, st, scratch, scratch + C, G,
-                         stride, C, count, mean, var);
-    } else {
-      if ((rc = partial_reduce<double>(stat_sum, stat_sq, nrows, stride, G, scratch, st))) return rc;
-      hipLaunchKernelGGL(bn_table_finalize_kernel<double>, dim3(ceil_div(C, 64)), dim3(1024), 0, st, scratch,
-                         scratch + (size_t)G * stride, G, stride, C, count, mean, var);
-    }
-  } else {
-    hipLaunchKernelGGL(bn_table_finalize_kernel<float>, dim3(ceil_div(C, 64)), dim3(1024), 0, st, stat_sum, stat_sq, nrows,
-                       stride, C, count, mean, var);
-  }
-  HIP_CHECK_RET(hipGetLastError());
-  return MMSKIN_OK;
-}
-
-__global__ void bn_coef_from_table_kernel(const float* __restrict__ mean_tab, const float* __restrict__ var_tab, int C,
-                                          int Cp, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                          float eps, float momentum, double count, float* running_mean,
-                                          float* running_var, int training, float* __restrict__ coef) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= Cp) return;
-  float sc = 0.f, sh = 0.f, mu = 0.f, is = 0.f, g = 0.f;
-  if (c < C) {
-    g = gamma[c];
-    float var;
-    if (training) {
-      mu = mean_tab[c]; var = var_tab[c];
-      double unbiased = count > 1.0 ? (double)var * count / (count - 1.0) : (double)var;
-      running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mu;
-      running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-    } else {
-      mu = running_mean[c]; var = running_var[c];
-    }
-    is = (float)(1.0 / sqrt((double)var + (double)eps));
-    sc = g * is;
-    sh = beta[c] - mu * sc;
-  }
-  coef[c] = sc; coef[Cp + c] = sh; coef[2 * Cp + c] = mu; coef[3 * Cp + c] = is; coef[4 * Cp + c] = g;
-}
-int bn_coef_from_table(const float* mean_tab, const float* var_tab, int C, int Cp, const float* gamma,
-                       const float* beta, float eps, float momentum, double count, float* running_mean,
-                       float* running_var, bool training, float* coef, hipStream_t st) {
-  hipLaunchKernelGGL(bn_coef_from_table_kernel, dim3(ceil_div(Cp, 256)), dim3(256), 0, st, mean_tab, var_tab, C, Cp,
-                     gamma, beta, eps, momentum, count, running_mean, running_var, training ? 1 : 0, coef);
-  HIP_CHECK_RET(hipGetLastError());
-  return MMSKIN_OK;
-}
-
-template <typename T>
 __global__ __launch_bounds__(EW_BLOCK) void avgpool2_fwd_kernel(const T* __restrict__ x, int H, int W, int CPR,
                                                                 T* __restrict__ dst, int pitch, size_t nchunks) {
   constexpr int EPC = DT<T>::EPC;
@@ -1478,7 +806,6 @@ int avgpool2_bwd(const T* dpool, int pitch, int N, int H, int W, int C, T* dx, h
   template int slice_accumulate_scaled<T>(T*, int, int, const T*, int, const float*, size_t, hipStream_t);       \
   template int slice_pack_deferred<T>(const T*, const T*, int, int, int, size_t, const float*, const float*, T*, hipStream_t); \
   template int slice_affine_inplace<T>(T*, const T*, int, int, size_t, const float*, const float*, hipStream_t); \
-  template int slice_stats<T>(const T*, int, int, size_t, float*, float*, int*, hipStream_t);                     \
   template int avgpool2_fwd<T>(const T*, int, int, int, int, T*, int, hipStream_t);                               \
   template int avgpool2_bwd<T>(const T*, int, int, int, int, int, T*, hipStream_t);
 INST_SLICE(float)
@@ -1695,31 +1022,6 @@ template <typename T>
 int adaptive_avgpool_bwd(const float* dout_nchw, int N, int H, int W, int C, int OH, int OW, T* dx, hipStream_t st) {
   hipLaunchKernelGGL(adaptive_avgpool_bwd_kernel<T>, dim3(ew_grid((size_t)N * H * W * C)), dim3(256), 0, st, dout_nchw, N, H, W, C,
                      OH, OW, dx);
-  HIP_CHECK_RET(hipGetLastError());
-  return MMSKIN_OK;
-}
-
-template <typename IN>
-__global__ void bias_grad_finalize_kernel(const IN* __restrict__ part, int nrows, int stride, int C, float* __restrict__ db) {
-  __shared__ double red[4][64];
-  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + cx;
-  double s = 0.0;
-  if (c < C)
-    for (int r = ry; r < nrows; r += 4) s += (double)part[(size_t)r * stride + c];
-  red[ry][cx] = s;
-  __syncthreads();
-  if (ry == 0 && c < C) db[c] = (float)((red[0][cx] + red[1][cx]) + (red[2][cx] + red[3][cx]));
-}
-int bias_grad_finalize(const float* partial, int nrows, int stride, int C, float* db, double* scratch, hipStream_t st) {
-  if (scratch && nrows > BN_SINGLE_STAGE_ROWS) {
-    const int G = reduce_groups(nrows);
-    int rc = partial_reduce<double>(partial, nullptr, nrows, stride, G, scratch, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(bias_grad_finalize_kernel<double>, dim3(ceil_div(C, 64)), dim3(256), 0, st, scratch, G, stride, C, db);
-  } else {
-    hipLaunchKernelGGL(bias_grad_finalize_kernel<float>, dim3(ceil_div(C, 64)), dim3(256), 0, st, partial, nrows, stride, C, db);
-  }
   HIP_CHECK_RET(hipGetLastError());
   return MMSKIN_OK;
 }

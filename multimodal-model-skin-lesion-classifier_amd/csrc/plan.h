@@ -268,7 +268,7 @@ struct BnBwdCoef {
 // caller's byte count.
 template <typename T>
 int bn_backward_from_sums(const T* dz, const T* x, const float* partial, int nrows, size_t rows, int C, const BnCoef& k, const float* gamma,
-                          float* dgamma, float* dbeta, const BnBwdCoef& c, double* red, T* dx, Profiler* prof, double prof_bytes,
+                          float* dgamma, float* dbeta, const BnBwdCoef& c, ColScratch red, T* dx, Profiler* prof, double prof_bytes,
                           hipStream_t st, int n_grad = -1, bool accumulate_bc = false, const float* sum_dz_x = nullptr) {
   ProfScope scope(prof, K_BN_BWD, st, 0.0, prof_bytes);
   if (int rc = bn_bwd_finalize(partial, nrows, C, (double)rows, gamma, k.mean, k.invstd, dgamma, dbeta, c.cA, c.cB, c.cC, red, st, n_grad,
@@ -280,7 +280,7 @@ int bn_backward_from_sums(const T* dz, const T* x, const float* partial, int nro
 // masked dy).  One profiler pair with the caller's byte count.
 template <typename T>
 int bn_backward(const T* dy, const T* x, const T* ymask, int mode, size_t rows, int C, const BnCoef& k, const float* gamma, float* dgamma,
-                float* dbeta, const BnBwdCoef& c, float* partial, double* red, T* dx, T* dz, Profiler* prof, double prof_bytes,
+                float* dbeta, const BnBwdCoef& c, float* partial, ColScratch red, T* dx, T* dz, Profiler* prof, double prof_bytes,
                 hipStream_t st, int n_grad = -1) {
   ProfScope scope(prof, K_BN_BWD, st, 0.0, prof_bytes);
   int nr = 0;
@@ -317,7 +317,7 @@ struct StemBufs {
   uint8_t* idx = nullptr;    // argmax tap of every pooled element
   float* coef = nullptr;     // BnCoef block (4 slots)
   float *ssum = nullptr, *ssq = nullptr;   // batch-statistics slabs of the conv epilogue
-  double* red = nullptr;     // reduction scratch of the finalize kernels
+  ColScratch red;            // reduction scratch of the finalize kernels
   // backward
   float* coefbwd = nullptr;  // BnBwdCoef block
   float* partial = nullptr;  // BatchNorm-backward partial sums
@@ -481,7 +481,7 @@ struct DenseRun {
   float* grads = nullptr;          // backward
   T *wf = nullptr, *wd = nullptr;  // staged weights
   float *stat_sum = nullptr, *stat_sq = nullptr;   // batch-statistics slabs
-  double* red = nullptr;
+  ColScratch red;                  // reduction scratch of the finalize kernels
   T* sBq[2] = {nullptr, nullptr};  // conv2 output / gradient, padded to 64 channels (forward uses [0]); alternate between layers
   T* sAq[2] = {nullptr, nullptr};  // gradient of conv1's output
   T *sU = nullptr, *sZ = nullptr, *sC = nullptr;   // gradient of u; of the padded prefix t; the transition conv's output / its gradient

@@ -94,6 +94,8 @@ _SIGNATURES = {
     "mmskin_dense_transition_forward": (_i, [_P] * 6 + [_i] * 7 + [_P, _P]),
     "mmskin_dense_transition_backward": (_i, [_P] * 7 + [_i] * 6 + [_P, _P]),
     "mmskin_slice_stats_workspace_bytes": (_i64, [_i64, _i, _i, _i]),
+    "mmskin_col_reduce_scratch_doubles": (_i64, [_i64]),
+    "mmskin_col_reduce_scratch_check": (_i, [_i, _i, _i, _i64]),
     "mmskin_slice_stats": (_i, [_P, _i64, _i, _i, _i, _P, _P, _i, _P, _P]),
     "mmskin_maxpool2_relu_workspace_bytes": (_i64, [_i] * 4),
     "mmskin_maxpool2_relu_forward": (_i, [_P] * 3 + [_i] * 5 + [_P, _P]),

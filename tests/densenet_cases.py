@@ -20,7 +20,7 @@ from mbconv_cases import EPC, rb
 
 GROWTH, BOTTLE, EPS, MOM = 32, 128, 1e-5, 0.1
 DENSE_DEPTHS = (6, 12, 32, 32)
-BN_SINGLE_STAGE_ROWS = 512            # ops.hip: more partial rows than this take bn_table_finalize's two-stage branch
+BN_SINGLE_STAGE_ROWS = 512            # bn.hip: more partial rows than this take the finalize entries' two-stage path
 
 
 def pad64(c):
@@ -73,7 +73,7 @@ def slice_id(c):
 
 
 def col_geom(rows, C, epc):
-    """col_geom of ops.hip -> (RL row lanes, RB rows per block, gx row blocks = partial rows)"""
+    """col_geom of ops_internal.h -> (RL row lanes, RB rows per block, gx row blocks = partial rows)"""
     cpr = C // epc
     cw = 256 if cpr >= 256 else cpr
     rl = 256 // cw

@@ -10,6 +10,10 @@ Bounds (the project's existing ones).
   bf16, chains: relative L2 distance from the fp64 truth at most 1.5 x the distance of the CPU emulation (fp64 arithmetic rounded to bf16
         where the plan stores a T) from the same truth -- the factor of test_gpu_densenet.py -- per tensor, per slice and per layer, no
         median.  Both distances go to the parity report (test_gpu_abn.REPORT)."""
+import os
+import subprocess
+import sys
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -223,6 +227,16 @@ def test_slice_stats_and_table_finalize(case):
     rec = dict(test="slice_stats", case=slice_id(c), mean=rel_err(mean, mean_ref), var=rel_err(var, var_ref))
     report(**rec)
     assert rec["mean"] < SUMS and rec["var"] < SUMS, rec   # inputs are exact in both element types: one bound
+
+
+def test_slice_stats_cases_on_the_two_stage_reduction():
+    """MMSKIN_BN_SINGLE_ROWS=1 (read once per process -> fresh interpreter) sends every row of SLICE_CASES that leaves more than one partial
+    row through partial_reduce + the table epilogue on the interleaved slab: G = 1 for the 70-row fp32 case (2 partial rows), G = 4 for the
+    12 805-row case (101), G = 64 for the two long ones as before."""
+    env = dict(os.environ, MMSKIN_BN_SINGLE_ROWS="1")
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", os.path.abspath(__file__), "-k", "test_slice_stats_and_table_finalize"],
+                       env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and " passed" in r.stdout and "skipped" not in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
 
 
 def test_unsupported_arguments_are_refused_before_any_launch():

@@ -90,12 +90,13 @@ def test_conv_bf16_tight_on_representable_inputs(case):
 
 def test_batchnorm_two_stage_reduction():
     """Statistics tables above MMSKIN_BN_SINGLE_ROWS rows take two reduction stages (partial_reduce + finalize): MMSKIN_BN_SINGLE_ROWS=4 sends
-    every case of test_batchnorm_train_forward_backward through them."""
+    every case of test_batchnorm_train_forward_backward with more than four partial rows through them (G = 1 .. 5 groups), and
+    test_batchnorm_train_forward_backward_reduction_scratch, selected by the same -k, fails there unless the first stage really ran."""
     import subprocess, sys
     env = dict(os.environ, MMSKIN_BN_SINGLE_ROWS="4")
     r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", os.path.abspath(__file__), "-k", "batchnorm_train_forward_backward"],
                        env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert r.returncode == 0 and " passed" in r.stdout and "skipped" not in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
 
 
 def test_conv_rejects_unsupported_shapes():
@@ -105,9 +106,27 @@ def test_conv_rejects_unsupported_shapes():
         conv_forward(x, w, 1, 1, "fp32")
 
 
+def partial_rows(rows, C, epc):
+    """col_geom of csrc/ops_internal.h: the partial rows column_stats / bn_bwd_reduce leave (epc = 4 fp32, 8 bf16 elements per 16-byte chunk)"""
+    cpr = C // epc
+    rl = 256 // min(cpr, 256)
+    rb = max((rows + 1023) // 1024, rl * 4)
+    rb = (rb + rl - 1) // rl * rl
+    return (rows + rb - 1) // rb
+
+
+# The first three leave 4 / 5 / 37 (fp32) and 2 / 5 / 19 (bf16) partial rows: the <= 64-row forms of the finalize kernels.  The last two have
+# 5 * 32 * 52 = 8320 rows.  C = 64: 130 partial rows in fp32 (16 row lanes x 4 rows per lane = 64 rows per block) and 65 in bf16 (32 lanes:
+# 128 per block) -- the smallest counts that put both element types on the 65 .. 512-row forms (64 x 16 forward, 16 x 16 backward).  C = 72:
+# 149 in fp32 (18 chunks per row: 14 lanes, 56 rows per block) and 75 in bf16 (9 chunks: 28 lanes, 112 per block); 72 is a multiple of
+# neither 64 nor 16, so the c < C guard of the last column block is live in the 64-wide and in the 16-wide form.
+BN_TRAIN_SHAPES = [(4, 64, 9, 7), (2, 2048, 3, 3), (3, 256, 14, 14), (5, 64, 32, 52), (5, 72, 32, 52)]
+assert [partial_rows(8320, C, epc) for C in (64, 72) for epc in (4, 8)] == [130, 65, 149, 75]
+
+
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 @pytest.mark.parametrize("relu", [0, 1])
-@pytest.mark.parametrize("shape", [(4, 64, 9, 7), (2, 2048, 3, 3), (3, 256, 14, 14)])
+@pytest.mark.parametrize("shape", BN_TRAIN_SHAPES)
 def test_batchnorm_train_forward_backward(shape, relu, dtype):
     N, C, H, W = shape
     g = torch.Generator().manual_seed(C + relu)
@@ -143,6 +162,41 @@ def test_batchnorm_train_forward_backward(shape, relu, dtype):
     torch.cuda.synchronize()
     assert rel_err(dx, xr.grad) < 3 * tol, rel_err(dx, xr.grad)
     assert rel_err(dg, gr.grad) < 3 * tol and rel_err(db, br.grad) < 3 * tol
+
+
+def test_batchnorm_train_forward_backward_reduction_scratch():
+    """Which reduction the forward's finalize took, read off a workspace poisoned to NaN beforehand.  (5, 72, 32, 52) in fp32 leaves 149 partial
+    rows.  Above MMSKIN_BN_SINGLE_ROWS (test_batchnorm_two_stage_reduction's child: 4) the first stage must have left G = ceil(149 / 32) = 5
+    fp64 group rows per slab at the head of the scratch carve -- the last 2 * 64 * C doubles of the workspace -- which add up to the column sums
+    of x and x^2, with the rest of the carve untouched; at the default (512) the whole carve is untouched.  The statistics are finite and right
+    either way.  Bound on the group sums: they add fp32 partials whose longest chain is 4 rows per lane + 14 lanes = 18 < 64 additions, so
+    each column's error is below 64 * 2^-24 * sum |x| (resp. x^2); the fp64 stages add nothing at that scale."""
+    N, C, H, W = shape = (5, 72, 32, 52)
+    nrows, single = partial_rows(N * H * W, C, 4), int(os.environ.get("MMSKIN_BN_SINGLE_ROWS", "512"))
+    assert nrows == 149
+    x = torch.randn(shape, generator=torch.Generator().manual_seed(7)) * 2 + 0.5
+    lib = _lib.load()
+    wsp = ws(lib.mmskin_batchnorm_workspace_bytes(N, C, H, W))
+    wsp.fill_(0xFF)                                                    # every float and double of the workspace: NaN
+    xd, gd, bd = x.to(DEV), torch.ones(C, device=DEV), torch.zeros(C, device=DEV)
+    rmd, rvd = torch.zeros(C, device=DEV), torch.ones(C, device=DEV)
+    y, sm, si = torch.empty_like(xd), torch.empty(C, device=DEV), torch.empty(C, device=DEV)
+    call("mmskin_batchnorm_forward", ptr(xd), ptr(gd), ptr(bd), ptr(rmd), ptr(rvd), ptr(y), ptr(sm), ptr(si), N, C, H, W, 1e-5, 0.1, 0, DT["fp32"],
+         ptr(wsp), stream())
+    torch.cuda.synchronize()
+    x64 = x.double()
+    assert bool(torch.isfinite(sm).all()) and bool(torch.isfinite(si).all()) and bool(torch.isfinite(y).all())
+    assert rel_err(sm, x64.mean((0, 2, 3))) < TOL["fp32"] and rel_err(si, 1 / torch.sqrt(x64.var((0, 2, 3), unbiased=False) + 1e-5)) < TOL["fp32"]
+    scratch = wsp[-2 * 64 * C * 8:].view(torch.float64).cpu()
+    if nrows > single:
+        G = min(64, (nrows + 31) // 32)
+        head, rest = scratch[:2 * G * C].view(2, G, C), scratch[2 * G * C:]
+        assert bool(torch.isfinite(head).all()), "the first stage left no group sums"
+        for got, v in ((head[0].sum(0), x64), (head[1].sum(0), x64 * x64)):
+            assert bool(((got - v.sum((0, 2, 3))).abs() <= 64 * 2.0 ** -24 * v.abs().sum((0, 2, 3))).all())
+    else:
+        rest = scratch
+    assert bool(torch.isnan(rest).all()), "doubles of the scratch carve that no stage of this reduction writes were written"
 
 
 def test_stem_backward_sums_from_the_pooled_side_and_zero_gamma():

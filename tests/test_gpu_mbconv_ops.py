@@ -204,6 +204,16 @@ def test_batchnorm_with_the_plans_activations(shape, act, with_res, dtype):
         report(**rec)
 
 
+def test_batchnorm_act_on_the_two_stage_reduction():
+    """MMSKIN_BN_SINGLE_ROWS=1 (read once per process -> fresh interpreter) sends the (4, 64, 9, 7) ReLU6 case -- 4 partial rows in fp32, 2 in
+    bf16 -- through partial_reduce + the table epilogue on the two split slabs of column_stats, and its backward through the two-stage
+    bn_bwd_finalize."""
+    env = dict(os.environ, MMSKIN_BN_SINGLE_ROWS="1")
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", os.path.abspath(__file__), "-k",
+                        "test_batchnorm_with_the_plans_activations and 4x64x9x7 and relu6 and plain"], env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and " passed" in r.stdout and "skipped" not in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+
+
 # ------------------------------------------------------------------ squeeze-excitation
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 @pytest.mark.parametrize("shape", SE_SHAPES, ids=lambda s: "x".join(map(str, s)))
