@@ -135,6 +135,17 @@ double mmskin_conv2d_wgrad_time(int N, int Cin, int H, int W, int Cout, int kh, 
 int64_t mmskin_conv_pipe_launches(void);
 /* launches of the ring weight-gradient kernel (wgrad_ring.hip) since load: tests assert the path they mean to cover ran */
 int64_t mmskin_wgrad_ring_launches(void);
+/* The weight-gradient plan of a convolution (the 7x7 / stride 2 stem and a 3-channel 3x3 first conv in the virtual form the plans run):
+ * out = family, tile_o, tile_k, variant, nsplit, per_split, reduce, slab_floats.  variant: 1 = the 1x1 / stride 1 form of a staged or ring
+ * kernel; MMSKIN_WG_RING3: window pieces per wave.  per_split counts pixel rows (STAGED, RING) or stages of whole image rows (TAPS3, RING3).
+ * Pure host arithmetic, no device needed; MMSKIN_ERR_ARG when no kernel takes the shape.  Tests assert it so that a case keeps covering the
+ * kernel it was written for.  mmskin_conv_wgrad_slab_check is the check every weight-gradient launcher makes before it launches: 0 when the
+ * plan's slab_floats fit in capacity_floats, else MMSKIN_ERR_ARG. */
+enum { MMSKIN_WG_STAGED = 0, MMSKIN_WG_TAPS3 = 1, MMSKIN_WG_RING = 2, MMSKIN_WG_RING3 = 3 };
+enum { MMSKIN_WGR_DIRECT = 0, MMSKIN_WGR_LANES = 1 };
+int mmskin_conv_wgrad_plan(int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int elem_bytes, int64_t out[8]);
+int mmskin_conv_wgrad_slab_check(int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int elem_bytes,
+                                 int64_t capacity_floats);
 int64_t mmskin_wgrad3_ring_launches(void);   /* ... of the all-taps 3x3 ring kernel (wgrad3_ring.hip) */
 /* Algebraic BatchNorm backward of an expanding 1x1 convolution x = conv(y, w) (csrc/abn.hip; bf16 operands): with
  * dz = cA g + cB x + cC per channel, dy = dz w and dw = dz^T y are computed from g, y, w and the coefficients alone

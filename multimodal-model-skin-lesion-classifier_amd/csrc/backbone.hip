@@ -48,7 +48,7 @@ struct Plan : PlanBase {
   std::vector<Block> blocks;
   int64_t staged_elems = 0;
   // workspace layout (bytes)
-  size_t off_img4, off_wf, off_wd, off_stat, off_pool, off_idx, off_scratch[7], off_slab, off_partial,
+  size_t off_img4, off_wf, off_wd, off_stat, off_pool, off_idx, off_scratch[7], off_slab, slab_bytes, off_partial,
       off_coefbwd, off_dwv, off_red, off_partial_b, off_stat_b, off_red_b;
   int red_C = 0;   // channels both reduction scratches were carved for (bn_reduce_scratch)
   size_t off_abn_wd = 0, off_abn_bias = 0, off_abn_S = 0, off_abn_cs = 0;   // algebraic BatchNorm backward scratch
@@ -261,6 +261,7 @@ int build_plan(Plan& p) {
       }
     }
   }
+  p.slab_bytes = slab_max;
   p.off_slab = carve(cur, slab_max);
   p.off_partial = carve(cur, partial_max);
   p.off_partial_b = carve(cur, partial_max);
@@ -289,7 +290,7 @@ StemBufs<T> stem_bufs(const Plan& p, unsigned char* ws) {
   b.coefbwd = reinterpret_cast<float*>(ws + p.off_coefbwd);
   b.partial = reinterpret_cast<float*>(ws + p.off_partial);
   b.dx0 = reinterpret_cast<T*>(ws + p.off_scratch[3]);
-  b.slab = reinterpret_cast<float*>(ws + p.off_slab);
+  b.slab = wgrad_slab_at(ws, p.off_slab, p.slab_bytes);
   b.dwv = reinterpret_cast<float*>(ws + p.off_dwv);
   return b;
 }
@@ -471,7 +472,7 @@ template <typename T>
 int backward_impl(Plan& p, const float* dfeat, const float* params, unsigned char* ws, float* grads,
                   hipStream_t st) {
   T* wd = reinterpret_cast<T*>(ws + p.off_wd);
-  float* slab = reinterpret_cast<float*>(ws + p.off_slab);
+  const WgradSlab slab = wgrad_slab_at(ws, p.off_slab, p.slab_bytes);
   float* partial = reinterpret_cast<float*>(ws + p.off_partial);
   float* cA = reinterpret_cast<float*>(ws + p.off_coefbwd);
   T* S[7];
@@ -526,7 +527,7 @@ int backward_impl(Plan& p, const float* dfeat, const float* params, unsigned cha
         float* S_out = reinterpret_cast<float*>(ws + p.off_abn_S);
         float* cs_out = reinterpret_cast<float*>(ws + p.off_abn_cs);
         ProfScope scope(&p.prof, K_WGRAD, wst, conv_flops(u.s), conv_bytes(u.s, sizeof(T)));
-        if (int r = launch_wgrad_gram(u.s.N, u.s.OH(), u.s.OW(), u.s.Cin, u.s.Cout, gbuf, uin, slab, S_out, cs_out, wst)) return r;
+        if (int r = launch_wgrad_gram(u.s.N, u.s.OH(), u.s.OW(), u.s.Cin, u.s.Cout, gbuf, uin, slab.p, S_out, cs_out, wst)) return r;
         return abn_wgrad_finalize(S_out, cs_out, params + u.w_off, reinterpret_cast<const float*>(ws + u.abn_coef_off), u.s.Cout, u.s.Cin,
                                   grads + u.w_off, wst);
       });

@@ -57,24 +57,24 @@ inline size_t conv_slab_floats(const ConvShape& s) {
 
 template <typename T>
 struct ConvWs {
-  StageDesc* table; T *xh, *wf, *yh, *wd, *dxh; float* slab; size_t total;   // yh: NHWC output (forward) or dy (backward)
+  StageDesc* table; T *xh, *wf, *yh, *wd, *dxh; WgradSlab slab; size_t total;   // yh: NHWC output (forward) or dy (backward)
   ConvWs(void* ws, const ConvShape& s) {
     Carver c(ws);
     const size_t in = (size_t)s.N * s.H * s.W * s.Cin, wgt = (size_t)s.Cout * s.Cin * s.kh * s.kw;
     table = c.take<StageDesc>(1);
     xh = c.take<T>(in); wf = c.take<T>(wgt); yh = c.take<T>((size_t)s.N * s.OH() * s.OW() * s.Cout);
-    wd = c.take<T>(wgt); dxh = c.take<T>(in); slab = c.take<float>(conv_slab_floats(s));
+    wd = c.take<T>(wgt); dxh = c.take<T>(in); slab.floats = conv_slab_floats(s); slab.p = c.take<float>(slab.floats);
     total = c.cur;
   }
 };
 // the weight-gradient timer writes an fp32 dw, which ConvWs<bf16_t>'s weight regions are too small for
 template <typename T>
 struct WgradTimeWs {
-  T *xh, *yh; float *dw, *slab; size_t total;
+  T *xh, *yh; float* dw; WgradSlab slab; size_t total;
   WgradTimeWs(void* ws, const ConvShape& s) {
     Carver c(ws);
     xh = c.take<T>((size_t)s.N * s.H * s.W * s.Cin); yh = c.take<T>((size_t)s.N * s.OH() * s.OW() * s.Cout);
-    dw = c.take<float>((size_t)s.Cout * s.Cin * s.kh * s.kw); slab = c.take<float>(conv_slab_floats(s));
+    dw = c.take<float>((size_t)s.Cout * s.Cin * s.kh * s.kw); slab.floats = conv_slab_floats(s); slab.p = c.take<float>(slab.floats);
     total = c.cur;
   }
 };
@@ -208,7 +208,8 @@ struct StemWs {
     c.take<T>(g.rows() * 64);   // (a second full-resolution gradient nothing writes: keeps mmskin_stem_workspace_bytes what it was)
     b.dx0 = c.take<T>(g.rows() * 64);
     b.partial = c.take<float>((size_t)bn_bwd_partial_rows(g.rows(), 64) * 2 * 64);
-    b.slab = c.take<float>(stem_wgrad_slab_bytes(g.N, g.OH, g.OW) / sizeof(float));
+    b.slab.floats = stem_wgrad_slab_bytes(g.N, g.OH, g.OW) / sizeof(float);
+    b.slab.p = c.take<float>(b.slab.floats);
     b.dwv = c.take<float>(64 * 256);
     b.red = bn_reduce_scratch(c.take<double>(bn_reduce_scratch_bytes(64) / sizeof(double)), 64);
     total = c.cur;
@@ -472,7 +473,7 @@ struct DenseBlockWs {
   int max_stage_elems = 0;
   int red_C = 0;   // channels the reduction scratch was carved for (bn_reduce_scratch)
   int64_t param_numel = 0, buffer_numel = 0, wf_elems = 0;
-  size_t table_off, xh_off, wf_off, wd_off, stat_off, stat_bytes, partial_off, coefbwd_off, defer_off, red_off, slab_off, sB_off[2], sU_off,
+  size_t table_off, xh_off, wf_off, wd_off, stat_off, stat_bytes, partial_off, coefbwd_off, defer_off, red_off, slab_off, slab_bytes, sB_off[2], sU_off,
       sA_off[2], sZ_off, rbuf_off, total;
   DenseBlockWs(int N, int C0, int L, int H, int W, size_t es) {
     b.H = H; b.W = W; b.C0 = C0; b.Ctot = C0 + DENSE_GROWTH * L; b.rows = (size_t)N * H * W;
@@ -522,6 +523,7 @@ struct DenseBlockWs {
     defer_off = carve(cur, 2 * (size_t)maxC * sizeof(float));
     red_C = maxC;
     red_off = carve(cur, bn_reduce_scratch_bytes(red_C));
+    slab_bytes = slab;
     slab_off = carve(cur, slab);
     for (int q = 0; q < 2; ++q) sB_off[q] = carve(cur, b.rows * DENSE_G_PAD * es);
     sU_off = carve(cur, b.rows * DENSE_BOTTLE * es);
@@ -539,7 +541,7 @@ struct DenseBlockWs {
     r.red = bn_reduce_scratch(ws + red_off, red_C);
     for (int q = 0; q < 2; ++q) { r.sBq[q] = reinterpret_cast<T*>(ws + sB_off[q]); r.sAq[q] = reinterpret_cast<T*>(ws + sA_off[q]); }
     r.sU = reinterpret_cast<T*>(ws + sU_off); r.sZ = reinterpret_cast<T*>(ws + sZ_off);
-    r.slab = reinterpret_cast<float*>(ws + slab_off); r.partial = reinterpret_cast<float*>(ws + partial_off);
+    r.slab = wgrad_slab_at(ws, slab_off, slab_bytes); r.partial = reinterpret_cast<float*>(ws + partial_off);
     r.cA = reinterpret_cast<float*>(ws + coefbwd_off); r.defer = reinterpret_cast<float*>(ws + defer_off);
     return r;
   }
@@ -598,7 +600,7 @@ struct DenseTransWs {
   StageDesc desc;
   int PH, PW;
   int red_C = 0;   // channels the reduction scratch was carved for (bn_reduce_scratch)
-  size_t table_off, wf_off, wd_off, sC_off, dst_off, sZ_off, partial_off, coefbwd_off, red_off, slab_off, rbuf_off, total;
+  size_t table_off, wf_off, wd_off, sC_off, dst_off, sZ_off, partial_off, coefbwd_off, red_off, slab_off, slab_bytes, rbuf_off, total;
   DenseTransWs(int N, int C, int H, int W, int Cdst, size_t es) {
     b.H = H; b.W = W; b.C0 = C; b.Ctot = C; b.rows = (size_t)N * H * W;
     PH = H / 2; PW = W / 2;
@@ -630,7 +632,8 @@ struct DenseTransWs {
     coefbwd_off = carve(cur, 3 * (size_t)C * sizeof(float));
     red_C = C;
     red_off = carve(cur, bn_reduce_scratch_bytes(red_C));
-    slab_off = carve(cur, conv_wgrad_slab_bytes(ct));
+    slab_bytes = conv_wgrad_slab_bytes(ct);
+    slab_off = carve(cur, slab_bytes);
     rbuf_off = carve(cur, 2 * (size_t)C * sizeof(float));
     total = cur;
   }
@@ -641,7 +644,7 @@ struct DenseTransWs {
     r.wf = reinterpret_cast<T*>(ws + wf_off); r.wd = reinterpret_cast<T*>(ws + wd_off);
     r.red = bn_reduce_scratch(ws + red_off, red_C);
     r.sZ = reinterpret_cast<T*>(ws + sZ_off); r.sC = reinterpret_cast<T*>(ws + sC_off);
-    r.slab = reinterpret_cast<float*>(ws + slab_off); r.partial = reinterpret_cast<float*>(ws + partial_off);
+    r.slab = wgrad_slab_at(ws, slab_off, slab_bytes); r.partial = reinterpret_cast<float*>(ws + partial_off);
     r.cA = reinterpret_cast<float*>(ws + coefbwd_off);
     return r;
   }
@@ -1143,6 +1146,45 @@ int mmskin_dense_transition_backward(const float* dnext, const float* x, const f
 int64_t mmskin_col_reduce_scratch_doubles(int64_t cols_total) { return cols_total < 0 ? -1 : (int64_t)col_reduce_scratch_doubles((size_t)cols_total); }
 int mmskin_col_reduce_scratch_check(int slabs, int nrows, int cols_total, int64_t doubles) {
   return col_reduce_scratch_check(slabs, nrows, cols_total, doubles < 0 ? 0 : (size_t)doubles);
+}
+// the launch geometry of a convolution as the plans run it: the 7x7 / stride 2 stem and the 3-channel 3x3 first conv through their virtual forms
+static bool wgrad_export_geom(const ConvShape& s, WgradArgs& g) {
+  if (s.Cin == 3 && s.Cout == 64 && s.kh == 7 && s.kw == 7 && s.stride == 2 && s.pad == 3) {
+    const StemGeom sg(s.N, s.H, s.W);
+    g = wgrad_geom_stem(sg.N, sg.OH, sg.OW, sg.Hp, sg.Wp);
+    return true;
+  }
+  if (s.Cin == 3 && s.Cout == 64 && s.kh == 3 && s.kw == 3 && s.pad == 1 && (s.stride == 1 || s.stride == 2)) {
+    g = wgrad_geom_first(s.N, s.OH(), s.OW(), s.H + 2, (s.W + 4 + 1) / 2 * 2, s.stride);
+    return true;
+  }
+  g = wgrad_geom_conv(s);
+  return false;
+}
+static int wgrad_export_plan(int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int elem_bytes, WgradArgs& g, WgradPlan& pl) {
+  ARG_CHECK(N > 0 && Cin > 0 && H > 0 && W > 0 && Cout > 0 && kh > 0 && kw > 0 && stride > 0 && pad >= 0 && (elem_bytes == 2 || elem_bytes == 4),
+            "conv_wgrad_plan: bad argument");
+  const ConvShape s = {N, H, W, Cin, Cout, kh, kw, stride, pad};
+  const bool virt = wgrad_export_geom(s, g);
+  ARG_CHECK(wgrad_plan(g, virt ? nullptr : &s, elem_bytes, pl), "conv_wgrad_plan: no weight-gradient kernel takes Cout=%d Ktot=%d", g.Cout, g.Ktot);
+  return MMSKIN_OK;
+}
+int mmskin_conv_wgrad_plan(int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int elem_bytes, int64_t out[8]) {
+  static_assert(WG_STAGED == MMSKIN_WG_STAGED && WG_TAPS3 == MMSKIN_WG_TAPS3 && WG_RING == MMSKIN_WG_RING && WG_RING3 == MMSKIN_WG_RING3 &&
+                WGR_DIRECT == MMSKIN_WGR_DIRECT && WGR_LANES == MMSKIN_WGR_LANES, "mmskin.h documents the WgradPlan values");
+  WgradArgs g;
+  WgradPlan pl;
+  ARG_CHECK(out, "conv_wgrad_plan: out required");
+  if (int rc = wgrad_export_plan(N, Cin, H, W, Cout, kh, kw, stride, pad, elem_bytes, g, pl)) return rc;
+  const int64_t v[8] = {pl.family, pl.tile_o, pl.tile_k, pl.variant, pl.nsplit, pl.per_split, pl.reduce, (int64_t)pl.slab_floats};
+  for (int i = 0; i < 8; ++i) out[i] = v[i];
+  return MMSKIN_OK;
+}
+int mmskin_conv_wgrad_slab_check(int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int elem_bytes, int64_t capacity_floats) {
+  WgradArgs g;
+  WgradPlan pl;
+  if (int rc = wgrad_export_plan(N, Cin, H, W, Cout, kh, kw, stride, pad, elem_bytes, g, pl)) return rc;
+  return wgrad_slab_check(g, pl, capacity_floats < 0 ? 0 : (size_t)capacity_floats);
 }
 int64_t mmskin_slice_stats_workspace_bytes(int64_t rows, int pitch, int c0, int C) {
   if (!SLICE_OK) return -1;

@@ -101,12 +101,35 @@ struct WgradArgs {
   int8_t offy[MMSKIN_MAX_TAPS], offx[MMSKIN_MAX_TAPS];
 };
 
-// ring form of the weight-gradient GEMM (wgrad_ring.hip): tile = 64 wo x 64 wk, 8 waves, 8 / (wo wk) pixel groups per workgroup
-struct WgradRingPlan { int wo, wk, nsplit, mps; bool s1; int gram_tiles; };
-bool wgrad_ring_tile(int M, int Cout, int Ktot, WgradRingPlan& r, bool simple);   // tile shape + split count from the GEMM dimensions (simple: 1x1 / stride 1)
-bool wgrad_ring_plan(const WgradArgs& a, WgradRingPlan& r);              // false: the shape stays on the register-staged kernel of wgrad.hip
-int wgrad_ring_launch(WgradArgs& a, const WgradRingPlan& r, hipStream_t st);   // fills a.nsplit / m_per_split / nblk_*; the caller reduces the slabs
-int wgrad_ring_launch_count();
+// ---- the weight-gradient plan ("The weight-gradient plan"): which kernel family takes a launch, with which tile, over
+// how many split slabs, and how the slabs are summed.  wgrad_plan() is the one place that decides; the launchers run what it returns and the
+// *_wgrad_slab_bytes() functions size from it.
+enum { WG_STAGED = 0, WG_TAPS3 = 1, WG_RING = 2, WG_RING3 = 3 };   // register-staged (wgrad.hip), all-taps 3x3 staged, ring, all-taps 3x3 ring
+enum { WGR_DIRECT = 0, WGR_LANES = 1 };                            // one thread per float4 column walks every slab | four row lanes meet in LDS
+struct WgradPlan {
+  int family;
+  int tile_o, tile_k;      // cout x k tile in elements (WG_RING3 / WG_TAPS3: cout tile x 64 cin, nine taps)
+  int variant;             // what else selects the instantiation.  WG_STAGED, WG_RING: 1 = the S1 form (gathered row m IS pixel m); WG_RING3: NYW
+  int nsplit, per_split;   // rows (WG_STAGED, WG_RING) or stages (WG_TAPS3, WG_RING3) per split
+  int reduce;              // WGR_DIRECT (<= 32 splits) or WGR_LANES
+  size_t slab_floats;      // what the launch writes: nsplit * Cout * Ktot
+};
+struct WgradSlab { float* p; size_t floats; };   // the split slabs and how many floats the caller carved for them
+inline WgradSlab wgrad_slab_at(unsigned char* ws, size_t off, size_t bytes) { return WgradSlab{reinterpret_cast<float*>(ws + off), bytes / sizeof(float)}; }
+// the launch geometries (dy / in / slab left null).  Virtual stem: 8 row taps of 32 elements over the NHWC4 image; virtual first conv: 4 taps over NHWC8.
+WgradArgs wgrad_geom_conv(const ConvShape& s);
+WgradArgs wgrad_geom_stem(int N, int OH, int OW, int Hp, int Wp);
+WgradArgs wgrad_geom_first(int N, int OH, int OW, int Hp, int Wp, int stride);
+// s: the convolution behind g for true convolutions (the two 3x3 families plan from it), null for the virtual geometries.  Pure: no HIP call,
+// no stream; reads MMSKIN_WGRAD3_BLOCKS once.  false: no family takes the shape.
+bool wgrad_plan(const WgradArgs& g, const ConvShape* s, int elem_bytes, WgradPlan& pl);
+int wgrad_slab_check(const WgradArgs& g, const WgradPlan& pl, size_t floats);   // MMSKIN_OK when the plan's slabs fit in `floats`: every launcher's check
+// family planners / launchers behind wgrad_plan() and the launchers of wgrad.hip (the ring files own their kernels' argument structs)
+struct WgradRingPlan { int wo, wk, nsplit, mps; bool s1; int gram_tiles; };   // tile = 64 wo x 64 wk, 8 waves, 8 / (wo wk) pixel groups per workgroup
+bool wgrad_ring_plan(const WgradArgs& a, WgradRingPlan& r);                   // false: the shape stays on the register-staged kernel of wgrad.hip
+int wgrad_ring_launch(WgradArgs& a, const WgradRingPlan& r, hipStream_t st);  // fills a.nsplit / m_per_split / nblk_*; the caller reduces the slabs
+bool wgrad3_ring_plan(const ConvShape& s, WgradPlan& pl);
+int wgrad3_ring_launch(const ConvShape& s, const WgradPlan& pl, const bf16_t* dout, const bf16_t* in, float* slab, hipStream_t st);
 // dY^T in plus in^T in and colsum(in) in one launch (1x1 / stride 1 layers whose Cout x Cin the ring kernel tiles): the slab rows are
 // [Cout main | gram tile rows]; returns the plan through r, reduces the slabs into s_out [Cout + gram rows][Cin] and the column sums
 // into colsum_out [Cin].  scratch: wgrad_gram_scratch_floats() floats behind the caller's slab.
@@ -189,7 +212,7 @@ int launch_vgg_first_conv_fwd(int N, int H, int W, int Hp, int Wp, const T* img8
                               float* stat_sq = nullptr);
 size_t vgg_first_wgrad_slab_bytes(int N, int H, int W);   // H, W = OUTPUT size
 template <typename T>
-int launch_vgg_first_conv_wgrad(int N, int H, int W, int Hp, int Wp, const T* dout, const T* img8, float* slab,
+int launch_vgg_first_conv_wgrad(int N, int H, int W, int Hp, int Wp, const T* dout, const T* img8, WgradSlab slab,
                                 float* dwv, hipStream_t st, int stride = 1);
 
 // 3x3 / stride 1 / pad 1, 64 -> 64 channels at 56 x 56 (ResNet-50 layer1 conv2): all nine taps from one staged input window, weights
@@ -204,16 +227,12 @@ size_t conv_wgrad_slab_bytes(const ConvShape& s);
 // GEMM operands carry zero padding (s.Cout / s.Cin rounded up to 64), dw is the UNPADDED
 // [cout_valid][cin_valid][kh][kw] tensor and the padded rows / channels are dropped.
 template <typename T>
-int launch_conv_wgrad(const ConvShape& s, const T* dout, const T* in, float* slab, float* dw,
+int launch_conv_wgrad(const ConvShape& s, const T* dout, const T* in, WgradSlab slab, float* dw,
                       hipStream_t st, int cout_valid = 0, int cin_valid = 0);
 size_t stem_wgrad_slab_bytes(int N, int OH, int OW);
 template <typename T>
 int launch_stem_conv_wgrad(int N, int OH, int OW, int Hp, int Wp, const T* dout, const T* img4,
-                           float* slab, float* dwv, hipStream_t st);
-
-// all-taps 3x3 / stride 1 / pad 1 weight gradient, ring form (wgrad3_ring.hip): launches the GEMM; the caller reduces *nsplit slabs [Cout][9 Cin]
-bool wgrad3_ring_takes(const ConvShape& s, int* nsplit);
-int launch_wgrad3_ring(const ConvShape& s, const bf16_t* dout, const bf16_t* in, float* slab, hipStream_t st, int* nsplit);
+                           WgradSlab slab, float* dwv, hipStream_t st);
 
 // algebraic BatchNorm backward of an expanding 1x1 convolution (abn.hip)
 int abn_prep(const float* W, const float* cA, const float* cB, const float* cC, int C4, int Cw, bf16_t* wd, float* bias, float* coef_copy,

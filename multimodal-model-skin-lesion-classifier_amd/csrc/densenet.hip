@@ -28,7 +28,7 @@ struct DensePlan : PlanBase {
   std::vector<DBlock> blocks;
   DTrans trans[3];
   BNRef n5; size_t coef5_off, y5_off;
-  size_t off_wf, off_wd, off_stat, off_partial, off_coefbwd, off_defer, off_dwv, off_red, off_slab;
+  size_t off_wf, off_wd, off_stat, off_partial, off_coefbwd, off_defer, off_dwv, off_red, off_slab, slab_bytes;
   int red_C = 0;   // channels the reduction scratch was carved for (bn_reduce_scratch)
   size_t off_sB, off_sB2, off_sU, off_sA, off_sA2, off_sX, off_sZ, off_sC;
   size_t stat_bytes = 0;
@@ -160,6 +160,7 @@ int build_dense_plan(DensePlan& p) {
   p.off_dwv = carve(cur, 64 * 256 * sizeof(float));
   p.red_C = maxC;
   p.off_red = carve(cur, bn_reduce_scratch_bytes(p.red_C));
+  p.slab_bytes = slab;
   p.off_slab = carve(cur, slab);
   p.off_sB = carve(cur, p.blocks[0].rows * G_PAD * es);
   p.off_sB2 = carve(cur, p.blocks[0].rows * G_PAD * es);
@@ -188,7 +189,7 @@ StemBufs<T> stem_bufs(const DensePlan& p, unsigned char* ws) {
   b.coefbwd = reinterpret_cast<float*>(ws + p.off_coefbwd);
   b.partial = reinterpret_cast<float*>(ws + p.off_partial);
   b.dx0 = reinterpret_cast<T*>(ws + p.off_sX);
-  b.slab = reinterpret_cast<float*>(ws + p.off_slab);
+  b.slab = wgrad_slab_at(ws, p.off_slab, p.slab_bytes);
   b.dwv = reinterpret_cast<float*>(ws + p.off_dwv);
   return b;
 }
@@ -207,7 +208,7 @@ DenseRun<T> dense_run(DensePlan& p, const float* params, float* buffers, float* 
   r.sU = reinterpret_cast<T*>(ws + p.off_sU);
   r.sZ = reinterpret_cast<T*>(ws + p.off_sZ);
   r.sC = reinterpret_cast<T*>(ws + p.off_sC);
-  r.slab = reinterpret_cast<float*>(ws + p.off_slab);
+  r.slab = wgrad_slab_at(ws, p.off_slab, p.slab_bytes);
   r.partial = reinterpret_cast<float*>(ws + p.off_partial);
   r.cA = reinterpret_cast<float*>(ws + p.off_coefbwd);
   r.defer = reinterpret_cast<float*>(ws + p.off_defer);

@@ -755,12 +755,13 @@ static int linear_backward_impl(const float* dy, const float* x, const float* w,
     const size_t slab_bytes = conv_wgrad_slab_bytes(s);
     const size_t star_floats = o.star_s ? (size_t)2 * colsum4_blocks(M, Np / 4) : 0;
     bf16_t *g16 = nullptr, *t16 = nullptr, *w16 = nullptr;   // dy; dx (padded route) or x; w transposed
-    float *slab = nullptr, *star_part = nullptr, *part = nullptr;
+    WgradSlab slab = {nullptr, slab_bytes / sizeof(float)};
+    float *star_part = nullptr, *part = nullptr;
     const bool placed = carve_scratch([&](Carver& c) {
       g16 = c.take<bf16_t>((size_t)M * Np);
       t16 = c.take<bf16_t>((size_t)M * Kp);
       w16 = c.take<bf16_t>((size_t)Np * Kp);
-      slab = reinterpret_cast<float*>(c.take<unsigned char>(slab_bytes));
+      slab.p = reinterpret_cast<float*>(c.take<unsigned char>(slab_bytes));
       if (star_floats) star_part = c.take<float>(star_floats);
       part = reinterpret_cast<float*>(c.take<unsigned char>(colsum4_part_bytes(N)));
     });
@@ -800,10 +801,11 @@ static int linear_backward_impl(const float* dy, const float* x, const float* w,
   if (path == LIN_BIG_F32) {
     ConvShape s = {M, 1, 1, K, N, 1, 1, 1, 0};
     const size_t slab_bytes = conv_wgrad_slab_bytes(s);
-    float *wt = nullptr, *slab = nullptr;
+    float* wt = nullptr;
+    WgradSlab slab = {nullptr, slab_bytes / sizeof(float)};
     const bool placed = carve_scratch([&](Carver& c) {
       wt = c.take<float>((size_t)N * K);
-      slab = reinterpret_cast<float*>(c.take<unsigned char>(slab_bytes));
+      slab.p = reinterpret_cast<float*>(c.take<unsigned char>(slab_bytes));
     });
     if (!placed) { mmskin_set_error("linear_backward: scratch allocation failed"); return MMSKIN_ERR_HIP; }
     if (dx) {

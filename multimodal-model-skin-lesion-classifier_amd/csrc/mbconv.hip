@@ -64,7 +64,7 @@ struct MBPlan : PlanBase {
   int n_sd = 0;                     // residual blocks with stochastic depth; 0: the plan takes no "sd_mask"
   const float* sd_mask = nullptr;   // [n_sd][N] keep/scale factors for this training step (null: no stochastic depth)
   int Hp, Wp, stemC;
-  size_t off_img8, off_wf, off_wd, off_stat, off_tab, off_partial, off_coefbwd, off_red, off_slab, off_dwv, off_dwpart,
+  size_t off_img8, off_wf, off_wd, off_stat, off_tab, off_partial, off_coefbwd, off_red, off_slab, slab_bytes, off_dwv, off_dwpart,
       off_setmp = 0, off_g[4];
   int red_C = 0;   // channels the reduction scratch was carved for (bn_reduce_scratch)
   size_t stat_bytes = 0;
@@ -194,6 +194,7 @@ int finish_plan(MBPlan& p, const char* arch) {
   p.off_coefbwd = carve(cur, 3 * (size_t)maxCp * sizeof(float));
   p.red_C = maxCp;
   p.off_red = carve(cur, bn_reduce_scratch_bytes(p.red_C));
+  p.slab_bytes = slab;
   p.off_slab = carve(cur, slab);
   p.off_dwv = carve(cur, 64 * 128 * sizeof(float));
   p.off_dwpart = carve(cur, (dwpart > 0 ? dwpart : 1) * sizeof(float));
@@ -374,7 +375,7 @@ template <typename T>
 int mb_backward(MBPlan& p, const float* dfeat, const float* params, unsigned char* ws, float* grads, hipStream_t st) {
   T* wf = reinterpret_cast<T*>(ws + p.off_wf);
   T* wd = reinterpret_cast<T*>(ws + p.off_wd);
-  float* slab = reinterpret_cast<float*>(ws + p.off_slab);
+  const WgradSlab slab = wgrad_slab_at(ws, p.off_slab, p.slab_bytes);
   float* partial = reinterpret_cast<float*>(ws + p.off_partial);
   float* cA = reinterpret_cast<float*>(ws + p.off_coefbwd);
   const ColScratch red = bn_reduce_scratch(ws + p.off_red, p.red_C);

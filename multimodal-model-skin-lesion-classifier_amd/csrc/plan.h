@@ -322,7 +322,8 @@ struct StemBufs {
   float* coefbwd = nullptr;  // BnBwdCoef block
   float* partial = nullptr;  // BatchNorm-backward partial sums
   T* dx0 = nullptr;          // gradient of the raw conv output [rows][64]
-  float *slab = nullptr, *dwv = nullptr;   // weight-gradient slab, and the gradient in the staged (64 x 256) layout
+  WgradSlab slab = {};       // weight-gradient slab with the floats carved for it
+  float* dwv = nullptr;      // the gradient in the staged (64 x 256) layout
 };
 // Where the stem's BatchNorm coefficients come from
 struct StemBn {
@@ -485,7 +486,8 @@ struct DenseRun {
   T* sBq[2] = {nullptr, nullptr};  // conv2 output / gradient, padded to 64 channels (forward uses [0]); alternate between layers
   T* sAq[2] = {nullptr, nullptr};  // gradient of conv1's output
   T *sU = nullptr, *sZ = nullptr, *sC = nullptr;   // gradient of u; of the padded prefix t; the transition conv's output / its gradient
-  float *slab = nullptr, *partial = nullptr, *cA = nullptr, *defer = nullptr;
+  WgradSlab slab = {};
+  float *partial = nullptr, *cA = nullptr, *defer = nullptr;
   SideStream* side = nullptr;      // null: the weight-gradient GEMMs run on the caller's stream
   bool use_side = false;
   int layer_no = 0;                // layers seen by this backward (picks the alternating operand buffers)

@@ -23,7 +23,7 @@ struct VggPlan : PlanBase {
   std::vector<VConv> convs;
   int Hp, Wp;                 // padded NHWC8 image
   int fH, fW;                 // spatial size after the five pools
-  size_t off_img8, off_wf, off_wd, off_partial, off_red, off_slab, off_dwv, off_g[2];
+  size_t off_img8, off_wf, off_wd, off_partial, off_red, off_slab, slab_bytes, off_dwv, off_g[2];
   int red_C;                  // channels the reduction scratch at off_red was carved for
 
   int forward(const void* image, const float* norm6, const float* params, float* buffers, unsigned char* ws,
@@ -100,6 +100,7 @@ int build_vgg_plan(VggPlan& p) {
   p.off_partial = carve(cur, partial);
   p.red_C = maxC;
   p.off_red = carve(cur, bn_reduce_scratch_bytes(p.red_C));
+  p.slab_bytes = slab;
   p.off_slab = carve(cur, slab);
   p.off_dwv = carve(cur, 64 * 128 * sizeof(float));
   p.off_g[0] = carve(cur, maxact * es);
@@ -144,7 +145,7 @@ int vgg_forward(VggPlan& p, const void* image, const float* norm6, const float* 
 template <typename T>
 int vgg_backward(VggPlan& p, const float* dfeat, const float* params, unsigned char* ws, float* grads, hipStream_t st) {
   T* wd = reinterpret_cast<T*>(ws + p.off_wd);
-  float* slab = reinterpret_cast<float*>(ws + p.off_slab);
+  const WgradSlab slab = wgrad_slab_at(ws, p.off_slab, p.slab_bytes);
   float* partial = reinterpret_cast<float*>(ws + p.off_partial);
   const ColScratch red = bn_reduce_scratch(ws + p.off_red, p.red_C);
   T* G[2] = {reinterpret_cast<T*>(ws + p.off_g[0]), reinterpret_cast<T*>(ws + p.off_g[1])};

@@ -6,8 +6,8 @@
 // they sit in memory ([m][channel], 16-byte chunks, XOR-swizzled by row) and bf16 fragments are read
 // with ds_read_b64_tr_b16 (the CDNA4 transposing LDS read); the exact-f32 path reads one dword per
 // lane, which needs no transpose.  The pixel range is split over workgroups; every split writes its
-// own fp32 slab (deterministic, no atomics) and wgrad_reduce sums the slabs straight into the
-// OIHW gradient tensor.
+// own fp32 slab (deterministic, no atomics) and wgrad_reduce4* sum the slabs straight into the
+// OIHW gradient tensor.  Which kernel, tile, split count and reduction a launch gets is decided in one place: wgrad_plan().
 #include <stdlib.h>
 
 #include "conv.h"
@@ -243,42 +243,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs p) {
     }
 }
 
-// sum split slabs; write dw[(cout*Cv + c)*ntaps + tap]  (OIHW when tap = r*kw + s) for cout < Coutv, c < Cv:
-// operands padded to the GEMM's 64-multiples (DenseNet) reduce straight into the unpadded parameter gradient
-__global__ void wgrad_reduce_kernel(const float* __restrict__ slab, float* __restrict__ dw, int nsplit,
-                                    int Cout, int C, int ntaps, int Coutv, int Cv) {
-  const int Ktot = C * ntaps;
-  const size_t total = (size_t)Cout * Ktot;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    float s = 0.f;
-    for (int k = 0; k < nsplit; ++k) s += slab[k * total + i];
-    int cout = (int)(i / Ktot), kk = (int)(i - (size_t)cout * Ktot);
-    int tap = kk / C, c = kk - tap * C;
-    if (cout < Coutv && c < Cv) dw[((size_t)cout * Cv + c) * ntaps + tap] = s;
-  }
-}
-
-// float4 variants of the slab reduction (the slabs are ~64 MB per layer: 3 GB per ResNet-50 step).
-// Stage 1: slab[nsplit][total] -> part[G][total]; a thread owns ONE float4 column and walks its group's rows with four
-// independent accumulators -- no LDS, no barrier (the generic partial_reduce gave a thread 1-2 rows and a barrier).
-__global__ __launch_bounds__(256) void wgrad_slab_group_kernel(const float4* __restrict__ slab, float4* __restrict__ part,
-                                                               int nsplit, int total4, int per) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= total4) return;
-  const int r0 = blockIdx.y * per, r1 = min(nsplit, r0 + per);
-  float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, a2 = a0, a3 = a0;
-  const float4* src = slab + (size_t)r0 * total4 + c;
-  int r = r0;
+// The slab reductions sum the split slabs and write dw[(cout*Cv + c)*ntaps + tap]  (OIHW when tap = r*kw + s) for cout < Coutv, c < Cv:
+// operands padded to the GEMM's 64-multiples (DenseNet) reduce straight into the unpadded parameter gradient.  float4 columns (the
+// slabs are ~64 MB per layer: 3 GB per ResNet-50 step), deterministic (fixed order).
 #define ACC4(a, u) a.x += u.x; a.y += u.y; a.z += u.z; a.w += u.w;
-  for (; r + 3 < r1; r += 4, src += (size_t)4 * total4) {
-    const float4 u0 = src[0], u1 = src[total4], u2 = src[(size_t)2 * total4], u3 = src[(size_t)3 * total4];
-    ACC4(a0, u0) ACC4(a1, u1) ACC4(a2, u2) ACC4(a3, u3)
-  }
-  for (; r < r1; ++r, src += total4) { const float4 u = src[0]; ACC4(a0, u) }
-  part[(size_t)blockIdx.y * total4 + c] =
-      make_float4((a0.x + a1.x) + (a2.x + a3.x), (a0.y + a1.y) + (a2.y + a3.y), (a0.z + a1.z) + (a2.z + a3.z), (a0.w + a1.w) + (a2.w + a3.w));
-}
-// Final stage: sum nsplit slabs, 4 consecutive k (= 4 consecutive channels of one tap, C % 4 == 0) per thread, scatter to OIHW
+// Few splits: sum nsplit slabs, 4 consecutive k (= 4 consecutive channels of one tap, C % 4 == 0) per thread, scatter to OIHW
 __global__ __launch_bounds__(256) void wgrad_reduce4_kernel(const float4* __restrict__ slab, float* __restrict__ dw, int nsplit,
                                                             int Cout, int C, int ntaps, int Coutv, int Cv) {
   const int Ktot = C * ntaps;
@@ -339,9 +308,10 @@ __global__ __launch_bounds__(256) void wgrad_reduce4_lanes_kernel(const float4* 
 }
 
 // ------------------------------------------------------------------------------------------ host
-static void wgrad_plan(int M, int Cout, int Ktot, int MS, int& BO, int& BKK, int& nsplit, int& mps, int ntaps = 1) {
-  BO = (Cout % 128 == 0) ? 128 : 64;
-  BKK = (Ktot % 128 == 0) ? 128 : 64;
+// WG_STAGED: tile and split count of the register-staged kernel (MS = rows per stage of the element type)
+static void wgrad_staged_plan(int M, int Cout, int Ktot, int MS, int ntaps, WgradPlan& pl) {
+  const int BO = (Cout % 128 == 0) ? 128 : 64;
+  const int BKK = (Ktot % 128 == 0) ? 128 : 64;
   MS *= (BO + BKK == 128) ? 4 : 2;   // rows per stage (MSF of the kernel)
   int tiles = (Cout / BO) * (Ktot / BKK);
   // workgroups to aim for (never exceeded: one extra workgroup costs a whole extra round of 2 x 256 resident slots).
@@ -352,123 +322,49 @@ static void wgrad_plan(int M, int Cout, int Ktot, int MS, int& BO, int& BKK, int
   const int target = (ntaps == 1 || tiles >= 64) ? one_round : two_rounds;
   int want = target / tiles > 0 ? target / tiles : 1;
   int max_split = M / (MS * 4) > 0 ? M / (MS * 4) : 1;
-  nsplit = want < max_split ? want : max_split;
+  int nsplit = want < max_split ? want : max_split;
   if (nsplit < 1) nsplit = 1;
-  mps = ceil_div(ceil_div(M, nsplit), MS) * MS;
-  nsplit = ceil_div(M, mps);
+  pl.family = WG_STAGED;
+  pl.tile_o = BO; pl.tile_k = BKK;
+  pl.per_split = ceil_div(ceil_div(M, nsplit), MS) * MS;
+  pl.nsplit = ceil_div(M, pl.per_split);
 }
 
-#define WG_DIRECT_SPLITS 32   // more splits than this are pre-reduced to WG_GROUPS partial slabs first
-#define WG_GROUPS 64        // upper bound; small outputs use more groups so the first stage still fills the chip
+#define WG_DIRECT_SPLITS 32   // more splits than this are summed by the four-lane kernel
+// Slabs behind the plan's own that NO kernel writes: the carve a two-stage reduction once used for its group partials.  The sizes keep it so
+// that no workspace moves; dropping it shifts every pinned plan size and is a change of its own.
+#define WG_UNWRITTEN_SLABS 64
 
-// sum the nsplit slabs [Cout][Ktot] (optionally through G group partials stored behind them) into the OIHW gradient
-static int reduce_slabs(float* slab, int nsplit, int Cout, int Ktot, float* dw, int C_for_layout, int ntaps_for_layout,
+// sum the plan's slabs [Cout][Ktot] into the OIHW gradient
+static int reduce_slabs(const float* slab, const WgradPlan& pl, int Cout, int Ktot, float* dw, int C_for_layout, int ntaps_for_layout,
                         int cout_valid, int cin_valid, hipStream_t st) {
-  size_t total = (size_t)Cout * Ktot;
-  const int total4 = (int)(total / 4);
-  const float* src = slab;
-  int nsrc = nsplit;
-  if (nsplit > WG_DIRECT_SPLITS && C_for_layout % 4 == 0) {
-    const int coutv = cout_valid > 0 ? cout_valid : Cout, cv = cin_valid > 0 ? cin_valid : C_for_layout;
-    hipLaunchKernelGGL(wgrad_reduce4_lanes_kernel, dim3(ceil_div(total4, 64)), dim3(256), 0, st, reinterpret_cast<const float4*>(slab),
-                       dw, nsplit, Cout, C_for_layout, ntaps_for_layout, coutv, cv);
-    HIP_CHECK_RET(hipGetLastError());
-    return MMSKIN_OK;
-  }
-  if (nsplit > WG_DIRECT_SPLITS) {   // many small splits: wide first-stage reduction to G <= WG_GROUPS partial slabs
-    float* slab2 = slab + (size_t)nsplit * total;
-    // >= 256k threads where the output allows it, <= 32 rows per thread, at least 2 rows per group
-    int G = ceil_div(262144, total4);
-    const int g_lo = ceil_div(nsplit, 32), g_hi = nsplit / 2 < WG_GROUPS ? nsplit / 2 : WG_GROUPS;
-    if (G < g_lo) G = g_lo;
-    if (G > g_hi) G = g_hi;
-    const int per = ceil_div(nsplit, G);
-    G = ceil_div(nsplit, per);
-    hipLaunchKernelGGL(wgrad_slab_group_kernel, dim3(ceil_div(total4, 256), G), dim3(256), 0, st,
-                       reinterpret_cast<const float4*>(slab), reinterpret_cast<float4*>(slab2), nsplit, total4, per);
-    HIP_CHECK_RET(hipGetLastError());
-    src = slab2;
-    nsrc = G;
-  }
+  ARG_CHECK(C_for_layout % 4 == 0, "wgrad: the slab reduction walks float4 columns of one tap, C=%d", C_for_layout);
+  const int total4 = (int)((size_t)Cout * Ktot / 4);
   const int coutv = cout_valid > 0 ? cout_valid : Cout, cv = cin_valid > 0 ? cin_valid : C_for_layout;
-  if (C_for_layout % 4 == 0) {
-    hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3(ceil_div(total4, 256)), dim3(256), 0, st, reinterpret_cast<const float4*>(src),
-                       dw, nsrc, Cout, C_for_layout, ntaps_for_layout, coutv, cv);
-  } else {
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, st, src, dw, nsrc, Cout, C_for_layout,
-                       ntaps_for_layout, coutv, cv);
-  }
+  if (pl.reduce == WGR_LANES)
+    hipLaunchKernelGGL(wgrad_reduce4_lanes_kernel, dim3(ceil_div(total4, 64)), dim3(256), 0, st, reinterpret_cast<const float4*>(slab),
+                       dw, pl.nsplit, Cout, C_for_layout, ntaps_for_layout, coutv, cv);
+  else
+    hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3(ceil_div(total4, 256)), dim3(256), 0, st, reinterpret_cast<const float4*>(slab),
+                       dw, pl.nsplit, Cout, C_for_layout, ntaps_for_layout, coutv, cv);
   HIP_CHECK_RET(hipGetLastError());
   return MMSKIN_OK;
-}
-
-template <typename T>
-static size_t slab_bytes(int M, int Cout, int Ktot, int ntaps) {
-  int BO, BKK, ns, mps;
-  wgrad_plan(M, Cout, Ktot, WG<T>::MS, BO, BKK, ns, mps, ntaps);
-  if constexpr (sizeof(T) == 2) {   // the ring kernel (wgrad_ring.hip) splits differently
-    WgradRingPlan rp;
-    for (int simple = 0; simple < 2; ++simple)
-      if (wgrad_ring_tile(M, Cout, Ktot, rp, simple != 0) && rp.nsplit > ns) ns = rp.nsplit;
-  }
-  return (size_t)(ns + (ns > WG_DIRECT_SPLITS ? WG_GROUPS : 0)) * Cout * Ktot * sizeof(float);
-}
-static size_t wgrad3_slab_bytes(const ConvShape& s);   // all-taps 3x3 path below
-size_t conv_wgrad_slab_bytes(const ConvShape& s) {
-  int M = s.N * s.OH() * s.OW(), K = s.kh * s.kw * s.Cin;
-  size_t a = slab_bytes<float>(M, s.Cout, K, s.kh * s.kw), b = slab_bytes<bf16_t>(M, s.Cout, K, s.kh * s.kw);
-  const size_t c = wgrad3_slab_bytes(s);
-  if (c > b) b = c;
-  return a > b ? a : b;
-}
-size_t stem_wgrad_slab_bytes(int N, int OH, int OW) {
-  size_t a = slab_bytes<float>(N * OH * OW, 64, 256, 8), b = slab_bytes<bf16_t>(N * OH * OW, 64, 256, 8);   // 8 virtual taps
-  return a > b ? a : b;
 }
 
 template <typename T, int BO, int BKK, int MSF>
-static int launch_wg(WgradArgs& a, hipStream_t st) {
-  a.nblk_o = a.Cout / BO;
-  a.nblk_k = a.Ktot / BKK;
-  int grid = a.nblk_o * a.nblk_k * a.nsplit;
-  if (a.simple1x1 && sizeof(T) == 2 && BO >= 64 && BKK >= 64 && BO + BKK >= 192) hipLaunchKernelGGL((wgrad_kernel<T, BO, BKK, MSF, 1, true>), dim3(grid), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((wgrad_kernel<T, BO, BKK, MSF, 1>), dim3(grid), dim3(256), 0, st, a);
+static int launch_wg(const WgradArgs& a, bool s1, hipStream_t st) {
+  const int grid = a.nblk_o * a.nblk_k * a.nsplit;
+  if constexpr (sizeof(T) == 2 && BO + BKK >= 192) {
+    if (s1) {
+      hipLaunchKernelGGL((wgrad_kernel<T, BO, BKK, MSF, 1, true>), dim3(grid), dim3(256), 0, st, a);
+      HIP_CHECK_RET(hipGetLastError());
+      return MMSKIN_OK;
+    }
+  }
+  hipLaunchKernelGGL((wgrad_kernel<T, BO, BKK, MSF, 1>), dim3(grid), dim3(256), 0, st, a);
   HIP_CHECK_RET(hipGetLastError());
   return MMSKIN_OK;
 }
-
-
-template <typename T>
-static int run_wgrad(WgradArgs& a, float* dw, int C_for_layout, int ntaps_for_layout, hipStream_t st,
-                     int cout_valid = 0, int cin_valid = 0) {
-  ARG_CHECK(a.Cout % 64 == 0 && a.Ktot % 64 == 0, "wgrad: Cout=%d Ktot=%d must be multiples of 64", a.Cout, a.Ktot);
-  ARG_CHECK(a.C % DT<T>::EPC == 0, "wgrad: C=%d", a.C);
-  ARG_CHECK(a.OW <= 240 && a.OH <= 240, "wgrad: output %dx%d too large for the 16-bit reciprocal pixel stepping", a.OH, a.OW);
-  if constexpr (sizeof(T) == 2) {
-    WgradRingPlan rp;
-    if (wgrad_ring_plan(a, rp)) {
-      int rc = wgrad_ring_launch(a, rp, st);
-      if (rc) return rc;
-      return reduce_slabs(a.slab, a.nsplit, a.Cout, a.Ktot, dw, C_for_layout, ntaps_for_layout, cout_valid, cin_valid, st);
-    }
-  }
-  int BO, BKK;
-  wgrad_plan(a.M, a.Cout, a.Ktot, WG<T>::MS, BO, BKK, a.nsplit, a.m_per_split, a.ntaps);
-  a.ablate = 0;
-#ifdef MMSKIN_ABLATE
-  { const char* v = getenv("MMSKIN_WGRAD_ABLATE"); a.ablate = v ? atoi(v) : 0; }
-#endif
-  int rc;
-  if (BO == 128 && BKK == 128) rc = launch_wg<T, 128, 128, 2>(a, st);
-  else if (BO == 128) rc = launch_wg<T, 128, 64, 2>(a, st);
-  else if (BKK == 128) rc = launch_wg<T, 64, 128, 2>(a, st);
-  else rc = launch_wg<T, 64, 64, 4>(a, st);
-  if (rc) return rc;
-  return reduce_slabs(a.slab, a.nsplit, a.Cout, a.Ktot, dw, C_for_layout, ntaps_for_layout, cout_valid, cin_valid, st);
-}
-
 
 // ------------------------------------------------------------------------------------------ 3x3 / stride 1 / pad 1, all taps per workgroup
 // The tapped kernel above gives every (cout tile, tap x cin tile) its own workgroup, so a 3x3 layer streams dY and the
@@ -634,17 +530,23 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3_kernel(const Wgrad3Args p) {
       }
 }
 
-static bool wgrad3_plan(const ConvShape& s, Wgrad3Args& a) {
-  if (s.kh != 3 || s.kw != 3 || s.stride != 1 || s.pad != 1) return false;
-  if (s.Cin % 64 || s.Cout % 64 || s.W > 64 || s.W < 1) return false;
+// the stage geometry of a shape the planner took
+static void wgrad3_geom(const ConvShape& s, Wgrad3Args& a) {
   int R = 64 / s.W;
   if (R > s.H) R = s.H;
-  if ((R + 2) * (s.W + 2) > W3_YROWS) return false;
   a.N = s.N; a.H = s.H; a.W = s.W; a.C = s.Cin; a.Cout = s.Cout;
   a.R = R; a.spi = ceil_div(s.H, R);
   a.total_stages = s.N * a.spi;
   a.nblk_o = s.Cout / 64; a.nblk_c = s.Cin / 64;
   a.yrows = (R + 2) * (s.W + 2);
+}
+// WG_TAPS3
+static bool wgrad_taps3_plan(const ConvShape& s, WgradPlan& pl) {
+  if (s.kh != 3 || s.kw != 3 || s.stride != 1 || s.pad != 1) return false;
+  if (s.Cin % 64 || s.Cout % 64 || s.W > 64 || s.W < 1) return false;
+  Wgrad3Args a;
+  wgrad3_geom(s, a);
+  if (a.yrows > W3_YROWS) return false;
   const int tiles = a.nblk_o * a.nblk_c;
   static const int target = env_knob("MMSKIN_WGRAD3_BLOCKS", 512);      // one round of 2 workgroups per CU
   int ns = target / tiles > 0 ? target / tiles : 1;
@@ -654,91 +556,164 @@ static bool wgrad3_plan(const ConvShape& s, Wgrad3Args& a) {
   constexpr int min_stages = 16;
   if (ns > a.total_stages / min_stages) ns = a.total_stages / min_stages > 0 ? a.total_stages / min_stages : 1;
   if (ns > a.total_stages) ns = a.total_stages;
-  a.stages_per_split = ceil_div(a.total_stages, ns);
-  a.nsplit = ceil_div(a.total_stages, a.stages_per_split);
+  pl.family = WG_TAPS3;
+  pl.tile_o = 64; pl.tile_k = 64; pl.variant = 0;
+  pl.per_split = ceil_div(a.total_stages, ns);
+  pl.nsplit = ceil_div(a.total_stages, pl.per_split);
   return true;
 }
-static size_t wgrad3_slab_bytes(const ConvShape& s) {
-  Wgrad3Args a = {};
-  int ns = wgrad3_plan(s, a) ? a.nsplit : 0, nr = 0;
-  if (wgrad3_ring_takes(s, &nr) && nr > ns) ns = nr;
-  if (!ns) return 0;
-  return (size_t)(ns + (ns > WG_DIRECT_SPLITS ? WG_GROUPS : 0)) * s.Cout * 9 * s.Cin * sizeof(float);
-}
-static int launch_wgrad3(const ConvShape& s, Wgrad3Args& a, const bf16_t* dout, const bf16_t* in, float* slab, float* dw,
-                         hipStream_t st, int cout_valid, int cin_valid) {
-  a.dy = dout; a.in = in; a.slab = slab;
-  HIP_CHECK_RET(opt_in_dynamic_lds(reinterpret_cast<const void*>(wgrad3x3_kernel), W3_LDS_BYTES));
-  hipLaunchKernelGGL(wgrad3x3_kernel, dim3(a.nblk_o * a.nblk_c * a.nsplit), dim3(256), W3_LDS_BYTES, st, a);
-  HIP_CHECK_RET(hipGetLastError());
-  return reduce_slabs(slab, a.nsplit, s.Cout, 9 * s.Cin, dw, s.Cin, 9, cout_valid, cin_valid, st);
-}
 
-template <typename T>
-int launch_conv_wgrad(const ConvShape& s, const T* dout, const T* in, float* slab, float* dw_oihw,
-                      hipStream_t st, int cout_valid, int cin_valid) {
-  ARG_CHECK(s.kh * s.kw <= MMSKIN_MAX_TAPS, "wgrad: too many taps");
-  if constexpr (sizeof(T) == 2) {
-    int nsr = 0;
-    if (wgrad3_ring_takes(s, &nsr)) {
-      int rc = launch_wgrad3_ring(s, dout, in, slab, st, &nsr);
-      if (rc) return rc;
-      return reduce_slabs(slab, nsr, s.Cout, 9 * s.Cin, dw_oihw, s.Cin, 9, cout_valid, cin_valid, st);
-    }
-    Wgrad3Args a3 = {};
-    if (wgrad3_plan(s, a3)) return launch_wgrad3(s, a3, dout, in, slab, dw_oihw, st, cout_valid, cin_valid);
-  }
+// ------------------------------------------------------------------------------------------ the plan
+WgradArgs wgrad_geom_conv(const ConvShape& s) {
   WgradArgs a = {};
-  a.dy = dout; a.in = in; a.slab = slab;
   a.N = s.N; a.IH = s.H; a.IW = s.W; a.C = s.Cin; a.Cpitch = s.Cin;
   a.OH = s.OH(); a.OW = s.OW();
   a.Cout = s.Cout; a.Ktot = s.kh * s.kw * s.Cin;
   a.Sy = s.stride; a.Sx = s.stride; a.ntaps = s.kh * s.kw;
   a.M = s.N * a.OH * a.OW;
   a.simple1x1 = (s.kh == 1 && s.kw == 1 && s.stride == 1 && s.pad == 0) ? 1 : 0;
-  for (int r = 0; r < s.kh; ++r)
+  for (int r = 0; r < s.kh && a.ntaps <= MMSKIN_MAX_TAPS; ++r)
     for (int q = 0; q < s.kw; ++q) {
       a.offy[r * s.kw + q] = (int8_t)(r - s.pad);
       a.offx[r * s.kw + q] = (int8_t)(q - s.pad);
     }
-  return run_wgrad<T>(a, dw_oihw, s.Cin, s.kh * s.kw, st, cout_valid, cin_valid);
+  return a;
 }
-
-template <typename T>
-int launch_stem_conv_wgrad(int N, int OH, int OW, int Hp, int Wp, const T* dout, const T* img4,
-                           float* slab, float* dwv, hipStream_t st) {
+WgradArgs wgrad_geom_stem(int N, int OH, int OW, int Hp, int Wp) {
   WgradArgs a = {};
-  a.dy = dout; a.in = img4; a.slab = slab;
   a.N = N; a.IH = Hp; a.IW = Wp / 2; a.C = 32; a.Cpitch = 8;
   a.OH = OH; a.OW = OW; a.Cout = 64; a.Ktot = 256;
   a.Sy = 2; a.Sx = 1; a.ntaps = 8;
   a.M = N * OH * OW;
   for (int r = 0; r < 8; ++r) { a.offy[r] = (int8_t)r; a.offx[r] = 0; }
-  // layout trick: C=256, ntaps=1 makes the reducer write dwv[cout][256] unchanged
-  return run_wgrad<T>(a, dwv, 256, 1, st);
+  return a;
 }
-
-size_t vgg_first_wgrad_slab_bytes(int N, int H, int W) {
-  size_t a = slab_bytes<float>(N * H * W, 64, 128, 4), b = slab_bytes<bf16_t>(N * H * W, 64, 128, 4);   // 4 virtual taps
-  return a > b ? a : b;
-}
-template <typename T>
-int launch_vgg_first_conv_wgrad(int N, int H, int W, int Hp, int Wp, const T* dout, const T* img8, float* slab,
-                                float* dwv, hipStream_t st, int stride) {
-  const int OH = (H + 2 - 3) / stride + 1, OW = (W + 2 - 3) / stride + 1;
+WgradArgs wgrad_geom_first(int N, int OH, int OW, int Hp, int Wp, int stride) {
   WgradArgs a = {};
-  a.dy = dout; a.in = img8; a.slab = slab;
   a.N = N; a.IH = Hp; a.IW = Wp; a.C = 32; a.Cpitch = 8;
   a.OH = OH; a.OW = OW; a.Cout = 64; a.Ktot = 128;
   a.Sy = stride; a.Sx = stride; a.ntaps = 4;
   a.M = N * OH * OW;
   for (int r = 0; r < 4; ++r) { a.offy[r] = (int8_t)(r < 3 ? r : 0); a.offx[r] = 0; }
-  return run_wgrad<T>(a, dwv, 128, 1, st);
+  return a;
+}
+
+bool wgrad_plan(const WgradArgs& g, const ConvShape* s, int elem_bytes, WgradPlan& pl) {
+  const bool bf16 = elem_bytes == 2;
+  WgradRingPlan rp;
+  if (g.ntaps > MMSKIN_MAX_TAPS) return false;
+  if (bf16 && s && wgrad3_ring_plan(*s, pl)) {
+  } else if (bf16 && s && wgrad_taps3_plan(*s, pl)) {
+  } else {
+    // what the two tapped kernels ask of the geometry (16-bit reciprocal pixel stepping: outputs up to 240 x 240)
+    if (g.Cout % 64 || g.Ktot % 64 || g.C % (16 / elem_bytes) || g.OW > 240 || g.OH > 240) return false;
+    if (bf16 && wgrad_ring_plan(g, rp)) {
+      pl.family = WG_RING;
+      pl.tile_o = 64 * rp.wo; pl.tile_k = 64 * rp.wk; pl.variant = rp.s1 ? 1 : 0;
+      pl.nsplit = rp.nsplit; pl.per_split = rp.mps;
+    } else {
+      wgrad_staged_plan(g.M, g.Cout, g.Ktot, bf16 ? WG<bf16_t>::MS : WG<float>::MS, g.ntaps, pl);
+      pl.variant = (bf16 && g.simple1x1 && pl.tile_o + pl.tile_k >= 192) ? 1 : 0;
+    }
+  }
+  pl.reduce = pl.nsplit > WG_DIRECT_SPLITS ? WGR_LANES : WGR_DIRECT;
+  pl.slab_floats = (size_t)pl.nsplit * g.Cout * g.Ktot;
+  return true;
+}
+
+int wgrad_slab_check(const WgradArgs& g, const WgradPlan& pl, size_t floats) {
+  ARG_CHECK(pl.slab_floats <= floats, "wgrad: N=%d %dx%d -> %dx%d, Cout=%d, Ktot=%d writes %d slabs = %zu floats, the caller carved %zu",
+            g.N, g.IH, g.IW, g.OH, g.OW, g.Cout, g.Ktot, pl.nsplit, pl.slab_floats, floats);
+  return MMSKIN_OK;
+}
+
+// bytes to carve for a geometry: the larger of the two element types' plans (the sizing callers know no dtype), plus the unwritten allowance
+static size_t wgrad_slab_bytes(const WgradArgs& g, const ConvShape* s) {
+  int ns = 0;
+  WgradPlan pl;
+  for (int eb = 2; eb <= 4; eb += 2)
+    if (wgrad_plan(g, s, eb, pl) && pl.nsplit > ns) ns = pl.nsplit;
+  // Two terms kept from the sizes before the plan was one function, so that no workspace moves; no kernel writes what they add.
+  // (1) 3x3 shapes the ring takes are also counted with the split count of the register-staged all-taps kernel, which aims at 512 workgroups
+  // where the ring aims at 256: it decides for 64-cout 3x3 layers over many pixels (DenseNet-169's 128 -> 64 conv2 from batch 64 at 224^2
+  // or batch 256 at 128^2, a 64 -> 64 layer at 56^2 from batch 256).
+  if (s && wgrad_taps3_plan(*s, pl) && pl.nsplit > ns) ns = pl.nsplit;
+  // (2) geometries every kernel refuses (an output past 240 x 240: the stem from 482^2 images on) keep the fp32 register-staged count.
+  if (!ns && g.Cout % 64 == 0 && g.Ktot % 64 == 0) { wgrad_staged_plan(g.M, g.Cout, g.Ktot, WG<float>::MS, g.ntaps, pl); ns = pl.nsplit; }
+  return (size_t)(ns + (ns > WG_DIRECT_SPLITS ? WG_UNWRITTEN_SLABS : 0)) * g.Cout * g.Ktot * sizeof(float);
+}
+size_t conv_wgrad_slab_bytes(const ConvShape& s) { return wgrad_slab_bytes(wgrad_geom_conv(s), &s); }
+size_t stem_wgrad_slab_bytes(int N, int OH, int OW) { return wgrad_slab_bytes(wgrad_geom_stem(N, OH, OW, 2 * OH + 8, 2 * OW + 8), nullptr); }
+size_t vgg_first_wgrad_slab_bytes(int N, int H, int W) { return wgrad_slab_bytes(wgrad_geom_first(N, H, W, H + 2, W + 8, 1), nullptr); }
+
+// ------------------------------------------------------------------------------------------ the launchers
+// geometry -> plan -> capacity -> the family's kernel -> reduction.  s: see wgrad_plan(); C_for_layout / ntaps_for_layout: how the reducer
+// reads a slab row (the virtual geometries pass one tap of Ktot channels: dwv[cout][Ktot] unchanged)
+template <typename T>
+static int run_wgrad(WgradArgs& a, const ConvShape* s, const T* dout, const T* in, WgradSlab slab, float* dw, int C_for_layout,
+                     int ntaps_for_layout, hipStream_t st, int cout_valid = 0, int cin_valid = 0) {
+  WgradPlan pl;
+  ARG_CHECK(wgrad_plan(a, s, (int)sizeof(T), pl),
+            "wgrad: no kernel takes Cout=%d Ktot=%d C=%d taps=%d output %dx%d (Cout, Ktot multiples of 64, C of %d, <= %d taps, output <= 240x240)",
+            a.Cout, a.Ktot, a.C, a.ntaps, a.OH, a.OW, DT<T>::EPC, MMSKIN_MAX_TAPS);
+  if (int rc = wgrad_slab_check(a, pl, slab.floats)) return rc;
+  a.dy = dout; a.in = in; a.slab = slab.p;
+  a.ablate = 0;
+#ifdef MMSKIN_ABLATE
+  { const char* v = getenv("MMSKIN_WGRAD_ABLATE"); a.ablate = v ? atoi(v) : 0; }
+#endif
+  int rc = MMSKIN_ERR_ARG;
+  if constexpr (sizeof(T) == 2) {
+    if (pl.family == WG_RING3) rc = wgrad3_ring_launch(*s, pl, dout, in, slab.p, st);
+    else if (pl.family == WG_TAPS3) {
+      Wgrad3Args a3;
+      wgrad3_geom(*s, a3);
+      a3.dy = dout; a3.in = in; a3.slab = slab.p;
+      a3.stages_per_split = pl.per_split; a3.nsplit = pl.nsplit;
+      HIP_CHECK_RET(opt_in_dynamic_lds(reinterpret_cast<const void*>(wgrad3x3_kernel), W3_LDS_BYTES));
+      hipLaunchKernelGGL(wgrad3x3_kernel, dim3(a3.nblk_o * a3.nblk_c * a3.nsplit), dim3(256), W3_LDS_BYTES, st, a3);
+      HIP_CHECK_RET(hipGetLastError());
+      rc = MMSKIN_OK;
+    } else if (pl.family == WG_RING) {
+      rc = wgrad_ring_launch(a, WgradRingPlan{pl.tile_o / 64, pl.tile_k / 64, pl.nsplit, pl.per_split, pl.variant != 0, 0}, st);
+    }
+  }
+  if (pl.family == WG_STAGED) {
+    a.nsplit = pl.nsplit; a.m_per_split = pl.per_split;
+    a.nblk_o = a.Cout / pl.tile_o; a.nblk_k = a.Ktot / pl.tile_k;
+    switch (pl.tile_o + pl.tile_k / 64) {
+      case 130: rc = launch_wg<T, 128, 128, 2>(a, pl.variant != 0, st); break;
+      case 129: rc = launch_wg<T, 128, 64, 2>(a, pl.variant != 0, st); break;
+      case 66: rc = launch_wg<T, 64, 128, 2>(a, pl.variant != 0, st); break;
+      case 65: rc = launch_wg<T, 64, 64, 4>(a, false, st); break;
+    }
+  }
+  if (rc) return rc;
+  return reduce_slabs(slab.p, pl, a.Cout, a.Ktot, dw, C_for_layout, ntaps_for_layout, cout_valid, cin_valid, st);
+}
+
+template <typename T>
+int launch_conv_wgrad(const ConvShape& s, const T* dout, const T* in, WgradSlab slab, float* dw_oihw,
+                      hipStream_t st, int cout_valid, int cin_valid) {
+  WgradArgs a = wgrad_geom_conv(s);
+  return run_wgrad<T>(a, &s, dout, in, slab, dw_oihw, s.Cin, s.kh * s.kw, st, cout_valid, cin_valid);
+}
+template <typename T>
+int launch_stem_conv_wgrad(int N, int OH, int OW, int Hp, int Wp, const T* dout, const T* img4,
+                           WgradSlab slab, float* dwv, hipStream_t st) {
+  WgradArgs a = wgrad_geom_stem(N, OH, OW, Hp, Wp);
+  return run_wgrad<T>(a, nullptr, dout, img4, slab, dwv, 256, 1, st);
+}
+template <typename T>
+int launch_vgg_first_conv_wgrad(int N, int H, int W, int Hp, int Wp, const T* dout, const T* img8, WgradSlab slab,
+                                float* dwv, hipStream_t st, int stride) {
+  WgradArgs a = wgrad_geom_first(N, (H + 2 - 3) / stride + 1, (W + 2 - 3) / stride + 1, Hp, Wp, stride);
+  return run_wgrad<T>(a, nullptr, dout, img8, slab, dwv, 128, 1, st);
 }
 
 #define INST(T)                                                                                   \
-  template int launch_vgg_first_conv_wgrad<T>(int, int, int, int, int, const T*, const T*, float*, float*, hipStream_t, int); \
-  template int launch_conv_wgrad<T>(const ConvShape&, const T*, const T*, float*, float*, hipStream_t, int, int); \
-  template int launch_stem_conv_wgrad<T>(int, int, int, int, int, const T*, const T*, float*, float*, hipStream_t);
+  template int launch_vgg_first_conv_wgrad<T>(int, int, int, int, int, const T*, const T*, WgradSlab, float*, hipStream_t, int); \
+  template int launch_conv_wgrad<T>(const ConvShape&, const T*, const T*, WgradSlab, float*, hipStream_t, int, int); \
+  template int launch_stem_conv_wgrad<T>(int, int, int, int, int, const T*, const T*, WgradSlab, float*, hipStream_t);
 INST(float)
 INST(bf16_t)

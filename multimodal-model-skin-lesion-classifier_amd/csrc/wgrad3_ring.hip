@@ -279,41 +279,39 @@ __global__ __launch_bounds__(512) void wgrad3_ring_kernel(const Wgrad3RingArgs p
 }
 
 // ------------------------------------------------------------------------------------------ host
-struct Wgrad3RingPlan { Wgrad3RingArgs a; int wob, g, nyw; };
-
-static bool wgrad3_ring_plan_(const ConvShape& s, Wgrad3RingPlan& pl) {
-  if (s.kh != 3 || s.kw != 3 || s.stride != 1 || s.pad != 1) return false;
-  if (s.Cin % 64 || s.Cout % 64 || s.W > 62 || s.W < 1) return false;
-  if ((uint64_t)s.N * s.H * s.W * s.Cout * 2 >= 0xE0000000ull || (uint64_t)s.N * s.H * s.W * s.Cin * 2 >= 0xE0000000ull) return false;
-  Wgrad3RingArgs& a = pl.a;
+// the stage geometry of a shape the planner took
+static void w3r_geom(const ConvShape& s, Wgrad3RingArgs& a) {
   int R = 64 / s.W;
   if (R > s.H) R = s.H;
   const int W2p = (s.W + 2 + 15) / 16 * 16;
-  if ((R + 2) * W2p > W3R_YMAX) return false;
   a.N = s.N; a.H = s.H; a.W = s.W; a.C = s.Cin; a.Cout = s.Cout;
   a.R = R; a.spi = ceil_div(s.H, R);
   a.W2p = W2p; a.yrows = (R + 2) * W2p;
   a.total_stages = s.N * a.spi;
-  pl.wob = (s.Cout % 128 == 0) ? 2 : 1;
-  pl.g = 2 / pl.wob;
-  pl.nyw = ceil_div(pl.g * (a.yrows / 8), 8);
-  a.nblk_o = s.Cout / (64 * pl.wob); a.nblk_c = s.Cin / 64;
-  const int tiles = a.nblk_o * a.nblk_c;
+}
+
+bool wgrad3_ring_plan(const ConvShape& s, WgradPlan& pl) {
+  if (s.kh != 3 || s.kw != 3 || s.stride != 1 || s.pad != 1) return false;
+  if (s.Cin % 64 || s.Cout % 64 || s.W > 62 || s.W < 1) return false;
+  if ((uint64_t)s.N * s.H * s.W * s.Cout * 2 >= 0xE0000000ull || (uint64_t)s.N * s.H * s.W * s.Cin * 2 >= 0xE0000000ull) return false;
+  Wgrad3RingArgs a;
+  w3r_geom(s, a);
+  if (a.yrows > W3R_YMAX) return false;
+  const int wob = (s.Cout % 128 == 0) ? 2 : 1, g = 2 / wob;
+  const int nyw = ceil_div(g * (a.yrows / 8), 8);
+  const int tiles = (s.Cout / (64 * wob)) * (s.Cin / 64);
   constexpr int target = 256;   // one 8-wave workgroup per CU
   int ns = target / tiles > 0 ? target / tiles : 1;
   // a split writes a whole tile x 9 taps of fp32 (147 - 295 KB) and the reduction reads it back: at least ~16 stages of work per split
   constexpr int min_stages = 16;
   if (ns > a.total_stages / min_stages) ns = a.total_stages / min_stages > 0 ? a.total_stages / min_stages : 1;
   if (ns > a.total_stages) ns = a.total_stages;
-  a.stages_per_split = ceil_div(ceil_div(a.total_stages, ns), pl.g) * pl.g;   // whole iterations
-  a.nsplit = ceil_div(a.total_stages, a.stages_per_split);
-  return true;
-}
-
-bool wgrad3_ring_takes(const ConvShape& s, int* nsplit) {
-  Wgrad3RingPlan pl;
-  if (!wgrad3_ring_plan_(s, pl)) return false;
-  if (nsplit) *nsplit = pl.a.nsplit;
+  pl.family = WG_RING3;
+  pl.tile_o = 64 * wob; pl.tile_k = 64;
+  // window pieces per wave and iteration the kernel is instantiated for
+  pl.variant = wob == 2 ? (nyw <= 2 ? 2 : 3) : (nyw <= 3 ? 3 : nyw <= 5 ? nyw : 6);
+  pl.per_split = ceil_div(ceil_div(a.total_stages, ns), g) * g;   // whole iterations
+  pl.nsplit = ceil_div(a.total_stages, pl.per_split);
   return true;
 }
 
@@ -330,24 +328,23 @@ static int w3r_launch_t(const Wgrad3RingArgs& a, hipStream_t st) {
   return MMSKIN_OK;
 }
 
-// launches the GEMM; the caller reduces the a.nsplit slabs [Cout][9 Cin]
-int launch_wgrad3_ring(const ConvShape& s, const bf16_t* dout, const bf16_t* in, float* slab, hipStream_t st, int* nsplit) {
-  Wgrad3RingPlan pl;
-  ARG_CHECK(wgrad3_ring_plan_(s, pl), "wgrad3_ring: shape not taken");
-  pl.a.dy = dout; pl.a.in = in; pl.a.slab = slab;
-  *nsplit = pl.a.nsplit;
+// launches the GEMM of a WG_RING3 plan; the caller reduces the pl.nsplit slabs [Cout][9 Cin]
+int wgrad3_ring_launch(const ConvShape& s, const WgradPlan& pl, const bf16_t* dout, const bf16_t* in, float* slab, hipStream_t st) {
+  Wgrad3RingArgs a;
+  w3r_geom(s, a);
+  a.dy = dout; a.in = in; a.slab = slab;
+  a.nblk_o = s.Cout / pl.tile_o; a.nblk_c = s.Cin / 64;
+  a.stages_per_split = pl.per_split; a.nsplit = pl.nsplit;
   ++g_w3r_launches;
   // stage = 40 KB (128-cout tile) / 32 KB (64-cout tile, two per iteration): three resp. two iterations in the ring
-  if (pl.wob == 2) {
-    switch (pl.nyw) {
-      case 1: case 2: return w3r_launch_t<2, 1, 2, 3>(pl.a, st);
-      default: return w3r_launch_t<2, 1, 3, 3>(pl.a, st);
-    }
+  switch (pl.tile_o * 10 + pl.variant) {
+    case 1282: return w3r_launch_t<2, 1, 2, 3>(a, st);
+    case 1283: return w3r_launch_t<2, 1, 3, 3>(a, st);
+    case 643: return w3r_launch_t<1, 2, 3, 2>(a, st);
+    case 644: return w3r_launch_t<1, 2, 4, 2>(a, st);
+    case 645: return w3r_launch_t<1, 2, 5, 2>(a, st);
+    case 646: return w3r_launch_t<1, 2, 6, 2>(a, st);
   }
-  switch (pl.nyw) {
-    case 1: case 2: case 3: return w3r_launch_t<1, 2, 3, 2>(pl.a, st);
-    case 4: return w3r_launch_t<1, 2, 4, 2>(pl.a, st);
-    case 5: return w3r_launch_t<1, 2, 5, 2>(pl.a, st);
-    default: return w3r_launch_t<1, 2, 6, 2>(pl.a, st);
-  }
+  mmskin_set_error("wgrad3_ring: no kernel for a %d-cout tile with %d window pieces", pl.tile_o, pl.variant);
+  return MMSKIN_ERR_ARG;
 }

@@ -294,7 +294,8 @@ __global__ __launch_bounds__(512) void wgrad_ring_kernel(const WgradArgs p) {
 // ------------------------------------------------------------------------------------------ host
 constexpr int RING_TARGET_BLOCKS = 256;   // one 8-wave workgroup per CU
 
-bool wgrad_ring_tile(int M, int Cout, int Ktot, WgradRingPlan& r, bool simple) {
+// tile shape + split count from the GEMM dimensions (simple: 1x1 / stride 1)
+static bool wgrad_ring_tile(int M, int Cout, int Ktot, WgradRingPlan& r, bool simple) {
   if (Cout % 64 || Ktot % 64) return false;
   // 1x1 / stride 1 layers: 128 x 128 tiles with two pixel groups wherever they fit -- half the slab bytes per workgroup for 4/3 of the
   // L2 -> LDS fill: l2.c3 56.5 -> 48.6 us, l3.c3 43.7 -> 40.3, l4.c3 41.8 -> 38.6 (profiles/r04_experiments.txt (4)); the gathering
@@ -453,7 +454,6 @@ static int ring_launch_t(const WgradArgs& a, bool s1, hipStream_t st) {
 }
 
 static int g_ring_launches = 0;
-int wgrad_ring_launch_count() { return g_ring_launches; }
 extern "C" int64_t mmskin_wgrad_ring_launches(void) { return g_ring_launches; }
 
 int wgrad_ring_launch(WgradArgs& a, const WgradRingPlan& r, hipStream_t st) {
@@ -464,11 +464,15 @@ int wgrad_ring_launch(WgradArgs& a, const WgradRingPlan& r, hipStream_t st) {
   ++g_ring_launches;
   // ring depth: G = 1 tiles move 24 KB per iteration (4 deep = 96 KB), G = 2 tiles 32 - 40 KB (3 deep = 96 - 120 KB).
   // The MFMA-bound tiles (layers 2 - 4) run with the two wave halves half an iteration apart (STAG).
-  if (r.wo == 4 && r.wk == 2) return ring_launch_t<4, 2, 4, true>(a, r.s1, st);
-  if (r.wo == 2 && r.wk == 4) return ring_launch_t<2, 4, 4, true>(a, r.s1, st);
-  if (r.wo == 2 && r.wk == 2) return ring_launch_t<2, 2, 4, true>(a, r.s1, st);
-  if (r.wo == 4 && r.wk == 1) return ring_launch_t<4, 1, 3>(a, r.s1, st);
-  if (r.wo == 1 && r.wk == 4) return ring_launch_t<1, 4, 3>(a, r.s1, st);
-  if (r.wo == 2 && r.wk == 1) return ring_launch_t<2, 1, 2>(a, r.s1, st);     // 48 KB per iteration (four groups): two deep
-  return ring_launch_t<1, 2, 2>(a, r.s1, st);
+  switch (r.wo * 10 + r.wk) {
+    case 42: return ring_launch_t<4, 2, 4, true>(a, r.s1, st);
+    case 24: return ring_launch_t<2, 4, 4, true>(a, r.s1, st);
+    case 22: return ring_launch_t<2, 2, 4, true>(a, r.s1, st);
+    case 41: return ring_launch_t<4, 1, 3>(a, r.s1, st);
+    case 14: return ring_launch_t<1, 4, 3>(a, r.s1, st);
+    case 21: return ring_launch_t<2, 1, 2>(a, r.s1, st);     // 48 KB per iteration (four groups): two deep
+    case 12: return ring_launch_t<1, 2, 2>(a, r.s1, st);
+  }
+  mmskin_set_error("wgrad_ring: no kernel for a %d x %d tile", 64 * r.wo, 64 * r.wk);
+  return MMSKIN_ERR_ARG;
 }

@@ -14,6 +14,8 @@ HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "
 
 F32, BF16 = 0, 1
 LINEAR_SMALL, LINEAR_BIG_F32, LINEAR_BIG_BF16, LINEAR_PADDED_BF16 = 0, 1, 2, 3   # mmskin_linear_route (MMSKIN_LINEAR_* in mmskin.h)
+WG_STAGED, WG_TAPS3, WG_RING, WG_RING3 = 0, 1, 2, 3   # mmskin_conv_wgrad_plan family (MMSKIN_WG_* in mmskin.h)
+WGR_DIRECT, WGR_LANES = 0, 1                          # ... and reduce
 
 _lib = None
 
@@ -61,6 +63,8 @@ _SIGNATURES = {
     "mmskin_conv2d_backward": (_i, [_P] * 5 + [_i] * 10 + [_P, _P]),
     "mmskin_conv_pipe_launches": (_i64, []),
     "mmskin_wgrad_ring_launches": (_i64, []),
+    "mmskin_conv_wgrad_plan": (_i, [_i] * 10 + [_P]),
+    "mmskin_conv_wgrad_slab_check": (_i, [_i] * 10 + [_i64]),
     "mmskin_conv3x3_c64_launches": (_i64, []),
     "mmskin_stem7x7_launches": (_i64, []),
     "mmskin_conv2d_dgrad_fused_rows": (_i, [_i] * 9),

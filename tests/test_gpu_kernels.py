@@ -567,31 +567,45 @@ torch.save([t.detach().cpu() for t in (y, xd.grad, wd.grad, bd.grad)], sys.argv[
 
 @pytest.mark.parametrize("blocks", ["3", "7"])
 def test_wgrad3x3_multi_stage_splits(blocks):
-    """All-taps 3x3 weight gradient with few workgroups (MMSKIN_WGRAD3_BLOCKS, read once -> fresh process): every split
-    walks many stages, crosses image boundaries and -- with 7 -- starts in the middle of an image (ragged last stage:
-    14 rows = 4 + 4 + 4 + 2).  bf16 path against torch on the same inputs."""
+    """All-taps 3x3 weight gradient with few workgroups (MMSKIN_WGRAD3_BLOCKS, read once -> fresh process).  The knob belongs to the
+    register-staged all-taps kernel (WG_TAPS3), which runs only where the ring refuses the shape: the first three shapes run the ring
+    (WG_RING3, asserted), the fourth -- 12 rows of 5 per stage, three stages per image with a ragged last one (30 = 12 + 12 + 6), 111
+    stages -- runs WG_TAPS3 over 3 splits of 37 stages or 6 of 19, so splits start inside images.  Family, tile and split count come from
+    the route table (tests/wgrad_plan_cases.py) and are asserted through mmskin_conv_wgrad_plan.  bf16 path against torch on the same
+    inputs, every tap plane separately."""
     import subprocess, sys
     code = r'''
 import sys
 sys.path[:0] = [%r, %r, %r]
 import torch, torch.nn.functional as F
 from gpu_util import DEV, conv_backward, rel_err
+from mmskin import _lib
+from wgrad_plan_cases import MULTI_STAGE_ROWS, TAPS3_KNOB, WG_TAPS3, plan
+lib = _lib.load()
 g = torch.Generator().manual_seed(11)
-for (N, Cin, H, W, Cout) in [(5, 64, 14, 14, 128), (3, 128, 9, 13, 64), (2, 64, 56, 56, 64)]:
+for row in MULTI_STAGE_ROWS:
+    N, Cin, H, W, Cout = row.shape[:5]
+    got = plan(lib, row.shape, 2)
+    assert got[:4] == (row.family, row.tile_o, row.tile_k, row.variant), (row, got)
+    if row.family == WG_TAPS3:
+        assert got[4:6] == TAPS3_KNOB[%r], got
     x = torch.randn(N, Cin, H, W, generator=g)
     w = torch.randn(Cout, Cin, 3, 3, generator=g) / (Cin * 9) ** 0.5
     xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
     y = F.conv2d(xr, wr, stride=1, padding=1)
     dy = torch.randn(y.shape, generator=g)
     y.backward(dy)
+    n0 = lib.mmskin_wgrad3_ring_launches()
     dx, dw = conv_backward(dy.to(DEV), x.to(DEV), w.to(DEV), 1, 1, "bf16")
+    assert lib.mmskin_wgrad3_ring_launches() == n0 + (0 if row.family == WG_TAPS3 else 1), row
     e = rel_err(dw, wr.grad)
-    print("ERR", (N, Cin, H, W, Cout), e)
-    assert e < 5e-2, e
+    per_tap = [rel_err(dw[:, :, t // 3, t %% 3], wr.grad[:, :, t // 3, t %% 3]) for t in range(9)]
+    print("ERR", (N, Cin, H, W, Cout), e, max(per_tap))
+    assert e < 5e-2 and max(per_tap) < 5e-2, (e, per_tap)
 '''
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MMSKIN_WGRAD3_BLOCKS=blocks)
     r = subprocess.run([sys.executable, "-c", code % (os.path.join(root, "tests"), root,
-                                                     os.path.join(root, "multimodal-model-skin-lesion-classifier_amd"))],
+                                                     os.path.join(root, "multimodal-model-skin-lesion-classifier_amd"), blocks)],
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr

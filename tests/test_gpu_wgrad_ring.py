@@ -4,7 +4,8 @@ through LDS) against torch's conv2d weight gradient (the ATen op the reference r
 Inputs are bf16-REPRESENTABLE, so the bf16 kernel multiplies exactly what the fp64 reference multiplies and the only difference left
 is the fp32 accumulation order: the bound is 1e-4 of the gradient's rms on the WORST element (measured ~2e-6), i.e. one dropped
 8-pixel fragment, one stale ring slot or one row taken from the neighbouring split fails it -- unlike the 5e-2 bf16 bound of
-test_gpu_kernels.py, which has to absorb operand rounding.  Every case asserts through mmskin_wgrad_ring_launches() that the ring
+test_gpu_kernels.py, which has to absorb operand rounding.  Every case asserts through mmskin_conv_wgrad_plan that the library
+plans the family, tile and variant the route table (tests/wgrad_plan_cases.py) names for it, and through mmskin_wgrad_ring_launches() that the ring
 kernel is what ran.  Measured errors go to gpurun_out/parity_report.jsonl."""
 import json
 import os
@@ -15,30 +16,14 @@ import torch.nn.functional as F
 
 from gpu_util import DEV, conv_backward, rel_err
 from mmskin import _lib
+from wgrad_plan_cases import BF16, RING3_ROWS, RING_ROWS, WG_RING, WG_RING3, plan
 
 pytestmark = pytest.mark.gpu
 REPORT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "parity_report.jsonl")
 TOL = 1e-4
 
-CASES = [
-    # N, Cin, H, W, Cout, k, stride, pad, what
-    (2, 64, 14, 14, 256, 1, 1, 0, "256x64 tile, two pixel groups meet in LDS, ragged last iteration (392 = 6*64 + 8)"),
-    (2, 256, 14, 14, 64, 1, 1, 0, "Cout = 64: 64x256 tile, two groups"),
-    (2, 256, 9, 11, 128, 1, 1, 0, "128x256 tile (one group of 8 waves), odd sizes, ragged last stage"),
-    (3, 128, 10, 10, 256, 1, 1, 0, "256x128 tile"),
-    (2, 128, 12, 12, 128, 1, 1, 0, "128x128 tile, two groups"),
-    (24, 128, 14, 14, 256, 1, 1, 0, "17 splits, the last one short"),
-    (40, 64, 14, 14, 256, 1, 1, 0, "two-group tile over 14 splits"),
-    (2, 256, 14, 14, 512, 1, 2, 0, "stride-2 gather (downsample 1x1), 2 cout tiles x 2 k tiles"),
-    (3, 256, 15, 13, 256, 1, 2, 0, "stride-2 gather on odd sizes"),
-    (2, 128, 14, 14, 128, 3, 2, 1, "3x3 stride 2: nine taps, padding taps zero-filled by out-of-range offsets"),
-    (2, 128, 15, 13, 128, 3, 2, 1, "3x3 stride 2, odd sizes"),
-    (16, 128, 28, 28, 128, 3, 2, 1, "3x3 stride 2 over 6 splits that cross image boundaries"),
-    (2, 64, 12, 12, 256, 3, 2, 1, "Cin = 64: nine 64-wide k tiles, one tap each, 256x64 tiles"),
-    (3, 192, 14, 14, 128, 1, 1, 0, "128x64 tiles, FOUR pixel groups of two waves (DenseNet bottleneck: Ktot = 64 x 3), ragged"),
-    (24, 320, 14, 14, 128, 1, 1, 0, "128x64 tiles over several splits"),
-    (3, 128, 14, 14, 64, 1, 1, 0, "64x128 tiles, four groups"),
-]
+# N, Cin, H, W, Cout, k, stride, pad, what -- with the family and tile every case must run, from the route table (tests/wgrad_plan_cases.py)
+CASES = [r.shape + (r.note,) for r in RING_ROWS]
 
 
 def _record(**kw):
@@ -62,6 +47,8 @@ def test_ring_wgrad_matches_fp64_reference(case):
     dy = _bf16_exact(torch.randn(N, Cout, OH, OW, generator=g))
     xr, wr = x.double(), w.double().requires_grad_(True)
     F.conv2d(xr, wr, stride=stride, padding=pad).backward(dy.double())
+    row = RING_ROWS[CASES.index(case)]
+    assert row.family == WG_RING and plan(lib, row.shape, BF16)[:4] == (row.family, row.tile_o, row.tile_k, row.variant), (what, plan(lib, row.shape, BF16))
     n0 = lib.mmskin_wgrad_ring_launches()
     _, dw = conv_backward(dy.to(DEV), x.to(DEV), w.to(DEV), stride, pad, "bf16")
     assert lib.mmskin_wgrad_ring_launches() == n0 + 1, "ring kernel not selected"
@@ -73,18 +60,8 @@ def test_ring_wgrad_matches_fp64_reference(case):
     assert err < TOL, (what, err)
 
 
-CASES3 = [
-    # N, Cin, H, W, Cout, what  (3x3 / stride 1 / pad 1: csrc/wgrad3_ring.hip)
-    (3, 64, 56, 56, 64, "one 56-wide row per stage, 64-cout tile: two groups take alternate stages and meet in LDS"),
-    (5, 64, 14, 14, 128, "four rows per stage, ragged last stage of every image (14 = 4+4+4+2), 128-cout tile"),
-    (3, 128, 28, 28, 128, "two rows per stage, two cin tiles"),
-    (4, 128, 7, 7, 256, "whole 7x7 images per stage, two cout tiles x two cin tiles"),
-    (2, 64, 9, 13, 64, "odd sizes: 4 rows of 13"),
-    (6, 64, 28, 28, 64, "64-cout tile at width 28"),
-    (9, 64, 7, 7, 64, "64-cout tile at width 7: odd stage count, the second group's last stage is empty"),
-    (70, 64, 14, 14, 64, "16 splits that start inside images"),
-    (40, 128, 14, 14, 128, "128-cout tile over 10 splits"),
-]
+# N, Cin, H, W, Cout, what  (3x3 / stride 1 / pad 1: csrc/wgrad3_ring.hip)
+CASES3 = [r.shape[:5] + (r.note,) for r in RING3_ROWS]
 
 
 @pytest.mark.parametrize("case", CASES3, ids=[f"k{i}" for i in range(len(CASES3))])
@@ -97,6 +74,8 @@ def test_ring_wgrad3x3_matches_fp64_reference(case):
     dy = _bf16_exact(torch.randn(N, Cout, H, W, generator=g))
     wr = w.double().requires_grad_(True)
     F.conv2d(x.double(), wr, stride=1, padding=1).backward(dy.double())
+    row = RING3_ROWS[CASES3.index(case)]
+    assert row.family == WG_RING3 and plan(lib, row.shape, BF16)[:4] == (row.family, row.tile_o, row.tile_k, row.variant), (what, plan(lib, row.shape, BF16))
     n0 = lib.mmskin_wgrad3_ring_launches()
     _, dw = conv_backward(dy.to(DEV), x.to(DEV), w.to(DEV), 1, 1, "bf16")
     assert lib.mmskin_wgrad3_ring_launches() == n0 + 1, "3x3 ring kernel not selected"
