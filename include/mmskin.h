@@ -727,6 +727,22 @@ int mmskin_criterion_backward(const void* logits, int logits_dtype, const void* 
                               float gamma, int B, int C, const float* dloss, const float* scratch, void* dlogits, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * One-vs-rest AUC of an evaluation pass as exact integer counts (csrc/auc.hip).  probs: fp32 [N][C], row-major, contiguous
+ * (the rows the criterion's probs_out collected); labels: int64 [N], read in place.  counts: int64 [3 C + 1] on the device,
+ *   counts[c]          pos[c]    rows with label c
+ *   counts[C + c]      neg[c]    rows with a label in [0, C) other than c
+ *   counts[2 C + c]    wins2[c]  sum over the pairs (i with label c, j with another label in [0, C)) of
+ *                                2 [probs[i][c] > probs[j][c]] + [probs[i][c] == probs[j][c]]
+ *   counts[3 C]        nan       NaN entries of probs in the rows that count
+ * Rows whose label lies outside [0, C) count nowhere, as in the criterion's meter; a NaN compares as neither greater nor equal.
+ * auc[c] = wins2[c] / (2 pos[c] neg[c]) is the Mann-Whitney statistic: the area under the ROC curve by trapezoids, ties at half
+ * weight.  All sums are integers (64-bit integer atomics), so the block is bitwise repeatable and independent of the launch
+ * geometry.  N^2 compares: a row is compared in the column of its own label only.  The entry zeroes `counts` on `stream` itself
+ * and allocates nothing.  2 <= C <= 1024, 1 <= N < 2^31; anything else, or a null argument, is MMSKIN_ERR_ARG with nothing
+ * launched (no GPU needed). */
+int mmskin_ovr_auc_counts(const float* probs, const int64_t* labels, int64_t N, int C, int64_t* counts, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * `custom-cnn` image encoder pieces (loadImageModelClassifier.py:50-60): small direct kernels for
  * shapes the MFMA implicit GEMM does not cover (Cin=3, Cout=16).  NCHW fp32. */
 int mmskin_direct_conv2d_forward(const float* x, const float* w, const float* b, float* y, int N, int Cin, int H, int W,

@@ -5,7 +5,8 @@ Layout:
   mmskin/    ctypes binding, autograd wrappers, parameter-holder modules, DP helper
   models/    drop-in modules with the reference's file / class names
 """
-from . import _lib, criterion  # noqa: F401
+from . import _lib, criterion, evaluate  # noqa: F401
 from .criterion import CrossEntropyLoss, EpochMeter, FocalLoss, SoftTargetCrossEntropy  # noqa: F401
+from .evaluate import evaluate_model  # noqa: F401
 
-__all__ = ["_lib", "criterion", "CrossEntropyLoss", "FocalLoss", "SoftTargetCrossEntropy", "EpochMeter"]
+__all__ = ["_lib", "criterion", "evaluate", "CrossEntropyLoss", "FocalLoss", "SoftTargetCrossEntropy", "EpochMeter", "evaluate_model"]

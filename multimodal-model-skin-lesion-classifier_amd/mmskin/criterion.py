@@ -20,7 +20,7 @@ fp32, also for bf16 logits; dlogits has the logits' dtype.  CPU tensors take the
     with torch.no_grad():
         for image, metadata, label in val_loader:
             meter.update(model(image, metadata), label)
-    metrics = meter.compute()                                       # AUC stays with the caller: roc_auc_score(labels, probs.cpu())
+    metrics = meter.compute()                                       # with the AUC and the .npy files: mmskin.evaluate.evaluate_model
 """
 import numpy as np
 import torch
