@@ -683,8 +683,12 @@ __global__ void embedding_bwd_kernel(const float* dout, const int64_t* ids, floa
     int64_t t = i / E;
     int id = (int)(t % card), col = (int)(t / card);
     float s = 0.f;
-    for (int bb = 0; bb < B; ++bb)
-      if (ids[(int64_t)bb * ncols + col] == id) s += dout[((int64_t)bb * ncols + col) * E + e];
+    for (int bb = 0; bb < B; ++bb) {
+      int64_t v = ids[(int64_t)bb * ncols + col];   // clamped as the forward clamps it: the row that was read gets the gradient
+      if (v < 0) v = 0;
+      if (v >= card) v = card - 1;
+      if (v == id) s += dout[((int64_t)bb * ncols + col) * E + e];
+    }
     dtable[i] = s;
   }
 }
