@@ -147,6 +147,25 @@ int mmskin_conv_wgrad_plan(int N, int Cin, int H, int W, int Cout, int kh, int k
 int mmskin_conv_wgrad_slab_check(int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int elem_bytes,
                                  int64_t capacity_floats);
 int64_t mmskin_wgrad3_ring_launches(void);   /* ... of the all-taps 3x3 ring kernel (wgrad3_ring.hip) */
+/* The route of a convolution forward (op 0) or data gradient (op 1) launch with the fused operands `flags` names (csrc/conv_gemm.hip
+ * conv_gemm_route; a Linear of M rows, K -> N is the convolution N = M, H = W = 1, Cin = K, Cout = N, 1x1): out = family, bm (tile rows
+ * computed), step (valid rows per row block), bn (tile columns), nst (LDS stages; 8 = the pipelined loop), epi (epilogue instantiation),
+ * group_m (grouped tile order, 0 = off), total_mblk (row blocks = statistics / partial rows written), nblk_n (column blocks).
+ * MMSKIN_CG_C64 / MMSKIN_CG_STEM7 (conv3x3_c64.hip, stem7x7.hip): family and total_mblk only.  op 2: the 7x7 / stride 2 stem of an
+ * N x 3 x H x W batch; op 3: the 3-channel 3x3 / pad 1 first conv at `stride`; both in the virtual form the plans run, other shape arguments
+ * unused, flags: MMSKIN_CRF_STATS (op 3 also BIAS, ADDEND, RELU).  Pure host arithmetic, no device needed; MMSKIN_ERR_ARG when no kernel
+ * takes the launch.  Tests assert it so that a case keeps covering the kernel it was written for. */
+enum { MMSKIN_CG_TILE128 = 0, MMSKIN_CG_BIG256 = 1, MMSKIN_CG_PIPE = 2, MMSKIN_CG_C64 = 3, MMSKIN_CG_STEM7 = 4 };
+enum {   /* op 0: statistics slabs | the caller takes the statistics row count | FwdFuse operands (a FwdFuse is passed when one is named) | no T output */
+  MMSKIN_CRF_STATS = 1, MMSKIN_CRF_ROWS_FREE = 2, MMSKIN_CRF_BIAS = 4, MMSKIN_CRF_ADDEND = 8, MMSKIN_CRF_RELU = 16, MMSKIN_CRF_GELU = 32,
+  MMSKIN_CRF_OUT_F32 = 64, MMSKIN_CRF_RESIDUAL = 128 /* gamma + fp32 residual (the transformer-residual epilogue) */, MMSKIN_CRF_MASK_OUT = 256,
+  MMSKIN_CRF_MUL = 512, MMSKIN_CRF_NO_OUT = 1024
+};
+enum {   /* op 1: addend | the addend is din | DgradFuse operands (a DgradFuse is passed when one is named; EMPTY: one without operands); k2 = flags >> 16 */
+  MMSKIN_CRD_ADDEND = 1, MMSKIN_CRD_ADDEND_IS_DIN = 2, MMSKIN_CRD_MASK_Y = 4, MMSKIN_CRD_MASK_BITS = 8, MMSKIN_CRD_X = 16, MMSKIN_CRD_SCALE_SHIFT = 32,
+  MMSKIN_CRD_X2 = 64, MMSKIN_CRD_IN2 = 128, MMSKIN_CRD_BIAS = 256, MMSKIN_CRD_ADDEND_S2 = 512, MMSKIN_CRD_PARTIAL = 1024, MMSKIN_CRD_EMPTY = 2048
+};
+int mmskin_conv_route(int op, int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int elem_bytes, int flags, int64_t out[9]);
 /* Algebraic BatchNorm backward of an expanding 1x1 convolution x = conv(y, w) (csrc/abn.hip; bf16 operands): with
  * dz = cA g + cB x + cC per channel, dy = dz w and dw = dz^T y are computed from g, y, w and the coefficients alone
  * (dy = [g | y][cA w ; w^T diag(cB) w] + cC w, dw = cA (g^T y) + cB (w (y^T y)) + cC (x) colsum(y)): neither dz nor x is read.

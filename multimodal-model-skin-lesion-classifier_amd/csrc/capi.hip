@@ -1186,6 +1186,55 @@ int mmskin_conv_wgrad_slab_check(int N, int Cin, int H, int W, int Cout, int kh,
   if (int rc = wgrad_export_plan(N, Cin, H, W, Cout, kh, kw, stride, pad, elem_bytes, g, pl)) return rc;
   return wgrad_slab_check(g, pl, capacity_floats < 0 ? 0 : (size_t)capacity_floats);
 }
+int mmskin_conv_route(int op, int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int elem_bytes, int flags, int64_t out[9]) {
+  static_assert(CG_TILE128 == MMSKIN_CG_TILE128 && CG_BIG256 == MMSKIN_CG_BIG256 && CG_PIPE == MMSKIN_CG_PIPE && CG_C64 == MMSKIN_CG_C64 &&
+                CG_STEM7 == MMSKIN_CG_STEM7, "mmskin.h documents the ConvRoute values");
+  ARG_CHECK(out && op >= 0 && op <= 3 && N > 0 && H > 0 && W > 0 && (elem_bytes == 2 || elem_bytes == 4), "conv_route: bad argument");
+  ARG_CHECK(op >= 2 || (Cin > 0 && Cout > 0 && kh > 0 && kw > 0 && stride > 0 && pad >= 0), "conv_route: bad argument");
+  // the route only asks whether an operand is there: one address stands for every operand a flag names
+  static float operand[1];
+  void* const set = operand;
+  auto on = [&](int bit) -> float* { return (flags & bit) ? operand : nullptr; };
+  const ConvShape s = {N, H, W, Cin, Cout, kh, kw, stride, pad};
+  ConvGemmArgs a;
+  ConvRoute r;
+  int rc = MMSKIN_OK;
+  if (op == 1) {
+    DgradFuse f;
+    f.mask_y = on(MMSKIN_CRD_MASK_Y); f.mask_bits = reinterpret_cast<const uint8_t*>(on(MMSKIN_CRD_MASK_BITS)); f.x = on(MMSKIN_CRD_X);
+    f.scale = f.shift = on(MMSKIN_CRD_SCALE_SHIFT); f.x2 = on(MMSKIN_CRD_X2); f.in2 = on(MMSKIN_CRD_IN2); f.k2 = (flags >> 16) & 0xffff;
+    f.bias = on(MMSKIN_CRD_BIAS); f.addend_s2 = (flags & MMSKIN_CRD_ADDEND_S2) != 0; f.partial = f.partial_b = on(MMSKIN_CRD_PARTIAL);
+    static float other[1];   // din; the addend is this or its own buffer
+    unsigned zero_mask;
+    rc = conv_route_dgrad(s, elem_bytes, set, set, other, (flags & MMSKIN_CRD_ADDEND) ? ((flags & MMSKIN_CRD_ADDEND_IS_DIN) ? other : operand) : nullptr,
+                          (flags & 0xffc) ? &f : nullptr, a, zero_mask, r);
+  } else {
+    FwdFuse f;
+    f.bias = on(MMSKIN_CRF_BIAS); f.addend = on(MMSKIN_CRF_ADDEND); f.relu = (flags & MMSKIN_CRF_RELU) != 0; f.gelu = (flags & MMSKIN_CRF_GELU) != 0;
+    f.out_f32 = on(MMSKIN_CRF_OUT_F32); f.gamma = f.res_f32 = on(MMSKIN_CRF_RESIDUAL); f.mul = on(MMSKIN_CRF_MUL);
+    f.mask_out = reinterpret_cast<uint8_t*>(on(MMSKIN_CRF_MASK_OUT));
+    float* const stats = on(MMSKIN_CRF_STATS);
+    if (op == 0) {
+      rc = conv_route_fwd(s, elem_bytes, set, set, (flags & MMSKIN_CRF_NO_OUT) ? nullptr : set, stats, stats, (flags & 0x3fc) ? &f : nullptr,
+                          (flags & MMSKIN_CRF_ROWS_FREE) != 0, a, r);
+    } else if (op == 2) {   // the 7x7 / stride 2 stem of an N x 3 x H x W batch, in the geometry the plans run
+      const StemGeom sg(N, H, W);
+      a = conv_geom_stem(sg.N, sg.OH, sg.OW, sg.Hp, sg.Wp);
+      a.in = a.w = set; a.out = set; a.stat_sum = a.stat_sq = stats;
+      rc = conv_route_stem(a, elem_bytes, sg.Hp, sg.Wp, r);
+    } else {                // the 3-channel 3x3 / pad 1 first conv (stride 1 | 2); flags: statistics, bias, addend, relu
+      ARG_CHECK(stride == 1 || stride == 2, "conv_route: first conv stride");
+      a = conv_geom_first(N, (H + 2 - 3) / stride + 1, (W + 2 - 3) / stride + 1, H + 2, (W + 4 + 1) / 2 * 2, stride);
+      a.in = a.w = set; a.out = set; a.stat_sum = a.stat_sq = stats;
+      a.ep_bias = f.bias; a.addend = f.addend; a.ep_relu = f.relu ? 1 : 0;
+      rc = conv_gemm_route(a, elem_bytes, r) ? MMSKIN_OK : MMSKIN_ERR_ARG;
+    }
+  }
+  if (rc) return rc;
+  const int64_t v[9] = {r.family, r.bm, r.step, r.bn, r.nst, r.epi, r.group_m, r.total_mblk, r.nblk_n};
+  for (int i = 0; i < 9; ++i) out[i] = v[i];
+  return MMSKIN_OK;
+}
 int64_t mmskin_slice_stats_workspace_bytes(int64_t rows, int pitch, int c0, int C) {
   if (!SLICE_OK) return -1;
   return ws_bytes<SliceStatsWs<float>>(rows, pitch, C);

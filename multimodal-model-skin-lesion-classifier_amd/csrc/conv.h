@@ -59,11 +59,10 @@ struct ConvGemmArgs {
   uint64_t in_bytes;   // size of the gather source in bytes (the pipelined kernel's buffer descriptor: reads past it return zeros); 0 = not set
   int bm_step;         // valid rows per row block (= the tile height except for the pipelined kernel's 196-of-224-row tiles); set by finish_classes
   int pipe_ok;         // the caller can take a row-block count that differs from ceil(rows / 128) (statistics slabs), so any tile height may be chosen
-  int group_m;         // > 1: tiles are ordered in groups of group_m row blocks x all column blocks, row block fastest (Linear GEMMs whose
-                       // weight matrix exceeds an XCD's 4 MB L2: the group's A rows stay resident while the weight streams through ONCE per group)
+  int group_m;         // > 1: tiles are ordered in groups of group_m row blocks x all column blocks, row block fastest (set from ConvRoute::group_m)
   // ---- two-source A operand (algebraic BatchNorm backward of an expanding 1x1 convolution, backbone.hip): reduction indices
-  // [0, K1) come from `in` (row pitch Cpitch), [K1, C) from `in2` (row pitch Cpitch >> pitch2_shift).  simple_src launches of the
-  // 128-row kernels only.
+  // [0, K1) come from `in` (row pitch Cpitch), [K1, C) from `in2` (row pitch Cpitch >> pitch2_shift).  1x1 / stride 1 launches of the
+  // non-pipelined kernels (the 128-row tiles and the 256 x 256 two-stage tile share one loader); the pipelined kernel ignores it.
   const void* in2;
   int K1, pitch2_shift;
   int addend_sub;          // 2: addend is the stride-2 SAMPLED tensor [N][ceil(OHf/2)][ceil(OWf/2)][Cout] (a stride-2 1x1 convolution's data gradient,
@@ -77,6 +76,21 @@ struct ConvGemmArgs {
 #endif
   TapClass cls[4];
 };
+
+// ---- the conv-GEMM route ("The conv-GEMM route"): which kernel family takes a forward / data-gradient launch, with which
+// tile (bm computed rows, step valid rows per row block, bn columns), LDS stages, epilogue instantiation and tile order, and how many row and
+// column blocks that makes.  conv_gemm_route() is the one place that decides; the launchers run what it returns.
+enum { CG_TILE128 = 0, CG_BIG256 = 1, CG_PIPE = 2, CG_C64 = 3, CG_STEM7 = 4 };   // 128-row tiles | 256x256 two-stage | pipelined | conv3x3_c64.hip | stem7x7.hip
+struct ConvRoute { int family, bm, step, bn, nst, epi, group_m, total_mblk, nblk_n; };   // CG_C64 / CG_STEM7: total_mblk = statistics rows, the rest unused
+// a: a launch geometry with its operands attached.  Pure: no HIP call, no stream, pointer fields only tested for null; reads
+// MMSKIN_CONV_PIPE_FORCE, MMSKIN_CONV_PIPE_TILE and MMSKIN_GEMM_GROUP_M once.  false + message: no kernel takes the launch.
+bool conv_gemm_route(const ConvGemmArgs& a, int elem_bytes, ConvRoute& r);
+// the launch geometries (pointers and fused operands left null).  Virtual stem: 8 row taps of 32 elements over the NHWC4 image; virtual
+// first conv: 4 taps over NHWC8.  dgrad: see conv_gemm.hip for in_place / fill_zeros / k2 / zero_mask.
+ConvGemmArgs conv_geom_fwd(const ConvShape& s, int elem_bytes);
+ConvGemmArgs conv_geom_dgrad(const ConvShape& s, int elem_bytes, bool in_place, bool fill_zeros, int k2, unsigned* zero_mask);
+ConvGemmArgs conv_geom_stem(int N, int OH, int OW, int Hp, int Wp);
+ConvGemmArgs conv_geom_first(int N, int OH, int OW, int Hp, int Wp, int stride);
 
 // wgrad: dW[cout][tap][c] = sum_m dY[m][cout] * gather(in)[m][tap][c]
 struct WgradArgs {
@@ -158,7 +172,7 @@ template <typename T>
 int launch_conv_fwd(const ConvShape& s, const T* in, const T* w_staged, T* out, float* stat_sum,
                     float* stat_sq, hipStream_t st, const FwdFuse* fuse = nullptr, int* stat_rows_out = nullptr);
 // number of stat partial rows the forward launch produces (rows of stat_sum / stat_sq) when the caller passes no stat_rows_out;
-// with stat_rows_out the launcher may pick a taller tile and reports the (smaller) row count there -- the slabs sized for
+// with stat_rows_out the route may pick a taller tile and the launcher reports the (smaller) row count there -- the slabs sized for
 // conv_fwd_stat_rows() always suffice
 int conv_fwd_stat_rows(const ConvShape& s);
 
@@ -183,6 +197,13 @@ struct DgradFuse {
   bool addend_s2 = false;       // the addend is compact: [N][ceil(H/2)][ceil(W/2)][Cin], added at the even pixels (see ConvGemmArgs::addend_sub)
 };
 int conv_dgrad_partial_rows(const ConvShape& s);
+// Route of one launch kind, as its launcher takes it: CG_C64 / CG_STEM7 where those kernels take the launch, else the geometry with these
+// operands attached (in a) through conv_gemm_route.  rows_free: the forward caller takes the launch's statistics row count.  MMSKIN_OK or MMSKIN_ERR_ARG.
+int conv_route_fwd(const ConvShape& s, int elem_bytes, const void* in, const void* w, void* out, float* stat_sum, float* stat_sq, const FwdFuse* fuse,
+                   bool rows_free, ConvGemmArgs& a, ConvRoute& r);
+int conv_route_dgrad(const ConvShape& s, int elem_bytes, const void* dout, const void* wt, void* din, const void* addend, const DgradFuse* fuse,
+                     ConvGemmArgs& a, unsigned& zero_mask, ConvRoute& r);
+int conv_route_stem(const ConvGemmArgs& a, int elem_bytes, int Hp, int Wp, ConvRoute& r);   // a: conv_geom_stem() with its operands
 
 // din[N][H][W][Cin] = dgrad(dout[N][OH][OW][Cout]); wt_staged is [Cin][kh*kw][Cout].
 // addend (optional, may alias din) is added in the epilogue.  accumulate_only_touched: for classes
@@ -197,7 +218,7 @@ template <typename T>
 int launch_stem_conv_fwd(int N, int OH, int OW, int Hp, int Wp, const T* img4, const T* wv, T* out,
                          float* stat_sum, float* stat_sq, hipStream_t st, int* stat_rows_out = nullptr);
 int stem_conv_stat_rows(int N, int OH, int OW);   // upper bound of the statistics rows a launch writes (allocation); the launch reports its own count
-// direct 7x7 / stride 2 convolution from an LDS-resident input window (stem7x7.hip; bf16, 112-wide output rows): launch_stem_conv_fwd routes to it
+// direct 7x7 / stride 2 convolution from an LDS-resident input window (stem7x7.hip; bf16, 112-wide output rows): conv_route_stem routes to it
 bool stem7x7_takes(int OH, int OW, int Hp, int Wp);
 int stem7x7_stat_rows(int N, int OH);
 int launch_stem7x7_fwd(int N, int OH, int OW, int Hp, int Wp, const bf16_t* img4, const bf16_t* wv, bf16_t* out, float* stat_sum, float* stat_sq,
@@ -216,7 +237,7 @@ int launch_vgg_first_conv_wgrad(int N, int H, int W, int Hp, int Wp, const T* do
                                 float* dwv, hipStream_t st, int stride = 1);
 
 // 3x3 / stride 1 / pad 1, 64 -> 64 channels at 56 x 56 (ResNet-50 layer1 conv2): all nine taps from one staged input window, weights
-// resident in LDS, one workgroup per image (conv3x3_c64.hip).  launch_conv_fwd / launch_conv_dgrad route to it when it takes the shape.
+// resident in LDS, one workgroup per image (conv3x3_c64.hip).  conv_route_fwd / conv_route_dgrad route to it when it takes the shape.
 bool conv3x3_c64_takes(const ConvShape& s, bool bf16);
 int launch_conv3x3_c64_fwd(const ConvShape& s, const bf16_t* in, const bf16_t* w_staged, bf16_t* out, float* stat_sum, float* stat_sq,
                            int stat_stride, hipStream_t st);

@@ -788,32 +788,11 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (EPI == 6 && WAVES_M * WAVE
 }
 
 // ------------------------------------------------------------------------------------------ host
+// geometry (conv_geom_*) -> operands -> route (conv_gemm_route: the ONE place that decides family, tile, stages, epilogue, order) -> launch_route
 #ifdef MMSKIN_ABLATE   // timing-experiment library only
 static unsigned long long* g_conv_stamps = nullptr;
 extern "C" void mmskin_debug_set_conv_stamps(void* device_ptr) { g_conv_stamps = reinterpret_cast<unsigned long long*>(device_ptr); }
 #endif
-template <typename T, int BM, int BN, int WMv, int WNv, int EPI, int NST>
-static int launch_cfg(const ConvGemmArgs& a, hipStream_t st) {
-  constexpr int NT = 64 * WMv * WNv;
-  constexpr int lds = conv_gemm_lds_bytes<BM, BN, T, NST, NT>();
-  auto kern = conv_gemm_kernel<T, BM, BN, WMv, WNv, EPI, NST>;
-  HIP_CHECK_RET(opt_in_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
-  int grid = a.total_mblk * a.nblk_n;
-  if (grid == 0) return MMSKIN_OK;
-  // Linear GEMMs ({M, 1, 1, K, N} shapes) with a weight matrix larger than an XCD's L2: with column blocks fastest every row block
-  // streamed the whole weight through L2 again (BEiT fc1: 1.2 GB of L2 fills per launch for 60 MB of operands,
-  // profiles/r03_step_traffic_beitv2-large-bert-rgatt.txt); groups of 8 row blocks keep their A rows resident instead.
-  static const int gm_env = env_knob("MMSKIN_GEMM_GROUP_M", 8);
-  ConvGemmArgs b = a;
-  b.group_m = 0;
-  if (gm_env > 1 && a.ncls == 1 && a.IH == 1 && a.IW == 1 && a.nblk_n >= 4 && (size_t)a.Cout * a.wrow * sizeof(T) > ((size_t)2 << 20) &&
-      a.total_mblk >= 2 * gm_env)
-    b.group_m = gm_env;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, st, b);
-  HIP_CHECK_RET(hipGetLastError());
-  return MMSKIN_OK;
-}
-
 #define CONV_BM 128
 
 static void finish_classes(ConvGemmArgs& a, int step = CONV_BM) {
@@ -827,252 +806,213 @@ static void finish_classes(ConvGemmArgs& a, int step = CONV_BM) {
   a.bm_step = step;
 }
 
-static int64_t g_pipe_launches = 0;
-extern "C" int64_t mmskin_conv_pipe_launches(void) { return g_pipe_launches; }
-struct PipeChoice { int bm, step; };
-// Selection of the pipelined kernel (NST == 8).  One 512-thread workgroup per CU: it pays where the reduction is deep enough to
-// amortise a ~8 us prologue + epilogue that nothing overlaps (row-weighted K >= PIPE_MIN_K) and the launch has enough tiles to cover
-// most of the chip (>= PIPE_MIN_TILES); measured per ResNet-50 layer in profiles/r03_experiments.txt.  MMSKIN_CONV_PIPE_FORCE=1
-// takes every eligible launch (tests), MMSKIN_CONV_PIPE_TILE = 256 | 224 | 196 pins the tile rows instead of the tile-count model below.
-constexpr int PIPE_MIN_K = 1024;
-constexpr int PIPE_MIN_TILES = 192;
-static bool pipe_choose(const ConvGemmArgs& a, bool tr, int prof, bool heavy, PipeChoice* out) {
-  static const int force = env_knob("MMSKIN_CONV_PIPE_FORCE", 0);
-  static const int pin = env_knob("MMSKIN_CONV_PIPE_TILE", 0);
-  if (!a.pipe_ok || a.in2 || a.addend_sub || prof == 7 || a.ep_mask_out || a.ep_mul || !a.out || a.in_bytes == 0 || a.in_bytes > 0xE0000000ull || (heavy && prof == 1) || a.Cout % 256 != 0 ||
-      a.C % 64 != 0 || a.ncls < 1)
+// ---- the route ("The conv-GEMM route").  Pure host arithmetic: pointer fields are only tested for null.
+// What the fused-operand set asks of the epilogue.  epi is the kernel's EPI: 0 plain store (+ statistics); 2 light (addend, bias, ReLU / GELU,
+// fp32 output, multiplier, mask output); 6 transformer residual; heavy = a fused BatchNorm-backward prologue of the consumer, in the profile
+// that has exactly its operands: 3 = x with scale + shift (+ bias); 4 = x + mask bits; 5 = 4 + x2; 7 = mask bits alone; 1 = everything else.
+struct ConvOperands { bool tr, heavy; int epi; };
+static ConvOperands conv_operands(const ConvGemmArgs& a) {
+  ConvOperands o;
+  o.tr = a.ep_gamma || a.res_f32 || a.ep_drop_p > 0.f;
+  o.heavy = a.ep_mask_y || a.ep_mask_bits || a.ep_x;
+  const bool light = a.addend || a.ep_bias || a.ep_relu || a.out_f32 || a.ep_mul || a.ep_mask_out;
+  int prof = 1;
+  if (o.heavy && !a.ep_mask_y && !a.ep_relu) {
+    if (a.ep_x && !a.addend && !a.ep_mask_bits && !a.ep_x2) prof = 3;
+    else if (!a.ep_bias && a.ep_x && a.ep_mask_bits && !a.ep_scale) prof = a.ep_x2 ? 5 : 4;
+    else if (!a.ep_bias && !a.ep_x && !a.ep_x2 && a.ep_mask_bits && !a.ep_scale) prof = 7;
+  }
+  o.epi = o.tr ? 6 : (o.heavy ? prof : (light ? 2 : 0));
+  return o;
+}
+// One predicate per family: the operands and geometry it accepts (its thresholds are in conv_gemm_route).  The 128-row family accepts every
+// launch that passes the contract checks.
+// Pipelined 224 / 256 x 256 tile (NST 8), bf16: any tap classes with Cout % 256 == 0 and whole 64-element K-tiles per tap, at most 128 of them;
+// a gather source its buffer descriptor can address; a T output; a caller that takes any row-block count; EPI 0, 2, 3, 4, 5, 6 -- no second
+// source, no compact addend, no multiplier, no mask output
+static bool pipe_accepts(const ConvGemmArgs& a, const ConvOperands& o) {
+  if (!a.pipe_ok || !a.out || a.in2 || a.addend_sub || a.ep_mul || a.ep_mask_out || o.epi == 1 || o.epi == 7 || a.in_bytes == 0 || a.in_bytes > 0xE0000000ull ||
+      a.Cout % 256 != 0 || a.C % 64 != 0 || a.ncls < 1)
     return false;
-  if (tr && (heavy || a.addend || a.stat_sum || !a.out_f32)) return false;   // the transformer-residual epilogue's own contract (checked below)
-  double ksum = 0, rsum = 0;
-  for (int i = 0; i < a.ncls; ++i) {
-    const int nk = a.cls[i].ntaps * a.C / 64;
-    if (nk < 1 || nk > KT_LDS_BYTES / 16) return false;
-    ksum += (double)a.cls[i].rows * nk * 64; rsum += a.cls[i].rows;
-  }
-  if (rsum <= 0) return false;
-  // the launch takes ceil(tiles / 256) rounds of a tile whose MFMA time goes with its COMPUTED rows
-  const int cand[3][2] = {{256, 256}, {224, 224}, {224, 196}};
-  double best = 1e30;
-  long best_tiles = 0;
-  for (int c = 0; c < 3; ++c) {
-    if (pin && cand[c][1] != pin) continue;
-    long tiles = 0;
-    for (int i = 0; i < a.ncls; ++i) tiles += (long)ceil_div(a.cls[i].rows, cand[c][1]) * (a.Cout / 256);
-    const double cost = (double)((tiles + 255) / 256) * cand[c][0];
-    if (cost < best) { best = cost; best_tiles = tiles; out->bm = cand[c][0]; out->step = cand[c][1]; }
-  }
-  if (best >= 1e30) return false;
-  // Linear GEMMs ({M, 1, 1, K, N}: no gather, one tap) already pay at K = 768 (BERT-base qkv / fc1 / output.dense: config 5 50.7 -> 50.3 ms);
-  // the ResNet convolutions do not below 1024 (profiles/r04_experiments.txt (0))
-  const double mink = (a.IH == 1 && a.IW == 1 && a.ncls == 1) ? 768 : PIPE_MIN_K;
-  return force || (ksum / rsum >= mink && best_tiles >= PIPE_MIN_TILES);
+  for (int i = 0; i < a.ncls; ++i)
+    if (a.cls[i].ntaps * a.C / 64 < 1 || a.cls[i].ntaps * a.C / 64 > KT_LDS_BYTES / 16) return false;
+  return true;
+}
+// 256 x 256 two-stage tile (NST 2), bf16: plain GEMMs only -- one class of one tap, unit strides, Cout % 256 == 0, a T output, no statistics,
+// EPI 0, 2 (bias, ReLU, fp32 output; no addend, GELU, multiplier or mask output) or 6.  A second source (in2) is accepted: the loader is the 128-row one.
+static bool big256_accepts(const ConvGemmArgs& a, const ConvOperands& o) {
+  return a.out && !a.ep_mask_out && !a.ep_mul && !o.heavy && !a.stat_sum && !a.addend && a.ep_relu != 2 && a.Cout % 256 == 0 && a.ncls == 1 &&
+         a.cls[0].ntaps == 1 && a.Sy == 1 && a.Sx == 1 && a.OS == 1;
 }
 
-template <typename T>
-static int dispatch_conv_gemm(ConvGemmArgs& a, hipStream_t st) {
-  ARG_CHECK(a.Cout % 64 == 0, "conv_gemm: Cout=%d must be a multiple of 64", a.Cout);
-  ARG_CHECK((a.C % DT<T>::EPC) == 0, "conv_gemm: C=%d not a multiple of %d", a.C, DT<T>::EPC);
+#define ROUTE_CHECK(cond, ...) do { if (!(cond)) { mmskin_set_error(__VA_ARGS__); return false; } } while (0)
+bool conv_gemm_route(const ConvGemmArgs& a, int elem_bytes, ConvRoute& r) {
+  // MMSKIN_CONV_PIPE_FORCE=1 sends every launch the pipelined family accepts to it (tests); MMSKIN_CONV_PIPE_TILE = 256 | 224 | 196 pins its
+  // tile rows instead of the tile-count model below
+  static const int force = env_knob("MMSKIN_CONV_PIPE_FORCE", 0);
+  static const int pin = env_knob("MMSKIN_CONV_PIPE_TILE", 0);
+  static const int gm_env = env_knob("MMSKIN_GEMM_GROUP_M", 8);
+  // Pipelined family.  One 512-thread workgroup per CU: it pays where the reduction is deep enough to amortise a ~8 us prologue + epilogue
+  // that nothing overlaps (row-weighted K >= PIPE_MIN_K) and the launch has enough tiles to cover most of the chip (>= PIPE_MIN_TILES);
+  // measured per ResNet-50 layer in profiles/r03_experiments.txt.  Linear GEMMs ({M, 1, 1, K, N}: no gather, one tap) already pay at K = 768
+  // (BERT-base qkv / fc1 / output.dense: config 5 50.7 -> 50.3 ms); the ResNet convolutions do not below 1024 (profiles/r04_experiments.txt (0)).
+  constexpr int PIPE_MIN_K = 1024, PIPE_MIN_K_LINEAR = 768, PIPE_MIN_TILES = 192;
+  // 256 x 256 two-stage family, 8 waves (one workgroup per CU, half the L2 -> LDS bytes per FLOP): a deep reduction whose grid still covers
+  // the chip -- fc2 / output.dense of the transformer encoders (K = 3072 / 4096: 1.03 - 1.05 PFLOP/s against 0.88 - 0.92 on the 128 x 128
+  // tile; at K <= 1024 the per-tile prologue and the 2-wave-per-SIMD epilogue cost more than the fill saves: profiles/r02_experiments.txt (9)).
+  // big_min_tiles >= 224 implies PIPE_MIN_TILES, so the family is reached only where the pipelined one declines: K > 8192 (128 K-tiles),
+  // a source above 0xE0000000 bytes -- or a second source.
+  constexpr int big_min_k = 2048, big_min_tiles = 224;
+  // 128-row family: the single-buffer variant (NST 1, 3-4 workgroups per CU) whenever the launch has enough workgroups to use the extra
+  // residency: measured on the ResNet-50 shape mix (scripts/conv_mix.py) it wins for every layer with more than ~2.5 workgroups per CU and
+  // loses for the 392-workgroup layer-4 launches.  Only the everything-profile (EPI 1) is a 168-VGPR kernel = 3 workgroups/CU = 768
+  // single-buffer slots (a 784-workgroup launch would spill into a second round); the others have the forward kernel's residency.
+  constexpr int nst1_min_blocks = 640, nst1_min_blocks_epi = 800;
+
+  const bool bf16 = elem_bytes == 2;
+  const ConvOperands o = conv_operands(a);
+  // ---- the contract, for every family
+  ROUTE_CHECK(a.Cout % 64 == 0, "conv_gemm: Cout=%d must be a multiple of 64", a.Cout);
+  ROUTE_CHECK(a.C % (16 / elem_bytes) == 0, "conv_gemm: C=%d not a multiple of %d", a.C, 16 / elem_bytes);
   for (int i = 0; i < a.ncls; ++i)
-    ARG_CHECK((a.cls[i].ntaps * a.C) % DT<T>::BK == 0, "conv_gemm: K=%d not a multiple of %d",
-              a.cls[i].ntaps * a.C, DT<T>::BK);
-  a.ablate = 0;
+    ROUTE_CHECK((a.cls[i].ntaps * a.C) % (128 / elem_bytes) == 0, "conv_gemm: K=%d not a multiple of %d", a.cls[i].ntaps * a.C, 128 / elem_bytes);
+  ROUTE_CHECK(!o.tr || (!o.heavy && !a.addend && !a.stat_sum && a.out_f32 && a.Cout % 128 == 0),
+              "conv_gemm: the transformer-residual epilogue needs an fp32 output, Cout %% 128 == 0 and no other fused operand");
+  ROUTE_CHECK(!o.tr || bf16, "conv_gemm: the transformer-residual epilogue is a bf16-operand feature");
+  auto blocks = [&](int step) { int n = 0; for (int i = 0; i < a.ncls; ++i) n += ceil_div(a.cls[i].rows, step); return n; };
+
+  r = ConvRoute{CG_TILE128, CONV_BM, CONV_BM, a.Cout % 128 == 0 ? 128 : 64, 2, o.epi, 0, 0, 0};
+  if (bf16 && pipe_accepts(a, o)) {
+    double ksum = 0, rsum = 0;
+    for (int i = 0; i < a.ncls; ++i) { ksum += (double)a.cls[i].rows * (a.cls[i].ntaps * a.C / 64) * 64; rsum += a.cls[i].rows; }
+    // the launch takes ceil(tiles / 256) rounds of a tile whose MFMA time goes with its COMPUTED rows
+    const int cand[3][2] = {{256, 256}, {224, 224}, {224, 196}};
+    double best = 1e30;
+    long best_tiles = 0;
+    int bm = 0, step = 0;   // computed rows, valid rows
+    for (int c = 0; c < 3; ++c) {
+      if (pin && cand[c][1] != pin) continue;
+      const long tiles = (long)blocks(cand[c][1]) * (a.Cout / 256);
+      const double cost = (double)((tiles + 255) / 256) * cand[c][0];
+      if (cost < best) { best = cost; best_tiles = tiles; bm = cand[c][0]; step = cand[c][1]; }
+    }
+    const double mink = (a.IH == 1 && a.IW == 1 && a.ncls == 1) ? PIPE_MIN_K_LINEAR : PIPE_MIN_K;
+    if (rsum > 0 && bm && (force || (ksum / rsum >= mink && best_tiles >= PIPE_MIN_TILES))) { r.family = CG_PIPE; r.bm = bm; r.step = step; r.bn = 256; r.nst = 8; }
+  }
+  if (r.family == CG_TILE128 && bf16 && big256_accepts(a, o) && a.wrow >= big_min_k && ceil_div(a.cls[0].rows, 256) * (a.Cout / 256) >= big_min_tiles) {
+    r.family = CG_BIG256; r.bm = r.step = r.bn = 256;
+  }
+  r.total_mblk = blocks(r.step);
+  r.nblk_n = a.Cout / r.bn;
+  if (r.family == CG_TILE128) r.nst = r.total_mblk * r.nblk_n > (o.epi == 1 ? nst1_min_blocks_epi : nst1_min_blocks) ? 1 : 2;
+  // Linear GEMMs ({M, 1, 1, K, N} shapes) with a weight matrix larger than an XCD's L2: with column blocks fastest every row block
+  // streamed the whole weight through L2 again (BEiT fc1: 1.2 GB of L2 fills per launch for 60 MB of operands,
+  // profiles/r03_step_traffic_beitv2-large-bert-rgatt.txt); groups of 8 row blocks keep their A rows resident instead.
+  if (gm_env > 1 && a.ncls == 1 && a.IH == 1 && a.IW == 1 && r.nblk_n >= 4 && (size_t)a.Cout * a.wrow * elem_bytes > ((size_t)2 << 20) && r.total_mblk >= 2 * gm_env)
+    r.group_m = gm_env;
+  return true;
+}
+
+// ---- the launcher.  Every instantiation exactly once: X(BM, BN, wave rows, wave columns, EPI, NST)
+#define CG_EPIS_FWD_BWD(X, BN, NST) X(128, BN, 2, 2, 0, NST) X(128, BN, 2, 2, 1, NST) X(128, BN, 2, 2, 2, NST) X(128, BN, 2, 2, 3, NST) \
+                                    X(128, BN, 2, 2, 4, NST) X(128, BN, 2, 2, 5, NST) X(128, BN, 2, 2, 7, NST)
+#define CG_EPIS_PIPE(X, BM) X(BM, 256, 2, 4, 0, 8) X(BM, 256, 2, 4, 2, 8) X(BM, 256, 2, 4, 3, 8) X(BM, 256, 2, 4, 4, 8) X(BM, 256, 2, 4, 5, 8) X(BM, 256, 2, 4, 6, 8)
+#define CONV_GEMM_BOTH_TYPES(X) CG_EPIS_FWD_BWD(X, 64, 1) CG_EPIS_FWD_BWD(X, 64, 2) CG_EPIS_FWD_BWD(X, 128, 1) CG_EPIS_FWD_BWD(X, 128, 2)   /* 128-row: 2 x 28 */
+#define CONV_GEMM_BF16_ONLY(X) X(128, 128, 2, 2, 6, 1) X(128, 128, 2, 2, 6, 2)                        /* 128-row, transformer residual */ \
+                               X(256, 256, 2, 4, 0, 2) X(256, 256, 2, 4, 2, 2) X(256, 256, 2, 4, 6, 2) /* 256 x 256 two-stage */          \
+                               CG_EPIS_PIPE(X, 224) CG_EPIS_PIPE(X, 256)                               /* pipelined */
+#define CG_KEY(bm, bn, epi, nst) ((((bm) * 1024 + (bn)) * 16 + (epi)) * 16 + (nst))
+
+template <typename T, int BM, int BN, int WMv, int WNv, int EPI, int NST>
+static int launch_cfg(const ConvGemmArgs& a, hipStream_t st) {
+  constexpr int NT = 64 * WMv * WNv;
+  constexpr int lds = conv_gemm_lds_bytes<BM, BN, T, NST, NT>();
+  auto kern = conv_gemm_kernel<T, BM, BN, WMv, WNv, EPI, NST>;
+  HIP_CHECK_RET(opt_in_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
+  hipLaunchKernelGGL(kern, dim3(a.total_mblk * a.nblk_n), dim3(NT), lds, st, a);
+  HIP_CHECK_RET(hipGetLastError());
+  return MMSKIN_OK;
+}
+
+static int64_t g_pipe_launches = 0;
+extern "C" int64_t mmskin_conv_pipe_launches(void) { return g_pipe_launches; }
+
+template <typename T>
+static int launch_route(const ConvRoute& r, ConvGemmArgs& a, hipStream_t st) {
+  finish_classes(a, r.step);
+  ARG_CHECK(a.total_mblk == r.total_mblk, "conv_gemm: the route counts %d row blocks, the launch has %d", r.total_mblk, a.total_mblk);
+  a.nblk_n = r.nblk_n; a.group_m = r.group_m; a.ablate = 0;
 #ifdef MMSKIN_ABLATE
   { const char* abl = getenv("MMSKIN_CONV_ABLATE"); a.ablate = abl ? atoi(abl) : 0; }
   a.stamps = g_conv_stamps;
 #endif
-  const bool tr = a.ep_gamma || a.res_f32 || a.ep_drop_p > 0.f;   // transformer-residual epilogue
-  const bool epi = a.addend || a.ep_mask_y || a.ep_mask_bits || a.ep_x || a.ep_bias || a.ep_relu || a.out_f32 || a.ep_mul || a.ep_mask_out || tr;
-  // Single-buffer variant (3-4 workgroups per CU) whenever the launch has enough workgroups to use the
-  // extra residency: measured on the ResNet-50 shape mix (scripts/conv_mix.py) it wins for every layer
-  // with more than ~2.5 workgroups per CU and loses for the 392-workgroup layer-4 launches.
-  constexpr int nst1_min_blocks = 640;
-  constexpr int nst1_min_blocks_epi = 800;   // fused-epilogue launches: 168 VGPRs = 3 workgroups/CU = 768 single-buffer slots; a 784-workgroup launch would spill into a second round
-  const int bn_sel = (a.Cout % 128 == 0) ? 128 : 64;
-  const bool heavy = a.ep_mask_y || a.ep_mask_bits || a.ep_x;   // needs a fused BatchNorm-backward epilogue
-  // 256 x 256 tile, 8 waves (one workgroup per CU, half the L2 -> LDS bytes per FLOP): plain GEMM-like launches (one tap class, no
-  // statistics, light epilogue) with a deep reduction whose grid still covers the chip -- fc2 / output.dense of the transformer
-  // encoders (K = 3072 / 4096: 1.03 - 1.05 PFLOP/s against 0.88 - 0.92 on the 128 x 128 tile; at K <= 1024 the per-tile prologue and
-  // the 2-wave-per-SIMD epilogue cost more than the fill saves: profiles/r02_experiments.txt (9)).
-  constexpr int big_min_k = 2048;
-  int prof = 1;
-  if (heavy && !a.ep_mask_y && !a.ep_relu) {
-    if (a.ep_x && !a.addend && !a.ep_mask_bits && !a.ep_x2) prof = 3;   // (+ optional bias)
-    else if (!a.ep_bias && a.ep_x && a.ep_mask_bits && !a.ep_scale) prof = a.ep_x2 ? 5 : 4;
-    else if (!a.ep_bias && !a.ep_x && !a.ep_x2 && a.ep_mask_bits && !a.ep_scale) prof = 7;
-  }
-  if constexpr (sizeof(T) == 2) {
-    PipeChoice pc;
-    if (pipe_choose(a, tr, prof, heavy, &pc)) {
-      finish_classes(a, pc.step);
-      a.nblk_n = a.Cout / 256;
-      ++g_pipe_launches;
-      const int e = tr ? 6 : (!epi ? 0 : (!heavy ? 2 : prof));
-#define GOP(BMv) (e == 0 ? launch_cfg<T, BMv, 256, 2, 4, 0, 8>(a, st) : e == 2 ? launch_cfg<T, BMv, 256, 2, 4, 2, 8>(a, st) : \
-                  e == 6 ? launch_cfg<T, BMv, 256, 2, 4, 6, 8>(a, st) : \
-                  e == 3 ? launch_cfg<T, BMv, 256, 2, 4, 3, 8>(a, st) : e == 4 ? launch_cfg<T, BMv, 256, 2, 4, 4, 8>(a, st) : launch_cfg<T, BMv, 256, 2, 4, 5, 8>(a, st))
-      return pc.bm == 256 ? GOP(256) : GOP(224);
-#undef GOP
-    }
-  }
-  if constexpr (sizeof(T) == 2) {
-    if (a.out && !a.ep_mask_out && !a.ep_mul && a.wrow >= big_min_k && a.ncls == 1 && !heavy && !a.stat_sum && !a.addend && a.Cout % 256 == 0 && a.ep_relu != 2 &&
-        a.cls[0].mblk_start == 0 && a.cls[0].ntaps == 1 && a.Sy == 1 && a.Sx == 1 && a.OS == 1) {   // plain GEMMs only (what the tests cover)
-      const int mb = ceil_div(a.cls[0].rows, 256), nb = a.Cout / 256;
-      if (mb * nb >= 224) {
-        a.total_mblk = mb; a.nblk_n = nb;
-        return !epi ? launch_cfg<T, 256, 256, 2, 4, 0, 2>(a, st) : (tr ? launch_cfg<T, 256, 256, 2, 4, 6, 2>(a, st) : launch_cfg<T, 256, 256, 2, 4, 2, 2>(a, st));
-      }
-    }
-  }
-  // only the everything-profile is a 168-VGPR kernel (768 single-buffer slots); the others have the forward kernel's residency
-  const bool one = a.total_mblk * (a.Cout / bn_sel) > ((heavy && prof == 1) ? nst1_min_blocks_epi : nst1_min_blocks);
-#define GO(BNv, E) (one ? launch_cfg<T, CONV_BM, BNv, 2, 2, E, 1>(a, st) : launch_cfg<T, CONV_BM, BNv, 2, 2, E, 2>(a, st))
-  if (tr) {
-    ARG_CHECK(!heavy && !a.addend && !a.stat_sum && a.out_f32 && a.Cout % 128 == 0,
-              "conv_gemm: the transformer-residual epilogue needs an fp32 output, Cout %% 128 == 0 and no other fused operand");
-    if constexpr (sizeof(T) == 2) { a.nblk_n = a.Cout / 128; return GO(128, 6); }
-    ARG_CHECK(false, "conv_gemm: the transformer-residual epilogue is a bf16-operand feature");
-  }
-  if (a.Cout % 128 == 0) {
-    a.nblk_n = a.Cout / 128;
-    return !epi ? GO(128, 0) : (!heavy ? GO(128, 2) : (prof == 3 ? GO(128, 3) : (prof == 4 ? GO(128, 4) : (prof == 5 ? GO(128, 5) : (prof == 7 ? GO(128, 7) : GO(128, 1))))));
-  }
-  a.nblk_n = a.Cout / 64;
-  return !epi ? GO(64, 0) : (!heavy ? GO(64, 2) : (prof == 3 ? GO(64, 3) : (prof == 4 ? GO(64, 4) : (prof == 5 ? GO(64, 5) : (prof == 7 ? GO(64, 7) : GO(64, 1))))));
-#undef GO
+  if (r.family == CG_PIPE) ++g_pipe_launches;
+  if (a.total_mblk * a.nblk_n == 0) return MMSKIN_OK;
+#define X(BM, BN, WMv, WNv, EPI, NST) case CG_KEY(BM, BN, EPI, NST): return launch_cfg<T, BM, BN, WMv, WNv, EPI, NST>(a, st);
+  switch (CG_KEY(r.bm, r.bn, r.epi, r.nst)) { CONV_GEMM_BOTH_TYPES(X) default: break; }
+  if constexpr (sizeof(T) == 2) switch (CG_KEY(r.bm, r.bn, r.epi, r.nst)) { CONV_GEMM_BF16_ONLY(X) default: break; }
+#undef X
+  ARG_CHECK(false, "conv_gemm: no %d-byte kernel with a %dx%d tile, epilogue %d and %d stages", (int)sizeof(T), r.bm, r.bn, r.epi, r.nst);
 }
 
-
-int conv_fwd_stat_rows(const ConvShape& s) { return ceil_div(s.N * s.OH() * s.OW(), CONV_BM); }
-int stem_conv_stat_rows(int N, int OH, int OW) { return ceil_div(N * OH * OW, CONV_BM); }
-
-template <typename T>
-int launch_conv_fwd(const ConvShape& s, const T* in, const T* w_staged, T* out, float* stat_sum,
-                    float* stat_sq, hipStream_t st, const FwdFuse* fuse, int* stat_rows_out) {
-  ARG_CHECK(s.kh * s.kw <= MMSKIN_MAX_TAPS, "conv_fwd: %dx%d kernel has too many taps", s.kh, s.kw);
-  if constexpr (sizeof(T) == 2) {
-    if (!fuse && (!stat_sum || stat_rows_out) && conv3x3_c64_takes(s, true)) {
-      if (stat_rows_out) *stat_rows_out = s.N;
-      return launch_conv3x3_c64_fwd(s, in, w_staged, out, stat_sum, stat_sq, s.Cout, st);
-    }
-  }
+// ---- launch geometries (pointers and fused operands left null)
+// one tap class over the whole OH x OW output; the caller fills the class's tap offsets
+static ConvGemmArgs geom_one_class(int N, int IH, int IW, int C, int Cpitch, int Cout, int ntaps, int Sy, int Sx, int OH, int OW) {
   ConvGemmArgs a = {};
-  a.in = in; a.w = w_staged; a.out = out; a.addend = nullptr;
-  if (fuse) {
-    a.ep_bias = fuse->bias; a.addend = fuse->addend; a.ep_relu = fuse->gelu ? 2 : (fuse->relu ? 1 : 0); a.out_f32 = fuse->out_f32;
-    a.ep_gamma = fuse->gamma; a.res_f32 = fuse->res_f32; a.ep_drop_p = fuse->drop_p; a.ep_seed_mix = mix64(fuse->seed); a.ep_offset = fuse->offset;
-    a.ep_mask_out = fuse->mask_out; a.ep_mul = fuse->mul;
-  }
-  a.stat_sum = stat_sum; a.stat_sq = stat_sq; a.stat_stride = s.Cout;
-  a.N = s.N; a.IH = s.H; a.IW = s.W; a.C = s.Cin; a.Cpitch = s.Cin;
-  a.in_bytes = (uint64_t)s.N * s.H * s.W * s.Cin * sizeof(T);
-  a.Cout = s.Cout; a.wrow = s.kh * s.kw * s.Cin;
-  a.Sy = s.stride; a.Sx = s.stride; a.OS = 1;
-  a.OHf = s.OH(); a.OWf = s.OW();
-  a.ncls = 1;
-  TapClass& c = a.cls[0];
-  c.a_dim = s.OH(); c.b_dim = s.OW(); c.ph = 0; c.pw = 0; c.ntaps = s.kh * s.kw;
-  for (int r = 0; r < s.kh; ++r)
-    for (int q = 0; q < s.kw; ++q) {
-      int t = r * s.kw + q;
-      c.offy[t] = (int8_t)(r - s.pad); c.offx[t] = (int8_t)(q - s.pad); c.wtap[t] = (int8_t)t;
-    }
+  a.N = N; a.IH = IH; a.IW = IW; a.C = C; a.Cpitch = Cpitch; a.Cout = Cout; a.wrow = ntaps * C; a.stat_stride = Cout;
+  a.Sy = Sy; a.Sx = Sx; a.OS = 1; a.OHf = OH; a.OWf = OW;
+  a.ncls = 1; a.cls[0].a_dim = OH; a.cls[0].b_dim = OW; a.cls[0].ntaps = ntaps;
   finish_classes(a);
+  return a;
+}
+ConvGemmArgs conv_geom_fwd(const ConvShape& s, int elem_bytes) {
+  ConvGemmArgs a = geom_one_class(s.N, s.H, s.W, s.Cin, s.Cin, s.Cout, s.kh * s.kw, s.stride, s.stride, s.OH(), s.OW());
+  a.in_bytes = (uint64_t)s.N * s.H * s.W * s.Cin * elem_bytes;
+  for (int t = 0; t < s.kh * s.kw; ++t) { a.cls[0].offy[t] = (int8_t)(t / s.kw - s.pad); a.cls[0].offx[t] = (int8_t)(t % s.kw - s.pad); a.cls[0].wtap[t] = (int8_t)t; }
   a.simple_src = (s.kh == 1 && s.kw == 1 && s.stride == 1 && s.pad == 0) ? 1 : 0;
-  a.pipe_ok = (!stat_sum || stat_rows_out) ? 1 : 0;
-  const int rc = dispatch_conv_gemm<T>(a, st);
-  if (stat_rows_out) *stat_rows_out = a.total_mblk;
-  return rc;
+  return a;
 }
-
-int conv_dgrad_partial_rows(const ConvShape& s) {
-  // every parity class rounds its row count up to a whole row block
-  return ceil_div(s.N * s.H * s.W, CONV_BM) + s.stride * s.stride;
+// virtual stem: macro pixel = 2 real pixels x 4 channels = 8 elements; one tap per kernel row r, each reading 32 contiguous elements
+// (8 real pixels x 4 ch) starting at macro pixel wo
+ConvGemmArgs conv_geom_stem(int N, int OH, int OW, int Hp, int Wp) {
+  ConvGemmArgs a = geom_one_class(N, Hp, Wp / 2, 32, 8, 64, 8, 2, 1, OH, OW);
+  for (int r = 0; r < 8; ++r) { a.cls[0].offy[r] = (int8_t)r; a.cls[0].wtap[r] = (int8_t)r; }
+  return a;
 }
-
-// Tap-less parity classes of a strided dgrad (1x1 / stride 2: three of four input pixels receive no gradient) are plain
-// zero fills.  As GEMM workgroups they cost a full prologue + row-index epilogue each (layer2's downsample dgrad: 9 408 of
-// 12 544 workgroups, 104 us of launch overhead with every load, MFMA and store ablated); here 16 B per lane, row-contiguous.
-__global__ __launch_bounds__(256) void parity_zero_fill_kernel(uint4* __restrict__ out, int H, int W, int chunks_per_pixel, int S,
-                                                               unsigned zero_mask) {
-  const int y = blockIdx.y, n = blockIdx.z;
-  const int t = blockIdx.x * 256 + threadIdx.x;          // over W * chunks_per_pixel
-  if (t >= W * chunks_per_pixel) return;
-  const int x = t / chunks_per_pixel;
-  if (!((zero_mask >> ((y % S) * S + (x % S))) & 1u)) return;
-  out[((size_t)(n * H + y) * W) * chunks_per_pixel + t] = make_uint4(0u, 0u, 0u, 0u);
+// virtual first conv: one tap per kernel row plus one all-zero tap, 32 elements each (see launch_vgg_first_conv_fwd in conv.h)
+ConvGemmArgs conv_geom_first(int N, int OH, int OW, int Hp, int Wp, int stride) {
+  ConvGemmArgs a = geom_one_class(N, Hp, Wp, 32, 8, 64, 4, stride, stride, OH, OW);
+  for (int r = 0; r < 4; ++r) { a.cls[0].offy[r] = (int8_t)(r < 3 ? r : 0); a.cls[0].wtap[r] = (int8_t)r; }
+  return a;
 }
-
-template <typename T>
-int launch_conv_dgrad(const ConvShape& s, const T* dout, const T* wt_staged, T* din, const T* addend,
-                      hipStream_t st, DgradFuse* fuse) {
-  ARG_CHECK(s.kh * s.kw <= MMSKIN_MAX_TAPS, "conv_dgrad: too many taps");
-  ARG_CHECK(s.stride == 1 || s.stride == 2, "conv_dgrad: stride %d unsupported", s.stride);
-  if constexpr (sizeof(T) == 2) {
-    const bool prof3 = fuse && fuse->x && fuse->scale && fuse->shift && !fuse->mask_y && !fuse->mask_bits && !fuse->x2 && fuse->x_pitch == 0 && fuse->partial;
-    if (!addend && (!fuse || prof3) && conv3x3_c64_takes(s, true))
-      return launch_conv3x3_c64_dgrad(s, dout, wt_staged, din, fuse, st);
-  }
+// Data gradient: one class per output-pixel parity, each with the taps that land on an integer source pixel.  in_place (the addend is
+// din): tap-less classes are left out; fill_zeros (no addend, no fused epilogue): they go to *zero_mask (bit ph * stride + pw) for
+// parity_zero_fill_kernel instead.  k2 > 0: reduction indices [Cout, Cout + k2) come from a second source with rows of k2 = Cout >> shift.
+ConvGemmArgs conv_geom_dgrad(const ConvShape& s, int elem_bytes, bool in_place, bool fill_zeros, int k2, unsigned* zero_mask) {
   ConvGemmArgs a = {};
-  a.in = dout; a.w = wt_staged; a.out = din; a.addend = addend;
-  if (fuse) {
-    ARG_CHECK(!(addend == din && addend != nullptr && s.stride != 1 && s.kh == 1),
-              "conv_dgrad: epilogue fusion needs a launch that covers every output pixel");
-    a.ep_mask_y = fuse->mask_y; a.ep_mask_bits = fuse->mask_bits; a.ep_x = fuse->x; a.ep_x_pitch = fuse->x_pitch; a.ep_scale = fuse->scale; a.ep_shift = fuse->shift;
-    a.ep_x2 = fuse->x2;
-    if (fuse->addend_s2) {
-      ARG_CHECK(addend && addend != din && s.kh == 1 && s.kw == 1 && s.stride == 1 && s.pad == 0, "conv_dgrad: a compact stride-2 addend needs a 1x1 / stride 1 launch and its own buffer");
-      a.addend_sub = 2;
-    }
-    a.stat_stride = 2 * s.Cin;
-    a.stat_sum = fuse->partial; a.stat_sq = fuse->partial + s.Cin;
-    if (fuse->x2) { a.stat_b_sum = fuse->partial_b; a.stat_b_sq = fuse->partial_b + s.Cin; }
-  }
   a.N = s.N; a.IH = s.OH(); a.IW = s.OW(); a.C = s.Cout; a.Cpitch = s.Cout;
-  a.in_bytes = (uint64_t)s.N * s.OH() * s.OW() * s.Cout * sizeof(T);
+  a.in_bytes = (uint64_t)s.N * s.OH() * s.OW() * s.Cout * elem_bytes;
   a.Cout = s.Cin; a.wrow = s.kh * s.kw * s.Cout;
-  if (fuse && fuse->in2) {
-    int sh = 0;
-    while ((fuse->k2 << sh) < s.Cout) ++sh;
-    ARG_CHECK(s.kh == 1 && s.kw == 1 && s.stride == 1 && s.pad == 0 && fuse->k2 > 0 && (fuse->k2 << sh) == s.Cout && fuse->k2 % DT<T>::BK == 0 &&
-              s.Cout % DT<T>::BK == 0, "conv_dgrad: the second operand needs a 1x1 / stride 1 layer and k2 * 2^j == Cout (k2=%d Cout=%d)", fuse->k2, s.Cout);
-    a.in2 = fuse->in2; a.K1 = s.Cout; a.pitch2_shift = sh;
-    a.C = s.Cout + fuse->k2; a.wrow = a.C;
-  }
-  if (fuse && fuse->bias) a.ep_bias = fuse->bias;
-  a.Sy = 1; a.Sx = 1; a.OS = s.stride;
-  a.OHf = s.H; a.OWf = s.W;
-  a.ncls = 0;
-  unsigned zero_mask = 0;   // parity classes (ph * stride + pw) without taps that only need zeros
+  if (k2 > 0) { a.K1 = s.Cout; a.C = s.Cout + k2; a.wrow = a.C; while ((k2 << a.pitch2_shift) < s.Cout) ++a.pitch2_shift; }
+  a.Sy = 1; a.Sx = 1; a.OS = s.stride; a.OHf = s.H; a.OWf = s.W;
+  *zero_mask = 0;
   for (int ph = 0; ph < s.stride; ++ph)
     for (int pw = 0; pw < s.stride; ++pw) {
       TapClass c = {};
       c.a_dim = (s.H - ph + s.stride - 1) / s.stride;
       c.b_dim = (s.W - pw + s.stride - 1) / s.stride;
       c.ph = ph; c.pw = pw; c.ntaps = 0;
-      for (int r = 0; r < s.kh; ++r) {
-        if ((ph + s.pad - r) % s.stride != 0) continue;
+      for (int r = 0; r < s.kh; ++r)
         for (int q = 0; q < s.kw; ++q) {
-          if ((pw + s.pad - q) % s.stride != 0) continue;
-          int t = c.ntaps++;
-          c.offy[t] = (int8_t)((ph + s.pad - r) / s.stride);
-          c.offx[t] = (int8_t)((pw + s.pad - q) / s.stride);
-          c.wtap[t] = (int8_t)(r * s.kw + q);
+          if ((ph + s.pad - r) % s.stride != 0 || (pw + s.pad - q) % s.stride != 0) continue;
+          const int t = c.ntaps++;
+          c.offy[t] = (int8_t)((ph + s.pad - r) / s.stride); c.offx[t] = (int8_t)((pw + s.pad - q) / s.stride); c.wtap[t] = (int8_t)(r * s.kw + q);
         }
-      }
       if (c.a_dim <= 0 || c.b_dim <= 0) continue;
-      // a tap-less class contributes zeros: skip it when accumulating in place
-      if (c.ntaps == 0 && addend == din && addend != nullptr) continue;
-      if (c.ntaps == 0 && addend == nullptr && !fuse) { zero_mask |= 1u << (ph * s.stride + pw); continue; }   // plain zero fill
+      if (c.ntaps == 0 && in_place) continue;   // a tap-less class contributes zeros: nothing to accumulate
+      if (c.ntaps == 0 && fill_zeros) { *zero_mask |= 1u << (ph * s.stride + pw); continue; }
       a.cls[a.ncls++] = c;
     }
-  if (zero_mask) {
-    const int cpp = s.Cin * (int)sizeof(T) / 16;
-    ARG_CHECK(s.H <= 65535 && s.N <= 65535 && (s.Cin * sizeof(T)) % 16 == 0, "conv_dgrad: zero fill grid");
-    hipLaunchKernelGGL(parity_zero_fill_kernel, dim3(ceil_div(s.W * cpp, 256), s.H, s.N), dim3(256), 0, st,
-                       reinterpret_cast<uint4*>(din), s.H, s.W, cpp, s.stride, zero_mask);
-    HIP_CHECK_RET(hipGetLastError());
-  }
   // Parity classes from the heaviest down (3x3 / stride 2 / pad 1: 4, 2, 2, 1 taps; 1x1 / stride 2: 1, 0, 0, 0): the long-K
   // workgroups start first and the short ones fill the tail of the launch instead of the other way round.
   for (int i = 1; i < a.ncls; ++i)
@@ -1080,59 +1020,119 @@ int launch_conv_dgrad(const ConvShape& s, const T* dout, const T* wt_staged, T* 
   finish_classes(a);
   a.simple_src = (s.kh == 1 && s.kw == 1 && s.stride == 1 && s.pad == 0 && a.ncls == 1) ? 1 : 0;
   a.pipe_ok = 1;
-  const int rc = dispatch_conv_gemm<T>(a, st);
-  if (fuse) fuse->rows_written = a.total_mblk;
-  return rc;
+  return a;
 }
 
-template <typename T>
-int launch_stem_conv_fwd(int N, int OH, int OW, int Hp, int Wp, const T* img4, const T* wv, T* out,
-                         float* stat_sum, float* stat_sq, hipStream_t st, int* stat_rows_out) {
-  if constexpr (sizeof(T) == 2) {
-    if (stem7x7_takes(OH, OW, Hp, Wp)) {   // direct convolution from an LDS-resident window (stem7x7.hip)
-      if (stat_rows_out) *stat_rows_out = stem7x7_stat_rows(N, OH);
-      return launch_stem7x7_fwd(N, OH, OW, Hp, Wp, img4, wv, out, stat_sum, stat_sq, st);
-    }
+// ---- per launch kind: the two kernels outside this file where they take the launch, else geometry + operands -> conv_gemm_route
+static ConvRoute route_outside(int family, int rows) { return ConvRoute{family, 0, 0, 0, 0, 0, 0, rows, 1}; }
+int conv_route_fwd(const ConvShape& s, int elem_bytes, const void* in, const void* w, void* out, float* stat_sum, float* stat_sq, const FwdFuse* fuse,
+                   bool rows_free, ConvGemmArgs& a, ConvRoute& r) {
+  ARG_CHECK(s.kh * s.kw <= MMSKIN_MAX_TAPS, "conv_fwd: %dx%d kernel has too many taps", s.kh, s.kw);
+  const bool any_rows = !stat_sum || rows_free;   // the caller sizes no statistics slab from conv_fwd_stat_rows()
+  if (elem_bytes == 2 && !fuse && any_rows && conv3x3_c64_takes(s, true)) { r = route_outside(CG_C64, s.N); return MMSKIN_OK; }
+  a = conv_geom_fwd(s, elem_bytes);
+  a.in = in; a.w = w; a.out = out; a.stat_sum = stat_sum; a.stat_sq = stat_sq; a.pipe_ok = any_rows ? 1 : 0;
+  if (fuse) {
+    a.ep_bias = fuse->bias; a.addend = fuse->addend; a.ep_relu = fuse->gelu ? 2 : (fuse->relu ? 1 : 0); a.out_f32 = fuse->out_f32;
+    a.ep_gamma = fuse->gamma; a.res_f32 = fuse->res_f32; a.ep_drop_p = fuse->drop_p; a.ep_seed_mix = mix64(fuse->seed); a.ep_offset = fuse->offset;
+    a.ep_mask_out = fuse->mask_out; a.ep_mul = fuse->mul;
   }
-  if (stat_rows_out) *stat_rows_out = stem_conv_stat_rows(N, OH, OW);
-  // virtual conv: macro pixel = 2 real pixels x 4 channels = 8 elements; one tap per kernel row r,
-  // each reading 32 contiguous elements (8 real pixels x 4 ch) starting at macro pixel wo.
-  ConvGemmArgs a = {};
-  a.in = img4; a.w = wv; a.out = out; a.addend = nullptr;
-  a.stat_sum = stat_sum; a.stat_sq = stat_sq; a.stat_stride = 64;
-  a.N = N; a.IH = Hp; a.IW = Wp / 2; a.C = 32; a.Cpitch = 8;
-  a.Cout = 64; a.wrow = 8 * 32;
-  a.Sy = 2; a.Sx = 1; a.OS = 1;
-  a.OHf = OH; a.OWf = OW;
-  a.ncls = 1;
-  TapClass& c = a.cls[0];
-  c.a_dim = OH; c.b_dim = OW; c.ph = 0; c.pw = 0; c.ntaps = 8;
-  for (int r = 0; r < 8; ++r) { c.offy[r] = (int8_t)r; c.offx[r] = 0; c.wtap[r] = (int8_t)r; }
-  finish_classes(a);
-  ARG_CHECK(2 * (OH - 1) + 7 < Hp && (OW - 1) + 3 < Wp / 2, "stem conv: padded image too small");
-  return dispatch_conv_gemm<T>(a, st);
+  return conv_gemm_route(a, elem_bytes, r) ? MMSKIN_OK : MMSKIN_ERR_ARG;
+}
+int conv_route_dgrad(const ConvShape& s, int elem_bytes, const void* dout, const void* wt, void* din, const void* addend, const DgradFuse* fuse,
+                     ConvGemmArgs& a, unsigned& zero_mask, ConvRoute& r) {
+  ARG_CHECK(s.kh * s.kw <= MMSKIN_MAX_TAPS, "conv_dgrad: too many taps");
+  ARG_CHECK(s.stride == 1 || s.stride == 2, "conv_dgrad: stride %d unsupported", s.stride);
+  const bool prof3 = fuse && fuse->x && fuse->scale && fuse->shift && !fuse->mask_y && !fuse->mask_bits && !fuse->x2 && fuse->x_pitch == 0 && fuse->partial;
+  zero_mask = 0;
+  if (elem_bytes == 2 && !addend && (!fuse || prof3) && conv3x3_c64_takes(s, true)) { r = route_outside(CG_C64, s.N); return MMSKIN_OK; }
+  const bool in_place = addend && addend == din, s1x1 = s.kh == 1 && s.kw == 1 && s.stride == 1 && s.pad == 0;
+  if (fuse) {
+    ARG_CHECK(!(in_place && s.stride != 1 && s.kh == 1), "conv_dgrad: epilogue fusion needs a launch that covers every output pixel");
+    ARG_CHECK(!fuse->addend_s2 || (addend && !in_place && s1x1), "conv_dgrad: a compact stride-2 addend needs a 1x1 / stride 1 launch and its own buffer");
+    const int bk = 128 / elem_bytes, k2 = fuse->k2;
+    ARG_CHECK(!fuse->in2 || (s1x1 && k2 > 0 && k2 % bk == 0 && s.Cout % bk == 0 && s.Cout % k2 == 0 && ((s.Cout / k2) & (s.Cout / k2 - 1)) == 0),
+              "conv_dgrad: the second operand needs a 1x1 / stride 1 layer and k2 * 2^j == Cout (k2=%d Cout=%d)", k2, s.Cout);
+  }
+  a = conv_geom_dgrad(s, elem_bytes, in_place, !addend && !fuse, (fuse && fuse->in2) ? fuse->k2 : 0, &zero_mask);
+  a.in = dout; a.w = wt; a.out = din; a.addend = addend;
+  if (fuse) {
+    a.ep_mask_y = fuse->mask_y; a.ep_mask_bits = fuse->mask_bits; a.ep_x = fuse->x; a.ep_x_pitch = fuse->x_pitch; a.ep_scale = fuse->scale; a.ep_shift = fuse->shift;
+    a.ep_x2 = fuse->x2; a.in2 = fuse->in2; a.ep_bias = fuse->bias; a.addend_sub = fuse->addend_s2 ? 2 : 0;
+    a.stat_stride = 2 * s.Cin;
+    a.stat_sum = fuse->partial; a.stat_sq = fuse->partial + s.Cin;
+    if (fuse->x2) { a.stat_b_sum = fuse->partial_b; a.stat_b_sq = fuse->partial_b + s.Cin; }
+  }
+  return conv_gemm_route(a, elem_bytes, r) ? MMSKIN_OK : MMSKIN_ERR_ARG;
+}
+// a: conv_geom_stem() with its operands attached
+int conv_route_stem(const ConvGemmArgs& a, int elem_bytes, int Hp, int Wp, ConvRoute& r) {
+  if (elem_bytes == 2 && stem7x7_takes(a.OHf, a.OWf, Hp, Wp)) { r = route_outside(CG_STEM7, stem7x7_stat_rows(a.N, a.OHf)); return MMSKIN_OK; }
+  ARG_CHECK(2 * (a.OHf - 1) + 7 < Hp && (a.OWf - 1) + 3 < Wp / 2, "stem conv: padded image too small");
+  return conv_gemm_route(a, elem_bytes, r) ? MMSKIN_OK : MMSKIN_ERR_ARG;
+}
+
+// the 128-row upper bounds callers size statistics / partial slabs from: every route writes at most this many rows
+int conv_fwd_stat_rows(const ConvShape& s) { return ceil_div(s.N * s.OH() * s.OW(), CONV_BM); }
+int stem_conv_stat_rows(int N, int OH, int OW) { return ceil_div(N * OH * OW, CONV_BM); }
+int conv_dgrad_partial_rows(const ConvShape& s) { return ceil_div(s.N * s.H * s.W, CONV_BM) + s.stride * s.stride; }   // every parity class rounds up to a whole row block
+
+template <typename T>
+int launch_conv_fwd(const ConvShape& s, const T* in, const T* w_staged, T* out, float* stat_sum, float* stat_sq, hipStream_t st, const FwdFuse* fuse, int* stat_rows_out) {
+  ConvGemmArgs a; ConvRoute r;
+  if (int rc = conv_route_fwd(s, (int)sizeof(T), in, w_staged, out, stat_sum, stat_sq, fuse, stat_rows_out != nullptr, a, r)) return rc;
+  if (stat_rows_out) *stat_rows_out = r.total_mblk;
+  if constexpr (sizeof(T) == 2) if (r.family == CG_C64) return launch_conv3x3_c64_fwd(s, in, w_staged, out, stat_sum, stat_sq, s.Cout, st);
+  return launch_route<T>(r, a, st);
+}
+
+// Tap-less parity classes of a strided dgrad (1x1 / stride 2: three of four input pixels receive no gradient) are plain
+// zero fills.  As GEMM workgroups they cost a full prologue + row-index epilogue each (layer2's downsample dgrad: 9 408 of
+// 12 544 workgroups, 104 us of launch overhead with every load, MFMA and store ablated); here 16 B per lane, row-contiguous.
+__global__ __launch_bounds__(256) void parity_zero_fill_kernel(uint4* __restrict__ out, int H, int W, int chunks_per_pixel, int S, unsigned zero_mask) {
+  const int y = blockIdx.y, n = blockIdx.z, t = blockIdx.x * 256 + threadIdx.x;   // t over W * chunks_per_pixel
+  if (t >= W * chunks_per_pixel) return;
+  const int x = t / chunks_per_pixel;
+  if (!((zero_mask >> ((y % S) * S + (x % S))) & 1u)) return;
+  out[((size_t)(n * H + y) * W) * chunks_per_pixel + t] = make_uint4(0u, 0u, 0u, 0u);
 }
 
 template <typename T>
-int launch_vgg_first_conv_fwd(int N, int H, int W, int Hp, int Wp, const T* img8, const T* wv, T* out,
-                              const FwdFuse* fuse, hipStream_t st, int stride, float* stat_sum, float* stat_sq) {
+int launch_conv_dgrad(const ConvShape& s, const T* dout, const T* wt_staged, T* din, const T* addend, hipStream_t st, DgradFuse* fuse) {
+  ConvGemmArgs a; ConvRoute r; unsigned zero_mask;   // zero_mask: parity classes (ph * stride + pw) without taps that only need zeros
+  if (int rc = conv_route_dgrad(s, (int)sizeof(T), dout, wt_staged, din, addend, fuse, a, zero_mask, r)) return rc;
+  if constexpr (sizeof(T) == 2) if (r.family == CG_C64) return launch_conv3x3_c64_dgrad(s, dout, wt_staged, din, fuse, st);
+  if (zero_mask) {
+    const int cpp = s.Cin * (int)sizeof(T) / 16;
+    ARG_CHECK(s.H <= 65535 && s.N <= 65535 && (s.Cin * sizeof(T)) % 16 == 0, "conv_dgrad: zero fill grid");
+    hipLaunchKernelGGL(parity_zero_fill_kernel, dim3(ceil_div(s.W * cpp, 256), s.H, s.N), dim3(256), 0, st, reinterpret_cast<uint4*>(din), s.H, s.W, cpp, s.stride, zero_mask);
+    HIP_CHECK_RET(hipGetLastError());
+  }
+  if (fuse) fuse->rows_written = r.total_mblk;
+  return launch_route<T>(r, a, st);
+}
+
+template <typename T>
+int launch_stem_conv_fwd(int N, int OH, int OW, int Hp, int Wp, const T* img4, const T* wv, T* out, float* stat_sum, float* stat_sq, hipStream_t st, int* stat_rows_out) {
+  ConvGemmArgs a = conv_geom_stem(N, OH, OW, Hp, Wp);
+  a.in = img4; a.w = wv; a.out = out; a.stat_sum = stat_sum; a.stat_sq = stat_sq;
+  ConvRoute r;
+  if (int rc = conv_route_stem(a, (int)sizeof(T), Hp, Wp, r)) return rc;
+  if (stat_rows_out) *stat_rows_out = r.total_mblk;
+  if constexpr (sizeof(T) == 2) if (r.family == CG_STEM7) return launch_stem7x7_fwd(N, OH, OW, Hp, Wp, img4, wv, out, stat_sum, stat_sq, st);
+  return launch_route<T>(r, a, st);
+}
+
+template <typename T>
+int launch_vgg_first_conv_fwd(int N, int H, int W, int Hp, int Wp, const T* img8, const T* wv, T* out, const FwdFuse* fuse, hipStream_t st, int stride, float* stat_sum, float* stat_sq) {
   // H, W: input image size; output = (H + 2 - 3) / stride + 1
   ARG_CHECK(Hp >= H + 2 && Wp >= W + 4 && (stride == 1 || stride == 2), "first 3x3 conv: padded image too small / stride");
-  const int OH = (H + 2 - 3) / stride + 1, OW = (W + 2 - 3) / stride + 1;
-  ConvGemmArgs a = {};
-  a.in = img8; a.w = wv; a.out = out;
-  a.stat_sum = stat_sum; a.stat_sq = stat_sq; a.stat_stride = 64;
+  ConvGemmArgs a = conv_geom_first(N, (H + 2 - 3) / stride + 1, (W + 2 - 3) / stride + 1, Hp, Wp, stride);
+  a.in = img8; a.w = wv; a.out = out; a.stat_sum = stat_sum; a.stat_sq = stat_sq;
   if (fuse) { a.ep_bias = fuse->bias; a.addend = fuse->addend; a.ep_relu = fuse->relu ? 1 : 0; }
-  a.N = N; a.IH = Hp; a.IW = Wp; a.C = 32; a.Cpitch = 8;
-  a.Cout = 64; a.wrow = 4 * 32;
-  a.Sy = stride; a.Sx = stride; a.OS = 1;
-  a.OHf = OH; a.OWf = OW;
-  a.ncls = 1;
-  TapClass& c = a.cls[0];
-  c.a_dim = OH; c.b_dim = OW; c.ph = 0; c.pw = 0; c.ntaps = 4;
-  for (int r = 0; r < 4; ++r) { c.offy[r] = (int8_t)(r < 3 ? r : 0); c.offx[r] = 0; c.wtap[r] = (int8_t)r; }
-  finish_classes(a);
-  return dispatch_conv_gemm<T>(a, st);
+  ConvRoute r;
+  if (!conv_gemm_route(a, (int)sizeof(T), r)) return MMSKIN_ERR_ARG;
+  return launch_route<T>(r, a, st);
 }
 
 #define INST(T)                                                                                      \

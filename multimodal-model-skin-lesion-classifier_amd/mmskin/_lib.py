@@ -16,6 +16,7 @@ F32, BF16 = 0, 1
 LINEAR_SMALL, LINEAR_BIG_F32, LINEAR_BIG_BF16, LINEAR_PADDED_BF16 = 0, 1, 2, 3   # mmskin_linear_route (MMSKIN_LINEAR_* in mmskin.h)
 WG_STAGED, WG_TAPS3, WG_RING, WG_RING3 = 0, 1, 2, 3   # mmskin_conv_wgrad_plan family (MMSKIN_WG_* in mmskin.h)
 WGR_DIRECT, WGR_LANES = 0, 1                          # ... and reduce
+CG_TILE128, CG_BIG256, CG_PIPE, CG_C64, CG_STEM7 = 0, 1, 2, 3, 4   # mmskin_conv_route family (MMSKIN_CG_* in mmskin.h)
 
 _lib = None
 
@@ -65,6 +66,7 @@ _SIGNATURES = {
     "mmskin_wgrad_ring_launches": (_i64, []),
     "mmskin_conv_wgrad_plan": (_i, [_i] * 10 + [_P]),
     "mmskin_conv_wgrad_slab_check": (_i, [_i] * 10 + [_i64]),
+    "mmskin_conv_route": (_i, [_i] * 12 + [_P]),
     "mmskin_conv3x3_c64_launches": (_i64, []),
     "mmskin_stem7x7_launches": (_i64, []),
     "mmskin_conv2d_dgrad_fused_rows": (_i, [_i] * 9),

@@ -23,6 +23,7 @@ CODE = r'''
 import sys
 sys.path[:0] = [%(tests)r, %(root)r, %(pkg)r]
 import json, os, torch, torch.nn.functional as F
+import conv_route_cases as CR
 from gpu_util import DEV, conv_backward, conv_forward, rel_err
 from mmskin import _lib
 lib = _lib.load()
@@ -50,6 +51,9 @@ for (N, Cin, H, W, Cout, k, s, p, ef, eb) in CASES:
     y_ref = F.conv2d(xr, wr, stride=s, padding=p)
     dy = rb(torch.randn(y_ref.shape, generator=g))
     y_ref.backward(dy.double())
+    for op, taken in ((CR.FWD, ef), (CR.DGRAD, eb)):   # the route the counters below confirm: the pinned tile, or the 128-row family
+        r = CR.route(lib, op, (N, Cin, H, W, Cout, k, s, p), CR.BF16)
+        assert r[:6] == ((CR.CG_PIPE,) + CR.KNOB_TILES[os.environ["MMSKIN_CONV_PIPE_TILE"]][:2] + (256, 8, 0) if taken else (CR.CG_TILE128, 128, 128, 128 if Cin %% 128 == 0 else 64, 2, 0)), (op, r)   # only data gradients (Cin columns) decline
     n0 = lib.mmskin_conv_pipe_launches()
     y = conv_forward(x.to(DEV), w.to(DEV), s, p, "bf16")
     n1 = lib.mmskin_conv_pipe_launches()
@@ -153,6 +157,7 @@ FUSED_CODE = r'''
 import sys, ctypes
 sys.path[:0] = [%(tests)r, %(root)r, %(pkg)r]
 import torch, torch.nn.functional as F
+import conv_route_cases as CR
 from gpu_util import DEV, rel_err, ws
 from mmskin import _lib
 from mmskin._lib import call, ptr, stream
@@ -176,6 +181,8 @@ for (N, Cin, H, W, Cout, k, s, p, c64) in [(3, 64, 56, 56, 64, 3, 1, 1, %(expect
     nw = ctypes.c_int(0)
     wsp = ws(lib.mmskin_conv2d_workspace_bytes(N, Cin, H, W, Cout, k, k, s, p))
     dev = [t.to(DEV) for t in (dy, w, xc, scale, shift)]
+    r = CR.route(lib, CR.DGRAD, (N, Cin, H, W, Cout, k, s, p), CR.BF16, CR.EPI_FLAGS[3])   # profile 3 of the 128-row tile, or its twin
+    assert r[0] == CR.CG_C64 if c64 else r[:6] == (CR.CG_TILE128, 128, 128, 128 if Cin %% 128 == 0 else 64, 2, 3), r
     n0 = lib.mmskin_conv3x3_c64_launches()
     call("mmskin_conv2d_dgrad_fused", *[ptr(t) for t in dev], ptr(dz), ptr(part), ctypes.addressof(nw), N, Cin, H, W, Cout, k, k, s, p, ptr(wsp), stream())
     torch.cuda.synchronize()
@@ -204,3 +211,30 @@ def test_dgrad_with_fused_batchnorm_backward_epilogue(on):
     code = FUSED_CODE % dict(tests=os.path.join(root, "tests"), root=root, pkg=os.path.join(root, "multimodal-model-skin-lesion-classifier_amd"), expect=int(on))
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
+
+
+def test_two_stage_256x256_tile_matches_fp64():
+    """The 256 x 256 two-stage tile (NST 2) is reached only where the pipelined kernel declines a deep plain GEMM; K = 8256 = 129 K-tiles
+    (one past its table) is the smallest such reduction: a 1x1 convolution 8256 -> 1024 over 120 x 120 pixels, 57 x 4 = 228 tiles.  Same
+    bound as the pipelined cases above: bf16-representable inputs, fp64 reference (taken on the device), every element within half a
+    bf16 ulp, relative L2 against the rounded reference < 1e-3."""
+    import torch
+    import conv_route_cases as CR
+    from gpu_util import DEV, conv_forward, rel_err
+    from mmskin import _lib
+    case = (1, 8256, 120, 120, 1024, 1, 1, 0)
+    lib = _lib.load()
+    assert CR.route(lib, CR.FWD, case, CR.BF16) == (CR.CG_BIG256, 256, 256, 256, 2, 0, 0, 57, 4)
+    n0 = lib.mmskin_conv_pipe_launches()
+    g = torch.Generator(device=DEV).manual_seed(31)
+    x = torch.randn(1, 8256, 120, 120, generator=g, device=DEV).bfloat16().float()
+    w = (torch.randn(1024, 8256, 1, 1, generator=g, device=DEV) / 8256 ** 0.5).bfloat16().float()
+    y = conv_forward(x, w, 1, 0, "bf16")
+    assert lib.mmskin_conv_pipe_launches() == n0
+    want = torch.einsum("chw,oc->ohw", x[0].double(), w[:, :, 0, 0].double())[None]
+    got = y.double()
+    wr = want.float().bfloat16().double()
+    l2 = float((got - wr).norm() / wr.norm())
+    print("256x256 two-stage: max err / rms", rel_err(got, want), "rel l2 vs rounded", l2)
+    assert bool(((got - want).abs() <= want.abs() * 2.0 ** -8 + 1e-5 * float(want.pow(2).mean().sqrt())).all())
+    assert l2 < 1e-3, l2

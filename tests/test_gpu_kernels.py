@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_route_cases as CR
 from gpu_util import DEV, DT, conv_backward, conv_forward, rel_err, ws
 from mmskin import _lib, ops
 from mmskin._lib import call, ptr, stream
@@ -47,6 +48,10 @@ def test_conv_forward_backward(case, dtype):
     y_ref = F.conv2d(xr, wr, stride=stride, padding=pad)
     dy = torch.randn(y_ref.shape, generator=g)
     y_ref.backward(dy)
+    # what these cases cover: the two-stage 128-row tile with the plain epilogue, 128 | 64 columns wide (tests/conv_route_cases.py has the rest)
+    eb = CR.BF16 if dtype == "bf16" else CR.F32
+    assert CR.route(_lib.load(), CR.FWD, case, eb)[:6] == (CR.CG_TILE128, 128, 128, 128 if Cout % 128 == 0 else 64, 2, 0)
+    assert CR.route(_lib.load(), CR.DGRAD, case, eb)[:6] == (CR.CG_TILE128, 128, 128, 128 if Cin % 128 == 0 else 64, 2, 0)
     y = conv_forward(x.to(DEV), w.to(DEV), stride, pad, dtype)
     assert rel_err(y, y_ref) < TOL[dtype], ("fwd", rel_err(y, y_ref))
     dx, dw = conv_backward(dy.to(DEV), x.to(DEV), w.to(DEV), stride, pad, dtype)
@@ -86,6 +91,37 @@ def test_conv_bf16_tight_on_representable_inputs(case):
         assert bool(((got - want).abs() <= want.abs() * 2.0 ** -8 + 1e-5 * float(want.pow(2).mean().sqrt())).all()), rec
     assert rec["fwd_l2r"] < 1e-3 and rec["dgrad_l2r"] < 1e-3, rec
     assert rec["wgrad"] < 1e-4, rec
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("hw,nst", [(203, 1), (202, 2)])
+def test_conv_single_buffer_and_two_stage_tiles(hw, nst, dtype):
+    """The 128-row tile on both sides of its 640-workgroup threshold: a 1x1 convolution 64 -> 128 over 2 x 203 x 203 pixels is 644 row blocks
+    (single LDS buffer, NST 1), over 2 x 202 x 202 it is 638 (two stages); the data gradient (64 columns) likewise.  bf16: representable
+    inputs against fp64, every element within half a bf16 ulp and relative L2 < 1e-3 against the rounded reference (the bound of
+    test_conv_bf16_tight_on_representable_inputs); fp32: this file's fp32 bound."""
+    case = (2, 64, hw, hw, 128, 1, 1, 0)
+    lib, eb = _lib.load(), CR.BF16 if dtype == "bf16" else CR.F32
+    assert CR.route(lib, CR.FWD, case, eb)[:6] == (CR.CG_TILE128, 128, 128, 128, nst, 0)
+    assert CR.route(lib, CR.DGRAD, case, eb)[:6] == (CR.CG_TILE128, 128, 128, 64, nst, 0)
+    g = torch.Generator().manual_seed(hw)
+    rb = (lambda t: t.bfloat16().float()) if dtype == "bf16" else (lambda t: t)
+    x, w = rb(torch.randn(2, 64, hw, hw, generator=g)), rb(torch.randn(128, 64, 1, 1, generator=g) / 8)
+    dy = rb(torch.randn(2, 128, hw, hw, generator=g))
+    y_ref = torch.einsum("nchw,oc->nohw", x.double(), w.double()[:, :, 0, 0])
+    dx_ref = torch.einsum("nohw,oc->nchw", dy.double(), w.double()[:, :, 0, 0])
+    y = conv_forward(x.to(DEV), w.to(DEV), 1, 0, dtype)
+    dx, _ = conv_backward(dy.to(DEV), x.to(DEV), w.to(DEV), 1, 0, dtype)
+    for name, got, want in (("fwd", y, y_ref), ("dgrad", dx, dx_ref)):
+        got = got.double().cpu()
+        if dtype == "fp32":
+            assert rel_err(got, want) < TOL["fp32"], (name, rel_err(got, want))
+            continue
+        wr = want.float().bfloat16().double()
+        l2 = float((got - wr).norm() / wr.norm())
+        print(name, "max err / rms", rel_err(got, want), "rel l2 vs rounded", l2)
+        assert bool(((got - want).abs() <= want.abs() * 2.0 ** -8 + 1e-5 * float(want.pow(2).mean().sqrt())).all()), name
+        assert l2 < 1e-3, (name, l2)
 
 
 def test_batchnorm_two_stage_reduction():
@@ -525,7 +561,7 @@ assert errs[0] > 1e-5      # really the bf16 path (outputs rounded to bf16), not
 
 
 def test_linear_bf16_grouped_tile_order():
-    """The grouped tile order of large-weight Linear GEMMs (csrc/conv_gemm.hip launch_cfg: groups of 8 row blocks x all column blocks, on
+    """The grouped tile order of large-weight Linear GEMMs (csrc/conv_gemm.hip conv_gemm_route, group_m: groups of 8 row blocks x all column blocks, on
     for weights above 2 MB with >= 16 row blocks and >= 4 column blocks -- BEiT / BERT fc1, fc2, qkv and their dx GEMMs): M = 19 x 128 rows
     (the last group is ragged: 19 % 8 = 3), K = 1024, N = 2048 in bf16-operand mode, forward and backward, against torch on bf16-rounded
     inputs AND bit-for-bit against the same launches with MMSKIN_GEMM_GROUP_M=0 (the remap only reorders tiles).  Both knobs
@@ -552,6 +588,8 @@ assert all(e < 5e-3 for e in errs), errs
 torch.save([t.detach().cpu() for t in (y, xd.grad, wd.grad, bd.grad)], sys.argv[1])
 '''
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    # the forward launch of the case: 19 row blocks x 16 column blocks of the 128-row tile, grouped by 8 (80 tiles of 256 rows: not pipelined)
+    assert CR.route(_lib.load(), CR.FWD, CR.linear(19 * 128, 1024, 2048), CR.BF16, CR.BIAS | CR.OUT_F32) == (CR.CG_TILE128, 128, 128, 128, 2, 2, 8, 19, 16)
     outs = []
     with tempfile.TemporaryDirectory() as td:
         for gm in ("8", "0"):

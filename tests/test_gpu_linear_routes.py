@@ -29,6 +29,7 @@ import itertools
 import pytest
 import torch
 
+import conv_route_cases as CR
 from gpu_util import DEV, linear_mode, rel_err
 from linear_route_cases import BIG_BF16, BIG_F32, PADDED, ROUTE_CASES, SMALL, case_id, make_inputs, reference
 from mmskin import _lib, ops
@@ -90,6 +91,14 @@ def check(label, got, want, metric, tol):
 def assert_route(M, K, N, route):
     got = _lib.load().mmskin_linear_route(M, K, N)
     assert got == route, f"({M}, {K}, {N}) in {ops.get_linear_dtype()} mode takes route {got}, the case was written for route {route}"
+    if route in (BIG_F32, BIG_BF16):
+        # ... and the conv-GEMM family behind it: these shapes stay on the 128-row tile with the light epilogue (bias; bf16 operands store
+        # fp32), below the pipelined / 256 x 256 thresholds that tests/conv_route_cases.py pins (K < 768 or fewer than 192 tiles of 256
+        # columns); two LDS stages up to 640 workgroups, one above (only 20992 x 512 x 512: 164 x 4 = 656)
+        eb, flags = (CR.F32, CR.BIAS) if route == BIG_F32 else (CR.BF16, CR.BIAS | CR.OUT_F32)
+        bn = 128 if N % 128 == 0 else 64
+        conv = CR.route(_lib.load(), CR.FWD, CR.linear(M, K, N), eb, flags)
+        assert conv[:6] == (CR.CG_TILE128, 128, 128, bn, 1 if -(-M // 128) * (N // bn) > 640 else 2, 2), conv
 
 
 def run_linear(x, w, b, dy, act, grads=(True, True, True)):
