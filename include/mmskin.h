@@ -635,6 +635,30 @@ int mmskin_scorecam_combine(const float* fmap, const float* minmax, const float*
                             int channel_block, float* heat, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Grad-CAM and Grad-CAM++ (interpretability/gradcam_atualizado.py:230-306), forward only, for R rows at once.  acts is the
+ * hooked activation of N images, fp32 [N, C, fh, fw]; row_image is int32 [R] and maps a row to its image.  Its entries are
+ * clamped to [0, N - 1] on the device: a bad entry reads the nearest image, never other memory.
+ *   weights  weights[r, c], [R, C].  The gradient g at the activations is
+ *              dfeat != NULL: g[r, c, i, j] = jac[row_image[r], c, i, j] * dfeat[r, c], jac [N, C, fh, fw], dfeat [R, C]
+ *                             (a target whose tail to the pooled features is diagonal in the channel: jac is
+ *                             d sum(features) / d acts, dfeat is d score / d features of the row)
+ *              dfeat == NULL: g[r] = jac[r], jac [R, C, fh, fw] (any other target: the gradients autograd returned)
+ *            mode 0, Grad-CAM:   w = mean_ij g
+ *            mode 1, Grad-CAM++: alpha = g^2 / (2 g^2 + sum_ij(acts * g^3) + 1e-8), w = sum_ij alpha * relu(g)
+ *            fp32 accumulation in a fixed order, no atomics
+ *   map      raw[r, i, j] = sum_c weights[r, c] * acts[row_image[r], c, i, j], [R, fh, fw], fp32 accumulation in a fixed order
+ *            (results repeat bit for bit); cam[r] = bilinear upsample (align_corners=False, the sampling of Score-CAM above)
+ *            to [H, W] of (relu(raw[r]) - min) / (max - min + 1e-8), min and max over the row's fh x fw map, [R, H, W].
+ *            Normalisation comes before the upsample (the reference's _normalize, then F.interpolate): the opposite order from
+ *            Score-CAM.  A flat map gives zeros, not NaN.
+ * Errors (nothing is launched): an extent < 1, R < 1, H < fh or W < fw, a mode other than 0 or 1; MMSKIN_ERR_UNSUPPORTED for a
+ * feature map of more than 4096 samples per channel (the map kernel's LDS tile). */
+int mmskin_gradcam_weights(const float* acts, const float* jac, const float* dfeat, const int32_t* row_image, int N, int R, int C,
+                           int fh, int fw, int mode, float* weights, void* stream);
+int mmskin_gradcam_map(const float* acts, const float* weights, const int32_t* row_image, int N, int R, int C, int fh, int fw, int H,
+                       int W, float* raw, float* cam, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Metadata-sensitivity sweeps (interpretability/flip_rate.py:164-256, inference_all_folds.py:116-140,
  * analyze_prediction_uncertainty.py:166-272): the image is encoded once, the fusion head runs on V metadata variants of the
  * batch (mmskin.sweep.MetadataSweep); these are the kernels before and after the head.

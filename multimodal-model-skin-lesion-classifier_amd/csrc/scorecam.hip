@@ -23,59 +23,14 @@
 
 #pragma clang fp contract(off)
 
+#include "cam_sample.h"   // axis_tap / make_tap / bilerp / block_minmax, shared with gradcam.hip; compiled here with contraction off
+
 namespace {
 
 constexpr int NT = 256;                   // threads per workgroup
 constexpr int PPT = 4;                    // mask: pixels per thread (one 16-byte store per colour plane)
 constexpr int MASK_G = 8;                 // mask: channels per workgroup (the image tile is read once and reused for them)
 constexpr int LDS_FLOATS = 12 * 1024;     // 48 KiB of dynamic LDS per workgroup, the most any of the kernels asks for
-
-// source taps of one destination index along one axis; every index is clamped to [0, in - 1]
-__device__ __forceinline__ void axis_tap(int d, float scale, int in, int& i0, int& i1, float& l) {
-  float s = ((float)d + 0.5f) * scale - 0.5f;
-  s = s < 0.f ? 0.f : s;
-  i0 = min(max((int)s, 0), in - 1);
-  i1 = min(i0 + 1, in - 1);
-  l = fminf(fmaxf(s - (float)i0, 0.f), 1.f);
-}
-
-// the four LDS offsets and two weights of one output pixel: the same for every channel
-struct Tap {
-  int a00, a01, a10, a11;
-  float lx, ly;
-};
-__device__ __forceinline__ Tap make_tap(int y, int x, int fh, int fw, float scale_h, float scale_w) {
-  int y0, y1, x0, x1;
-  Tap t;
-  axis_tap(y, scale_h, fh, y0, y1, t.ly);
-  axis_tap(x, scale_w, fw, x0, x1, t.lx);
-  t.a00 = y0 * fw + x0; t.a01 = y0 * fw + x1; t.a10 = y1 * fw + x0; t.a11 = y1 * fw + x1;
-  return t;
-}
-__device__ __forceinline__ float bilerp(const float* src, const Tap& t) {
-  const float f00 = src[t.a00], f10 = src[t.a10];
-  const float top = f00 + t.lx * (src[t.a01] - f00);
-  const float bot = f10 + t.lx * (src[t.a11] - f10);
-  return top + t.ly * (bot - top);
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-// min / max over the workgroup; every thread returns with the result.  red: 8 floats of LDS
-__device__ __forceinline__ void block_minmax(float& mn, float& mx, float* red) {
-  mn = wave_min(mn);
-  mx = wave_max(mx);
-  const int wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) { red[wave] = mn; red[4 + wave] = mx; }
-  __syncthreads();
-  mn = red[0]; mx = red[4];
-  for (int w = 1; w < nwave; ++w) { mn = fminf(mn, red[w]); mx = fmaxf(mx, red[4 + w]); }
-}
 
 // One workgroup per channel.  A wave walks rows, its lanes walk columns: no integer division per pixel.
 __global__ __launch_bounds__(NT) void scorecam_minmax_kernel(const float* __restrict__ fmap, int fh, int fw, int H, int W,

@@ -186,6 +186,8 @@ _SIGNATURES = {
     "mmskin_scorecam_minmax": (_i, [_P] + [_i] * 5 + [_P, _P]),
     "mmskin_scorecam_mask": (_i, [_P] * 3 + [_i] * 8 + [_P, _P]),
     "mmskin_scorecam_combine": (_i, [_P] * 3 + [_i] * 6 + [_P, _P]),
+    "mmskin_gradcam_weights": (_i, [_P] * 4 + [_i] * 6 + [_P, _P]),
+    "mmskin_gradcam_map": (_i, [_P] * 3 + [_i] * 7 + [_P] * 3),
     "mmskin_metadata_variants": (_i, [_P, _i, _P, _P, _i, _P, _i, _P, _P, _f, _P, _P, _i, _P, _P, _P, _i, _i, _P]),
     "mmskin_sweep_reduce": (_i, [_P, _i, _P, _P, _i, _i, _i] + [_P] * 7 + [_P]),
     "mmskin_criterion_scratch_floats": (_i64, [_i, _i, _i]),

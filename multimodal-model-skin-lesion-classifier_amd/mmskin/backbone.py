@@ -729,5 +729,16 @@ class HipCustomCNN(nn.Sequential):
 
     def forward(self, x):
         conv = self[0]
+        if len(conv._forward_hooks) > 0:
+            # a class-activation-map consumer hooked the conv: its raw output, the hooks, then the ReLU in torch ops, so that
+            # autograd.grad(score, activations) reaches what the hook saw (without hooks the ReLU stays fused into the conv)
+            y = ops.direct_conv2d(x, conv.weight, conv.bias, 2, 1, False)
+            if not y.requires_grad:
+                y = y.detach().requires_grad_(True)
+            for hook in list(conv._forward_hooks.values()):
+                out = hook(conv, (x,), y)
+                if out is not None:
+                    y = out
+            return self[5](ops.pool_gap(torch.relu(y), 2))
         y = ops.direct_conv2d(x, conv.weight, conv.bias, 2, 1, True)
         return self[5](ops.pool_gap(y, 2))

@@ -7,13 +7,28 @@ stay on the device, and one kernel pair sums, rectifies and normalises the heat 
 copy per explained image.  The normalised upsampled maps are never stored; the kernels recompute them from the feature map.
 
 Eval mode, forward only: nothing here is differentiable.
+
+Grad-CAM and Grad-CAM++ with the reference's classes and call (interpretability/gradcam_atualizado.py:201-306), batched over
+images and metadata variants (`GradCAM`, `GradCAMPlusPlus`).  The reference runs the whole model twice and one backward per
+(image, variant) pair (multiple_sample_using_gradcam_plusplus_atualizado.py:341-399: 30 encoder passes for one image with 15
+variants).  The activations at the target layer do not depend on the metadata, and on the two targets the encoders' plans
+support -- the last conv of a ResNet, `image_encoder.features[-1]` of DenseNet-169 -- the tail from the activations to the
+pooled features is diagonal in the channel.  So `generate_batch` encodes every image ONCE through the hooked eval route, takes
+J = d sum(features) / d activations in one backward, runs the fusion head once on all R = images x variants rows
+(`MultimodalModel.fuse`) and one head backward for d score / d features, and two HIP kernels (mmskin.ops.gradcam_weights,
+gradcam_map) form the gradient J * dfeat in registers, the channel weights, the weighted sum, and the normalised upsampled
+maps.  Any other layer that delivers a 4-D map takes the generic route: the whole model at batch R, autograd's gradient at the
+layer, the same kernels.  Out of scope: second-order differentiation (the reference squares and cubes the first-order gradient
+and never differentiates again), DenseNet's `find_last_conv` target, and the MBConv / VGG plans, whose encoders run no hooks.
 """
 from collections.abc import Mapping
 
 import torch
+import torch.nn as nn
 
 from . import ops
 from ._lib import MMSkinError
+from .backbone import RESNET_DEPTHS, _FlatBackbone
 
 
 def _expand_batch(metadata, n):
@@ -98,3 +113,164 @@ class ScoreCAM:
             self.hook_handle = self.target_layer.register_forward_hook(self.hook_fn)
         self.scores = scores
         return ops.scorecam_combine(fmap, minmax, scores, (H, W)).cpu().numpy()
+
+
+def _check_rows(metadata, rows, who):
+    """metadata of `rows` rows: a tensor (rows, V), or a mapping of such tensors"""
+    if isinstance(metadata, Mapping):
+        for v in metadata.values():
+            _check_rows(v, rows, who)
+    elif torch.is_tensor(metadata) and (metadata.dim() == 0 or metadata.shape[0] != rows):
+        raise ValueError(f"{who}: metadata must have {rows} rows (images x variants_per_image, image-major), got shape "
+                         f"{tuple(metadata.shape)}")
+
+
+class _GradCAMBase:
+    """The reference's BaseCAM (gradcam_atualizado.py:201-224): a forward hook on target_layer keeps the activations."""
+    mode = None
+
+    def __init__(self, model, target_layer):
+        """
+        model: the loaded multimodal model (eval mode).
+        target_layer: the last conv of a ResNet encoder or `image_encoder.features[-1]` of DenseNet-169 (one encoder pass per
+            image), or any ordinary nn.Module layer that returns a 4-D map (the whole model runs on every row).
+        """
+        self.model = model
+        self.target_layer = target_layer
+        self.activations = None
+        self.weights = None          # after generate_batch, device tensors: channel weights [R, C]
+        self.raw = None              # the weighted sums before ReLU and normalisation [R, fh, fw]
+        self.pred = None             # predicted class of every row [R] (argmax of the logits)
+        self.probs = None            # soft-max of the logits [R, K]
+        self._fh = self.target_layer.register_forward_hook(self._forward_hook)
+
+    def _forward_hook(self, module, input, output):
+        self.activations = output
+
+    def clear(self):
+        self.activations = None
+        self.weights = self.raw = self.pred = self.probs = None
+
+    def remove_hook(self):
+        self._fh.remove()
+
+    def _on_plan_route(self):
+        """The one place the route is chosen: True when target_layer is a target the encoder's plan serves through its hooked
+        eval route AND the tail behind it is diagonal in the channel (ResNet: BN(eval) + skip + ReLU + average pool; DenseNet
+        features[-1]: ReLU + average pool), with the model split at encode_image / fuse."""
+        enc = getattr(self.model, "image_encoder", None)
+        if not isinstance(enc, _FlatBackbone) or not hasattr(self.model, "encode_image") or not hasattr(self.model, "fuse"):
+            return False
+        if enc.arch in RESNET_DEPTHS:
+            convs = [m for m in enc.modules() if isinstance(m, nn.Conv2d)]
+            return bool(convs) and self.target_layer is convs[-1]
+        if enc.arch == "densenet169":
+            feats = getattr(enc, "features", None)
+            return isinstance(feats, nn.Sequential) and len(feats) > 0 and self.target_layer is feats[-1]
+        return False
+
+    def _taken_activations(self, rows):
+        acts = self.activations
+        who = type(self).__name__
+        if acts is None:
+            raise MMSkinError(f"{who}: the forward hook on target_layer did not fire")
+        if not torch.is_tensor(acts) or acts.dim() != 4 or acts.shape[0] != rows:
+            raise MMSkinError(f"{who}: target_layer must deliver a ({rows}, C, fh, fw) feature map, got "
+                              f"{tuple(acts.shape) if torch.is_tensor(acts) else type(acts).__name__}")
+        if not acts.requires_grad:
+            raise MMSkinError(f"{who}: the activations of target_layer are not part of the autograd graph")
+        return acts
+
+    def _selected(self, logits, target_class, rows):
+        """(the logit every row is explained by [rows], argmax [rows], soft-max [rows, K]), all on the device"""
+        who = type(self).__name__
+        if logits.dim() != 2 or logits.shape[0] != rows:
+            raise MMSkinError(f"{who}: the model must return logits of shape ({rows}, K), got {tuple(logits.shape)}")
+        K = logits.shape[1]
+        pred = logits.detach().argmax(dim=1)
+        if target_class is None:
+            index = pred
+        elif torch.is_tensor(target_class):
+            if target_class.dim() != 1 or target_class.shape[0] != rows or target_class.is_floating_point():
+                raise ValueError(f"{who}: target_class must be an int, None or an int tensor [{rows}], got "
+                                 f"{target_class.dtype} {tuple(target_class.shape)}")
+            if bool(((target_class < 0) | (target_class >= K)).any()):       # checked where the tensor lives
+                raise ValueError(f"{who}: target_class has entries outside 0 .. {K - 1}")
+            index = target_class.to(logits.device).long()
+        else:
+            if not 0 <= int(target_class) < K:
+                raise ValueError(f"{who}: target_class {target_class} is outside 0 .. {K - 1}")
+            index = torch.full((rows,), int(target_class), device=logits.device, dtype=torch.long)
+        return logits.gather(1, index[:, None])[:, 0], pred, torch.softmax(logits.detach().float(), dim=1)
+
+    def generate_batch(self, images, metadata, target_class=None, variants_per_image=1):
+        """images (N, 3, H, W); metadata of R = N * variants_per_image rows, image-major (rows n * V .. n * V + V - 1 belong to
+        image n): a tensor or a mapping of tensors; target_class an int, an int tensor [R], or None = every row's own predicted
+        class, taken on the device from the same head forward -> device tensor [R, H, W] float32 in [0, 1].
+
+        Every row is normalised on its own, so row r equals the reference's `generate(images[n:n + 1], metadata[r:r + 1], t_r)`
+        run row by row.  Leaves self.weights [R, C], self.raw [R, fh, fw], self.pred [R], self.probs [R, K] and the detached
+        self.activations on the object; nothing is copied to the host."""
+        who = type(self).__name__
+        model = self.model
+        if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != 3 or images.shape[0] < 1:
+            raise ValueError(f"{who}.generate_batch: images must have shape (N, 3, H, W), got "
+                             f"{tuple(images.shape) if torch.is_tensor(images) else type(images).__name__}")
+        V = int(variants_per_image)
+        if V < 1:
+            raise ValueError(f"{who}.generate_batch: variants_per_image must be >= 1, got {variants_per_image}")
+        if model.training:
+            raise MMSkinError(f"{who} runs in eval mode: call model.eval() first")
+        N = images.shape[0]
+        R = N * V
+        _check_rows(metadata, R, f"{who}.generate_batch")
+        device = getattr(model, "device", None) or next(model.parameters()).device
+        images = images.detach().to(device).float().contiguous()
+        H, W = images.shape[2:]
+        self.clear()
+        try:
+            with torch.enable_grad():
+                if self._on_plan_route():
+                    feats = model.encode_image(images)                              # the one encoder pass; the hook delivers A
+                    acts = self._taken_activations(N)
+                    jac, = torch.autograd.grad(feats.sum(), acts)
+                    tiled = feats.detach().repeat_interleave(V, dim=0).requires_grad_(True)
+                    selected, pred, probs = self._selected(model.fuse(tiled, metadata), target_class, R)
+                    dfeat, = torch.autograd.grad(selected.sum(), tiled)
+                    dfeat = dfeat.float().contiguous()
+                    row_image = torch.arange(N, device=device, dtype=torch.int32).repeat_interleave(V)
+                else:
+                    logits = model(images.repeat_interleave(V, dim=0) if V > 1 else images, metadata)
+                    acts = self._taken_activations(R)
+                    selected, pred, probs = self._selected(logits, target_class, R)
+                    jac, = torch.autograd.grad(selected.sum(), acts)
+                    dfeat = None
+                    row_image = torch.arange(R, device=device, dtype=torch.int32)
+        except BaseException:
+            self.clear()             # no half-built graph stays on the object; the hook stays on the layer
+            raise
+        acts = acts.detach().float().contiguous()
+        weights = ops.gradcam_weights(acts, jac.detach().float().contiguous(), dfeat, row_image, self.mode)
+        raw, cam = ops.gradcam_map(acts, weights, row_image, (H, W))
+        self.activations, self.weights, self.raw, self.pred, self.probs = acts, weights, raw, pred, probs
+        return cam
+
+    def generate(self, image, metadata, target_class):
+        """image (1, 3, H, W), metadata of one row, target_class an int -> np.ndarray [H, W] float32 in [0, 1]: the reference's
+        call and result; the R = 1 case of generate_batch."""
+        if not torch.is_tensor(image) or image.dim() != 4 or image.shape[0] != 1 or image.shape[1] != 3:
+            raise ValueError(f"{type(self).__name__}.generate: image must have shape (1, 3, H, W), got "
+                             f"{tuple(image.shape) if torch.is_tensor(image) else type(image).__name__}: the min-max of the "
+                             "reference runs over the whole batch and is only meaningful for one image (generate_batch "
+                             "normalises every row on its own)")
+        return self.generate_batch(image, metadata, target_class)[0].cpu().numpy()
+
+
+class GradCAM(_GradCAMBase):
+    """weights = mean of the gradient over the map (gradcam_atualizado.py:230-257)"""
+    mode = ops.GRADCAM
+
+
+class GradCAMPlusPlus(_GradCAMBase):
+    """weights = sum of alpha * relu(gradient), alpha = g^2 / (2 g^2 + sum(A g^3) + 1e-8) (gradcam_atualizado.py:263-306)"""
+    mode = ops.GRADCAM_PLUSPLUS

@@ -1105,6 +1105,49 @@ def scorecam_combine(fmap, minmax, scores, size, channel_block=0):
     return heat
 
 
+# ---------------------------------------------------------------------------------------------- Grad-CAM / Grad-CAM++ (forward only)
+GRADCAM, GRADCAM_PLUSPLUS = 0, 1          # `mode` of mmskin_gradcam_weights
+
+
+def _gradcam_dims(acts, row_image, what):
+    _need_gpu(acts, what)
+    if acts.dim() != 4 or acts.dtype != torch.float32 or not acts.is_contiguous():
+        raise ValueError(f"{what}: the activations must be a contiguous fp32 [N, C, fh, fw] tensor, got {tuple(acts.shape)} {acts.dtype}")
+    if not torch.is_tensor(row_image) or not row_image.is_cuda or row_image.dim() != 1 or row_image.dtype != torch.int32 \
+            or not row_image.is_contiguous() or row_image.shape[0] < 1:
+        raise ValueError(f"{what}: row_image must be a contiguous int32 [R] device tensor with R >= 1")
+    return tuple(acts.shape) + (row_image.shape[0],)
+
+
+def gradcam_weights(acts, jac, dfeat, row_image, mode):
+    """Channel weights [R, C] of Grad-CAM (mode GRADCAM: mean of the gradient) or Grad-CAM++ (mode GRADCAM_PLUSPLUS) for R rows
+    over the activations acts [N, C, fh, fw] of N images; row_image int32 [R] maps a row to its image (clamped to [0, N - 1] on
+    the device).  With dfeat [R, C] the gradient of row r is jac[row_image[r]] * dfeat[r, :, None, None], jac [N, C, fh, fw];
+    with dfeat None jac is the gradient itself, [R, C, fh, fw]."""
+    N, C, fh, fw, R = _gradcam_dims(acts, row_image, "gradcam_weights")
+    if mode not in (GRADCAM, GRADCAM_PLUSPLUS):
+        raise ValueError(f"gradcam_weights: mode must be GRADCAM (0) or GRADCAM_PLUSPLUS (1), got {mode!r}")
+    _dev_tensor(jac, torch.float32, (N if dfeat is not None else R, C, fh, fw), "gradcam_weights: jac")
+    if dfeat is not None:
+        _dev_tensor(dfeat, torch.float32, (R, C), "gradcam_weights: dfeat")
+    weights = torch.empty((R, C), device=acts.device, dtype=torch.float32)
+    call("mmskin_gradcam_weights", ptr(acts), ptr(jac), ptr(dfeat), ptr(row_image), N, R, C, fh, fw, int(mode), ptr(weights), stream())
+    return weights
+
+
+def gradcam_map(acts, weights, row_image, size):
+    """(raw [R, fh, fw], cam [R, H, W]): raw[r] = sum_c weights[r, c] * acts[row_image[r], c]; cam[r] = relu(raw[r]) min-max
+    normalised over its fh x fw map (+1e-8 in the denominator: a flat map gives zeros), then upsampled bilinearly
+    (align_corners=False) to size = (H, W)."""
+    N, C, fh, fw, R = _gradcam_dims(acts, row_image, "gradcam_map")
+    H, W = int(size[0]), int(size[1])
+    _dev_tensor(weights, torch.float32, (R, C), "gradcam_map: weights")
+    raw = torch.empty((R, fh, fw), device=acts.device, dtype=torch.float32)
+    cam = torch.empty((R, max(H, 0), max(W, 0)), device=acts.device, dtype=torch.float32)
+    call("mmskin_gradcam_map", ptr(acts), ptr(weights), ptr(row_image), N, R, C, fh, fw, H, W, ptr(raw), ptr(cam), stream())
+    return raw, cam
+
+
 # ---------------------------------------------------------------------------------------------- metadata sweeps (forward only)
 META_NONE, META_CAT_SET, META_CAT_TOGGLE, META_NUM_ADD, META_NUM_SET = 0, 1, 2, 3, 4          # MMSKIN_META_* of mmskin.h
 # one record per variant: struct mmskin_meta_variant of include/mmskin.h (32 bytes)
