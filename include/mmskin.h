@@ -56,6 +56,17 @@ int mmskin_backbone_feature_hw(mmskin_backbone_t h, int* out_h, int* out_w);
  * whose named weight has shape [C][1][k][k]. */
 int mmskin_backbone_num_units(mmskin_backbone_t h);
 int mmskin_backbone_unit_info(mmskin_backbone_t h, int index, char* name, int name_cap, int64_t* info12);
+/* What the ResNet plan decided for unit `index` when it was created (no GPU needed): an OR of
+ *   MMSKIN_UNIT_ABN         algebraic BatchNorm backward: no dz and no BatchNorm-backward apply pass for this unit
+ *   MMSKIN_UNIT_FWD2P       two-pass forward: the unit's raw convolution output is never stored
+ *   MMSKIN_UNIT_GRAM        ... and its forward statistics come from the Gram matrix of its input, kept for backward
+ *   MMSKIN_UNIT_DS          the unit is a block's downsample branch
+ *   MMSKIN_UNIT_DS_COMPACT  ... whose data gradient is computed on the pixels the stride-2 convolution read only
+ *   MMSKIN_UNIT_LAST_BLOCK  the unit belongs to the last block (its gradient arrives from the average pool)
+ * Plans of the other architectures: MMSKIN_ERR_UNSUPPORTED. */
+enum { MMSKIN_UNIT_ABN = 1, MMSKIN_UNIT_FWD2P = 2, MMSKIN_UNIT_GRAM = 4, MMSKIN_UNIT_DS = 8, MMSKIN_UNIT_DS_COMPACT = 16,
+       MMSKIN_UNIT_LAST_BLOCK = 32 };
+int mmskin_backbone_unit_flags(mmskin_backbone_t h, int index, int* flags);
 /* Per-kernel-class timing with HIP events recorded on the launch stream (off by default).  Classes:
  * 0 conv fwd (implicit GEMM), 1 conv dgrad, 2 wgrad(+reduce), 3 BN fwd (finalize+apply), 4 BN bwd,
  * 5 weight staging, 6 stem pack/pool.  read() synchronises, returns the totals accumulated since

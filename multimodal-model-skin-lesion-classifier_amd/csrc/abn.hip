@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void abn_prep_kernel(const float* __restrict__
 
 int abn_prep(const float* W, const float* cA, const float* cB, const float* cC, int C4, int Cw, bf16_t* wd, float* bias, float* coef_copy,
              hipStream_t st) {
-  ARG_CHECK((Cw == 64 || Cw == 128 || Cw == 256) && C4 <= 1024 && C4 % (4 * (256 / Cw)) == 0, "abn_prep: C4=%d Cw=%d", C4, Cw);
+  ARG_CHECK(abn_accepts(C4, Cw), "abn_prep: C4=%d Cw=%d", C4, Cw);
   hipLaunchKernelGGL(abn_prep_kernel, dim3(Cw), dim3(256), 0, st, W, cA, cB, cC, C4, Cw, wd, bias, coef_copy);
   HIP_CHECK_RET(hipGetLastError());
   return MMSKIN_OK;
@@ -85,7 +85,7 @@ __global__ void abn_wgrad_finalize_kernel(const float* __restrict__ S, const flo
 
 int abn_wgrad_finalize(const float* S, const float* colsum, const float* W, const float* coef, int C4, int Cw, float* dW, hipStream_t st,
                        const float* gram) {
-  ARG_CHECK(Cw <= 256, "abn_wgrad_finalize: Cw=%d", Cw);
+  ARG_CHECK(abn_accepts(C4, Cw), "abn_wgrad_finalize: C4=%d Cw=%d", C4, Cw);
   hipLaunchKernelGGL(abn_wgrad_finalize_kernel, dim3(C4), dim3(Cw), 0, st, S, gram ? gram : S + (size_t)C4 * Cw, colsum, W, coef, C4, Cw, dW);
   HIP_CHECK_RET(hipGetLastError());
   return MMSKIN_OK;

@@ -7,7 +7,10 @@
 // backward.  Parameters stay fp32 masters in one flat buffer laid out in torchvision's
 // named_parameters() order; they are re-staged to the compute dtype (K-contiguous GEMM operands) at
 // the start of every forward.
+#include <algorithm>
+
 #include "plan.h"
+#include "../../include/mmskin.h"
 
 namespace {
 
@@ -35,11 +38,14 @@ struct Block {
   size_t in_off;   // block input activation (bytes)
   int in_C, in_H, in_W;
   int seg_done = -1;   // gradient segment that is complete once this block's backward has been enqueued
+  bool ds_compact = false;   // stride-2 1x1 downsample in front of a 1x1 / stride 1 conv1: its data gradient is computed on the pixels the
+                             // convolution read only, and conv1's data gradient adds it at the even pixels (knob MMSKIN_DS_COMPACT, default on)
 };
 
-// side-stream slots of backward: 0 / 1 = the alternating dX buffers, 2 = the downsample branch's dX, 3 / 4 = the block-output gradient
-// buffers S[0] / S[1] (algebraic path: the weight-gradient stream reads them itself)
-constexpr int SIDE_SLOTS = 5;
+// Side-stream slots of backward: one per gradient buffer that the main stream writes and a weight-gradient launch on the side stream
+// reads (SideStream::run hands the buffer over, SideStream::acquire comes before the main stream writes it again).  BwdBufs below
+// says which buffer each slot guards.
+enum SideSlot { SLOT_DX0 = 0, SLOT_DX1, SLOT_DS, SLOT_G0, SLOT_G1, SIDE_SLOTS };
 
 struct Plan : PlanBase {
   int arch;
@@ -64,6 +70,7 @@ struct Plan : PlanBase {
   int last_conv_grad(const float* dfeat, const unsigned char* ws, float* dx_nchw, hipStream_t st) override;
   int num_units() const override { return (int)units.size(); }
   int unit_info(int index, std::string* name, int64_t* info12) const override;
+  int unit_flags(int index, int* flags) const override;
 };
 
 int add_unit(Plan& p, const std::string& conv_name, const std::string& bn_name, ConvShape s) {
@@ -109,6 +116,9 @@ int build_plan(Plan& p) {
       }
       if (stride != 1 || cin != cout)
         blk.ds = add_unit(p, base + ".downsample.0", base + ".downsample.1", {p.N, h, w, cin, cout, 1, 1, stride, 0});
+      static const bool ds_compact_on = env_knob("MMSKIN_DS_COMPACT", 1) != 0;
+      const ConvShape& c1 = p.units[blk.units[0]].s;   // conv1's data gradient adds the compact gradient in its fused epilogue; the first block has none
+      blk.ds_compact = ds_compact_on && blk.ds >= 0 && !p.blocks.empty() && stride == 2 && c1.kh == 1 && c1.stride == 1;
       if (b == 0 && li > 0) {   // layerN's parameters start here: everything from this offset on completes first in backward
         blk.seg_done = 3 - li;
         seg_starts.push_back(p.units[blk.units[0]].w_off);
@@ -213,9 +223,7 @@ int build_plan(Plan& p) {
     for (int ui : cand) {
       Unit& u = p.units[ui];
       WgradRingPlan rp;
-      int sh = 0;
-      while ((u.s.Cin << sh) < u.s.Cout) ++sh;
-      if (p.dtype != 1 || !bottleneck || u.s.kh != 1 || u.s.stride != 1 || u.s.Cin > abn_maxc || u.s.Cin % 64 || (u.s.Cin << sh) != u.s.Cout ||
+      if (p.dtype != 1 || !bottleneck || u.s.kh != 1 || u.s.stride != 1 || u.s.Cin > abn_maxc || !abn_accepts(u.s.Cout, u.s.Cin) ||
           !wgrad_gram_plan((int)u.rows(), u.s.Cout, u.s.Cin, rp) || rp.gram_tiles != 1)
         continue;
       u.abn = true;
@@ -237,7 +245,9 @@ int build_plan(Plan& p) {
       size_t slab2 = 0;
       for (Block& b : p.blocks) {
         Unit& u = p.units[b.units.back()];
-        if (!u.abn || b.ds >= 0) continue;
+        // never in the last block: its gradient arrives from the average pool with no sums, so its BatchNorm backward runs from dy
+        // and reads the raw output a two-pass unit does not store (today no unit there is algebraic either: 512 input channels)
+        if (!u.abn || b.ds >= 0 || &b == &p.blocks.back()) continue;
         u.fwd2p = true;
         size_t sb = wgrad_gram_slab_bytes((int)u.rows(), u.s.Cout, u.s.Cin);
         if (sb > slab2) slab2 = sb;
@@ -274,6 +284,38 @@ int build_plan(Plan& p) {
   return MMSKIN_OK;
 }
 
+// Backward's gradient buffers by role.  Each is one of the plan's seven scratch regions of maxact_bytes (the largest activation).
+//   role      region  slot        written by the main stream                          read by
+//   G[0 / 1]  0 / 1   SLOT_G0/1   pool backward; conv1's data gradient (a block reads  main: the block below; side: the algebraic weight
+//                                 one and writes the other)                            gradient of its conv3 / downsample (g itself)
+//   dX[0 / 1] 2 / 6   SLOT_DX0/1  a unit's BatchNorm backward, alternating per unit    main: its data gradient; side: its weight gradient
+//   dXd       5       SLOT_DS     the downsample branch's BatchNorm backward           main / side: the branch's two gradients
+//   dY        3       -           data gradient of units 1.. (masked, sums taken)      main: BatchNorm backward of the unit below
+//   dZ        4       -           BatchNorm backward from dy (last block)              main: conv1's data gradient (residual addend)
+// Region 3 has three roles and no slot.  Inside the block loop only the main stream touches it, and each role is consumed before
+// the next is written: dY goes from unit i's data gradient to unit i-1's BatchNorm backward; ds_addend (the compact stride-2
+// downsample gradient) is written after the block's last dY was consumed and read by conv1's data gradient right behind it;
+// stem_dx0 is written after the last block, and the stem's weight gradient that reads it is handed over and joined through
+// SLOT_DX0 (the dX pair is idle by then) before backward returns.
+template <typename T>
+struct SlotBuf {
+  T* p;
+  int slot;
+};
+template <typename T>
+struct BwdBufs {
+  SlotBuf<T> G[2], dX[2], dXd;
+  T *dY, *dZ, *ds_addend, *stem_dx0;
+  BwdBufs(const Plan& p, unsigned char* ws) {
+    auto region = [&](int i) { return reinterpret_cast<T*>(ws + p.off_scratch[i]); };
+    G[0] = {region(0), SLOT_G0}; G[1] = {region(1), SLOT_G1};
+    dX[0] = {region(2), SLOT_DX0}; dX[1] = {region(6), SLOT_DX1};
+    dXd = {region(5), SLOT_DS};
+    dY = ds_addend = stem_dx0 = region(3);
+    dZ = region(4);
+  }
+};
+
 template <typename T>
 StemBufs<T> stem_bufs(const Plan& p, unsigned char* ws) {
   const Unit& u0 = p.units[0];
@@ -289,7 +331,7 @@ StemBufs<T> stem_bufs(const Plan& p, unsigned char* ws) {
   b.red = bn_reduce_scratch(ws + p.off_red, p.red_C);
   b.coefbwd = reinterpret_cast<float*>(ws + p.off_coefbwd);
   b.partial = reinterpret_cast<float*>(ws + p.off_partial);
-  b.dx0 = reinterpret_cast<T*>(ws + p.off_scratch[3]);
+  b.dx0 = BwdBufs<T>(p, ws).stem_dx0;
   b.slab = wgrad_slab_at(ws, p.off_slab, p.slab_bytes);
   b.dwv = reinterpret_cast<float*>(ws + p.off_dwv);
   return b;
@@ -303,9 +345,8 @@ int forward_eval(Plan& p, const void* image, const float* norm6, const float* pa
                  float* features, hipStream_t st, bool reuse_table) {
   const float eps = 1e-5f;
   T* wf = reinterpret_cast<T*>(ws + p.off_wf);
-  int rc, maxC = 64;
-  for (const Unit& u : p.units) maxC = u.s.Cout > maxC ? u.s.Cout : maxC;
-  if (!reuse_table) PROF(K_BN_FWD, 0.0, 0.0, bn_eval_table(p.table_dev, (int)p.units.size(), maxC, params, buffers, ws, eps, st));
+  int rc;
+  if (!reuse_table) PROF(K_BN_FWD, 0.0, 0.0, bn_eval_table(p.table_dev, (int)p.units.size(), p.red_C, params, buffers, ws, eps, st));
   auto shift_of = [&](const Unit& u) { return BnCoef(reinterpret_cast<float*>(ws + u.coef_off), u.s.Cout).shift; };
   // stem: the 7x7 conv keeps its own BN + ReLU + max-pool kernel; its coefficients are in the table above
   if ((rc = stem_forward<T>(stem_bufs<T>(p, ws), p.sg, image, norm6, StemBn(), &p.prof, st))) return rc;
@@ -332,6 +373,14 @@ int forward_eval(Plan& p, const void* image, const float* norm6, const float* pa
   }
   Unit& last = p.units[p.blocks.back().units.back()];
   return avgpool_fwd<T>(reinterpret_cast<const T*>(ws + last.y_off), p.N, last.s.OH() * last.s.OW(), last.s.Cout, features, st);
+}
+
+// g^T in, in^T in and colsum(in) of a 1x1 / stride 1 unit (launch_wgrad_gram; mode as there).  This is the one launch of the algebraic
+// path that exists for bf16 only, and build_plan sets Unit::abn / fwd2p / gram_off on bf16 plans only: the one place that says so.
+template <typename T>
+int wgrad_gram(const ConvShape& s, const T* g, const T* in, float* slab, float* s_out, float* colsum_out, hipStream_t st, int mode = 0) {
+  if constexpr (sizeof(T) == 2) return launch_wgrad_gram(s.N, s.OH(), s.OW(), s.Cin, s.Cout, g, in, slab, s_out, colsum_out, st, mode);
+  else return MMSKIN_ERR_UNSUPPORTED;
 }
 
 template <typename T>
@@ -397,41 +446,38 @@ int forward_impl(Plan& p, const void* image, const float* norm6, const float* pa
       // the downsample conv + its BN statistics only meet the main branch at the block's final BN-apply:
       // they run on the side stream (own stat slab / reduction scratch) beside conv1..conv3
       Unit& d = p.units[b.ds];
+      const hipStream_t dst = use_side ? p.side.s : st;   // (the profiled path has no side stream: main stream, main scratch)
+      float* dsum = use_side ? stat_b_sum : stat_sum;
+      float* dsq = use_side ? stat_b_sq : stat_sq;
       if (use_side) {
         HIP_CHECK_RET(hipEventRecord(p.side.f_ready, st));
-        HIP_CHECK_RET(hipStreamWaitEvent(p.side.s, p.side.f_ready, 0));
-        int nrows_d = 0;
-        if ((rc = launch_conv_fwd<T>(d.s, in, wf + d.wf_off, reinterpret_cast<T*>(ws + d.x_off),
-                                     training ? stat_b_sum : nullptr, training ? stat_b_sq : nullptr, p.side.s, nullptr, &nrows_d))) return rc;
-        if ((rc = bn_coeffs_on(d, nrows_d, stat_b_sum, stat_b_sq,
-                               bn_reduce_scratch(ws + p.off_red_b, p.red_C), p.side.s))) return rc;
-        HIP_CHECK_RET(hipEventRecord(p.side.f_done, p.side.s));
-      } else {
-        int nrows_d = 0;
-        PROF(K_CONV_FWD, conv_flops(d.s), conv_bytes(d.s, sizeof(T)),
-             launch_conv_fwd<T>(d.s, in, wf + d.wf_off, reinterpret_cast<T*>(ws + d.x_off),
-                                training ? stat_sum : nullptr, training ? stat_sq : nullptr, st, nullptr, &nrows_d));
-        if ((rc = bn_coeffs(d, nrows_d))) return rc;
+        HIP_CHECK_RET(hipStreamWaitEvent(dst, p.side.f_ready, 0));
       }
+      int nrows_d = 0;
+      {
+        ProfScope scope(&p.prof, K_CONV_FWD, dst, conv_flops(d.s), conv_bytes(d.s, sizeof(T)));
+        if ((rc = launch_conv_fwd<T>(d.s, in, wf + d.wf_off, reinterpret_cast<T*>(ws + d.x_off), training ? dsum : nullptr,
+                                     training ? dsq : nullptr, dst, nullptr, &nrows_d))) return rc;
+      }
+      if ((rc = bn_coeffs_on(d, nrows_d, dsum, dsq, bn_reduce_scratch(ws + (use_side ? p.off_red_b : p.off_red), p.red_C), dst))) return rc;
+      if (use_side) HIP_CHECK_RET(hipEventRecord(p.side.f_done, dst));
     }
     for (int i = 0; i < nu; ++i) {
       Unit& u = p.units[b.units[i]];
       T* x = reinterpret_cast<T*>(ws + u.x_off);
       T* y = reinterpret_cast<T*>(ws + u.y_off);
       int nrows_u = 0;   // statistics row blocks this launch wrote (the launcher picks the tile height)
-      const bool two_pass = training && u.fwd2p && i + 1 == nu && sizeof(T) == 2;
+      const bool two_pass = training && u.fwd2p;   // (a block's final unit)
       const bool gram_pass = two_pass && u.gram_off != 0;
       if (gram_pass) {
-        if constexpr (sizeof(T) == 2) {
-          float* gm = reinterpret_cast<float*>(ws + u.gram_off);
-          float* gcs = gm + (size_t)128 * u.s.Cin;
-          PROF(K_BN_FWD, 0.0, (double)u.rows() * u.s.Cin * sizeof(T),
-               launch_wgrad_gram(u.s.N, u.s.OH(), u.s.OW(), u.s.Cin, u.s.Cout, nullptr, cur, reinterpret_cast<float*>(ws + p.off_abn_slab2), gm, gcs, st, 2));
-          const BnCoef kq(reinterpret_cast<float*>(ws + u.coef_off), u.s.Cout);
-          PROF(K_BN_FWD, 0.0, 0.0, gram_stats_finalize(gm, gcs, params + u.w_off, u.s.Cout, u.s.Cin, (double)u.rows(), params + u.g_off, params + u.b_off, eps, mom,
-                                                       buffers + u.rm_off, buffers + u.rv_off, kq.scale, kq.shift, kq.mean, kq.invstd, st));
-          nrows_u = -1;   // coefficients done
-        }
+        float* gm = reinterpret_cast<float*>(ws + u.gram_off);
+        float* gcs = gm + (size_t)128 * u.s.Cin;
+        PROF(K_BN_FWD, 0.0, (double)u.rows() * u.s.Cin * sizeof(T),
+             wgrad_gram<T>(u.s, nullptr, cur, reinterpret_cast<float*>(ws + p.off_abn_slab2), gm, gcs, st, 2));
+        const BnCoef kq(reinterpret_cast<float*>(ws + u.coef_off), u.s.Cout);
+        PROF(K_BN_FWD, 0.0, 0.0, gram_stats_finalize(gm, gcs, params + u.w_off, u.s.Cout, u.s.Cin, (double)u.rows(), params + u.g_off, params + u.b_off, eps, mom,
+                                                     buffers + u.rm_off, buffers + u.rv_off, kq.scale, kq.shift, kq.mean, kq.invstd, st));
+        nrows_u = -1;   // coefficients done
       } else {
         PROF(K_CONV_FWD, conv_flops(u.s), conv_bytes(u.s, sizeof(T)),
              launch_conv_fwd<T>(u.s, cur, wf + u.wf_off, two_pass ? (T*)nullptr : x, training ? stat_sum : nullptr,
@@ -468,220 +514,250 @@ int forward_impl(Plan& p, const void* image, const float* norm6, const float* pa
                         features, st);
 }
 
+// ------------------------------------------------------------------------------------------ backward
+// The gradient of a block's output, as the step that finished the block above hands it to the block below.
+//   masked_with_sums: dz is already multiplied by the block's ReLU mask (Block::mask_off bits), and conv1's data gradient of the block
+//   above, which wrote it, left the BatchNorm-backward partial sums of the block's final unit in `partial` (sum dz, sum dz * x against
+//   that unit's raw output x; a two-pass unit has no x and takes the second sum from its weight-gradient GEMM instead) and of its
+//   downsample branch in `partial_b` (against the branch's raw output), sum_rows rows each.
+//   Otherwise dz is the plain gradient dy: the last block's, which arrives from the average pool.
 template <typename T>
-int backward_impl(Plan& p, const float* dfeat, const float* params, unsigned char* ws, float* grads,
-                  hipStream_t st) {
-  T* wd = reinterpret_cast<T*>(ws + p.off_wd);
-  const WgradSlab slab = wgrad_slab_at(ws, p.off_slab, p.slab_bytes);
-  float* partial = reinterpret_cast<float*>(ws + p.off_partial);
-  float* cA = reinterpret_cast<float*>(ws + p.off_coefbwd);
-  T* S[7];
-  for (int i = 0; i < 7; ++i) S[i] = reinterpret_cast<T*>(ws + p.off_scratch[i]);
-  int rc;
+struct BlockGrad {
+  SlotBuf<T> dz;
+  bool masked_with_sums;
+  int sum_rows;
+};
 
-  const ColScratch red = bn_reduce_scratch(ws + p.off_red, p.red_C);
-  const auto coef_of = [&](const Unit& u) { return BnCoef(reinterpret_cast<float*>(ws + u.coef_off), u.s.Cout); };
-  // BN backward of unit u given dy: fills dx (and optionally dz)
-  auto bn_bwd = [&](Unit& u, const T* dy, const T* ymask, int mode, T* dx, T* dz) -> int {
-    return bn_backward<T>(dy, reinterpret_cast<const T*>(ws + u.x_off), ymask, mode, u.rows(), u.s.Cout, coef_of(u), params + u.g_off,
-                          grads + u.g_off, grads + u.b_off, BnBwdCoef(cA, u.s.Cout), partial, red, dx, dz, &p.prof,
-                          (mode == MASK_FROM_Y ? 7.0 : 5.0) * u.rows() * u.s.Cout * sizeof(T), st);
-  };
+// The folded data-gradient weights [cA (.) W ; Q] and bias r that abn_prep writes and the algebraic data gradient reads: one set for a
+// block's conv3, one for a stride-1 downsample convolution (both are live between the block's tail and its block-input step).
+enum AbnSet { ABN_CONV3, ABN_DS };
 
-  float* partial_b = reinterpret_cast<float*>(ws + p.off_partial_b);
-  // BN backward of unit u when `dz` is ALREADY masked and its partial sums (sum dz, sum dz*x) were
-  // produced by the epilogue of the dgrad launch that wrote dz: finalize + one apply pass.
-  // dx == nullptr: finalize only (gamma / beta gradients and the coefficients cA, cB, cC) -- the algebraic path folds the apply
-  // into its two GEMMs
-  auto bn_bwd_fused = [&](Unit& u, const T* dz, const float* part, int nrows, T* dx, const float* sum_dz_x = nullptr) -> int {
-    return bn_backward_from_sums<T>(dz, reinterpret_cast<const T*>(ws + u.x_off), part, nrows, u.rows(), u.s.Cout, coef_of(u), params + u.g_off,
-                                    grads + u.g_off, grads + u.b_off, BnBwdCoef(cA, u.s.Cout), red, dx, &p.prof,
-                                    dx ? 3.0 * u.rows() * u.s.Cout * sizeof(T) : 0.0, st, -1, false, sum_dz_x);
-  };
+template <typename T>
+struct ResNetBackward {
+  Plan& p;
+  const float* params;
+  unsigned char* ws;
+  float* grads;
+  hipStream_t st;
+  const bool use_side;   // weight gradients on the side stream (off on the profiled path)
+  const BwdBufs<T> B;
+  const WgradSlab slab;
+  const ColScratch red;
+  int dxi = 0;           // which of B.dX holds the current dX
 
-  Unit& last = p.units[p.blocks.back().units.back()];
-  T* g = S[0];
-  T* gin = S[1];
-  if ((rc = avgpool_bwd<T>(dfeat, p.N, last.s.OH() * last.s.OW(), last.s.Cout, g, st))) return rc;
+  ResNetBackward(Plan& plan, const float* params_, unsigned char* ws_, float* grads_, hipStream_t st_)
+      : p(plan), params(params_), ws(ws_), grads(grads_), st(st_), use_side(!plan.prof.on), B(plan, ws_),
+        slab(wgrad_slab_at(ws_, plan.off_slab, plan.slab_bytes)), red(bn_reduce_scratch(ws_ + plan.off_red, plan.red_C)) {}
 
-  // ---- side stream for the weight-gradient GEMMs
-  const bool use_side = !p.prof.on;
-  if (use_side && (rc = p.side.init(SIDE_SLOTS))) return rc;
-  p.side.begin_backward();
-  T* DX[3] = {S[2], S[6], S[5]};
-  auto acquire = [&](int i) { return p.side.acquire(i, st, use_side); };
-  auto wgrad_async = [&](Unit& u, int i, const T* uin) -> int {
-    return p.side.run(i, st, use_side, [&](hipStream_t wst) {
-      ProfScope scope(&p.prof, K_WGRAD, wst, conv_flops(u.s), conv_bytes(u.s, sizeof(T)));
-      return launch_conv_wgrad<T>(u.s, DX[i], uin, slab, grads + u.w_off, wst);
-    });
-  };
-  int dxi = 0;   // index of the buffer holding the current dX
-  // algebraic path: the main stream may write S[0] / S[1] again (two blocks later) only after the launch reading it has finished
-  auto g_slot = [&](const T* buf) { return buf == S[0] ? 3 : 4; };
-  auto g_acquire = [&](const T* buf) { return acquire(g_slot(buf)); };
-  // dW = cA (.) (g^T y) + cB (.) (W (y^T y)) + cC (x) colsum(y) on the weight-gradient stream
-  auto wgrad_abn_async = [&](Unit& u, const T* gbuf, const T* uin) -> int {
-    if constexpr (sizeof(T) == 2) {
-      return p.side.run(g_slot(gbuf), st, use_side, [&](hipStream_t wst) {
-        float* S_out = reinterpret_cast<float*>(ws + p.off_abn_S);
-        float* cs_out = reinterpret_cast<float*>(ws + p.off_abn_cs);
-        ProfScope scope(&p.prof, K_WGRAD, wst, conv_flops(u.s), conv_bytes(u.s, sizeof(T)));
-        if (int r = launch_wgrad_gram(u.s.N, u.s.OH(), u.s.OW(), u.s.Cin, u.s.Cout, gbuf, uin, slab.p, S_out, cs_out, wst)) return r;
-        return abn_wgrad_finalize(S_out, cs_out, params + u.w_off, reinterpret_cast<const float*>(ws + u.abn_coef_off), u.s.Cout, u.s.Cin,
-                                  grads + u.w_off, wst);
-      });
-    } else {
-      return MMSKIN_ERR_UNSUPPORTED;
-    }
-  };
-
-  bool fused_ready = false;   // g already holds the masked dz of this block's final unit, partials in the slabs
-  int fused_rows = 0;
-  for (int bi = (int)p.blocks.size() - 1; bi >= 0; --bi) {
-    Block& b = p.blocks[bi];
-    const int nu = (int)b.units.size();
-    const T* in = reinterpret_cast<const T*>(ws + b.in_off);
-    Unit& ul = p.units[b.units[nu - 1]];
-    const T* out = reinterpret_cast<const T*>(ws + ul.y_off);
-    T* dY = S[3];
-    T* dZ = S[4];
-    T* dXd = DX[2];
-    const bool has_ds = b.ds >= 0;
-    const T* dz_final;   // masked gradient of the block output (residual branch addend)
+  template <typename U>
+  U* at(size_t off) const { return reinterpret_cast<U*>(ws + off); }
+  T* wd(const Unit& u) const { return at<T>(p.off_wd) + u.wd_off; }
+  float* partial() const { return at<float>(p.off_partial); }
+  float* partial_b() const { return at<float>(p.off_partial_b); }
+  BnCoef coef_of(const Unit& u) const { return BnCoef(at<float>(u.coef_off), u.s.Cout); }
+  BnBwdCoef bwd_coef(const Unit& u) const { return BnBwdCoef(at<float>(p.off_coefbwd), u.s.Cout); }
+  const T* x_of(const Unit& u) const { return at<const T>(u.x_off); }
+  const T* input_of(const Block& b, int i) const { return at<const T>(i == 0 ? b.in_off : p.units[b.units[i - 1]].y_off); }
+  const SlotBuf<T>& dX() const { return B.dX[dxi]; }
+  bool algebraic(const Unit& u, const BlockGrad<T>& bg) const { return u.abn && bg.masked_with_sums; }
+  int acquire(int slot) { return p.side.acquire(slot, st, use_side); }
+  int next_dX() {   // the next dX goes to the other buffer of the pair: the weight gradient handed the current one may still be reading it
     dxi ^= 1;
-    if ((rc = acquire(dxi))) return rc;
-    if (has_ds && (rc = acquire(2))) return rc;
-    T* dX = DX[dxi];
-    const bool abn = fused_ready && ul.abn && sizeof(T) == 2;
-    if (fused_ready) {
-      const T* uin3 = nu > 1 ? reinterpret_cast<const T*>(ws + p.units[b.units[nu - 2]].y_off) : in;
-      const float* sgx = nullptr;
-      if (abn && ul.fwd2p) {
-        // two-pass unit: x was never stored.  g^T y first (main stream: the BatchNorm-backward sum of g x is W . (g^T y) row by row)
-        if constexpr (sizeof(T) == 2) {
-          float* S2 = reinterpret_cast<float*>(ws + p.off_abn_S2);
-          p.prof.begin(K_WGRAD, st);
-          rc = launch_wgrad_gram(ul.s.N, ul.s.OH(), ul.s.OW(), ul.s.Cin, ul.s.Cout, g, uin3, reinterpret_cast<float*>(ws + p.off_abn_slab2), S2,
-                                 reinterpret_cast<float*>(ws + p.off_abn_cs2), st, ul.gram_off ? 1 : 0);
-          p.prof.end(st);
-          if (p.prof.on) { p.prof.flops[K_WGRAD] += conv_flops(ul.s); p.prof.bytes[K_WGRAD] += conv_bytes(ul.s, sizeof(T)); }
-          if (rc) return rc;
-          if ((rc = abn_sgx(S2, params + ul.w_off, ul.s.Cout, ul.s.Cin, reinterpret_cast<float*>(ws + p.off_abn_sgx), st))) return rc;
-          sgx = reinterpret_cast<const float*>(ws + p.off_abn_sgx);
-        }
-      }
-      if ((rc = bn_bwd_fused(ul, g, partial, fused_rows, abn ? nullptr : dX, sgx))) return rc;
-      if (abn) {   // fold the coefficients into this block's conv3 data-gradient weights; keep a copy for the weight-gradient fix-up
-        if constexpr (sizeof(T) == 2) {
-          const BnBwdCoef c(cA, ul.s.Cout);
-          if ((rc = abn_prep(params + ul.w_off, c.cA, c.cB, c.cC, ul.s.Cout, ul.s.Cin, reinterpret_cast<bf16_t*>(ws + p.off_abn_wd),
-                             reinterpret_cast<float*>(ws + p.off_abn_bias), reinterpret_cast<float*>(ws + ul.abn_coef_off), st))) return rc;
-          const float* gkept = ul.gram_off ? reinterpret_cast<const float*>(ws + ul.gram_off) : nullptr;   // y^T y | colsum(y) from the forward pass
-          if (ul.fwd2p && (rc = abn_wgrad_finalize(reinterpret_cast<const float*>(ws + p.off_abn_S2),
-                                                   gkept ? gkept + (size_t)128 * ul.s.Cin : reinterpret_cast<const float*>(ws + p.off_abn_cs2), params + ul.w_off,
-                                                   reinterpret_cast<const float*>(ws + ul.abn_coef_off), ul.s.Cout, ul.s.Cin, grads + ul.w_off, st, gkept))) return rc;
-        }
-      }
-      if (has_ds) {
-        Unit& d = p.units[b.ds];
-        const bool abn_d = d.abn && sizeof(T) == 2;
-        if ((rc = bn_bwd_fused(d, g, partial_b, fused_rows, abn_d ? nullptr : dXd))) return rc;
-        if (abn_d) {
-          if constexpr (sizeof(T) == 2) {
-            const BnBwdCoef c(cA, d.s.Cout);
-            if ((rc = abn_prep(params + d.w_off, c.cA, c.cB, c.cC, d.s.Cout, d.s.Cin, reinterpret_cast<bf16_t*>(ws + p.off_abn_wd2),
-                               reinterpret_cast<float*>(ws + p.off_abn_bias2), reinterpret_cast<float*>(ws + d.abn_coef_off), st))) return rc;
-          }
-        }
-      }
-      dz_final = g;
-    } else {
-      if ((rc = bn_bwd(ul, g, out, MASK_FROM_Y, dX, has_ds ? nullptr : dZ))) return rc;
-      if (has_ds)
-        if ((rc = bn_bwd(p.units[b.ds], g, out, MASK_FROM_Y, dXd, nullptr))) return rc;
-      dz_final = dZ;
-    }
-    for (int i = nu - 1; i >= 0; --i) {
-      Unit& u = p.units[b.units[i]];
-      const T* uin = i == 0 ? in : reinterpret_cast<const T*>(ws + p.units[b.units[i - 1]].y_off);
-      const bool abn_u = abn && i == nu - 1;
-      if (abn_u) { if (!u.fwd2p && (rc = wgrad_abn_async(u, g, uin))) return rc; }   // (two-pass units: done above, on this stream)
-      else if ((rc = wgrad_async(u, dxi, uin))) return rc;
-      if (i > 0) {
-        // dgrad writes the gradient of unit i-1's ReLU output; its epilogue applies that ReLU's mask and
-        // accumulates unit i-1's BN-backward sums, so the stand-alone reduce pass is gone.
-        Unit& up = p.units[b.units[i - 1]];
-        DgradFuse f;
-        f.x = ws + up.x_off; f.scale = coef_of(up).scale; f.shift = coef_of(up).shift; f.partial = partial;
-        if (abn_u) {   // dY = [g | y] [cA (.) W ; Q] + r: no dz in memory
-          f.in2 = uin; f.k2 = u.s.Cin; f.bias = reinterpret_cast<const float*>(ws + p.off_abn_bias);
-          PROF(K_CONV_DGRAD, conv_flops(u.s), conv_bytes(u.s, sizeof(T), 1), launch_conv_dgrad<T>(u.s, g, reinterpret_cast<const T*>(ws + p.off_abn_wd), dY, (const T*)nullptr, st, &f));
-        } else
-        PROF(K_CONV_DGRAD, conv_flops(u.s), conv_bytes(u.s, sizeof(T), 1), launch_conv_dgrad<T>(u.s, dX, wd + u.wd_off, dY, (const T*)nullptr, st, &f));
-        dxi ^= 1;                              // the next dX goes to the other buffer: wgrad(u) may still read this one
-        if ((rc = acquire(dxi))) return rc;
-        dX = DX[dxi];
-        if ((rc = bn_bwd_fused(up, dY, partial, f.rows_written, dX))) return rc;
-      } else {
-        const T* addend = dz_final;
-        bool ds_addend_compact = false;
-        static const bool ds_compact = env_knob("MMSKIN_DS_COMPACT", 1) != 0;
-        if (has_ds) {
-          Unit& d = p.units[b.ds];
-          if ((rc = g_acquire(gin))) return rc;
-          if (fused_ready && d.abn && sizeof(T) == 2) {   // stride-1 downsample convolution on the algebraic path, as conv3 above
-            if ((rc = wgrad_abn_async(d, g, in))) return rc;
-            DgradFuse fd;
-            fd.in2 = in; fd.k2 = d.s.Cin; fd.bias = reinterpret_cast<const float*>(ws + p.off_abn_bias2);
-            PROF(K_CONV_DGRAD, conv_flops(d.s), conv_bytes(d.s, sizeof(T)), launch_conv_dgrad<T>(d.s, g, reinterpret_cast<const T*>(ws + p.off_abn_wd2), gin, (const T*)nullptr, st, &fd));
-          } else if (ds_compact && bi > 0 && d.s.kh == 1 && d.s.stride == 2 && d.s.pad == 0 && u.s.kh == 1 && u.s.stride == 1) {
-            // Stride-2 1x1 downsample: its data gradient lives on the even pixels only.  It is computed as the dense GEMM over the pixels the
-            // convolution read (a 1x1 / stride 1 launch on the OH x OW grid) into a COMPACT buffer, and conv1's dgrad adds it at the even
-            // pixels in its epilogue: the zero fill of the other three quarters (154 + 77 + 38 MB written, then read back as the addend)
-            // and its launches are gone.
-            if ((rc = wgrad_async(d, 2, in))) return rc;
-            ConvShape dc = d.s;
-            dc.H = d.s.OH(); dc.W = d.s.OW(); dc.stride = 1;
-            PROF(K_CONV_DGRAD, conv_flops(d.s), conv_bytes(d.s, sizeof(T)), launch_conv_dgrad<T>(dc, dXd, wd + d.wd_off, S[3], (const T*)nullptr, st));
-            ds_addend_compact = true;
-          } else {
-            if ((rc = wgrad_async(d, 2, in))) return rc;
-            PROF(K_CONV_DGRAD, conv_flops(d.s), conv_bytes(d.s, sizeof(T)), launch_conv_dgrad<T>(d.s, dXd, wd + d.wd_off, gin, (const T*)nullptr, st));
-          }
-          addend = ds_addend_compact ? S[3] : gin;   // main-branch dgrad accumulates on top (in place unless the branch's gradient is compact)
-        }
-        if ((rc = g_acquire(gin))) return rc;
-        DgradFuse f;
-        DgradFuse* fp = nullptr;
-        if (bi > 0) {   // gin is the gradient of the previous block's output: fuse that block's final BN reduce
-          Block& pb = p.blocks[bi - 1];
-          Unit& pu = p.units[pb.units.back()];
-          f.mask_bits = ws + pb.mask_off; f.x = pu.fwd2p ? nullptr : ws + pu.x_off; f.partial = partial;   // two-pass unit: no raw output to take sums against
-          if (pb.ds >= 0) { f.x2 = ws + p.units[pb.ds].x_off; f.partial_b = partial_b; }
-          f.addend_s2 = ds_addend_compact;
-          fp = &f;
-        }
-        PROF(K_CONV_DGRAD, conv_flops(u.s), conv_bytes(u.s, sizeof(T), 1 + (fp ? (f.x2 ? 3 : 2) : 0)), launch_conv_dgrad<T>(u.s, dX, wd + u.wd_off, gin, addend, st, fp));
-        fused_ready = fp != nullptr;
-        fused_rows = f.rows_written;
-      }
-    }
-    T* t = g; g = gin; gin = t;
-    if (b.seg_done >= 0 && (rc = p.segment_done(b.seg_done, st, use_side))) return rc;
+    return acquire(dX().slot);
   }
 
-  // ---- stem: g = grad wrt pooled activation.  Its BatchNorm backward touches none of the buffers the side stream's
-  // weight-gradient GEMMs are still reading (dX ring, forward activations) or writing (slab), so it runs on the main
-  // stream BESIDE the tail of layer1's wgrads; the stem's own wgrad needs the slab and queues behind them on the side stream.
-  Unit& u0 = p.units[0];
-  const StemBufs<T> sb = stem_bufs<T>(p, ws);   // dx0 = S[3]
-  if ((rc = stem_backward<T>(sb, p.sg, g, params + u0.g_off, grads + u0.g_off, grads + u0.b_off, stem_sums_pooled(), &p.prof,
-                             3.5 * u0.rows() * 64 * sizeof(T), st))) return rc;
-  if ((rc = p.side.run(0, st, use_side, [&](hipStream_t wst) { return stem_wgrad<T>(sb, p.sg, grads + u0.w_off, &p.prof, wst); }))) return rc;
-  if ((rc = acquire(0))) return rc;   // final join: everything the side stream was given has finished before backward's last event
-  return p.segment_done((int)p.segments.size() - 1, st, false);
-}
+  // ---- BatchNorm backward of unit u, three forms
+  // from dy: reduce -> finalize -> apply with the ReLU mask taken from the block output y; fills dx and, when given, dz (the masked dy)
+  int bn_from_dy(Unit& u, const T* dy, const T* y, T* dx, T* dz) {
+    return bn_backward<T>(dy, x_of(u), y, MASK_FROM_Y, u.rows(), u.s.Cout, coef_of(u), params + u.g_off, grads + u.g_off, grads + u.b_off,
+                          bwd_coef(u), partial(), red, dx, dz, &p.prof, 7.0 * u.rows() * u.s.Cout * sizeof(T), st);
+  }
+  // from sums: dz is masked already and the data gradient that wrote it left its partial sums: finalize + one apply pass.
+  // dx == nullptr: finalize only (gamma / beta gradients and cA, cB, cC); sum_dz_x: the second sum from elsewhere (two-pass units)
+  int bn_from_sums(Unit& u, const T* dz, const float* part, int nrows, T* dx, const float* sum_dz_x = nullptr) {
+    return bn_backward_from_sums<T>(dz, x_of(u), part, nrows, u.rows(), u.s.Cout, coef_of(u), params + u.g_off, grads + u.g_off,
+                                    grads + u.b_off, bwd_coef(u), red, dx, &p.prof, dx ? 3.0 * u.rows() * u.s.Cout * sizeof(T) : 0.0, st, -1,
+                                    false, sum_dz_x);
+  }
+  // algebraic (abn.hip): finalize without the apply pass, then fold cA, cB, cC into data-gradient weights of buffer set k; u keeps a
+  // copy of the coefficients for its weight gradient.  A two-pass unit stored no x: its g^T y runs first, on this stream (the sum of
+  // g x is W . (g^T y) row by row), and its weight gradient is finished here from the same product.
+  int bn_algebraic(Unit& u, const BlockGrad<T>& bg, const float* part, AbnSet k, const T* uin) {
+    int rc;
+    const T* g = bg.dz.p;
+    float* S2 = at<float>(p.off_abn_S2);
+    float* coef_copy = at<float>(u.abn_coef_off);
+    const float* sgx = nullptr;
+    if (u.fwd2p) {
+      PROF(K_WGRAD, conv_flops(u.s), conv_bytes(u.s, sizeof(T)),
+           wgrad_gram<T>(u.s, g, uin, at<float>(p.off_abn_slab2), S2, at<float>(p.off_abn_cs2), st, u.gram_off ? 1 : 0));
+      if ((rc = abn_sgx(S2, params + u.w_off, u.s.Cout, u.s.Cin, at<float>(p.off_abn_sgx), st))) return rc;
+      sgx = at<float>(p.off_abn_sgx);
+    }
+    if ((rc = bn_from_sums(u, g, part, bg.sum_rows, nullptr, sgx))) return rc;
+    const BnBwdCoef c = bwd_coef(u);
+    if ((rc = abn_prep(params + u.w_off, c.cA, c.cB, c.cC, u.s.Cout, u.s.Cin, at<bf16_t>(k == ABN_DS ? p.off_abn_wd2 : p.off_abn_wd),
+                       at<float>(k == ABN_DS ? p.off_abn_bias2 : p.off_abn_bias), coef_copy, st))) return rc;
+    if (!u.fwd2p) return MMSKIN_OK;
+    const float* gkept = u.gram_off ? at<const float>(u.gram_off) : nullptr;   // y^T y | colsum(y) from the forward pass
+    return abn_wgrad_finalize(S2, gkept ? gkept + (size_t)128 * u.s.Cin : at<const float>(p.off_abn_cs2), params + u.w_off, coef_copy, u.s.Cout,
+                              u.s.Cin, grads + u.w_off, st, gkept);
+  }
+  // ... and its data gradient din = [g | y] [cA (.) W ; Q] + r from set k: no dz in memory.  f: the epilogue of the unit below, if any
+  int dgrad_algebraic(const Unit& u, AbnSet k, const T* g, const T* uin, T* din, DgradFuse& f, int extra_in_shaped) {
+    int rc;
+    f.in2 = uin; f.k2 = u.s.Cin; f.bias = at<const float>(k == ABN_DS ? p.off_abn_bias2 : p.off_abn_bias);
+    PROF(K_CONV_DGRAD, conv_flops(u.s), conv_bytes(u.s, sizeof(T), extra_in_shaped),
+         launch_conv_dgrad<T>(u.s, g, at<const T>(k == ABN_DS ? p.off_abn_wd2 : p.off_abn_wd), din, (const T*)nullptr, st, &f));
+    return MMSKIN_OK;
+  }
+
+  // ---- weight gradients: handed to the side stream with the buffer they read
+  int wgrad_async(Unit& u, const SlotBuf<T>& dx, const T* uin) {
+    return p.side.run(dx.slot, st, use_side, [&](hipStream_t wst) {
+      ProfScope scope(&p.prof, K_WGRAD, wst, conv_flops(u.s), conv_bytes(u.s, sizeof(T)));
+      return launch_conv_wgrad<T>(u.s, dx.p, uin, slab, grads + u.w_off, wst);
+    });
+  }
+  // algebraic: dW = cA (.) (g^T y) + cB (.) (W (y^T y)) + cC (x) colsum(y), reading the block-output gradient g itself
+  int wgrad_abn_async(Unit& u, const SlotBuf<T>& g, const T* uin) {
+    return p.side.run(g.slot, st, use_side, [&](hipStream_t wst) {
+      float* S_out = at<float>(p.off_abn_S);
+      float* cs_out = at<float>(p.off_abn_cs);
+      ProfScope scope(&p.prof, K_WGRAD, wst, conv_flops(u.s), conv_bytes(u.s, sizeof(T)));
+      if (int r = wgrad_gram<T>(u.s, g.p, uin, slab.p, S_out, cs_out, wst)) return r;
+      return abn_wgrad_finalize(S_out, cs_out, params + u.w_off, at<const float>(u.abn_coef_off), u.s.Cout, u.s.Cin, grads + u.w_off, wst);
+    });
+  }
+  int wgrad_of(const Block& b, int i, const BlockGrad<T>& bg) {   // unit i of the block, from the current dX
+    Unit& u = p.units[b.units[i]];
+    if (!algebraic(u, bg)) return wgrad_async(u, dX(), input_of(b, i));
+    return u.fwd2p ? MMSKIN_OK : wgrad_abn_async(u, bg.dz, input_of(b, i));   // (two-pass units: finished in bn_algebraic)
+  }
+
+  // ---- the three steps of a block
+  // tail: BatchNorm backward of the block's final unit (dx into the next dX, or algebraic set ABN_CONV3) and of its downsample branch
+  // (B.dXd, or ABN_DS).  *dz_final: the masked gradient of the block output, the residual addend of a block without a branch.
+  int tail(const Block& b, const BlockGrad<T>& bg, const T** dz_final) {
+    int rc;
+    const int nu = (int)b.units.size();
+    Unit& ul = p.units[b.units[nu - 1]];
+    Unit* d = b.ds >= 0 ? &p.units[b.ds] : nullptr;
+    if ((rc = next_dX())) return rc;
+    if (d && (rc = acquire(B.dXd.slot))) return rc;
+    if (!bg.masked_with_sums) {
+      ARG_CHECK(!ul.fwd2p, "backbone_backward: a two-pass unit stores no raw output, its BatchNorm backward cannot start from dy");
+      const T* out = at<const T>(ul.y_off);
+      *dz_final = B.dZ;
+      if ((rc = bn_from_dy(ul, bg.dz.p, out, dX().p, d ? nullptr : B.dZ))) return rc;
+      return d ? bn_from_dy(*d, bg.dz.p, out, B.dXd.p, nullptr) : MMSKIN_OK;
+    }
+    *dz_final = bg.dz.p;
+    if (ul.abn) rc = bn_algebraic(ul, bg, partial(), ABN_CONV3, input_of(b, nu - 1));
+    else rc = bn_from_sums(ul, bg.dz.p, partial(), bg.sum_rows, dX().p);
+    if (rc || !d) return rc;
+    if (d->abn) return bn_algebraic(*d, bg, partial_b(), ABN_DS, nullptr);
+    return bn_from_sums(*d, bg.dz.p, partial_b(), bg.sum_rows, B.dXd.p);
+  }
+
+  // unit i > 0: its weight gradient is handed off, its data gradient writes the gradient of unit i-1's ReLU output into B.dY -- the
+  // epilogue applies that ReLU's mask and takes unit i-1's BatchNorm-backward sums -- and unit i-1's BatchNorm backward makes the next dX
+  int unit(const Block& b, int i, const BlockGrad<T>& bg) {
+    int rc;
+    Unit& u = p.units[b.units[i]];
+    Unit& up = p.units[b.units[i - 1]];
+    if ((rc = wgrad_of(b, i, bg))) return rc;
+    DgradFuse f;
+    f.x = ws + up.x_off; f.scale = coef_of(up).scale; f.shift = coef_of(up).shift; f.partial = partial();
+    if (algebraic(u, bg)) {
+      if ((rc = dgrad_algebraic(u, ABN_CONV3, bg.dz.p, input_of(b, i), B.dY, f, 1))) return rc;
+    } else {
+      PROF(K_CONV_DGRAD, conv_flops(u.s), conv_bytes(u.s, sizeof(T), 1), launch_conv_dgrad<T>(u.s, dX().p, wd(u), B.dY, (const T*)nullptr, st, &f));
+    }
+    if ((rc = next_dX())) return rc;
+    return bn_from_sums(up, B.dY, partial(), f.rows_written, dX().p);
+  }
+
+  // block input: the downsample branch's data gradient (algebraic, compact stride-2 or dense) and conv1's on top of it -- or on top of
+  // dz_final -- into gin, with the mask and the BatchNorm-backward sums of the block below in its epilogue.  Returns what that block takes.
+  int block_input(int bi, const BlockGrad<T>& bg, const T* dz_final, const SlotBuf<T>& gin, BlockGrad<T>* below) {
+    int rc;
+    const Block& b = p.blocks[bi];
+    Unit& u = p.units[b.units[0]];
+    const T* in = input_of(b, 0);
+    if ((rc = wgrad_of(b, 0, bg))) return rc;
+    if ((rc = acquire(gin.slot))) return rc;   // an algebraic weight gradient of the block above may still be reading it
+    const T* addend = dz_final;
+    if (b.ds >= 0) {
+      Unit& d = p.units[b.ds];
+      addend = b.ds_compact ? B.ds_addend : gin.p;   // conv1's data gradient accumulates on top (in place unless the branch's gradient is compact)
+      if (algebraic(d, bg)) {   // stride-1 downsample convolution, as conv3
+        if ((rc = wgrad_abn_async(d, bg.dz, in))) return rc;
+        DgradFuse fd;
+        if ((rc = dgrad_algebraic(d, ABN_DS, bg.dz.p, in, gin.p, fd, 0))) return rc;
+      } else {
+        if ((rc = wgrad_async(d, B.dXd, in))) return rc;
+        // Stride-2 1x1 downsample: its data gradient lives on the even pixels only.  Compact: the dense GEMM over the pixels the
+        // convolution read (a 1x1 / stride 1 launch on the OH x OW grid) into B.ds_addend, and conv1's data gradient adds it at the even
+        // pixels in its epilogue: no zero fill of the other three quarters (154 + 77 + 38 MB written, then read back as the addend).
+        ConvShape dc = d.s;
+        if (b.ds_compact) { dc.H = d.s.OH(); dc.W = d.s.OW(); dc.stride = 1; }
+        PROF(K_CONV_DGRAD, conv_flops(d.s), conv_bytes(d.s, sizeof(T)),
+             launch_conv_dgrad<T>(dc, B.dXd.p, wd(d), b.ds_compact ? B.ds_addend : gin.p, (const T*)nullptr, st));
+      }
+    }
+    DgradFuse f;
+    DgradFuse* fp = nullptr;
+    if (bi > 0) {   // gin is the gradient of the block below's output: fuse that block's mask and final BatchNorm-backward sums
+      const Block& pb = p.blocks[bi - 1];
+      const Unit& pu = p.units[pb.units.back()];
+      f.mask_bits = ws + pb.mask_off; f.x = pu.fwd2p ? nullptr : ws + pu.x_off; f.partial = partial();   // two-pass unit: no raw output to take sums against
+      if (pb.ds >= 0) { f.x2 = ws + p.units[pb.ds].x_off; f.partial_b = partial_b(); }
+      f.addend_s2 = b.ds_compact;
+      fp = &f;
+    }
+    PROF(K_CONV_DGRAD, conv_flops(u.s), conv_bytes(u.s, sizeof(T), 1 + (fp ? (f.x2 ? 3 : 2) : 0)),
+         launch_conv_dgrad<T>(u.s, dX().p, wd(u), gin.p, addend, st, fp));
+    *below = BlockGrad<T>{gin, fp != nullptr, f.rows_written};
+    return MMSKIN_OK;
+  }
+
+  // the stem: g = gradient of the pooled activation.  Its BatchNorm backward touches none of the buffers the side stream's
+  // weight-gradient GEMMs are still reading (dX ring, forward activations) or writing (slab), so it runs on the main stream BESIDE the
+  // tail of layer1's weight gradients; the stem's own needs the slab and queues behind them on the side stream.
+  int stem(const T* g) {
+    int rc;
+    Unit& u0 = p.units[0];
+    const StemBufs<T> sb = stem_bufs<T>(p, ws);
+    if ((rc = stem_backward<T>(sb, p.sg, g, params + u0.g_off, grads + u0.g_off, grads + u0.b_off, stem_sums_pooled(), &p.prof,
+                               3.5 * u0.rows() * 64 * sizeof(T), st))) return rc;
+    if ((rc = p.side.run(SLOT_DX0, st, use_side, [&](hipStream_t wst) { return stem_wgrad<T>(sb, p.sg, grads + u0.w_off, &p.prof, wst); }))) return rc;
+    return acquire(SLOT_DX0);   // final join: everything the side stream was given has finished before backward's last event
+  }
+
+  int run(const float* dfeat) {
+    int rc;
+    const Unit& last = p.units[p.blocks.back().units.back()];
+    BlockGrad<T> bg = {B.G[0], false, 0};
+    if ((rc = avgpool_bwd<T>(dfeat, p.N, last.s.OH() * last.s.OW(), last.s.Cout, bg.dz.p, st))) return rc;
+    if (use_side && (rc = p.side.init(SIDE_SLOTS))) return rc;
+    p.side.begin_backward();
+    int gi = 0;   // B.G[gi] holds the gradient of the current block's output
+    for (int bi = (int)p.blocks.size() - 1; bi >= 0; --bi) {
+      const Block& b = p.blocks[bi];
+      const T* dz_final;
+      if ((rc = tail(b, bg, &dz_final))) return rc;
+      for (int i = (int)b.units.size() - 1; i > 0; --i)
+        if ((rc = unit(b, i, bg))) return rc;
+      BlockGrad<T> below;
+      if ((rc = block_input(bi, bg, dz_final, B.G[gi ^= 1], &below))) return rc;
+      bg = below;
+      if (b.seg_done >= 0 && (rc = p.segment_done(b.seg_done, st, use_side))) return rc;
+    }
+    if ((rc = stem(bg.dz.p))) return rc;
+    return p.segment_done((int)p.segments.size() - 1, st, false);
+  }
+};
 
 int Plan::forward(const void* image, const float* norm6, const float* params, float* buffers, unsigned char* ws,
                   float* features, bool training, hipStream_t st) {
@@ -689,8 +765,8 @@ int Plan::forward(const void* image, const float* norm6, const float* params, fl
   return forward_impl<float>(*this, image, norm6, params, buffers, ws, features, training, st);
 }
 int Plan::backward(const float* dfeat, const float* params, unsigned char* ws, float* grads, hipStream_t st) {
-  if (dtype == 1) return backward_impl<bf16_t>(*this, dfeat, params, ws, grads, st);
-  return backward_impl<float>(*this, dfeat, params, ws, grads, st);
+  if (dtype == 1) return ResNetBackward<bf16_t>(*this, params, ws, grads, st).run(dfeat);
+  return ResNetBackward<float>(*this, params, ws, grads, st).run(dfeat);
 }
 // torchvision's last nn.Conv2d in module order is the final block's last conv (layerN.k.conv3 / conv2)
 int Plan::last_conv_shape(int* C, int* OH, int* OW) const {
@@ -721,6 +797,18 @@ int Plan::unit_info(int index, std::string* name, int64_t* info12) const {
   return MMSKIN_OK;
 }
 
+int Plan::unit_flags(int index, int* flags) const {
+  const Unit& u = units[index];
+  int f = (u.abn ? MMSKIN_UNIT_ABN : 0) | (u.fwd2p ? MMSKIN_UNIT_FWD2P : 0) | (u.gram_off ? MMSKIN_UNIT_GRAM : 0);
+  for (const Block& b : blocks) {
+    if (b.ds != index && std::find(b.units.begin(), b.units.end(), index) == b.units.end()) continue;
+    if (&b == &blocks.back()) f |= MMSKIN_UNIT_LAST_BLOCK;
+    if (b.ds == index) f |= MMSKIN_UNIT_DS | (b.ds_compact ? MMSKIN_UNIT_DS_COMPACT : 0);
+  }
+  *flags = f;
+  return MMSKIN_OK;
+}
+
 }  // namespace
 
 PlanBase* make_resnet_plan(int arch, int N, int H, int W, int dtype, int* rc) {
@@ -732,7 +820,6 @@ PlanBase* make_resnet_plan(int arch, int N, int H, int W, int dtype, int* rc) {
 }
 
 // ------------------------------------------------------------------------------------------ C ABI
-#include "../../include/mmskin.h"
 
 struct mmskin_backbone { PlanBase* plan = nullptr; };
 
@@ -827,6 +914,15 @@ int mmskin_backbone_unit_info(mmskin_backbone_t h, int index, char* name, int na
   if (rc) return rc;
   if (name && name_cap > 0) { strncpy(name, nm.c_str(), name_cap - 1); name[name_cap - 1] = 0; }
   return MMSKIN_OK;
+}
+
+int mmskin_backbone_unit_flags(mmskin_backbone_t h, int index, int* flags) {
+  ARG_CHECK(h && flags, "backbone_unit_flags: null argument");
+  if (h->plan->num_units() == 0) { mmskin_set_error("backbone_unit_flags: this plan reports no units"); return MMSKIN_ERR_UNSUPPORTED; }
+  ARG_CHECK(index >= 0 && index < h->plan->num_units(), "backbone_unit_flags: index %d out of range", index);
+  int rc = h->plan->unit_flags(index, flags);
+  if (rc == MMSKIN_ERR_UNSUPPORTED) mmskin_set_error("backbone_unit_flags: this plan exports no unit flags");
+  return rc;
 }
 
 int mmskin_backbone_forward(mmskin_backbone_t h, const float* image_nchw, const float* params, float* buffers,

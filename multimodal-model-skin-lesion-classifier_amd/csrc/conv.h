@@ -255,7 +255,16 @@ template <typename T>
 int launch_stem_conv_wgrad(int N, int OH, int OW, int Hp, int Wp, const T* dout, const T* img4,
                            WgradSlab slab, float* dwv, hipStream_t st);
 
-// algebraic BatchNorm backward of an expanding 1x1 convolution (abn.hip)
+// algebraic BatchNorm backward of an expanding 1x1 convolution (abn.hip), Cw -> C4 channels.
+// abn_accepts: the shapes its kernels take.  abn_prep: Cw in {64, 128, 256} (256 threads split a Q row as 256 / Cw parts x Cw columns),
+// C4 <= 1024 (one LDS column) and C4 % (4 * (256 / Cw)) == 0 (each part walks its share four rows at a time); abn_wgrad_finalize: one
+// thread per input channel, Cw <= 256; the data gradient that reads abn_prep's wd (DgradFuse::in2): C4 = Cw * 2^j.  abn_prep and
+// abn_wgrad_finalize check it at launch, the ResNet plan when it picks the units that take this path.
+inline bool abn_accepts(int C4, int Cw) {
+  if (Cw != 64 && Cw != 128 && Cw != 256) return false;
+  const int ratio = C4 / Cw;
+  return C4 > 0 && C4 <= 1024 && C4 % (4 * (256 / Cw)) == 0 && C4 % Cw == 0 && (ratio & (ratio - 1)) == 0;
+}
 int abn_prep(const float* W, const float* cA, const float* cB, const float* cC, int C4, int Cw, bf16_t* wd, float* bias, float* coef_copy,
              hipStream_t st);
 int abn_wgrad_finalize(const float* S, const float* colsum, const float* W, const float* coef, int C4, int Cw, float* dW, hipStream_t st,

@@ -168,6 +168,7 @@ struct PlanBase {
   // per-unit introspection (tests / diagnostics); plans without it report zero units
   virtual int num_units() const { return 0; }
   virtual int unit_info(int, std::string*, int64_t*) const { return MMSKIN_ERR_UNSUPPORTED; }
+  virtual int unit_flags(int, int*) const { return MMSKIN_ERR_UNSUPPORTED; }   // MMSKIN_UNIT_* bits: the plan's decisions for one unit
 
   int ensure_table() {   // uploaded on the first forward (create() needs no GPU)
     if (table_dev) return MMSKIN_OK;

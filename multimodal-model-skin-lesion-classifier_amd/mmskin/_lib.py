@@ -53,6 +53,7 @@ _SIGNATURES = {
                                           ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i64)]),
     "mmskin_backbone_num_units": (_i, [_P]),
     "mmskin_backbone_unit_info": (_i, [_P, _i, ctypes.c_char_p, _i, ctypes.POINTER(_i64)]),
+    "mmskin_backbone_unit_flags": (_i, [_P, _i, ctypes.POINTER(_i)]),
     "mmskin_backbone_forward": (_i, [_P, _P, _P, _P, _P, _P, _i, _P]),
     "mmskin_backbone_forward_u8": (_i, [_P, _P, _P, _P, _P, _P, _P, _i, _P]),
     "mmskin_backbone_backward": (_i, [_P, _P, _P, _P, _P, _P]),
