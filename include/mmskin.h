@@ -284,6 +284,20 @@ int mmskin_maxpool2_relu_backward(const float* dpool, const float* y, float* dz,
 int64_t mmskin_adaptive_avgpool_workspace_bytes(int N, int C, int H, int W);
 int mmskin_adaptive_avgpool_forward(const float* x, float* out, int N, int C, int H, int W, int dtype, void* workspace, void* stream);
 int mmskin_adaptive_avgpool_backward(const float* dout, float* dx, int N, int C, int H, int W, int dtype, void* workspace, void* stream);
+/* DynamicCNN: GroupNorm(8 groups, C) + ReLU of a raw convolution output y [N,C,H,W], optionally followed by MaxPool2d(2, 2) in the same
+ * kernel.  pool = 0: out = z [N,C,H,W], idx unused (may be NULL).  pool = 1: out = the pooled z [N,C,H/2,W/2] (floor; the un-pooled z is
+ * never stored) and idx = the argmax tap 0..3 of every pooled element, bytes in the kernel's layout [N,H/2,W/2,C], format and tie-break of
+ * mmskin_maxpool2_relu_forward.  mean / rstd (may be NULL): the statistics [N,8], from per-workgroup (count, mean, M2) partials combined by
+ * Chan's formula in fp64 -- no atomics, bitwise repeatable.  Backward: gout = the gradient at `out` (same shape) -> dy [N,C,H,W], dgamma,
+ * dbeta [C] (may be NULL); it recomputes the statistics, the argmax bytes and the ReLU mask from y, no mask is stored.
+ * Errors, before any launch: groups != 8 or C not a multiple of 64 (or above 1024): MMSKIN_ERR_UNSUPPORTED (workspace_bytes: -1); a
+ * non-positive extent, or a map smaller than 2x2 with pool: MMSKIN_ERR_ARG. */
+int64_t mmskin_groupnorm8_relu_workspace_bytes(int N, int C, int H, int W, int groups, int pool);
+int mmskin_groupnorm8_relu_forward(const float* y, const float* gamma, const float* beta, float* out, unsigned char* idx, float* mean, float* rstd,
+                                   int N, int C, int H, int W, int groups, int pool, float eps, int dtype, void* workspace, void* stream);
+int mmskin_groupnorm8_relu_backward(const float* gout, const float* y, const float* gamma, const float* beta, float* dy, float* dgamma,
+                                    float* dbeta, int N, int C, int H, int W, int groups, int pool, float eps, int dtype, void* workspace,
+                                    void* stream);
 /* the ResNet stem: conv7x7/2 (OIHW [64,3,7,7]) -> BN(train) -> ReLU -> maxpool3x3/2; y [N,64,PH,PW] */
 int64_t mmskin_stem_workspace_bytes(int N, int H, int W);
 int mmskin_stem_forward(const float* x, const float* w, const float* gamma, const float* beta, float* y, int N, int H,

@@ -768,6 +768,54 @@ int adaptive_bwd_op(const float* dout, float* dx, int N, int C, int H, int W, vo
   return nhwc_to_nchw<T>(s.dxh, N, C, H, W, dx, st);
 }
 
+// DynamicCNN: GroupNorm(8, C) + ReLU (+ 2x2 max-pool) and its backward, which recomputes the forward's statistics (and argmax bytes) first
+template <typename T>
+struct GroupNormWs {
+  T *yh, *oh, *gh, *dyh; uint8_t* idx; float *mean, *rstd, *sums, *partial, *dg, *db; double* stat; ColScratch red; size_t total; int PH, PW;
+  GroupNormWs(void* ws, int N, int C, int H, int W, bool pool) {
+    PH = pool ? H / 2 : H; PW = pool ? W / 2 : W;
+    Carver c(ws);
+    const size_t rows = (size_t)N * H * W, orows = (size_t)N * PH * PW;
+    yh = c.take<T>(rows * C); oh = c.take<T>(orows * C); idx = c.take<uint8_t>(pool ? orows * C : 0);
+    gh = c.take<T>(orows * C); dyh = c.take<T>(rows * C);
+    mean = c.take<float>((size_t)N * 8); rstd = c.take<float>((size_t)N * 8); sums = c.take<float>((size_t)N * 16);
+    stat = c.take<double>(gn8_stat_scratch_bytes(N) / sizeof(double));
+    partial = c.take<float>(gn8_bwd_partial_bytes(N, C) / sizeof(float));
+    dg = c.take<float>(C); db = c.take<float>(C);
+    red = bn_reduce_scratch(c.take<double>(bn_reduce_scratch_bytes(C) / sizeof(double)), C);
+    total = c.cur;
+  }
+};
+template <typename T>
+int groupnorm_fwd_op(const float* y, const float* gamma, const float* beta, float* out, uint8_t* idx, float* mean, float* rstd, int N, int C, int H,
+                     int W, bool pool, float eps, void* ws, hipStream_t st) {
+  GroupNormWs<T> s(ws, N, C, H, W, pool);
+  int rc;
+  if ((rc = nchw_to_nhwc<T>(y, N, C, H, W, s.yh, st))) return rc;
+  if ((rc = gn8_stats<T>(s.yh, N, H * W, C, eps, s.stat, s.mean, s.rstd, st))) return rc;
+  if (mean) HIP_CHECK_RET(hipMemcpyAsync(mean, s.mean, (size_t)N * 8 * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (rstd) HIP_CHECK_RET(hipMemcpyAsync(rstd, s.rstd, (size_t)N * 8 * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (pool) {
+    if ((rc = gn8_relu_pool_apply<T>(s.yh, s.mean, s.rstd, gamma, beta, N, H, W, C, s.oh, s.idx, st))) return rc;
+    if (idx) HIP_CHECK_RET(hipMemcpyAsync(idx, s.idx, (size_t)N * s.PH * s.PW * C, hipMemcpyDeviceToDevice, st));
+  } else if ((rc = gn8_relu_apply<T>(s.yh, s.mean, s.rstd, gamma, beta, N, H, W, C, s.oh, st))) {
+    return rc;
+  }
+  return out ? nhwc_to_nchw<T>(s.oh, N, C, s.PH, s.PW, out, st) : MMSKIN_OK;
+}
+template <typename T>
+int groupnorm_bwd_op(const float* gout, const float* y, const float* gamma, const float* beta, float* dy, float* dgamma, float* dbeta, int N, int C,
+                     int H, int W, bool pool, float eps, void* ws, hipStream_t st) {
+  GroupNormWs<T> s(ws, N, C, H, W, pool);
+  int rc;
+  if ((rc = groupnorm_fwd_op<T>(y, gamma, beta, nullptr, nullptr, nullptr, nullptr, N, C, H, W, pool, eps, ws, st))) return rc;
+  if ((rc = nchw_to_nhwc<T>(gout, N, C, s.PH, s.PW, s.gh, st))) return rc;
+  if ((rc = gn8_relu_backward<T>(s.gh, pool ? s.idx : nullptr, s.yh, s.mean, s.rstd, gamma, beta, N, H, W, C, s.partial, s.sums, s.red,
+                                 dgamma ? dgamma : s.dg, dbeta ? dbeta : s.db, s.dyh, st)))
+    return rc;
+  return nhwc_to_nchw<T>(s.dyh, N, C, H, W, dy, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1284,5 +1332,26 @@ int mmskin_adaptive_avgpool_backward(const float* dout, float* dx, int N, int C,
   DISPATCH(dtype, adaptive_bwd_op<float>(dout, dx, N, C, H, W, workspace, st), adaptive_bwd_op<bf16_t>(dout, dx, N, C, H, W, workspace, st));
 }
 #undef APOOL_OK
+
+int64_t mmskin_groupnorm8_relu_workspace_bytes(int N, int C, int H, int W, int groups, int pool) {
+  if (gn8_check(N, C, H, W, groups, pool != 0, "groupnorm8_relu_workspace_bytes")) return -1;
+  return ws_bytes<GroupNormWs<float>>(N, C, H, W, pool != 0);
+}
+int mmskin_groupnorm8_relu_forward(const float* y, const float* gamma, const float* beta, float* out, unsigned char* idx, float* mean, float* rstd,
+                                   int N, int C, int H, int W, int groups, int pool, float eps, int dtype, void* workspace, void* stream) {
+  if (int rc = gn8_check(N, C, H, W, groups, pool != 0, "groupnorm8_relu_forward")) return rc;
+  ARG_CHECK(y && gamma && beta && out && workspace && (!pool || idx), "groupnorm8_relu_forward: null argument");
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype, groupnorm_fwd_op<float>(y, gamma, beta, out, idx, mean, rstd, N, C, H, W, pool != 0, eps, workspace, st),
+           groupnorm_fwd_op<bf16_t>(y, gamma, beta, out, idx, mean, rstd, N, C, H, W, pool != 0, eps, workspace, st));
+}
+int mmskin_groupnorm8_relu_backward(const float* gout, const float* y, const float* gamma, const float* beta, float* dy, float* dgamma, float* dbeta,
+                                    int N, int C, int H, int W, int groups, int pool, float eps, int dtype, void* workspace, void* stream) {
+  if (int rc = gn8_check(N, C, H, W, groups, pool != 0, "groupnorm8_relu_backward")) return rc;
+  ARG_CHECK(gout && y && gamma && beta && dy && workspace, "groupnorm8_relu_backward: null argument");
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype, groupnorm_bwd_op<float>(gout, y, gamma, beta, dy, dgamma, dbeta, N, C, H, W, pool != 0, eps, workspace, st),
+           groupnorm_bwd_op<bf16_t>(gout, y, gamma, beta, dy, dgamma, dbeta, N, C, H, W, pool != 0, eps, workspace, st));
+}
 
 }  // extern "C"

@@ -203,6 +203,30 @@ int adaptive_avgpool_bwd(const float* dout_nchw, int N, int H, int W, int C, int
 // db[c] = sum over rows of partial[r*stride + c]   (conv bias gradient from dgrad-epilogue / column_stats partials)
 int bias_grad_finalize(const float* partial, int nrows, int stride, int C, float* db, ColScratch scratch, hipStream_t st);
 
+// ---- GroupNorm(8, C) + ReLU (+ 2x2 max-pool) of the DynamicCNN trunk (groupnorm.hip); C a multiple of 64, statistics per (sample, group)
+// MMSKIN_OK when the kernels take the arguments; MMSKIN_ERR_UNSUPPORTED (groups != 8, C not a multiple of 64 or above 1024) or MMSKIN_ERR_ARG
+// (shape) with a message starting with `who`.  No launch.
+int gn8_check(int N, int C, int H, int W, int groups, bool pool, const char* who);
+size_t gn8_stat_scratch_bytes(int N);          // fp64 (count, mean, M2) partials of gn8_stats
+size_t gn8_bwd_partial_bytes(int N, int C);    // per-workgroup [2][C] sums of gn8_relu_backward
+// mean / rstd [N][8] of y [N][HW][C]: per-workgroup (count, mean, M2) combined by Chan's formula in fp64, no atomics
+template <typename T>
+int gn8_stats(const T* y, int N, int HW, int C, float eps, double* scratch, float* mean, float* rstd, hipStream_t st);
+// z = relu(gamma * (y - mean) * rstd + beta)
+template <typename T>
+int gn8_relu_apply(const T* y, const float* mean, const float* rstd, const float* gamma, const float* beta, int N, int H, int W, int C, T* z,
+                   hipStream_t st);
+// the 2x2 / stride 2 max-pool (floor) of that z and its argmax bytes (maxpool2_fwd's format and tie-break); z itself is not stored
+template <typename T>
+int gn8_relu_pool_apply(const T* y, const float* mean, const float* rstd, const float* gamma, const float* beta, int N, int H, int W, int C,
+                        T* pooled, uint8_t* idx, hipStream_t st);
+// gout: the gradient at z [N][H][W][C] (idx == nullptr) or at the pooled tensor [N][H/2][W/2][C] with its argmax bytes -> dy, dgamma, dbeta.
+// The ReLU mask is recomputed from y.  sums: [N][8][2] floats; partial: gn8_bwd_partial_bytes(); red: scratch of the column reducer (2 * C columns).
+template <typename T>
+int gn8_relu_backward(const T* gout, const uint8_t* idx, const T* y, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                      int N, int H, int W, int C, float* partial, float* sums, ColScratch red, float* dgamma, float* dbeta, T* dy,
+                      hipStream_t st);
+
 // Grad-CAM: dx[n][c][hw] (NCHW fp32) = dfeat[n][c] / HW * (y[n][hw][c] > 0) * scale[c]  -- the gradient of the pooled
 // features w.r.t. the raw output of the last conv under eval-mode BatchNorm (y = relu(x*scale + shift + skip), NHWC T)
 template <typename T>
