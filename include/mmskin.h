@@ -33,7 +33,17 @@ int mmskin_version(void);
  * (multimodalIntraInterModal.py:167; factory loadImageModelClassifier.py:65-75) and its backward.
  * Parameters: ONE flat fp32 buffer in torchvision named_parameters() order (conv.weight OIHW,
  * bn.weight, bn.bias ...); buffers: ONE flat fp32 buffer (running_mean, running_var per BN).
- * tensor_info enumerates names/offsets/shapes so the host can expose them as state_dict entries. */
+ * tensor_info enumerates names/offsets/shapes so the host can expose them as state_dict entries.
+ *
+ * arch is a fixed name ("resnet-18", "resnet-50", "densenet169", "densenet169-features", "vgg16-features", "mobilenet-v2",
+ * "efficientnet-b0", "efficientnet-b7") or the configured NAS trunk
+ *     dynamic-cnn/<f0>-<f1>-...-<fn>/l<layers_per_block>/p<0|1>/k<kernel_size>        e.g. dynamic-cnn/64-128-256/l2/p1/k3
+ * = [Conv2d(k, pad k/2, no bias) -> GroupNorm(8, f) -> ReLU] x layers per filter f, MaxPool2d(2, 2) after each block when p1, then
+ * AdaptiveAvgPool2d(1): features [N, fn].  Parameters are named by their index in that Sequential ("0.weight", "1.weight", "1.bias",
+ * "3.weight", ...); there are no buffers.  An optional fifth field "/t0" keeps the last layer's activation and runs the global average
+ * as separate launches (for timing against the default fused tail, "/t1").  Any other spelling: MMSKIN_ERR_ARG.  Refused with
+ * MMSKIN_ERR_UNSUPPORTED: k != 3, a filter that is not a multiple of 64 or above 1024, f0 != 64; with MMSKIN_ERR_ARG: no filter,
+ * l < 1, height or width above 240, a map below 2x2 in front of a pool. */
 typedef struct mmskin_backbone* mmskin_backbone_t;
 int mmskin_backbone_create(const char* arch, int batch, int height, int width, int dtype, mmskin_backbone_t* out);
 void mmskin_backbone_destroy(mmskin_backbone_t h);
@@ -298,6 +308,17 @@ int mmskin_groupnorm8_relu_forward(const float* y, const float* gamma, const flo
 int mmskin_groupnorm8_relu_backward(const float* gout, const float* y, const float* gamma, const float* beta, float* dy, float* dgamma,
                                     float* dbeta, int N, int C, int H, int W, int groups, int pool, float eps, int dtype, void* workspace,
                                     void* stream);
+/* The same operator where AdaptiveAvgPool2d(1) is its only consumer (the DynamicCNN trunk's last layer): feat [N,C] fp32 = the mean over the
+ * (pooled, with pool) map of relu(GroupNorm(y)), reduced through per-workgroup partial rows combined in a fixed order (bitwise repeatable).
+ * No activation, argmax or gradient tensor is stored: backward takes dfeat [N,C], forms dfeat / (OH * OW) in registers and, with pool,
+ * recomputes each window's argmax from y (first maximum, row-major; a NaN wins).  mean, rstd, dgamma, dbeta may be NULL.  Same refusals
+ * as mmskin_groupnorm8_relu_*. */
+int64_t mmskin_groupnorm8_relu_gap_workspace_bytes(int N, int C, int H, int W, int groups, int pool);
+int mmskin_groupnorm8_relu_gap_forward(const float* y, const float* gamma, const float* beta, float* feat, float* mean, float* rstd, int N, int C,
+                                       int H, int W, int groups, int pool, float eps, int dtype, void* workspace, void* stream);
+int mmskin_groupnorm8_relu_gap_backward(const float* dfeat, const float* y, const float* gamma, const float* beta, float* dy, float* dgamma,
+                                        float* dbeta, int N, int C, int H, int W, int groups, int pool, float eps, int dtype, void* workspace,
+                                        void* stream);
 /* the ResNet stem: conv7x7/2 (OIHW [64,3,7,7]) -> BN(train) -> ReLU -> maxpool3x3/2; y [N,64,PH,PW] */
 int64_t mmskin_stem_workspace_bytes(int N, int H, int W);
 int mmskin_stem_forward(const float* x, const float* w, const float* gamma, const float* beta, float* y, int N, int H,

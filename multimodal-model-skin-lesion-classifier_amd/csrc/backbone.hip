@@ -836,12 +836,14 @@ int mmskin_backbone_create(const char* arch, int batch, int height, int width, i
   else if (!strcmp(arch, "mobilenet-v2")) a = 2;
   else if (!strcmp(arch, "efficientnet-b0")) a = 100;
   else if (!strcmp(arch, "efficientnet-b7")) a = 107;
+  else if (!strncmp(arch, "dynamic-cnn/", 12)) a = 3;         // configured NAS trunk: the string carries filters / layers / pooling / kernel
   else { mmskin_set_error("backbone_create: Backbone '%s' has no HIP plan", arch); return MMSKIN_ERR_UNSUPPORTED; }
   ARG_CHECK(batch > 0 && height >= 32 && width >= 32, "backbone_create: bad shape %dx%dx%d", batch, height, width);
   ARG_CHECK(dtype == MMSKIN_F32 || dtype == MMSKIN_BF16, "backbone_create: dtype %d", dtype);
   int rc = MMSKIN_OK;
   PlanBase* p = (a == 169 || a == 1690) ? make_densenet_plan(batch, height, width, dtype, a == 1690, &rc)
                 : a == 16               ? make_vgg_plan(batch, height, width, dtype, &rc)
+                : a == 3                ? make_dynamic_cnn_plan(arch, batch, height, width, dtype, &rc)
                 : a == 2                ? make_mobilenet_plan(batch, height, width, dtype, &rc)
                 : a >= 100              ? make_efficientnet_plan(a - 100, batch, height, width, dtype, &rc)
                                         : make_resnet_plan(a, batch, height, width, dtype, &rc);

@@ -816,6 +816,45 @@ int groupnorm_bwd_op(const float* gout, const float* y, const float* gamma, cons
   return nhwc_to_nchw<T>(s.dyh, N, C, H, W, dy, st);
 }
 
+// DynamicCNN's tail: GroupNorm(8, C) + ReLU (+ pool) + global average in one kernel pair; no activation, argmax or gradient tensor to carve
+template <typename T>
+struct GroupNormGapWs {
+  T *yh, *dyh; float *mean, *rstd, *sums, *partial, *dg, *db; double* stat; ColScratch red; size_t total;
+  GroupNormGapWs(void* ws, int N, int C, int H, int W) {
+    Carver c(ws);
+    const size_t rows = (size_t)N * H * W;
+    yh = c.take<T>(rows * C); dyh = c.take<T>(rows * C);
+    mean = c.take<float>((size_t)N * 8); rstd = c.take<float>((size_t)N * 8); sums = c.take<float>((size_t)N * 16);
+    stat = c.take<double>(gn8_stat_scratch_bytes(N) / sizeof(double));
+    partial = c.take<float>(gn8_bwd_partial_bytes(N, C) / sizeof(float));
+    dg = c.take<float>(C); db = c.take<float>(C);
+    red = bn_reduce_scratch(c.take<double>(bn_reduce_scratch_bytes(C) / sizeof(double)), C);
+    total = c.cur;
+  }
+};
+template <typename T>
+int groupnorm_gap_fwd_op(const float* y, const float* gamma, const float* beta, float* feat, float* mean, float* rstd, int N, int C, int H, int W,
+                         bool pool, float eps, void* ws, hipStream_t st) {
+  GroupNormGapWs<T> s(ws, N, C, H, W);
+  int rc;
+  if ((rc = nchw_to_nhwc<T>(y, N, C, H, W, s.yh, st))) return rc;
+  if ((rc = gn8_stats<T>(s.yh, N, H * W, C, eps, s.stat, s.mean, s.rstd, st))) return rc;
+  if (mean) HIP_CHECK_RET(hipMemcpyAsync(mean, s.mean, (size_t)N * 8 * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (rstd) HIP_CHECK_RET(hipMemcpyAsync(rstd, s.rstd, (size_t)N * 8 * sizeof(float), hipMemcpyDeviceToDevice, st));
+  return feat ? gn8_relu_gap_apply<T>(s.yh, s.mean, s.rstd, gamma, beta, N, H, W, C, pool, s.partial, feat, st) : MMSKIN_OK;
+}
+template <typename T>
+int groupnorm_gap_bwd_op(const float* dfeat, const float* y, const float* gamma, const float* beta, float* dy, float* dgamma, float* dbeta, int N,
+                         int C, int H, int W, bool pool, float eps, void* ws, hipStream_t st) {
+  GroupNormGapWs<T> s(ws, N, C, H, W);
+  int rc;
+  if ((rc = groupnorm_gap_fwd_op<T>(y, gamma, beta, nullptr, nullptr, nullptr, N, C, H, W, pool, eps, ws, st))) return rc;
+  if ((rc = gn8_relu_gap_backward<T>(dfeat, s.yh, s.mean, s.rstd, gamma, beta, N, H, W, C, pool, s.partial, s.sums, s.red, dgamma ? dgamma : s.dg,
+                                     dbeta ? dbeta : s.db, s.dyh, st)))
+    return rc;
+  return nhwc_to_nchw<T>(s.dyh, N, C, H, W, dy, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1352,6 +1391,28 @@ int mmskin_groupnorm8_relu_backward(const float* gout, const float* y, const flo
   hipStream_t st = (hipStream_t)stream;
   DISPATCH(dtype, groupnorm_bwd_op<float>(gout, y, gamma, beta, dy, dgamma, dbeta, N, C, H, W, pool != 0, eps, workspace, st),
            groupnorm_bwd_op<bf16_t>(gout, y, gamma, beta, dy, dgamma, dbeta, N, C, H, W, pool != 0, eps, workspace, st));
+}
+
+int64_t mmskin_groupnorm8_relu_gap_workspace_bytes(int N, int C, int H, int W, int groups, int pool) {
+  if (gn8_check(N, C, H, W, groups, pool != 0, "groupnorm8_relu_gap_workspace_bytes")) return -1;
+  return ws_bytes<GroupNormGapWs<float>>(N, C, H, W);
+}
+int mmskin_groupnorm8_relu_gap_forward(const float* y, const float* gamma, const float* beta, float* feat, float* mean, float* rstd, int N, int C,
+                                       int H, int W, int groups, int pool, float eps, int dtype, void* workspace, void* stream) {
+  if (int rc = gn8_check(N, C, H, W, groups, pool != 0, "groupnorm8_relu_gap_forward")) return rc;
+  ARG_CHECK(y && gamma && beta && feat && workspace, "groupnorm8_relu_gap_forward: null argument");
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype, groupnorm_gap_fwd_op<float>(y, gamma, beta, feat, mean, rstd, N, C, H, W, pool != 0, eps, workspace, st),
+           groupnorm_gap_fwd_op<bf16_t>(y, gamma, beta, feat, mean, rstd, N, C, H, W, pool != 0, eps, workspace, st));
+}
+int mmskin_groupnorm8_relu_gap_backward(const float* dfeat, const float* y, const float* gamma, const float* beta, float* dy, float* dgamma,
+                                        float* dbeta, int N, int C, int H, int W, int groups, int pool, float eps, int dtype, void* workspace,
+                                        void* stream) {
+  if (int rc = gn8_check(N, C, H, W, groups, pool != 0, "groupnorm8_relu_gap_backward")) return rc;
+  ARG_CHECK(dfeat && y && gamma && beta && dy && workspace, "groupnorm8_relu_gap_backward: null argument");
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype, groupnorm_gap_bwd_op<float>(dfeat, y, gamma, beta, dy, dgamma, dbeta, N, C, H, W, pool != 0, eps, workspace, st),
+           groupnorm_gap_bwd_op<bf16_t>(dfeat, y, gamma, beta, dy, dgamma, dbeta, N, C, H, W, pool != 0, eps, workspace, st));
 }
 
 }  // extern "C"

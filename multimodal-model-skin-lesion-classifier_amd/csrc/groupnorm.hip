@@ -12,6 +12,10 @@
 // the argmax bytes on the fly.  Pass 1 leaves per-workgroup per-channel sums of dz and dz * xhat (one sample per workgroup, so the per-(sample,
 // group) sums of dz * gamma and dz * gamma * xhat follow from them); dgamma / dbeta go through the fp64 column reducer (bias_grad_finalize);
 // pass 2 writes dy = rstd * (gamma * dz - (S1 + xhat * S2) / m) once.
+// Trunk tail: the last activation's one consumer is AdaptiveAvgPool2d(1), so gn8_relu_gap_apply reduces relu(...) (or its 2x2 maxima)
+// straight to feat[n][c] through per-workgroup partial rows and a fixed-order combine, and gn8_relu_gap_backward runs the same two backward
+// passes with the gradient dfeat[n][c] / (OH * OW) formed in registers (with a pool: at the window's argmax, recomputed from y).  Neither z,
+// nor the pooled tensor, nor argmax bytes, nor a gradient tensor exist for that layer.
 #include "ops_internal.h"
 
 namespace {
@@ -129,7 +133,29 @@ __global__ __launch_bounds__(EW_BLOCK) void gn_relu_apply_kernel(const T* __rest
   }
 }
 
-// one thread per pooled chunk: the four taps' activations, their maximum and its tap (first maximum, row-major; a NaN wins)
+// The activations of the four taps of the 2x2 window whose first tap is at p00, their maximum and its tap (first maximum, row-major; a NaN
+// wins): the one place the pool's decision is made, for the pooled forward, the fused tail and the tail's backward, which recomputes it.
+template <typename T>
+__device__ __forceinline__ void gn_window_max(const T* __restrict__ p00, int W, int C, float m, float r, const float (&ga)[DT<T>::EPC],
+                                              const float (&be)[DT<T>::EPC], Chunk<T>& best, uint8_t (&bi)[DT<T>::EPC]) {
+  constexpr int EPC = DT<T>::EPC;
+  Chunk<T> v[4];
+  v[0].load(p00); v[1].load(p00 + C); v[2].load(p00 + (size_t)W * C); v[3].load(p00 + (size_t)W * C + C);
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) v[k].v[e] = relu_keep_nan(gn_pre((v[k].v[e] - m) * r, ga[e], be[e]));
+  best = v[0];
+#pragma unroll
+  for (int e = 0; e < EPC; ++e) bi[e] = 0;
+#pragma unroll
+  for (int k = 1; k < 4; ++k)
+#pragma unroll
+    for (int e = 0; e < EPC; ++e)
+      if (v[k].v[e] > best.v[e] || v[k].v[e] != v[k].v[e]) { best.v[e] = v[k].v[e]; bi[e] = (uint8_t)k; }
+}
+
+// one thread per pooled chunk
 template <typename T>
 __global__ __launch_bounds__(EW_BLOCK) void gn_relu_pool_kernel(const T* __restrict__ y, const float* __restrict__ mean,
                                                                 const float* __restrict__ rstd, const float* __restrict__ gamma,
@@ -144,62 +170,131 @@ __global__ __launch_bounds__(EW_BLOCK) void gn_relu_pool_kernel(const T* __restr
     const int ph = (int)(t % PH);
     const size_t n = t / PH;
     const float m = mean[n * GN_GROUPS + c0 / cpg], r = rstd[n * GN_GROUPS + c0 / cpg];
-    const T* p00 = y + ((n * H + 2 * ph) * W + 2 * pw) * C + c0;
-    Chunk<T> v[4];
-    v[0].load(p00); v[1].load(p00 + C); v[2].load(p00 + (size_t)W * C); v[3].load(p00 + (size_t)W * C + C);
     float ga[EPC], be[EPC];
 #pragma unroll
     for (int e = 0; e < EPC; ++e) { ga[e] = gamma[c0 + e]; be[e] = beta[c0 + e]; }
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) v[k].v[e] = relu_keep_nan(gn_pre((v[k].v[e] - m) * r, ga[e], be[e]));
-    Chunk<T> best = v[0];
+    Chunk<T> best;
     uint8_t bi[EPC];
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) bi[e] = 0;
-#pragma unroll
-    for (int k = 1; k < 4; ++k)
-#pragma unroll
-      for (int e = 0; e < EPC; ++e)
-        if (v[k].v[e] > best.v[e] || v[k].v[e] != v[k].v[e]) { best.v[e] = v[k].v[e]; bi[e] = (uint8_t)k; }
+    gn_window_max<T>(y + ((n * H + 2 * ph) * W + 2 * pw) * C + c0, W, C, m, r, ga, be, best, bi);
     best.store(pooled + i * EPC);
 #pragma unroll
     for (int e = 0; e < EPC; ++e) idx[i * EPC + e] = bi[e];
   }
 }
 
-// The gradient that reaches z at input pixel (n, h, w), chunk column cc: gout itself (idx == nullptr), or the pooled gradient where this
-// pixel is its window's argmax (zero elsewhere, and in the row / column an odd extent leaves outside every window).
+// The fused tail, forward: a workgroup owns a run of (pooled) pixels of one sample, as in the statistics kernel; thread (row lane, chunk
+// column) sums its activations in fp32, the row lanes are combined through LDS in index order: partial[(n * nblk + blk)][C].
 template <typename T>
-__device__ __forceinline__ void gn_grad_at(const T* __restrict__ gout, const uint8_t* __restrict__ idx, size_t n, int h, int w, int H, int W,
-                                           int CPR, int cc, Chunk<T>& g) {
+__global__ __launch_bounds__(GN_BLOCK) void gn_relu_gap_kernel(const T* __restrict__ y, const float* __restrict__ mean,
+                                                               const float* __restrict__ rstd, const float* __restrict__ gamma,
+                                                               const float* __restrict__ beta, int H, int W, int C, int CPR, int RL, int PB,
+                                                               int pool, float* __restrict__ partial) {
   constexpr int EPC = DT<T>::EPC;
-  if (!idx) {
-    g.load(gout + (((n * H + h) * W + w) * CPR + cc) * EPC);
-    return;
+  __shared__ float red[GN_BLOCK * EPC];   // [RL][C]
+  const int tid = threadIdx.x, cc = tid % CPR, ry = tid / CPR, c0 = cc * EPC;
+  const int OW = pool ? W / 2 : W, OHW = (pool ? H / 2 : H) * OW;
+  const int n = blockIdx.y, p0 = blockIdx.x * PB, p1 = min(OHW, p0 + PB);
+  if (ry < RL) {
+    const int grp = c0 / (C / GN_GROUPS);
+    const float m = mean[n * GN_GROUPS + grp], r = rstd[n * GN_GROUPS + grp];
+    float ga[EPC], be[EPC], acc[EPC];
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) { ga[e] = gamma[c0 + e]; be[e] = beta[c0 + e]; acc[e] = 0.f; }
+    const T* base = y + (size_t)n * H * W * C + c0;
+    for (int p = p0 + ry; p < p1; p += RL) {
+      Chunk<T> v;
+      if (pool) {
+        const int ph = p / OW, pw = p - ph * OW;
+        uint8_t bi[EPC];
+        gn_window_max<T>(base + ((size_t)(2 * ph) * W + 2 * pw) * C, W, C, m, r, ga, be, v, bi);
+      } else {
+        v.load(base + (size_t)p * C);
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) v.v[e] = relu_keep_nan(gn_pre((v.v[e] - m) * r, ga[e], be[e]));
+      }
+#pragma unroll
+      for (int e = 0; e < EPC; ++e) acc[e] += v.v[e];
+    }
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) red[ry * C + c0 + e] = acc[e];
   }
-  const int PH = H / 2, PW = W / 2, ph = h >> 1, pw = w >> 1;
+  __syncthreads();
+  float* out = partial + ((size_t)n * gridDim.x + blockIdx.x) * C;
+  for (int c = tid; c < C; c += GN_BLOCK) {
+    float s = 0.f;
+    for (int r = 0; r < RL; ++r) s += red[r * C + c];
+    out[c] = s;
+  }
+}
+
+// feat[n][c] = the workgroups' partial sums of (n, c) in index order (fp64) / pixels
+__global__ void gn_gap_finalize_kernel(const float* __restrict__ partial, int NC, int C, int nblk, double inv_cnt, float* __restrict__ feat) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= NC) return;
+  const int n = i / C, c = i - n * C;
+  double s = 0.0;
+  for (int b = 0; b < nblk; ++b) s += (double)partial[((size_t)n * nblk + b) * C + c];
+  feat[i] = (float)(s * inv_cnt);
+}
+
+// Where the gradient at z comes from.  Stored (GAP false): gout is the gradient at z (idx == nullptr) or at the pooled tensor, routed through
+// its argmax bytes.  Trunk tail (GAP true): dfeat[n][c] * inv_cnt at every pixel, or with a pool at each window's argmax, recomputed from y.
+template <typename T>
+struct GnGrad {
+  const T* gout;
+  const uint8_t* idx;
+  const float* dfeat;
+  float inv_cnt;
+  int pool;
+};
+
+// The gradient that reaches z at input pixel (n, h, w), chunk column cc (zero off the argmax, and in the row / column an odd extent leaves
+// outside every window).  m, r, ga, be: the thread's statistics and affine parameters (GAP with a pool evaluates the window's activations).
+template <typename T, bool GAP>
+__device__ __forceinline__ void gn_grad_at(const GnGrad<T>& s, const T* __restrict__ y, size_t n, int h, int w, int H, int W, int CPR, int cc,
+                                           float m, float r, const float (&ga)[DT<T>::EPC], const float (&be)[DT<T>::EPC], Chunk<T>& g) {
+  constexpr int EPC = DT<T>::EPC;
+  const int PH = H / 2, PW = W / 2, ph = h >> 1, pw = w >> 1, tap = (h & 1) * 2 + (w & 1);
+  if constexpr (GAP) {
+    const int C = CPR * EPC;
 #pragma unroll
-  for (int e = 0; e < EPC; ++e) g.v[e] = 0.f;
-  if (ph < PH && pw < PW) {
-    const size_t po = (((n * PH + ph) * PW + pw) * CPR + cc) * EPC;
-    const int tap = (h & 1) * 2 + (w & 1);
-    Chunk<T> t;
-    t.load(gout + po);
-    uint32_t taps[EPC / 4];   // po is a multiple of EPC: the chunk's argmax bytes are EPC / 4 aligned words
+    for (int e = 0; e < EPC; ++e) g.v[e] = s.dfeat[n * C + cc * EPC + e] * s.inv_cnt;
+    if (!s.pool) return;
+    if (ph < PH && pw < PW) {
+      Chunk<T> best;
+      uint8_t bi[EPC];
+      gn_window_max<T>(y + (((n * H + 2 * ph) * W + 2 * pw) * CPR + cc) * EPC, W, C, m, r, ga, be, best, bi);
 #pragma unroll
-    for (int j = 0; j < EPC / 4; ++j) taps[j] = *reinterpret_cast<const uint32_t*>(idx + po + 4 * j);
+      for (int e = 0; e < EPC; ++e)
+        if ((int)bi[e] != tap) g.v[e] = 0.f;
+    } else {
 #pragma unroll
-    for (int e = 0; e < EPC; ++e)
-      if ((int)((taps[e >> 2] >> (8 * (e & 3))) & 0xffu) == tap) g.v[e] = t.v[e];
+      for (int e = 0; e < EPC; ++e) g.v[e] = 0.f;
+    }
+  } else {
+    if (!s.idx) {
+      g.load(s.gout + (((n * H + h) * W + w) * CPR + cc) * EPC);
+      return;
+    }
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) g.v[e] = 0.f;
+    if (ph < PH && pw < PW) {
+      const size_t po = (((n * PH + ph) * PW + pw) * CPR + cc) * EPC;
+      Chunk<T> t;
+      t.load(s.gout + po);
+      uint32_t taps[EPC / 4];   // po is a multiple of EPC: the chunk's argmax bytes are EPC / 4 aligned words
+#pragma unroll
+      for (int j = 0; j < EPC / 4; ++j) taps[j] = *reinterpret_cast<const uint32_t*>(s.idx + po + 4 * j);
+#pragma unroll
+      for (int e = 0; e < EPC; ++e)
+        if ((int)((taps[e >> 2] >> (8 * (e & 3))) & 0xffu) == tap) g.v[e] = t.v[e];
+    }
   }
 }
 
 // pass 1: partial[(n * nblk + blk)][0][C] = sum dz, [1][C] = sum dz * xhat over the workgroup's pixels of sample n
-template <typename T>
-__global__ __launch_bounds__(GN_BLOCK) void gn_bwd_reduce_kernel(const T* __restrict__ gout, const uint8_t* __restrict__ idx,
-                                                                 const T* __restrict__ y, const float* __restrict__ mean,
+template <typename T, bool GAP>
+__global__ __launch_bounds__(GN_BLOCK) void gn_bwd_reduce_kernel(const GnGrad<T> src, const T* __restrict__ y, const float* __restrict__ mean,
                                                                  const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                                  const float* __restrict__ beta, int H, int W, int C, int CPR, int RL, int PB,
                                                                  float* __restrict__ partial) {
@@ -221,7 +316,7 @@ __global__ __launch_bounds__(GN_BLOCK) void gn_bwd_reduce_kernel(const T* __rest
       const int h = p / W, w = p - h * W;
       Chunk<T> v, g;
       v.load(y + ((size_t)n * HW + p) * C + c0);
-      gn_grad_at<T>(gout, idx, (size_t)n, h, w, H, W, CPR, cc, g);
+      gn_grad_at<T, GAP>(src, y, (size_t)n, h, w, H, W, CPR, cc, m, r, ga, be, g);
 #pragma unroll
       for (int e = 0; e < EPC; ++e) {
         const float xh = (v.v[e] - m) * r;
@@ -267,9 +362,8 @@ __global__ __launch_bounds__(64) void gn_group_sums_kernel(const float* __restri
 }
 
 // pass 2: dy = rstd * (gamma * dz - (S1 + xhat * S2) / m), one thread per input chunk
-template <typename T>
-__global__ __launch_bounds__(EW_BLOCK) void gn_bwd_apply_kernel(const T* __restrict__ gout, const uint8_t* __restrict__ idx,
-                                                                const T* __restrict__ y, const float* __restrict__ mean,
+template <typename T, bool GAP>
+__global__ __launch_bounds__(EW_BLOCK) void gn_bwd_apply_kernel(const GnGrad<T> src, const T* __restrict__ y, const float* __restrict__ mean,
                                                                 const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                                 const float* __restrict__ beta, const float* __restrict__ sums, int H, int W,
                                                                 int C, int CPR, float inv_m, T* __restrict__ dy, size_t nchunks) {
@@ -283,14 +377,17 @@ __global__ __launch_bounds__(EW_BLOCK) void gn_bwd_apply_kernel(const T* __restr
     const size_t n = t / H;
     const size_t sg = n * GN_GROUPS + c0 / cpg;
     const float m = mean[sg], r = rstd[sg], S1 = sums[2 * sg], S2 = sums[2 * sg + 1];
+    float ga[EPC], be[EPC];
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) { ga[e] = gamma[c0 + e]; be[e] = beta[c0 + e]; }
     Chunk<T> v, g;
     v.load(y + i * EPC);
-    gn_grad_at<T>(gout, idx, n, h, w, H, W, CPR, cc, g);
+    gn_grad_at<T, GAP>(src, y, n, h, w, H, W, CPR, cc, m, r, ga, be, g);
 #pragma unroll
     for (int e = 0; e < EPC; ++e) {
-      const float xh = (v.v[e] - m) * r, ga = gamma[c0 + e];
-      const float dz = gn_pre(xh, ga, beta[c0 + e]) > 0.f ? g.v[e] : 0.f;
-      v.v[e] = r * (ga * dz - fmaf(xh, S2, S1) * inv_m);
+      const float xh = (v.v[e] - m) * r;
+      const float dz = gn_pre(xh, ga[e], be[e]) > 0.f ? g.v[e] : 0.f;
+      v.v[e] = r * (ga[e] * dz - fmaf(xh, S2, S1) * inv_m);
     }
     v.store(dy + i * EPC);
   }
@@ -344,12 +441,27 @@ int gn8_relu_pool_apply(const T* y, const float* mean, const float* rstd, const 
 }
 
 template <typename T>
-int gn8_relu_backward(const T* gout, const uint8_t* idx, const T* y, const float* mean, const float* rstd, const float* gamma, const float* beta,
-                      int N, int H, int W, int C, float* partial, float* sums, ColScratch red, float* dgamma, float* dbeta, T* dy,
-                      hipStream_t st) {
+int gn8_relu_gap_apply(const T* y, const float* mean, const float* rstd, const float* gamma, const float* beta, int N, int H, int W, int C,
+                       bool pool, float* partial, float* feat, hipStream_t st) {
+  ARG_CHECK(!pool || (H >= 2 && W >= 2), "gn8_relu_gap_apply: map %dx%d smaller than the window", H, W);
+  const int OHW = pool ? (H / 2) * (W / 2) : H * W;
+  const GnGeom g = gn_geom(OHW, C, DT<T>::EPC);
+  hipLaunchKernelGGL(gn_relu_gap_kernel<T>, dim3(g.nblk, N), dim3(GN_BLOCK), 0, st, y, mean, rstd, gamma, beta, H, W, C, g.CPR, g.RL, g.PB,
+                     (int)pool, partial);
+  HIP_CHECK_RET(hipGetLastError());
+  hipLaunchKernelGGL(gn_gap_finalize_kernel, dim3(ceil_div(N * C, 256)), dim3(256), 0, st, partial, N * C, C, g.nblk, 1.0 / (double)OHW, feat);
+  HIP_CHECK_RET(hipGetLastError());
+  return MMSKIN_OK;
+}
+
+namespace {
+// the backward of both gradient sources: pass 1, the group sums, dgamma / dbeta through the column reducer, pass 2
+template <typename T, bool GAP>
+int gn_backward_launch(const GnGrad<T>& src, const T* y, const float* mean, const float* rstd, const float* gamma, const float* beta, int N, int H,
+                       int W, int C, float* partial, float* sums, ColScratch red, float* dgamma, float* dbeta, T* dy, hipStream_t st) {
   constexpr int EPC = DT<T>::EPC;
   const GnGeom g = gn_geom(H * W, C, EPC);
-  hipLaunchKernelGGL(gn_bwd_reduce_kernel<T>, dim3(g.nblk, N), dim3(GN_BLOCK), 0, st, gout, idx, y, mean, rstd, gamma, beta, H, W, C, g.CPR, g.RL,
+  hipLaunchKernelGGL((gn_bwd_reduce_kernel<T, GAP>), dim3(g.nblk, N), dim3(GN_BLOCK), 0, st, src, y, mean, rstd, gamma, beta, H, W, C, g.CPR, g.RL,
                      g.PB, partial);
   HIP_CHECK_RET(hipGetLastError());
   hipLaunchKernelGGL(gn_group_sums_kernel, dim3(N * GN_GROUPS), dim3(64), 0, st, partial, gamma, g.nblk, C, sums);
@@ -358,10 +470,29 @@ int gn8_relu_backward(const T* gout, const uint8_t* idx, const T* y, const float
   if (int rc = bias_grad_finalize(partial + C, N * g.nblk, 2 * C, C, dgamma, red, st)) return rc;
   const size_t nch = (size_t)N * H * W * (C / EPC);
   const float inv_m = 1.f / ((float)(H * W) * (float)(C / GN_GROUPS));
-  hipLaunchKernelGGL(gn_bwd_apply_kernel<T>, dim3(ew_grid(nch)), dim3(EW_BLOCK), 0, st, gout, idx, y, mean, rstd, gamma, beta, sums, H, W, C,
+  hipLaunchKernelGGL((gn_bwd_apply_kernel<T, GAP>), dim3(ew_grid(nch)), dim3(EW_BLOCK), 0, st, src, y, mean, rstd, gamma, beta, sums, H, W, C,
                      C / EPC, inv_m, dy, nch);
   HIP_CHECK_RET(hipGetLastError());
   return MMSKIN_OK;
+}
+}  // namespace
+
+template <typename T>
+int gn8_relu_backward(const T* gout, const uint8_t* idx, const T* y, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                      int N, int H, int W, int C, float* partial, float* sums, ColScratch red, float* dgamma, float* dbeta, T* dy,
+                      hipStream_t st) {
+  const GnGrad<T> src = {gout, idx, nullptr, 0.f, idx != nullptr};
+  return gn_backward_launch<T, false>(src, y, mean, rstd, gamma, beta, N, H, W, C, partial, sums, red, dgamma, dbeta, dy, st);
+}
+
+template <typename T>
+int gn8_relu_gap_backward(const float* dfeat, const T* y, const float* mean, const float* rstd, const float* gamma, const float* beta, int N, int H,
+                          int W, int C, bool pool, float* partial, float* sums, ColScratch red, float* dgamma, float* dbeta, T* dy,
+                          hipStream_t st) {
+  ARG_CHECK(!pool || (H >= 2 && W >= 2), "gn8_relu_gap_backward: map %dx%d smaller than the window", H, W);
+  const int OHW = pool ? (H / 2) * (W / 2) : H * W;
+  const GnGrad<T> src = {nullptr, nullptr, dfeat, 1.f / (float)OHW, (int)pool};
+  return gn_backward_launch<T, true>(src, y, mean, rstd, gamma, beta, N, H, W, C, partial, sums, red, dgamma, dbeta, dy, st);
 }
 
 #define INSTANTIATE(T)                                                                                                                          \
@@ -370,6 +501,10 @@ int gn8_relu_backward(const T* gout, const uint8_t* idx, const T* y, const float
   template int gn8_relu_pool_apply<T>(const T*, const float*, const float*, const float*, const float*, int, int, int, int, T*, uint8_t*,       \
                                       hipStream_t);                                                                                             \
   template int gn8_relu_backward<T>(const T*, const uint8_t*, const T*, const float*, const float*, const float*, const float*, int, int, int,  \
-                                    int, float*, float*, ColScratch, float*, float*, T*, hipStream_t);
+                                    int, float*, float*, ColScratch, float*, float*, T*, hipStream_t);                                          \
+  template int gn8_relu_gap_apply<T>(const T*, const float*, const float*, const float*, const float*, int, int, int, int, bool, float*, float*, \
+                                     hipStream_t);                                                                                              \
+  template int gn8_relu_gap_backward<T>(const float*, const T*, const float*, const float*, const float*, const float*, int, int, int, int,     \
+                                        bool, float*, float*, ColScratch, float*, float*, T*, hipStream_t);
 INSTANTIATE(float)
 INSTANTIATE(bf16_t)

@@ -226,6 +226,18 @@ template <typename T>
 int gn8_relu_backward(const T* gout, const uint8_t* idx, const T* y, const float* mean, const float* rstd, const float* gamma, const float* beta,
                       int N, int H, int W, int C, float* partial, float* sums, ColScratch red, float* dgamma, float* dbeta, T* dy,
                       hipStream_t st);
+// The trunk's tail, where AdaptiveAvgPool2d(1) is the activation's only consumer: feat[n][c] (fp32) = mean over the map (pool: over the floor-pooled
+// map, gn8_relu_pool_apply's taps) of relu(gamma * (y - mean) * rstd + beta).  Nothing else is stored.  partial: gn8_bwd_partial_bytes();
+// per-workgroup rows combined in index order, no atomics.
+template <typename T>
+int gn8_relu_gap_apply(const T* y, const float* mean, const float* rstd, const float* gamma, const float* beta, int N, int H, int W, int C,
+                       bool pool, float* partial, float* feat, hipStream_t st);
+// gn8_relu_backward with the gradient dfeat[n][c] / (OH * OW) formed in registers; with a pool it reaches each window's argmax, recomputed
+// from y by the forward's own expression and tie-break.
+template <typename T>
+int gn8_relu_gap_backward(const float* dfeat, const T* y, const float* mean, const float* rstd, const float* gamma, const float* beta, int N, int H,
+                          int W, int C, bool pool, float* partial, float* sums, ColScratch red, float* dgamma, float* dbeta, T* dy,
+                          hipStream_t st);
 
 // Grad-CAM: dx[n][c][hw] (NCHW fp32) = dfeat[n][c] / HW * (y[n][hw][c] > 0) * scale[c]  -- the gradient of the pooled
 // features w.r.t. the raw output of the last conv under eval-mode BatchNorm (y = relu(x*scale + shift + skip), NHWC T)

@@ -1,5 +1,5 @@
 // Shared scaffolding of the image-encoder plan executors (backbone.hip: ResNet, densenet.hip: DenseNet, vgg.hip: VGG,
-// mbconv.hip: MobileNet-V2 / EfficientNet).
+// mbconv.hip: MobileNet-V2 / EfficientNet, dynamic_cnn.hip: the NAS DynamicCNN trunk).
 // A plan is built once per (architecture, batch, H, W, dtype): it fixes the flat parameter / buffer
 // layout (torchvision named_parameters() order), the workspace carve-up and the launch sequence, so
 // that one C-ABI call runs a whole forward or backward on the caller's stream.
@@ -513,5 +513,6 @@ int dense_transition_backward(DenseRun<T>& r, DBlock& pb, DTrans& tr, const T* d
 PlanBase* make_resnet_plan(int arch, int N, int H, int W, int dtype, int* rc);
 PlanBase* make_densenet_plan(int N, int H, int W, int dtype, bool feature_map, int* rc);
 PlanBase* make_vgg_plan(int N, int H, int W, int dtype, int* rc);
+PlanBase* make_dynamic_cnn_plan(const char* arch, int N, int H, int W, int dtype, int* rc);   // arch: the dynamic-cnn/... string (mmskin.h)
 PlanBase* make_mobilenet_plan(int N, int H, int W, int dtype, int* rc);
 PlanBase* make_efficientnet_plan(int variant, int N, int H, int W, int dtype, int* rc);

@@ -110,6 +110,9 @@ _SIGNATURES = {
     "mmskin_groupnorm8_relu_workspace_bytes": (_i64, [_i] * 6),
     "mmskin_groupnorm8_relu_forward": (_i, [_P] * 7 + [_i] * 6 + [_f, _i, _P, _P]),
     "mmskin_groupnorm8_relu_backward": (_i, [_P] * 7 + [_i] * 6 + [_f, _i, _P, _P]),
+    "mmskin_groupnorm8_relu_gap_workspace_bytes": (_i64, [_i] * 6),
+    "mmskin_groupnorm8_relu_gap_forward": (_i, [_P] * 6 + [_i] * 6 + [_f, _i, _P, _P]),
+    "mmskin_groupnorm8_relu_gap_backward": (_i, [_P] * 7 + [_i] * 6 + [_f, _i, _P, _P]),
     "mmskin_adaptive_avgpool_workspace_bytes": (_i64, [_i] * 4),
     "mmskin_adaptive_avgpool_forward": (_i, [_P] * 2 + [_i] * 5 + [_P, _P]),
     "mmskin_adaptive_avgpool_backward": (_i, [_P] * 2 + [_i] * 5 + [_P, _P]),

@@ -542,6 +542,48 @@ class HipVGGFeatures(_FlatBackbone):
         self._init_flat(compute_dtype)
 
 
+def dynamic_cnn_arch(filters, layers_per_block, use_pooling, kernel_size=3):
+    """The arch string of a DynamicCNN trunk (grammar: include/mmskin.h, next to mmskin_backbone_create)."""
+    return "dynamic-cnn/%s/l%d/p%d/k%d" % ("-".join(str(int(f)) for f in filters), int(layers_per_block), int(bool(use_pooling)),
+                                             int(kernel_size))
+
+
+class HipDynamicCNNFeatures(_FlatBackbone):
+    """The reference's NAS trunk (dynamicMultimodalmodel.py:45-71: `conv_block` followed by `global_pool`) on the plan executor
+    csrc/dynamic_cnn.hip: [Conv2d(k, pad k//2, no bias) -> GroupNorm(8, C) -> ReLU] x layers_per_block per filter, MaxPool2d(2, 2) per
+    block with use_pooling.  Children carry the reference Sequential's indices ("0", "1", "2", ...), so keys read `0.weight`,
+    `1.weight`, `1.bias`, ...; default torch initialisation in the reference's construction order.  Returns the globally pooled
+    features [N, filters[-1]] fp32.  What the plan refuses (kernel_size != 3, a filter that is not a multiple of 64, filters[0] != 64,
+    ...) raises MMSkinError when the first plan is made."""
+
+    def __init__(self, filters, layers_per_block, use_pooling, kernel_size=3, in_channels=3, compute_dtype=None):
+        super().__init__()
+        if in_channels != 3:
+            raise _lib.MMSkinError(f"HipDynamicCNNFeatures: in_channels = {in_channels} is not supported (RGB images only)")
+        filters, k = [int(f) for f in filters], int(kernel_size)
+        if not filters or int(layers_per_block) < 1:
+            raise _lib.MMSkinError("HipDynamicCNNFeatures: filters is empty or layers_per_block < 1: the trunk has no layer")
+        self.arch = dynamic_cnn_arch(filters, layers_per_block, use_pooling, k)
+        cin, idx = in_channels, 0
+        for f in filters:
+            for _ in range(int(layers_per_block)):
+                self.add_module(str(idx), nn.Conv2d(cin, f, kernel_size=k, padding=k // 2, bias=False))
+                self.add_module(str(idx + 1), nn.GroupNorm(8, f))
+                self.add_module(str(idx + 2), nn.ReLU(inplace=True))
+                cin, idx = f, idx + 3
+            if use_pooling:
+                self.add_module(str(idx), nn.MaxPool2d(2, 2))
+                idx += 1
+        self.num_features = cin
+        self._init_flat(compute_dtype)
+
+    def __len__(self):
+        return len(self._modules)
+
+    def __getitem__(self, i):   # conv_block[i], as on the reference's nn.Sequential
+        return list(self._modules.values())[i]
+
+
 class HipVGG16(nn.Module):
     """torchvision vgg16 with the last classifier layer dropped (loadImageModelClassifier.py:77-81) -> 4096 features."""
 
