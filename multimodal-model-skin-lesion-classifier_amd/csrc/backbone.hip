@@ -147,14 +147,11 @@ int build_plan(Plan& p) {
   std::vector<StageDesc> table;
   int64_t wf = 0, wd = 0;
   for (Unit& u : p.units) {
-    StageDesc d = {};
-    d.src_off = u.w_off;
-    d.Cout = u.s.Cout; d.Cin = u.s.Cin; d.taps = u.s.kh * u.s.kw; d.stem = u.stem ? 1 : 0;
-    u.wf_off = wf; u.wd_off = wd;
-    d.fwd_off = wf; d.dgrad_off = wd;
-    int64_t n = u.stem ? 64 * 256 : (int64_t)d.Cout * d.Cin * d.taps;
-    wf += n;
-    if (!u.stem) wd += n;
+    if (!u.stem) { stage_append(table, u.w_off, u.s.Cout, u.s.Cin, u.s.kh * u.s.kw, 0, 0, wf, wd, p.max_stage_elems, u.wf_off, u.wd_off); continue; }
+    StageDesc d = {};   // the stem row: a 64 x 256 forward slot (virtual [64][8][32]) and no data-gradient slot
+    d.src_off = u.w_off; d.Cout = u.s.Cout; d.Cin = u.s.Cin; d.taps = u.s.kh * u.s.kw; d.stem = 1;
+    u.wf_off = d.fwd_off = wf; u.wd_off = d.dgrad_off = wd;
+    wf += 64 * 256;
     if (d.Cout * d.Cin * d.taps > p.max_stage_elems) p.max_stage_elems = d.Cout * d.Cin * d.taps;
     table.push_back(d);
   }
@@ -761,12 +758,10 @@ struct ResNetBackward {
 
 int Plan::forward(const void* image, const float* norm6, const float* params, float* buffers, unsigned char* ws,
                   float* features, bool training, hipStream_t st) {
-  if (dtype == 1) return forward_impl<bf16_t>(*this, image, norm6, params, buffers, ws, features, training, st);
-  return forward_impl<float>(*this, image, norm6, params, buffers, ws, features, training, st);
+  return by_dtype(dtype, [&](auto t) { return forward_impl<decltype(t)>(*this, image, norm6, params, buffers, ws, features, training, st); });
 }
 int Plan::backward(const float* dfeat, const float* params, unsigned char* ws, float* grads, hipStream_t st) {
-  if (dtype == 1) return ResNetBackward<bf16_t>(*this, params, ws, grads, st).run(dfeat);
-  return ResNetBackward<float>(*this, params, ws, grads, st).run(dfeat);
+  return by_dtype(dtype, [&](auto t) { return ResNetBackward<decltype(t)>(*this, params, ws, grads, st).run(dfeat); });
 }
 // torchvision's last nn.Conv2d in module order is the final block's last conv (layerN.k.conv3 / conv2)
 int Plan::last_conv_shape(int* C, int* OH, int* OW) const {
@@ -812,11 +807,7 @@ int Plan::unit_flags(int index, int* flags) const {
 }  // namespace
 
 PlanBase* make_resnet_plan(int arch, int N, int H, int W, int dtype, int* rc) {
-  Plan* p = new Plan();
-  p->arch = arch; p->N = N; p->H = H; p->W = W; p->dtype = dtype;
-  *rc = build_plan(*p);
-  if (*rc) { delete p; return nullptr; }
-  return p;
+  return make_plan<Plan>(N, H, W, dtype, rc, [arch](Plan& p) { p.arch = arch; return build_plan(p); });
 }
 
 // ------------------------------------------------------------------------------------------ C ABI

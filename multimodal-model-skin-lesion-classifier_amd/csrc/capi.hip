@@ -612,7 +612,7 @@ struct DenseTransWs {
       std::vector<StageDesc> one;
       int64_t wf = 0, wd = 0;
       int max_elems = 0;
-      dense_stage(one, t.w_off, C / 2, C, 1, C / 2, C, wf, wd, max_elems, t.wf, t.wd);   // as build_dense_plan stages a transition
+      stage_append(one, t.w_off, C / 2, C, 1, C / 2, C, wf, wd, max_elems, t.wf, t.wd);   // as build_dense_plan stages a transition
       desc = one[0];
     }
     const ConvShape ct = {N, H, W, C, C / 2, 1, 1, 1, 0};
@@ -1242,7 +1242,7 @@ static bool wgrad_export_geom(const ConvShape& s, WgradArgs& g) {
     return true;
   }
   if (s.Cin == 3 && s.Cout == 64 && s.kh == 3 && s.kw == 3 && s.pad == 1 && (s.stride == 1 || s.stride == 2)) {
-    g = wgrad_geom_first(s.N, s.OH(), s.OW(), s.H + 2, (s.W + 4 + 1) / 2 * 2, s.stride);
+    g = wgrad_geom_first(FirstGeom(s.N, s.H, s.W, s.stride));
     return true;
   }
   g = wgrad_geom_conv(s);
@@ -1311,7 +1311,7 @@ int mmskin_conv_route(int op, int N, int Cin, int H, int W, int Cout, int kh, in
       rc = conv_route_stem(a, elem_bytes, sg.Hp, sg.Wp, r);
     } else {                // the 3-channel 3x3 / pad 1 first conv (stride 1 | 2); flags: statistics, bias, addend, relu
       ARG_CHECK(stride == 1 || stride == 2, "conv_route: first conv stride");
-      a = conv_geom_first(N, (H + 2 - 3) / stride + 1, (W + 2 - 3) / stride + 1, H + 2, (W + 4 + 1) / 2 * 2, stride);
+      a = conv_geom_first(FirstGeom(N, H, W, stride));
       a.in = a.w = set; a.out = set; a.stat_sum = a.stat_sq = stats;
       a.ep_bias = f.bias; a.addend = f.addend; a.ep_relu = f.relu ? 1 : 0;
       rc = conv_gemm_route(a, elem_bytes, r) ? MMSKIN_OK : MMSKIN_ERR_ARG;

@@ -90,7 +90,8 @@ bool conv_gemm_route(const ConvGemmArgs& a, int elem_bytes, ConvRoute& r);
 ConvGemmArgs conv_geom_fwd(const ConvShape& s, int elem_bytes);
 ConvGemmArgs conv_geom_dgrad(const ConvShape& s, int elem_bytes, bool in_place, bool fill_zeros, int k2, unsigned* zero_mask);
 ConvGemmArgs conv_geom_stem(int N, int OH, int OW, int Hp, int Wp);
-ConvGemmArgs conv_geom_first(int N, int OH, int OW, int Hp, int Wp, int stride);
+struct FirstGeom;
+ConvGemmArgs conv_geom_first(const FirstGeom& g);
 
 // wgrad: dW[cout][tap][c] = sum_m dY[m][cout] * gather(in)[m][tap][c]
 struct WgradArgs {
@@ -133,7 +134,7 @@ inline WgradSlab wgrad_slab_at(unsigned char* ws, size_t off, size_t bytes) { re
 // the launch geometries (dy / in / slab left null).  Virtual stem: 8 row taps of 32 elements over the NHWC4 image; virtual first conv: 4 taps over NHWC8.
 WgradArgs wgrad_geom_conv(const ConvShape& s);
 WgradArgs wgrad_geom_stem(int N, int OH, int OW, int Hp, int Wp);
-WgradArgs wgrad_geom_first(int N, int OH, int OW, int Hp, int Wp, int stride);
+WgradArgs wgrad_geom_first(const FirstGeom& g);
 // s: the convolution behind g for true convolutions (the two 3x3 families plan from it), null for the virtual geometries.  Pure: no HIP call,
 // no stream; reads MMSKIN_WGRAD3_BLOCKS once.  false: no family takes the shape.
 bool wgrad_plan(const WgradArgs& g, const ConvShape* s, int elem_bytes, WgradPlan& pl);
@@ -224,17 +225,35 @@ int stem7x7_stat_rows(int N, int OH);
 int launch_stem7x7_fwd(int N, int OH, int OW, int Hp, int Wp, const bf16_t* img4, const bf16_t* wv, bf16_t* out, float* stat_sum, float* stat_sq,
                        hipStream_t st);
 
-// VGG's first conv (3x3 s1 p1, Cin=3) as a virtual conv over the zero-bordered NHWC8 image of pack_nhwc8: one tap
-// per kernel row, each reading 32 contiguous elements (4 pixels x 8 ch; 3 x 3 of them carry weights), plus one
-// all-zero tap so K = 4 x 32 = 128.  wv / dwv are [64][4][32].
+// The 3-channel 3x3 / pad 1 first conv (stride 1: VGG, DynamicCNN; stride 2: MobileNet-V2, EfficientNet) as a virtual conv over the
+// zero-bordered NHWC8 image of pack_nhwc8: one tap per kernel row, each reading 32 contiguous elements (4 pixels x 8 ch; 3 x 3 of them
+// carry weights), plus one all-zero tap so K = 4 x 32 = 128.  wv / dwv are [64][4][32]; narrower convs leave the upper rows zero.
+struct FirstGeom {
+  static constexpr int COUT = 64, K = 128, WV_ELEMS = COUT * K;   // the virtual operand [COUT][K]
+  int N, H, W, stride;
+  int OH, OW;   // conv output
+  int Hp, Wp;   // the padded image: pixel (h, w) at (h + 1, w + 1), the last tap's reach on the right, even width
+  FirstGeom(int n = 0, int h = 0, int w = 0, int s = 1) : N(n), H(h), W(w), stride(s) {
+    OH = (H + 2 - 3) / stride + 1; OW = (W + 2 - 3) / stride + 1;
+    Hp = H + 2; Wp = (W + 4 + 1) / 2 * 2;
+  }
+  size_t rows() const { return (size_t)N * OH * OW; }
+  size_t img8_elems() const { return (size_t)N * Hp * Wp * 8; }
+  ConvShape conv() const { return ConvShape{N, H, W, 3, COUT, 3, 3, stride, 1}; }
+  // what the weight-gradient kernels ask of the output (16-bit reciprocal pixel stepping, wgrad_plan): every plan checks it when it is built
+  int check(const char* who) const {
+    ARG_CHECK(OH <= 240 && OW <= 240, "%s: first conv output height x width %dx%d (input %dx%d, stride %d) too large for the weight-gradient kernel's pixel stepping (240 x 240)",
+              who, OH, OW, H, W, stride);
+    return MMSKIN_OK;
+  }
+};
+// fuse: bias / addend / relu only; stat_sum / stat_sq: optional batch-statistics slabs of ceil(rows / 128) rows
 template <typename T>
-int launch_vgg_first_conv_fwd(int N, int H, int W, int Hp, int Wp, const T* img8, const T* wv, T* out,
-                              const FwdFuse* fuse, hipStream_t st, int stride = 1, float* stat_sum = nullptr,
-                              float* stat_sq = nullptr);
-size_t vgg_first_wgrad_slab_bytes(int N, int H, int W);   // H, W = OUTPUT size
+int launch_first3_conv_fwd(const FirstGeom& g, const T* img8, const T* wv, T* out, const FwdFuse* fuse, hipStream_t st, float* stat_sum = nullptr,
+                           float* stat_sq = nullptr);
+size_t first3_wgrad_slab_bytes(const FirstGeom& g);
 template <typename T>
-int launch_vgg_first_conv_wgrad(int N, int H, int W, int Hp, int Wp, const T* dout, const T* img8, WgradSlab slab,
-                                float* dwv, hipStream_t st, int stride = 1);
+int launch_first3_conv_wgrad(const FirstGeom& g, const T* dout, const T* img8, WgradSlab slab, float* dwv, hipStream_t st);
 
 // 3x3 / stride 1 / pad 1, 64 -> 64 channels at 56 x 56 (ResNet-50 layer1 conv2): all nine taps from one staged input window, weights
 // resident in LDS, one workgroup per image (conv3x3_c64.hip).  conv_route_fwd / conv_route_dgrad route to it when it takes the shape.

@@ -979,9 +979,9 @@ ConvGemmArgs conv_geom_stem(int N, int OH, int OW, int Hp, int Wp) {
   for (int r = 0; r < 8; ++r) { a.cls[0].offy[r] = (int8_t)r; a.cls[0].wtap[r] = (int8_t)r; }
   return a;
 }
-// virtual first conv: one tap per kernel row plus one all-zero tap, 32 elements each (see launch_vgg_first_conv_fwd in conv.h)
-ConvGemmArgs conv_geom_first(int N, int OH, int OW, int Hp, int Wp, int stride) {
-  ConvGemmArgs a = geom_one_class(N, Hp, Wp, 32, 8, 64, 4, stride, stride, OH, OW);
+// virtual first conv: one tap per kernel row plus one all-zero tap, 32 elements each (see FirstGeom in conv.h)
+ConvGemmArgs conv_geom_first(const FirstGeom& g) {
+  ConvGemmArgs a = geom_one_class(g.N, g.Hp, g.Wp, 32, 8, FirstGeom::COUT, 4, g.stride, g.stride, g.OH, g.OW);
   for (int r = 0; r < 4; ++r) { a.cls[0].offy[r] = (int8_t)(r < 3 ? r : 0); a.cls[0].wtap[r] = (int8_t)r; }
   return a;
 }
@@ -1124,10 +1124,9 @@ int launch_stem_conv_fwd(int N, int OH, int OW, int Hp, int Wp, const T* img4, c
 }
 
 template <typename T>
-int launch_vgg_first_conv_fwd(int N, int H, int W, int Hp, int Wp, const T* img8, const T* wv, T* out, const FwdFuse* fuse, hipStream_t st, int stride, float* stat_sum, float* stat_sq) {
-  // H, W: input image size; output = (H + 2 - 3) / stride + 1
-  ARG_CHECK(Hp >= H + 2 && Wp >= W + 4 && (stride == 1 || stride == 2), "first 3x3 conv: padded image too small / stride");
-  ConvGemmArgs a = conv_geom_first(N, (H + 2 - 3) / stride + 1, (W + 2 - 3) / stride + 1, Hp, Wp, stride);
+int launch_first3_conv_fwd(const FirstGeom& g, const T* img8, const T* wv, T* out, const FwdFuse* fuse, hipStream_t st, float* stat_sum, float* stat_sq) {
+  ARG_CHECK(g.stride == 1 || g.stride == 2, "first 3x3 conv: stride %d", g.stride);
+  ConvGemmArgs a = conv_geom_first(g);
   a.in = img8; a.w = wv; a.out = out; a.stat_sum = stat_sum; a.stat_sq = stat_sq;
   if (fuse) { a.ep_bias = fuse->bias; a.addend = fuse->addend; a.ep_relu = fuse->relu ? 1 : 0; }
   ConvRoute r;
@@ -1136,7 +1135,7 @@ int launch_vgg_first_conv_fwd(int N, int H, int W, int Hp, int Wp, const T* img8
 }
 
 #define INST(T)                                                                                      \
-  template int launch_vgg_first_conv_fwd<T>(int, int, int, int, int, const T*, const T*, T*, const FwdFuse*, hipStream_t, int, float*, float*); \
+  template int launch_first3_conv_fwd<T>(const FirstGeom&, const T*, const T*, T*, const FwdFuse*, hipStream_t, float*, float*); \
   template int launch_conv_fwd<T>(const ConvShape&, const T*, const T*, T*, float*, float*, hipStream_t, const FwdFuse*, int*); \
   template int launch_conv_dgrad<T>(const ConvShape&, const T*, const T*, T*, const T*, hipStream_t, DgradFuse*);      \
   template int launch_stem_conv_fwd<T>(int, int, int, int, int, const T*, const T*, T*, float*, float*, hipStream_t, int*);

@@ -82,7 +82,7 @@ int build_dense_plan(DensePlan& p) {
   // ---- staged weights + stage table (stem first: its slot needs zeroed padding taps)
   int64_t wf = 0, wd = 0;
   auto stage = [&](int64_t src, int Cout, int Cin, int taps, int Cop, int Cip, int64_t& wf_off, int64_t& wd_off) {
-    dense_stage(p.table_host, src, Cout, Cin, taps, Cop, Cip, wf, wd, p.max_stage_elems, wf_off, wd_off);
+    stage_append(p.table_host, src, Cout, Cin, taps, Cop, Cip, wf, wd, p.max_stage_elems, wf_off, wd_off);
   };
   {
     StageDesc d = {};
@@ -509,20 +509,14 @@ int dense_backward(DensePlan& p, const float* dfeat, const float* params, unsign
 
 int DensePlan::forward(const void* image, const float* norm6, const float* params, float* buffers, unsigned char* ws,
                        float* features, bool training, hipStream_t st) {
-  if (dtype == 1) return dense_forward<bf16_t>(*this, image, norm6, params, buffers, ws, features, training, st);
-  return dense_forward<float>(*this, image, norm6, params, buffers, ws, features, training, st);
+  return by_dtype(dtype, [&](auto t) { return dense_forward<decltype(t)>(*this, image, norm6, params, buffers, ws, features, training, st); });
 }
 int DensePlan::backward(const float* dfeat, const float* params, unsigned char* ws, float* grads, hipStream_t st) {
-  if (dtype == 1) return dense_backward<bf16_t>(*this, dfeat, params, ws, grads, st);
-  return dense_backward<float>(*this, dfeat, params, ws, grads, st);
+  return by_dtype(dtype, [&](auto t) { return dense_backward<decltype(t)>(*this, dfeat, params, ws, grads, st); });
 }
 
 }  // namespace
 
 PlanBase* make_densenet_plan(int N, int H, int W, int dtype, bool feature_map, int* rc) {
-  DensePlan* p = new DensePlan();
-  p->N = N; p->H = H; p->W = W; p->dtype = dtype; p->fmap = feature_map;
-  *rc = build_dense_plan(*p);
-  if (*rc) { delete p; return nullptr; }
-  return p;
+  return make_plan<DensePlan>(N, H, W, dtype, rc, [feature_map](DensePlan& p) { p.fmap = feature_map; return build_dense_plan(p); });
 }

@@ -8,8 +8,8 @@
 // y, mean and rstd are kept for the backward; the un-pooled z of a pooled layer never exists.  The LAST layer's activation has one consumer,
 // the global average, so gn8_relu_gap_apply reduces it straight to the features and gn8_relu_gap_backward forms its gradient in registers:
 // that layer stores y alone.  Backward per layer: GroupNorm + ReLU (+ pool) backward -> dy, dgamma, dbeta; weight gradient against the
-// layer's input; plain data gradient (the ReLU mask belongs to the GroupNorm backward of the layer below).  The first layer is VGG's virtual
-// first conv over the packed NHWC8 image and has no data gradient.
+// layer's input; plain data gradient (the ReLU mask belongs to the GroupNorm backward of the layer below).  The first layer is the virtual
+// 3-channel first conv over the packed NHWC8 image (FirstGeom) and has no data gradient.
 #include "plan.h"
 
 namespace {
@@ -29,9 +29,10 @@ struct DynamicCnnPlan : PlanBase {
   int layers_per_block = 0, ksize = 0;
   bool pooling = false, fused_tail = true;
   std::vector<DcLayer> layers;
-  int Hp, Wp;                 // padded NHWC8 image
+  FirstGeom fg;               // the first conv (3 -> 64) and its padded NHWC8 image
+  FirstCarve first;
   int fH, fW;                 // spatial size the global average sees
-  size_t off_img8, off_wf, off_wd, off_gnstat, off_partial, off_sums, off_red, off_slab, slab_bytes, off_dwv, off_g[2];
+  size_t off_wf, off_wd, off_gnstat, off_partial, off_sums, off_red, off_slab, slab_bytes, off_g[2];
   int red_C;                  // channels the reduction scratch at off_red was carved for
 
   int forward(const void* image, const float* norm6, const float* params, float* buffers, unsigned char* ws,
@@ -93,7 +94,8 @@ int build_dynamic_cnn_plan(DynamicCnnPlan& p, const char* arch) {
     mmskin_set_error("dynamic-cnn: filters[0] = %d is not supported (the first conv's virtual operand is [64][4][32])", p.filters[0]);
     return MMSKIN_ERR_UNSUPPORTED;
   }
-  ARG_CHECK(p.H <= 240 && p.W <= 240, "dynamic-cnn: height x width %dx%d too large for the weight-gradient kernel's pixel stepping", p.H, p.W);
+  p.fg = FirstGeom(p.N, p.H, p.W, 1);
+  if (int rc = p.fg.check("dynamic-cnn")) return rc;
 
   int cin = 3, h = p.H, w = p.W, idx = 0;
   for (int f : p.filters) {
@@ -117,29 +119,18 @@ int build_dynamic_cnn_plan(DynamicCnnPlan& p, const char* arch) {
   }
   p.fH = h; p.fW = w;
   p.feat_dim = p.filters.back(); p.out_h = 1; p.out_w = 1;
-  p.Hp = p.H + 2; p.Wp = (p.W + 4 + 1) / 2 * 2;
 
-  int64_t wf = 64 * 128, wd = 0;   // slot 0 of wf: the first conv's virtual operand
+  int64_t wf = FirstGeom::WV_ELEMS, wd = 0;   // slot 0 of wf: the first conv's virtual operand
   for (size_t i = 1; i < p.layers.size(); ++i) {
     DcLayer& c = p.layers[i];
-    StageDesc d = {};
-    d.src_off = c.w_off; d.Cout = c.Cout; d.Cin = c.Cin; d.taps = 9;
-    c.wf = wf; c.wd = wd;
-    d.fwd_off = wf; d.dgrad_off = wd;
-    const int64_t n = (int64_t)c.Cout * c.Cin * 9;
-    wf += n; wd += n;
-    if (n > p.max_stage_elems) p.max_stage_elems = (int)n;
-    p.table_host.push_back(d);
+    stage_append(p.table_host, c.w_off, c.Cout, c.Cin, 9, 0, 0, wf, wd, p.max_stage_elems, c.wf, c.wd);
   }
-  p.layers[0].wf = 0;
 
   // the one carve: sizes and lays out the workspace
   const size_t es = p.esz();
-  size_t cur = 0;
-  p.off_img8 = carve(cur, (size_t)p.N * p.Hp * p.Wp * 8 * es);
+  size_t cur = 0, maxact = 0, partial = 0, slab = p.first.image(cur, p.fg, es);
   p.off_wf = carve(cur, (size_t)wf * es);
   p.off_wd = carve(cur, (size_t)wd * es);
-  size_t maxact = 0, partial = 0, slab = vgg_first_wgrad_slab_bytes(p.N, p.H, p.W);
   int maxC = 64;
   for (size_t i = 0; i < p.layers.size(); ++i) {
     DcLayer& c = p.layers[i];
@@ -168,7 +159,7 @@ int build_dynamic_cnn_plan(DynamicCnnPlan& p, const char* arch) {
   p.off_red = carve(cur, bn_reduce_scratch_bytes(p.red_C));   // the column reducer's scratch for the widest 2 * C
   p.slab_bytes = slab;
   p.off_slab = carve(cur, slab);
-  p.off_dwv = carve(cur, 64 * 128 * sizeof(float));
+  p.first.dwv(cur);
   p.off_g[0] = carve(cur, maxact * es);
   p.off_g[1] = carve(cur, maxact * es);
   p.ws_bytes = cur;
@@ -193,9 +184,6 @@ int dynamic_cnn_forward(DynamicCnnPlan& p, const void* image, const float* norm6
     if ((rc = p.ensure_table())) return rc;
     PROF(K_STAGE, 0.0, 0.0, stage_weights<T>(p.table_dev, (int)p.table_host.size(), p.max_stage_elems, params, wf, wd, true, st));
   }
-  PROF(K_STAGE, 0.0, 0.0, vgg_stage_first<T>(params + p.layers[0].w_off, wf, st));
-  T* img8 = reinterpret_cast<T*>(ws + p.off_img8);
-  PROF(K_STEM_MISC, 0.0, 0.0, pack_nhwc8<T>(image, norm6, p.N, p.H, p.W, p.Hp, p.Wp, img8, st));
   const T* cur = nullptr;
   for (size_t i = 0; i < p.layers.size(); ++i) {
     DcLayer& c = p.layers[i];
@@ -206,7 +194,7 @@ int dynamic_cnn_forward(DynamicCnnPlan& p, const void* image, const float* norm6
     const size_t in_elems = (size_t)p.N * c.H * c.W * c.Cout;
     ConvShape s = {p.N, c.H, c.W, c.Cin, c.Cout, 3, 3, 1, 1};
     if (i == 0) {
-      PROF(K_CONV_FWD, conv_flops(s), conv_bytes(s, sizeof(T)), launch_vgg_first_conv_fwd<T>(p.N, p.H, p.W, p.Hp, p.Wp, img8, wf, y, nullptr, st));
+      if ((rc = first_conv_forward<T>(p.first.bufs<T>(ws, wf, y), p.fg, image, norm6, params + c.w_off, nullptr, nullptr, nullptr, &p.prof, st))) return rc;
     } else {
       PROF(K_CONV_FWD, conv_flops(s), conv_bytes(s, sizeof(T)), launch_conv_fwd<T>(s, cur, wf + c.wf, y, nullptr, nullptr, st));
     }
@@ -260,12 +248,7 @@ int dynamic_cnn_backward(DynamicCnnPlan& p, const float* dfeat, const float* par
     }
     gi ^= 1;
     ConvShape s = {p.N, c.H, c.W, c.Cin, c.Cout, 3, 3, 1, 1};
-    if (i == 0) {
-      float* dwv = reinterpret_cast<float*>(ws + p.off_dwv);
-      PROF(K_WGRAD, conv_flops(s), 0.0,
-           launch_vgg_first_conv_wgrad<T>(p.N, p.H, p.W, p.Hp, p.Wp, dy, reinterpret_cast<const T*>(ws + p.off_img8), slab, dwv, st));
-      return vgg_wgrad_unpack_first(dwv, grads + c.w_off, st);
-    }
+    if (i == 0) return first_conv_wgrad<T>(p.first.bufs<T>(ws, nullptr, nullptr, slab), p.fg, dy, grads + c.w_off, FirstGeom::COUT, &p.prof, st);
     const T* in = reinterpret_cast<const T*>(ws + p.layers[i - 1].a_off);
     PROF(K_WGRAD, conv_flops(s), conv_bytes(s, sizeof(T)), launch_conv_wgrad<T>(s, dy, in, slab, grads + c.w_off, st));
     // plain data gradient: the ReLU mask (and the pool) of the layer below are undone by its own GroupNorm backward
@@ -278,20 +261,14 @@ int dynamic_cnn_backward(DynamicCnnPlan& p, const float* dfeat, const float* par
 int DynamicCnnPlan::forward(const void* image, const float* norm6, const float* params, float* buffers, unsigned char* ws,
                             float* features, bool training, hipStream_t st) {
   (void)buffers; (void)training;   // GroupNorm keeps no running statistics: train and eval run the same kernels
-  if (dtype == 1) return dynamic_cnn_forward<bf16_t>(*this, image, norm6, params, ws, features, st);
-  return dynamic_cnn_forward<float>(*this, image, norm6, params, ws, features, st);
+  return by_dtype(dtype, [&](auto t) { return dynamic_cnn_forward<decltype(t)>(*this, image, norm6, params, ws, features, st); });
 }
 int DynamicCnnPlan::backward(const float* dfeat, const float* params, unsigned char* ws, float* grads, hipStream_t st) {
-  if (dtype == 1) return dynamic_cnn_backward<bf16_t>(*this, dfeat, params, ws, grads, st);
-  return dynamic_cnn_backward<float>(*this, dfeat, params, ws, grads, st);
+  return by_dtype(dtype, [&](auto t) { return dynamic_cnn_backward<decltype(t)>(*this, dfeat, params, ws, grads, st); });
 }
 
 }  // namespace
 
 PlanBase* make_dynamic_cnn_plan(const char* arch, int N, int H, int W, int dtype, int* rc) {
-  DynamicCnnPlan* p = new DynamicCnnPlan();
-  p->N = N; p->H = H; p->W = W; p->dtype = dtype;
-  *rc = build_dynamic_cnn_plan(*p, arch);
-  if (*rc) { delete p; return nullptr; }
-  return p;
+  return make_plan<DynamicCnnPlan>(N, H, W, dtype, rc, [arch](DynamicCnnPlan& p) { return build_dynamic_cnn_plan(p, arch); });
 }

@@ -63,9 +63,10 @@ struct MBPlan : PlanBase {
   std::vector<SEBlock> ses;
   int n_sd = 0;                     // residual blocks with stochastic depth; 0: the plan takes no "sd_mask"
   const float* sd_mask = nullptr;   // [n_sd][N] keep/scale factors for this training step (null: no stochastic depth)
-  int Hp, Wp, stemC;
-  size_t off_img8, off_wf, off_wd, off_stat, off_tab, off_partial, off_coefbwd, off_red, off_slab, slab_bytes, off_dwv, off_dwpart,
-      off_setmp = 0, off_g[4];
+  int stemC;
+  FirstGeom fg;                     // the stride-2 first conv (3 -> stemC <= 64) and its padded NHWC8 image
+  FirstCarve first;
+  size_t off_wf, off_wd, off_stat, off_tab, off_partial, off_coefbwd, off_red, off_slab, slab_bytes, off_dwpart, off_setmp = 0, off_g[4];
   int red_C = 0;   // channels the reduction scratch was carved for (bn_reduce_scratch)
   size_t stat_bytes = 0;
 
@@ -116,32 +117,22 @@ int add_unit(MBPlan& p, int kind, const std::string& conv_name, const std::strin
 
 // Staged-weight table and workspace carve-up, once the builder has registered every unit.
 int finish_plan(MBPlan& p, const char* arch) {
-  ARG_CHECK(p.units[0].OH <= 240 && p.units[0].OW <= 240, "%s: input %dx%d too large for the weight-gradient kernel", arch, p.H, p.W);
-  p.Hp = p.H + 2; p.Wp = (p.W + 4 + 1) / 2 * 2;
+  p.fg = FirstGeom(p.N, p.H, p.W, p.units[0].stride);
+  if (int rc = p.fg.check(arch)) return rc;
 
   // ---- staged weights
-  int64_t wf = 64 * 128, wd = 0;   // slot 0: first conv's virtual operand
-  p.units[0].wf = 0;
+  int64_t wf = FirstGeom::WV_ELEMS, wd = 0;   // slot 0: first conv's virtual operand
   for (size_t i = 1; i < p.units.size(); ++i) {
     MBUnit& u = p.units[i];
     if (u.kind == U_DW) { u.wf = wf; wf += (int64_t)u.ksize * u.ksize * u.Coutp; continue; }
-    StageDesc d = {};
-    d.src_off = u.w_off; d.Cout = u.Cout; d.Cin = u.Cin; d.taps = 1; d.Cout_pad = u.Coutp; d.Cin_pad = u.Cinp;
-    u.wf = wf; u.wd = wd;
-    d.fwd_off = wf; d.dgrad_off = wd;
-    const int64_t n = (int64_t)u.Coutp * u.Cinp;
-    wf += n; wd += n;
-    if (n > p.max_stage_elems) p.max_stage_elems = (int)n;
-    p.table_host.push_back(d);
+    stage_append(p.table_host, u.w_off, u.Cout, u.Cin, 1, u.Coutp, u.Cinp, wf, wd, p.max_stage_elems, u.wf, u.wd);
   }
 
   // ---- workspace
   const size_t es = p.esz();
-  size_t cur = 0;
-  p.off_img8 = carve(cur, (size_t)p.N * p.Hp * p.Wp * 8 * es);
+  size_t cur = 0, maxact = 0, stat_floats = 0, partial = 0, dwpart = 0, setmp = 0, slab = p.first.image(cur, p.fg, es);
   p.off_wf = carve(cur, (size_t)wf * es);
   p.off_wd = carve(cur, (size_t)(wd > 0 ? wd : 1) * es);
-  size_t maxact = 0, stat_floats = 0, partial = 0, dwpart = 0, setmp = 0, slab = vgg_first_wgrad_slab_bytes(p.N, p.units[0].OH, p.units[0].OW);
   int maxCp = 64;
   size_t prev_y = 0, block_in = 0;
   for (size_t i = 0; i < p.units.size(); ++i) {
@@ -196,7 +187,7 @@ int finish_plan(MBPlan& p, const char* arch) {
   p.off_red = carve(cur, bn_reduce_scratch_bytes(p.red_C));
   p.slab_bytes = slab;
   p.off_slab = carve(cur, slab);
-  p.off_dwv = carve(cur, 64 * 128 * sizeof(float));
+  p.first.dwv(cur);
   p.off_dwpart = carve(cur, (dwpart > 0 ? dwpart : 1) * sizeof(float));
   if (setmp) p.off_setmp = carve(cur, setmp * sizeof(float));
   for (int i = 0; i < 4; ++i) p.off_g[i] = carve(cur, maxact * es);
@@ -314,7 +305,7 @@ int mb_forward(MBPlan& p, const void* image, const float* norm6, const float* pa
   int rc;
   if ((rc = p.ensure_table())) return rc;
   PROF(K_STAGE, 0.0, 0.0, stage_weights<T>(p.table_dev, (int)p.table_host.size(), p.max_stage_elems, params, wf, wd, training, st));
-  PROF(K_STAGE, 0.0, 0.0, vgg_stage_first<T>(params + p.units[0].w_off, wf, st, p.stemC));
+  PROF(K_STAGE, 0.0, 0.0, first3_stage<T>(params + p.units[0].w_off, wf, st, p.stemC));
   for (MBUnit& u : p.units)
     if (u.kind == U_DW) PROF(K_STAGE, 0.0, 0.0, dw_stage_weights<T>(params + u.w_off, u.Cout, u.Coutp, wf + u.wf, st, u.ksize));
   for (SEBlock& se : p.ses) {
@@ -322,8 +313,6 @@ int mb_forward(MBPlan& p, const void* image, const float* norm6, const float* pa
     PROF(K_STAGE, 0.0, 0.0, pad_matrix(params + se.w2_off, se.C, se.Csq, se.Cp, se.Csq, reinterpret_cast<float*>(ws + se.w2p_off), st));
     PROF(K_STAGE, 0.0, 0.0, pad_matrix(params + se.b2_off, 1, se.C, 1, se.Cp, reinterpret_cast<float*>(ws + se.b2p_off), st));
   }
-  T* img8 = reinterpret_cast<T*>(ws + p.off_img8);
-  PROF(K_STEM_MISC, 0.0, 0.0, pack_nhwc8<T>(image, norm6, p.N, p.H, p.W, p.Hp, p.Wp, img8, st));
 
   for (MBUnit& u : p.units) {
     const size_t rows = (size_t)p.N * u.OH * u.OW;
@@ -333,11 +322,9 @@ int mb_forward(MBPlan& p, const void* image, const float* norm6, const float* pa
     const int Cp = u.Coutp;
     const BnCoef k(reinterpret_cast<float*>(ws + u.coef_off), Cp);
     int nrows = 0;
-    if (u.kind == U_FIRST) {
-      ConvShape s = {p.N, p.H, p.W, 3, 64, 3, 3, 2, 1};
-      PROF(K_CONV_FWD, conv_flops(s) / 2, conv_bytes(s, sizeof(T)),
-           launch_vgg_first_conv_fwd<T>(p.N, p.H, p.W, p.Hp, p.Wp, img8, wf, x, nullptr, st, 2, training ? stat_sum : nullptr,
-                                        training ? stat_sq : nullptr));
+    if (u.kind == U_FIRST) {   // weights staged above (null here); the profile counts half the 64-column GEMM
+      if ((rc = first_conv_forward<T>(p.first.bufs<T>(ws, wf, x), p.fg, image, norm6, nullptr, nullptr, training ? stat_sum : nullptr,
+                                      training ? stat_sq : nullptr, &p.prof, st, 0.5))) return rc;
       nrows = (int)((rows + 127) / 128);
     } else if (u.kind == U_PW) {
       ConvShape s = {p.N, u.H, u.W, u.Cinp, u.Coutp, 1, 1, 1, 0};
@@ -419,13 +406,7 @@ int mb_backward(MBPlan& p, const float* dfeat, const float* params, unsigned cha
                              BnBwdCoef(cA, Cp), partial, red, B[a], nullptr, &p.prof, 6.0 * rows * Cp * sizeof(T), st, u.Cout))) return rc;
     const T* dx = B[a];
     // ---- convolution backward
-    if (u.kind == U_FIRST) {
-      float* dwv = reinterpret_cast<float*>(ws + p.off_dwv);
-      ConvShape s = {p.N, p.H, p.W, 3, 64, 3, 3, 2, 1};
-      PROF(K_WGRAD, conv_flops(s) / 2, 0.0,
-           launch_vgg_first_conv_wgrad<T>(p.N, p.H, p.W, p.Hp, p.Wp, dx, reinterpret_cast<const T*>(ws + p.off_img8), slab, dwv, st, 2));
-      return vgg_wgrad_unpack_first(dwv, grads + u.w_off, st, p.stemC);
-    }
+    if (u.kind == U_FIRST) return first_conv_wgrad<T>(p.first.bufs<T>(ws, nullptr, nullptr, slab), p.fg, dx, grads + u.w_off, p.stemC, &p.prof, st, 0.5);
     int b;
     if (u.kind == U_PW) {
       ConvShape s = {p.N, u.H, u.W, u.Cinp, u.Coutp, 1, 1, 1, 0};
@@ -456,21 +437,10 @@ int mb_backward(MBPlan& p, const float* dfeat, const float* params, unsigned cha
 
 int MBPlan::forward(const void* image, const float* norm6, const float* params, float* buffers, unsigned char* ws,
                     float* features, bool training, hipStream_t st) {
-  if (dtype == 1) return mb_forward<bf16_t>(*this, image, norm6, params, buffers, ws, features, training, st);
-  return mb_forward<float>(*this, image, norm6, params, buffers, ws, features, training, st);
+  return by_dtype(dtype, [&](auto t) { return mb_forward<decltype(t)>(*this, image, norm6, params, buffers, ws, features, training, st); });
 }
 int MBPlan::backward(const float* dfeat, const float* params, unsigned char* ws, float* grads, hipStream_t st) {
-  if (dtype == 1) return mb_backward<bf16_t>(*this, dfeat, params, ws, grads, st);
-  return mb_backward<float>(*this, dfeat, params, ws, grads, st);
-}
-
-template <typename Build>
-PlanBase* make_plan(int N, int H, int W, int dtype, int* rc, Build build) {
-  MBPlan* p = new MBPlan();
-  p->N = N; p->H = H; p->W = W; p->dtype = dtype;
-  *rc = build(*p);
-  if (*rc) { delete p; return nullptr; }
-  return p;
+  return by_dtype(dtype, [&](auto t) { return mb_backward<decltype(t)>(*this, dfeat, params, ws, grads, st); });
 }
 
 }  // namespace
@@ -522,8 +492,8 @@ template int se_backward<float>(const SEArgs&, const float*, const float*, float
 template int se_backward<bf16_t>(const SEArgs&, const bf16_t*, const bf16_t*, float*, float*, float*, float*, float*, bf16_t*, Profiler*, hipStream_t);
 
 PlanBase* make_mobilenet_plan(int N, int H, int W, int dtype, int* rc) {
-  return make_plan(N, H, W, dtype, rc, build_mobilenet_v2);
+  return make_plan<MBPlan>(N, H, W, dtype, rc, build_mobilenet_v2);
 }
 PlanBase* make_efficientnet_plan(int variant, int N, int H, int W, int dtype, int* rc) {
-  return make_plan(N, H, W, dtype, rc, [variant](MBPlan& p) { return build_efficientnet(p, variant); });
+  return make_plan<MBPlan>(N, H, W, dtype, rc, [variant](MBPlan& p) { return build_efficientnet(p, variant); });
 }

@@ -181,14 +181,15 @@ int avgpool2_fwd(const T* x, int N, int H, int W, int C, T* dst, int pitch, hipS
 template <typename T>
 int avgpool2_bwd(const T* dpool, int pitch, int N, int H, int W, int C, T* dx, hipStream_t st);
 
-// ---- VGG pieces (conv + bias + ReLU stacks with 2x2 max-pools, torchvision vgg16 `features` + `avgpool`)
+// ---- the 3-channel 3x3 first conv of VGG, DynamicCNN, MobileNet-V2 and EfficientNet (FirstGeom in conv.h; plan.h runs these as first_conv_*)
 // image (fp32 NCHW, or uint8 NHWC with norm6 != nullptr) -> zero-bordered NHWC8 [N][H+2][Wp][8], pixel (h,w) at (h+1, w+1)
 template <typename T>
 int pack_nhwc8(const void* img, const float* norm6, int N, int H, int W, int Hp, int Wp, T* out, hipStream_t st);
 // [64][3][3][3] OIHW fp32 -> virtual-conv operand [64][4][32]: (o, r, s*8 + c); tap 3 and unused slots stay zero
 template <typename T>
-int vgg_stage_first(const float* w, T* wv, hipStream_t st, int cout = 64);   // cout <= 64 real output channels
-int vgg_wgrad_unpack_first(const float* dwv, float* dw, hipStream_t st, int cout = 64);
+int first3_stage(const float* w, T* wv, hipStream_t st, int cout = 64);   // cout <= 64 real output channels
+int first3_wgrad_unpack(const float* dwv, float* dw, hipStream_t st, int cout = 64);
+// ---- VGG pieces (conv + bias + ReLU stacks with 2x2 max-pools, torchvision vgg16 `features` + `avgpool`)
 // 2x2 stride-2 max pool (floor), idx = argmax tap 0..3 per element (first max, row-major)
 template <typename T>
 int maxpool2_fwd(const T* x, int N, int H, int W, int C, T* y, uint8_t* idx, hipStream_t st);

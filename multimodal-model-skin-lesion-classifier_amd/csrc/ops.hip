@@ -860,7 +860,7 @@ int pack_nhwc8(const void* img, const float* norm6, int N, int H, int W, int Hp,
 }
 
 template <typename T>
-__global__ void vgg_stage_first_kernel(const float* __restrict__ w, T* __restrict__ wv, int cout) {
+__global__ void first3_stage_kernel(const float* __restrict__ w, T* __restrict__ wv, int cout) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;   // over cout*3*3*3 (o, c, r, s)
   if (i < cout * 27) {
     int o = i / 27, rem = i - o * 27;
@@ -870,13 +870,13 @@ __global__ void vgg_stage_first_kernel(const float* __restrict__ w, T* __restric
   }
 }
 template <typename T>
-int vgg_stage_first(const float* w, T* wv, hipStream_t st, int cout) {
+int first3_stage(const float* w, T* wv, hipStream_t st, int cout) {
   HIP_CHECK_RET(hipMemsetAsync(wv, 0, 64 * 128 * sizeof(T), st));
-  hipLaunchKernelGGL(vgg_stage_first_kernel<T>, dim3(ceil_div(64 * 27, 256)), dim3(256), 0, st, w, wv, cout);
+  hipLaunchKernelGGL(first3_stage_kernel<T>, dim3(ceil_div(64 * 27, 256)), dim3(256), 0, st, w, wv, cout);
   HIP_CHECK_RET(hipGetLastError());
   return MMSKIN_OK;
 }
-__global__ void vgg_wgrad_unpack_first_kernel(const float* __restrict__ dwv, float* __restrict__ dw, int cout) {
+__global__ void first3_wgrad_unpack_kernel(const float* __restrict__ dwv, float* __restrict__ dw, int cout) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < cout * 27) {
     int o = i / 27, rem = i - o * 27;
@@ -885,8 +885,8 @@ __global__ void vgg_wgrad_unpack_first_kernel(const float* __restrict__ dwv, flo
     dw[i] = dwv[((size_t)o * 4 + r) * 32 + s2 * 8 + c];
   }
 }
-int vgg_wgrad_unpack_first(const float* dwv, float* dw, hipStream_t st, int cout) {
-  hipLaunchKernelGGL(vgg_wgrad_unpack_first_kernel, dim3(ceil_div(64 * 27, 256)), dim3(256), 0, st, dwv, dw, cout);
+int first3_wgrad_unpack(const float* dwv, float* dw, hipStream_t st, int cout) {
+  hipLaunchKernelGGL(first3_wgrad_unpack_kernel, dim3(ceil_div(64 * 27, 256)), dim3(256), 0, st, dwv, dw, cout);
   HIP_CHECK_RET(hipGetLastError());
   return MMSKIN_OK;
 }
@@ -1028,7 +1028,7 @@ int adaptive_avgpool_bwd(const float* dout_nchw, int N, int H, int W, int C, int
 
 #define INST_VGG(T)                                                                                         \
   template int pack_nhwc8<T>(const void*, const float*, int, int, int, int, int, T*, hipStream_t);          \
-  template int vgg_stage_first<T>(const float*, T*, hipStream_t, int);                                      \
+  template int first3_stage<T>(const float*, T*, hipStream_t, int);                                      \
   template int maxpool2_fwd<T>(const T*, int, int, int, int, T*, uint8_t*, hipStream_t);                    \
   template int maxpool2_bwd_relu<T>(const T*, const uint8_t*, const T*, int, int, int, int, T*, hipStream_t); \
   template int adaptive_avgpool_fwd<T>(const T*, int, int, int, int, int, int, float*, hipStream_t);        \

@@ -214,6 +214,34 @@ static inline size_t carve(size_t& cursor, size_t bytes) {
   return o;
 }
 
+// One staged weight [Cout][Cin][taps] appended to `table` (every plan's stage table and the op-level carves of capi.hip).  wf / wd: the
+// running element cursors of the forward / data-gradient staging buffers, the weight's own offsets returned in wf_off / wd_off.
+// Cop / Cip: the staged (zero-padded) dims, 0 = as Cout / Cin.
+inline void stage_append(std::vector<StageDesc>& table, int64_t src, int Cout, int Cin, int taps, int Cop, int Cip, int64_t& wf, int64_t& wd,
+                         int& max_stage_elems, int64_t& wf_off, int64_t& wd_off) {
+  StageDesc d = {};
+  d.src_off = src; d.Cout = Cout; d.Cin = Cin; d.taps = taps; d.Cout_pad = Cop; d.Cin_pad = Cip;
+  wf_off = wf; wd_off = wd;
+  d.fwd_off = wf; d.dgrad_off = wd;
+  const int64_t n = (int64_t)(Cop ? Cop : Cout) * (Cip ? Cip : Cin) * taps;
+  wf += n; wd += n;
+  if (n > max_stage_elems) max_stage_elems = (int)n;
+  table.push_back(d);
+}
+
+// The body of every plan factory (create() needs no GPU): a Plan for (N, H, W, dtype) that build(plan) fills; nullptr and *rc on failure
+template <class Plan, class Build>
+PlanBase* make_plan(int N, int H, int W, int dtype, int* rc, Build build) {
+  Plan* p = new Plan();
+  p->N = N; p->H = H; p->W = W; p->dtype = dtype;
+  *rc = build(*p);
+  if (*rc) { delete p; return nullptr; }
+  return p;
+}
+// f(T()) for the plan's element type: the forward / backward overrides call their templates through it
+template <class F>
+int by_dtype(int dtype, F f) { return dtype == 1 ? f(bf16_t()) : f(float()); }
+
 // One profiler event pair around `call_` on stream `st`, its FLOPs / bytes added to class cls_; returns from the enclosing function
 // (which has `int rc` and `hipStream_t st`) when the call fails.  prof_ may be null (op-level callers).
 #define PROF_AT(prof_, cls_, flops_, bytes_, call_)            \
@@ -379,6 +407,49 @@ int stem_wgrad(const StemBufs<T>& b, const StemGeom& g, float* dw, Profiler* pro
   return stem_wgrad_unpack(b.dwv, dw, st);
 }
 
+// ---- the 3-channel 3x3 first conv of VGG, DynamicCNN (stride 1), MobileNet-V2 and EfficientNet (stride 2): FirstGeom in conv.h
+template <typename T>
+struct FirstBufs {
+  T* img8 = nullptr;      // packed image [N][Hp][Wp][8]
+  T* wv = nullptr;        // staged weights [64][128]: slot 0 of the plan's forward staging buffer
+  T* out = nullptr;       // conv output [rows][64]
+  WgradSlab slab = {};    // weight-gradient slab with the floats carved for it
+  float* dwv = nullptr;   // the gradient in the staged layout
+};
+// Where a plan keeps them (byte offsets into its workspace).  The image is the front of the workspace, dwv sits where the plan calls
+// dwv(); the staged weights are the first FirstGeom::WV_ELEMS elements of the forward staging buffer, so the plan's stage_append cursor
+// starts there.
+struct FirstCarve {
+  size_t off_img8 = 0, off_dwv = 0;
+  // returns the first conv's weight-gradient slab bytes: the seed of the plan's slab maximum
+  size_t image(size_t& cur, const FirstGeom& g, size_t es) { off_img8 = carve(cur, g.img8_elems() * es); return first3_wgrad_slab_bytes(g); }
+  void dwv(size_t& cur) { off_dwv = carve(cur, FirstGeom::WV_ELEMS * sizeof(float)); }
+  template <typename T>
+  FirstBufs<T> bufs(unsigned char* ws, T* wv, T* out, WgradSlab slab = {}) const {
+    return FirstBufs<T>{reinterpret_cast<T*>(ws + off_img8), wv, out, slab, reinterpret_cast<float*>(ws + off_dwv)};
+  }
+};
+// image (as PlanBase::forward takes it) -> b.out: stage w [cout][3][3][3] (null: b.wv is staged already), pack, conv.  fuse: optional
+// bias / ReLU epilogue; ssum / ssq: optional batch-statistics slabs; flops_scale: the share of the 64-column GEMM the caller's profile counts
+template <typename T>
+int first_conv_forward(const FirstBufs<T>& b, const FirstGeom& g, const void* image, const float* norm6, const float* w, const FwdFuse* fuse,
+                       float* ssum, float* ssq, Profiler* prof, hipStream_t st, double flops_scale = 1.0) {
+  int rc;
+  if (w) PROF_AT(prof, K_STAGE, 0.0, 0.0, first3_stage<T>(w, b.wv, st));
+  PROF_AT(prof, K_STEM_MISC, 0.0, 0.0, pack_nhwc8<T>(image, norm6, g.N, g.H, g.W, g.Hp, g.Wp, b.img8, st));
+  PROF_AT(prof, K_CONV_FWD, conv_flops(g.conv()) * flops_scale, conv_bytes(g.conv(), sizeof(T)),
+          launch_first3_conv_fwd<T>(g, b.img8, b.wv, b.out, fuse, st, ssum, ssq));
+  return MMSKIN_OK;
+}
+// dy (gradient of b.out), b.img8 -> dw [cout][3][3][3]
+template <typename T>
+int first_conv_wgrad(const FirstBufs<T>& b, const FirstGeom& g, const T* dy, float* dw, int cout, Profiler* prof, hipStream_t st,
+                     double flops_scale = 1.0) {
+  int rc;
+  PROF_AT(prof, K_WGRAD, conv_flops(g.conv()) * flops_scale, 0.0, launch_first3_conv_wgrad<T>(g, dy, b.img8, b.slab, b.dwv, st));
+  return first3_wgrad_unpack(b.dwv, dw, st, cout);
+}
+
 // ---- squeeze-excitation (mbconv.hip): the chain the MBConv plan runs behind a depthwise unit, shared with the op-level entry
 // points mmskin_se_* so that a test of the chain runs the plan's own launches.  Channels are padded to Cp = pad64(C).
 struct SEArgs {
@@ -431,22 +502,10 @@ inline void dense_layer_geom(DLayer& l, int c0, int i) {   // layer i of a block
   l.Cin = c0 + DENSE_GROWTH * i;
   l.Cp = (l.Cin + 63) / 64 * 64;
 }
-// one staged weight appended to `table`; wf / wd are the running element cursors of the forward / data-gradient staging buffers
-inline void dense_stage(std::vector<StageDesc>& table, int64_t src, int Cout, int Cin, int taps, int Cop, int Cip, int64_t& wf, int64_t& wd,
-                        int& max_stage_elems, int64_t& wf_off, int64_t& wd_off) {
-  StageDesc d = {};
-  d.src_off = src; d.Cout = Cout; d.Cin = Cin; d.taps = taps; d.Cout_pad = Cop; d.Cin_pad = Cip;
-  wf_off = wf; wd_off = wd;
-  d.fwd_off = wf; d.dgrad_off = wd;
-  const int64_t n = (int64_t)Cop * Cip * taps;
-  wf += n; wd += n;
-  if (n > max_stage_elems) max_stage_elems = (int)n;
-  table.push_back(d);
-}
 inline void dense_stage_layer(DLayer& l, std::vector<StageDesc>& table, int64_t& wf, int64_t& wd, int& max_stage_elems) {
   l.tab1 = (int)table.size();
-  dense_stage(table, l.w1_off, DENSE_BOTTLE, l.Cin, 1, DENSE_BOTTLE, l.Cp, wf, wd, max_stage_elems, l.wf1, l.wd1);
-  dense_stage(table, l.w2_off, DENSE_GROWTH, DENSE_BOTTLE, 9, DENSE_G_PAD, DENSE_BOTTLE, wf, wd, max_stage_elems, l.wf2, l.wd2);
+  stage_append(table, l.w1_off, DENSE_BOTTLE, l.Cin, 1, DENSE_BOTTLE, l.Cp, wf, wd, max_stage_elems, l.wf1, l.wd1);
+  stage_append(table, l.w2_off, DENSE_GROWTH, DENSE_BOTTLE, 9, DENSE_G_PAD, DENSE_BOTTLE, wf, wd, max_stage_elems, l.wf2, l.wd2);
 }
 // inference: conv1 carries norm2's scale, its epilogue adds shift + ReLU (coef2_off must be carved)
 inline void dense_fold_norm2(const DLayer& l, std::vector<StageDesc>& table) {

@@ -21,9 +21,10 @@ struct VConv {
 
 struct VggPlan : PlanBase {
   std::vector<VConv> convs;
-  int Hp, Wp;                 // padded NHWC8 image
+  FirstGeom fg;               // the first conv (3 -> 64) and its padded NHWC8 image
+  FirstCarve first;
   int fH, fW;                 // spatial size after the five pools
-  size_t off_img8, off_wf, off_wd, off_partial, off_red, off_slab, slab_bytes, off_dwv, off_g[2];
+  size_t off_wf, off_wd, off_partial, off_red, off_slab, slab_bytes, off_g[2];
   int red_C;                  // channels the reduction scratch at off_red was carved for
 
   int forward(const void* image, const float* norm6, const float* params, float* buffers, unsigned char* ws,
@@ -53,29 +54,19 @@ int build_vgg_plan(VggPlan& p) {
   }
   p.fH = h; p.fW = w;
   p.feat_dim = 512; p.out_h = 7; p.out_w = 7;
-  ARG_CHECK(p.H <= 240 && p.W <= 240, "vgg16: input %dx%d too large for the weight-gradient kernel's pixel stepping", p.H, p.W);
-  p.Hp = p.H + 2; p.Wp = (p.W + 4 + 1) / 2 * 2;
+  p.fg = FirstGeom(p.N, p.H, p.W, 1);
+  if (int rc = p.fg.check("vgg16")) return rc;
 
-  int64_t wf = 64 * 128, wd = 0;   // slot 0 of wf: the first conv's virtual operand
+  int64_t wf = FirstGeom::WV_ELEMS, wd = 0;   // slot 0 of wf: the first conv's virtual operand
   for (size_t i = 1; i < p.convs.size(); ++i) {
     VConv& c = p.convs[i];
-    StageDesc d = {};
-    d.src_off = c.w_off; d.Cout = c.Cout; d.Cin = c.Cin; d.taps = 9;
-    c.wf = wf; c.wd = wd;
-    d.fwd_off = wf; d.dgrad_off = wd;
-    const int64_t n = (int64_t)c.Cout * c.Cin * 9;
-    wf += n; wd += n;
-    if (n > p.max_stage_elems) p.max_stage_elems = (int)n;
-    p.table_host.push_back(d);
+    stage_append(p.table_host, c.w_off, c.Cout, c.Cin, 9, 0, 0, wf, wd, p.max_stage_elems, c.wf, c.wd);
   }
-  p.convs[0].wf = 0;
 
   const size_t es = p.esz();
-  size_t cur = 0;
-  p.off_img8 = carve(cur, (size_t)p.N * p.Hp * p.Wp * 8 * es);
+  size_t cur = 0, maxact = 0, partial = 0, slab = p.first.image(cur, p.fg, es);
   p.off_wf = carve(cur, (size_t)wf * es);
   p.off_wd = carve(cur, (size_t)wd * es);
-  size_t maxact = 0, partial = 0, slab = vgg_first_wgrad_slab_bytes(p.N, p.H, p.W);
   int maxC = 64;
   for (VConv& c : p.convs) {
     const size_t rows = (size_t)p.N * c.H * c.W;
@@ -102,7 +93,7 @@ int build_vgg_plan(VggPlan& p) {
   p.off_red = carve(cur, bn_reduce_scratch_bytes(p.red_C));
   p.slab_bytes = slab;
   p.off_slab = carve(cur, slab);
-  p.off_dwv = carve(cur, 64 * 128 * sizeof(float));
+  p.first.dwv(cur);
   p.off_g[0] = carve(cur, maxact * es);
   p.off_g[1] = carve(cur, maxact * es);
   p.ws_bytes = cur;
@@ -117,9 +108,6 @@ int vgg_forward(VggPlan& p, const void* image, const float* norm6, const float* 
   int rc;
   if ((rc = p.ensure_table())) return rc;
   PROF(K_STAGE, 0.0, 0.0, stage_weights<T>(p.table_dev, (int)p.table_host.size(), p.max_stage_elems, params, wf, wd, true, st));
-  PROF(K_STAGE, 0.0, 0.0, vgg_stage_first<T>(params + p.convs[0].w_off, wf, st));
-  T* img8 = reinterpret_cast<T*>(ws + p.off_img8);
-  PROF(K_STEM_MISC, 0.0, 0.0, pack_nhwc8<T>(image, norm6, p.N, p.H, p.W, p.Hp, p.Wp, img8, st));
   const T* cur = nullptr;
   for (size_t i = 0; i < p.convs.size(); ++i) {
     VConv& c = p.convs[i];
@@ -127,8 +115,7 @@ int vgg_forward(VggPlan& p, const void* image, const float* norm6, const float* 
     FwdFuse f; f.bias = params + c.b_off; f.relu = true;
     ConvShape s = {p.N, c.H, c.W, c.Cin, c.Cout, 3, 3, 1, 1};
     if (i == 0) {
-      PROF(K_CONV_FWD, conv_flops(s), conv_bytes(s, sizeof(T)),
-           launch_vgg_first_conv_fwd<T>(p.N, p.H, p.W, p.Hp, p.Wp, img8, wf, y, &f, st));
+      if ((rc = first_conv_forward<T>(p.first.bufs<T>(ws, wf, y), p.fg, image, norm6, params + c.w_off, &f, nullptr, nullptr, &p.prof, st))) return rc;
     } else {
       PROF(K_CONV_FWD, conv_flops(s), conv_bytes(s, sizeof(T)), launch_conv_fwd<T>(s, cur, wf + c.wf, y, nullptr, nullptr, st, &f));
     }
@@ -168,12 +155,7 @@ int vgg_backward(VggPlan& p, const float* dfeat, const float* params, unsigned c
     const T* dz = G[gi];
     PROF(K_BN_BWD, 0.0, 0.0, bias_grad_finalize(partial, part_rows, part_stride, c.Cout, grads + c.b_off, red, st));
     ConvShape s = {p.N, c.H, c.W, c.Cin, c.Cout, 3, 3, 1, 1};
-    if (i == 0) {
-      float* dwv = reinterpret_cast<float*>(ws + p.off_dwv);
-      PROF(K_WGRAD, conv_flops(s), 0.0,
-           launch_vgg_first_conv_wgrad<T>(p.N, p.H, p.W, p.Hp, p.Wp, dz, reinterpret_cast<const T*>(ws + p.off_img8), slab, dwv, st));
-      return vgg_wgrad_unpack_first(dwv, grads + c.w_off, st);
-    }
+    if (i == 0) return first_conv_wgrad<T>(p.first.bufs<T>(ws, nullptr, nullptr, slab), p.fg, dz, grads + c.w_off, FirstGeom::COUT, &p.prof, st);
     VConv& prev = p.convs[i - 1];
     const T* in = prev.pool_after ? reinterpret_cast<const T*>(ws + prev.p_off) : reinterpret_cast<const T*>(ws + prev.y_off);
     PROF(K_WGRAD, conv_flops(s), conv_bytes(s, sizeof(T)), launch_conv_wgrad<T>(s, dz, in, slab, grads + c.w_off, st));
@@ -196,20 +178,14 @@ int vgg_backward(VggPlan& p, const float* dfeat, const float* params, unsigned c
 int VggPlan::forward(const void* image, const float* norm6, const float* params, float* buffers, unsigned char* ws,
                      float* features, bool training, hipStream_t st) {
   (void)buffers; (void)training;   // no BatchNorm: train and eval run the same kernels
-  if (dtype == 1) return vgg_forward<bf16_t>(*this, image, norm6, params, ws, features, st);
-  return vgg_forward<float>(*this, image, norm6, params, ws, features, st);
+  return by_dtype(dtype, [&](auto t) { return vgg_forward<decltype(t)>(*this, image, norm6, params, ws, features, st); });
 }
 int VggPlan::backward(const float* dfeat, const float* params, unsigned char* ws, float* grads, hipStream_t st) {
-  if (dtype == 1) return vgg_backward<bf16_t>(*this, dfeat, params, ws, grads, st);
-  return vgg_backward<float>(*this, dfeat, params, ws, grads, st);
+  return by_dtype(dtype, [&](auto t) { return vgg_backward<decltype(t)>(*this, dfeat, params, ws, grads, st); });
 }
 
 }  // namespace
 
 PlanBase* make_vgg_plan(int N, int H, int W, int dtype, int* rc) {
-  VggPlan* p = new VggPlan();
-  p->N = N; p->H = H; p->W = W; p->dtype = dtype;
-  *rc = build_vgg_plan(*p);
-  if (*rc) { delete p; return nullptr; }
-  return p;
+  return make_plan<VggPlan>(N, H, W, dtype, rc, build_vgg_plan);
 }

@@ -588,12 +588,12 @@ WgradArgs wgrad_geom_stem(int N, int OH, int OW, int Hp, int Wp) {
   for (int r = 0; r < 8; ++r) { a.offy[r] = (int8_t)r; a.offx[r] = 0; }
   return a;
 }
-WgradArgs wgrad_geom_first(int N, int OH, int OW, int Hp, int Wp, int stride) {
+WgradArgs wgrad_geom_first(const FirstGeom& g) {
   WgradArgs a = {};
-  a.N = N; a.IH = Hp; a.IW = Wp; a.C = 32; a.Cpitch = 8;
-  a.OH = OH; a.OW = OW; a.Cout = 64; a.Ktot = 128;
-  a.Sy = stride; a.Sx = stride; a.ntaps = 4;
-  a.M = N * OH * OW;
+  a.N = g.N; a.IH = g.Hp; a.IW = g.Wp; a.C = 32; a.Cpitch = 8;
+  a.OH = g.OH; a.OW = g.OW; a.Cout = FirstGeom::COUT; a.Ktot = FirstGeom::K;
+  a.Sy = g.stride; a.Sx = g.stride; a.ntaps = 4;
+  a.M = g.N * g.OH * g.OW;
   for (int r = 0; r < 4; ++r) { a.offy[r] = (int8_t)(r < 3 ? r : 0); a.offx[r] = 0; }
   return a;
 }
@@ -644,7 +644,12 @@ static size_t wgrad_slab_bytes(const WgradArgs& g, const ConvShape* s) {
 }
 size_t conv_wgrad_slab_bytes(const ConvShape& s) { return wgrad_slab_bytes(wgrad_geom_conv(s), &s); }
 size_t stem_wgrad_slab_bytes(int N, int OH, int OW) { return wgrad_slab_bytes(wgrad_geom_stem(N, OH, OW, 2 * OH + 8, 2 * OW + 8), nullptr); }
-size_t vgg_first_wgrad_slab_bytes(int N, int H, int W) { return wgrad_slab_bytes(wgrad_geom_first(N, H, W, H + 2, W + 8, 1), nullptr); }
+size_t first3_wgrad_slab_bytes(const FirstGeom& g) {
+  // Sized as a stride-1 conv over an image of the OUTPUT size with 8 columns of padding, whatever g runs: kept from before FirstGeom so that no workspace moves.
+  WgradArgs a = wgrad_geom_first(g);
+  a.IH = g.OH + 2; a.IW = g.OW + 8; a.Sy = a.Sx = 1;
+  return wgrad_slab_bytes(a, nullptr);
+}
 
 // ------------------------------------------------------------------------------------------ the launchers
 // geometry -> plan -> capacity -> the family's kernel -> reduction.  s: see wgrad_plan(); C_for_layout / ntaps_for_layout: how the reducer
@@ -705,14 +710,13 @@ int launch_stem_conv_wgrad(int N, int OH, int OW, int Hp, int Wp, const T* dout,
   return run_wgrad<T>(a, nullptr, dout, img4, slab, dwv, 256, 1, st);
 }
 template <typename T>
-int launch_vgg_first_conv_wgrad(int N, int H, int W, int Hp, int Wp, const T* dout, const T* img8, WgradSlab slab,
-                                float* dwv, hipStream_t st, int stride) {
-  WgradArgs a = wgrad_geom_first(N, (H + 2 - 3) / stride + 1, (W + 2 - 3) / stride + 1, Hp, Wp, stride);
-  return run_wgrad<T>(a, nullptr, dout, img8, slab, dwv, 128, 1, st);
+int launch_first3_conv_wgrad(const FirstGeom& g, const T* dout, const T* img8, WgradSlab slab, float* dwv, hipStream_t st) {
+  WgradArgs a = wgrad_geom_first(g);
+  return run_wgrad<T>(a, nullptr, dout, img8, slab, dwv, FirstGeom::K, 1, st);
 }
 
 #define INST(T)                                                                                   \
-  template int launch_vgg_first_conv_wgrad<T>(int, int, int, int, int, const T*, const T*, WgradSlab, float*, hipStream_t, int); \
+  template int launch_first3_conv_wgrad<T>(const FirstGeom&, const T*, const T*, WgradSlab, float*, hipStream_t); \
   template int launch_conv_wgrad<T>(const ConvShape&, const T*, const T*, WgradSlab, float*, hipStream_t, int, int); \
   template int launch_stem_conv_wgrad<T>(int, int, int, int, int, const T*, const T*, WgradSlab, float*, hipStream_t);
 INST(float)

@@ -8,7 +8,8 @@ host arithmetic over the layout struct that the op itself carves, csrc/capi.hip 
   tensors the op must hold (counted here from the shapes alone, fp32 elements unless the op is bf16-only).
 * mmskin_backbone_create needs no device either: the carve-up of every plan (workspace bytes, parameter and buffer counts, and the
   twelve unit_info fields of the first and last unit where a plan reports units) is pinned to the values of commit a9b9008, before the
-  stem geometry and the side-stream slots were each written once."""
+  stem geometry and the side-stream slots were each written once; the DynamicCNN rows to those of commit 4961f46, before the 3-channel
+  first conv's geometry and the stage-table append were each written once."""
 import ctypes
 
 import pytest
@@ -154,7 +155,7 @@ def test_one_abn_workspace_serves_both_entry_points():
 
 # ---- plan carve-ups: (arch, (N, H, W), dtype) -> (workspace bytes, param numel, buffer numel, units, (info12 of the first unit, of the last))
 # None: not pinned -- the ResNet stem unit has no post-activation buffer (its output is the pooled map), and its y_off field was
-# uninitialised memory in the library these values were recorded from
+# uninitialised memory in the library these values were recorded from.  The dynamic-cnn rows: recorded from the library of commit 4961f46
 PLAN_PINS = {
     ('resnet-18', (2, 64, 64), 'fp32'): (106652672, 11176512, 9600, 20, ((89508864, None, 89507840, 2048, 64, 32, 32, 3, 64, 64, 91206656, 92384256), (91190272, 92366848, 91182080, 8, 512, 2, 2, 512, 2, 2, 91206656, 92384256))),
     ('resnet-18', (2, 64, 64), 'bf16'): (58688512, 11176512, 9600, 20, ((44763136, None, 44762112, 2048, 64, 32, 32, 3, 64, 64, 45649920, 46255104), (45641728, 46246400, 45633536, 8, 512, 2, 2, 512, 2, 2, 45649920, 46255104))),
@@ -188,6 +189,22 @@ PLAN_PINS = {
     ('efficientnet-b7', (2, 64, 64), 'bf16'): (322325248, 63786960, 310720, 163, ((211194368, 211456512, 211718656, 2048, 64, 32, 32, 3, 64, 64, 0, 319179520), (299639808, 299680768, 299721728, 8, 2560, 2, 2, 640, 2, 2, 299616768, 319179520))),
     ('efficientnet-b7', (3, 96, 128), 'fp32'): (847353856, 63786960, 310720, 163, ((423343360, 425702656, 428061952, 9216, 64, 48, 64, 3, 96, 128, 0, 819042304), (797800192, 798168832, 798537472, 36, 2560, 3, 4, 640, 3, 4, 797695232, 819042304))),
     ('efficientnet-b7', (3, 96, 128), 'bf16'): (460767232, 63786960, 310720, 163, ((211671808, 212851456, 214031104, 9216, 64, 48, 64, 3, 96, 128, 0, 446611456), (425737984, 425922304, 426106624, 36, 2560, 3, 4, 640, 3, 4, 425679104, 446611456))),
+    ('dynamic-cnn/64/l1/p0/k3', (2, 64, 64), 'fp32'): (10994688, 1856, 0, 0, ()),
+    ('dynamic-cnn/64/l1/p0/k3', (2, 64, 64), 'bf16'): (7688960, 1856, 0, 0, ()),
+    ('dynamic-cnn/64/l1/p0/k3', (3, 96, 128), 'fp32'): (41354496, 1856, 0, 0, ()),
+    ('dynamic-cnn/64/l1/p0/k3', (3, 96, 128), 'bf16'): (26561536, 1856, 0, 0, ()),
+    ('dynamic-cnn/64/l1/p0/k3/t0', (2, 64, 64), 'fp32'): (13091840, 1856, 0, 0, ()),
+    ('dynamic-cnn/64/l1/p0/k3/t0', (2, 64, 64), 'bf16'): (8737536, 1856, 0, 0, ()),
+    ('dynamic-cnn/64/l1/p0/k3/t0', (3, 96, 128), 'fp32'): (50791680, 1856, 0, 0, ()),
+    ('dynamic-cnn/64/l1/p0/k3/t0', (3, 96, 128), 'bf16'): (31280128, 1856, 0, 0, ()),
+    ('dynamic-cnn/64-128/l2/p1/k3', (2, 64, 64), 'fp32'): (26429184, 260544, 0, 0, ()),
+    ('dynamic-cnn/64-128/l2/p1/k3', (2, 64, 64), 'bf16'): (18159104, 260544, 0, 0, ()),
+    ('dynamic-cnn/64-128/l2/p1/k3', (3, 96, 128), 'fp32'): (148244480, 260544, 0, 0, ()),
+    ('dynamic-cnn/64-128/l2/p1/k3', (3, 96, 128), 'bf16'): (114724608, 260544, 0, 0, ()),
+    ('dynamic-cnn/64-128-256/l2/p1/k3', (2, 64, 64), 'fp32'): (35670272, 1146304, 0, 0, ()),
+    ('dynamic-cnn/64-128-256/l2/p1/k3', (2, 64, 64), 'bf16'): (22943744, 1146304, 0, 0, ()),
+    ('dynamic-cnn/64-128-256/l2/p1/k3', (3, 96, 128), 'fp32'): (164203008, 1146304, 0, 0, ()),
+    ('dynamic-cnn/64-128-256/l2/p1/k3', (3, 96, 128), 'bf16'): (123015424, 1146304, 0, 0, ()),
 }
 
 

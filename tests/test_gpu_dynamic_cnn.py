@@ -92,8 +92,13 @@ def cpu_runs(case, with_emulation):
     return cpu, x, w, runs
 
 
+# The first conv alone (one layer, no pool: dynamic-cnn/64/l1/p0/k3) on an image of odd height and width, so the rounding of the packed
+# image's width to an even number (FirstGeom) shows in every row the conv reads.  33 x 35: mmskin_backbone_create takes no side under 32.
+FIRST_CONV_ODD = ((64,), 1, False, (2, 33, 35))
+
+
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("case", do.TRUNK_CASES, ids=do.trunk_id)
+@pytest.mark.parametrize("case", do.TRUNK_CASES + (FIRST_CONV_ODD,), ids=do.trunk_id)
 def test_trunk_train_step_vs_oracle(case, dtype):
     from mmskin.backbone import HipDynamicCNNFeatures
     filters, layers, pool, _ = case
