@@ -500,6 +500,27 @@ int mmskin_window_attention_backward(const float* dO, const float* q, const floa
                                      float* dq, float* dk, float* dv, int B, int nwy, int nwx, int ws, int H, int Dh, int64_t q_tok,
                                      int64_t q_head, int64_t o_tok, int64_t o_head, float scale, float drop_p, uint64_t seed,
                                      uint64_t offset, void* stream);
+/* Shifted-window attention of the Swin Transformer (timm swin_transformer.py SwinTransformerBlock._attn around WindowAttention; reached
+ * through loadImageModelClassifier.py:117-131, train_pad_20.py:516 "swin-tiny"), fp32, one wave per (window, head), ws*ws <= 64, Dh 32 or 64,
+ * on an image-major token grid [B][Hp][Wp]: window (wy, wx), row (r, c) of the image ROLLED by (-shift_y, -shift_x) is the token
+ * ((wy ws + r + shift_y) mod Hp, (wx ws + c + shift_x) mod Wp) of the un-rolled activation -- q / k / v are read and o (dq, dk, dv) written
+ * there, so neither roll nor window_partition / window_reverse is a copy.  logit_ij = scale q_i . k_j
+ * + bias_table[(r_i - r_j + ws - 1)(2 ws - 1) + (c_i - c_j + ws - 1)][h] - 100 [region(i) != region(j)], the regions being timm's slices
+ * [0, Hp - ws), [Hp - ws, Hp - shift), [Hp - shift, Hp) per axis of the rolled image (an axis with shift 0: no wrap, no mask; timm shifts
+ * per axis, an axis no longer than the window stays unshifted).  bias_table
+ * [(2 ws - 1)^2][H]; q_tok / q_head / o_tok / o_head and dropout as mmskin_window_attention_*; lse [B*(Hp/ws)*(Wp/ws)][H][ws*ws].
+ * The backward also writes dbias_table (may be NULL: not computed), the sum of d(logit_ij) over images, windows and the pairs of each
+ * relative position, through per-window partials in `workspace` (mmskin_swin_attention_workspace_bytes, -1 for a shape the kernels
+ * refuse) and the fp64 column reducer: no atomics, bitwise repeatable.  Errors before any launch: ws*ws > 64, Dh not 32 / 64, Hp or Wp
+ * not a multiple of ws, a shift outside [0, ws), dropout outside [0, 1), a null or misaligned pointer. */
+int64_t mmskin_swin_attention_workspace_bytes(int B, int Hp, int Wp, int ws, int H);
+int mmskin_swin_attention_forward(const float* q, const float* k, const float* v, const float* bias_table, float* o, float* lse, int B, int Hp,
+                                  int Wp, int ws, int shift_y, int shift_x, int H, int Dh, int64_t q_tok, int64_t q_head, int64_t o_tok, int64_t o_head,
+                                  float scale, float drop_p, uint64_t seed, uint64_t offset, void* stream);
+int mmskin_swin_attention_backward(const float* dO, const float* q, const float* k, const float* v, const float* bias_table, const float* o,
+                                   const float* lse, float* dq, float* dk, float* dv, float* dbias_table, void* workspace, int B, int Hp,
+                                   int Wp, int ws, int shift_y, int shift_x, int H, int Dh, int64_t q_tok, int64_t q_head, int64_t o_tok, int64_t o_head,
+                                   float scale, float drop_p, uint64_t seed, uint64_t offset, void* stream);
 /* Channel attention of DaViT's ChannelBlock (timm davit.py ChannelAttention.forward; loadImageModelClassifier.py:117-131), fp32, on
  * token-major operands: per (batch, group of Dh = 32 channels)  A = softmax(scale * q^T k) [32 x 32] (the reduction runs over the N tokens),
  * x[n][i] = sum_j A[i][j] v[n][j].  q / k / v (and dq / dk / dv): element strides q_tok between tokens and q_b between batches, group g

@@ -1,6 +1,6 @@
 """Softmax attention over the C ABI: the one route decision (attention_route), the three entry points that ask it (attention,
-attention_blhd, attention_packed), the autograd Functions of the five kernel families, and DaViT's window / channel attention on the
-same packed-qkv caller.  The route table is written out once, in DESIGN.md ("The attention route"); tests/attention_route_cases.py holds
+attention_blhd, attention_packed), the autograd Functions of the five kernel families, and DaViT's window / channel attention and Swin's
+shifted-window attention (entry points of their own, outside the route) on the same packed-qkv caller.  The route table is written out once, in DESIGN.md ("The attention route"); tests/attention_route_cases.py holds
 it as data."""
 import ctypes
 import os
@@ -221,6 +221,66 @@ def window_attention(qkv, ws, dropout_p=0.0, training=False):
     nw = B * (Hp // ws) * (Wp // ws)
     seed, offset = _dropout_state(p, nw * H * (ws * ws) ** 2)
     return WindowAttentionFn.apply(qkv, ws, p, seed, offset)
+
+
+@no_second_order
+class SwinWindowAttentionFn(torch.autograd.Function):
+    """Shifted-window attention of the Swin Transformer on the packed qkv of an image-major token grid, qkv [B, Hp, Wp, 3, H, Dh] and
+    bias_table [(2 ws - 1)^2, H] -> [B, Hp, Wp, H, Dh]: the cyclic shift, the window partition, the relative-position bias gather and the
+    -100 region mask of timm's SwinTransformerBlock._attn / WindowAttention are index arithmetic of mmskin_swin_attention_*; the backward
+    writes d(qkv) packed and the table gradient through a fixed-order fp64 reduction."""
+
+    @staticmethod
+    def forward(ctx, qkv, bias_table, ws, shift, drop_p, seed, offset):
+        _need_gpu(qkv, "swin_window_attention")
+        if qkv.dim() != 6 or qkv.shape[3] != 3:
+            raise _lib.MMSkinError(f"mmskin.swin_window_attention: qkv {tuple(qkv.shape)} is not [B, Hp, Wp, 3, H, Dh]")
+        qkv, bias_table = _f32c(qkv), _f32c(bias_table)
+        B, Hp, Wp, three, H, Dh = qkv.shape
+        if ws < 1 or tuple(bias_table.shape) != ((2 * ws - 1) ** 2, H) or not bias_table.is_cuda:
+            raise _lib.MMSkinError(f"mmskin.swin_window_attention: bias table {tuple(bias_table.shape)}, expected {((2 * ws - 1) ** 2, H)} on the GPU")
+        ctx.rng = (float(drop_p), int(seed), int(offset))
+        ctx.geom = (B, Hp, Wp, int(ws), *_shift_yx(shift), H, Dh, 3 * H * Dh, Dh, H * Dh, Dh, Dh ** -0.5)
+        o = torch.empty((B, Hp, Wp, H, Dh), device=qkv.device, dtype=torch.float32)
+        lse = torch.empty((B * (Hp // ws) * (Wp // ws), H, ws * ws), device=qkv.device, dtype=torch.float32)
+        call("mmskin_swin_attention_forward", *_qkv_ptrs(qkv), ptr(bias_table), ptr(o), ptr(lse), *ctx.geom, *ctx.rng, stream())
+        ctx.save_for_backward(qkv, bias_table, o, lse)
+        return o
+
+    @staticmethod
+    def backward(ctx, dO):
+        qkv, bias_table, o, lse = ctx.saved_tensors
+        B, Hp, Wp, ws, _, _, H = ctx.geom[:7]
+        dO = _f32c(dO)
+        dqkv = torch.empty_like(qkv)
+        dtable = workspace = None
+        if ctx.needs_input_grad[1]:
+            dtable = torch.empty_like(bias_table)
+            workspace = torch.empty(_lib.load().mmskin_swin_attention_workspace_bytes(B, Hp, Wp, ws, H), device=qkv.device, dtype=torch.uint8)
+        call("mmskin_swin_attention_backward", ptr(dO), *_qkv_ptrs(qkv), ptr(bias_table), ptr(o), ptr(lse), *_qkv_ptrs(dqkv), ptr(dtable),
+             ptr(workspace), *ctx.geom, *ctx.rng, stream())
+        return dqkv, dtable, None, None, None, None, None
+
+
+def _shift_yx(shift):
+    """one shift for both axes, or timm's per-axis (shift_y, shift_x)"""
+    return (int(shift), int(shift)) if isinstance(shift, int) else (int(shift[0]), int(shift[1]))
+
+
+def swin_window_attention_ok(qkv, bias_table, ws, shift):
+    """shapes mmskin_swin_attention_* takes: fp32 packed qkv [B, Hp, Wp, 3, H, Dh] and table [(2 ws - 1)^2, H] on the GPU, Hp / Wp
+    multiples of ws, ws*ws <= 64, 0 <= shift < ws (one int, or one per axis), Dh 32 / 64"""
+    return (qkv.is_cuda and qkv.dtype == torch.float32 and qkv.dim() == 6 and qkv.shape[3] == 3 and qkv.is_contiguous() and ws >= 1
+            and qkv.shape[1] % ws == 0 and qkv.shape[2] % ws == 0 and _rows_ok(ws * ws, qkv.shape[5]) and all(0 <= s < ws for s in _shift_yx(shift))
+            and bias_table.is_cuda and bias_table.dtype == torch.float32 and tuple(bias_table.shape) == ((2 * ws - 1) ** 2, qkv.shape[4]))
+
+
+def swin_window_attention(qkv, bias_table, ws, shift, dropout_p=0.0, training=False):
+    """softmax(q k^T / sqrt(Dh) + relative-position bias + shift mask) v inside every ws x ws window of the token grid rolled by
+    (-shift, -shift) -- or by (-shift[0], -shift[1]) -- and written back un-rolled; qkv [B, Hp, Wp, 3, H, Dh], bias_table [(2 ws - 1)^2, H] -> [B, Hp, Wp, H, Dh]."""
+    p = dropout_p if training else 0.0
+    seed, offset = _dropout_state(p, qkv.numel() // (3 * qkv.shape[-1]) * (ws * ws) if qkv.dim() == 6 else 0)
+    return SwinWindowAttentionFn.apply(qkv, bias_table, ws, shift, p, seed, offset)
 
 
 @no_second_order

@@ -15,7 +15,8 @@ from ._autograd import (_dropout_counter, _dropout_state, _dtype_code, _f32c, _n
                         no_second_order)
 from ._lib import call, ptr, stream
 from .attention import (LongAttentionFn, _bmm, attention, attention_blhd, attention_packed, attention_route,  # noqa: F401
-                        channel_attention, channel_attention_ok, window_attention, window_attention_ok)
+                        channel_attention, channel_attention_ok, swin_window_attention, swin_window_attention_ok, window_attention,
+                        window_attention_ok)
 
 
 # ---------------------------------------------------------------------------------------------- the Linear family (csrc/linear.hip)

@@ -3,7 +3,7 @@
 Same static-method API, argument meaning, return values and error strings as the reference's
 ``loadModels``.  Image backbones with a gfx950 plan: ``custom-cnn``, ``resnet-18``, ``resnet-50``,
 ``densenet169``, ``vgg16``, ``mobilenet-v2``, ``efficientnet-b0/b7``, and the timm encoders ``beitv2_*``, ``vit_*``,
-``davit_*``, ``caformer_*`` and ``coat_lite_*``.
+``davit_*``, ``caformer_*``, ``coat_lite_*`` and ``swin_*_patch4_window7_224``.
 Weights are randomly initialised (torchvision layout and init); pretrained checkpoints are loaded by
 the caller with ``load_state_dict`` -- there is no network access from this package.
 """
@@ -77,7 +77,7 @@ class loadModels:
                     p.requires_grad = True
             else:
                 loadModels.set_backbone_train_mode(model, backbone_train_mode)
-        elif cnn_model_name.startswith(("beitv2_", "vit_", "davit_", "caformer_", "coat_")):
+        elif cnn_model_name.startswith(("beitv2_", "vit_", "davit_", "caformer_", "coat_", "swin_", "swinv2_")):
             # the reference's generic timm branch (:117-152): create_model(name) + reset_classifier(0), F = num_features,
             # "partial" unfreezes the last block
             if cnn_model_name.startswith("beitv2_"):
@@ -92,6 +92,9 @@ class loadModels:
             elif cnn_model_name.startswith("coat_"):
                 from hip_coat import HipCoaT
                 model = HipCoaT(cnn_model_name)
+            elif cnn_model_name.startswith(("swin_", "swinv2_")):
+                from hip_swin import HipSwinTransformer
+                model = HipSwinTransformer(cnn_model_name)      # Swin-V2 and the window-12 models: NotImplementedError naming the configs
             else:
                 from hip_vit import HipVisionTransformer
                 model = HipVisionTransformer(cnn_model_name)
@@ -104,7 +107,8 @@ class loadModels:
                 else:
                     # reference :135-140, "fallback: último child".  CoaT has neither `stages` nor `blocks`; its last child after
                     # reset_classifier(0) is the Identity head, which has no parameters: "partial" leaves a CoaT encoder fully
-                    # frozen, exactly as the reference does.
+                    # frozen, exactly as the reference does.  Swin is the same case: its stages are called `layers`, and its last
+                    # child is the parameter-less ClassifierHead.
                     last = list(model.children())[-1]
                 for p in last.parameters():
                     p.requires_grad = True
