@@ -12,6 +12,20 @@ SMALL = dict(num_classes=6, num_heads=8, device="cpu", cnn_model_name="custom-cn
              vocab_size=20, unfreeze_weights="unfrozen_weights")
 
 
+def arena(shapes, dev, seed):
+    """One flat randn tensor on `dev` and Parameters that are consecutive views of it (what mmskin/backbone.py's _repack builds)."""
+    g = torch.Generator().manual_seed(seed)
+    n = sum(int(torch.tensor(s).prod()) for s in shapes)
+    flat = torch.randn(n, generator=g).to(dev)
+    ps, off = [], 0
+    for s in shapes:
+        k = int(torch.tensor(s).prod())
+        p = torch.nn.Parameter(torch.empty(0, device=dev))
+        p.data = flat[off:off + k].view(s)
+        ps.append(p); off += k
+    return flat, ps
+
+
 def golden(name):
     with open(os.path.join(GOLDEN, name + ".json")) as f:
         return json.load(f)

@@ -1,14 +1,17 @@
 """mmskin.optim.Adam: torch.optim.Adam's update (train_pad_20.py:54,113) with one launch per flat parameter arena.
-CPU: the class is a plain drop-in (no arena -> torch's own step).  -m gpu: arena runs against torch.optim.Adam on the same values."""
+CPU: the class is a plain drop-in (no arena -> torch's own step; hooks, closure, no run on CPU tensors).  -m gpu: arena runs against
+torch.optim.Adam on the same values (the scenarios where runs change are in test_gpu_optim.py)."""
 import os
 import sys
 
 import pytest
 import torch
+from torch.optim.optimizer import register_optimizer_step_post_hook
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "multimodal-model-skin-lesion-classifier_amd")]
 from mmskin.optim import Adam   # noqa: E402
+from helpers import arena as _arena   # noqa: E402
 
 
 def test_cpu_parameters_take_torchs_own_step():
@@ -25,17 +28,75 @@ def test_cpu_parameters_take_torchs_own_step():
     assert o2.state_dict()["state"].keys() == o1.state_dict()["state"].keys()
 
 
-def _arena(shapes, dev, seed):
-    g = torch.Generator().manual_seed(seed)
-    n = sum(int(torch.tensor(s).prod()) for s in shapes)
-    flat = torch.randn(n, generator=g).to(dev)
-    ps, off = [], 0
-    for s in shapes:
-        k = int(torch.tensor(s).prod())
-        p = torch.nn.Parameter(torch.empty(0, device=dev))
-        p.data = flat[off:off + k].view(s)
-        ps.append(p); off += k
-    return flat, ps
+@pytest.mark.parametrize("plain_first", [True, False])
+def test_step_hooks_fire_once_per_step(plain_first):
+    """A plain torch.optim.Adam created elsewhere in the process wraps torch.optim.Adam.step at class level with the hook runner, and
+    mmskin's step() calls that method: every pre-, post- and global post-hook still fires exactly once per step(), whether the plain
+    optimizer was created before the arena optimizer or after it."""
+    w = [torch.randn(5, 3, requires_grad=True), torch.randn(7, requires_grad=True)]
+    other = [torch.randn(3, requires_grad=True)]
+    if plain_first:
+        torch.optim.Adam(other, lr=1e-2)
+    o = Adam(w, lr=1e-2)
+    if not plain_first:
+        torch.optim.Adam(other, lr=1e-2)
+    fired = dict(pre=0, post=0, glob=0)
+
+    def count(key):
+        def hook(opt, args, kwargs):
+            if opt is o:
+                fired[key] += 1
+        return hook
+
+    handles = [o.register_step_pre_hook(count("pre")), o.register_step_post_hook(count("post")),
+               register_optimizer_step_post_hook(count("glob"))]
+    try:
+        for it in range(1, 4):
+            for p in w:
+                p.grad = torch.randn_like(p)
+            o.step()
+            assert fired == dict(pre=it, post=it, glob=it)
+    finally:
+        for h in handles:
+            h.remove()
+    assert float(o.state[w[0]]["step"]) == 3.0      # what a scheduler or logger that counts steps sees
+
+
+def test_step_returns_the_closures_loss_and_applies_its_gradients():
+    torch.manual_seed(1)
+    w1 = [torch.randn(5, 3, requires_grad=True)]
+    w2 = [w1[0].detach().clone().requires_grad_(True)]
+    o1, o2 = torch.optim.Adam(w1, lr=1e-2), Adam(w2, lr=1e-2)
+
+    def closure(w, opt):
+        def run():
+            opt.zero_grad()
+            loss = (w[0] ** 2).sum()
+            loss.backward()
+            return loss
+        return run
+
+    for _ in range(2):
+        w2[0].grad = torch.full_like(w2[0], 1e3)      # stale: the closure's gradient is the one applied
+        l1, l2 = o1.step(closure(w1, o1)), o2.step(closure(w2, o2))
+        assert float(l1) == float(l2) and torch.equal(w1[0], w2[0])
+
+
+def test_find_runs_needs_cuda_tensors_with_gradients():
+    """An arena of CPU tensors (with gradients laid out as the backward would) forms no run, and neither do members that take no
+    gradient (requires_grad=False): the arena path is for CUDA parameters that are being trained."""
+    flat, ps = _arena([(300, 300), (256, 300), (70000,)], "cpu", 3)
+    gflat, off = torch.randn(flat.numel()), 0
+    for p in ps:
+        p.grad = gflat[off:off + p.numel()].view(p.shape); off += p.numel()
+    assert Adam._find_runs(ps) == [] and Adam._find_runs(ps, lambda q: 0) == []
+    o = Adam(ps, lr=1e-3)
+    o.step()
+    assert o._runs == {}
+    frozen = _arena([(300, 300), (256, 300)], "cpu", 4)[1]
+    for p in frozen:
+        p.requires_grad_(False)
+    assert all(p.grad is None for p in frozen) and Adam._find_runs(frozen) == []
 
 
 @pytest.mark.gpu
