@@ -477,7 +477,9 @@ __global__ __launch_bounds__(256) void flash_fwd2_kernel(const FlashArgs p) {
       if constexpr (sizeof(IO) == 4) *reinterpret_cast<float4*>(dst) = make_float4(a0, a1, a2, a3);
       else *reinterpret_cast<uint2*>(dst) = make_uint2(pack_bf16(a0, a1), pack_bf16(a2, a3));
     }
-  if (p.lse && hh == 0) p.lse[(int64_t)bh * L + qi] = m_run * 0.6931471805599453f + __logf(fmaxf(l_run, 1e-38f));
+  // A running maximum still at -FLT_MAX is a row whose keys all carry a key mask that saturated in the log2 domain (HF's finfo.min times
+  // log2 e, clamped above): its natural-log score is the mask itself, -FLT_MAX, as flash_fwd_kernel gives it -- not -FLT_MAX ln 2.
+  if (p.lse && hh == 0) p.lse[(int64_t)bh * L + qi] = (m_run > -3.4028235e38f ? m_run * 0.6931471805599453f : m_run) + __logf(fmaxf(l_run, 1e-38f));
 }
 
 }  // namespace

@@ -13,9 +13,9 @@
 // Two kernels, both the forward kernel's tile machinery (64-row tiles, bf16 operands, fp32 accumulation, 16x16x32 MFMA, LDS row
 // pitch D * 2 + 16 B that serves b128 row reads and transposing reads alike, one barrier per streamed tile):
 //   * flash_bwd_dq_kernel : one workgroup = 64 QUERY rows, K / V tiles streamed; S and dP in the accumulator layout (a key per lane,
-//     four queries per lane), dS -> bf16 -> a wave-private LDS tile -> A operand of dQ += dS K (K by transposing reads);
+//     four queries per lane), dS -> bf16 hi + lo -> a wave-private LDS tile -> A operands of dQ += dS K (K by transposing reads);
 //   * flash_bwd_dkv_kernel: one workgroup = 64 KEY rows, Q / dO tiles streamed; S^T and dP^T (a query per lane, four keys per lane),
-//     (P . keep)^T and dS^T through wave-private tiles -> dV += P^T dO, dK += dS^T Q.
+//     (P . keep)^T and dS^T, each as bf16 hi + lo, through wave-private tiles -> dV += P^T dO, dK += dS^T Q.
 // Each recomputes S (2 x the forward's QK^T); neither needs a reduction across workgroups, so the result is deterministic.
 // The dropout mask is regenerated from the forward's counter (element index of the [B, H, L, L] tensor).  q, k, v, o, dO, dq, dk, dv are
 // fp32 with element strides (last dim contiguous); bias [H, L, L] and its transpose biasT [H, key, query] (coalesced in the second
@@ -52,6 +52,14 @@ __device__ __forceinline__ uint32_t fb_pack(float a, float b) { return f32_to_bf
 __device__ __forceinline__ uint4 fb_load8(const float* p) {
   const float4 a = *reinterpret_cast<const float4*>(p), c = *reinterpret_cast<const float4*>(p + 4);
   return make_uint4(fb_pack(a.x, a.y), fb_pack(a.z, a.w), fb_pack(c.x, c.y), fb_pack(c.z, c.w));
+}
+// An fp32 value as TWO bf16 MFMA operands, hi = bf16(x) and lo = bf16(x - hi): hi + lo carries 16 significant bits.  dS and P^T enter
+// the gradient products this way -- a single bf16 rounding (2^-8 of each term) put the worst element of dQ / dK / dV 2 - 3 % of the
+// rms off on heavy-tailed softmax weights (tests/test_gpu_flash_probe.py (f)).
+__device__ __forceinline__ uint16_t fb_split(float x, uint16_t& lo) {
+  const uint32_t hi = f32_to_bf16_bits(x);
+  lo = (uint16_t)f32_to_bf16_bits(x - bf16_bits_to_f32(hi));
+  return (uint16_t)hi;
 }
 __device__ __forceinline__ f32x4_t fb_mma(const uint4& a, const uint4& b, f32x4_t c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
@@ -153,6 +161,7 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(const FlashBwdArgs p)
       }
     }
     if (t + 1 < nt) load_tile(t + 1);
+    uint16_t dlo[4][4];      // the lo halves of scale dS, written over the tile once its hi fragments are in registers
     // ---- S = Q K^T, dP = dO V^T (a key per lane, queries 4 g + r)
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
@@ -175,19 +184,31 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(const FlashBwdArgs p)
         if (p.drop_p > 0.f && valid) zs = attn_keep(dk, attn_row_base((uint64_t)bh * L + (uint64_t)qi, Lh), kj) ? inv_keep : 0.f;
         const float ds = pr * (dp[r] * zs - dl_r[r]);
         if (p.ds_out && valid) p.ds_out[(((int64_t)bh * L + qi) * L) + kj] = ds;
-        *reinterpret_cast<uint16_t*>(Ps + (4 * g + r) * PPITCH + (16 * n + l15) * 2) = (uint16_t)f32_to_bf16_bits(ds * p.scale);
+        *reinterpret_cast<uint16_t*>(Ps + (4 * g + r) * PPITCH + (16 * n + l15) * 2) = fb_split(ds * p.scale, dlo[n][r]);
       }
     }
-    // ---- dQ += dS K : A = dS [16 q x 32 keys] (row reads of the wave-private tile), B = K [32 keys x 16 d] (transposing reads)
+    // ---- dQ += dS K : A = dS [16 q x 32 keys] (row reads of the wave-private tile), B = K [32 keys x 16 d] (transposing reads).
+    // dS = hi + lo: the hi fragments are read, the lo halves go over the same tile (DS instructions of one wave execute in order)
+    // and are read in turn; every K fragment then feeds two MFMAs.
+    uint4 pfh[2], pfl[2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) pfh[ks] = *reinterpret_cast<const uint4*>(Ps + l15 * PPITCH + (32 * ks + 8 * g) * 2);
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) *reinterpret_cast<uint16_t*>(Ps + (4 * g + r) * PPITCH + (16 * n + l15) * 2) = dlo[n][r];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) pfl[ks] = *reinterpret_cast<const uint4*>(Ps + l15 * PPITCH + (32 * ks + 8 * g) * 2);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      const uint4 pf = *reinterpret_cast<const uint4*>(Ps + l15 * PPITCH + (32 * ks + 8 * g) * 2);
       const int r0 = 32 * ks + 8 * g + tq, r1 = r0 + 4;
 #pragma unroll
       for (int dn = 0; dn < DN; ++dn) {
         const int colb = (16 * dn + 4 * tp) * 2;
         const uint2 lo = fb_tr16_b64(Ks + r0 * PITCH + colb), hi = fb_tr16_b64(Ks + r1 * PITCH + colb);
-        acc[dn] = fb_mma(pf, make_uint4(lo.x, lo.y, hi.x, hi.y), acc[dn]);
+        const uint4 kfr = make_uint4(lo.x, lo.y, hi.x, hi.y);
+        acc[dn] = fb_mma(pfh[ks], kfr, acc[dn]);
+        acc[dn] = fb_mma(pfl[ks], kfr, acc[dn]);
       }
     }
     if (t + 1 < nt) store_tile((t + 1) & 1);
@@ -278,6 +299,7 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(const FlashBwdArgs p
       }
     }
     if (t + 1 < nt) load_tile(t + 1);
+    uint16_t plo[4][4], dlo[4][4];      // the lo halves of (P . keep)^T and scale dS^T
     // ---- S^T = K Q^T, dP^T = V dO^T (a query per lane, keys 4 g + r)
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
@@ -299,23 +321,45 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(const FlashBwdArgs p
         float zs = 1.f;
         if (p.drop_p > 0.f && valid) zs = attn_keep(dk, attn_row_base((uint64_t)bh * L + (uint64_t)qi, Lh), kj) ? inv_keep : 0.f;
         const float ds = pr * (dp[r] * zs - dl_c[n]);
-        *reinterpret_cast<uint16_t*>(Pt + (4 * g + r) * PPITCH + (16 * n + l15) * 2) = (uint16_t)f32_to_bf16_bits(pr * zs);
-        *reinterpret_cast<uint16_t*>(St + (4 * g + r) * PPITCH + (16 * n + l15) * 2) = (uint16_t)f32_to_bf16_bits(ds * p.scale);
+        *reinterpret_cast<uint16_t*>(Pt + (4 * g + r) * PPITCH + (16 * n + l15) * 2) = fb_split(pr * zs, plo[n][r]);
+        *reinterpret_cast<uint16_t*>(St + (4 * g + r) * PPITCH + (16 * n + l15) * 2) = fb_split(ds * p.scale, dlo[n][r]);
       }
     }
-    // ---- dV += (P . keep)^T dO,  dK += dS^T Q : A = the wave-private [16 keys x 64 queries] tiles (row reads), B = dO / Q (transposing reads)
+    // ---- dV += (P . keep)^T dO,  dK += dS^T Q : A = the wave-private [16 keys x 64 queries] tiles (row reads), B = dO / Q (transposing reads).
+    // Both A operands are hi + lo: hi fragments to registers, lo halves over the same tiles (in-order DS of one wave), lo fragments;
+    // every dO / Q fragment then feeds two MFMAs.
+    uint4 pfh[2], sfh[2], pfl[2], sfl[2];
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      const uint4 pf = *reinterpret_cast<const uint4*>(Pt + l15 * PPITCH + (32 * ks + 8 * g) * 2);
-      const uint4 sf = *reinterpret_cast<const uint4*>(St + l15 * PPITCH + (32 * ks + 8 * g) * 2);
+      pfh[ks] = *reinterpret_cast<const uint4*>(Pt + l15 * PPITCH + (32 * ks + 8 * g) * 2);
+      sfh[ks] = *reinterpret_cast<const uint4*>(St + l15 * PPITCH + (32 * ks + 8 * g) * 2);
+    }
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        *reinterpret_cast<uint16_t*>(Pt + (4 * g + r) * PPITCH + (16 * n + l15) * 2) = plo[n][r];
+        *reinterpret_cast<uint16_t*>(St + (4 * g + r) * PPITCH + (16 * n + l15) * 2) = dlo[n][r];
+      }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      pfl[ks] = *reinterpret_cast<const uint4*>(Pt + l15 * PPITCH + (32 * ks + 8 * g) * 2);
+      sfl[ks] = *reinterpret_cast<const uint4*>(St + l15 * PPITCH + (32 * ks + 8 * g) * 2);
+    }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
       const int r0 = 32 * ks + 8 * g + tq, r1 = r0 + 4;
 #pragma unroll
       for (int dn = 0; dn < DN; ++dn) {
         const int colb = (16 * dn + 4 * tp) * 2;
         const uint2 glo = fb_tr16_b64(Gs + r0 * PITCH + colb), ghi = fb_tr16_b64(Gs + r1 * PITCH + colb);
-        dva[dn] = fb_mma(pf, make_uint4(glo.x, glo.y, ghi.x, ghi.y), dva[dn]);
+        const uint4 gfr = make_uint4(glo.x, glo.y, ghi.x, ghi.y);
+        dva[dn] = fb_mma(pfh[ks], gfr, dva[dn]);
+        dva[dn] = fb_mma(pfl[ks], gfr, dva[dn]);
         const uint2 qlo = fb_tr16_b64(Qs + r0 * PITCH + colb), qhi = fb_tr16_b64(Qs + r1 * PITCH + colb);
-        dka[dn] = fb_mma(sf, make_uint4(qlo.x, qlo.y, qhi.x, qhi.y), dka[dn]);
+        const uint4 qfr = make_uint4(qlo.x, qlo.y, qhi.x, qhi.y);
+        dka[dn] = fb_mma(sfh[ks], qfr, dka[dn]);
+        dka[dn] = fb_mma(sfl[ks], qfr, dka[dn]);
       }
     }
     if (t + 1 < nt) store_tile((t + 1) & 1);
