@@ -796,6 +796,50 @@ int mmskin_sweep_reduce(const void* logits, int logits_dtype, const float* base,
                         int32_t* confusion, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Shapley values of the metadata columns on the model itself (csrc/shapley.hip, mmskin.shapley.MetadataShapley): the image is
+ * encoded once, the fusion head runs on the rows of an antithetic permutation walk, these are the kernels before and after
+ * the head.  Players are the encoder's M = n_cat + n_num COLUMNS (a categorical column is its whole one-hot block), numbered
+ * categorical first as in metadata_variants.  With G background rows, P permutations and K = 2 P (M - 1):
+ *     v(S) = (1/G) sum_g out(head(f, mix(x, b_g, S)))       mix takes column j from x if j is in S, else from b_g
+ *     phi_j = (1/2P) sum_p [ v(S_{q+1}) - v(S_q) + v(T_{M-q}) - v(T_{M-q-1}) ]     q = position of j in permutation p
+ * S_n / T_n = the first / last n entries of the permutation; S_0 = T_0 = empty and S_M = T_M = all are shared by all p.
+ *
+ * Row order of a batch's walk, mmskin_shapley_rows = batch (1 + G + K G) rows (-1 for extents out of range):
+ *     rows [0, batch (K+1) G)      row ((b (K+1) + k) G + g): sample b, coalition k, background row g, where
+ *                                  k = (p 2 + side) (M-1) + (n-1) is S_n (side 0) or T_n (side 1) of permutation p,
+ *                                  n = 1 .. M-1, and k = K is the empty coalition (G rows)
+ *     the last `batch` rows        row b of them is x_b unmixed (v(all), one row per sample)
+ * Both entry points take a row range [row0, row1) of that order and the buffer of THAT RANGE (out / logits point at row0).
+ *
+ * shapley_coalitions: codes int32 [batch][n_cat], numeric fp32 [batch][n_num] (NaN = missing) of the explained rows, bg_codes
+ * [G][n_cat] and bg_numeric [G][n_num] of the background; col_offset, onehot_width, mean, scale, nan_fill as
+ * mmskin_metadata_encode takes them and col_offset_host a host copy; perm_host int32 [P][M] in HOST memory, validated (every
+ * row a permutation of 0 .. M-1), inverted and uploaded on `stream` into pos_scratch, P x M int32 of device memory that the
+ * caller only provides (allocated until the kernel has run).  out fp32 [row1 - row0][out_width]: each row is the encoding of
+ * the mixed raw row exactly as mmskin_metadata_encode gives it (bit for bit; -1 = unseen code = all-zero block, NaN filled),
+ * zeros beyond the encoder's width, cut when out_width is smaller.  Every element is written once, no atomics.
+ *
+ * shapley_reduce: logits [row1 - row0][C], fp32 (logits_dtype 0) or bf16 (1), of a range whose ends below batch (K+1) G are
+ * multiples of G (whole coalitions).  output: MMSKIN_SHAPLEY_PROB (soft-max, exp(x - max) / sum in fp32) or _LOGIT.  It fills
+ * v fp64 [batch][K + 2][C]: the mean over each coalition's G rows in fp64 in a fixed order, entry K = v(empty), K + 1 =
+ * v(all).  The ranges of several calls fill v chunk by chunk.  finish != 0, on the call that completes v, then writes phi fp32
+ * [batch][M][C] (the sum over p = 0 .. P-1 in fp64, in that order), base = v(empty) and full = v(all) fp32 [batch][C], and,
+ * with abs_sum non-null, ADDS |phi| over b = 0 .. batch-1, in that order, into the caller-zeroed fp64 [M][C] abs_sum; it needs
+ * perm_host / pos_scratch as above.  No atomics anywhere: two runs are bitwise equal.  An empty range with finish is allowed.
+ * Errors (nothing is launched): an extent < 1, a table row that is not a permutation, a range outside the walk or one that
+ * splits a coalition, null arguments; 2 <= C <= 64, anything else is MMSKIN_ERR_UNSUPPORTED. */
+#define MMSKIN_SHAPLEY_PROB 0
+#define MMSKIN_SHAPLEY_LOGIT 1
+int64_t mmskin_shapley_rows(int batch, int G, int P, int M);
+int mmskin_shapley_coalitions(const int32_t* codes, const float* numeric, int batch, const int32_t* bg_codes, const float* bg_numeric,
+                              int G, int n_cat, const int32_t* col_offset, const int32_t* col_offset_host, int onehot_width, int n_num,
+                              const float* mean, const float* scale, float nan_fill, const int32_t* perm_host, int32_t* pos_scratch,
+                              int P, int64_t row0, int64_t row1, float* out, int out_width, void* stream);
+int mmskin_shapley_reduce(const void* logits, int logits_dtype, int output, int batch, int G, int P, int M, int C, int64_t row0,
+                          int64_t row1, double* v, int finish, const int32_t* perm_host, int32_t* pos_scratch, float* phi, float* base,
+                          float* full, double* abs_sum, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The criterion (csrc/criterion.hip): one forward and one backward launch for three kinds of loss on logits [B][C], row-major,
  * fp32 (logits_dtype 0) or bf16 (1); all arithmetic fp32.  1 <= B <= 2^20, 2 <= C <= 1024.  With m = max z_i,
  * ls = ln sum exp(z_i - m), ce = ls - (z_i[y] - m), p = softmax(z_i):

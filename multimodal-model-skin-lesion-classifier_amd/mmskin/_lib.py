@@ -200,6 +200,9 @@ _SIGNATURES = {
     "mmskin_gradcam_map": (_i, [_P] * 3 + [_i] * 7 + [_P] * 3),
     "mmskin_metadata_variants": (_i, [_P, _i, _P, _P, _i, _P, _i, _P, _P, _f, _P, _P, _i, _P, _P, _P, _i, _i, _P]),
     "mmskin_sweep_reduce": (_i, [_P, _i, _P, _P, _i, _i, _i] + [_P] * 7 + [_P]),
+    "mmskin_shapley_rows": (_i64, [_i] * 4),
+    "mmskin_shapley_coalitions": (_i, [_P, _P, _i, _P, _P, _i, _i, _P, _P, _i, _i, _P, _P, _f, _P, _P, _i, _i64, _i64, _P, _i, _P]),
+    "mmskin_shapley_reduce": (_i, [_P, _i, _i] + [_i] * 5 + [_i64, _i64, _P, _i] + [_P] * 6 + [_P]),
     "mmskin_criterion_scratch_floats": (_i64, [_i, _i, _i]),
     "mmskin_criterion_forward": (_i, [_P, _i, _P, _P, _i, _i, _f, _i, _i] + [_P] * 6),
     "mmskin_criterion_backward": (_i, [_P, _i, _P, _P, _i, _i, _f, _i, _i] + [_P] * 4),

@@ -1222,3 +1222,85 @@ def sweep_reduce(logits, base, flips, transitions, confusion=None, labels=None, 
     call("mmskin_sweep_reduce", ptr(logits), _dtype_code(logits), ptr(base), ptr(labels), V, B, C, ptr(probs), ptr(pred), ptr(margin),
          ptr(stats), ptr(flips), ptr(transitions), ptr(confusion) if labels is not None else None, stream())
     return probs, pred, margin, stats
+
+
+# ---------------------------------------------------------------------------------------------- metadata Shapley values (forward only)
+SHAPLEY_PROB, SHAPLEY_LOGIT = 0, 1                                                           # MMSKIN_SHAPLEY_* of mmskin.h
+
+
+def shapley_rows(batch, G, P, M):
+    """Rows of a batch's coalition walk, batch * (1 + G + P * 2 * (M - 1) * G), in the row order of include/mmskin.h."""
+    n = int(_lib.load().mmskin_shapley_rows(int(batch), int(G), int(P), int(M)))
+    if n < 0:
+        raise ValueError(f"shapley_rows: batch {batch}, G {G}, P {P}, M {M}: an extent is < 1 or the walk is out of range")
+    return n
+
+
+def _shapley_table(perms, M, what):
+    perms = np.ascontiguousarray(perms)
+    if perms.dtype != np.int32 or perms.ndim != 2 or perms.shape[1] != M:
+        raise ValueError(f"{what}: perms must be an int32 [P, {M}] table, got {perms.dtype} {perms.shape}")
+    return perms
+
+
+def shapley_coalitions(codes, numeric, bg_codes, bg_numeric, col_offset, mean, scale, nan_fill, perms, out_width, row0=0, row1=None,
+                       out=None):
+    """The encoded metadata rows [row1 - row0, out_width] of rows [row0, row1) of a batch's coalition walk, in one kernel
+    (mmskin_shapley_coalitions).  codes int32 [B, n_cat] / numeric fp32 [B, n_num] of the explained rows and bg_codes [G, n_cat] /
+    bg_numeric [G, n_num] of the background on the device; col_offset a HOST int32 array [n_cat + 1]; mean / scale fp32 [n_num] on
+    the device; perms a HOST int32 [P, M] table of permutations (validated by the library)."""
+    _need_gpu(codes, "shapley_coalitions")
+    (B, n_cat), n_num, G = codes.shape, numeric.shape[1], bg_codes.shape[0]
+    dev = codes.device
+    perms = _shapley_table(perms, n_cat + n_num, "shapley_coalitions")
+    _dev_tensor(codes, torch.int32, (B, n_cat), "shapley_coalitions: codes")
+    _dev_tensor(numeric, torch.float32, (B, n_num), "shapley_coalitions: numeric")
+    _dev_tensor(bg_codes, torch.int32, (G, n_cat), "shapley_coalitions: bg_codes")
+    _dev_tensor(bg_numeric, torch.float32, (G, n_num), "shapley_coalitions: bg_numeric")
+    off_host = np.ascontiguousarray(col_offset, dtype=np.int32)
+    if off_host.shape != (n_cat + 1,):
+        raise ValueError(f"shapley_coalitions: col_offset must have {n_cat + 1} entries, got {off_host.shape}")
+    if n_num:
+        _dev_tensor(mean, torch.float32, (n_num,), "shapley_coalitions: mean")
+        _dev_tensor(scale, torch.float32, (n_num,), "shapley_coalitions: scale")
+    P, out_width, row0 = len(perms), int(out_width), int(row0)
+    row1 = shapley_rows(B, G, P, n_cat + n_num) if row1 is None else int(row1)
+    if out is None:
+        out = torch.empty((max(row1 - row0, 0), max(out_width, 0)), device=dev, dtype=torch.float32)
+    else:
+        _dev_tensor(out, torch.float32, (row1 - row0, out_width), "shapley_coalitions: out")
+    off_dev = torch.from_numpy(off_host).to(dev)
+    scratch = torch.empty(max(perms.size, 1), dtype=torch.int32, device=dev)          # the library uploads the inverse table into it
+    call("mmskin_shapley_coalitions", ptr(codes), ptr(numeric), B, ptr(bg_codes), ptr(bg_numeric), G, n_cat, ptr(off_dev),
+         ctypes.c_void_p(off_host.ctypes.data), int(off_host[-1]), n_num, ptr(mean) if n_num else None, ptr(scale) if n_num else None,
+         float(nan_fill), ctypes.c_void_p(perms.ctypes.data), ptr(scratch), P, row0, row1, ptr(out), out_width, stream())
+    return out
+
+
+def shapley_reduce(logits, v, perms, G, row0, output=SHAPLEY_PROB, finish=False, abs_sum=None):
+    """logits [rows, C] (fp32 or bf16) of rows [row0, row0 + rows) of the walk -> the coalition means into v fp64 [B, K + 2, C]
+    (K = 2 P (M - 1); mmskin_shapley_reduce).  The range is cut at multiples of G.  With finish, on the call that completes v:
+    returns (phi fp32 [B, M, C], base [B, C] = v(empty), full [B, C] = v(all)) and ADDS sum_b |phi| into abs_sum fp64 [M, C] when
+    that is given; otherwise returns None."""
+    _need_gpu(logits, "shapley_reduce")
+    if logits.dim() != 2 or logits.dtype not in (torch.float32, torch.bfloat16) or not logits.is_contiguous():
+        raise ValueError(f"shapley_reduce: logits must be a contiguous fp32 or bf16 [rows, C] tensor, got {logits.dtype} {tuple(logits.shape)}")
+    perms = np.ascontiguousarray(perms)
+    if perms.dtype != np.int32 or perms.ndim != 2:
+        raise ValueError(f"shapley_reduce: perms must be an int32 [P, M] table, got {perms.dtype} {perms.shape}")
+    (rows, C), (P, M), dev = logits.shape, perms.shape, logits.device
+    if v is None or v.dim() != 3:
+        raise ValueError("shapley_reduce: v must be a float64 [B, K + 2, C] device tensor")
+    B = v.shape[0]
+    _dev_tensor(v, torch.float64, (B, 2 * P * (M - 1) + 2, C), "shapley_reduce: v")
+    phi = base = full = scratch = None
+    if finish:
+        phi = torch.empty((B, M, C), device=dev, dtype=torch.float32)
+        base, full = torch.empty((B, C), device=dev, dtype=torch.float32), torch.empty((B, C), device=dev, dtype=torch.float32)
+        scratch = torch.empty(max(perms.size, 1), dtype=torch.int32, device=dev)
+        if abs_sum is not None:
+            _dev_tensor(abs_sum, torch.float64, (M, C), "shapley_reduce: abs_sum")
+    call("mmskin_shapley_reduce", ptr(logits), _dtype_code(logits), int(output), B, int(G), P, M, C, int(row0), int(row0) + rows, ptr(v),
+         int(bool(finish)), ctypes.c_void_p(perms.ctypes.data), ptr(scratch), ptr(phi), ptr(base), ptr(full),
+         ptr(abs_sum) if finish else None, stream())
+    return (phi, base, full) if finish else None
