@@ -840,6 +840,62 @@ int mmskin_shapley_reduce(const void* logits, int logits_dtype, int output, int 
                           float* full, double* abs_sum, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * LIME explanations of the encoded metadata columns on the model itself (csrc/lime.hip, mmskin.lime.MetadataLime): what lime's
+ * LimeTabularExplainer(mode="regression", discretize_continuous=False).explain_instance(row, predict_fn, num_features=K) does,
+ * with the network as predict_fn.  F <= 128 features (every encoded column, one-hot cells included, as a continuous feature),
+ * N rows per explained sample, rows sample-major: row = b N + s.  mean / scale: fp64 [F] on the device, the StandardScaler of
+ * the encoded training rows (scale has no zero: the caller replaces 0 by 1).
+ *     row_0 = x bit for bit;  row_s[f] = n(s, f) * (float)scale[f] + (float)mean[f]   (around_instance: + x[f]), in fp32, unfused
+ *     z = ((double)row - mean) / scale;  d_s = |z_s - z_0|_2;  w_s = sqrt(exp(-d_s^2 / (0.75 sqrt F)^2))
+ * The generator: h = mix64(mix64(seed) ^ (sample << 40 | s << 8 | f)), mix64 = the splitmix64 finaliser (x += 0x9E3779B97F4A7C15;
+ * x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31), sample = sample0 + b;
+ * u1 = ((h >> 41) + 0.5) 2^-23, u2 = (((h & 0xffffffff) >> 9) + 0.5) 2^-23, n = sqrtf(-2 logf(u1)) cosf(6.2831855f u2), fp32.
+ * n depends on (seed, sample, s, f) only, so any row range gives the bytes of one full call.
+ *
+ * All three entry points take a row range [row0, row1) and the buffers OF THAT RANGE (out / rows / w / logits point at row0).
+ *
+ * lime_neighbourhood: x fp32 [batch][x_stride] -> out fp32 [row1 - row0][out_width] (columns >= F zero) and the weights
+ * w [row1 - row0], fp32 (MMSKIN_LIME_W_F32) or fp64 (_F64), computed from the row just written.  Every element is written once.
+ *
+ * lime_reduce: the rows, their weights and the head's logits [row1 - row0][C] (fp32: logits_dtype 0, bf16: 1) are ADDED into the
+ * caller-zeroed acc, mmskin_lime_accumulator_doubles(batch, N, F, C) doubles.  y = the logits (MMSKIN_LIME_LOGIT) or their
+ * soft-max (_PROB: e = exp(x - max) taken in fp64 and rounded to fp32, summed over c = 0 .. C-1 in fp32, e / sum in fp32).  With
+ * a = [z (F), 1, y (C)] it holds, per sample and per slab of 256 consecutive s, sum_s w a_i a_j for i <= F and all j, row-major
+ * [F + 1][F + 1 + C], then sum_s w y_c^2 [C]: sum w, sum w z, sum w y, sum w z z^T, sum w z y^T, sum w y^2.  Every element is
+ * summed over its slab's rows in ascending s, continuing from the value in memory, and the slabs are added in ascending order by
+ * lime_solve: the result does not depend on where the rows were cut between calls.  Calls that share acc are ordered on one stream.
+ *
+ * lime_solve: per (sample, class), sklearn's Ridge(alpha, fit_intercept=True).fit(Z, y, sample_weight=w) in closed form from the
+ * sums: zbar, ybar the weighted means, G = Zc^T W Zc, R = Zc^T W yc, Syy = sum w yc^2;  beta0 = (G + 0.01 I)^-1 R;  U = the K
+ * features with the largest |beta0_j z_0j| (ties to the lower index; lime's `highest_weights`);  beta = (G_UU + I)^-1 R_U;
+ * intercept = ybar - zbar_U beta;  score = 1 - (Syy - 2 beta R_U + beta^T G_UU beta) / Syy (Syy = 0: 1 if the numerator is 0,
+ * else 0);  local_pred = intercept + z_0U beta.  Both systems by Cholesky in fp64.  Outputs, all fp64 but feature: coef and
+ * feature (int32) [batch][C][K] in descending |beta| (ties to the lower index), intercept, score, local_pred [batch][C]; dense
+ * [batch][C][F] (beta scattered, zeros elsewhere) when non-null; with abs_sum non-null, |beta| is ADDED over b = 0 .. batch-1, in
+ * that order, into the caller-zeroed fp64 [F][C] abs_sum.  workspace: mmskin_lime_solve_workspace_bytes(batch, F, C) bytes.  The
+ * call WAITS for the stream (it reads the factorisations' verdict back): a pivot that is not positive returns
+ * MMSKIN_ERR_NUMERIC, that (sample, class) and abs_sum are left unwritten.  It cannot run under stream capture.
+ * No atomics anywhere: two runs are bitwise equal.  Errors (nothing is launched): an extent < 1, F > 128, C > 64, K < 1 or K > F,
+ * widths below F, a range outside the batch's rows or with row1 < row0, an unknown dtype or output, a null argument; the two
+ * size queries return -1. */
+#define MMSKIN_ERR_NUMERIC 4
+#define MMSKIN_LIME_PROB 0
+#define MMSKIN_LIME_LOGIT 1
+#define MMSKIN_LIME_W_F32 0
+#define MMSKIN_LIME_W_F64 1
+int64_t mmskin_lime_accumulator_doubles(int batch, int N, int F, int C);
+int64_t mmskin_lime_solve_workspace_bytes(int batch, int F, int C);
+int mmskin_lime_neighbourhood(const float* x, int x_stride, int batch, const double* mean, const double* scale, int F, int N,
+                              uint64_t seed, int64_t sample0, int around_instance, int64_t row0, int64_t row1, float* out,
+                              int out_width, void* w, int w_dtype, void* stream);
+int mmskin_lime_reduce(const float* rows, int width, const void* w, int w_dtype, const void* logits, int logits_dtype, int output,
+                       const double* mean, const double* scale, int batch, int N, int F, int C, int64_t row0, int64_t row1,
+                       double* acc, void* stream);
+int mmskin_lime_solve(const double* acc, const float* x, int x_stride, const double* mean, const double* scale, int batch, int N,
+                      int F, int C, int K, double* coef, int32_t* feature, double* intercept, double* score, double* local_pred,
+                      double* dense, double* abs_sum, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The criterion (csrc/criterion.hip): one forward and one backward launch for three kinds of loss on logits [B][C], row-major,
  * fp32 (logits_dtype 0) or bf16 (1); all arithmetic fp32.  1 <= B <= 2^20, 2 <= C <= 1024.  With m = max z_i,
  * ls = ln sum exp(z_i - m), ce = ls - (z_i[y] - m), p = softmax(z_i):

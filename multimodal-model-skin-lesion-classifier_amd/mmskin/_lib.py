@@ -203,6 +203,11 @@ _SIGNATURES = {
     "mmskin_shapley_rows": (_i64, [_i] * 4),
     "mmskin_shapley_coalitions": (_i, [_P, _P, _i, _P, _P, _i, _i, _P, _P, _i, _i, _P, _P, _f, _P, _P, _i, _i64, _i64, _P, _i, _P]),
     "mmskin_shapley_reduce": (_i, [_P, _i, _i] + [_i] * 5 + [_i64, _i64, _P, _i] + [_P] * 6 + [_P]),
+    "mmskin_lime_accumulator_doubles": (_i64, [_i] * 4),
+    "mmskin_lime_solve_workspace_bytes": (_i64, [_i] * 3),
+    "mmskin_lime_neighbourhood": (_i, [_P, _i, _i, _P, _P, _i, _i, _u64, _i64, _i, _i64, _i64, _P, _i, _P, _i, _P]),
+    "mmskin_lime_reduce": (_i, [_P, _i, _P, _i, _P, _i, _i, _P, _P] + [_i] * 4 + [_i64, _i64, _P, _P]),
+    "mmskin_lime_solve": (_i, [_P, _P, _i, _P, _P] + [_i] * 5 + [_P] * 9),
     "mmskin_criterion_scratch_floats": (_i64, [_i, _i, _i]),
     "mmskin_criterion_forward": (_i, [_P, _i, _P, _P, _i, _i, _f, _i, _i] + [_P] * 6),
     "mmskin_criterion_backward": (_i, [_P, _i, _P, _P, _i, _i, _f, _i, _i] + [_P] * 4),

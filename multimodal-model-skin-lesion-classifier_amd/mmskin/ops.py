@@ -1304,3 +1304,101 @@ def shapley_reduce(logits, v, perms, G, row0, output=SHAPLEY_PROB, finish=False,
          int(bool(finish)), ctypes.c_void_p(perms.ctypes.data), ptr(scratch), ptr(phi), ptr(base), ptr(full),
          ptr(abs_sum) if finish else None, stream())
     return (phi, base, full) if finish else None
+
+
+# ---------------------------------------------------------------------------------------------- metadata LIME (forward only)
+LIME_PROB, LIME_LOGIT = 0, 1                                                                 # MMSKIN_LIME_* of mmskin.h
+LIME_MAX_FEATURES = 128
+
+
+def _lime_stats(mean, scale, F, what):
+    _dev_tensor(mean, torch.float64, (F,), f"{what}: mean")
+    _dev_tensor(scale, torch.float64, (F,), f"{what}: scale")
+
+
+def _lime_weight_code(w, what):
+    if w.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{what}: the weights must be fp32 or fp64, got {w.dtype}")
+    return int(w.dtype == torch.float64)                                                     # MMSKIN_LIME_W_F32 / _F64
+
+
+def lime_accumulator(batch, N, F, C, device):
+    """The zeroed fp64 accumulator lime_reduce adds into and lime_solve reads (mmskin_lime_accumulator_doubles)."""
+    n = int(_lib.load().mmskin_lime_accumulator_doubles(int(batch), int(N), int(F), int(C)))
+    if n < 0:
+        raise ValueError(f"lime_accumulator: batch {batch}, N {N}, F {F}, C {C}: an extent is < 1 or out of range (F <= {LIME_MAX_FEATURES}, "
+                         "C <= 64)")
+    return torch.zeros(n, dtype=torch.float64, device=device)
+
+
+def lime_neighbourhood(x, mean, scale, N, seed, out_width=None, row0=0, row1=None, sample0=0, around_instance=False, out=None,
+                       weights=None, weight_dtype=torch.float64):
+    """Rows [row0, row1) of the B * N neighbourhood rows of x fp32 [B, >= F] (sample-major; row 0 of a sample is x itself, the
+    others counter-based normal draws of (seed, sample0 + b, s, f) scaled by mean / scale fp64 [F]) and their LIME kernel weights:
+    (rows fp32 [row1 - row0, out_width], weights [row1 - row0]) (mmskin_lime_neighbourhood)."""
+    _need_gpu(x, "lime_neighbourhood")
+    F = int(mean.shape[0]) if mean is not None and mean.dim() == 1 else -1
+    if x.dim() != 2 or x.dtype != torch.float32 or x.stride(1) != 1 or x.shape[1] < F:
+        raise ValueError(f"lime_neighbourhood: x must be fp32 [B, >= {F}] with unit column stride, got {x.dtype} {tuple(x.shape)}")
+    _lime_stats(mean, scale, F, "lime_neighbourhood")
+    B, N, row0 = int(x.shape[0]), int(N), int(row0)
+    row1 = B * N if row1 is None else int(row1)
+    out_width = F if out_width is None else int(out_width)
+    n = max(row1 - row0, 0)
+    if out is None:
+        out = torch.empty((n, max(out_width, 0)), device=x.device, dtype=torch.float32)
+    else:
+        _dev_tensor(out, torch.float32, (row1 - row0, out_width), "lime_neighbourhood: out")
+    if weights is None:
+        weights = torch.empty((n,), device=x.device, dtype=weight_dtype)
+    code = _lime_weight_code(weights, "lime_neighbourhood")
+    _dev_tensor(weights, weights.dtype, (row1 - row0,), "lime_neighbourhood: weights")
+    call("mmskin_lime_neighbourhood", ptr(x), int(x.stride(0)), B, ptr(mean), ptr(scale), F, N, int(seed) & (2 ** 64 - 1), int(sample0),
+         int(bool(around_instance)), row0, row1, ptr(out), out_width, ptr(weights), code, stream())
+    return out, weights
+
+
+def lime_reduce(rows, weights, logits, mean, scale, acc, batch, N, row0, output=LIME_PROB):
+    """Adds rows [row0, row0 + n) of a batch's neighbourhood -- the rows fp32 [n, >= F], their weights [n] and the head's logits
+    [n, C] (fp32 or bf16) -- into acc (lime_accumulator): every weighted sum the ridge fits need (mmskin_lime_reduce)."""
+    _need_gpu(logits, "lime_reduce")
+    if logits.dim() != 2 or logits.dtype not in (torch.float32, torch.bfloat16) or not logits.is_contiguous():
+        raise ValueError(f"lime_reduce: logits must be a contiguous fp32 or bf16 [rows, C] tensor, got {logits.dtype} {tuple(logits.shape)}")
+    n, C = logits.shape
+    F = int(mean.shape[0]) if mean is not None and mean.dim() == 1 else -1
+    _lime_stats(mean, scale, F, "lime_reduce")
+    if rows is None or rows.dim() != 2:
+        raise ValueError("lime_reduce: rows must be an fp32 [rows, width] device tensor")
+    _dev_tensor(rows, torch.float32, (n, rows.shape[1]), "lime_reduce: rows")
+    code = _lime_weight_code(weights, "lime_reduce")
+    _dev_tensor(weights, weights.dtype, (n,), "lime_reduce: weights")
+    want = int(_lib.load().mmskin_lime_accumulator_doubles(int(batch), int(N), F, int(C)))
+    _dev_tensor(acc, torch.float64, (max(want, 0),), "lime_reduce: acc")
+    call("mmskin_lime_reduce", ptr(rows), int(rows.shape[1]), ptr(weights), code, ptr(logits), _dtype_code(logits), int(output), ptr(mean),
+         ptr(scale), int(batch), int(N), F, int(C), int(row0), int(row0) + int(n), ptr(acc), stream())
+
+
+def lime_solve(acc, x, mean, scale, N, C, num_features, want_dense=True, abs_sum=None):
+    """The ridge fits of every (sample, class) from the sums in acc: (coef fp64 [B, C, K], feature int32 [B, C, K] in descending
+    |coef|, intercept, score, local_pred fp64 [B, C], dense fp64 [B, C, F] or None); ADDS sum_b |coef| into abs_sum fp64 [F, C] when
+    given.  Waits for the stream; a factorisation that fails raises MMSkinError (mmskin_lime_solve)."""
+    _need_gpu(x, "lime_solve")
+    F = int(mean.shape[0]) if mean is not None and mean.dim() == 1 else -1
+    if x.dim() != 2 or x.dtype != torch.float32 or x.stride(1) != 1 or x.shape[1] < F:
+        raise ValueError(f"lime_solve: x must be fp32 [B, >= {F}] with unit column stride, got {x.dtype} {tuple(x.shape)}")
+    _lime_stats(mean, scale, F, "lime_solve")
+    B, C, K, dev = int(x.shape[0]), int(C), int(num_features), x.device
+    want = int(_lib.load().mmskin_lime_accumulator_doubles(B, int(N), F, C))
+    _dev_tensor(acc, torch.float64, (max(want, 0),), "lime_solve: acc")
+    if abs_sum is not None:
+        _dev_tensor(abs_sum, torch.float64, (F, C), "lime_solve: abs_sum")
+    k = max(K, 0)
+    coef = torch.empty((B, C, k), dtype=torch.float64, device=dev)
+    feature = torch.empty((B, C, k), dtype=torch.int32, device=dev)
+    intercept, score, local_pred = (torch.empty((B, C), dtype=torch.float64, device=dev) for _ in range(3))
+    dense = torch.empty((B, C, F), dtype=torch.float64, device=dev) if want_dense else None
+    nbytes = int(_lib.load().mmskin_lime_solve_workspace_bytes(B, F, C))
+    workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    call("mmskin_lime_solve", ptr(acc), ptr(x), int(x.stride(0)), ptr(mean), ptr(scale), B, int(N), F, C, K, ptr(coef), ptr(feature),
+         ptr(intercept), ptr(score), ptr(local_pred), ptr(dense), ptr(abs_sum), ptr(workspace), stream())
+    return coef, feature, intercept, score, local_pred, dense

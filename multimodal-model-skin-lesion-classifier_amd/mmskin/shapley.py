@@ -1,7 +1,8 @@
 """Shapley values of the metadata on the model itself, batched on the GPU.
 
 The reference explains the metadata contribution to prob_NEV ... prob_MEL on a SURROGATE
-(src/scripts/data_preprocessing/shap_values.py, lime_padufes20.py): a 300-tree RandomForestRegressor fitted on (encoded
+(src/scripts/data_preprocessing/shap_values.py; lime_padufes20.py does the same with LIME, see mmskin.lime for that half): a
+300-tree RandomForestRegressor fitted on (encoded
 metadata -> recorded probabilities), explained with shap's permutation explainer, because ~10^5 batch-1 forwards of the real
 model per explained sample are out of reach.  The surrogate explains the forest, not the network, sees no image, and treats
 each one-hot CELL as a feature, so most of its coalitions are rows no patient could have.  Here the network itself is explained:
