@@ -896,6 +896,48 @@ int mmskin_lime_solve(const double* acc, const float* x, int x_stride, const dou
                       double* dense, double* abs_sum, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Permutation importance of the metadata on a validation fold (csrc/permute.hip,
+ * mmskin.permutation.MetadataPermutationImportance): sklearn.inspection.permutation_importance with the network as the estimator.
+ * The fold's S <= MMSKIN_PERMUTATION_MAX_SAMPLES images are encoded once; for each of R repeats and G feature groups the fusion
+ * head runs on the S rows whose columns of that group come from a shuffled sample, and the fold is scored again.  Groups are sets
+ * of ENCODED columns: group int32 [width], group[j] = the group of column j in 0 .. G-1, or -1 for a column that is never shuffled
+ * (a one-hot block is one group, so a shuffled row is bit for bit the encoding of the mixed raw row).
+ * Row order of the study: row = (r G + g) S + s; a CELL (r, g) is S consecutive rows; R G S rows in all.
+ *
+ * permutation_indices: perm int32 [R][G][S], perm[r][g] = the positions i = 0 .. S-1 in ascending order of the 64-bit keys
+ * (h_i >> 32) << 32 | i with h_i = mix64(mix64(seed) ^ (r << 40 | g << 20 | i)), mix64 as under LIME above.  A pure function of
+ * (seed, r, g, S); S = 1 gives the identity.  One workgroup per cell sorts the keys in LDS.
+ *
+ * permuted_rows: x fp32 [S][x_stride] (x_stride >= width) -> out fp32 [row1 - row0][width], the rows [row0, row1) of the study
+ * (out points at row0): column j of row (r, g, s) is x[perm[r][g][s]][j] where group[j] == g and x[s][j] elsewhere.  Every
+ * element is written once, so any cut of the rows gives the bytes of one full call.  A table entry outside 0 .. S-1 is read as s.
+ *
+ * permutation_scores: logits fp32 [row1 - row0][K] of a range cut at multiples of S (whole cells; anything else is an error),
+ * labels int64 [S] read in place (a label outside [0, K) counts nowhere).  For each cell of the range it WRITES
+ *   confusion int32 [R G][K][K]      [true][predicted], predicted = the first arg-max of the logits
+ *   counts    int64 [R G][3 K + 1]   pos[K], neg[K], wins2[K], nan: the block of mmskin_ovr_auc_counts below, on
+ *                                    p = soft-max in fp32 (e_c = exp(x_c - max) taken in fp64 and rounded to fp32, summed over
+ *                                    c = 0 .. K-1 in fp32, e_c / sum in fp32)
+ * Integers only and no atomics: two runs are bitwise equal, and the ranges of several calls fill the cells chunk by chunk.
+ *
+ * permutation_finalize: per cell, in fp64: accuracy = trace / rows; balanced accuracy = the mean over the classes that occur of
+ * their recall; auc = the mean over the classes with a positive and a negative row of wins2 / (2 pos neg), NaN when there is no
+ * such class or nan > 0 (accuracy and balanced accuracy are NaN when no row counts).  metrics fp64 [3][G][R] in that order of
+ * metrics, importances [3][G][R] = baseline[m] - metrics (baseline fp64 [3] on the device), mean and std [3][G] over r = 0 .. R-1
+ * in that order, std with ddof = 0: sqrt(sum (v - mean)^2 / R).
+ * Errors (nothing is launched, no GPU needed): an extent < 1 or out of range, S > MMSKIN_PERMUTATION_MAX_SAMPLES, a range
+ * outside the study or one that splits a cell, width > x_stride, a null argument; 2 <= K <= 64, anything else is
+ * MMSKIN_ERR_UNSUPPORTED. */
+#define MMSKIN_PERMUTATION_MAX_SAMPLES 4096
+int mmskin_permutation_indices(uint64_t seed, int R, int G, int S, int32_t* perm, void* stream);
+int mmskin_permuted_rows(const float* x, int x_stride, const int32_t* group, const int32_t* perm, int R, int G, int S, int width,
+                         int64_t row0, int64_t row1, float* out, void* stream);
+int mmskin_permutation_scores(const float* logits, const int64_t* labels, int R, int G, int S, int K, int64_t row0, int64_t row1,
+                              int32_t* confusion, int64_t* counts, void* stream);
+int mmskin_permutation_finalize(const int32_t* confusion, const int64_t* counts, const double* baseline, int R, int G, int K,
+                                double* metrics, double* importances, double* mean, double* std, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The criterion (csrc/criterion.hip): one forward and one backward launch for three kinds of loss on logits [B][C], row-major,
  * fp32 (logits_dtype 0) or bf16 (1); all arithmetic fp32.  1 <= B <= 2^20, 2 <= C <= 1024.  With m = max z_i,
  * ls = ln sum exp(z_i - m), ce = ls - (z_i[y] - m), p = softmax(z_i):

@@ -18,6 +18,7 @@
 //              exactly once: they also build the class histogram of their chunk (pos, neg = valid rows - pos) and count the
 //              NaN entries of the valid rows.
 #include "../../include/mmskin.h"
+#include "auc_pairs.h"
 #include "common.h"
 
 namespace {
@@ -93,7 +94,7 @@ __global__ __launch_bounds__(NT) void ovr_auc_counts_kernel(const float* __restr
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const float v = s_tile[(r + k) * C + col];               // (r + k) < TJ, col < C: inside TJ * C <= TILE_FLOATS
-          const int32_t w = si > v ? 2 : (si == v ? 1 : 0);        // a NaN on either side: 0
+          const int32_t w = auc_wins2(si, v);                      // a NaN on either side: 0
           a += (ys[k] >= 0 && ys[k] != yi) ? w : 0;
         }
       }

@@ -8,5 +8,7 @@ Layout:
 from . import _lib, criterion, evaluate  # noqa: F401
 from .criterion import CrossEntropyLoss, EpochMeter, FocalLoss, SoftTargetCrossEntropy  # noqa: F401
 from .evaluate import evaluate_model  # noqa: F401
+from .permutation import MetadataPermutationImportance  # noqa: F401
 
-__all__ = ["_lib", "criterion", "evaluate", "CrossEntropyLoss", "FocalLoss", "SoftTargetCrossEntropy", "EpochMeter", "evaluate_model"]
+__all__ = ["_lib", "criterion", "evaluate", "CrossEntropyLoss", "FocalLoss", "SoftTargetCrossEntropy", "EpochMeter", "evaluate_model",
+           "MetadataPermutationImportance"]

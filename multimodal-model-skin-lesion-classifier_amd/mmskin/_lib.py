@@ -208,6 +208,10 @@ _SIGNATURES = {
     "mmskin_lime_neighbourhood": (_i, [_P, _i, _i, _P, _P, _i, _i, _u64, _i64, _i, _i64, _i64, _P, _i, _P, _i, _P]),
     "mmskin_lime_reduce": (_i, [_P, _i, _P, _i, _P, _i, _i, _P, _P] + [_i] * 4 + [_i64, _i64, _P, _P]),
     "mmskin_lime_solve": (_i, [_P, _P, _i, _P, _P] + [_i] * 5 + [_P] * 9),
+    "mmskin_permutation_indices": (_i, [_u64, _i, _i, _i, _P, _P]),
+    "mmskin_permuted_rows": (_i, [_P, _i, _P, _P, _i, _i, _i, _i, _i64, _i64, _P, _P]),
+    "mmskin_permutation_scores": (_i, [_P, _P, _i, _i, _i, _i, _i64, _i64, _P, _P, _P]),
+    "mmskin_permutation_finalize": (_i, [_P, _P, _P, _i, _i, _i, _P, _P, _P, _P, _P]),
     "mmskin_criterion_scratch_floats": (_i64, [_i, _i, _i]),
     "mmskin_criterion_forward": (_i, [_P, _i, _P, _P, _i, _i, _f, _i, _i] + [_P] * 6),
     "mmskin_criterion_backward": (_i, [_P, _i, _P, _P, _i, _i, _f, _i, _i] + [_P] * 4),

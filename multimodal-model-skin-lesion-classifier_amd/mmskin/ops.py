@@ -1402,3 +1402,85 @@ def lime_solve(acc, x, mean, scale, N, C, num_features, want_dense=True, abs_sum
     call("mmskin_lime_solve", ptr(acc), ptr(x), int(x.stride(0)), ptr(mean), ptr(scale), B, int(N), F, C, K, ptr(coef), ptr(feature),
          ptr(intercept), ptr(score), ptr(local_pred), ptr(dense), ptr(abs_sum), ptr(workspace), stream())
     return coef, feature, intercept, score, local_pred, dense
+
+
+# ---------------------------------------------------------------------------------------------- metadata permutation importance (forward only)
+PERMUTATION_MAX_SAMPLES = 4096                                                               # MMSKIN_PERMUTATION_MAX_SAMPLES of mmskin.h
+PERMUTATION_METRICS = ("accuracy", "balanced_accuracy", "auc")                               # the order of every [3, ...] output
+
+
+def permutation_indices(seed, R, G, S, device):
+    """perm int32 [R, G, S]: per (repeat, group) the argsort of the counter-based keys of (seed, r, g, position)
+    (mmskin_permutation_indices)."""
+    if not torch.cuda.is_available():
+        raise _lib.MMSkinError("permutation_indices needs a HIP device; there is no CPU fallback")
+    R, G, S = int(R), int(G), int(S)
+    perm = torch.empty((max(R, 0), max(G, 0), max(S, 0)), dtype=torch.int32, device=device)
+    call("mmskin_permutation_indices", int(seed) & (2 ** 64 - 1), R, G, S, ptr(perm), stream())
+    return perm
+
+
+def permuted_rows(x, group, perm, row0=0, row1=None, out=None):
+    """Rows [row0, row1) of the study, fp32 [row1 - row0, width]: row (r G + g) S + s is x[s] with the columns j of group[j] == g
+    taken from x[perm[r, g, s]] (mmskin_permuted_rows).  x fp32 [S, width] with unit column stride, group int32 [width] (-1: never
+    shuffled), perm int32 [R, G, S], all on the device."""
+    _need_gpu(x, "permuted_rows")
+    if x.dim() != 2 or x.dtype != torch.float32 or x.stride(1) != 1:
+        raise ValueError(f"permuted_rows: x must be fp32 [S, width] with unit column stride, got {x.dtype} {tuple(x.shape)}")
+    S, width = x.shape
+    if perm is None or perm.dim() != 3:
+        raise ValueError("permuted_rows: perm must be an int32 [R, G, S] device tensor")
+    R, G = perm.shape[:2]
+    _dev_tensor(perm, torch.int32, (R, G, S), "permuted_rows: perm")
+    _dev_tensor(group, torch.int32, (width,), "permuted_rows: group")
+    row0 = int(row0)
+    row1 = R * G * S if row1 is None else int(row1)
+    if out is None:
+        out = torch.empty((max(row1 - row0, 0), width), device=x.device, dtype=torch.float32)
+    else:
+        _dev_tensor(out, torch.float32, (row1 - row0, width), "permuted_rows: out")
+    call("mmskin_permuted_rows", ptr(x), int(x.stride(0)), ptr(group), ptr(perm), R, G, S, width, row0, row1, ptr(out), stream())
+    return out
+
+
+def permutation_accumulators(R, G, K, device):
+    """(confusion int32 [R, G, K, K], counts int64 [R, G, 3 K + 1]) for permutation_scores to fill."""
+    return (torch.zeros((R, G, K, K), dtype=torch.int32, device=device), torch.zeros((R, G, 3 * K + 1), dtype=torch.int64, device=device))
+
+
+def permutation_scores(logits, labels, confusion, counts, row0):
+    """The cells of rows [row0, row0 + n) of the study -- n and row0 multiples of S -- scored from their logits fp32 [n, K]: the
+    confusion counts and the one-vs-rest AUC integers of each cell are written into confusion / counts
+    (permutation_accumulators; mmskin_permutation_scores).  labels int64 [S]."""
+    _need_gpu(logits, "permutation_scores")
+    if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError(f"permutation_scores: logits must be a contiguous fp32 [rows, K] tensor, got {logits.dtype} {tuple(logits.shape)}")
+    n, K = logits.shape
+    if confusion is None or confusion.dim() != 4:
+        raise ValueError("permutation_scores: confusion must be an int32 [R, G, K, K] device tensor")
+    R, G = confusion.shape[:2]
+    _dev_tensor(confusion, torch.int32, (R, G, K, K), "permutation_scores: confusion")
+    _dev_tensor(counts, torch.int64, (R, G, 3 * K + 1), "permutation_scores: counts")
+    if labels is None or labels.dim() != 1:
+        raise ValueError("permutation_scores: labels must be an int64 [S] device tensor")
+    S = labels.shape[0]
+    _dev_tensor(labels, torch.int64, (S,), "permutation_scores: labels")
+    call("mmskin_permutation_scores", ptr(logits), ptr(labels), R, G, S, K, int(row0), int(row0) + n, ptr(confusion), ptr(counts), stream())
+
+
+def permutation_finalize(confusion, counts, baseline):
+    """(metrics, importances fp64 [3, G, R], mean, std fp64 [3, G]) from the filled accumulators and baseline fp64 [3] on the
+    device; the first axis is PERMUTATION_METRICS (mmskin_permutation_finalize)."""
+    _need_gpu(confusion, "permutation_finalize")
+    if confusion.dim() != 4:
+        raise ValueError("permutation_finalize: confusion must be an int32 [R, G, K, K] device tensor")
+    R, G, K = confusion.shape[:3]
+    _dev_tensor(confusion, torch.int32, (R, G, K, K), "permutation_finalize: confusion")
+    _dev_tensor(counts, torch.int64, (R, G, 3 * K + 1), "permutation_finalize: counts")
+    _dev_tensor(baseline, torch.float64, (3,), "permutation_finalize: baseline")
+    dev = confusion.device
+    metrics, importances = (torch.empty((3, G, R), dtype=torch.float64, device=dev) for _ in range(2))
+    mean, std = (torch.empty((3, G), dtype=torch.float64, device=dev) for _ in range(2))
+    call("mmskin_permutation_finalize", ptr(confusion), ptr(counts), ptr(baseline), R, G, K, ptr(metrics), ptr(importances), ptr(mean),
+         ptr(std), stream())
+    return metrics, importances, mean, std
