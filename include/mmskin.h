@@ -726,6 +726,43 @@ int mmskin_gradcam_map(const float* acts, const float* weights, const int32_t* r
                        int W, float* raw, float* cam, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Faithfulness scores of a saliency map (mmskin.faithfulness.CamFaithfulness): deletion / insertion curves (Petsiuk et al.,
+ * RISE) and average drop / increase in confidence (Chattopadhay et al., Grad-CAM++), forward only.  images and baseline are
+ * fp32 [N, 3, H, W], saliency fp32 [N, H * W].
+ *   rank     rank[n, p] = #{q : s[n,q] > s[n,p]} + #{q < p : s[n,q] == s[n,p]}, int32 [N, HW]: descending saliency, ties by
+ *            ascending (row-major) pixel index; -0.0 == +0.0; a NaN ranks below every number and NaNs tie among themselves.
+ *            Pair counting on integer keys: no atomics, a function of the input alone.
+ *   blur     separable Gaussian of `planes` planes of H x W with reflect padding (no edge repeat): horizontal pass, then vertical,
+ *            each acc = acc + taps[t] * x in ascending t from 0, every operation rounded to fp32 on its own.  taps is HOST memory,
+ *            ksize floats (the caller computes them in fp64, normalises and rounds them); it is read before the call returns.
+ *   mean     out[plane, :] = the plane's mean: fp64 partial sums of stride 256, a halving tree, one division, one rounding.
+ *   perturb  out[j] for j < n is the image of row-table entry rows[j] = (image, k, mode), int32 [n, 3]; rows n .. n_pad are zeros;
+ *            fp32 [n_pad, 3, H, W].  With count = (k * H * W) / S (integer):
+ *              mode 0, deletion:     rank < count ? baseline : image
+ *              mode 1, insertion:    rank < count ? image : baseline
+ *              mode 2, explanation:  baseline + h * (image - baseline), h = min(max(saliency, 0), 1) (NaN -> 0), difference,
+ *                                    product and sum each rounded to fp32
+ *            per pixel, the same for the three colour planes.  Entries are clamped on the device (image to [0, N - 1], k to
+ *            [0, S], mode to [0, 2]): a bad entry reads the nearest image, never other memory.
+ *   curves   logits fp32 [>= N * P, C], P = 2 S + 3: row n * P + k is deletion step k of image n, n * P + S + 1 + k insertion
+ *            step k, n * P + 2 S + 2 the explanation image.  target int32 [N] (clamped to [0, C - 1]) or NULL = the first largest
+ *            logit of the image's deletion step 0, the clean image.  All in fp64 in a fixed order, no atomics:
+ *              curves  [2, N, S + 1]  soft-max probability of the target class: deletion, insertion
+ *              scalars [4, N]         deletion area, insertion area (trapezoids over x = k / S), average drop
+ *                                     max(0, p - p_expl) / p, increase 1[p_expl > p], p = deletion step 0
+ *              means   [4]            the means of the four over the N images;  target_out int32 [N] the class used
+ * Errors (nothing is launched): an extent < 1, S < 1, S > 1024, S > H * W (perturb), n < 1, n > n_pad, ksize even or > 31,
+ * ksize / 2 >= min(H, W); MMSKIN_ERR_UNSUPPORTED for H * W above mmskin_faith_max_pixels() = 65536 (rank, perturb). */
+int mmskin_faith_max_pixels(void);
+int mmskin_faith_rank(const float* saliency, int N, int HW, int32_t* rank, void* stream);
+int mmskin_faith_blur(const float* x, int planes, int H, int W, const float* taps, int ksize, float* out, void* stream);
+int mmskin_faith_mean(const float* x, int planes, int HW, float* out, void* stream);
+int mmskin_faith_perturb(const float* images, const float* baseline, const int32_t* rank, const float* saliency, const int32_t* rows,
+                         int N, int H, int W, int S, int n, int n_pad, float* out, void* stream);
+int mmskin_faith_curves(const float* logits, const int32_t* target, int N, int S, int C, double* curves, double* scalars,
+                        double* means, int32_t* target_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Metadata-sensitivity sweeps (interpretability/flip_rate.py:164-256, inference_all_folds.py:116-140,
  * analyze_prediction_uncertainty.py:166-272): the image is encoded once, the fusion head runs on V metadata variants of the
  * batch (mmskin.sweep.MetadataSweep); these are the kernels before and after the head.

@@ -198,6 +198,12 @@ _SIGNATURES = {
     "mmskin_scorecam_combine": (_i, [_P] * 3 + [_i] * 6 + [_P, _P]),
     "mmskin_gradcam_weights": (_i, [_P] * 4 + [_i] * 6 + [_P, _P]),
     "mmskin_gradcam_map": (_i, [_P] * 3 + [_i] * 7 + [_P] * 3),
+    "mmskin_faith_max_pixels": (_i, []),
+    "mmskin_faith_rank": (_i, [_P, _i, _i, _P, _P]),
+    "mmskin_faith_blur": (_i, [_P, _i, _i, _i, _P, _i, _P, _P]),
+    "mmskin_faith_mean": (_i, [_P, _i, _i, _P, _P]),
+    "mmskin_faith_perturb": (_i, [_P] * 5 + [_i] * 6 + [_P, _P]),
+    "mmskin_faith_curves": (_i, [_P, _P, _i, _i, _i] + [_P] * 5),
     "mmskin_metadata_variants": (_i, [_P, _i, _P, _P, _i, _P, _i, _P, _P, _f, _P, _P, _i, _P, _P, _P, _i, _i, _P]),
     "mmskin_sweep_reduce": (_i, [_P, _i, _P, _P, _i, _i, _i] + [_P] * 7 + [_P]),
     "mmskin_shapley_rows": (_i64, [_i] * 4),

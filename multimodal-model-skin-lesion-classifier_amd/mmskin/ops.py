@@ -1149,6 +1149,122 @@ def gradcam_map(acts, weights, row_image, size):
     return raw, cam
 
 
+# ---------------------------------------------------------------------------------------------- CAM faithfulness (forward only)
+FAITH_DELETION, FAITH_INSERTION, FAITH_EXPLANATION = 0, 1, 2          # `mode` of a row-table entry of mmskin_faith_perturb
+FAITH_MAX_STEPS, FAITH_MAX_KSIZE = 1024, 31
+
+
+def faith_max_pixels():
+    """the largest H * W the rank and perturb kernels take"""
+    return int(_lib.load().mmskin_faith_max_pixels())
+
+
+def gaussian_taps(ksize, sigma):
+    """The ksize taps of a Gaussian of standard deviation sigma, computed in fp64, normalised to sum 1, rounded to fp32."""
+    ksize = int(ksize)
+    if ksize < 1 or ksize % 2 == 0 or ksize > FAITH_MAX_KSIZE:
+        raise ValueError(f"gaussian_taps: ksize must be odd and in 1 .. {FAITH_MAX_KSIZE}, got {ksize}")
+    if not float(sigma) > 0:
+        raise ValueError(f"gaussian_taps: sigma must be > 0, got {sigma}")
+    x = np.arange(ksize, dtype=np.float64) - ksize // 2
+    w = np.exp(-0.5 * (x / float(sigma)) ** 2)
+    return (w / w.sum()).astype(np.float32)
+
+
+def _faith_saliency(saliency, what):
+    _need_gpu(saliency, what)
+    if saliency.dim() != 3 or saliency.dtype != torch.float32 or not saliency.is_contiguous() or saliency.shape[0] < 1:
+        raise ValueError(f"{what}: the saliency must be a contiguous fp32 [N, H, W] tensor, got {tuple(saliency.shape)} {saliency.dtype}")
+    return tuple(saliency.shape)
+
+
+def faith_rank(saliency, out=None):
+    """Rank of every pixel of saliency [N, H, W] within its image -> int32 [N, H, W]: descending saliency, ties by ascending
+    row-major index, -0.0 == +0.0, NaN below every number (NaNs tie among themselves)."""
+    N, H, W = _faith_saliency(saliency, "faith_rank")
+    if out is None:
+        out = torch.empty((N, H, W), device=saliency.device, dtype=torch.int32)
+    else:
+        _dev_tensor(out, torch.int32, (N, H, W), "faith_rank: out")
+    call("mmskin_faith_rank", ptr(saliency), N, H * W, ptr(out), stream())
+    return out
+
+
+def _faith_planes(x, what):
+    _need_gpu(x, what)
+    if x.dim() < 2 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"{what}: the input must be a contiguous fp32 [..., H, W] tensor, got {tuple(x.shape)} {x.dtype}")
+    H, W = x.shape[-2:]
+    return int(x.numel() // max(H * W, 1)), int(H), int(W)
+
+
+def faith_blur(x, taps, out=None):
+    """Separable Gaussian blur with reflect padding of every [H, W] plane of x [..., H, W]; taps: the fp32 numpy array of
+    gaussian_taps (horizontal pass, then vertical, ascending taps, every operation rounded to fp32)."""
+    planes, H, W = _faith_planes(x, "faith_blur")
+    taps = np.ascontiguousarray(taps, dtype=np.float32)
+    if taps.ndim != 1:
+        raise ValueError(f"faith_blur: taps must be a 1-D array, got shape {taps.shape}")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _dev_tensor(out, torch.float32, x.shape, "faith_blur: out")
+    call("mmskin_faith_blur", ptr(x), planes, H, W, ctypes.c_void_p(taps.ctypes.data), int(taps.shape[0]), ptr(out), stream())
+    return out
+
+
+def faith_mean(x, out=None):
+    """Every [H, W] plane of x [..., H, W] replaced by its mean (fp64 sums in a fixed order, rounded to fp32 once)."""
+    planes, H, W = _faith_planes(x, "faith_mean")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _dev_tensor(out, torch.float32, x.shape, "faith_mean: out")
+    call("mmskin_faith_mean", ptr(x), planes, H * W, ptr(out), stream())
+    return out
+
+
+def faith_perturb(images, baseline, rank, saliency, rows, steps, n, n_pad, out=None):
+    """One chunk of model inputs [n_pad, 3, H, W]: row j < n is the image of rows[j] = (image, k, mode), int32 [>= n, 3] on the
+    device (FAITH_DELETION: the k * H * W // steps top-ranked pixels come from the baseline; FAITH_INSERTION: only they come
+    from the image; FAITH_EXPLANATION: baseline + clamp(saliency, 0, 1) * (image - baseline)); rows n .. n_pad are zeros."""
+    N, H, W = _faith_saliency(saliency, "faith_perturb")
+    _dev_tensor(images, torch.float32, (N, 3, H, W), "faith_perturb: images")
+    _dev_tensor(baseline, torch.float32, (N, 3, H, W), "faith_perturb: baseline")
+    _dev_tensor(rank, torch.int32, (N, H, W), "faith_perturb: rank")
+    if not torch.is_tensor(rows) or not rows.is_cuda or rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != 3 \
+            or not rows.is_contiguous() or rows.shape[0] < n:
+        raise ValueError(f"faith_perturb: rows must be a contiguous int32 [>= {n}, 3] device tensor")
+    if out is None:
+        out = torch.empty((max(int(n_pad), 0), 3, H, W), device=images.device, dtype=torch.float32)
+    else:
+        _dev_tensor(out, torch.float32, (n_pad, 3, H, W), "faith_perturb: out")
+    call("mmskin_faith_perturb", ptr(images), ptr(baseline), ptr(rank), ptr(saliency), ptr(rows), N, H, W, int(steps), int(n), int(n_pad),
+         ptr(out), stream())
+    return out
+
+
+def faith_curves(logits, steps, n_images, target=None):
+    """logits fp32 [>= N * (2 S + 3), C], image-major rows (deletion 0 .. S, insertion 0 .. S, explanation); target int32 [N] or
+    None = the argmax of every image's deletion step 0 -> (curves [2, N, S + 1], scalars [4, N], means [4], target [N]): fp64
+    (target int32); scalars = deletion area, insertion area, average drop, increase."""
+    _need_gpu(logits, "faith_curves")
+    N, S = int(n_images), int(steps)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous() or logits.shape[0] < N * (2 * S + 3):
+        raise ValueError(f"faith_curves: logits must be a contiguous fp32 [>= {N * (2 * S + 3)}, C] tensor, got {tuple(logits.shape)} "
+                         f"{logits.dtype}")
+    if target is not None:
+        _dev_tensor(target, torch.int32, (N,), "faith_curves: target")
+    dev = logits.device
+    curves = torch.empty((2, max(N, 0), max(S, 0) + 1), device=dev, dtype=torch.float64)
+    scalars = torch.empty((4, max(N, 0)), device=dev, dtype=torch.float64)
+    means = torch.empty((4,), device=dev, dtype=torch.float64)
+    target_out = torch.empty((max(N, 0),), device=dev, dtype=torch.int32)
+    call("mmskin_faith_curves", ptr(logits), ptr(target), N, S, int(logits.shape[1]), ptr(curves), ptr(scalars), ptr(means),
+         ptr(target_out), stream())
+    return curves, scalars, means, target_out
+
+
 # ---------------------------------------------------------------------------------------------- metadata sweeps (forward only)
 META_NONE, META_CAT_SET, META_CAT_TOGGLE, META_NUM_ADD, META_NUM_SET = 0, 1, 2, 3, 4          # MMSKIN_META_* of mmskin.h
 # one record per variant: struct mmskin_meta_variant of include/mmskin.h (32 bytes)
