@@ -763,6 +763,46 @@ int mmskin_faith_curves(const float* logits, const int32_t* target, int N, int S
                         double* means, int32_t* target_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * RISE saliency (Petsiuk et al., 2018; mmskin.rise.RISE), forward only: the image under many random smooth masks, the masks
+ * averaged with the target-class probability of their forward as the weight.  A mask is a pure function of (seed, mask index j,
+ * pixel); every kernel evaluates it in registers and no mask tensor exists in device memory.
+ *
+ * The mask.  grid = g (2 .. 16), p1 strictly inside (0, 1), image H x W, cell size ch = ceil(H / g), cw = ceil(W / g).  Mask j
+ * has a binary cell grid G_j[g + 1][g + 1] and a shift (dy_j, dx_j), 0 <= dy < ch, 0 <= dx < cw, shared by all images of a call:
+ *   key = mix64(seed), word(j, q) = mix64(key ^ (j * 1024 + q))      (mix64: the splitmix64 finaliser of every generator here)
+ *   cell q = row * (g + 1) + col is on iff (word(j, q) >> 40) < floor(p1 * 2^24 + 0.5)
+ *   dy = ((word(j, 1022) >> 32) * ch) >> 32,  dx = ((word(j, 1023) >> 32) * cw) >> 32        ((g + 1)^2 <= 289 < 1022)
+ * Its value at pixel (y, x) is the bilinear upsample of G_j by (ch, cw) with half-pixel centres (align_corners = false) and edge
+ * clamp, cropped at (dy, dx), stated in integers:
+ *   ty = 2 (y + dy) + 1 - ch,  iy = floor(ty / (2 ch)),  ry = ty - iy * 2 ch;  tx, ix, rx likewise with x, dx, cw
+ *   m = [ (2ch - ry)(2cw - rx) G[iy][ix] + (2ch - ry) rx G[iy][ix+1] + ry (2cw - rx) G[iy+1][ix] + ry rx G[iy+1][ix+1] ] / (4 ch cw)
+ * with every index clamped to 0 .. g.  The numerator is an integer below 2^24; the kernels convert it and 4 ch cw to fp32 (both
+ * exact) and divide once, so m is the correctly rounded fp32 of an exact rational.  Sums take that fp32 value widened to double.
+ *
+ *   masks       out fp32 [n, H, W] = masks j0 .. j0 + n - 1 (tests and drawing; not on the hot path)
+ *   apply       one chunk of model inputs, fp32 [n_pad, 3, H, W]: row r0 + i of the image-major row space R = N * n_masks is
+ *               (image r / n_masks, mask r % n_masks); out[i] = baseline + m * (image - baseline), difference, product and sum each
+ *               rounded to fp32; the three colour planes of a pixel share m.  Rows n .. n_pad are zeros.  images and baseline
+ *               are fp32 [N, 3, H, W].
+ *   accumulate  launched once, after all chunks.  logits fp32 [>= N * n_masks, K] in that row order, clean_logits fp32 [N, K] of
+ *               the unmasked images, target int32 [N] (clamped to [0, K - 1]) or NULL = the first largest clean logit, taken on
+ *               the device.  w[n][j] = the fp64 soft-max probability of the target class of row (n, j).  Outputs, fp64, every sum
+ *               in ascending j with one owner per element and no atomics (bitwise repeatable):
+ *                 saliency_sum [N, H, W]  sum_j w[n][j] * m_j(p)          coverage [H, W]  sum_j m_j(p)
+ *                 clean_prob   [N]        the probability of the target class on the clean image;  target_used int32 [N]
+ *               workspace: mmskin_rise_workspace_bytes(N, n_masks) bytes (w, and 80 bytes of cell table per mask), 8-byte aligned.
+ * Errors (nothing is launched): grid outside 2 .. 16, p1 outside (0, 1), an extent < 1, n_masks < 1, n < 1, n > n_pad,
+ * r0 < 0 or r0 + n > N * n_masks, N, n or n_pad above 65535, K above 65536, a null argument; MMSKIN_ERR_UNSUPPORTED for n_masks
+ * (masks: j0 + n) above 2^20 and for H * W above mmskin_faith_max_pixels().  workspace_bytes answers -1 for what it refuses. */
+int mmskin_rise_masks(uint64_t seed, int j0, int n, int grid, double p1, int H, int W, float* out, void* stream);
+int mmskin_rise_apply(const float* images, const float* baseline, int N, int H, int W, uint64_t seed, int grid, double p1, int n_masks,
+                      int64_t r0, int n, int n_pad, float* out, void* stream);
+int64_t mmskin_rise_workspace_bytes(int N, int n_masks);
+int mmskin_rise_accumulate(const float* logits, const int32_t* target, const float* clean_logits, int N, int K, int H, int W,
+                           uint64_t seed, int grid, double p1, int n_masks, double* saliency_sum, double* coverage, double* clean_prob,
+                           int32_t* target_used, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Metadata-sensitivity sweeps (interpretability/flip_rate.py:164-256, inference_all_folds.py:116-140,
  * analyze_prediction_uncertainty.py:166-272): the image is encoded once, the fusion head runs on V metadata variants of the
  * batch (mmskin.sweep.MetadataSweep); these are the kernels before and after the head.

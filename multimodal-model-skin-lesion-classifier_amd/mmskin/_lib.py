@@ -22,7 +22,7 @@ _lib = None
 
 c_f = ctypes.c_void_p          # device pointers travel as void*
 _i, _i64, _f = ctypes.c_int, ctypes.c_int64, ctypes.c_float
-_u64 = ctypes.c_uint64
+_u64, _d = ctypes.c_uint64, ctypes.c_double
 _P = ctypes.c_void_p
 
 _SIGNATURES = {
@@ -204,6 +204,10 @@ _SIGNATURES = {
     "mmskin_faith_mean": (_i, [_P, _i, _i, _P, _P]),
     "mmskin_faith_perturb": (_i, [_P] * 5 + [_i] * 6 + [_P, _P]),
     "mmskin_faith_curves": (_i, [_P, _P, _i, _i, _i] + [_P] * 5),
+    "mmskin_rise_masks": (_i, [_u64, _i, _i, _i, _d, _i, _i, _P, _P]),
+    "mmskin_rise_apply": (_i, [_P, _P, _i, _i, _i, _u64, _i, _d, _i, _i64, _i, _i, _P, _P]),
+    "mmskin_rise_workspace_bytes": (_i64, [_i, _i]),
+    "mmskin_rise_accumulate": (_i, [_P, _P, _P] + [_i] * 4 + [_u64, _i, _d, _i] + [_P] * 6),
     "mmskin_metadata_variants": (_i, [_P, _i, _P, _P, _i, _P, _i, _P, _P, _f, _P, _P, _i, _P, _P, _P, _i, _i, _P]),
     "mmskin_sweep_reduce": (_i, [_P, _i, _P, _P, _i, _i, _i] + [_P] * 7 + [_P]),
     "mmskin_shapley_rows": (_i64, [_i] * 4),

@@ -1265,6 +1265,88 @@ def faith_curves(logits, steps, n_images, target=None):
     return curves, scalars, means, target_out
 
 
+# ---------------------------------------------------------------------------------------------- RISE saliency (forward only)
+RISE_MAX_GRID, RISE_MAX_MASKS = 16, 1 << 20
+
+
+def _rise_args(seed, grid, p1, what):
+    seed, grid, p1 = int(seed), int(grid), float(p1)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"{what}: seed must fit 64 unsigned bits, got {seed}")
+    if not 2 <= grid <= RISE_MAX_GRID:
+        raise ValueError(f"{what}: grid must be in 2 .. {RISE_MAX_GRID}, got {grid}")
+    if not 0.0 < p1 < 1.0:
+        raise ValueError(f"{what}: p1 must lie strictly inside (0, 1), got {p1}")
+    return seed, grid, p1
+
+
+def rise_masks(seed, j0, n, grid, p1, H, W, device=None, out=None):
+    """Masks j0 .. j0 + n - 1 of (seed, grid, p1) on an H x W image -> fp32 [n, H, W] (the definition: include/mmskin.h).  For
+    tests and drawing: RISE itself never materialises a mask."""
+    seed, grid, p1 = _rise_args(seed, grid, p1, "rise_masks")
+    n, H, W = int(n), int(H), int(W)
+    if out is None:
+        if device is None or torch.device(device).type != "cuda":
+            raise _lib.MMSkinError(f"rise_masks: needs a GPU device, got {device!r}")
+        out = torch.empty((max(n, 0), max(H, 0), max(W, 0)), device=device, dtype=torch.float32)
+    else:
+        _dev_tensor(out, torch.float32, (n, H, W), "rise_masks: out")
+    call("mmskin_rise_masks", seed, int(j0), n, grid, p1, H, W, ptr(out), stream())
+    return out
+
+
+def rise_apply(images, baseline, seed, grid, p1, n_masks, r0, n, n_pad, out=None):
+    """One chunk of model inputs [n_pad, 3, H, W]: row i < n is baseline + m * (image - baseline) for row r0 + i of the
+    image-major row space N * n_masks (image r // n_masks under mask r % n_masks); rows n .. n_pad are zeros."""
+    seed, grid, p1 = _rise_args(seed, grid, p1, "rise_apply")
+    _need_gpu(images, "rise_apply")
+    if images.dim() != 4 or images.shape[1] != 3 or images.shape[0] < 1:
+        raise ValueError(f"rise_apply: images must be a contiguous fp32 [N, 3, H, W] tensor, got {tuple(images.shape)}")
+    N, _, H, W = images.shape
+    _dev_tensor(images, torch.float32, (N, 3, H, W), "rise_apply: images")
+    _dev_tensor(baseline, torch.float32, (N, 3, H, W), "rise_apply: baseline")
+    if out is None:
+        out = torch.empty((max(int(n_pad), 0), 3, H, W), device=images.device, dtype=torch.float32)
+    else:
+        _dev_tensor(out, torch.float32, (n_pad, 3, H, W), "rise_apply: out")
+    call("mmskin_rise_apply", ptr(images), ptr(baseline), N, H, W, seed, grid, p1, int(n_masks), int(r0), int(n), int(n_pad), ptr(out),
+         stream())
+    return out
+
+
+def rise_accumulate(logits, clean_logits, size, seed, grid, p1, n_masks, target=None, out=None):
+    """logits fp32 [>= N * n_masks, K] (image-major rows), clean_logits fp32 [N, K], size = (H, W), target int32 [N] or None =
+    the argmax of the clean logits -> (saliency_sum [N, H, W], coverage [H, W], clean_prob [N], target_used int32 [N]): fp64 sums
+    over the masks in ascending order, weighted by the soft-max probability of the target class.  out: those four, preallocated."""
+    seed, grid, p1 = _rise_args(seed, grid, p1, "rise_accumulate")
+    _need_gpu(logits, "rise_accumulate")
+    H, W, n_masks = int(size[0]), int(size[1]), int(n_masks)
+    if not torch.is_tensor(clean_logits) or clean_logits.dim() != 2 or clean_logits.shape[0] < 1:
+        raise ValueError("rise_accumulate: clean_logits must be a contiguous fp32 [N, K] device tensor")
+    N, K = clean_logits.shape
+    _dev_tensor(clean_logits, torch.float32, (N, K), "rise_accumulate: clean_logits")
+    if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous() or logits.shape[1] != K \
+            or logits.shape[0] < N * n_masks:
+        raise ValueError(f"rise_accumulate: logits must be a contiguous fp32 [>= {N * n_masks}, {K}] tensor, got {tuple(logits.shape)} "
+                         f"{logits.dtype}")
+    if target is not None:
+        _dev_tensor(target, torch.int32, (N,), "rise_accumulate: target")
+    dev = logits.device
+    if out is None:
+        out = (torch.empty((N, max(H, 0), max(W, 0)), device=dev, dtype=torch.float64),
+               torch.empty((max(H, 0), max(W, 0)), device=dev, dtype=torch.float64),
+               torch.empty((N,), device=dev, dtype=torch.float64), torch.empty((N,), device=dev, dtype=torch.int32))
+    else:
+        for t, dtype, shape, name in zip(out, (torch.float64,) * 3 + (torch.int32,), ((N, H, W), (H, W), (N,), (N,)),
+                                         ("saliency_sum", "coverage", "clean_prob", "target_used")):
+            _dev_tensor(t, dtype, shape, f"rise_accumulate: {name}")
+    nbytes = int(_lib.load().mmskin_rise_workspace_bytes(N, n_masks))
+    workspace = torch.empty((max(nbytes, 8),), device=dev, dtype=torch.uint8)
+    call("mmskin_rise_accumulate", ptr(logits), ptr(target), ptr(clean_logits), N, K, H, W, seed, grid, p1, n_masks, ptr(out[0]),
+         ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(workspace), stream())
+    return tuple(out)
+
+
 # ---------------------------------------------------------------------------------------------- metadata sweeps (forward only)
 META_NONE, META_CAT_SET, META_CAT_TOGGLE, META_NUM_ADD, META_NUM_SET = 0, 1, 2, 3, 4          # MMSKIN_META_* of mmskin.h
 # one record per variant: struct mmskin_meta_variant of include/mmskin.h (32 bytes)
