@@ -1015,6 +1015,66 @@ int mmskin_permutation_finalize(const int32_t* confusion, const int64_t* counts,
                                 double* metrics, double* importances, double* mean, double* std, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Bootstrap confidence intervals of a fold's metrics (csrc/bootstrap.hip, mmskin.bootstrap.BootstrapMetrics): the non-parametric
+ * bootstrap over the N rows of a validation fold, B replicates, each scored as exact integers.  scores fp32 [N][K] are the
+ * soft-max rows of an evaluation pass; labels and preds int64 [N], read in place, both in [0, K) (the caller drops other rows; a
+ * row whose label is outside counts nowhere, a prediction outside enters no confusion cell).
+ * 1 <= N <= MMSKIN_BOOTSTRAP_MAX_ROWS, 2 <= K <= MMSKIN_BOOTSTRAP_MAX_CLASSES, 1 <= B <= MMSKIN_BOOTSTRAP_MAX_RESAMPLES.
+ *
+ * The generator keeps no state: key = mix64(seed) (mix64 as under LIME above); replicate b, draw t (0 <= t < N):
+ * h = mix64(key ^ ((uint64) b << 32 | t)), u = h >> 32.  MMSKIN_BOOTSTRAP_PLAIN: draw t hits row (u N) >> 32 (64-bit arithmetic;
+ * the bias of multiply-high is below N / 2^32).  MMSKIN_BOOTSTRAP_STRATIFIED: with c the label of row t and m_c the ascending list
+ * of the n_c rows with label c, draw t hits m_c[(u n_c) >> 32], so every class keeps its count.  MMSKIN_BOOTSTRAP_POINT: no draws,
+ * every weight is 1 (the fold itself).  w_b[i] = the number of draws of replicate b that hit row i; sum_i w_b[i] = N.  The
+ * weights depend on (seed, b, N) only -- stratified: and on the labels -- never on the scores, on B or on the range of a call.
+ *
+ * The caller's tables, all int32 on the device (mmskin.ops.bootstrap_tables builds them with a device sort):
+ *   order [K][N]        order[c][q] = the row at position q when the rows are sorted by scores[.][c], ascending
+ *   lo, hi [K][N]       the tie group of position q in that order: scores[order[c][x]][c] == scores[order[c][q]][c] exactly for
+ *                       lo[c][q] <= x < hi[c][q], 0 <= lo <= q < hi <= N
+ *   members [N]         the rows in ascending order of (label, row); class_start [K + 1]: members[class_start[c] ..
+ *                       class_start[c + 1]) are the rows with label c.  Read in stratified mode only (may be NULL otherwise).
+ * An entry out of range is skipped, never followed.
+ *
+ * bootstrap_weights: w int32 [b1 - b0][N], the weights of replicates [b0, b1) (w points at b0).
+ * bootstrap_replicates: for each replicate b of [b0, b1) it WRITES, once, and nothing outside those slices:
+ *   confusion int32 [B][K][K]     confusion[b][y][p] = the sum of w_b[i] over the rows with label y and prediction p
+ *   counts    int64 [B][3 K]      pos[K], neg[K] (weighted row counts), wins2[K]: wins2[c] = the sum over (i with label c, j with
+ *                                 another label) of w_b[i] w_b[j] (2 [s[i][c] > s[j][c]] + [s[i][c] == s[j][c]]), the pair rule
+ *                                 of mmskin_ovr_auc_counts below.  The scores must hold no NaN (the caller checks).
+ * One workgroup per replicate; w_b lives in LDS only; integer LDS atomics and single-owner sums: bitwise repeatable.  In POINT
+ * mode the integers equal mmskin_ovr_auc_counts and the criterion meter's confusion matrix on the same rows.
+ *
+ * bootstrap_finalize: metrics fp64 [M][B], M = mmskin_bootstrap_metric_columns(K) = 7 + 2 K, column m of replicate b at
+ * metrics[m B + b]:  0 accuracy, 1 balanced_accuracy (mean recall over the classes that occur), 2 precision, 3 recall, 4 f1_score
+ * (K = 2: of class 1; otherwise weighted by the true counts; a ratio with a zero denominator is 0), 5 auc (K = 2: of class 1;
+ * otherwise the mean of the per-class AUCs weighted by pos over the classes with a positive and a negative row), 6 macro_auc
+ * (their unweighted mean), 7 + c recall of class c, 7 + K + c AUC of class c = wins2 / (2 pos neg).  A metric that is undefined
+ * in a replicate is NaN there.  summary fp64 [5][M]: n_valid (the replicates that are not NaN), mean, std (ddof = 1) over the
+ * valid replicates summed in replicate order, and the q_lo and q_hi quantiles of the valid replicates by numpy's linear method
+ * (0 <= q_lo <= q_hi <= 1); all NaN when n_valid = 0, std NaN when n_valid = 1.
+ * bootstrap_compare: two metric tables fp64 [M][B] -> delta [M][B] = a - b (NaN if either is), its summary [5][M] as above, and
+ * sign_counts int64 [M][2] = the number of replicates with delta <= 0 and with delta >= 0.
+ * Errors (nothing is launched, no GPU needed): N, K or B outside the limits is MMSKIN_ERR_UNSUPPORTED with the limit's name in
+ * the message; an unknown mode, a range outside [0, B], quantiles out of order, a null argument are MMSKIN_ERR_ARG. */
+#define MMSKIN_BOOTSTRAP_MAX_ROWS 16384
+#define MMSKIN_BOOTSTRAP_MAX_CLASSES 64
+#define MMSKIN_BOOTSTRAP_MAX_RESAMPLES 8192
+#define MMSKIN_BOOTSTRAP_PLAIN 0
+#define MMSKIN_BOOTSTRAP_STRATIFIED 1
+#define MMSKIN_BOOTSTRAP_POINT 2
+int mmskin_bootstrap_metric_columns(int K);
+int mmskin_bootstrap_weights(uint64_t seed, int mode, int N, int K, int B, const int64_t* labels, const int32_t* members,
+                             const int32_t* class_start, int b0, int b1, int32_t* w, void* stream);
+int mmskin_bootstrap_replicates(uint64_t seed, int mode, int N, int K, int B, const int64_t* labels, const int64_t* preds,
+                                const int32_t* members, const int32_t* class_start, const int32_t* order, const int32_t* lo,
+                                const int32_t* hi, int b0, int b1, int32_t* confusion, int64_t* counts, void* stream);
+int mmskin_bootstrap_finalize(const int32_t* confusion, const int64_t* counts, int B, int K, double q_lo, double q_hi,
+                              double* metrics, double* summary, void* stream);
+int mmskin_bootstrap_compare(const double* metrics_a, const double* metrics_b, int B, int M, double q_lo, double q_hi, double* delta,
+                             double* summary, int64_t* sign_counts, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The criterion (csrc/criterion.hip): one forward and one backward launch for three kinds of loss on logits [B][C], row-major,
  * fp32 (logits_dtype 0) or bf16 (1); all arithmetic fp32.  1 <= B <= 2^20, 2 <= C <= 1024.  With m = max z_i,
  * ls = ln sum exp(z_i - m), ce = ls - (z_i[y] - m), p = softmax(z_i):

@@ -222,6 +222,11 @@ _SIGNATURES = {
     "mmskin_permuted_rows": (_i, [_P, _i, _P, _P, _i, _i, _i, _i, _i64, _i64, _P, _P]),
     "mmskin_permutation_scores": (_i, [_P, _P, _i, _i, _i, _i, _i64, _i64, _P, _P, _P]),
     "mmskin_permutation_finalize": (_i, [_P, _P, _P, _i, _i, _i, _P, _P, _P, _P, _P]),
+    "mmskin_bootstrap_metric_columns": (_i, [_i]),
+    "mmskin_bootstrap_weights": (_i, [_u64, _i, _i, _i, _i, _P, _P, _P, _i, _i, _P, _P]),
+    "mmskin_bootstrap_replicates": (_i, [_u64, _i, _i, _i, _i] + [_P] * 7 + [_i, _i, _P, _P, _P]),
+    "mmskin_bootstrap_finalize": (_i, [_P, _P, _i, _i, _d, _d, _P, _P, _P]),
+    "mmskin_bootstrap_compare": (_i, [_P, _P, _i, _i, _d, _d, _P, _P, _P, _P]),
     "mmskin_criterion_scratch_floats": (_i64, [_i, _i, _i]),
     "mmskin_criterion_forward": (_i, [_P, _i, _P, _P, _i, _i, _f, _i, _i] + [_P] * 6),
     "mmskin_criterion_backward": (_i, [_P, _i, _P, _P, _i, _i, _f, _i, _i] + [_P] * 4),

@@ -1682,3 +1682,155 @@ def permutation_finalize(confusion, counts, baseline):
     call("mmskin_permutation_finalize", ptr(confusion), ptr(counts), ptr(baseline), R, G, K, ptr(metrics), ptr(importances), ptr(mean),
          ptr(std), stream())
     return metrics, importances, mean, std
+
+
+# ---------------------------------------------------------------------------------------------- bootstrap intervals of a fold's metrics
+BOOTSTRAP_MAX_ROWS = 16384                                                                   # MMSKIN_BOOTSTRAP_MAX_* of mmskin.h
+BOOTSTRAP_MAX_CLASSES = 64
+BOOTSTRAP_MAX_RESAMPLES = 8192
+BOOTSTRAP_PLAIN, BOOTSTRAP_STRATIFIED, BOOTSTRAP_POINT = 0, 1, 2                             # MMSKIN_BOOTSTRAP_PLAIN ...
+BOOTSTRAP_METRICS = ("accuracy", "balanced_accuracy", "precision", "recall", "f1_score", "auc", "macro_auc")   # columns 0 .. 6
+BOOTSTRAP_CLASS_METRICS = ("per_class_recall", "per_class_auc")                              # columns 7 .. 7 + K and 7 + K .. 7 + 2 K
+BOOTSTRAP_SUMMARY = ("n_valid", "mean", "std", "low", "high")                                # the rows of a summary
+
+
+def bootstrap_check_limits(what, N=None, K=None, B=None):
+    """MMSkinError naming the limit that a row, class or replicate count breaks (the C entry points check the same)"""
+    if N is not None and not 1 <= N <= BOOTSTRAP_MAX_ROWS:
+        raise _lib.MMSkinError(f"{what}: {N} rows; a replicate's weights live in LDS, which holds 1 .. BOOTSTRAP_MAX_ROWS = {BOOTSTRAP_MAX_ROWS}")
+    if K is not None and not 2 <= K <= BOOTSTRAP_MAX_CLASSES:
+        raise _lib.MMSkinError(f"{what}: {K} classes; the kernels hold 2 .. BOOTSTRAP_MAX_CLASSES = {BOOTSTRAP_MAX_CLASSES}")
+    if B is not None and not 1 <= B <= BOOTSTRAP_MAX_RESAMPLES:
+        raise _lib.MMSkinError(f"{what}: {B} replicates; a metric column is sorted in LDS, which holds 1 .. BOOTSTRAP_MAX_RESAMPLES = "
+                               f"{BOOTSTRAP_MAX_RESAMPLES}")
+
+
+def bootstrap_quantiles(confidence):
+    """the two quantiles of the percentile interval, as numpy forms them from the percentiles 100 a / 2 and 100 (1 - a / 2)"""
+    a = 1.0 - float(confidence)
+    return float(np.true_divide(100.0 * a / 2.0, 100)), float(np.true_divide(100.0 * (1.0 - a / 2.0), 100))
+
+
+def bootstrap_tables(scores, labels, preds=None):
+    """The per-call tables of a fold (mmskin.h): scores fp32 [N, K] and labels integer [N] in [0, K) on the device (no NaN, no label
+    outside: the caller has dropped those rows), preds integer [N] or None for the first arg-max of each row.  Returns a dict:
+    labels, preds int64 [N]; order, lo, hi int32 [K, N] (per class the rows in ascending order of their score, and each position's
+    tie group); members int32 [N], class_start int32 [K + 1] (the rows grouped by label); N, K.  A device sort, not a kernel of ours:
+    this runs once per call."""
+    _need_gpu(scores, "bootstrap_tables")
+    if scores.dim() != 2 or scores.dtype != torch.float32:
+        raise ValueError(f"bootstrap_tables: scores must be an fp32 [N, K] tensor, got {scores.dtype} {tuple(scores.shape)}")
+    N, K = scores.shape
+    bootstrap_check_limits("bootstrap_tables", N=N, K=K)
+    dev = scores.device
+    if labels is None or tuple(labels.shape) != (N,) or labels.dtype.is_floating_point or labels.dtype == torch.bool or labels.device != dev:
+        raise ValueError(f"bootstrap_tables: labels must be an integer {(N,)} tensor on {dev}")
+    labels = labels.detach().long().contiguous()
+    if preds is None:
+        preds = scores.argmax(dim=1)
+    elif tuple(preds.shape) != (N,) or preds.dtype.is_floating_point or preds.dtype == torch.bool or preds.device != dev:
+        raise ValueError(f"bootstrap_tables: preds must be an integer {(N,)} tensor on {dev}")
+    preds = preds.detach().long().contiguous()
+    vals, order = torch.sort(scores.detach().t().contiguous(), dim=1, stable=True)           # [K, N]
+    at = torch.arange(N, device=dev, dtype=torch.int64).expand(K, N)
+    edge = torch.ones((K, 1), dtype=torch.bool, device=dev)
+    differs = vals[:, 1:] != vals[:, :-1]                                                    # position q + 1 opens a new tie group
+    lo = torch.cummax(torch.where(torch.cat([edge, differs], dim=1), at, torch.zeros_like(at)), dim=1).values
+    ends = torch.where(torch.cat([differs, edge], dim=1), at + 1, torch.full_like(at, N))
+    hi = torch.cummin(ends.flip(1), dim=1).values.flip(1)
+    members = torch.sort(labels, stable=True).indices
+    class_start = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+    class_start[1:] = torch.cumsum(torch.bincount(labels.clamp(0, K - 1), minlength=K), dim=0)
+    i32 = lambda t: t.to(torch.int32).contiguous()
+    return {"labels": labels, "preds": preds, "order": i32(order), "lo": i32(lo), "hi": i32(hi), "members": i32(members),
+            "class_start": i32(class_start), "N": int(N), "K": int(K)}
+
+
+def _bootstrap_range(B, b0, b1):
+    b0 = int(b0)
+    return b0, (B if b1 is None else int(b1))
+
+
+def bootstrap_weights(seed, n_rows, n_resamples, device=None, b0=0, b1=None, tables=None):
+    """w int32 [b1 - b0, N]: how often each row is drawn in the replicates [b0, b1) of a study of `n_resamples`
+    (mmskin_bootstrap_weights).  Plain resampling needs no table; with `tables` (bootstrap_tables) the draws are stratified by
+    label.  The weights depend on (seed, replicate, N) -- stratified: and the labels -- only."""
+    N, B = int(n_rows), int(n_resamples)
+    K = 2 if tables is None else tables["K"]
+    bootstrap_check_limits("bootstrap_weights", N=N, K=K, B=B)
+    if tables is not None and tables["N"] != N:
+        raise ValueError(f"bootstrap_weights: the tables hold {tables['N']} rows, n_rows is {N}")
+    b0, b1 = _bootstrap_range(B, b0, b1)
+    if not torch.cuda.is_available():
+        raise _lib.MMSkinError("bootstrap_weights needs a HIP device; there is no CPU fallback")
+    dev = tables["labels"].device if tables is not None else (torch.device("cuda") if device is None else torch.device(device))
+    with torch.cuda.device(dev):
+        w = torch.empty((max(b1 - b0, 0), N), dtype=torch.int32, device=dev)
+        if tables is None:
+            call("mmskin_bootstrap_weights", int(seed) & (2 ** 64 - 1), BOOTSTRAP_PLAIN, N, K, B, None, None, None, b0, b1, ptr(w), stream())
+        else:
+            call("mmskin_bootstrap_weights", int(seed) & (2 ** 64 - 1), BOOTSTRAP_STRATIFIED, N, K, B, ptr(tables["labels"]),
+                 ptr(tables["members"]), ptr(tables["class_start"]), b0, b1, ptr(w), stream())
+    return w
+
+
+def bootstrap_accumulators(B, K, device, fill=0):
+    """(confusion int32 [B, K, K], counts int64 [B, 3 K]) for bootstrap_replicates to fill"""
+    bootstrap_check_limits("bootstrap_accumulators", K=int(K), B=int(B))
+    return (torch.full((B, K, K), fill, dtype=torch.int32, device=device), torch.full((B, 3 * K), fill, dtype=torch.int64, device=device))
+
+
+def bootstrap_replicates(tables, seed, mode, confusion, counts, b0=0, b1=None):
+    """The integers of replicates [b0, b1) written into their slices of confusion int32 [B, K, K] and counts int64 [B, 3 K] (pos,
+    neg, wins2), one workgroup per replicate (mmskin_bootstrap_replicates).  mode: BOOTSTRAP_PLAIN, BOOTSTRAP_STRATIFIED, or
+    BOOTSTRAP_POINT for the fold itself (all weights 1)."""
+    N, K = tables["N"], tables["K"]
+    _need_gpu(tables["labels"], "bootstrap_replicates")
+    if confusion is None or confusion.dim() != 3:
+        raise ValueError("bootstrap_replicates: confusion must be an int32 [B, K, K] device tensor")
+    B = confusion.shape[0]
+    bootstrap_check_limits("bootstrap_replicates", N=N, K=K, B=B)
+    _dev_tensor(confusion, torch.int32, (B, K, K), "bootstrap_replicates: confusion")
+    _dev_tensor(counts, torch.int64, (B, 3 * K), "bootstrap_replicates: counts")
+    b0, b1 = _bootstrap_range(B, b0, b1)
+    call("mmskin_bootstrap_replicates", int(seed) & (2 ** 64 - 1), int(mode), N, K, B, ptr(tables["labels"]), ptr(tables["preds"]),
+         ptr(tables["members"]), ptr(tables["class_start"]), ptr(tables["order"]), ptr(tables["lo"]), ptr(tables["hi"]), b0, b1, ptr(confusion),
+         ptr(counts), stream())
+
+
+def bootstrap_finalize(confusion, counts, confidence=0.95):
+    """(metrics fp64 [7 + 2 K, B], summary fp64 [5, 7 + 2 K]) on the device from the filled accumulators: the metric columns in the
+    order BOOTSTRAP_METRICS, then K per-class recalls, then K per-class AUCs; the summary rows are BOOTSTRAP_SUMMARY
+    (mmskin_bootstrap_finalize)."""
+    _need_gpu(confusion, "bootstrap_finalize")
+    if confusion.dim() != 3:
+        raise ValueError("bootstrap_finalize: confusion must be an int32 [B, K, K] device tensor")
+    B, K = confusion.shape[:2]
+    bootstrap_check_limits("bootstrap_finalize", K=K, B=B)
+    _dev_tensor(confusion, torch.int32, (B, K, K), "bootstrap_finalize: confusion")
+    _dev_tensor(counts, torch.int64, (B, 3 * K), "bootstrap_finalize: counts")
+    q_lo, q_hi = bootstrap_quantiles(confidence)
+    M = 7 + 2 * K
+    metrics = torch.empty((M, B), dtype=torch.float64, device=confusion.device)
+    summary = torch.empty((5, M), dtype=torch.float64, device=confusion.device)
+    call("mmskin_bootstrap_finalize", ptr(confusion), ptr(counts), B, K, q_lo, q_hi, ptr(metrics), ptr(summary), stream())
+    return metrics, summary
+
+
+def bootstrap_compare(metrics_a, metrics_b, confidence=0.95):
+    """(delta fp64 [M, B] = a - b, summary fp64 [5, M] of delta, sign_counts int64 [M, 2] = the replicates with delta <= 0 and with
+    delta >= 0) from two metric tables of bootstrap_finalize made with one seed (mmskin_bootstrap_compare)."""
+    _need_gpu(metrics_a, "bootstrap_compare")
+    if metrics_a.dim() != 2:
+        raise ValueError("bootstrap_compare: the metric tables must be fp64 [M, B] device tensors")
+    M, B = metrics_a.shape
+    bootstrap_check_limits("bootstrap_compare", B=B)
+    _dev_tensor(metrics_a, torch.float64, (M, B), "bootstrap_compare: metrics_a")
+    _dev_tensor(metrics_b, torch.float64, (M, B), "bootstrap_compare: metrics_b")
+    q_lo, q_hi = bootstrap_quantiles(confidence)
+    dev = metrics_a.device
+    delta = torch.empty((M, B), dtype=torch.float64, device=dev)
+    summary = torch.empty((5, M), dtype=torch.float64, device=dev)
+    sign_counts = torch.empty((M, 2), dtype=torch.int64, device=dev)
+    call("mmskin_bootstrap_compare", ptr(metrics_a), ptr(metrics_b), B, M, q_lo, q_hi, ptr(delta), ptr(summary), ptr(sign_counts), stream())
+    return delta, summary, sign_counts
