@@ -1075,6 +1075,78 @@ int mmskin_bootstrap_compare(const double* metrics_a, const double* metrics_b, i
                              double* summary, int64_t* sign_counts, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Calibration of a fold's probabilities (csrc/calibration.hip, mmskin.calibration.Calibration / TemperatureScaling): reliability
+ * tables as exact integers, ECE / MCE / class-wise ECE, Brier score and NLL, their bootstrap, and post-hoc temperature scaling.
+ * probs fp32 [N][K] are soft-max rows (0 <= p <= 1, no NaN: the caller checks); labels int64 [N], read in place, in [0, K) (the
+ * caller drops other rows; a label outside is a hit nowhere and adds nothing to the sums).
+ * 1 <= N <= MMSKIN_CALIBRATION_MAX_ROWS, 2 <= K <= MMSKIN_CALIBRATION_MAX_CLASSES, 1 <= n_bins <= MMSKIN_CALIBRATION_MAX_BINS,
+ * 1 <= R <= MMSKIN_BOOTSTRAP_MAX_RESAMPLES.
+ *
+ * There are K + 1 tables.  Table 0 is the top-label table: the confidence of row i is p[i][pred_i] with pred_i the FIRST arg-max
+ * of the row, its hit is [pred_i == label_i].  Table 1 + c is class c one-vs-rest: confidence p[i][c], hit [label_i == c].
+ * Bins are right-closed.  edges fp32 [K + 1][n_bins + 1], per table, ascending, e_0 = 0 and e_{n_bins} = 1 (neither is read).  The
+ * bin of a confidence p is the number of interior edges e_1 .. e_{n_bins - 1} that are < p, compared in fp32:
+ * np.searchsorted(edges[1:-1], p, side="left").  So p = 0 lies in bin 0, a p exactly on an edge lies in the lower bin, and equal
+ * edges leave empty bins between them.  The fixed-point confidence is q(p) = (int64) rint((double) p 2^30)
+ * (MMSKIN_CALIBRATION_CONF_SCALE_LOG2 = 30, S = 2^30): exact for p >= 2^-7, otherwise off by at most 2^-31 per row.  Every table
+ * entry is an integer, hence independent of the order of summation.
+ *
+ * calibration_codes: the per-fold pass, the same for every replicate: bin uint8 [K + 1][N], q int32 [K + 1][N], hit uint8
+ * [K + 1][N] (table-major: the later passes read them coalesced along N).
+ * calibration_bins: tables int64 [R][K + 1][n_bins][3] = per replicate, table and bin: count = sum w, hits = sum w hit,
+ * conf = sum w q, over the rows of that bin; weights int32 [R][N].  Precondition of a weighted call: w >= 0 and, per replicate,
+ * sum_i w[r][i] < 2^31 (bootstrap weights sum to N), so count and hits stay below 2^31 and conf below 2^61.  One workgroup owns a
+ * (replicate, tile of tables) pair, accumulates it in LDS with integer atomics and WRITES its slice once, nothing outside the R
+ * slices; the caller need not zero the buffer.  A code bin[t][i] >= n_bins is skipped, never followed.  weights == NULL: R is
+ * taken as 1 and every weight as 1; the rows are spread over workgroups that finish with 64-bit integer global atomics into the
+ * slice, which the entry zeroes on `stream` itself.  No floating-point atomics: bitwise repeatable.
+ * calibration_sums: sums fp64 [R][2]: sums[r][0] = sum_i w_i sum_k (p_ik - [label_i == k])^2 (the multi-class Brier sum),
+ * sums[r][1] = sum_i w_i (-log max(p[i][label_i], FLT_MIN)) (the NLL sum), in fp64.  The order is fixed: the rows are cut into
+ * C = min(ceil(N / 4096), 256) chunks of ceil(N / C) rows, a workgroup of 256 threads sums one (chunk, replicate) -- thread t its
+ * rows t, t + 256, ... in order, then a butterfly over the lanes and the waves in order -- and the chunk partials are added in
+ * chunk order.  scratch: mmskin_calibration_sums_scratch_doubles(N, R) = 2 C R doubles (weights == NULL: R = 1), -1 out of range.
+ * calibration_finalize: metrics fp64 [M][R], M = mmskin_calibration_metric_columns(K) = 6 + K, column m of replicate r at
+ * metrics[m R + r].  With W = sum_b count_b of table 0 and d_b = |hits_b S - conf_b| (an exact integer):
+ *   0 ece = sum_b d_b / (S W)              1 mce = max over the non-empty bins of d_b / (S count_b)     (both of table 0)
+ *   2 classwise_ece = the mean over the classes of column 6 + c
+ *   3 confidence_gap = (sum_b conf_b / S - sum_b hits_b) / W of table 0, formed as the exact integer sum_b conf_b - S sum_b hits_b
+ *     over S W: signed, positive when the model is over-confident
+ *   4 brier = sums[r][0] / W               5 nll = sums[r][1] / W               6 + c: the ece of table 1 + c
+ * W = 0 gives NaN in that replicate.  summary fp64 [5][M] is that of bootstrap_finalize above: n_valid, mean, std (ddof = 1), and
+ * the q_lo and q_hi quantiles by numpy's linear method.
+ *
+ * Temperature scaling.  src fp32 [N][K]: the logits z = src, or with from_probs != 0 saved probabilities, z = log(max(src,
+ * FLT_MIN)) in fp64 (soft-max is shift invariant, so they serve as well).  betas: fp64 [G] ON THE HOST, read before the call
+ * returns, 1 <= G <= MMSKIN_TEMPERATURE_MAX_CANDIDATES, each finite and > 0 (beta = 1 / T).  Per candidate, with pi = softmax(beta
+ * z) formed stably in fp64 (shifted by the row's maximum, the variance about the row's mean), a row gives lse(beta z) - beta z_y,
+ * E_pi[z] - z_y and Var_pi[z]; out fp64 [G][3] on the device are their sums over the rows whose label lies in [0, K): the NLL sum,
+ * its first and its second derivative in beta.  One pass over the rows serves all G candidates (a workgroup reads a row once);
+ * the order is fixed: workgroup j of W = min(ceil(N / 64), 1024) takes the 64-row tiles j, j + W, ..., sums a tile over its rows by
+ * a butterfly and the tiles in order, and the W partials are added in order.  scratch: mmskin_temperature_scratch_doubles(N, G) =
+ * 3 G W doubles, -1 out of range.  temperature_apply: out fp32 [N][K] = softmax(beta z), fp64 arithmetic, rounded once.
+ * Errors (nothing is launched, no GPU needed): N, K, n_bins, R or G outside the limits is MMSKIN_ERR_UNSUPPORTED with the limit's
+ * name in the message; quantiles out of order, a beta that is not finite and positive, a null argument are MMSKIN_ERR_ARG. */
+#define MMSKIN_CALIBRATION_MAX_ROWS (1 << 24)
+#define MMSKIN_CALIBRATION_MAX_CLASSES 64
+#define MMSKIN_CALIBRATION_MAX_BINS 64
+#define MMSKIN_CALIBRATION_CONF_SCALE_LOG2 30
+#define MMSKIN_TEMPERATURE_MAX_CANDIDATES 64
+int mmskin_calibration_metric_columns(int K);
+int64_t mmskin_calibration_sums_scratch_doubles(int N, int R);
+int64_t mmskin_temperature_scratch_doubles(int N, int G);
+int mmskin_calibration_codes(const float* probs, const int64_t* labels, int N, int K, const float* edges, int n_bins, uint8_t* bin,
+                             int32_t* q, uint8_t* hit, void* stream);
+int mmskin_calibration_bins(int N, int K, int n_bins, const uint8_t* bin, const int32_t* q, const uint8_t* hit, const int32_t* weights,
+                            int R, int64_t* tables, void* stream);
+int mmskin_calibration_sums(const float* probs, const int64_t* labels, int N, int K, const int32_t* weights, int R, double* scratch,
+                            double* sums, void* stream);
+int mmskin_calibration_finalize(const int64_t* tables, const double* sums, int R, int K, int n_bins, double q_lo, double q_hi,
+                                double* metrics, double* summary, void* stream);
+int mmskin_temperature_stats(const float* src, int from_probs, const int64_t* labels, int N, int K, const double* betas, int G,
+                             double* scratch, double* out, void* stream);
+int mmskin_temperature_apply(const float* src, int from_probs, int N, int K, double beta, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The criterion (csrc/criterion.hip): one forward and one backward launch for three kinds of loss on logits [B][C], row-major,
  * fp32 (logits_dtype 0) or bf16 (1); all arithmetic fp32.  1 <= B <= 2^20, 2 <= C <= 1024.  With m = max z_i,
  * ls = ln sum exp(z_i - m), ce = ls - (z_i[y] - m), p = softmax(z_i):

@@ -6,9 +6,10 @@ Layout:
   models/    drop-in modules with the reference's file / class names
 """
 from . import _lib, criterion, evaluate  # noqa: F401
+from .calibration import Calibration, TemperatureScaling  # noqa: F401
 from .criterion import CrossEntropyLoss, EpochMeter, FocalLoss, SoftTargetCrossEntropy  # noqa: F401
 from .evaluate import evaluate_model  # noqa: F401
 from .permutation import MetadataPermutationImportance  # noqa: F401
 
 __all__ = ["_lib", "criterion", "evaluate", "CrossEntropyLoss", "FocalLoss", "SoftTargetCrossEntropy", "EpochMeter", "evaluate_model",
-           "MetadataPermutationImportance"]
+           "MetadataPermutationImportance", "Calibration", "TemperatureScaling"]

@@ -227,6 +227,15 @@ _SIGNATURES = {
     "mmskin_bootstrap_replicates": (_i, [_u64, _i, _i, _i, _i] + [_P] * 7 + [_i, _i, _P, _P, _P]),
     "mmskin_bootstrap_finalize": (_i, [_P, _P, _i, _i, _d, _d, _P, _P, _P]),
     "mmskin_bootstrap_compare": (_i, [_P, _P, _i, _i, _d, _d, _P, _P, _P, _P]),
+    "mmskin_calibration_metric_columns": (_i, [_i]),
+    "mmskin_calibration_sums_scratch_doubles": (_i64, [_i, _i]),
+    "mmskin_temperature_scratch_doubles": (_i64, [_i, _i]),
+    "mmskin_calibration_codes": (_i, [_P, _P, _i, _i, _P, _i, _P, _P, _P, _P]),
+    "mmskin_calibration_bins": (_i, [_i, _i, _i, _P, _P, _P, _P, _i, _P, _P]),
+    "mmskin_calibration_sums": (_i, [_P, _P, _i, _i, _P, _i, _P, _P, _P]),
+    "mmskin_calibration_finalize": (_i, [_P, _P, _i, _i, _i, _d, _d, _P, _P, _P]),
+    "mmskin_temperature_stats": (_i, [_P, _i, _P, _i, _i, ctypes.POINTER(_d), _i, _P, _P, _P]),
+    "mmskin_temperature_apply": (_i, [_P, _i, _i, _i, _d, _P, _P]),
     "mmskin_criterion_scratch_floats": (_i64, [_i, _i, _i]),
     "mmskin_criterion_forward": (_i, [_P, _i, _P, _P, _i, _i, _f, _i, _i] + [_P] * 6),
     "mmskin_criterion_backward": (_i, [_P, _i, _P, _P, _i, _i, _f, _i, _i] + [_P] * 4),

@@ -1834,3 +1834,182 @@ def bootstrap_compare(metrics_a, metrics_b, confidence=0.95):
     sign_counts = torch.empty((M, 2), dtype=torch.int64, device=dev)
     call("mmskin_bootstrap_compare", ptr(metrics_a), ptr(metrics_b), B, M, q_lo, q_hi, ptr(delta), ptr(summary), ptr(sign_counts), stream())
     return delta, summary, sign_counts
+
+
+# ---------------------------------------------------------------------------------------------- calibration of a fold's probabilities
+CALIBRATION_MAX_ROWS = 1 << 24                                                               # MMSKIN_CALIBRATION_MAX_* of mmskin.h
+CALIBRATION_MAX_CLASSES = 64
+CALIBRATION_MAX_BINS = 64
+CALIBRATION_CONF_SCALE_LOG2 = 30                                                             # q(p) = rint(p 2^30)
+TEMPERATURE_MAX_CANDIDATES = 64
+CALIBRATION_METRICS = ("ece", "mce", "classwise_ece", "confidence_gap", "brier", "nll")      # columns 0 .. 5
+CALIBRATION_CLASS_METRICS = ("per_class_ece",)                                               # columns 6 .. 6 + K
+CALIBRATION_BINNINGS = ("uniform", "quantile")
+
+
+def calibration_check_limits(what, N=None, K=None, n_bins=None, R=None):
+    """MMSkinError naming the limit that a row, class, bin or replicate count breaks (the C entry points check the same)"""
+    if N is not None and not 1 <= N <= CALIBRATION_MAX_ROWS:
+        raise _lib.MMSkinError(f"{what}: {N} rows; the codes are indexed in 31 bits, which holds 1 .. CALIBRATION_MAX_ROWS = "
+                               f"{CALIBRATION_MAX_ROWS}")
+    if K is not None and not 2 <= K <= CALIBRATION_MAX_CLASSES:
+        raise _lib.MMSkinError(f"{what}: {K} classes; the kernels hold 2 .. CALIBRATION_MAX_CLASSES = {CALIBRATION_MAX_CLASSES}")
+    if n_bins is not None and not 1 <= n_bins <= CALIBRATION_MAX_BINS:
+        raise _lib.MMSkinError(f"{what}: {n_bins} bins; a table's cells live in LDS, which holds 1 .. CALIBRATION_MAX_BINS = "
+                               f"{CALIBRATION_MAX_BINS}")
+    if R is not None and not 1 <= R <= BOOTSTRAP_MAX_RESAMPLES:
+        raise _lib.MMSkinError(f"{what}: {R} replicates; a metric column is sorted in LDS, which holds 1 .. BOOTSTRAP_MAX_RESAMPLES = "
+                               f"{BOOTSTRAP_MAX_RESAMPLES}")
+
+
+def _calibration_fold(what, probs, labels):
+    _need_gpu(probs, what)
+    if probs.dim() != 2 or probs.dtype != torch.float32 or not probs.is_contiguous():
+        raise ValueError(f"{what}: probs must be a contiguous fp32 [N, K] tensor, got {probs.dtype} {tuple(probs.shape)}")
+    N, K = probs.shape
+    calibration_check_limits(what, N=N, K=K)
+    _dev_tensor(labels, torch.int64, (N,), f"{what}: labels")
+    return N, K
+
+
+def calibration_confidences(probs):
+    """fp32 [K + 1, N]: row 0 the top-label confidence (the row's maximum), row 1 + c the column of class c (torch or numpy)"""
+    if isinstance(probs, np.ndarray):
+        return np.concatenate([probs.max(axis=1)[None], probs.T], axis=0)
+    return torch.cat([probs.max(dim=1).values[None], probs.t()], dim=0).contiguous()
+
+
+def calibration_edges(probs, labels, n_bins, binning="uniform"):
+    """fp32 [K + 1, n_bins + 1]: the bin edges of every table (mmskin.h), e_0 = 0 and e_n = 1.  "uniform": fp32(j / n_bins) for
+    every table.  "quantile": per table, with its N confidences sorted ascending, e_j = sorted[ceil(j N / n_bins) - 1] for
+    1 <= j < n_bins, so the right-closed bins hold about N / n_bins rows each; equal edges are allowed and leave empty bins.
+    probs fp32 [N, K] as a tensor (a device sort) or a numpy array; labels are not read (the tables bin every row)."""
+    n_bins = int(n_bins)
+    N, K = probs.shape
+    calibration_check_limits("calibration_edges", N=N, K=K, n_bins=n_bins)
+    if binning not in CALIBRATION_BINNINGS:
+        raise ValueError(f"calibration_edges: binning must be one of {CALIBRATION_BINNINGS}, got {binning!r}")
+    host = isinstance(probs, np.ndarray)
+    if binning == "uniform":
+        row = (np.arange(n_bins + 1, dtype=np.float64) / n_bins).astype(np.float32)
+        edges = np.ascontiguousarray(np.broadcast_to(row, (K + 1, n_bins + 1)))
+        return edges if host else torch.from_numpy(edges).to(probs.device)
+    at = -(-np.arange(1, n_bins, dtype=np.int64) * N // n_bins) - 1                             # ceil(j N / n_bins) - 1, in [0, N)
+    conf = calibration_confidences(probs)
+    if host:
+        edges = np.empty((K + 1, n_bins + 1), dtype=np.float32)
+        edges[:, 1:n_bins] = np.sort(conf, axis=1)[:, at]
+    else:
+        edges = torch.empty((K + 1, n_bins + 1), dtype=torch.float32, device=probs.device)
+        edges[:, 1:n_bins] = torch.sort(conf, dim=1).values[:, torch.from_numpy(at).to(probs.device)]
+    edges[:, 0], edges[:, n_bins] = 0.0, 1.0
+    return edges
+
+
+def calibration_codes(probs, labels, edges):
+    """(bin uint8, q int32, hit uint8), each [K + 1, N]: the per-fold codes of every (table, row) (mmskin_calibration_codes)"""
+    N, K = _calibration_fold("calibration_codes", probs, labels)
+    if edges is None or edges.dim() != 2:
+        raise ValueError("calibration_codes: edges must be an fp32 [K + 1, n_bins + 1] device tensor")
+    n_bins = edges.shape[1] - 1
+    calibration_check_limits("calibration_codes", n_bins=n_bins)
+    _dev_tensor(edges, torch.float32, (K + 1, n_bins + 1), "calibration_codes: edges")
+    dev = probs.device
+    code, hit = (torch.empty((K + 1, N), dtype=torch.uint8, device=dev) for _ in range(2))
+    q = torch.empty((K + 1, N), dtype=torch.int32, device=dev)
+    call("mmskin_calibration_codes", ptr(probs), ptr(labels), N, K, ptr(edges), n_bins, ptr(code), ptr(q), ptr(hit), stream())
+    return code, q, hit
+
+
+def calibration_bins(codes, n_bins, weights=None, tables=None, b0=0):
+    """tables int64 [R, K + 1, n_bins, 3] (count, hits, conf) from the codes of calibration_codes (mmskin_calibration_bins).
+    weights None: the fold itself, R = 1.  weights int32 [r, N] (>= 0, each row summing below 2^31): one replicate per row,
+    written into the slices [b0, b0 + r) of `tables` (allocated [r, ...] when None) and nowhere else."""
+    code, q, hit = codes
+    _need_gpu(code, "calibration_bins")
+    T, N = code.shape
+    K, n_bins = T - 1, int(n_bins)
+    r = 1 if weights is None else (weights.shape[0] if weights.dim() == 2 else 0)
+    calibration_check_limits("calibration_bins", N=N, K=K, n_bins=n_bins, R=r)
+    _dev_tensor(code, torch.uint8, (T, N), "calibration_bins: bin")
+    _dev_tensor(q, torch.int32, (T, N), "calibration_bins: q")
+    _dev_tensor(hit, torch.uint8, (T, N), "calibration_bins: hit")
+    if weights is not None:
+        _dev_tensor(weights, torch.int32, (r, N), "calibration_bins: weights")
+    if tables is None:
+        tables, b0 = torch.empty((r, T, n_bins, 3), dtype=torch.int64, device=code.device), 0
+    b0 = int(b0)
+    if tables.dim() != 4 or not 0 <= b0 <= b0 + r <= tables.shape[0]:
+        raise ValueError(f"calibration_bins: replicates [{b0}, {b0 + r}) are not a range of the tables {tuple(tables.shape)}")
+    _dev_tensor(tables, torch.int64, (tables.shape[0], T, n_bins, 3), "calibration_bins: tables")
+    call("mmskin_calibration_bins", N, K, n_bins, ptr(code), ptr(q), ptr(hit), ptr(weights), r, ptr(tables[b0:]), stream())
+    return tables
+
+
+def calibration_sums(probs, labels, weights=None):
+    """fp64 [R, 2]: the weighted Brier and NLL sums of every replicate (mmskin_calibration_sums); weights None: the fold, R = 1"""
+    N, K = _calibration_fold("calibration_sums", probs, labels)
+    r = 1 if weights is None else (weights.shape[0] if weights.dim() == 2 else 0)
+    calibration_check_limits("calibration_sums", R=r)
+    if weights is not None:
+        _dev_tensor(weights, torch.int32, (r, N), "calibration_sums: weights")
+    dev = probs.device
+    scratch = torch.empty(_lib.load().mmskin_calibration_sums_scratch_doubles(N, r), dtype=torch.float64, device=dev)
+    sums = torch.empty((r, 2), dtype=torch.float64, device=dev)
+    call("mmskin_calibration_sums", ptr(probs), ptr(labels), N, K, ptr(weights), r, ptr(scratch), ptr(sums), stream())
+    return sums
+
+
+def calibration_finalize(tables, sums, confidence=0.95):
+    """(metrics fp64 [6 + K, R], summary fp64 [5, 6 + K]) on the device: the columns CALIBRATION_METRICS, then K per-class ECEs;
+    the summary rows are BOOTSTRAP_SUMMARY (mmskin_calibration_finalize)."""
+    _need_gpu(tables, "calibration_finalize")
+    if tables.dim() != 4:
+        raise ValueError("calibration_finalize: tables must be an int64 [R, K + 1, n_bins, 3] device tensor")
+    R, T, n_bins = tables.shape[:3]
+    K = T - 1
+    calibration_check_limits("calibration_finalize", K=K, n_bins=n_bins, R=R)
+    _dev_tensor(tables, torch.int64, (R, T, n_bins, 3), "calibration_finalize: tables")
+    _dev_tensor(sums, torch.float64, (R, 2), "calibration_finalize: sums")
+    q_lo, q_hi = bootstrap_quantiles(confidence)
+    M = 6 + K
+    metrics = torch.empty((M, R), dtype=torch.float64, device=tables.device)
+    summary = torch.empty((5, M), dtype=torch.float64, device=tables.device)
+    call("mmskin_calibration_finalize", ptr(tables), ptr(sums), R, K, n_bins, q_lo, q_hi, ptr(metrics), ptr(summary), stream())
+    return metrics, summary
+
+
+def _temperature_source(what, src):
+    _need_gpu(src, what)
+    if src.dim() != 2 or src.dtype != torch.float32 or not src.is_contiguous():
+        raise ValueError(f"{what}: the scores must be a contiguous fp32 [N, K] tensor, got {src.dtype} {tuple(src.shape)}")
+    N, K = src.shape
+    calibration_check_limits(what, N=N, K=K)
+    return N, K
+
+
+def temperature_stats(src, labels, betas, from_probs=False):
+    """fp64 [G, 3] on the device: per candidate beta = 1 / T the NLL sum of softmax(beta z) over the rows and its first and second
+    derivative in beta (mmskin_temperature_stats).  src fp32 [N, K]: logits, or probabilities with from_probs (z = log p);
+    betas: G <= TEMPERATURE_MAX_CANDIDATES positive floats on the host."""
+    N, K = _temperature_source("temperature_stats", src)
+    _dev_tensor(labels, torch.int64, (N,), "temperature_stats: labels")
+    betas = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
+    G = len(betas)
+    if not 1 <= G <= TEMPERATURE_MAX_CANDIDATES:
+        raise _lib.MMSkinError(f"temperature_stats: {G} candidates; one launch holds 1 .. TEMPERATURE_MAX_CANDIDATES = "
+                               f"{TEMPERATURE_MAX_CANDIDATES}")
+    dev = src.device
+    scratch = torch.empty(_lib.load().mmskin_temperature_scratch_doubles(N, G), dtype=torch.float64, device=dev)
+    out = torch.empty((G, 3), dtype=torch.float64, device=dev)
+    call("mmskin_temperature_stats", ptr(src), int(bool(from_probs)), ptr(labels), N, K, betas.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+         G, ptr(scratch), ptr(out), stream())
+    return out
+
+
+def temperature_apply(src, beta, from_probs=False):
+    """fp32 [N, K] = softmax(beta z), z the logits `src` or log(src) with from_probs (mmskin_temperature_apply)"""
+    N, K = _temperature_source("temperature_apply", src)
+    out = torch.empty_like(src)
+    call("mmskin_temperature_apply", ptr(src), int(bool(from_probs)), N, K, float(beta), ptr(out), stream())
+    return out
