@@ -1204,6 +1204,51 @@ int mmskin_criterion_backward(const void* logits, int logits_dtype, const void* 
 int mmskin_ovr_auc_counts(const float* probs, const int64_t* labels, int64_t N, int C, int64_t* counts, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * One-vs-rest ROC and precision-recall curves of an evaluation pass as exact integers (csrc/curves.hip, mmskin.curves.FoldCurves).
+ * probs: fp32 [N][C], row-major, contiguous; labels: int64 [N], read in place.  Rows whose label lies outside [0, C) count
+ * nowhere, as in mmskin_ovr_auc_counts.  Per class c, with s_i = probs[i][c] over the valid rows:
+ *   pos[c], neg[c]   the valid rows with label c, and the valid rows minus pos[c]
+ *   thr[c][k]        the distinct values of the column under float ==, descending: thr[c][0] > ... > thr[c][n_points[c] - 1]; the
+ *                    stored value is that of the tie group's row with the lowest index (-0 == +0 is one group)
+ *   tp[c][k]         #{i : y_i == c, s_i >= thr[c][k]}          fp[c][k]  #{i : y_i != c, s_i >= thr[c][k]}
+ * A NaN score is neither greater nor equal: it is no threshold and counts in no tp or fp, but its row counts in pos / neg, and
+ * counts[2 C] reports the NaN entries of the valid rows.
+ * mmskin_ovr_curves writes thr fp32 [C][N], tp and fp int32 [C][N] (every slot: those at and past n_points[c] are zero),
+ * n_points int32 [C] and counts int64 [2 C + 1] = { pos[C], neg[C], nan }; it zeroes what it must on `stream` itself.  The ROC
+ * start (0, 0) at threshold +inf and the precision-recall end (precision 1, recall 0) are NOT stored.  With them,
+ * sklearn's roc_curve(y == c, s, drop_intermediate=False) is fpr = [0, fp / neg], tpr = [0, tp / pos], thresholds = [inf, thr];
+ * precision_recall_curve is the reversed tp / (tp + fp) and tp / pos with (1, 0) appended, thresholds the reversed thr.
+ * Everything is an integer or a copy of an input: bitwise repeatable, independent of the launch geometry.  N^2 C compares.
+ * scratch: mmskin_ovr_curves_scratch_ints(N, C) int32 values, not initialised by the caller; -1 out of range.
+ *
+ * mmskin_ovr_curves_summary: summary fp64 [C][S], S = mmskin_ovr_curves_summary_columns(n_spec, n_sens) = 5 + 3 (n_spec + n_sens)
+ * (-1 when a count is outside 0 .. MMSKIN_CURVES_MAX_OPERATING_POINTS), from the arrays above; specificities fp64 [n_spec] and
+ * sensitivities fp64 [n_sens] on the DEVICE.  With tp_{-1} = fp_{-1} = 0:
+ *   0 auc                = W / (2 pos neg), W = sum_k (fp_k - fp_{k-1}) (tp_k + tp_{k-1}), an integer that equals wins2[c] of
+ *                          mmskin_ovr_auc_counts: the trapezoid area IS the Mann-Whitney statistic
+ *   1 average_precision  = sum_k ((tp_k - tp_{k-1}) / pos) (tp_k / (tp_k + fp_k)); fixed order: thread t of 512 adds its points
+ *                          t, t + 512, ... in order, then a butterfly over the lanes, then the waves in order
+ *   2 youden_j, 3 youden_threshold, 4 youden_index: the stored point that maximises tp_k / pos - fp_k / neg, compared as the exact
+ *                          integer tp_k neg - fp_k pos; on ties the first point.  J = that integer / (pos neg)
+ *   5 + 3 a ..           sensitivity at specificity q_a, its threshold and index: among the points with
+ *                          (double) (neg - fp_k) >= q_a * (double) neg (one fp64 multiply, no division) the largest tp_k / pos and
+ *                          the first point that reaches it; no such point: 0, +inf, -1 (the (0, 0) start)
+ *   5 + 3 n_spec + 3 b.. specificity at sensitivity t_b, its threshold and index: among the points with
+ *                          (double) tp_k >= t_b * (double) pos the largest (neg - fp_k) / neg and the first that reaches it, which
+ *                          is the first admissible point; no such point (t_b > 1, or NaN scores): NaN, NaN, -1
+ * A class with pos == 0 or neg == 0 keeps its integer arrays but every summary value is NaN; a class without a stored point
+ * (every score NaN) has NaN for Youden's three.  Indices are stored as fp64 (exact below 2^53).
+ * 2 <= C <= 1024, 1 <= N < 2^31; anything else, or a null argument, is MMSKIN_ERR_ARG with nothing launched (no GPU needed). */
+#define MMSKIN_CURVES_MAX_OPERATING_POINTS 8
+int64_t mmskin_ovr_curves_scratch_ints(int64_t N, int C);
+int mmskin_ovr_curves_summary_columns(int n_spec, int n_sens);
+int mmskin_ovr_curves(const float* probs, const int64_t* labels, int64_t N, int C, int32_t* scratch, float* thr, int32_t* tp,
+                      int32_t* fp, int32_t* n_points, int64_t* counts, void* stream);
+int mmskin_ovr_curves_summary(const float* thr, const int32_t* tp, const int32_t* fp, const int32_t* n_points, const int64_t* counts,
+                              int64_t N, int C, const double* specificities, int n_spec, const double* sensitivities, int n_sens,
+                              double* summary, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * `custom-cnn` image encoder pieces (loadImageModelClassifier.py:50-60): small direct kernels for
  * shapes the MFMA implicit GEMM does not cover (Cin=3, Cout=16).  NCHW fp32. */
 int mmskin_direct_conv2d_forward(const float* x, const float* w, const float* b, float* y, int N, int Cin, int H, int W,

@@ -7,9 +7,10 @@ Layout:
 """
 from . import _lib, criterion, evaluate  # noqa: F401
 from .calibration import Calibration, TemperatureScaling  # noqa: F401
+from .curves import FoldCurves  # noqa: F401
 from .criterion import CrossEntropyLoss, EpochMeter, FocalLoss, SoftTargetCrossEntropy  # noqa: F401
 from .evaluate import evaluate_model  # noqa: F401
 from .permutation import MetadataPermutationImportance  # noqa: F401
 
 __all__ = ["_lib", "criterion", "evaluate", "CrossEntropyLoss", "FocalLoss", "SoftTargetCrossEntropy", "EpochMeter", "evaluate_model",
-           "MetadataPermutationImportance", "Calibration", "TemperatureScaling"]
+           "MetadataPermutationImportance", "Calibration", "TemperatureScaling", "FoldCurves"]

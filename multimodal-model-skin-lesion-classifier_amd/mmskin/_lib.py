@@ -240,6 +240,10 @@ _SIGNATURES = {
     "mmskin_criterion_forward": (_i, [_P, _i, _P, _P, _i, _i, _f, _i, _i] + [_P] * 6),
     "mmskin_criterion_backward": (_i, [_P, _i, _P, _P, _i, _i, _f, _i, _i] + [_P] * 4),
     "mmskin_ovr_auc_counts": (_i, [_P, _P, _i64, _i, _P, _P]),
+    "mmskin_ovr_curves_scratch_ints": (_i64, [_i64, _i]),
+    "mmskin_ovr_curves_summary_columns": (_i, [_i, _i]),
+    "mmskin_ovr_curves": (_i, [_P, _P, _i64, _i] + [_P] * 7),
+    "mmskin_ovr_curves_summary": (_i, [_P] * 5 + [_i64, _i, _P, _i, _P, _i, _P, _P]),
     "mmskin_pool_gap_forward":(_i, [_P] * 3 + [_i] * 5 + [_P]),
     "mmskin_pool_gap_backward": (_i, [_P] * 3 + [_i] * 5 + [_P]),
     "mmskin_star_relu_forward_bf16": (_i, [_P] * 4 + [_i64, _i, _i, _P]),

@@ -4,7 +4,8 @@
     auc_from_counts(counts, num_classes)           the `auc` of the reference's metrics dict from those integers
     per_class_auc(counts)                          wins2 / (2 pos neg), NaN where a class has no positive or no negative row
     evaluate_model(model, dataloader, targets, device, fold_num, base_dir, model_name="None")
-                                                   drop-in for utils/model_metrics.py:15-134
+                                                   drop-in for utils/model_metrics.py:15-134; curves=True adds the fold's ROC and
+                                                   precision-recall curves (mmskin.curves.FoldCurves)
 
 wins2[c] sums, over the pairs (row i with label c, row j with another label), 2 [p[i, c] > p[j, c]] + [p[i, c] == p[j, c]], so
 auc[c] = wins2[c] / (2 pos[c] neg[c]) is the Mann-Whitney statistic: what sklearn's roc_auc_score computes by trapezoids, ties at
@@ -103,7 +104,7 @@ def _dataset_rows(dataloader):
 
 
 def evaluate_model(model, dataloader, targets, device, fold_num: int, base_dir: str, model_name: str = "None", *, extras=False,
-                   image_names=False):
+                   image_names=False, curves=False):
     """utils/model_metrics.py:15-134 in one forward pass -> (metrics, all_labels [N], all_preds [N], all_probs [N, C]) as numpy
     arrays, with labels.npy / predictions.npy / probabilities.npy / targets.npy written to base_dir/{model_name}_fold_{fold_num}.
 
@@ -118,7 +119,10 @@ def evaluate_model(model, dataloader, targets, device, fold_num: int, base_dir: 
     LOGITS, the returned predictions the arg-max of the probabilities: they differ only where two logits round to one
     probability.  Labels outside [0, C) count in no metric (sklearn would count them as errors).
     extras=True adds loss (mean cross-entropy), confusion [C, C] and per_class_auc [C] to metrics; image_names=True appends the
-    names in loader order to the returned tuple, which is all save_predictions.py needs to write predictions_eval_fold_N.csv."""
+    names in loader order to the returned tuple, which is all save_predictions.py needs to write predictions_eval_fold_N.csv.
+    curves=True adds metrics["curves"], the mmskin.curves.FoldCurves of the fold (one-vs-rest ROC and precision-recall curves
+    with their operating points) built from the device buffers before they are copied, and writes curves.npz beside the .npy
+    files; where the probabilities hold a NaN it is None and nothing is written, as for `auc`."""
     folder_path = os.path.join(base_dir, f"{model_name}_fold_{fold_num}")
     os.makedirs(folder_path, exist_ok=True)
     model.eval()
@@ -155,6 +159,10 @@ def evaluate_model(model, dataloader, targets, device, fold_num: int, base_dir: 
     labels = labels_buf[:row] if labels_buf is not None else torch.cat(label_chunks)
     num_classes = meter.num_classes
     counts = ovr_auc_counts(probs, labels)
+    fold_curves = None
+    if curves and counts["nan"] == 0:
+        from .curves import FoldCurves
+        fold_curves = FoldCurves.from_probs(probs, labels)
     preds = probs.argmax(dim=1)
     summary = meter.compute()
     all_labels, all_preds, all_probs = labels.cpu().numpy(), preds.cpu().numpy(), probs.cpu().numpy()
@@ -172,5 +180,9 @@ def evaluate_model(model, dataloader, targets, device, fold_num: int, base_dir: 
         print("[WARN] AUC computation failed: the probabilities contain NaN")
     if extras:
         metrics.update(loss=summary["loss"], confusion=summary["confusion"], per_class_auc=per_class_auc(counts))
+    if curves:
+        metrics["curves"] = fold_curves
+        if fold_curves is not None:
+            fold_curves.save(folder_path)
     out = (metrics, all_labels, all_preds, all_probs)
     return out + (names,) if image_names else out

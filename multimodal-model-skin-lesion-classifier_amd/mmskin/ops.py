@@ -2013,3 +2013,72 @@ def temperature_apply(src, beta, from_probs=False):
     out = torch.empty_like(src)
     call("mmskin_temperature_apply", ptr(src), int(bool(from_probs)), N, K, float(beta), ptr(out), stream())
     return out
+
+
+# ---------------------------------------------------------------------------------------------- ROC / precision-recall curves of a fold
+CURVES_MAX_CLASSES = 1024                                                                    # the limits of mmskin_ovr_auc_counts
+CURVES_MAX_ROWS = 2 ** 31 - 1
+CURVES_MAX_OPERATING_POINTS = 8                                                              # MMSKIN_CURVES_MAX_OPERATING_POINTS of mmskin.h
+
+
+def curves_check_limits(what, N=None, C=None, n_spec=None, n_sens=None):
+    """MMSkinError naming the limit that a row, class or operating-point count breaks (the C entry points check the same)"""
+    if C is not None and not 2 <= C <= CURVES_MAX_CLASSES:
+        raise _lib.MMSkinError(f"{what}: {C} classes; the kernels hold 2 .. CURVES_MAX_CLASSES = {CURVES_MAX_CLASSES}")
+    if N is not None and not 1 <= N <= CURVES_MAX_ROWS:
+        raise _lib.MMSkinError(f"{what}: {N} rows is outside 1 .. CURVES_MAX_ROWS = 2^31 - 1")
+    for n, kind in ((n_spec, "specificities"), (n_sens, "sensitivities")):
+        if n is not None and not 0 <= n <= CURVES_MAX_OPERATING_POINTS:
+            raise _lib.MMSkinError(f"{what}: {n} {kind}; a summary holds 0 .. CURVES_MAX_OPERATING_POINTS = {CURVES_MAX_OPERATING_POINTS}")
+
+
+def ovr_curves(probs, labels, out=None):
+    """(thr fp32 [C, N], tp int32 [C, N], fp int32 [C, N], n_points int32 [C], counts int64 [2 C + 1] = pos, neg, nan) on the device
+    (mmskin_ovr_curves): per class the distinct scores, descending, with the true and false positives at each; slots at and past
+    n_points[c] are zero.  probs fp32 [N, C] contiguous, labels int64 [N].  out: the five tensors to write into, or None."""
+    _need_gpu(probs, "ovr_curves")
+    if probs.dim() != 2 or probs.dtype != torch.float32 or not probs.is_contiguous():
+        raise ValueError(f"ovr_curves: probs must be a contiguous fp32 [N, C] tensor, got {probs.dtype} {tuple(probs.shape)}")
+    N, C = probs.shape
+    curves_check_limits("ovr_curves", N=N, C=C)
+    _dev_tensor(labels, torch.int64, (N,), "ovr_curves: labels")
+    dev = probs.device
+    if out is None:
+        out = (torch.empty((C, N), dtype=torch.float32, device=dev), torch.empty((C, N), dtype=torch.int32, device=dev),
+               torch.empty((C, N), dtype=torch.int32, device=dev), torch.empty(C, dtype=torch.int32, device=dev),
+               torch.empty(2 * C + 1, dtype=torch.int64, device=dev))
+    thr, tp, fp, n_points, counts = out
+    _dev_tensor(thr, torch.float32, (C, N), "ovr_curves: thr")
+    _dev_tensor(tp, torch.int32, (C, N), "ovr_curves: tp")
+    _dev_tensor(fp, torch.int32, (C, N), "ovr_curves: fp")
+    _dev_tensor(n_points, torch.int32, (C,), "ovr_curves: n_points")
+    _dev_tensor(counts, torch.int64, (2 * C + 1,), "ovr_curves: counts")
+    scratch = torch.empty(_lib.load().mmskin_ovr_curves_scratch_ints(N, C), dtype=torch.int32, device=dev)
+    call("mmskin_ovr_curves", ptr(probs), ptr(labels), N, C, ptr(scratch), ptr(thr), ptr(tp), ptr(fp), ptr(n_points), ptr(counts), stream())
+    return thr, tp, fp, n_points, counts
+
+
+def ovr_curves_summary(curves, specificities=(), sensitivities=()):
+    """fp64 [C, 5 + 3 (A + B)] on the device from the tensors of ovr_curves (mmskin_ovr_curves_summary): auc, average_precision,
+    youden_j / threshold / index, then (sensitivity, threshold, index) per requested specificity and (specificity, threshold, index)
+    per requested sensitivity; the requests are host sequences of floats."""
+    thr, tp, fp, n_points, counts = curves
+    _need_gpu(thr, "ovr_curves_summary")
+    if thr.dim() != 2:
+        raise ValueError("ovr_curves_summary: thr must be an fp32 [C, N] device tensor")
+    C, N = thr.shape
+    spec = np.ascontiguousarray(specificities, dtype=np.float64).reshape(-1)
+    sens = np.ascontiguousarray(sensitivities, dtype=np.float64).reshape(-1)
+    curves_check_limits("ovr_curves_summary", N=N, C=C, n_spec=len(spec), n_sens=len(sens))
+    _dev_tensor(thr, torch.float32, (C, N), "ovr_curves_summary: thr")
+    _dev_tensor(tp, torch.int32, (C, N), "ovr_curves_summary: tp")
+    _dev_tensor(fp, torch.int32, (C, N), "ovr_curves_summary: fp")
+    _dev_tensor(n_points, torch.int32, (C,), "ovr_curves_summary: n_points")
+    _dev_tensor(counts, torch.int64, (2 * C + 1,), "ovr_curves_summary: counts")
+    dev = thr.device
+    requests = torch.from_numpy(np.concatenate([spec, sens, [0.0]])).to(dev)                     # one copy; never empty
+    S = _lib.load().mmskin_ovr_curves_summary_columns(len(spec), len(sens))
+    summary = torch.empty((C, S), dtype=torch.float64, device=dev)
+    call("mmskin_ovr_curves_summary", ptr(thr), ptr(tp), ptr(fp), ptr(n_points), ptr(counts), N, C, ptr(requests), len(spec),
+         ptr(requests[len(spec):]), len(sens), ptr(summary), stream())
+    return summary
