@@ -234,6 +234,17 @@ int mmskin_batchnorm_act_forward(const float* x, const float* res, const float* 
 int mmskin_batchnorm_act_backward(const float* dy, const float* x, const float* y, const float* gamma, const float* beta,
                                   const float* save_mean, const float* save_invstd, float* dx, float* dres, float* dgamma, float* dbeta,
                                   int N, int C, int H, int W, int act, int has_residual, int dtype, void* workspace, void* stream);
+/* The two element-wise BatchNorm apply passes alone, on [rows][C] device tensors of element type `dtype` (fp32, or bf16 bit patterns) and
+ * given coefficient vectors; C a multiple of 4 (fp32) / 8 (bf16).  For tests of the launch geometry at shapes the plans do not run.
+ * Forward: y = act(x * scale + shift [+ res | + res * rscale + rshift]); relu != 0 with relu_cap 0: ReLU, > 0: capped ReLU, < 0: SiLU;
+ * mask_bits (may be NULL): one byte per 16-byte chunk, bit e = (stored y of element e > 0).
+ * Backward: dz = mask(dy) by mask_mode (0 none, 1 x * scale + shift > 0, 2 ymask > 0, 3 0 < ymask < 6, 4 times SiLU'(x * scale + shift)),
+ * dx = cA * dz + cB * x + cC; dz (may be NULL) receives the masked dy. */
+int mmskin_bn_apply_rows(const void* x, const void* res, const float* scale, const float* shift, const float* rscale, const float* rshift,
+                         void* y, unsigned char* mask_bits, int64_t rows, int C, int relu, float relu_cap, int dtype, void* stream);
+int mmskin_bn_bwd_apply_rows(const void* dy, const void* x, const void* ymask, const float* scale, const float* shift, int mask_mode,
+                             const float* cA, const float* cB, const float* cC, void* dx, void* dz, int64_t rows, int C, int dtype,
+                             void* stream);
 /* Squeeze-excitation (torchvision SqueezeExcitation: y * sigmoid(fc2(silu(fc1(mean_hw y))))): y, y_se, dy_se, dy are [N][Cp][HW] with
  * Cp = C rounded up to 64 (the plan keeps the padding channels of y at zero); w1 [Csq][C], b1 [Csq], w2 [C][Csq], b2 [C] and their
  * gradients are unpadded.  The backward recomputes the forward's small activations. */

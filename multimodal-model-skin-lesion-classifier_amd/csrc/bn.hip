@@ -285,36 +285,91 @@ int bn_eval_coeffs(int C, const float* gamma, const float* beta, const float* ru
   return MMSKIN_OK;
 }
 
+// Thread mapping of the two apply passes (bn_apply, bn_bwd_apply): column-stationary.  A 256-thread block is CW chunk columns x RL row
+// lanes (CW = min(C / EPC, 256), RL = 256 / CW; threads past CW * RL idle when CW does not divide 256, blockIdx.y walks column blocks
+// when a row has more than 256 chunks), so a thread's channels are fixed for the launch: it loads its per-channel coefficients into
+// registers once and then does APPLY_ROWS rows, RL apart (rows r0 + j * RL, r0 = blockIdx.x * RL * APPLY_ROWS + ry), issuing every
+// payload load of the group before the first use.  For each j the block still touches RL consecutive rows = up to 256 consecutive
+// chunks, as with one chunk per thread.  No loop: blockIdx.x covers every row group (many short workgroups stream faster than few
+// long ones, ew_grid); the last group of a launch takes its rows one at a time.
+constexpr int APPLY_ROWS = 4;
+struct ApplyGeom { int CPR, CW, RL; unsigned gx, gy; };
+static inline int apply_geom(size_t rows, int CPR, ApplyGeom* g, const char* who) {
+  g->CPR = CPR;
+  g->CW = CPR < EW_BLOCK ? CPR : EW_BLOCK;
+  g->RL = EW_BLOCK / g->CW;
+  const size_t per_block = (size_t)g->RL * APPLY_ROWS, gx = (rows + per_block - 1) / per_block;
+  ARG_CHECK(gx <= 0x7fffffffu && ceil_div(CPR, g->CW) <= 65535, "%s: %zu rows x %d chunks per row", who, rows, CPR);
+  g->gx = gx ? (unsigned)gx : 1u;
+  g->gy = (unsigned)ceil_div(CPR, g->CW);
+  return MMSKIN_OK;
+}
+// the calling thread's chunk column and first row; false: an idle thread
+__device__ __forceinline__ bool apply_thread(const ApplyGeom& g, int* col, size_t* r0) {
+  const int ry = (int)threadIdx.x / g.CW;
+  *col = (int)blockIdx.y * g.CW + ((int)threadIdx.x - ry * g.CW);
+  *r0 = (size_t)blockIdx.x * ((size_t)g.RL * APPLY_ROWS) + ry;
+  return ry < g.RL && *col < g.CPR;
+}
+
+// N rows of one chunk column, `stride` elements apart, from element offset `off` (chunk index `chunk`, `cstride` chunks apart)
+template <typename T, int RELU, int RES, bool NT, int N>
+__device__ __forceinline__ void bn_apply_rows(const T* __restrict__ x, const T* __restrict__ res, T* __restrict__ y,
+                                              uint8_t* __restrict__ mask_bits, size_t off, size_t stride, size_t chunk, size_t cstride,
+                                              const float* scale, const float* shift, const float* rscale, const float* rshift,
+                                              float relu_cap) {
+  constexpr int EPC = DT<T>::EPC;
+  Chunk<T> v[N], r[N];
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    if (NT) v[j].load_nt(x + off + j * stride); else v[j].load(x + off + j * stride);     // the raw conv output is read once more only in backward
+    if (RES) { if (NT) r[j].load_nt(res + off + j * stride); else r[j].load(res + off + j * stride); }
+  }
+  if (N > 1) __builtin_amdgcn_sched_barrier(0);   // every load of the group is issued before the first use
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    uint32_t bits = 0;
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) {
+      float t = v[j].v[e] * scale[e] + shift[e];
+      if (RES == 1) t += r[j].v[e];
+      if (RES == 2) t += r[j].v[e] * rscale[e] + rshift[e];
+      // SiLU is its own instantiation: as a run-time branch its exp + divide were if-converted into the ReLU path
+      // and made the (HBM-bound) pass VALU-bound -- 3x slower BatchNorm-apply on every backbone
+      if (RELU == 2) t = t / (1.f + __expf(-t));
+      else if (RELU == 1) { t = fmaxf(t, 0.f); if (relu_cap > 0.f) t = fminf(t, relu_cap); }
+      v[j].v[e] = t;
+      bits |= (from_f32<T>(t) != 0 && t > 0.f ? 1u : 0u) << e;   // bit = (stored y > 0)
+    }
+    v[j].store(y + off + j * stride);
+    if (mask_bits) mask_bits[chunk + j * cstride] = (uint8_t)bits;   // one byte per 16-byte chunk: the ReLU mask for backward
+  }
+}
+
 template <typename T, int RELU, int RES, bool NT = false>  // RELU: 0 none, 1 relu / capped relu, 2 SiLU; RES: 0 none, 1 plain residual, 2 residual*rscale + rshift
 __global__ __launch_bounds__(EW_BLOCK) void bn_apply_kernel(const T* __restrict__ x, const T* __restrict__ res,
                                                             const float* __restrict__ scale,
                                                             const float* __restrict__ shift,
                                                             const float* __restrict__ rscale,
                                                             const float* __restrict__ rshift, T* __restrict__ y,
-                                                            uint8_t* __restrict__ mask_bits, size_t nchunks, int CPR,
+                                                            uint8_t* __restrict__ mask_bits, size_t rows, ApplyGeom g,
                                                             float relu_cap) {
   constexpr int EPC = DT<T>::EPC;
-  for (size_t i = blockIdx.x * (size_t)EW_BLOCK + threadIdx.x; i < nchunks; i += (size_t)gridDim.x * EW_BLOCK) {
-    int c0 = (int)(i % CPR) * EPC;
-    Chunk<T> v;
-    if (NT) v.load_nt(x + i * EPC); else v.load(x + i * EPC);     // the raw conv output is read once more only in backward
-    Chunk<T> r;
-    if (RES) { if (NT) r.load_nt(res + i * EPC); else r.load(res + i * EPC); }
-    uint32_t bits = 0;
+  int col;
+  size_t r0;
+  if (!apply_thread(g, &col, &r0) || r0 >= rows) return;
+  float sc[EPC], sh[EPC], rsc[EPC], rsh[EPC];   // this thread's channels: constant for the launch
 #pragma unroll
-    for (int e = 0; e < EPC; ++e) {
-      float t = v.v[e] * scale[c0 + e] + shift[c0 + e];
-      if (RES == 1) t += r.v[e];
-      if (RES == 2) t += r.v[e] * rscale[c0 + e] + rshift[c0 + e];
-      // SiLU is its own instantiation: as a run-time branch its exp + divide were if-converted into the ReLU path
-      // and made the (HBM-bound) pass VALU-bound -- 3x slower BatchNorm-apply on every backbone
-      if (RELU == 2) t = t / (1.f + __expf(-t));
-      else if (RELU == 1) { t = fmaxf(t, 0.f); if (relu_cap > 0.f) t = fminf(t, relu_cap); }
-      v.v[e] = t;
-      bits |= (from_f32<T>(t) != 0 && t > 0.f ? 1u : 0u) << e;   // bit = (stored y > 0)
-    }
-    v.store(y + i * EPC);
-    if (mask_bits) mask_bits[i] = (uint8_t)bits;   // one byte per 16-byte chunk: the ReLU mask for backward
+  for (int e = 0; e < EPC; ++e) {
+    sc[e] = scale[col * EPC + e]; sh[e] = shift[col * EPC + e];
+    if (RES == 2) { rsc[e] = rscale[col * EPC + e]; rsh[e] = rshift[col * EPC + e]; }
+  }
+  const size_t chunk = r0 * g.CPR + col, cstride = (size_t)g.RL * g.CPR;
+  if (r0 + (size_t)(APPLY_ROWS - 1) * g.RL < rows) {
+    bn_apply_rows<T, RELU, RES, NT, APPLY_ROWS>(x, res, y, mask_bits, chunk * EPC, cstride * EPC, chunk, cstride, sc, sh, rsc, rsh, relu_cap);
+  } else {
+    for (size_t r = r0, ch = chunk; r < rows; r += g.RL, ch += cstride)
+      bn_apply_rows<T, RELU, RES, NT, 1>(x, res, y, mask_bits, ch * EPC, 0, ch, 0, sc, sh, rsc, rsh, relu_cap);
   }
 }
 
@@ -323,17 +378,18 @@ int bn_apply(const T* x, const T* res, const float* scale, const float* shift, c
              const float* rshift, T* y, size_t rows, int C, bool relu, hipStream_t st, uint8_t* mask_bits,
              float relu_cap) {
   constexpr int EPC = DT<T>::EPC;
-  ARG_CHECK(C % EPC == 0, "bn_apply: C=%d", C);
-  size_t nch = rows * (C / EPC);
-  int grid = ew_grid(nch);
+  ARG_CHECK(C % EPC == 0 && C >= EPC, "bn_apply: C=%d", C);
+  ApplyGeom g;
+  if (int rc = apply_geom(rows, C / EPC, &g, "bn_apply")) return rc;
+  const dim3 grid(g.gx, g.gy);
   int mode = res ? (rscale ? 2 : 1) : 0;
 #ifdef MMSKIN_ABLATE   // `make ablate` only: upper bound of folding the plain BN + ReLU apply into its consumers (wrong results, valid timing)
   { static const int abl = [] { const char* v = getenv("MMSKIN_BN_ABLATE"); return v ? atoi(v) : 0; }(); if ((abl & 1) && mode == 0 && relu) return MMSKIN_OK; }
 #endif
-#define LAUNCH(R, H) hipLaunchKernelGGL((bn_apply_kernel<T, R, H>), dim3(grid), dim3(EW_BLOCK), 0, st, x, res, scale, shift, rscale, rshift, y, mask_bits, nch, C / EPC, relu_cap)
+#define LAUNCH(R, H) hipLaunchKernelGGL((bn_apply_kernel<T, R, H>), grid, dim3(EW_BLOCK), 0, st, x, res, scale, shift, rscale, rshift, y, mask_bits, rows, g, relu_cap)
   if (relu && relu_cap < 0.f) { if (mode == 2) LAUNCH(2, 2); else if (mode == 1) LAUNCH(2, 1); else LAUNCH(2, 0); }
   else if (relu) {
-#define LAUNCH_NT(R, H) hipLaunchKernelGGL((bn_apply_kernel<T, R, H, true>), dim3(grid), dim3(EW_BLOCK), 0, st, x, res, scale, shift, rscale, rshift, y, mask_bits, nch, C / EPC, relu_cap)
+#define LAUNCH_NT(R, H) hipLaunchKernelGGL((bn_apply_kernel<T, R, H, true>), grid, dim3(EW_BLOCK), 0, st, x, res, scale, shift, rscale, rshift, y, mask_bits, rows, g, relu_cap)
     if (mode == 2) LAUNCH_NT(1, 2); else if (mode == 1) LAUNCH_NT(1, 1); else LAUNCH_NT(1, 0);
 #undef LAUNCH_NT
   }
@@ -406,34 +462,39 @@ int bn_eval_table(const StageDesc* table_dev, int nlayers, int maxC, const float
 }
 
 // ------------------------------------------------------------------ BN backward
+constexpr bool mask_reads_y(int mode) { return mode == MASK_FROM_Y || mode == MASK_FROM_Y6; }
+// the mask rules on loaded chunks: yv is read by the MASK_FROM_Y / MASK_FROM_Y6 modes only, scale / shift (the chunk's EPC channels) by
+// MASK_FROM_X / MASK_SILU_X only
 template <typename T, int MODE>
-__device__ __forceinline__ void masked_dy(Chunk<T>& dz, const Chunk<T>& xv, const T* ymask, size_t off,
-                                          const float* scale, const float* shift, int c0) {
+__device__ __forceinline__ void mask_chunk(Chunk<T>& dz, const Chunk<T>& xv, const Chunk<T>& yv, const float* scale, const float* shift) {
   constexpr int EPC = DT<T>::EPC;
   if (MODE == MASK_FROM_X) {
 #pragma unroll
     for (int e = 0; e < EPC; ++e)
-      if (!(xv.v[e] * scale[c0 + e] + shift[c0 + e] > 0.f)) dz.v[e] = 0.f;
+      if (!(xv.v[e] * scale[e] + shift[e] > 0.f)) dz.v[e] = 0.f;
   } else if (MODE == MASK_FROM_Y) {
-    Chunk<T> yv;
-    yv.load(ymask + off);
 #pragma unroll
     for (int e = 0; e < EPC; ++e)
       if (!(yv.v[e] > 0.f)) dz.v[e] = 0.f;
   } else if (MODE == MASK_FROM_Y6) {
-    Chunk<T> yv;
-    yv.load(ymask + off);
 #pragma unroll
     for (int e = 0; e < EPC; ++e)
       if (!(yv.v[e] > 0.f && yv.v[e] < 6.f)) dz.v[e] = 0.f;
   } else if (MODE == MASK_SILU_X) {
 #pragma unroll
     for (int e = 0; e < EPC; ++e) {
-      const float t = xv.v[e] * scale[c0 + e] + shift[c0 + e];
+      const float t = xv.v[e] * scale[e] + shift[e];
       const float sg = 1.f / (1.f + __expf(-t));
       dz.v[e] *= sg * (1.f + t * (1.f - sg));
     }
   }
+}
+template <typename T, int MODE>
+__device__ __forceinline__ void masked_dy(Chunk<T>& dz, const Chunk<T>& xv, const T* ymask, size_t off,
+                                          const float* scale, const float* shift, int c0) {
+  Chunk<T> yv;
+  if (mask_reads_y(MODE)) yv.load(ymask + off);
+  mask_chunk<T, MODE>(dz, xv, yv, scale + c0, shift + c0);
 }
 
 template <typename T, int MODE>
@@ -485,23 +546,56 @@ int bn_bwd_reduce(const T* dy, const T* x, const T* ymask, const float* scale, c
   return MMSKIN_OK;
 }
 
+// N rows of one chunk column, `stride` elements apart, from element offset `off`: every load of the group, then row by row
+template <typename T, int MODE, bool WRITE_DZ, bool NT, int N>
+__device__ __forceinline__ void bn_bwd_apply_rows(const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ ymask,
+                                                  T* __restrict__ dx, T* __restrict__ dz_out, size_t off, size_t stride,
+                                                  const float* scale, const float* shift, const float* a, const float* b, const float* c) {
+  constexpr int EPC = DT<T>::EPC;
+  Chunk<T> dz[N], xv[N], yv[N];
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    if (NT) { dz[j].load_nt(dy + off + j * stride); xv[j].load_nt(x + off + j * stride); }
+    else { dz[j].load(dy + off + j * stride); xv[j].load(x + off + j * stride); }
+    if (mask_reads_y(MODE)) yv[j].load(ymask + off + j * stride);
+  }
+  if (N > 1) __builtin_amdgcn_sched_barrier(0);   // every load of the group is issued before the first use
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    mask_chunk<T, MODE>(dz[j], xv[j], yv[j], scale, shift);
+    if (WRITE_DZ) dz[j].store(dz_out + off + j * stride);
+    // cA dz + cB x + cC with its roundings pinned (the product cB x, then one fused cA dz + that, then + cC): left to the compiler's
+    // contraction, the masked instantiations fused the other product and differed from the unmasked ones in the last bit
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) xv[j].v[e] = __builtin_fmaf(a[e], dz[j].v[e], b[e] * xv[j].v[e]) + c[e];
+    xv[j].store(dx + off + j * stride);
+  }
+}
+
 template <typename T, int MODE, bool WRITE_DZ, bool NT = false>
 __global__ __launch_bounds__(EW_BLOCK) void bn_bwd_apply_kernel(
     const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ ymask,
     const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ cA,
     const float* __restrict__ cB, const float* __restrict__ cC, T* __restrict__ dx, T* __restrict__ dz_out,
-    size_t nchunks, int CPR) {
+    size_t rows, ApplyGeom g) {
   constexpr int EPC = DT<T>::EPC;
-  for (size_t i = blockIdx.x * (size_t)EW_BLOCK + threadIdx.x; i < nchunks; i += (size_t)gridDim.x * EW_BLOCK) {
-    const int c0 = (int)(i % CPR) * EPC;
-    const size_t off = i * EPC;
-    Chunk<T> dz, xv;
-    if (NT) { dz.load_nt(dy + off); xv.load_nt(x + off); } else { dz.load(dy + off); xv.load(x + off); }
-    masked_dy<T, MODE>(dz, xv, ymask, off, scale, shift, c0);
-    if (WRITE_DZ) dz.store(dz_out + off);
+  constexpr bool COEF = MODE == MASK_FROM_X || MODE == MASK_SILU_X;   // the modes that recompute scale * x + shift
+  int col;
+  size_t r0;
+  if (!apply_thread(g, &col, &r0) || r0 >= rows) return;
+  float a[EPC], b[EPC], c[EPC], sc[EPC], sh[EPC];   // this thread's channels: constant for the launch
 #pragma unroll
-    for (int e = 0; e < EPC; ++e) xv.v[e] = cA[c0 + e] * dz.v[e] + cB[c0 + e] * xv.v[e] + cC[c0 + e];
-    xv.store(dx + off);
+  for (int e = 0; e < EPC; ++e) {
+    a[e] = cA[col * EPC + e]; b[e] = cB[col * EPC + e]; c[e] = cC[col * EPC + e];
+    if (COEF) { sc[e] = scale[col * EPC + e]; sh[e] = shift[col * EPC + e]; }
+  }
+  const size_t off = (r0 * g.CPR + col) * EPC, stride = (size_t)g.RL * g.CPR * EPC;
+  if (r0 + (size_t)(APPLY_ROWS - 1) * g.RL < rows) {
+    bn_bwd_apply_rows<T, MODE, WRITE_DZ, NT, APPLY_ROWS>(dy, x, ymask, dx, dz_out, off, stride, sc, sh, a, b, c);
+  } else {
+    size_t o = off;
+    for (size_t r = r0; r < rows; r += g.RL, o += stride)
+      bn_bwd_apply_rows<T, MODE, WRITE_DZ, NT, 1>(dy, x, ymask, dx, dz_out, o, 0, sc, sh, a, b, c);
   }
 }
 
@@ -510,13 +604,14 @@ int bn_bwd_apply(const T* dy, const T* x, const T* ymask, const float* scale, co
                  int mask_mode, const float* cA, const float* cB, const float* cC, T* dx, T* dz_out,
                  size_t rows, int C, hipStream_t st) {
   constexpr int EPC = DT<T>::EPC;
-  ARG_CHECK(C % EPC == 0, "bn_bwd_apply: C=%d", C);
-  size_t nch = rows * (C / EPC);
-  int grid = ew_grid(nch);
+  ARG_CHECK(C % EPC == 0 && C >= EPC, "bn_bwd_apply: C=%d", C);
+  ApplyGeom g;
+  if (int rc = apply_geom(rows, C / EPC, &g, "bn_bwd_apply")) return rc;
+  const dim3 grid(g.gx, g.gy);
 #ifdef MMSKIN_ABLATE   // `make ablate` only: upper bound of folding the BN-backward apply into the dgrad / weight-gradient operand loads
   { static const int abl = [] { const char* v = getenv("MMSKIN_BN_ABLATE"); return v ? atoi(v) : 0; }(); if ((abl & 2) && mask_mode == MASK_NONE && !dz_out) return MMSKIN_OK; }
 #endif
-#define LAUNCH(M, W) hipLaunchKernelGGL((bn_bwd_apply_kernel<T, M, W>), dim3(grid), dim3(EW_BLOCK), 0, st, dy, x, ymask, scale, shift, cA, cB, cC, dx, dz_out, nch, C / EPC)
+#define LAUNCH(M, W) hipLaunchKernelGGL((bn_bwd_apply_kernel<T, M, W>), grid, dim3(EW_BLOCK), 0, st, dy, x, ymask, scale, shift, cA, cB, cC, dx, dz_out, rows, g)
   if (mask_mode == MASK_FROM_X) { if (dz_out) LAUNCH(MASK_FROM_X, true); else LAUNCH(MASK_FROM_X, false); }
   else if (mask_mode == MASK_FROM_Y) { if (dz_out) LAUNCH(MASK_FROM_Y, true); else LAUNCH(MASK_FROM_Y, false); }
   else if (mask_mode == MASK_FROM_Y6) { if (dz_out) LAUNCH(MASK_FROM_Y6, true); else LAUNCH(MASK_FROM_Y6, false); }
@@ -525,7 +620,7 @@ int bn_bwd_apply(const T* dy, const T* x, const T* ymask, const float* scale, co
     // nontemporal loads of dz / x (each is read for the last time here; dx stays cacheable: the dgrad and the weight-gradient
     // GEMM read it next): same-box A/B 20.74 -> 20.43 ms per step (cacheable / nontemporal, profiles/r02_experiments.txt)
     if (dz_out) LAUNCH(MASK_NONE, true);
-    else hipLaunchKernelGGL((bn_bwd_apply_kernel<T, MASK_NONE, false, true>), dim3(grid), dim3(EW_BLOCK), 0, st, dy, x, ymask, scale, shift, cA, cB, cC, dx, dz_out, nch, C / EPC);
+    else hipLaunchKernelGGL((bn_bwd_apply_kernel<T, MASK_NONE, false, true>), grid, dim3(EW_BLOCK), 0, st, dy, x, ymask, scale, shift, cA, cB, cC, dx, dz_out, rows, g);
   }
 #undef LAUNCH
   HIP_CHECK_RET(hipGetLastError());

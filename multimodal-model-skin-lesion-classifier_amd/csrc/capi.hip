@@ -1138,6 +1138,25 @@ int mmskin_batchnorm_act_backward(const float* dy, const float* x, const float* 
            bn_act_bwd_op<bf16_t>(dy, x, y, gamma, beta, save_mean, save_invstd, dx, dres, dgamma, dbeta, N, C, H, W, act, workspace, st));
 }
 
+int mmskin_bn_apply_rows(const void* x, const void* res, const float* scale, const float* shift, const float* rscale, const float* rshift,
+                         void* y, unsigned char* mask_bits, int64_t rows, int C, int relu, float relu_cap, int dtype, void* stream) {
+  ARG_CHECK(x && scale && shift && y && rows > 0 && C > 0 && (!rscale || (res && rshift)), "bn_apply_rows: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype,
+           bn_apply<float>((const float*)x, (const float*)res, scale, shift, rscale, rshift, (float*)y, (size_t)rows, C, relu != 0, st, mask_bits, relu_cap),
+           bn_apply<bf16_t>((const bf16_t*)x, (const bf16_t*)res, scale, shift, rscale, rshift, (bf16_t*)y, (size_t)rows, C, relu != 0, st, mask_bits, relu_cap));
+}
+int mmskin_bn_bwd_apply_rows(const void* dy, const void* x, const void* ymask, const float* scale, const float* shift, int mask_mode,
+                             const float* cA, const float* cB, const float* cC, void* dx, void* dz, int64_t rows, int C, int dtype,
+                             void* stream) {
+  ARG_CHECK(dy && x && scale && shift && cA && cB && cC && dx && rows > 0 && C > 0 && mask_mode >= MASK_NONE && mask_mode <= MASK_SILU_X &&
+            (ymask || !(mask_mode == MASK_FROM_Y || mask_mode == MASK_FROM_Y6)), "bn_bwd_apply_rows: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype,
+           bn_bwd_apply<float>((const float*)dy, (const float*)x, (const float*)ymask, scale, shift, mask_mode, cA, cB, cC, (float*)dx, (float*)dz, (size_t)rows, C, st),
+           bn_bwd_apply<bf16_t>((const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)ymask, scale, shift, mask_mode, cA, cB, cC, (bf16_t*)dx, (bf16_t*)dz, (size_t)rows, C, st));
+}
+
 #define SE_ARGS_OK (N > 0 && C > 0 && Cp == pad64(C) && Csq > 0 && HW > 0)
 int64_t mmskin_se_workspace_bytes(int N, int Cp, int Csq, int HW) {
   if (!(N > 0 && Cp > 0 && Csq > 0 && HW > 0)) return -1;

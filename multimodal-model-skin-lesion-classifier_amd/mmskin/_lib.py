@@ -87,6 +87,8 @@ _SIGNATURES = {
     "mmskin_batchnorm_act_workspace_bytes": (_i64, [_i] * 4),
     "mmskin_batchnorm_act_forward": (_i, [_P] * 9 + [_i] * 4 + [_f, _f, _i, _i, _P, _P]),
     "mmskin_batchnorm_act_backward": (_i, [_P] * 11 + [_i] * 7 + [_P, _P]),
+    "mmskin_bn_apply_rows": (_i, [_P] * 8 + [_i64, _i, _i, _f, _i, _P]),
+    "mmskin_bn_bwd_apply_rows": (_i, [_P] * 5 + [_i] + [_P] * 5 + [_i64, _i, _i, _P]),
     "mmskin_se_workspace_bytes": (_i64, [_i] * 4),
     "mmskin_se_forward": (_i, [_P] * 6 + [_i] * 6 + [_P, _P]),
     "mmskin_se_backward": (_i, [_P] * 11 + [_i] * 6 + [_P, _P]),
