@@ -140,6 +140,33 @@ int mmskin_conv2d_dgrad_fused_rows(int N, int Cin, int H, int W, int Cout, int k
 int mmskin_conv2d_dgrad_fused(const float* dy, const float* w, const float* xc, const float* scale, const float* shift, float* dz,
                               float* partial, int* rows_written, int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride,
                               int pad, void* workspace, void* stream);
+/* The data gradient with any fused epilogue of csrc/conv_gemm.hip the ResNet plan attaches (DgradFuse), op level, fp32 or bf16:
+ * v = dgrad(dy) + addend; v = 0 where the mask says so (mask_y > 0 | mask_bits | x * scale + shift > 0); dz = v; per row block the partial
+ * sums [rows][2][Cin] of the stored dz and dz * x (partial), and of dz and dz * x2 (partial_b).  `flags` are the MMSKIN_CRD_* bits of
+ * mmskin_conv_route below, so a caller can ask the route table which instantiation its launch runs; each names one operand, which must be
+ * non-null exactly when its flag is set (SCALE_SHIFT: scale and shift, needs X; X2: x2 and partial_b, needs X and PARTIAL; PARTIAL:
+ * partial and rows_written).  IN2, BIAS and EMPTY are refused.  addend, mask_y, x, x2: [N,Cin,H,W]; with ADDEND_S2 the addend is the
+ * compact [N,Cin,ceil(H/2),ceil(W/2)] tensor added at the even pixels (1x1 / stride 1 layers).  ADDEND | ADDEND_IS_DIN: addend == dz, the
+ * gradient is accumulated into what dz holds (pixels no tap reaches keep their value).  mask_bits is taken in the kernel's own layout, not
+ * converted: one byte per 16-byte chunk of the NHWC `dtype` tensor [N*H*W][Cin], byte (row * Cin + c) * elem_bytes >> 4, bit e = element e
+ * of the chunk passes (8 elements per byte in bf16, 4 in fp32).  partial / partial_b: mmskin_conv2d_dgrad_fused_rows(...) rows;
+ * *rows_written = rows the launch produced.  A refused call has launched nothing. */
+int64_t mmskin_conv2d_dgrad_epilogue_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad);
+int mmskin_conv2d_dgrad_epilogue(const float* dy, const float* w, const float* addend, const float* mask_y, const unsigned char* mask_bits,
+                                 const float* x, const float* scale, const float* shift, const float* x2, float* dz, float* partial,
+                                 float* partial_b, int* rows_written, int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride,
+                                 int pad, int flags, int dtype, void* workspace, void* stream);
+/* The forward convolution with the light epilogue (FwdFuse) or the statistics slabs, op level, fp32 or bf16:
+ * v = acc * mul + addend + bias; ReLU; y = v; mask_out bit = (stored value > 0), in the layout above over [N*OH*OW][Cout].  `flags` are
+ * MMSKIN_CRF_* bits: MUL, BIAS ([Cout] fp32), ADDEND ([N,Cout,OH,OW]) and MASK_OUT name a pointer each, non-null exactly when set; RELU
+ * names none; STATS: stat_sum, stat_sq [rows][Cout] (rows = mmskin_conv2d_forward_epilogue_stat_rows(...)) and stat_rows, which
+ * receives the rows written (with ROWS_FREE the route may pick fewer); NO_OUT (needs STATS): nothing is stored, y is not written and may
+ * be null.  GELU, OUT_F32 and RESIDUAL are refused (the Linear entry points own them).  A refused call has launched nothing. */
+int64_t mmskin_conv2d_forward_epilogue_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad);
+int mmskin_conv2d_forward_epilogue_stat_rows(int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad);
+int mmskin_conv2d_forward_epilogue(const float* x, const float* w, const float* mul, const float* bias, const float* addend, float* y,
+                                   float* stat_sum, float* stat_sq, int* stat_rows, unsigned char* mask_out, int N, int Cin, int H, int W,
+                                   int Cout, int kh, int kw, int stride, int pad, int flags, int dtype, void* workspace, void* stream);
 /* launches of the layer-1 all-taps 3x3 kernel (csrc/conv3x3_c64.hip) since load */
 int64_t mmskin_conv3x3_c64_launches(void);
 int64_t mmskin_stem7x7_launches(void);   /* ... of the direct 7x7 stem convolution (stem7x7.hip) */

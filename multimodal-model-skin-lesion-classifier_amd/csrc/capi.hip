@@ -107,6 +107,91 @@ int conv_bwd_op(const float* dy, const float* x, const float* w, float* dx, floa
   return MMSKIN_OK;
 }
 
+// the mmskin_conv_route flags that name an operand (or, EMPTY, the absence of one) of a DgradFuse / FwdFuse: a launch gets the struct when one is set
+constexpr int CRD_FUSE_BITS = MMSKIN_CRD_MASK_Y | MMSKIN_CRD_MASK_BITS | MMSKIN_CRD_X | MMSKIN_CRD_SCALE_SHIFT | MMSKIN_CRD_X2 | MMSKIN_CRD_IN2 | MMSKIN_CRD_BIAS |
+                              MMSKIN_CRD_ADDEND_S2 | MMSKIN_CRD_PARTIAL | MMSKIN_CRD_EMPTY;
+constexpr int CRF_FUSE_BITS = MMSKIN_CRF_BIAS | MMSKIN_CRF_ADDEND | MMSKIN_CRF_RELU | MMSKIN_CRF_GELU | MMSKIN_CRF_OUT_F32 | MMSKIN_CRF_RESIDUAL | MMSKIN_CRF_MASK_OUT |
+                              MMSKIN_CRF_MUL;
+static_assert(CRD_FUSE_BITS == 0xffc && CRF_FUSE_BITS == 0x3fc, "the masks mmskin_conv_route has always applied");
+
+// ---- the fused epilogues op by op (mmskin_conv2d_dgrad_epilogue / mmskin_conv2d_forward_epilogue): the tensor operands of a DgradFuse /
+// FwdFuse arrive NCHW fp32 and are converted into the workspace; mask bytes, per-channel vectors and the fp32 slabs go to the launcher as
+// the caller passed them.  Both ask the route first, so a launch the launcher would refuse is refused before anything runs.
+struct DgradEpiArgs {
+  const float *dy, *w, *addend, *mask_y; const uint8_t* mask_bits; const float *x, *scale, *shift, *x2;
+  float *dz, *partial, *partial_b; int* rows_written; int flags;
+};
+template <typename T>
+struct DgradEpiWs {
+  StageDesc* table; T *dyh, *wf, *wd, *dzh, *addh, *myh, *xh, *x2h; size_t total;
+  DgradEpiWs(void* ws, const ConvShape& s) {
+    Carver c(ws);
+    const size_t in = (size_t)s.N * s.H * s.W * s.Cin, wgt = (size_t)s.Cout * s.Cin * s.kh * s.kw;
+    table = c.take<StageDesc>(1);
+    dyh = c.take<T>((size_t)s.N * s.OH() * s.OW() * s.Cout); wf = c.take<T>(wgt); wd = c.take<T>(wgt);
+    dzh = c.take<T>(in); addh = c.take<T>(in); myh = c.take<T>(in); xh = c.take<T>(in); x2h = c.take<T>(in);   // addh: the compact addend is smaller
+    total = c.cur;
+  }
+};
+template <typename T>
+int dgrad_epilogue_op(const DgradEpiArgs& g, const ConvShape& s, void* ws, hipStream_t st) {
+  DgradEpiWs<T> c(ws, s);
+  const int fl = g.flags;
+  const bool in_place = (fl & MMSKIN_CRD_ADDEND_IS_DIN) != 0, s2 = (fl & MMSKIN_CRD_ADDEND_S2) != 0;
+  DgradFuse f;
+  f.mask_y = (fl & MMSKIN_CRD_MASK_Y) ? c.myh : nullptr; f.mask_bits = g.mask_bits; f.x = (fl & MMSKIN_CRD_X) ? c.xh : nullptr;
+  f.scale = g.scale; f.shift = g.shift; f.x2 = (fl & MMSKIN_CRD_X2) ? c.x2h : nullptr; f.partial = g.partial; f.partial_b = g.partial_b; f.addend_s2 = s2;
+  DgradFuse* const fp = (fl & CRD_FUSE_BITS) ? &f : nullptr;   // a DgradFuse when a flag names one of its operands, as mmskin_conv_route passes it
+  const T* const addend = (fl & MMSKIN_CRD_ADDEND) ? (in_place ? c.dzh : c.addh) : nullptr;
+  int rc;
+  { ConvGemmArgs a; ConvRoute r; unsigned zero_mask;
+    if ((rc = conv_route_dgrad(s, (int)sizeof(T), c.dyh, c.wd, c.dzh, addend, fp, a, zero_mask, r))) return rc; }
+  if ((rc = nchw_to_nhwc<T>(g.dy, s.N, s.Cout, s.OH(), s.OW(), c.dyh, st))) return rc;
+  if ((rc = stage_one<T>(g.w, s.Cout, s.Cin, s.kh * s.kw, false, c.wf, c.wd, c.table, st))) return rc;
+  if (in_place) { if ((rc = nchw_to_nhwc<T>(g.dz, s.N, s.Cin, s.H, s.W, c.dzh, st))) return rc; }
+  else if (addend && (rc = nchw_to_nhwc<T>(g.addend, s.N, s.Cin, s2 ? (s.H + 1) / 2 : s.H, s2 ? (s.W + 1) / 2 : s.W, c.addh, st))) return rc;
+  if (f.mask_y && (rc = nchw_to_nhwc<T>(g.mask_y, s.N, s.Cin, s.H, s.W, c.myh, st))) return rc;
+  if (f.x && (rc = nchw_to_nhwc<T>(g.x, s.N, s.Cin, s.H, s.W, c.xh, st))) return rc;
+  if (f.x2 && (rc = nchw_to_nhwc<T>(g.x2, s.N, s.Cin, s.H, s.W, c.x2h, st))) return rc;
+  if ((rc = launch_conv_dgrad<T>(s, c.dyh, c.wd, c.dzh, addend, st, fp))) return rc;
+  if (g.rows_written) *g.rows_written = f.rows_written;
+  return nhwc_to_nchw<T>(c.dzh, s.N, s.Cin, s.H, s.W, g.dz, st);
+}
+
+struct FwdEpiArgs {
+  const float *x, *w, *mul, *bias, *addend; float *y, *stat_sum, *stat_sq; int* stat_rows; uint8_t* mask_out; int flags;
+};
+template <typename T>
+struct FwdEpiWs {
+  StageDesc* table; T *xh, *wf, *yh, *addh; size_t total;
+  FwdEpiWs(void* ws, const ConvShape& s) {
+    Carver c(ws);
+    const size_t out = (size_t)s.N * s.OH() * s.OW() * s.Cout;
+    table = c.take<StageDesc>(1);
+    xh = c.take<T>((size_t)s.N * s.H * s.W * s.Cin); wf = c.take<T>((size_t)s.Cout * s.Cin * s.kh * s.kw); yh = c.take<T>(out); addh = c.take<T>(out);
+    total = c.cur;
+  }
+};
+template <typename T>
+int fwd_epilogue_op(const FwdEpiArgs& g, const ConvShape& s, void* ws, hipStream_t st) {
+  FwdEpiWs<T> c(ws, s);
+  const int fl = g.flags;
+  const bool rows_free = (fl & MMSKIN_CRF_ROWS_FREE) != 0;
+  FwdFuse f;
+  f.bias = g.bias; f.mul = g.mul; f.mask_out = g.mask_out; f.relu = (fl & MMSKIN_CRF_RELU) != 0; f.addend = (fl & MMSKIN_CRF_ADDEND) ? c.addh : nullptr;
+  const FwdFuse* const fp = (fl & CRF_FUSE_BITS) ? &f : nullptr;   // a FwdFuse when a flag names one of its operands, as mmskin_conv_route passes it
+  T* const out = (fl & MMSKIN_CRF_NO_OUT) ? nullptr : c.yh;
+  int rc, rows = 0;
+  ConvGemmArgs a; ConvRoute r;
+  if ((rc = conv_route_fwd(s, (int)sizeof(T), c.xh, c.wf, out, g.stat_sum, g.stat_sq, fp, rows_free, a, r))) return rc;
+  if ((rc = nchw_to_nhwc<T>(g.x, s.N, s.Cin, s.H, s.W, c.xh, st))) return rc;
+  if ((rc = stage_one<T>(g.w, s.Cout, s.Cin, s.kh * s.kw, false, c.wf, (T*)nullptr, c.table, st))) return rc;
+  if (f.addend && (rc = nchw_to_nhwc<T>(g.addend, s.N, s.Cout, s.OH(), s.OW(), c.addh, st))) return rc;
+  if ((rc = launch_conv_fwd<T>(s, c.xh, c.wf, out, g.stat_sum, g.stat_sq, st, fp, rows_free ? &rows : nullptr))) return rc;
+  if (g.stat_rows) *g.stat_rows = rows_free ? rows : r.total_mblk;
+  return out ? nhwc_to_nchw<T>(c.yh, s.N, s.Cout, s.OH(), s.OW(), g.y, st) : MMSKIN_OK;
+}
+
 // Average microseconds per launch of `run` (0 = launched) on stream st: three warm-up launches, then `iters` between an event pair.
 // -1.0 when a launch or an event call fails; both events are destroyed on every path.
 template <class F>
@@ -921,6 +1006,77 @@ int mmskin_conv2d_dgrad_fused(const float* dy, const float* w, const float* xc, 
   return nhwc_to_nchw<T>(c.dxh, N, Cin, H, W, dz, st);
 }
 
+/* The data gradient with any fused epilogue the ResNet plan attaches (DgradFuse; flags = MMSKIN_CRD_* as mmskin_conv_route takes them), and
+ * the forward with the light epilogue or the statistics slabs (FwdFuse; MMSKIN_CRF_*): see mmskin.h.  Every flag names an operand that
+ * must be there, every operand needs its flag; what the launcher itself refuses is refused before the first launch as well. */
+#define OPERAND(who, bit, name, present) \
+  ARG_CHECK(((flags & (bit)) != 0) == (present), "%s: flag " #bit " and operand " name " must come together (flags 0x%x)", who, flags)
+int64_t mmskin_conv2d_dgrad_epilogue_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad) {
+  ConvShape s = {N, H, W, Cin, Cout, kh, kw, stride, pad};
+  return ws_bytes<DgradEpiWs<float>>(s);
+}
+int mmskin_conv2d_dgrad_epilogue(const float* dy, const float* w, const float* addend, const float* mask_y, const unsigned char* mask_bits,
+                                 const float* x, const float* scale, const float* shift, const float* x2, float* dz, float* partial,
+                                 float* partial_b, int* rows_written, int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride,
+                                 int pad, int flags, int dtype, void* workspace, void* stream) {
+  const char* const who = "conv2d_dgrad_epilogue";
+  const int known = MMSKIN_CRD_ADDEND | MMSKIN_CRD_ADDEND_IS_DIN | MMSKIN_CRD_MASK_Y | MMSKIN_CRD_MASK_BITS | MMSKIN_CRD_X | MMSKIN_CRD_SCALE_SHIFT |
+                    MMSKIN_CRD_X2 | MMSKIN_CRD_ADDEND_S2 | MMSKIN_CRD_PARTIAL;
+  ARG_CHECK(dy && w && dz && workspace, "%s: null argument", who);
+  ARG_CHECK(N > 0 && Cin > 0 && H > 0 && W > 0 && Cout > 0 && kh > 0 && kw > 0 && stride > 0 && pad >= 0, "%s: bad shape", who);
+  ARG_CHECK(!(flags & ~known), "%s: flags 0x%x: IN2, BIAS and EMPTY are not taken here", who, flags);
+  OPERAND(who, MMSKIN_CRD_ADDEND, "addend", addend != nullptr);
+  OPERAND(who, MMSKIN_CRD_ADDEND_IS_DIN, "addend == dz", addend == dz);
+  ARG_CHECK(!(flags & MMSKIN_CRD_ADDEND_S2) || (flags & (MMSKIN_CRD_ADDEND | MMSKIN_CRD_ADDEND_IS_DIN)) == MMSKIN_CRD_ADDEND,
+            "%s: ADDEND_S2 needs an addend of its own (flags 0x%x)", who, flags);
+  OPERAND(who, MMSKIN_CRD_MASK_Y, "mask_y", mask_y != nullptr);
+  OPERAND(who, MMSKIN_CRD_MASK_BITS, "mask_bits", mask_bits != nullptr);
+  OPERAND(who, MMSKIN_CRD_X, "x", x != nullptr);
+  OPERAND(who, MMSKIN_CRD_SCALE_SHIFT, "scale", scale != nullptr);
+  OPERAND(who, MMSKIN_CRD_SCALE_SHIFT, "shift", shift != nullptr);
+  OPERAND(who, MMSKIN_CRD_X2, "x2", x2 != nullptr);
+  OPERAND(who, MMSKIN_CRD_X2, "partial_b", partial_b != nullptr);
+  OPERAND(who, MMSKIN_CRD_PARTIAL, "partial", partial != nullptr);
+  OPERAND(who, MMSKIN_CRD_PARTIAL, "rows_written", rows_written != nullptr);
+  ARG_CHECK(!(flags & MMSKIN_CRD_SCALE_SHIFT) || (flags & MMSKIN_CRD_X), "%s: SCALE_SHIFT masks from x: it needs X (flags 0x%x)", who, flags);
+  ARG_CHECK(!(flags & MMSKIN_CRD_X2) || ((flags & MMSKIN_CRD_X) && (flags & MMSKIN_CRD_PARTIAL)), "%s: X2 needs X and PARTIAL (flags 0x%x)", who, flags);
+  const ConvShape s = {N, H, W, Cin, Cout, kh, kw, stride, pad};
+  const DgradEpiArgs g = {dy, w, addend, mask_y, mask_bits, x, scale, shift, x2, dz, partial, partial_b, rows_written, flags};
+  DISPATCH(dtype, dgrad_epilogue_op<float>(g, s, workspace, ST(stream)), dgrad_epilogue_op<bf16_t>(g, s, workspace, ST(stream)));
+}
+int64_t mmskin_conv2d_forward_epilogue_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad) {
+  ConvShape s = {N, H, W, Cin, Cout, kh, kw, stride, pad};
+  return ws_bytes<FwdEpiWs<float>>(s);
+}
+int mmskin_conv2d_forward_epilogue_stat_rows(int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad) {
+  ConvShape s = {N, H, W, Cin, Cout, kh, kw, stride, pad};
+  const int a = conv_fwd_stat_rows(s);
+  return a > N ? a : N;   // the layer-1 all-taps kernel writes one row per image
+}
+int mmskin_conv2d_forward_epilogue(const float* x, const float* w, const float* mul, const float* bias, const float* addend, float* y,
+                                   float* stat_sum, float* stat_sq, int* stat_rows, unsigned char* mask_out, int N, int Cin, int H, int W,
+                                   int Cout, int kh, int kw, int stride, int pad, int flags, int dtype, void* workspace, void* stream) {
+  const char* const who = "conv2d_forward_epilogue";
+  const int known = MMSKIN_CRF_STATS | MMSKIN_CRF_ROWS_FREE | MMSKIN_CRF_BIAS | MMSKIN_CRF_ADDEND | MMSKIN_CRF_RELU | MMSKIN_CRF_MASK_OUT | MMSKIN_CRF_MUL |
+                    MMSKIN_CRF_NO_OUT;
+  ARG_CHECK(x && w && workspace, "%s: null argument", who);
+  ARG_CHECK(N > 0 && Cin > 0 && H > 0 && W > 0 && Cout > 0 && kh > 0 && kw > 0 && stride > 0 && pad >= 0, "%s: bad shape", who);
+  ARG_CHECK(!(flags & ~known), "%s: flags 0x%x: GELU, OUT_F32 and RESIDUAL belong to the Linear entry points", who, flags);
+  OPERAND(who, MMSKIN_CRF_MUL, "mul", mul != nullptr);
+  OPERAND(who, MMSKIN_CRF_BIAS, "bias", bias != nullptr);
+  OPERAND(who, MMSKIN_CRF_ADDEND, "addend", addend != nullptr);
+  OPERAND(who, MMSKIN_CRF_MASK_OUT, "mask_out", mask_out != nullptr);
+  OPERAND(who, MMSKIN_CRF_STATS, "stat_sum", stat_sum != nullptr);
+  OPERAND(who, MMSKIN_CRF_STATS, "stat_sq", stat_sq != nullptr);
+  OPERAND(who, MMSKIN_CRF_STATS, "stat_rows", stat_rows != nullptr);
+  ARG_CHECK(!(flags & (MMSKIN_CRF_ROWS_FREE | MMSKIN_CRF_NO_OUT)) || (flags & MMSKIN_CRF_STATS), "%s: ROWS_FREE and NO_OUT need STATS (flags 0x%x)", who, flags);
+  ARG_CHECK(y || (flags & MMSKIN_CRF_NO_OUT), "%s: y required unless NO_OUT", who);
+  const ConvShape s = {N, H, W, Cin, Cout, kh, kw, stride, pad};
+  const FwdEpiArgs g = {x, w, mul, bias, addend, y, stat_sum, stat_sq, stat_rows, mask_out, flags};
+  DISPATCH(dtype, fwd_epilogue_op<float>(g, s, workspace, ST(stream)), fwd_epilogue_op<bf16_t>(g, s, workspace, ST(stream)));
+}
+#undef OPERAND
+
 /* timing helper: runs the forward conv kernel `iters` times on NHWC buffers already resident in the
  * workspace (contents irrelevant) and returns the average microseconds per launch. */
 double mmskin_conv2d_time(int N, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int dtype,
@@ -1313,7 +1469,7 @@ int mmskin_conv_route(int op, int N, int Cin, int H, int W, int Cout, int kh, in
     static float other[1];   // din; the addend is this or its own buffer
     unsigned zero_mask;
     rc = conv_route_dgrad(s, elem_bytes, set, set, other, (flags & MMSKIN_CRD_ADDEND) ? ((flags & MMSKIN_CRD_ADDEND_IS_DIN) ? other : operand) : nullptr,
-                          (flags & 0xffc) ? &f : nullptr, a, zero_mask, r);
+                          (flags & CRD_FUSE_BITS) ? &f : nullptr, a, zero_mask, r);
   } else {
     FwdFuse f;
     f.bias = on(MMSKIN_CRF_BIAS); f.addend = on(MMSKIN_CRF_ADDEND); f.relu = (flags & MMSKIN_CRF_RELU) != 0; f.gelu = (flags & MMSKIN_CRF_GELU) != 0;
@@ -1321,7 +1477,7 @@ int mmskin_conv_route(int op, int N, int Cin, int H, int W, int Cout, int kh, in
     f.mask_out = reinterpret_cast<uint8_t*>(on(MMSKIN_CRF_MASK_OUT));
     float* const stats = on(MMSKIN_CRF_STATS);
     if (op == 0) {
-      rc = conv_route_fwd(s, elem_bytes, set, set, (flags & MMSKIN_CRF_NO_OUT) ? nullptr : set, stats, stats, (flags & 0x3fc) ? &f : nullptr,
+      rc = conv_route_fwd(s, elem_bytes, set, set, (flags & MMSKIN_CRF_NO_OUT) ? nullptr : set, stats, stats, (flags & CRF_FUSE_BITS) ? &f : nullptr,
                           (flags & MMSKIN_CRF_ROWS_FREE) != 0, a, r);
     } else if (op == 2) {   // the 7x7 / stride 2 stem of an N x 3 x H x W batch, in the geometry the plans run
       const StemGeom sg(N, H, W);

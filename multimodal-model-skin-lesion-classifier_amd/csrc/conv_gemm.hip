@@ -1029,7 +1029,8 @@ int conv_route_fwd(const ConvShape& s, int elem_bytes, const void* in, const voi
                    bool rows_free, ConvGemmArgs& a, ConvRoute& r) {
   ARG_CHECK(s.kh * s.kw <= MMSKIN_MAX_TAPS, "conv_fwd: %dx%d kernel has too many taps", s.kh, s.kw);
   const bool any_rows = !stat_sum || rows_free;   // the caller sizes no statistics slab from conv_fwd_stat_rows()
-  if (elem_bytes == 2 && !fuse && any_rows && conv3x3_c64_takes(s, true)) { r = route_outside(CG_C64, s.N); return MMSKIN_OK; }
+  // out: the all-taps kernel always stores its tile, so a statistics-only pass (no output) stays on the 128-row tile
+  if (elem_bytes == 2 && !fuse && any_rows && out && conv3x3_c64_takes(s, true)) { r = route_outside(CG_C64, s.N); return MMSKIN_OK; }
   a = conv_geom_fwd(s, elem_bytes);
   a.in = in; a.w = w; a.out = out; a.stat_sum = stat_sum; a.stat_sq = stat_sq; a.pipe_ok = any_rows ? 1 : 0;
   if (fuse) {

@@ -72,6 +72,11 @@ _SIGNATURES = {
     "mmskin_stem7x7_launches": (_i64, []),
     "mmskin_conv2d_dgrad_fused_rows": (_i, [_i] * 9),
     "mmskin_conv2d_dgrad_fused": (_i, [_P] * 8 + [_i] * 9 + [_P, _P]),
+    "mmskin_conv2d_dgrad_epilogue_workspace_bytes": (_i64, [_i] * 9),
+    "mmskin_conv2d_dgrad_epilogue": (_i, [_P] * 13 + [_i] * 11 + [_P, _P]),
+    "mmskin_conv2d_forward_epilogue_workspace_bytes": (_i64, [_i] * 9),
+    "mmskin_conv2d_forward_epilogue_stat_rows": (_i, [_i] * 9),
+    "mmskin_conv2d_forward_epilogue": (_i, [_P] * 10 + [_i] * 11 + [_P, _P]),
     "mmskin_wgrad3_ring_launches": (_i64, []),
     "mmskin_abn_workspace_bytes": (_i64, [_i] * 5),
     "mmskin_abn_backward": (_i, [_P] * 6 + [_i] * 5 + [_P, _P, _P, _P]),

@@ -4,7 +4,8 @@
 * the table names every instantiation class behind launch_route's switch, or lists it in UNREACHABLE with the reason;
 * a transcription of the cascade the launchers ran before there was one route function (pipe_choose + dispatch_conv_gemm + launch_cfg's
   group_m rule + the two outer `takes`) agrees with the export on all nine values over a grid -- except the launches the contract checks
-  now refuse for every family, which are enumerated by their flag pattern;
+  now refuse for every family, which are enumerated by their flag pattern, and a forward without an output, which no longer goes to the
+  all-taps kernel (it always stores);
 * no route writes more statistics / partial rows than conv_fwd_stat_rows / conv_dgrad_partial_rows promise;
 * the three knobs, each in a child process (they are read once)."""
 import itertools
@@ -150,7 +151,7 @@ def _old_dispatch(eb, a):
     return (C.CG_TILE128, 128, 128, bn_sel, nst, e, group_m(total128, a["Cout"] // bn_sel), total128, a["Cout"] // bn_sel)
 
 
-def _old_route(op, shape, eb, flags):
+def _old_route(op, shape, eb, flags, c64_needs_out=False):
     N, Cin, H, W, Cout, k, stride, pad = shape
     OH, OW = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     f = lambda bit: bool(flags & bit)
@@ -167,7 +168,7 @@ def _old_route(op, shape, eb, flags):
     if op == C.FWD:
         fuse = bool(flags & 0x3fc)
         rows_ok = not f(C.STATS) or f(C.ROWS_FREE)
-        if not fuse and rows_ok and _old_c64_takes(shape, eb):
+        if not fuse and rows_ok and not (c64_needs_out and f(C.NO_OUT)) and _old_c64_takes(shape, eb):
             return (C.CG_C64, 0, 0, 0, 0, 0, 0, N, 1)
         return _old_dispatch(eb, dict(Cout=Cout, C=Cin, wrow=k * k * Cin, IH=H, IW=W, Sy=stride, Sx=stride, OS=1, cls=[(N * OH * OW, k * k)], in_bytes=N * H * W * Cin * eb,
                                       pipe_ok=rows_ok, out=not f(C.NO_OUT), stat_sum=f(C.STATS), bias=f(C.BIAS), addend=f(C.ADDEND), relu=2 if f(C.GELU) else int(f(C.RELU)),
@@ -237,7 +238,7 @@ def test_route_agrees_with_the_cascade_it_replaced_and_keeps_the_row_bounds():
     lib = _lib.load()
     pts = _grid()
     assert len(pts) >= 5000, len(pts)
-    refused = families = 0
+    refused = rerouted = families = 0
     seen = set()
     for op, shape, flags in pts:
         N, Cin, H, W_, Cout, k, stride, pad = shape
@@ -248,6 +249,12 @@ def test_route_agrees_with_the_cascade_it_replaced_and_keeps_the_row_bounds():
                 assert got is None, (op, shape, eb, hex(flags), got)
                 refused += 1
                 continue
+            # the other: the cascade sent a forward WITHOUT an output to the all-taps kernel, which stores its tile unconditionally (a store through
+            # a null pointer); the route keeps such a launch on the rest of the cascade
+            if op == C.FWD and flags & C.NO_OUT and old is not None and old[0] == C.CG_C64:
+                old = _old_route(op, shape, eb, flags, c64_needs_out=True)
+                assert old[0] == C.CG_TILE128, old
+                rerouted += 1
             assert got == old, (op, shape, eb, hex(flags), got, old)
             if got is None:
                 continue
@@ -256,7 +263,7 @@ def test_route_agrees_with_the_cascade_it_replaced_and_keeps_the_row_bounds():
                 assert got[7] <= _cd(N * H * W_, 128) + stride * stride, (shape, got)          # conv_dgrad_partial_rows
             else:
                 assert got[7] <= _cd(N * ((H + 2 * pad - k) // stride + 1) * ((W_ + 2 * pad - k) // stride + 1), 128), (shape, got)   # conv_fwd_stat_rows / stem_conv_stat_rows
-    assert refused > 0 and seen == {C.CG_TILE128, C.CG_BIG256, C.CG_PIPE, C.CG_C64, C.CG_STEM7}
+    assert refused > 0 and rerouted > 0 and seen == {C.CG_TILE128, C.CG_BIG256, C.CG_PIPE, C.CG_C64, C.CG_STEM7}
 
 
 def test_table_rows_keep_the_row_bounds_and_agree_with_the_cascade():

@@ -53,6 +53,18 @@ def _conv(N, Cin, H, W, Cout, k, s, p):
     return "mmskin_conv2d_workspace_bytes", (N, Cin, H, W, Cout, k, k, s, p), 4 * (2 * N * H * W * Cin + N * OH * OW * Cout + 2 * Cout * Cin * k * k)
 
 
+def _dgrad_epilogue(N, Cin, H, W, Cout, k, s, p):
+    OH, OW = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    # NHWC dy; dz, addend, mask_y, x, x2 of the input's size; the staged forward and data-gradient weights
+    return "mmskin_conv2d_dgrad_epilogue_workspace_bytes", (N, Cin, H, W, Cout, k, k, s, p), 4 * (5 * N * H * W * Cin + N * OH * OW * Cout + 2 * Cout * Cin * k * k)
+
+
+def _forward_epilogue(N, Cin, H, W, Cout, k, s, p):
+    OH, OW = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    # NHWC input, output and addend; the staged weight
+    return "mmskin_conv2d_forward_epilogue_workspace_bytes", (N, Cin, H, W, Cout, k, k, s, p), 4 * (N * H * W * Cin + 2 * N * OH * OW * Cout + Cout * Cin * k * k)
+
+
 def _bn(N, C, H, W):
     return "mmskin_batchnorm_workspace_bytes", (N, C, H, W), 4 * 3 * N * C * H * W                # x, y or dy, dx
 
@@ -119,6 +131,9 @@ ROWS = (
                          (2, 128, 14, 14, 128, 3, 2, 1), (2, 128, 15, 13, 128, 3, 2, 1), (2, 256, 14, 14, 512, 1, 2, 0), (1, 512, 7, 7, 512, 3, 1, 1),
                          (2, 64, 56, 56, 64, 3, 1, 1), (3, 128, 28, 28, 64, 3, 1, 1), (5, 64, 14, 14, 128, 3, 1, 1), (2, 64, 9, 13, 64, 3, 1, 1),
                          (2, 64, 8, 8, 64, 3, 1, 1), (2, 64, 8, 8, 64, 1, 2, 0), (1, 3, 8, 8, 16, 3, 1, 1)]]
+    # shapes of tests/conv_epilogue_cases.py and the one of tests/test_gpu_workspace_bounds.py
+    + [f(*c) for f in (_dgrad_epilogue, _forward_epilogue)
+       for c in [(2, 64, 9, 11, 128, 1, 1, 0), (2, 128, 15, 13, 128, 3, 2, 1), (2, 256, 14, 14, 512, 1, 2, 0), (2, 64, 203, 203, 64, 1, 1, 0), (2, 64, 8, 8, 64, 3, 1, 1)]]
     + [_bn(*c) for c in [(4, 64, 9, 7), (2, 2048, 3, 3), (3, 256, 14, 14), (2, 64, 8, 8)]]
     + [_abn(*c) for c in [(2, 64, 256, 14, 14), (3, 128, 512, 9, 11), (20, 64, 256, 14, 14), (6, 128, 512, 14, 14), (256, 64, 256, 56, 56)]]   # tests/test_gpu_abn.py
     + [_stem(*c) for c in [(2, 32, 32), (3, 50, 70), (3, 224, 224)]]

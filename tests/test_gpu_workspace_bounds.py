@@ -61,6 +61,48 @@ def dgrad_fused_case():
     return lib.mmskin_conv2d_workspace_bytes(*shape), run
 
 
+def dgrad_epilogue_case(dtype):
+    import conv_epilogue_oracle as O
+    import conv_route_cases as CR
+    N, Cin, H, W, Cout, k, s, p = 2, 64, 8, 8, 64, 3, 1, 1
+    g = torch.Generator().manual_seed(16)
+    dy, w = _rand(g, N, Cout, H, W), _rand(g, Cout, Cin, k, k, scale=(Cout * k * k) ** -0.5)
+    addend, mask_y, x, x2 = (_rand(g, N, Cin, H, W) for _ in range(4))
+    bits = O.pack_bits(torch.rand(N, Cin, H, W, generator=g) > 0.5, dtype).to(DEV)
+    shape = (N, Cin, H, W, Cout, k, k, s, p)
+    flags = CR.D_ADDEND | CR.D_MASK_Y | CR.D_MASK_BITS | CR.D_X | CR.D_X2 | CR.D_PARTIAL      # every tensor operand: every region of the layout
+    lib = _lib.load()
+    rows = lib.mmskin_conv2d_dgrad_fused_rows(*shape)
+
+    def run(wsp):
+        dz, part, part_b, nw = _new(N, Cin, H, W), torch.zeros(rows, 2, Cin, device=DEV), torch.zeros(rows, 2, Cin, device=DEV), ctypes.c_int(0)
+        call("mmskin_conv2d_dgrad_epilogue", ptr(dy), ptr(w), ptr(addend), ptr(mask_y), ptr(bits), ptr(x), None, None, ptr(x2), ptr(dz), ptr(part), ptr(part_b),
+             ctypes.addressof(nw), *shape, flags, DT[dtype], ptr(wsp), stream())
+        return dz, part[: nw.value], part_b[: nw.value]
+    return lib.mmskin_conv2d_dgrad_epilogue_workspace_bytes(*shape), run
+
+
+def forward_epilogue_case(dtype):
+    import conv_epilogue_oracle as O
+    import conv_route_cases as CR
+    N, Cin, H, W, Cout, k, s, p = 2, 64, 8, 8, 64, 3, 1, 1
+    g = torch.Generator().manual_seed(17)
+    x, w, addend = _rand(g, N, Cin, H, W), _rand(g, Cout, Cin, k, k, scale=(Cin * k * k) ** -0.5), _rand(g, N, Cout, H, W)
+    mul, bias = torch.rand(Cout, generator=g).to(DEV) + 0.5, _rand(g, Cout, scale=0.3)
+    shape = (N, Cin, H, W, Cout, k, k, s, p)
+    flags = CR.MUL | CR.BIAS | CR.ADDEND | CR.RELU | CR.MASK_OUT | CR.STATS
+    lib = _lib.load()
+    rows = lib.mmskin_conv2d_forward_epilogue_stat_rows(*shape)
+
+    def run(wsp):
+        y, ssum, ssq, nw = _new(N, Cout, H, W), torch.zeros(rows, Cout, device=DEV), torch.zeros(rows, Cout, device=DEV), ctypes.c_int(0)
+        mask = torch.zeros(O.mask_bytes(N * H * W, Cout, dtype) // 4 * 4, dtype=torch.uint8, device=DEV)
+        call("mmskin_conv2d_forward_epilogue", ptr(x), ptr(w), ptr(mul), ptr(bias), ptr(addend), ptr(y), ptr(ssum), ptr(ssq), ctypes.addressof(nw), ptr(mask),
+             *shape, flags, DT[dtype], ptr(wsp), stream())
+        return y, ssum[: nw.value], ssq[: nw.value], mask
+    return lib.mmskin_conv2d_forward_epilogue_workspace_bytes(*shape), run
+
+
 def batchnorm_case(dtype):
     N, C, H, W = 2, 64, 8, 8
     g = torch.Generator().manual_seed(6)
@@ -251,6 +293,8 @@ CASES = (
     [(f"conv2d_k3s1-{d}", lambda d=d: conv_case(3, 1, 1, d)) for d in BOTH]
     + [(f"conv2d_k1s2-{d}", lambda d=d: conv_case(1, 2, 0, d)) for d in BOTH]
     + [("dgrad_fused-bf16", dgrad_fused_case)]
+    + [(f"dgrad_epilogue-{d}", lambda d=d: dgrad_epilogue_case(d)) for d in BOTH]
+    + [(f"forward_epilogue-{d}", lambda d=d: forward_epilogue_case(d)) for d in BOTH]
     + [(f"batchnorm-{d}", lambda d=d: batchnorm_case(d)) for d in BOTH]
     + [(f"{e[len('mmskin_'):]}-bf16", lambda e=e: abn_case(e)) for e in ("mmskin_abn_backward", "mmskin_abn_backward_kept_gram", "mmskin_conv1x1_gram_stats")]
     + [(f"stem-{d}", lambda d=d: stem_case(d)) for d in BOTH]
