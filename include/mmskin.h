@@ -1287,6 +1287,62 @@ int mmskin_ovr_curves_summary(const float* thr, const int32_t* tp, const int32_t
                               double* summary, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Per-sample predictive uncertainty (csrc/uncertainty.hip, mmskin.uncertainty.PredictiveUncertainty): the views of test-time
+ * augmentation, the reduction of T stochastic passes to per-row statistics, and the risk-coverage ranking of a fold.
+ *
+ * mmskin_dihedral_views: src [B][C][H][W] of elements of elem_bytes = 1, 2 or 4 bytes (copied, never interpreted); dst
+ * [V][B][C][H][W], one slab per set bit of the 8-bit view_mask, in ascending view id.  View v is y = rot90(x, k = v & 3) over the
+ * last two axes (counter-clockwise, torch.rot90 / np.rot90) followed by a flip along W when v & 4 (torch.flip(y, (3,))):
+ *   0 x[i][j]              1 x[j][W-1-i]          2 x[H-1-i][W-1-j]      3 x[H-1-j][i]
+ *   4 x[i][W-1-j]          5 x[H-1-j][W-1-i]      6 x[H-1-i][j]          7 x[j][i]          (the source of y[i][j])
+ * The odd views (bits 1, 3, 5, 7: mask & 0xaa) turn the plane by a quarter and need H == W; views 0, 2, 4, 6 take any shape.  A
+ * pure permutation, bit-exact; the source is read once and every element of the V slabs is written exactly once, nothing else.
+ * Errors (MMSKIN_ERR_ARG, nothing launched, no GPU needed): an extent below 1, elem_bytes other than 1, 2, 4, view_mask outside
+ * 1 .. 255, a quarter-turn view with H != W, a null argument, src == dst.
+ *
+ * mmskin_uncertainty_reduce: logits fp32, element (t, n, c) at logits[t pass_stride + n row_stride + c] (strides in elements:
+ * row_stride >= C, pass_stride >= 0; a contiguous [T][N][C] block has pass_stride = N C, row_stride = C).
+ * 1 <= T <= MMSKIN_UNCERTAINTY_MAX_PASSES, 2 <= C <= MMSKIN_UNCERTAINTY_MAX_CLASSES, 1 <= N <= 2^24.  Per row n, in fp64, over
+ * t = 0 .. T - 1 in that order, with p_t = softmax of pass t (exp(x - max) / sum, the sum over the classes a butterfly):
+ *   mean_prob fp64 [N][C]   (sum_t p_t) / T
+ *   prob_std  fp64 [N][C]   sqrt((sum_t (p_t - mean)^2) / T): the population standard deviation, from a second walk over the passes
+ *   votes     int32 [N][C]  the passes whose arg-max LOGIT is class c, the first index among equal logits
+ *   pred      int32 [N]     the first index of the largest mean probability
+ *   stats     fp64 [N][7]   0 confidence = mean_prob[pred]          1 margin = confidence - the largest other mean probability
+ *                           2 predictive entropy H[mean_prob], nats   3 expected entropy (sum_t H[p_t]) / T
+ *                           4 mutual information max(col 2 - col 3, 0) 5 variation ratio 1 - max_c votes[c] / T
+ *                           6 prob_std[pred]
+ * H[p] = -sum_c p_c log p_c with 0 log 0 = 0.  A row with a non-finite logit in any pass gets NaN in mean_prob, prob_std and
+ * stats, zero votes and pred = -1.  One wave per row and no atomics: a row's output depends on neither the other rows of the call
+ * nor the launch geometry, and a call is bitwise repeatable.  T or C outside the limits is MMSKIN_ERR_UNSUPPORTED with the limit's
+ * name in the message; N or a stride out of range, a null argument are MMSKIN_ERR_ARG; nothing is launched (no GPU needed).
+ *
+ * mmskin_risk_coverage: score fp64 [N] (larger = less sure; no NaN: the caller checks), wrong uint8 [N] (non-zero = the prediction
+ * is an error), 1 <= N <= MMSKIN_BOOTSTRAP_MAX_ROWS.  counts int32 [N][4]: row i holds, over all j, n_lt = #{score_j < score_i},
+ * n_eq = #{score_j == score_i} (i itself included), e_lt and e_eq = the wrong rows among each.  N^2 compares from LDS tiles,
+ * integer atomics into the block, which the entry zeroes on `stream` itself: exact and independent of the launch geometry.
+ * mmskin_risk_coverage_summary: out fp64 [8] from counts and wrong.  The rows are ranked by ascending score; e(k) is the number of
+ * errors among the k surest rows, and inside a tie group (ranks n_lt + 1 .. n_lt + n_eq) it is the expectation over the order of
+ * the ties, e(k) = e_lt + (k - n_lt) e_eq / n_eq:
+ *   0 aurc = (1 / N) sum_{k = 1 .. N} e(k) / k, the area under the risk-coverage curve
+ *   1 the optimal aurc for the same number of errors E, all of them ranked last: (1 / N) sum_{k > N - E} (k - (N - E)) / k
+ *   2 e-aurc = col 0 - col 1
+ *   3 the error-detection AUROC of the score: wins2 / (2 E (N - E)) with wins2 = sum over the wrong rows of 2 (n_lt - e_lt) +
+ *     (n_eq - e_eq), the Mann-Whitney count of auc_pairs.h (ties at half weight); NaN when E = 0 or E = N
+ *   4 the error rate E / N      5 N      6 E      7 the number of distinct scores
+ * The two sums have a fixed order (one workgroup: thread t of 1024 adds its ranks t + 1, t + 1025, ..., a butterfly over the
+ * lanes, the waves in order); the rest is integer.  Counts that are no ranking (a rank that no tie group covers) give NaN in
+ * columns 0 and 2.  N outside the limit is MMSKIN_ERR_UNSUPPORTED with the limit's name in the message, a null argument is
+ * MMSKIN_ERR_ARG; nothing is launched (no GPU needed). */
+#define MMSKIN_UNCERTAINTY_MAX_PASSES 4096
+#define MMSKIN_UNCERTAINTY_MAX_CLASSES 64
+int mmskin_dihedral_views(const void* src, void* dst, int B, int C, int H, int W, int elem_bytes, int view_mask, void* stream);
+int mmskin_uncertainty_reduce(const float* logits, int64_t pass_stride, int64_t row_stride, int T, int N, int C, double* mean_prob,
+                              double* prob_std, int32_t* votes, int32_t* pred, double* stats, void* stream);
+int mmskin_risk_coverage(const double* score, const uint8_t* wrong, int N, int32_t* counts, void* stream);
+int mmskin_risk_coverage_summary(const int32_t* counts, const uint8_t* wrong, int N, double* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * `custom-cnn` image encoder pieces (loadImageModelClassifier.py:50-60): small direct kernels for
  * shapes the MFMA implicit GEMM does not cover (Cin=3, Cout=16).  NCHW fp32. */
 int mmskin_direct_conv2d_forward(const float* x, const float* w, const float* b, float* y, int N, int Cin, int H, int W,

@@ -6,6 +6,7 @@ first-order gradients -- so first-order results under create_graph=True stay exa
 
 Below that: what ops.py and attention.py both need and neither owns -- the tensor checks every Function opens with, the Linear operand
 mode and the dropout counter."""
+import contextlib
 import functools
 
 import torch
@@ -82,11 +83,30 @@ def get_linear_dtype():
 
 
 _dropout_counter = [0]
+_dropout_streams = []                  # [seed, counter] of every open dropout_stream, the innermost last
+
+
+@contextlib.contextmanager
+def dropout_stream(seed):
+    """Inside the block every dropout of the library draws from a stream of its own: _dropout_state hands out `seed` and offsets
+    from a private counter that starts at 0, so equal seeds and an equal sequence of calls repeat the masks bit for bit.  The
+    global counter and torch's seed are neither read nor moved; the stream ends with the block, also after an exception."""
+    state = [int(seed) & 0xFFFFFFFFFFFFFFFF, 0]
+    _dropout_streams.append(state)
+    try:
+        yield state
+    finally:
+        _dropout_streams.remove(state)
 
 
 def _dropout_state(p, n):
     if p <= 0.0:
         return 0, 0
+    if _dropout_streams:               # callers import this function by name: the override lives here
+        state = _dropout_streams[-1]
+        off = state[1]
+        state[1] += n
+        return state[0], off
     off = _dropout_counter[0]          # this call consumes counters [off, off + n): ranges of successive calls never overlap
     _dropout_counter[0] += n
     return torch.initial_seed() & 0xFFFFFFFFFFFFFFFF, off

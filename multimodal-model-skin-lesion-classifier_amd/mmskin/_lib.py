@@ -251,6 +251,10 @@ _SIGNATURES = {
     "mmskin_ovr_curves_summary_columns": (_i, [_i, _i]),
     "mmskin_ovr_curves": (_i, [_P, _P, _i64, _i] + [_P] * 7),
     "mmskin_ovr_curves_summary": (_i, [_P] * 5 + [_i64, _i, _P, _i, _P, _i, _P, _P]),
+    "mmskin_dihedral_views": (_i, [_P, _P] + [_i] * 6 + [_P]),
+    "mmskin_uncertainty_reduce": (_i, [_P, _i64, _i64, _i, _i, _i] + [_P] * 5 + [_P]),
+    "mmskin_risk_coverage": (_i, [_P, _P, _i, _P, _P]),
+    "mmskin_risk_coverage_summary": (_i, [_P, _P, _i, _P, _P]),
     "mmskin_pool_gap_forward":(_i, [_P] * 3 + [_i] * 5 + [_P]),
     "mmskin_pool_gap_backward": (_i, [_P] * 3 + [_i] * 5 + [_P]),
     "mmskin_star_relu_forward_bf16": (_i, [_P] * 4 + [_i64, _i, _i, _P]),

@@ -2082,3 +2082,99 @@ def ovr_curves_summary(curves, specificities=(), sensitivities=()):
     call("mmskin_ovr_curves_summary", ptr(thr), ptr(tp), ptr(fp), ptr(n_points), ptr(counts), N, C, ptr(requests), len(spec),
          ptr(requests[len(spec):]), len(sens), ptr(summary), stream())
     return summary
+
+
+# ---------------------------------------------------------------------------------------------- per-sample predictive uncertainty
+UNCERTAINTY_MAX_PASSES = 4096                                                                # MMSKIN_UNCERTAINTY_MAX_* of mmskin.h
+UNCERTAINTY_MAX_CLASSES = 64
+UNCERTAINTY_MAX_ROWS = 1 << 24
+UNCERTAINTY_STATS = ("confidence", "margin", "predictive_entropy", "expected_entropy", "mutual_information", "variation_ratio",
+                     "predicted_std")                                                        # columns 0 .. 6 of stats
+RISK_COVERAGE_MAX_ROWS = BOOTSTRAP_MAX_ROWS
+RISK_COVERAGE_SUMMARY = ("aurc", "optimal_aurc", "e_aurc", "error_auroc", "error_rate", "n", "n_wrong", "n_distinct")
+VIEWS_DIHEDRAL, VIEWS_FLIPS = 0xFF, 0x55                                                     # all 8 views; views 0, 2, 4, 6
+
+
+def view_ids(view_mask):
+    """the view ids of an 8-bit mask, ascending: the order of the slabs mmskin_dihedral_views writes"""
+    return [v for v in range(8) if (int(view_mask) >> v) & 1]
+
+
+def dihedral_views(src, view_mask, out=None):
+    """[V, B, C, H, W], one slab per set bit of `view_mask` in ascending view id (mmskin_dihedral_views): view v is
+    torch.rot90(src, v & 3, (2, 3)), flipped along W when v & 4.  src: a contiguous [B, C, H, W] device tensor of 1-, 2- or 4-byte
+    elements (copied bit for bit).  The library refuses an empty mask and a quarter-turn view of a non-square plane."""
+    _need_gpu(src, "dihedral_views")
+    if src.dim() != 4 or not src.is_contiguous() or src.element_size() not in (1, 2, 4):
+        raise ValueError(f"dihedral_views: src must be a contiguous [B, C, H, W] tensor of 1-, 2- or 4-byte elements, got {src.dtype} "
+                         f"{tuple(src.shape)}")
+    view_mask = int(view_mask)
+    V = len(view_ids(view_mask & 0xFF))
+    B, C, H, W = src.shape
+    if out is None:
+        out = torch.empty((V, B, C, H, W), dtype=src.dtype, device=src.device)
+    _dev_tensor(out, src.dtype, (V, B, C, H, W), "dihedral_views: out")
+    call("mmskin_dihedral_views", ptr(src), ptr(out), B, C, H, W, src.element_size(), view_mask, stream())
+    return out
+
+
+def uncertainty_check_limits(what, T=None, C=None, N=None):
+    """MMSkinError naming the limit that a pass, class or row count breaks (the C entry points check the same)"""
+    if T is not None and not 1 <= T <= UNCERTAINTY_MAX_PASSES:
+        raise _lib.MMSkinError(f"{what}: T = {T} passes; one call holds 1 .. UNCERTAINTY_MAX_PASSES = {UNCERTAINTY_MAX_PASSES}")
+    if C is not None and not 2 <= C <= UNCERTAINTY_MAX_CLASSES:
+        raise _lib.MMSkinError(f"{what}: C = {C} classes; the kernel holds one class per lane, 2 .. UNCERTAINTY_MAX_CLASSES = "
+                               f"{UNCERTAINTY_MAX_CLASSES}")
+    if N is not None and not 1 <= N <= UNCERTAINTY_MAX_ROWS:
+        raise _lib.MMSkinError(f"{what}: N = {N} rows is outside 1 .. UNCERTAINTY_MAX_ROWS = 2^24")
+
+
+def uncertainty_reduce(logits):
+    """(mean_prob fp64 [N, C], prob_std fp64 [N, C], votes int32 [N, C], pred int32 [N], stats fp64 [N, 7]) on the device from the
+    logits fp32 [T, N, C] of T passes (mmskin_uncertainty_reduce); the columns of stats are UNCERTAINTY_STATS.  The classes of a row
+    must be contiguous; the pass and row strides are taken from the tensor, so a slice of a larger block is read in place."""
+    _need_gpu(logits, "uncertainty_reduce")
+    if logits.dim() != 3 or logits.dtype != torch.float32:
+        raise ValueError(f"uncertainty_reduce: logits must be an fp32 [T, N, C] tensor, got {logits.dtype} {tuple(logits.shape)}")
+    T, N, C = logits.shape
+    uncertainty_check_limits("uncertainty_reduce", T=T, C=C, N=N)
+    if logits.stride(2) != 1 and C > 1:
+        raise ValueError(f"uncertainty_reduce: the classes of a row must be contiguous, got strides {logits.stride()}")
+    dev = logits.device
+    mean_prob, prob_std = (torch.empty((N, C), dtype=torch.float64, device=dev) for _ in range(2))
+    votes = torch.empty((N, C), dtype=torch.int32, device=dev)
+    pred = torch.empty(N, dtype=torch.int32, device=dev)
+    stats = torch.empty((N, 7), dtype=torch.float64, device=dev)
+    call("mmskin_uncertainty_reduce", ptr(logits), logits.stride(0) if T > 1 else N * logits.stride(1), logits.stride(1) if N > 1 else C, T, N,
+         C, ptr(mean_prob), ptr(prob_std), ptr(votes), ptr(pred), ptr(stats), stream())
+    return mean_prob, prob_std, votes, pred, stats
+
+
+def risk_coverage_check_limits(what, N):
+    if not 1 <= N <= RISK_COVERAGE_MAX_ROWS:
+        raise _lib.MMSkinError(f"{what}: N = {N} rows; the ranking is held in LDS, which holds 1 .. BOOTSTRAP_MAX_ROWS = {RISK_COVERAGE_MAX_ROWS}")
+
+
+def risk_coverage(score, wrong):
+    """counts int32 [N, 4] = (n_lt, n_eq, e_lt, e_eq) per row (mmskin_risk_coverage): the rows with a smaller and with an equal
+    score (itself included) and the wrong rows among each.  score fp64 [N] (larger = less sure, no NaN), wrong uint8 [N]."""
+    _need_gpu(score, "risk_coverage")
+    N = score.shape[0] if score.dim() == 1 else 0
+    risk_coverage_check_limits("risk_coverage", N)
+    _dev_tensor(score, torch.float64, (N,), "risk_coverage: score")
+    _dev_tensor(wrong, torch.uint8, (N,), "risk_coverage: wrong")
+    counts = torch.empty((N, 4), dtype=torch.int32, device=score.device)
+    call("mmskin_risk_coverage", ptr(score), ptr(wrong), N, ptr(counts), stream())
+    return counts
+
+
+def risk_coverage_summary(counts, wrong):
+    """fp64 [8] on the device, the values RISK_COVERAGE_SUMMARY, from the counts of risk_coverage (mmskin_risk_coverage_summary)"""
+    _need_gpu(counts, "risk_coverage_summary")
+    N = counts.shape[0] if counts.dim() == 2 else 0
+    risk_coverage_check_limits("risk_coverage_summary", N)
+    _dev_tensor(counts, torch.int32, (N, 4), "risk_coverage_summary: counts")
+    _dev_tensor(wrong, torch.uint8, (N,), "risk_coverage_summary: wrong")
+    out = torch.empty(8, dtype=torch.float64, device=counts.device)
+    call("mmskin_risk_coverage_summary", ptr(counts), ptr(wrong), N, ptr(out), stream())
+    return out
