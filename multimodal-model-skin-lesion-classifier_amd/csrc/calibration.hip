@@ -44,16 +44,6 @@ static_assert((MAX_K + 1) * (int64_t)MAX_N < (1ll << 31), "a code index fits 31 
 
 template <typename T> __host__ __device__ __forceinline__ T lesser(T a, T b) { return b < a ? b : a; }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {         // a butterfly: every lane ends with the same, order-fixed sum
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint64_t u = (uint64_t)__double_as_longlong(v);
-    const uint32_t lo = __shfl_xor((uint32_t)u, o, 64), hi = __shfl_xor((uint32_t)(u >> 32), o, 64);
-    v += __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-  }
-  return v;
-}
-
 // ------------------------------------------------------------------------------------------------ codes
 __global__ __launch_bounds__(NT) void calibration_codes_kernel(const float* __restrict__ probs, const int64_t* __restrict__ labels, int N,
                                                                int K, const float* __restrict__ edges, int n_bins,

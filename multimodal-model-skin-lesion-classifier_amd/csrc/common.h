@@ -194,6 +194,44 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// the same in fp64: a double travels as its two 32-bit halves
+__device__ __forceinline__ double shfl_xor_f64(double v, int o) {
+  const uint64_t u = (uint64_t)__double_as_longlong(v);
+  const uint32_t lo = __shfl_xor((uint32_t)u, o, 64), hi = __shfl_xor((uint32_t)(u >> 32), o, 64);
+  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+__device__ __forceinline__ double shfl_f64(double v, int src) {
+  const uint64_t u = (uint64_t)__double_as_longlong(v);
+  const uint32_t lo = __shfl((uint32_t)u, src, 64), hi = __shfl((uint32_t)(u >> 32), src, 64);
+  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {         // a butterfly: every lane ends with the same, order-fixed sum
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += shfl_xor_f64(v, o);
+  return v;
+}
+__device__ __forceinline__ double wave_max_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, shfl_xor_f64(v, o));
+  return v;
+}
+// (value, index) of the maximum over the wave, the FIRST index among equal values; every lane returns with the result
+__device__ __forceinline__ void wave_argmax(float& val, int& idx) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(val, o, 64);
+    const int oi = __shfl_xor(idx, o, 64);
+    if (ov > val || (ov == val && oi < idx)) { val = ov; idx = oi; }
+  }
+}
+__device__ __forceinline__ void wave_argmax(double& val, int& idx) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ov = shfl_xor_f64(val, o);
+    const int oi = __shfl_xor(idx, o, 64);
+    if (ov > val || (ov == val && oi < idx)) { val = ov; idx = oi; }
+  }
+}
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }

@@ -65,15 +65,6 @@ __device__ __forceinline__ void publish(int32_t* p, int32_t v) { __hip_atomic_st
 __device__ __forceinline__ float fetch(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ int32_t fetch(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-__device__ __forceinline__ void wave_argmax_first(float& val, int& idx) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(val, o, 64);
-    const int oi = __shfl_xor(idx, o, 64);
-    if (ov > val || (ov == val && oi < idx)) { val = ov; idx = oi; }
-  }
-}
-
 template <typename T, int KPL>
 __device__ __forceinline__ void load_row(const T* __restrict__ row, int C, int lane, float (&z)[KPL]) {
 #pragma unroll
@@ -118,7 +109,7 @@ __global__ __launch_bounds__(NT) void criterion_forward_kernel(const T* __restri
 #pragma unroll
     for (int k = 1; k < KPL; ++k)
       if (z[k] > top) { top = z[k]; arg = lane + 64 * k; }        // ascending classes: the first maximum stays
-    wave_argmax_first(top, arg);
+    wave_argmax(top, arg);
     const float m = top;
     float e = 0.f;                                                 // every class but the arg-max, whose term is exactly 1:
 #pragma unroll

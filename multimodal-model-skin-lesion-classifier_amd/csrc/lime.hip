@@ -46,9 +46,6 @@ constexpr int SLAB = 256;                // rows of a sample per block of partia
 constexpr int TI = 32, TJ = 64, RS = 32; // reduce: tile rows (z, 1), tile columns (z, 1, y), rows staged at a time
 constexpr double ALPHA_SELECT = 0.01, ALPHA_FIT = 1.0;
 
-__device__ __forceinline__ float load_logit(const float* p, int64_t i) { return p[i]; }
-__device__ __forceinline__ float load_logit(const bf16_t* p, int64_t i) { return bf16_bits_to_f32(p[i]); }
-
 __host__ __device__ inline int64_t block_doubles(int F, int C) { return (int64_t)(F + 1) * (F + 1 + C) + C; }
 inline int slabs_of(int N) { return (N + SLAB - 1) / SLAB; }
 
@@ -125,15 +122,15 @@ __global__ __launch_bounds__(NT) void lime_reduce_kernel(const float* __restrict
           // exp(x - max) rounded to fp32 from the fp64 exp (so the value does not depend on an fp32 exp's last bit), summed in
           // c = 0 .. C-1 order and divided, all in fp32
           float top = -INFINITY, sum = 0.f;
-          for (int c = 0; c < C; ++c) top = fmaxf(top, load_logit(logits, base + c));
+          for (int c = 0; c < C; ++c) top = fmaxf(top, to_f32(logits[base + c]));
           for (int c = 0; c < C; ++c) {
-            const float e = (float)exp((double)(load_logit(logits, base + c) - top));
+            const float e = (float)exp((double)(to_f32(logits[base + c]) - top));
             yv[tid][c] = e;
             sum += e;
           }
           for (int c = 0; c < C; ++c) yv[tid][c] = yv[tid][c] / sum;
         } else {
-          for (int c = 0; c < C; ++c) yv[tid][c] = load_logit(logits, base + c);
+          for (int c = 0; c < C; ++c) yv[tid][c] = to_f32(logits[base + c]);
         }
       }
     }

@@ -9,6 +9,7 @@
 // is "parity unpinned" against cv2 itself; oracle/preprocess.py restates the same algorithm in numpy.
 #include "../../include/mmskin.h"
 #include "common.h"
+#include "meta_encode.h"
 
 namespace {
 
@@ -60,15 +61,11 @@ __global__ __launch_bounds__(256) void metadata_encode_kernel(const int32_t* __r
   const int onehot_width = width - n_num;
   float v;
   if (j < onehot_width) {
-    int col = 0;   // the column this one-hot slot belongs to (n_cat is a handful: linear scan)
-    while (col + 1 < n_cat && col_offset[col + 1] <= j) ++col;
-    const int code = codes[(int64_t)b * n_cat + col];          // < 0: category unseen at fit time -> all zeros (handle_unknown='ignore')
-    v = (code == j - col_offset[col]) ? 1.f : 0.f;
+    const int col = meta_slot_column(j, n_cat, col_offset);
+    v = meta_onehot_cell(codes[(int64_t)b * n_cat + col], j, col_offset[col]);   // handle_unknown='ignore'
   } else {
     const int k = j - onehot_width;
-    float x = numeric[(int64_t)b * n_num + k];
-    if (x != x) x = nan_fill;                                   // pd.to_numeric(errors="coerce").fillna(-1)
-    v = (x - mean[k]) / scale[k];
+    v = meta_numeric_cell(numeric[(int64_t)b * n_num + k], mean[k], scale[k], nan_fill);
   }
   out[i] = v;
 }

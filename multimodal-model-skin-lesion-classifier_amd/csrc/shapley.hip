@@ -17,9 +17,9 @@
 // so every coalition starts on a multiple of G and a row range cut at multiples of G never splits one.
 //
 //   coalitions  raw codes / numerics of x and of the background + the inverse permutation table -> the encoded metadata rows of
-//               a row range.  One thread per output element, every element written exactly once, no atomics; the arithmetic is
-//               that of metadata_encode_kernel (preprocess.hip) / metadata_variants_kernel (sweep.hip), so a row equals the
-//               encoding of the mixed raw row bit for bit.
+//               a row range.  One thread per output element, every element written exactly once, no atomics; the cell is
+//               meta_encode.h's, the one metadata_encode_kernel (preprocess.hip) and metadata_variants_kernel (sweep.hip) call,
+//               so a row equals the encoding of the mixed raw row bit for bit.
 //   value       logits of a row range -> v: soft-max (or nothing), then the mean over the G rows of each coalition in fp64.  One
 //               wave serves one coalition; it holds 64 / cpad rows at a time (cpad = C rounded up to a power of two, one lane
 //               per class), each row group sums its rows g, g + 64 / cpad, ... in that order, and the groups are then added in a
@@ -30,6 +30,7 @@
 // tests/shapley_oracle.py restates all of it in numpy.
 #include "../../include/mmskin.h"
 #include "common.h"
+#include "meta_encode.h"
 
 #include <vector>
 
@@ -54,12 +55,7 @@ __global__ __launch_bounds__(NT) void shapley_coalitions_kernel(const int32_t* _
   const int64_t r = row0 + i / out_width;
   float v = 0.f;                                                 // columns past the encoder's width
   if (j < onehot_width + n_num) {
-    int col = 0;   // the column this slot belongs to (n_cat is a handful: linear scan)
-    if (j < onehot_width) {
-      while (col + 1 < n_cat && col_offset[col + 1] <= j) ++col;
-    } else {
-      col = n_cat + (j - onehot_width);
-    }
+    const int col = j < onehot_width ? meta_slot_column(j, n_cat, col_offset) : n_cat + (j - onehot_width);
     // does the explained row supply this column (col in the coalition), or background row g?
     int b, g = 0;
     bool own = true;
@@ -81,22 +77,18 @@ __global__ __launch_bounds__(NT) void shapley_coalitions_kernel(const int32_t* _
       }
     }
     if (j < onehot_width) {
-      const int code = own ? codes[(int64_t)b * n_cat + col] : bg_codes[(int64_t)g * n_cat + col];   // < 0: unseen at fit time -> zeros
-      v = (code == j - col_offset[col]) ? 1.f : 0.f;
+      const int code = own ? codes[(int64_t)b * n_cat + col] : bg_codes[(int64_t)g * n_cat + col];
+      v = meta_onehot_cell(code, j, col_offset[col]);
     } else {
       const int k = j - onehot_width;
-      float x = own ? numeric[(int64_t)b * n_num + k] : bg_numeric[(int64_t)g * n_num + k];
-      if (x != x) x = nan_fill;                                   // pd.to_numeric(errors="coerce").fillna(-1)
-      v = (x - mean[k]) / scale[k];
+      const float x = own ? numeric[(int64_t)b * n_num + k] : bg_numeric[(int64_t)g * n_num + k];
+      v = meta_numeric_cell(x, mean[k], scale[k], nan_fill);
     }
   }
   out[i] = v;
 }
 
 // ------------------------------------------------------------------------------------------------ value
-__device__ __forceinline__ float load_logit(const float* p, int64_t i) { return p[i]; }
-__device__ __forceinline__ float load_logit(const bf16_t* p, int64_t i) { return bf16_bits_to_f32(p[i]); }
-
 // reductions over the aligned groups of `width` lanes (a power of two): every lane of a group ends with its group's result
 __device__ __forceinline__ float group_max(float v, int width) {
   for (int o = width >> 1; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -125,7 +117,7 @@ __global__ __launch_bounds__(NT) void shapley_value_kernel(const T* __restrict__
   for (int g0 = 0; g0 < rows; g0 += groups) {
     const int g = g0 + group;
     const bool on = live && g < rows;
-    const float x = on ? load_logit(src, (int64_t)g * C + c) : -INFINITY;
+    const float x = on ? to_f32(src[(int64_t)g * C + c]) : -INFINITY;
     float val = x;
     if (output == MMSKIN_SHAPLEY_PROB) {                          // exp(x - max) / sum, as torch.softmax and sweep_reduce
       const float top = group_max(x, cpad);
@@ -217,8 +209,7 @@ extern "C" int mmskin_shapley_coalitions(const int32_t* codes, const float* nume
                                          const int32_t* col_offset_host, int onehot_width, int n_num, const float* mean, const float* scale,
                                          float nan_fill, const int32_t* perm_host, int32_t* pos_scratch, int P, int64_t row0, int64_t row1,
                                          float* out, int out_width, void* stream) {
-  ARG_CHECK(n_cat >= 0 && n_num >= 0 && n_cat + n_num >= 1 && onehot_width >= n_cat, "shapley_coalitions: bad shape (%d categorical, %d numeric, "
-            "one-hot width %d)", n_cat, n_num, onehot_width);
+  if (int rc = check_meta_layout("shapley_coalitions", n_cat, n_num, onehot_width, col_offset, col_offset_host)) return rc;
   const int M = n_cat + n_num;
   int64_t coalition_rows = 0, rows = 0;
   if (int rc = walk_extents("shapley_coalitions", batch, G, P, M, &coalition_rows, &rows)) return rc;
@@ -227,13 +218,8 @@ extern "C" int mmskin_shapley_coalitions(const int32_t* codes, const float* nume
             (long long)row0, (long long)row1, (long long)rows);
   ARG_CHECK((row1 - row0) * out_width < ((int64_t)1 << 38), "shapley_coalitions: %lld rows x %d are out of range", (long long)(row1 - row0),
             out_width);
-  ARG_CHECK(out && perm_host && pos_scratch && col_offset && col_offset_host && ((codes && bg_codes) || n_cat == 0) &&
-                (n_num == 0 || (numeric && bg_numeric && mean && scale)),
+  ARG_CHECK(out && perm_host && pos_scratch && ((codes && bg_codes) || n_cat == 0) && (n_num == 0 || (numeric && bg_numeric && mean && scale)),
             "shapley_coalitions: null argument");
-  ARG_CHECK(col_offset_host[0] == 0 && col_offset_host[n_cat] == onehot_width, "shapley_coalitions: col_offset must run from 0 to the one-hot "
-            "width %d", onehot_width);
-  for (int c = 0; c < n_cat; ++c)
-    ARG_CHECK(col_offset_host[c + 1] > col_offset_host[c], "shapley_coalitions: column %d has no category", c);
   if (int rc = upload_positions("shapley_coalitions", perm_host, P, M, pos_scratch, stream)) return rc;
   const int64_t total = (row1 - row0) * out_width;
   hipLaunchKernelGGL(shapley_coalitions_kernel, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, ST(stream), codes, numeric, bg_codes,

@@ -5,8 +5,8 @@
 //   variants   codes + raw numerics + a table of V one-column mutations (+ an optional missing mask) -> the V encoded metadata
 //              batches [V][B][out_width], i.e. mutate_metadata / simulate_missing_metadata, OneHotEncoder, fillna(-1),
 //              StandardScaler and the pad-or-cut to the checkpoint's vocab_size in one pass.  One thread per output element,
-//              every element written exactly once, no atomics.  The numeric arithmetic is the (x - mean) / scale of
-//              metadata_encode_kernel (preprocess.hip), so an unmutated, unmasked variant equals its output bit for bit.
+//              every element written exactly once, no atomics.  The cell is meta_encode.h's, the one metadata_encode_kernel
+//              (preprocess.hip) calls, so an unmutated, unmasked variant equals its output bit for bit.
 //   reduce     logits [V][B][C] + baseline logits [B][C] (+ labels) -> soft-max, prediction, top-2 margin, entropy / KL / JS /
 //              confidence change per (v, b), and the flip / transition / confusion COUNTS added to the caller's counters.
 //              One wave per (v, b) row, one lane per class (C <= 64); a workgroup serves one variant, counts into an LDS
@@ -17,6 +17,7 @@
 // integer outputs and in the margin.
 #include "../../include/mmskin.h"
 #include "common.h"
+#include "meta_encode.h"
 
 #pragma clang fp contract(off)
 
@@ -45,45 +46,30 @@ __global__ __launch_bounds__(NT) void metadata_variants_kernel(const int32_t* __
   const int n_col = n_cat + n_num;
   float r = 0.f;                                                 // columns past the encoder's width
   if (j < onehot_width) {
-    int col = 0;   // the column this one-hot slot belongs to (n_cat is a handful: linear scan)
-    while (col + 1 < n_cat && col_offset[col + 1] <= j) ++col;
-    int code = codes[(int64_t)b * n_cat + col];                  // < 0: category unseen at fit time -> all zeros
+    const int col = meta_slot_column(j, n_cat, col_offset);
+    int code = codes[(int64_t)b * n_cat + col];
     const mmskin_meta_variant rec = table[v];
     if (rec.column == col) {
       if (rec.op == MMSKIN_META_CAT_SET) code = rec.a;
       else if (rec.op == MMSKIN_META_CAT_TOGGLE) code = code == rec.a ? rec.b : rec.a;
     }
     if (mask && mask[vb * n_col + col]) code = missing_code[col];
-    r = (code == j - col_offset[col]) ? 1.f : 0.f;
+    r = meta_onehot_cell(code, j, col_offset[col]);
   } else if (j < onehot_width + n_num) {
     const int k = j - onehot_width;
     float x = numeric[(int64_t)b * n_num + k];
     const mmskin_meta_variant rec = table[v];
     if (rec.column == n_cat + k) {
-      if (rec.op == MMSKIN_META_NUM_ADD) x = x + rec.value;      // NaN stays NaN and is filled below
+      if (rec.op == MMSKIN_META_NUM_ADD) x = x + rec.value;      // NaN stays NaN and is filled by the cell
       else if (rec.op == MMSKIN_META_NUM_SET) x = rec.value;
     }
     if (mask && mask[vb * n_col + n_cat + k]) x = nan_fill;
-    if (x != x) x = nan_fill;                                     // pd.to_numeric(errors="coerce").fillna(-1)
-    r = (x - mean[k]) / scale[k];
+    r = meta_numeric_cell(x, mean[k], scale[k], nan_fill);
   }
   out[i] = r;
 }
 
 // ------------------------------------------------------------------------------------------------ reduce
-__device__ __forceinline__ float load_logit(const float* p, int64_t i) { return p[i]; }
-__device__ __forceinline__ float load_logit(const bf16_t* p, int64_t i) { return bf16_bits_to_f32(p[i]); }
-
-// (value, index) of the maximum over the wave, the FIRST index among equal values; every lane returns with the result
-__device__ __forceinline__ void wave_argmax(float& val, int& idx) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(val, o, 64);
-    const int oi = __shfl_xor(idx, o, 64);
-    if (ov > val || (ov == val && oi < idx)) { val = ov; idx = oi; }
-  }
-}
-
 // what one row of logits gives: lane c holds class c (lanes >= C hold nothing)
 struct Row {
   float p;        // soft-max probability: exp(x - max) / sum, as torch.softmax
@@ -126,7 +112,7 @@ __global__ __launch_bounds__(NT) void sweep_reduce_kernel(const T* __restrict__ 
   const bool live = lane < C;
   for (int b = b0 + wave; b < b1; b += NT / 64) {          // uniform per wave: the shuffles below see all 64 lanes
     const int64_t row = (int64_t)v * B + b;
-    const Row cur = row_stats(live ? load_logit(logits, row * C + lane) : 0.f, lane, C);
+    const Row cur = row_stats(live ? to_f32(logits[row * C + lane]) : 0.f, lane, C);
     const Row ref = row_stats(live ? base[(int64_t)b * C + lane] : 0.f, lane, C);
     // entropy, KL(variant || base), JS(variant, base) on the safe probabilities (analyze_prediction_uncertainty.py:172-189)
     const float m = 0.5f * (cur.q + ref.q);
@@ -173,17 +159,12 @@ extern "C" int mmskin_metadata_variants(const int32_t* codes, int n_cat, const i
                                         void* stream) {
   ARG_CHECK(V >= 1 && batch >= 1 && out_width >= 1, "metadata_variants: every extent must be >= 1 (V %d, batch %d, out_width %d)", V, batch,
             out_width);
-  ARG_CHECK(n_cat >= 0 && n_num >= 0 && n_cat + n_num >= 1 && onehot_width >= n_cat, "metadata_variants: bad shape (%d categorical, %d numeric, "
-            "one-hot width %d)", n_cat, n_num, onehot_width);
+  if (int rc = check_meta_layout("metadata_variants", n_cat, n_num, onehot_width, col_offset, col_offset_host)) return rc;
   ARG_CHECK((int64_t)V * batch * out_width < ((int64_t)1 << 40) && V <= (1 << 20), "metadata_variants: %d x %d x %d is out of range", V, batch,
             out_width);
-  ARG_CHECK(out && variants_host && variants_scratch && col_offset && col_offset_host && (codes || n_cat == 0) &&
-                (n_num == 0 || (numeric && mean && scale)) && (!mask || missing_code || n_cat == 0),
+  ARG_CHECK(out && variants_host && variants_scratch && (codes || n_cat == 0) && (n_num == 0 || (numeric && mean && scale)) &&
+                (!mask || missing_code || n_cat == 0),
             "metadata_variants: null argument");
-  ARG_CHECK(col_offset_host[0] == 0 && col_offset_host[n_cat] == onehot_width, "metadata_variants: col_offset must run from 0 to the one-hot "
-            "width %d", onehot_width);
-  for (int c = 0; c < n_cat; ++c)
-    ARG_CHECK(col_offset_host[c + 1] > col_offset_host[c], "metadata_variants: column %d has no category", c);
   for (int v = 0; v < V; ++v) {
     const mmskin_meta_variant& r = variants_host[v];
     if (r.op == MMSKIN_META_NONE) continue;

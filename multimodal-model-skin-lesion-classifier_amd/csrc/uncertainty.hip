@@ -36,38 +36,6 @@ static_assert(MAX_N <= 0x4000, "the summary keeps row + 1 in 15 bits beside a st
 
 typedef unsigned long long u64;
 
-__device__ __forceinline__ double shfl_xor_f64(double v, int o) {
-  const u64 u = (u64)__double_as_longlong(v);
-  const uint32_t lo = __shfl_xor((uint32_t)u, o, 64), hi = __shfl_xor((uint32_t)(u >> 32), o, 64);
-  return __longlong_as_double((long long)(((u64)hi << 32) | lo));
-}
-__device__ __forceinline__ double shfl_f64(double v, int src) {
-  const u64 u = (u64)__double_as_longlong(v);
-  const uint32_t lo = __shfl((uint32_t)u, src, 64), hi = __shfl((uint32_t)(u >> 32), src, 64);
-  return __longlong_as_double((long long)(((u64)hi << 32) | lo));
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {         // a butterfly: every lane ends with the same, order-fixed sum
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += shfl_xor_f64(v, o);
-  return v;
-}
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, shfl_xor_f64(v, o));
-  return v;
-}
-// (value, index) of the maximum over the wave, the FIRST index among equal values (wave_argmax of sweep.hip)
-template <typename V> __device__ __forceinline__ V shfl_xor_any(V v, int o);
-template <> __device__ __forceinline__ float shfl_xor_any<float>(float v, int o) { return __shfl_xor(v, o, 64); }
-template <> __device__ __forceinline__ double shfl_xor_any<double>(double v, int o) { return shfl_xor_f64(v, o); }
-template <typename V> __device__ __forceinline__ void wave_argmax(V& val, int& idx) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const V ov = shfl_xor_any<V>(val, o);
-    const int oi = __shfl_xor(idx, o, 64);
-    if (ov > val || (ov == val && oi < idx)) { val = ov; idx = oi; }
-  }
-}
 __device__ __forceinline__ int wave_max_i32(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));

@@ -26,13 +26,13 @@ Eval mode, forward only.
 import numpy as np
 import torch
 
+from . import _metadata_head as mh
 from . import ops
-from ._lib import MMSkinError
 
 OUTPUTS = {"prob": ops.LIME_PROB, "logit": ops.LIME_LOGIT}
 
 
-class LimeResult:
+class LimeResult(mh.AbsSum):
     """What `MetadataLime.explain` returns.  Per row of THIS batch, fp64 device tensors: `coef` [B, C, K] and `features` (int32)
     [B, C, K] in descending |coef| -- the explanation --, `intercept`, `score` (the weighted R^2 of the local fit), `local_pred`
     [B, C], `dense` [B, C, F] (coef scattered over all features, zeros where none was kept).  Accumulated since the last reset:
@@ -42,10 +42,6 @@ class LimeResult:
         self.features, self.coef, self.intercept, self.score, self.local_pred = features, coef, intercept, score, local_pred
         self.dense, self.abs_sum, self.n_samples = dense, abs_sum, n_samples
 
-    @property
-    def mean_abs(self):
-        return self.abs_sum / max(self.n_samples, 1)
-
     def as_list(self, b, c, feature_names=None):
         """lime's Explanation.as_list() of sample b for class c: [(name, importance)] in descending |importance|."""
         idx, val = self.features[b, c].tolist(), self.coef[b, c].tolist()
@@ -54,7 +50,7 @@ class LimeResult:
         return [(feature_names[j] if feature_names is not None else str(j), v) for j, v in zip(idx, val)]
 
 
-class MetadataLime:
+class MetadataLime(mh.AbsSum):
     # Rows per fusion-head call: the head is launch-bound on small blocks, and the [rows, F] image-feature
     # tile of a call is 64 MiB at F = 2048
     default_rows_per_head_call = 8192
@@ -92,10 +88,7 @@ class MetadataLime:
         if output not in OUTPUTS:
             raise ValueError(f"MetadataLime: output must be 'prob' or 'logit', got {output!r}")
         self.output, self.seed, self.sample_around_instance = output, int(seed), bool(sample_around_instance)
-        rows_per = int(rows_per_head_call) if rows_per_head_call is not None else self.default_rows_per_head_call
-        if rows_per < 1:
-            raise ValueError(f"MetadataLime: rows_per_head_call must be >= 1, got {rows_per_head_call}")
-        self.rows_per_head_call = rows_per
+        self.rows_per_head_call = mh.rows_per_call("MetadataLime", "rows_per_head_call", rows_per_head_call, self.default_rows_per_head_call)
         self.reset()
 
     @staticmethod
@@ -106,30 +99,12 @@ class MetadataLime:
         scale[scale == 0.0] = 1.0
         return mean, scale
 
-    def reset(self):
-        """Forget the accumulated |coef| (a new data set) and restart the generator's sample counter."""
-        self.abs_sum = None
-        self.n_samples = 0
-
-    def global_importance(self):
-        """(importance [F] = mean_abs averaged over the classes, the features in descending order of it)."""
-        if self.abs_sum is None:
-            raise ValueError("global_importance: nothing has been explained since the last reset()")
-        importance = (self.abs_sum / max(self.n_samples, 1)).mean(-1)
-        return importance, torch.argsort(importance, descending=True, stable=True)
-
     # ---- per batch
     def explain(self, images, encoded_rows):
         """One batch: images [B, ...] as the model takes them, encoded_rows fp32 [B, F] (MetadataEncoder.transform).  Adds the batch's
         |coef| to the running sums and returns a LimeResult."""
         model = self.model
-        if model.training:
-            raise MMSkinError("MetadataLime runs in eval mode: call model.eval() first")
-        if getattr(model, "text_model_name", None) != "one-hot-encoder":
-            raise ValueError(f"MetadataLime is defined on encoded one-hot rows: text_model_name is {getattr(model, 'text_model_name', None)!r}, "
-                             "not 'one-hot-encoder'")
-        if model.attention_mecanism in ("no-metadata", "no-metadata-without-mlp"):
-            raise ValueError(f"MetadataLime: the fusion {model.attention_mecanism!r} does not read the metadata, there is nothing to explain")
+        mh.check_metadata_model("MetadataLime", model, "explain")
         F, N, K = self.n_features, self.num_samples, self.num_features
         if F != model.vocab_size:
             raise ValueError(f"MetadataLime: the training rows have {F} columns, the model's vocab_size is {model.vocab_size}")
@@ -155,10 +130,8 @@ class MetadataLime:
                                                         around_instance=self.sample_around_instance)
                 # the image-feature tile of THIS call only: row -> its sample
                 sample = torch.div(torch.arange(r0, r1, device=dev), N, rounding_mode="floor")
-                logits = model.fuse(img_feat.index_select(0, sample), metas)
-                if logits.dtype not in (torch.float32, torch.bfloat16):
-                    logits = logits.float()
-                ops.lime_reduce(metas, weights, logits.contiguous(), mean, scale, acc, B, N, r0, output=OUTPUTS[self.output])
+                logits = mh.head_logits(model, img_feat.index_select(0, sample), metas)
+                ops.lime_reduce(metas, weights, logits, mean, scale, acc, B, N, r0, output=OUTPUTS[self.output])
             coef, feature, intercept, score, local_pred, dense = ops.lime_solve(acc, x, mean, scale, N, C, K, abs_sum=self.abs_sum)
         self.n_samples += B
         return LimeResult(feature, coef, intercept, score, local_pred, dense, self.abs_sum, self.n_samples)

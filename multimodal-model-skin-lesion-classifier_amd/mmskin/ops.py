@@ -1361,6 +1361,29 @@ def _dev_tensor(t, dtype, shape, what):
     return t
 
 
+def _encoder_args(what, codes, numeric, col_offset, mean, scale):
+    """The encoder's side of a call that encodes rows: codes int32 [B, n_cat] / numeric fp32 [B, n_num] and mean / scale fp32 [n_num]
+    on the device, col_offset a HOST int32 array [n_cat + 1] -> (B, n_cat, n_num, the offsets on the host, the offsets on the device)"""
+    (B, n_cat), n_num = codes.shape, numeric.shape[1]
+    _dev_tensor(codes, torch.int32, (B, n_cat), f"{what}: codes")
+    _dev_tensor(numeric, torch.float32, (B, n_num), f"{what}: numeric")
+    off_host = np.ascontiguousarray(col_offset, dtype=np.int32)
+    if off_host.shape != (n_cat + 1,):
+        raise ValueError(f"{what}: col_offset must have {n_cat + 1} entries, got {off_host.shape}")
+    if n_num:
+        _dev_tensor(mean, torch.float32, (n_num,), f"{what}: mean")
+        _dev_tensor(scale, torch.float32, (n_num,), f"{what}: scale")
+    return B, n_cat, n_num, off_host, torch.from_numpy(off_host).to(codes.device)
+
+
+def _logits_arg(what, logits, ndim):
+    """The head's logits as the reduce kernels read them: contiguous fp32 or bf16, [V, B, C] or [rows, C]"""
+    if logits.dim() != ndim or logits.dtype not in (torch.float32, torch.bfloat16) or not logits.is_contiguous():
+        raise ValueError(f"{what}: logits must be a contiguous fp32 or bf16 {'[V, B, C]' if ndim == 3 else '[rows, C]'} tensor, got "
+                         f"{logits.dtype} {tuple(logits.shape)}")
+    return logits.shape
+
+
 def metadata_variants(codes, numeric, col_offset, mean, scale, nan_fill, table, out_width, mask=None, missing_code=None, out=None):
     """The V mutated, encoded metadata batches [V, B, out_width] of one batch, in one kernel (mmskin_metadata_variants).
     codes int32 [B, n_cat] and numeric fp32 [B, n_num] on the device; col_offset a HOST int32 array [n_cat + 1]; mean / scale fp32
@@ -1370,16 +1393,8 @@ def metadata_variants(codes, numeric, col_offset, mean, scale, nan_fill, table, 
     table = np.ascontiguousarray(table)
     if table.dtype != META_VARIANT_DTYPE or table.ndim != 1:
         raise ValueError("metadata_variants: table must be a 1-D array of META_VARIANT_DTYPE records")
-    V, (B, n_cat), n_num = len(table), codes.shape, numeric.shape[1]
-    dev = codes.device
-    _dev_tensor(codes, torch.int32, (B, n_cat), "metadata_variants: codes")
-    _dev_tensor(numeric, torch.float32, (B, n_num), "metadata_variants: numeric")
-    off_host = np.ascontiguousarray(col_offset, dtype=np.int32)
-    if off_host.shape != (n_cat + 1,):
-        raise ValueError(f"metadata_variants: col_offset must have {n_cat + 1} entries, got {off_host.shape}")
-    if n_num:
-        _dev_tensor(mean, torch.float32, (n_num,), "metadata_variants: mean")
-        _dev_tensor(scale, torch.float32, (n_num,), "metadata_variants: scale")
+    V, dev = len(table), codes.device
+    B, n_cat, n_num, off_host, off_dev = _encoder_args("metadata_variants", codes, numeric, col_offset, mean, scale)
     if mask is not None:
         _dev_tensor(mask, torch.uint8, (V, B, n_cat + n_num), "metadata_variants: mask")
         if n_cat:
@@ -1389,7 +1404,6 @@ def metadata_variants(codes, numeric, col_offset, mean, scale, nan_fill, table, 
         out = torch.empty((V, B, max(out_width, 0)), device=dev, dtype=torch.float32)
     else:
         _dev_tensor(out, torch.float32, (V, B, out_width), "metadata_variants: out")
-    off_dev = torch.from_numpy(off_host).to(dev)
     scratch = torch.empty(max(table.nbytes, 1), dtype=torch.uint8, device=dev)      # the library uploads the table into it
     call("mmskin_metadata_variants", ptr(codes), n_cat, ptr(off_dev), ctypes.c_void_p(off_host.ctypes.data), int(off_host[-1]),
          ptr(numeric), n_num, ptr(mean) if n_num else None, ptr(scale) if n_num else None, float(nan_fill),
@@ -1403,9 +1417,7 @@ def sweep_reduce(logits, base, flips, transitions, confusion=None, labels=None, 
     (v, b); the flip / transition (/ confusion, with labels int32 [B]) counts are ADDED to the int32 device counters flips [V],
     transitions [V, C, C], confusion [V, C, C] (mmskin_sweep_reduce)."""
     _need_gpu(logits, "sweep_reduce")
-    if logits.dim() != 3 or logits.dtype not in (torch.float32, torch.bfloat16) or not logits.is_contiguous():
-        raise ValueError(f"sweep_reduce: logits must be a contiguous fp32 or bf16 [V, B, C] tensor, got {logits.dtype} {tuple(logits.shape)}")
-    V, B, C = logits.shape
+    V, B, C = _logits_arg("sweep_reduce", logits, 3)
     dev = logits.device
     _dev_tensor(base, torch.float32, (B, C), "sweep_reduce: base")
     _dev_tensor(flips, torch.int32, (V,), "sweep_reduce: flips")
@@ -1448,26 +1460,17 @@ def shapley_coalitions(codes, numeric, bg_codes, bg_numeric, col_offset, mean, s
     bg_numeric [G, n_num] of the background on the device; col_offset a HOST int32 array [n_cat + 1]; mean / scale fp32 [n_num] on
     the device; perms a HOST int32 [P, M] table of permutations (validated by the library)."""
     _need_gpu(codes, "shapley_coalitions")
-    (B, n_cat), n_num, G = codes.shape, numeric.shape[1], bg_codes.shape[0]
-    dev = codes.device
-    perms = _shapley_table(perms, n_cat + n_num, "shapley_coalitions")
-    _dev_tensor(codes, torch.int32, (B, n_cat), "shapley_coalitions: codes")
-    _dev_tensor(numeric, torch.float32, (B, n_num), "shapley_coalitions: numeric")
+    G, dev = bg_codes.shape[0], codes.device
+    perms = _shapley_table(perms, codes.shape[1] + numeric.shape[1], "shapley_coalitions")
+    B, n_cat, n_num, off_host, off_dev = _encoder_args("shapley_coalitions", codes, numeric, col_offset, mean, scale)
     _dev_tensor(bg_codes, torch.int32, (G, n_cat), "shapley_coalitions: bg_codes")
     _dev_tensor(bg_numeric, torch.float32, (G, n_num), "shapley_coalitions: bg_numeric")
-    off_host = np.ascontiguousarray(col_offset, dtype=np.int32)
-    if off_host.shape != (n_cat + 1,):
-        raise ValueError(f"shapley_coalitions: col_offset must have {n_cat + 1} entries, got {off_host.shape}")
-    if n_num:
-        _dev_tensor(mean, torch.float32, (n_num,), "shapley_coalitions: mean")
-        _dev_tensor(scale, torch.float32, (n_num,), "shapley_coalitions: scale")
     P, out_width, row0 = len(perms), int(out_width), int(row0)
     row1 = shapley_rows(B, G, P, n_cat + n_num) if row1 is None else int(row1)
     if out is None:
         out = torch.empty((max(row1 - row0, 0), max(out_width, 0)), device=dev, dtype=torch.float32)
     else:
         _dev_tensor(out, torch.float32, (row1 - row0, out_width), "shapley_coalitions: out")
-    off_dev = torch.from_numpy(off_host).to(dev)
     scratch = torch.empty(max(perms.size, 1), dtype=torch.int32, device=dev)          # the library uploads the inverse table into it
     call("mmskin_shapley_coalitions", ptr(codes), ptr(numeric), B, ptr(bg_codes), ptr(bg_numeric), G, n_cat, ptr(off_dev),
          ctypes.c_void_p(off_host.ctypes.data), int(off_host[-1]), n_num, ptr(mean) if n_num else None, ptr(scale) if n_num else None,
@@ -1481,12 +1484,11 @@ def shapley_reduce(logits, v, perms, G, row0, output=SHAPLEY_PROB, finish=False,
     returns (phi fp32 [B, M, C], base [B, C] = v(empty), full [B, C] = v(all)) and ADDS sum_b |phi| into abs_sum fp64 [M, C] when
     that is given; otherwise returns None."""
     _need_gpu(logits, "shapley_reduce")
-    if logits.dim() != 2 or logits.dtype not in (torch.float32, torch.bfloat16) or not logits.is_contiguous():
-        raise ValueError(f"shapley_reduce: logits must be a contiguous fp32 or bf16 [rows, C] tensor, got {logits.dtype} {tuple(logits.shape)}")
+    rows, C = _logits_arg("shapley_reduce", logits, 2)
     perms = np.ascontiguousarray(perms)
     if perms.dtype != np.int32 or perms.ndim != 2:
         raise ValueError(f"shapley_reduce: perms must be an int32 [P, M] table, got {perms.dtype} {perms.shape}")
-    (rows, C), (P, M), dev = logits.shape, perms.shape, logits.device
+    (P, M), dev = perms.shape, logits.device
     if v is None or v.dim() != 3:
         raise ValueError("shapley_reduce: v must be a float64 [B, K + 2, C] device tensor")
     B = v.shape[0]
@@ -1560,9 +1562,7 @@ def lime_reduce(rows, weights, logits, mean, scale, acc, batch, N, row0, output=
     """Adds rows [row0, row0 + n) of a batch's neighbourhood -- the rows fp32 [n, >= F], their weights [n] and the head's logits
     [n, C] (fp32 or bf16) -- into acc (lime_accumulator): every weighted sum the ridge fits need (mmskin_lime_reduce)."""
     _need_gpu(logits, "lime_reduce")
-    if logits.dim() != 2 or logits.dtype not in (torch.float32, torch.bfloat16) or not logits.is_contiguous():
-        raise ValueError(f"lime_reduce: logits must be a contiguous fp32 or bf16 [rows, C] tensor, got {logits.dtype} {tuple(logits.shape)}")
-    n, C = logits.shape
+    n, C = _logits_arg("lime_reduce", logits, 2)
     F = int(mean.shape[0]) if mean is not None and mean.dim() == 1 else -1
     _lime_stats(mean, scale, F, "lime_reduce")
     if rows is None or rows.dim() != 2:

@@ -25,8 +25,8 @@ Eval mode, forward only.
 import numpy as np
 import torch
 
+from . import _metadata_head as mh
 from . import ops
-from ._lib import MMSkinError
 
 METRICS = ops.PERMUTATION_METRICS
 
@@ -71,10 +71,7 @@ class MetadataPermutationImportance:
         self.n_repeats, self.seed = int(n_repeats), int(seed)
         if self.n_repeats < 1:
             raise ValueError(f"MetadataPermutationImportance: n_repeats must be >= 1, got {n_repeats}")
-        rows = int(rows_per_call) if rows_per_call is not None else self.default_rows_per_call
-        if rows < 1:
-            raise ValueError(f"MetadataPermutationImportance: rows_per_call must be >= 1, got {rows_per_call}")
-        self.rows_per_call = rows
+        self.rows_per_call = mh.rows_per_call("MetadataPermutationImportance", "rows_per_call", rows_per_call, self.default_rows_per_call)
         if image_batch_size is not None and int(image_batch_size) < 1:
             raise ValueError(f"MetadataPermutationImportance: image_batch_size must be >= 1, got {image_batch_size}")
         self.image_batch_size = None if image_batch_size is None else int(image_batch_size)
@@ -128,14 +125,7 @@ class MetadataPermutationImportance:
         """The fold: images [S, ...] as the model takes them, metadata fp32 [S, vocab_size] (the ENCODED rows,
         MetadataEncoder.transform), labels integer [S].  Returns a PermutationImportanceResult."""
         model = self.model
-        if model.training:
-            raise MMSkinError("MetadataPermutationImportance runs in eval mode: call model.eval() first")
-        if getattr(model, "text_model_name", None) != "one-hot-encoder":
-            raise ValueError(f"MetadataPermutationImportance is defined on encoded one-hot rows: text_model_name is "
-                             f"{getattr(model, 'text_model_name', None)!r}, not 'one-hot-encoder'")
-        if model.attention_mecanism in ("no-metadata", "no-metadata-without-mlp"):
-            raise ValueError(f"MetadataPermutationImportance: the fusion {model.attention_mecanism!r} does not read the metadata, there is "
-                             "nothing to explain")
+        mh.check_metadata_model("MetadataPermutationImportance", model, "explain")
         W, K = int(model.vocab_size), int(model.num_classes)
         x, y = torch.as_tensor(metadata), torch.as_tensor(labels)
         S = int(images.shape[0])
@@ -157,7 +147,7 @@ class MetadataPermutationImportance:
             perm = ops.permutation_indices(self.seed, R, G, S, dev)
             # the unshuffled fold is a study of one cell
             base_conf, base_counts = ops.permutation_accumulators(1, 1, K, dev)
-            ops.permutation_scores(self._head(img_feat, x), y, base_conf, base_counts, 0)
+            ops.permutation_scores(mh.head_logits(model, img_feat, x, fp32=True), y, base_conf, base_counts, 0)
             baseline = ops.permutation_finalize(base_conf, base_counts, torch.zeros(3, dtype=torch.float64, device=dev))[0][:, 0, 0].contiguous()
             confusion, counts = ops.permutation_accumulators(R, G, K, dev)
             sample = torch.arange(S, device=dev)
@@ -165,12 +155,8 @@ class MetadataPermutationImportance:
                 r1 = min(r0 + per_call, total)
                 metas = ops.permuted_rows(x, group, perm, row0=r0, row1=r1)
                 # the image-feature tile of THIS call only: both ends are multiples of S, so the samples simply repeat
-                logits = self._head(img_feat.index_select(0, sample.repeat((r1 - r0) // S)), metas)
+                logits = mh.head_logits(model, img_feat.index_select(0, sample.repeat((r1 - r0) // S)), metas, fp32=True)   # the scores take fp32 only
                 ops.permutation_scores(logits, y, confusion, counts, r0)
             metrics, importances, mean, std = ops.permutation_finalize(confusion, counts, baseline)
         host = [t.cpu().numpy() for t in (metrics, importances, mean, std, baseline)]
         return PermutationImportanceResult(*host, self.group_names)
-
-    def _head(self, img_feat, metas):
-        logits = self.model.fuse(img_feat, metas)
-        return logits.float().contiguous()

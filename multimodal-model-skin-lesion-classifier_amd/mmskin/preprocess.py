@@ -93,11 +93,14 @@ class MetadataEncoder:
             out[:, j] = [table.get(str(v), -1) for v in rows[:, j]]
         return torch.from_numpy(out)
 
+    def col_offsets(self):
+        """Host int32 [n_cat + 1]: the one-hot block of categorical column c is the slots [off[c], off[c + 1])."""
+        return np.concatenate([[0], np.cumsum([len(c) for c in self.categories_])]).astype(np.int32)
+
     def _tables(self, device):
         t = self._dev.get(str(device))
         if t is None:
-            off = np.concatenate([[0], np.cumsum([len(c) for c in self.categories_])]).astype(np.int32)
-            t = (torch.from_numpy(off).to(device), torch.tensor(self.mean_, dtype=torch.float32, device=device),
+            t = (torch.from_numpy(self.col_offsets()).to(device), torch.tensor(self.mean_, dtype=torch.float32, device=device),
                  torch.tensor(self.scale_, dtype=torch.float32, device=device))
             self._dev[str(device)] = t
         return t

@@ -38,13 +38,13 @@ Eval mode, forward only.
 import numpy as np
 import torch
 
+from . import _metadata_head as mh
 from . import ops
-from ._lib import MMSkinError
 
 OUTPUTS = {"prob": ops.SHAPLEY_PROB, "logit": ops.SHAPLEY_LOGIT}
 
 
-class ShapleyResult:
+class ShapleyResult(mh.AbsSum):
     """What `MetadataShapley.explain` returns.  Per row of THIS batch: `values` fp32 [B, M, C], `base` [B, C] = v(empty) (it
     depends on the image) and `full` [B, C] = v(all).  Accumulated since the last reset: `abs_sum` fp64 [M, C], `n_samples`, and
     `mean_abs` = abs_sum / n_samples (the script's features x classes heat map).  Everything but `n_samples` is a device tensor."""
@@ -52,12 +52,8 @@ class ShapleyResult:
     def __init__(self, values, base, full, abs_sum, n_samples):
         self.values, self.base, self.full, self.abs_sum, self.n_samples = values, base, full, abs_sum, n_samples
 
-    @property
-    def mean_abs(self):
-        return self.abs_sum / max(self.n_samples, 1)
 
-
-class MetadataShapley:
+class MetadataShapley(mh.AbsSum):
     # Rows per fusion-head call (rounded down to a multiple of G): the head is launch-bound on small blocks (DESIGN.md section
     # 13), and the [rows, F] image-feature tile of a call is 64 MiB at F = 2048
     default_rows_per_head_call = 8192
@@ -94,9 +90,7 @@ class MetadataShapley:
             raise ValueError(f"MetadataShapley: output must be 'prob' or 'logit', got {output!r}")
         self.output = output
         self.permutations = self.draw_permutations(self.n_players, int(n_permutations), seed)
-        rows = int(rows_per_head_call) if rows_per_head_call is not None else self.default_rows_per_head_call
-        if rows < 1:
-            raise ValueError(f"MetadataShapley: rows_per_head_call must be >= 1, got {rows_per_head_call}")
+        rows = mh.rows_per_call("MetadataShapley", "rows_per_head_call", rows_per_head_call, self.default_rows_per_head_call)
         self.rows_per_head_call = max(rows // G, 1) * G                       # whole coalitions: the reduce takes no split one
         self.out_width = int(out_width) if out_width is not None else int(getattr(model, "vocab_size", encoder.width))
         self.reset()
@@ -107,11 +101,6 @@ class MetadataShapley:
         rng = np.random.default_rng(seed)
         return np.stack([rng.permutation(n_players) for _ in range(n_permutations)]).astype(np.int32)
 
-    def reset(self):
-        """Forget the accumulated |values| (a new data set)."""
-        self.abs_sum = None
-        self.n_samples = 0
-
     def rows_per_sample(self):
         """1 + G + P 2 (M - 1) G: v(all), v(empty) and the interior coalitions of the P antithetic walks."""
         G, P, M = self.n_background, len(self.permutations), self.n_players
@@ -119,40 +108,19 @@ class MetadataShapley:
 
     def column_names(self, categorical_columns, numeric_columns):
         """The players' names in the order of `values`' second axis: the categorical columns, then the numeric ones."""
-        cats, nums = list(categorical_columns), list(numeric_columns)
-        if len(cats) != len(self.encoder.categories_) or len(nums) != len(self.encoder.mean_):
-            raise ValueError(f"column_names: the encoder has {len(self.encoder.categories_)} categorical + {len(self.encoder.mean_)} "
-                             f"numeric columns, got {len(cats)} + {len(nums)} names")
+        cats, nums = mh.check_columns("column_names", self.encoder, categorical_columns, numeric_columns)
         return cats + nums
-
-    def global_importance(self):
-        """(importance [M] = mean_abs averaged over the classes, the players in descending order of it): the script's global
-        ranking, of which it prints the first 10."""
-        if self.abs_sum is None:
-            raise ValueError("global_importance: nothing has been explained since the last reset()")
-        importance = (self.abs_sum / max(self.n_samples, 1)).mean(-1)
-        return importance, torch.argsort(importance, descending=True)
 
     # ---- per batch
     def explain(self, images, codes, numeric):
         """One batch: images [B, ...] as the model takes them, codes int32 [B, n_cat] (MetadataEncoder.codes), numeric [B, n_num]
         (NaN = missing).  Adds the batch's |values| to the running sums and returns a ShapleyResult."""
         model, enc = self.model, self.encoder
-        if model.training:
-            raise MMSkinError("MetadataShapley runs in eval mode: call model.eval() first")
-        if getattr(model, "text_model_name", None) != "one-hot-encoder":
-            raise ValueError(f"MetadataShapley is defined on encoded one-hot rows: text_model_name is {getattr(model, 'text_model_name', None)!r}, "
-                             "not 'one-hot-encoder'")
-        if model.attention_mecanism in ("no-metadata", "no-metadata-without-mlp"):
-            raise ValueError(f"MetadataShapley: the fusion {model.attention_mecanism!r} does not read the metadata, there is nothing to explain")
+        mh.check_metadata_model("MetadataShapley", model, "explain")
         if self.out_width != model.vocab_size:
             raise ValueError(f"MetadataShapley: out_width {self.out_width} is not the model's vocab_size {model.vocab_size}")
-        n_cat, n_num = len(enc.categories_), len(enc.mean_)
-        codes, numeric = torch.as_tensor(codes), torch.as_tensor(numeric)
         B = int(images.shape[0])
-        if tuple(codes.shape) != (B, n_cat) or tuple(numeric.shape) != (B, n_num):
-            raise ValueError(f"MetadataShapley.explain: a batch of {B} images needs codes {(B, n_cat)} and numeric {(B, n_num)}, got "
-                             f"{tuple(codes.shape)} and {tuple(numeric.shape)}")
+        codes, numeric = mh.batch_codes("MetadataShapley.explain", B, enc, codes, numeric)
         C, G, M, perms = int(model.num_classes), self.n_background, self.n_players, self.permutations
         if self.abs_sum is not None and tuple(self.abs_sum.shape) != (M, C):
             raise ValueError(f"MetadataShapley.explain: the sums hold {tuple(self.abs_sum.shape)} players x classes; call reset() first")
@@ -166,7 +134,7 @@ class MetadataShapley:
             codes = codes.to(device=dev, dtype=torch.int32).contiguous()
             numeric = numeric.to(device=dev, dtype=torch.float32).contiguous()
             bg_codes, bg_numeric = self.background_codes.to(dev), self.background_numeric.to(dev)
-            off_host = np.concatenate([[0], np.cumsum([len(c) for c in enc.categories_])]).astype(np.int32)
+            off_host = enc.col_offsets()
             if self.abs_sum is None:
                 self.abs_sum = torch.zeros((M, C), dtype=torch.float64, device=dev)
             v = torch.empty((B, K + 2, C), dtype=torch.float64, device=dev)
@@ -178,10 +146,8 @@ class MetadataShapley:
                 # the image-feature tile of THIS call only: row -> its sample, in the walk's row order
                 rows = torch.arange(r0, r1, device=dev)
                 sample = torch.where(rows < coalition_rows, torch.div(rows, (K + 1) * G, rounding_mode="floor"), rows - coalition_rows)
-                logits = model.fuse(img_feat.index_select(0, sample), metas)
-                if logits.dtype not in (torch.float32, torch.bfloat16):
-                    logits = logits.float()
-                out = ops.shapley_reduce(logits.contiguous(), v, perms, G, r0, output=OUTPUTS[self.output], finish=r1 == total,
+                logits = mh.head_logits(model, img_feat.index_select(0, sample), metas)
+                out = ops.shapley_reduce(logits, v, perms, G, r0, output=OUTPUTS[self.output], finish=r1 == total,
                                          abs_sum=self.abs_sum)
         values, base, full = out
         self.n_samples += B

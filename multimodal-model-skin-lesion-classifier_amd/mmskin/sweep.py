@@ -24,8 +24,8 @@ are compared with it.  Eval mode, forward only.
 import numpy as np
 import torch
 
+from . import _metadata_head as mh
 from . import ops
-from ._lib import MMSkinError
 
 
 class SweepResult:
@@ -59,9 +59,7 @@ class MetadataSweep:
         out_width: width of the encoded metadata rows, padded with zeros or cut; must equal model.vocab_size (the default).
         """
         self.model, self.encoder, self.device = model, encoder, device
-        self.rows_per_head_call = int(rows_per_head_call) if rows_per_head_call is not None else self.default_rows_per_head_call
-        if self.rows_per_head_call < 1:
-            raise ValueError(f"MetadataSweep: rows_per_head_call must be >= 1, got {rows_per_head_call}")
+        self.rows_per_head_call = mh.rows_per_call("MetadataSweep", "rows_per_head_call", rows_per_head_call, self.default_rows_per_head_call)
         self.out_width = int(out_width) if out_width is not None else int(getattr(model, "vocab_size", encoder.width))
         self.reset()
 
@@ -80,10 +78,7 @@ class MetadataSweep:
         list of pairs, to mutate a column more than once) column name -> ("toggle", a, b) | ("set", value) | ("add", value).
         `categorical_columns` / `numeric_columns` name the encoder's columns in its order; categorical values are given as
         the strings the encoder was fitted on (a string it has not seen encodes as an all-zero block)."""
-        cats, nums = list(categorical_columns), list(numeric_columns)
-        if len(cats) != len(self.encoder.categories_) or len(nums) != len(self.encoder.mean_):
-            raise ValueError(f"flip_variants: the encoder has {len(self.encoder.categories_)} categorical + {len(self.encoder.mean_)} "
-                             f"numeric columns, got {len(cats)} + {len(nums)} names")
+        cats, nums = mh.check_columns("flip_variants", self.encoder, categorical_columns, numeric_columns)
         items = list(spec.items()) if hasattr(spec, "items") else list(spec)
         table = np.zeros(1 + len(items), dtype=ops.META_VARIANT_DTYPE)
         for i, (name, rule) in enumerate(items, start=1):
@@ -113,12 +108,9 @@ class MetadataSweep:
         caller).  Returns (table, mask uint8 [1 + len(rates), n_rows, n_cat + n_num]) in the kernel's [categorical | numeric]
         column order; hand `run` the rows mask[:, r0:r1] of its batch."""
         rates, seeds = list(rates), list(seeds) if np.ndim(seeds) else [seeds] * len(list(rates))
-        n_num, n_cat = len(list(numeric_columns)), len(list(categorical_columns))
         if len(seeds) != len(rates):
             raise ValueError(f"missing_variants: {len(rates)} rates but {len(seeds)} seeds")
-        if n_cat != len(self.encoder.categories_) or n_num != len(self.encoder.mean_):
-            raise ValueError(f"missing_variants: the encoder has {len(self.encoder.categories_)} categorical + {len(self.encoder.mean_)} "
-                             f"numeric columns, got {n_cat} + {n_num} names")
+        n_cat, n_num = map(len, mh.check_columns("missing_variants", self.encoder, categorical_columns, numeric_columns))
         mask = np.zeros((1 + len(rates), int(n_rows), n_cat + n_num), dtype=np.uint8)
         for i, (rate, seed) in enumerate(zip(rates, seeds), start=1):
             keep = np.random.default_rng(seed).random((int(n_rows), n_num + n_cat)) < (1 - rate)
@@ -135,13 +127,7 @@ class MetadataSweep:
         [B, n_num] (NaN = missing), variants from flip_variants / missing_variants (variant 0 = baseline), mask uint8
         [V, B, n_cat + n_num] or None, labels [B] or None.  Adds this batch to the sweep's counters and returns a SweepResult."""
         model, enc = self.model, self.encoder
-        if model.training:
-            raise MMSkinError("MetadataSweep runs in eval mode: call model.eval() first")
-        if getattr(model, "text_model_name", None) != "one-hot-encoder":
-            raise ValueError(f"MetadataSweep is defined on encoded one-hot rows: text_model_name is {getattr(model, 'text_model_name', None)!r}, "
-                             "not 'one-hot-encoder'")
-        if model.attention_mecanism in ("no-metadata", "no-metadata-without-mlp"):
-            raise ValueError(f"MetadataSweep: the fusion {model.attention_mecanism!r} does not read the metadata, there is nothing to sweep")
+        mh.check_metadata_model("MetadataSweep", model, "sweep")
         if self.out_width != model.vocab_size:
             raise ValueError(f"MetadataSweep: out_width {self.out_width} is not the model's vocab_size {model.vocab_size}")
         table = np.ascontiguousarray(variants)
@@ -150,11 +136,8 @@ class MetadataSweep:
         if int(table["op"][0]) != ops.META_NONE:
             raise ValueError("MetadataSweep.run: variant 0 must be the baseline (op NONE)")
         V, n_cat, n_num = len(table), len(enc.categories_), len(enc.mean_)
-        codes, numeric = torch.as_tensor(codes), torch.as_tensor(numeric)
         B = int(images.shape[0])
-        if tuple(codes.shape) != (B, n_cat) or tuple(numeric.shape) != (B, n_num):
-            raise ValueError(f"MetadataSweep.run: a batch of {B} images needs codes {(B, n_cat)} and numeric {(B, n_num)}, got "
-                             f"{tuple(codes.shape)} and {tuple(numeric.shape)}")
+        codes, numeric = mh.batch_codes("MetadataSweep.run", B, enc, codes, numeric)
         if mask is not None:
             mask = torch.as_tensor(mask)
             if tuple(mask.shape) != (V, B, n_cat + n_num):
@@ -177,16 +160,13 @@ class MetadataSweep:
             if mask is not None:
                 mask = mask.to(device=dev, dtype=torch.uint8).contiguous()
             missing = torch.from_numpy(self._missing_codes()).to(dev) if mask is not None and n_cat else None
-            off_host = np.concatenate([[0], np.cumsum([len(c) for c in enc.categories_])]).astype(np.int32)
-            metas = ops.metadata_variants(codes, numeric, off_host, mean, scale, enc.nan_fill, table, self.out_width, mask=mask,
+            metas = ops.metadata_variants(codes, numeric, enc.col_offsets(), mean, scale, enc.nan_fill, table, self.out_width, mask=mask,
                                           missing_code=missing)
             feats = img_feat.unsqueeze(0).expand(V, *img_feat.shape).contiguous().reshape(V * B, -1)
             metas = metas.reshape(V * B, self.out_width)
             step = self.rows_per_head_call
-            parts = [model.fuse(feats[r0:r0 + step], metas[r0:r0 + step]) for r0 in range(0, V * B, step)]
-            logits = (parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)).reshape(V, B, C).contiguous()
-            if logits.dtype not in (torch.float32, torch.bfloat16):
-                logits = logits.float()
+            parts = [mh.head_logits(model, feats[r0:r0 + step], metas[r0:r0 + step]) for r0 in range(0, V * B, step)]
+            logits = (parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)).reshape(V, B, C)
             if self.flips is None:
                 self.flips = torch.zeros(V, dtype=torch.int32, device=dev)
                 self.transitions = torch.zeros((V, C, C), dtype=torch.int32, device=dev)

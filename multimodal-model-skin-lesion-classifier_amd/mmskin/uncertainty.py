@@ -30,6 +30,7 @@ import torch.nn as nn
 from . import ops
 from ._autograd import dropout_stream
 from ._lib import MMSkinError
+from ._metadata_head import rows_per_call
 from .sweep import MetadataSweep
 
 STATS = ops.UNCERTAINTY_STATS
@@ -134,12 +135,9 @@ class PredictiveUncertainty:
         images_per_model_call: most images one model call of `tta` gets.
         """
         self.model, self.device = model, device
-        self.rows_per_head_call = int(rows_per_head_call) if rows_per_head_call is not None else self.default_rows_per_head_call
-        self.images_per_model_call = int(images_per_model_call) if images_per_model_call is not None else self.default_images_per_model_call
-        if self.rows_per_head_call < 1:
-            raise ValueError(f"PredictiveUncertainty: rows_per_head_call must be >= 1, got {rows_per_head_call}")
-        if self.images_per_model_call < 1:
-            raise ValueError(f"PredictiveUncertainty: images_per_model_call must be >= 1, got {images_per_model_call}")
+        self.rows_per_head_call = rows_per_call("PredictiveUncertainty", "rows_per_head_call", rows_per_head_call, self.default_rows_per_head_call)
+        self.images_per_model_call = rows_per_call("PredictiveUncertainty", "images_per_model_call", images_per_model_call,
+                                                   self.default_images_per_model_call)
         self.reset()
 
     def reset(self):
