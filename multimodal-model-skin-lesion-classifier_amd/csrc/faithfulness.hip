@@ -23,13 +23,15 @@
 
 #pragma clang fp contract(off)
 
+#include "perturb_tile.h"   // tile_pixel / tile_store / blend, shared with rise.hip; compiled here with contraction off
+#include "target_prob.h"    // pick_target / row_probability / TARGET_MAX_CLASSES, shared with rise.hip
+
 namespace {
 
 constexpr int NT = 256;                   // threads per workgroup
 constexpr int PPT = 4;                    // perturb: pixels per thread (one 16-byte store per colour plane)
 constexpr int MAX_PIXELS = 65536;         // rank / perturb: H * W (256 x 256)
 constexpr int MAX_STEPS = 1024;           // perturb / curves: S
-constexpr int MAX_CLASSES = 65536;        // curves: C
 constexpr int RANK_TILE = 2048;           // rank: keys staged per round, a multiple of NT
 constexpr int BLUR_T = 32;                // blur: output tile edge
 constexpr int BLUR_MAX_R = 15;            // blur: ksize <= 31
@@ -130,7 +132,8 @@ __global__ __launch_bounds__(NT) void faith_blur_kernel(const float* __restrict_
   }
 }
 
-// fixed-order fp64 sum over a workgroup: red[tid] holds the thread's partial; the tree halves NT; every thread gets the total
+// fixed-order fp64 sum over a workgroup: red[tid] holds the thread's partial; the tree halves NT; every thread gets the total.
+// Not uncertainty.hip's block_sum_f64, which adds wave totals: the orders differ, so the two do not merge bitwise.
 __device__ __forceinline__ double block_tree_sum(double* red, int tid) {
   __syncthreads();
   for (int s = NT / 2; s > 0; s >>= 1) {
@@ -157,19 +160,19 @@ __global__ __launch_bounds__(NT) void faith_mean_kernel(const float* __restrict_
 enum { MODE_DELETION = 0, MODE_INSERTION = 1, MODE_EXPLANATION = 2 };
 
 // grid = (pixel tiles of NT * PPT, rows of the chunk).  The row's (image, k, mode) entry is the same for the whole workgroup and
-// is clamped to what exists: a bad entry reads the nearest image, step or mode, never other memory.  VEC: a thread's PPT pixels
-// are consecutive and 16-byte aligned in every plane (H * W a multiple of 4): dwordx4 loads and one dwordx4 store per plane;
-// otherwise pixel k of a thread is tile + k * NT + tid and the accesses are coalesced dwords.  Rows n .. n_pad are zeros.
+// is clamped to what exists: a bad entry reads the nearest image, step or mode, never other memory.  The pixels of a
+// thread, the store and the blend are perturb_tile.h's, which describes VEC; the guarded loads are written out here (see there).
+// This kernel's own: the rank test, which selects, and the clamped saliency that the explanation row blends with.  Rows n ..
+// n_pad are zeros.
 template <bool VEC>
 __global__ __launch_bounds__(NT) void faith_perturb_kernel(const float* __restrict__ images, const float* __restrict__ baseline,
                                                            const int32_t* __restrict__ rank, const float* __restrict__ sal,
                                                            const int32_t* __restrict__ rows, int N, int HW, int S, int n,
                                                            float* __restrict__ out) {
   const int tid = threadIdx.x, j = blockIdx.y;
-  const int base = blockIdx.x * (NT * PPT);
   int p[PPT];
 #pragma unroll
-  for (int k = 0; k < PPT; ++k) p[k] = VEC ? base + tid * PPT + k : base + k * NT + tid;
+  for (int k = 0; k < PPT; ++k) p[k] = tile_pixel<VEC, NT, PPT>(blockIdx.x, tid, k);
   float* dst = out + (size_t)j * 3 * HW;
   const bool live = j < n;
   int img = 0, mode = MODE_DELETION, count = 0;
@@ -238,27 +241,19 @@ __global__ __launch_bounds__(NT) void faith_perturb_kernel(const float* __restri
 #pragma unroll
       for (int k = 0; k < PPT; ++k) {
         if (mode == MODE_EXPLANATION) {
-          const float d = xv[k] - bv[k];
-          const float m = h[k] * d;
-          v[k] = bv[k] + m;
+          v[k] = blend(bv[k], xv[k], h[k]);
         } else {
           v[k] = take_base[k] ? bv[k] : xv[k];
         }
       }
     }
-    if (VEC) {
-      if (p[0] < HW) *reinterpret_cast<float4*>(dst + (size_t)ch * HW + p[0]) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < PPT; ++k)
-        if (p[k] < HW) dst[(size_t)ch * HW + p[k]] = v[k];
-    }
+    tile_store<VEC>(dst, (size_t)ch * HW, p, HW, v);
   }
 }
 
 // One workgroup per image.  Rows of image n in `logits`: n * P + k deletion step k, n * P + S + 1 + k insertion step k,
 // n * P + 2 S + 2 the explanation image, P = 2 S + 3; deletion step 0 is the clean image.  Every thread takes rows t, t + NT,
-// ...: the soft-max probability of the target class in fp64 (maximum, then the sum of exp(l - max) in ascending class order).
+// ...: the soft-max probability of the target class in fp64 (target_prob.h).
 // Three threads of three different waves then form the areas and the two confidence scores, each a serial loop in ascending k.
 __global__ __launch_bounds__(NT) void faith_curves_kernel(const float* __restrict__ logits, const int32_t* __restrict__ target_in,
                                                           int N, int S, int C, double* __restrict__ curves,
@@ -268,30 +263,13 @@ __global__ __launch_bounds__(NT) void faith_curves_kernel(const float* __restric
   const int tid = threadIdx.x, n = blockIdx.x, P = 2 * S + 3;
   const float* rows = logits + (size_t)n * P * C;
   if (tid == 0) {
-    int t;
-    if (target_in) {
-      t = min(max(target_in[n], 0), C - 1);
-    } else {                                             // the first largest logit of the clean row; a NaN is never larger
-      t = 0;
-      float best = rows[0];
-      for (int c = 1; c < C; ++c) {
-        const float v = rows[c];
-        if (v > best || (best != best && v == v)) { best = v; t = c; }
-      }
-    }
+    const int t = pick_target(rows, C, target_in, n);    // on the clean row
     s_target = t;
     target_out[n] = t;
   }
   __syncthreads();
   const int target = s_target;
-  for (int t = tid; t < P; t += NT) {
-    const float* l = rows + (size_t)t * C;
-    double m = (double)l[0];
-    for (int c = 1; c < C; ++c) m = fmax(m, (double)l[c]);
-    double sum = 0.0;
-    for (int c = 0; c < C; ++c) sum = sum + exp((double)l[c] - m);
-    s_p[t] = exp((double)l[target] - m) / sum;
-  }
+  for (int t = tid; t < P; t += NT) s_p[t] = row_probability(rows + (size_t)t * C, C, target);
   __syncthreads();
   for (int t = tid; t < 2 * (S + 1); t += NT) {
     const int which = t / (S + 1), k = t - which * (S + 1);
@@ -394,7 +372,7 @@ extern "C" int mmskin_faith_perturb(const float* images, const float* baseline, 
 extern "C" int mmskin_faith_curves(const float* logits, const int32_t* target, int N, int S, int C, double* curves, double* scalars,
                                    double* means, int32_t* target_out, void* stream) {
   ARG_CHECK(N >= 1 && C >= 1, "faith_curves: every extent must be >= 1 (%d images, %d classes)", N, C);
-  ARG_CHECK(N <= (1 << 20) && C <= MAX_CLASSES, "faith_curves: %d images or %d classes out of range", N, C);
+  ARG_CHECK(N <= (1 << 20) && C <= TARGET_MAX_CLASSES, "faith_curves: %d images or %d classes out of range", N, C);
   ARG_CHECK(S >= 1 && S <= MAX_STEPS, "faith_curves: %d steps is outside 1 .. %d", S, MAX_STEPS);
   ARG_CHECK(logits && curves && scalars && means && target_out, "faith_curves: null argument");
   hipLaunchKernelGGL(faith_curves_kernel, dim3(N), dim3(NT), 0, ST(stream), logits, target, N, S, C, curves, scalars, target_out);

@@ -21,6 +21,9 @@
 
 #pragma clang fp contract(off)
 
+#include "perturb_tile.h"   // tile_pixel / tile_store / blend, shared with faithfulness.hip; compiled here with contraction off
+#include "target_prob.h"    // pick_target / row_probability / TARGET_MAX_CLASSES, shared with faithfulness.hip
+
 namespace {
 
 constexpr int NT = 256;                   // threads per workgroup
@@ -30,7 +33,6 @@ constexpr int MAX_CELLS = (MAX_GRID + 1) * (MAX_GRID + 1);
 constexpr int ENTRY = 20;                 // words of a mask's entry: MAX_GRID + 1 rows, dy, dx, one of padding
 constexpr int E_DY = 17, E_DX = 18;
 constexpr int MAX_MASKS = 1 << 20;
-constexpr int MAX_CLASSES = 65536;
 constexpr int NI = 4;                     // accumulate: images per workgroup (fp64 accumulators per thread, plus the coverage)
 constexpr int MB = 32;                    // accumulate: masks staged in LDS per round
 
@@ -100,20 +102,19 @@ __global__ __launch_bounds__(NT) void rise_masks_kernel(Geom q, int j0, float* _
   }
 }
 
-// grid = (pixel tiles of NT * PPT, rows of the chunk).  VEC: a thread's PPT pixels are consecutive and 16-byte aligned in every
-// plane (H * W a multiple of 4): dwordx4 loads and one dwordx4 store per plane; otherwise pixel k of a thread is
-// tile + k * NT + tid and the accesses are coalesced dwords.  Rows n .. n_pad are zeros.
+// grid = (pixel tiles of NT * PPT, rows of the chunk).  The pixels of a thread, the store and the blend are perturb_tile.h's,
+// which describes VEC; the guarded loads are written out here (see there).  RISE's own is m: the mask of the row, evaluated
+// once per pixel for the three colour planes.  Rows n .. n_pad are zeros.
 template <bool VEC>
 __global__ __launch_bounds__(NT) void rise_apply_kernel(const float* __restrict__ images, const float* __restrict__ baseline, Geom q,
                                                         int n_masks, int64_t r0, int n, float* __restrict__ out) {
   __shared__ uint8_t s_bit[MAX_CELLS];
   __shared__ uint32_t s_e[ENTRY];
   const int tid = threadIdx.x, row = blockIdx.y, HW = q.H * q.W;
-  const int base = blockIdx.x * (NT * PPT);
   const bool live = row < n;                                  // the same for the whole workgroup
   int p[PPT];
 #pragma unroll
-  for (int k = 0; k < PPT; ++k) p[k] = VEC ? base + tid * PPT + k : base + k * NT + tid;
+  for (int k = 0; k < PPT; ++k) p[k] = tile_pixel<VEC, NT, PPT>(blockIdx.x, tid, k);
   float* dst = out + (size_t)row * 3 * HW;
   int img = 0;
   float m[PPT] = {0.f, 0.f, 0.f, 0.f};
@@ -153,29 +154,10 @@ __global__ __launch_bounds__(NT) void rise_apply_kernel(const float* __restrict_
         }
       }
 #pragma unroll
-      for (int k = 0; k < PPT; ++k) {
-        const float d = xv[k] - bv[k];
-        const float t = m[k] * d;
-        v[k] = bv[k] + t;
-      }
+      for (int k = 0; k < PPT; ++k) v[k] = blend(bv[k], xv[k], m[k]);
     }
-    if (VEC) {
-      if (p[0] < HW) *reinterpret_cast<float4*>(dst + (size_t)c * HW + p[0]) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < PPT; ++k)
-        if (p[k] < HW) dst[(size_t)c * HW + p[k]] = v[k];
-    }
+    tile_store<VEC>(dst, (size_t)c * HW, p, HW, v);
   }
-}
-
-// fp64 soft-max probability of class t of one row of K logits: the maximum, then the sum of exp(l - max) in ascending class order
-__device__ __forceinline__ double row_probability(const float* __restrict__ l, int K, int t) {
-  double mx = (double)l[0];
-  for (int c = 1; c < K; ++c) mx = fmax(mx, (double)l[c]);
-  double sum = 0.0;
-  for (int c = 0; c < K; ++c) sum = sum + exp((double)l[c] - mx);
-  return exp((double)l[t] - mx) / sum;
 }
 
 // One thread per image: the class it is explained on and the probability of that class on the clean image.
@@ -184,17 +166,7 @@ __global__ __launch_bounds__(NT) void rise_target_kernel(const float* __restrict
   const int n = blockIdx.x * NT + threadIdx.x;
   if (n >= N) return;
   const float* l = clean + (size_t)n * K;
-  int t;
-  if (target_in) {
-    t = min(max(target_in[n], 0), K - 1);
-  } else {                                                    // the first largest logit; a NaN is never larger
-    t = 0;
-    float best = l[0];
-    for (int c = 1; c < K; ++c) {
-      const float v = l[c];
-      if (v > best || (best != best && v == v)) { best = v; t = c; }
-    }
-  }
+  const int t = pick_target(l, K, target_in, n);
   target_used[n] = t;
   clean_prob[n] = row_probability(l, K, t);
 }
@@ -341,7 +313,7 @@ extern "C" int mmskin_rise_accumulate(const float* logits, const int32_t* target
   Geom q;
   if (int rc = make_geom("rise_accumulate", seed, grid, p1, H, W, &q)) return rc;
   ARG_CHECK(N >= 1 && N <= 65535, "rise_accumulate: N = %d images is outside 1 .. 65535", N);
-  ARG_CHECK(K >= 1 && K <= MAX_CLASSES, "rise_accumulate: K = %d classes is outside 1 .. %d", K, MAX_CLASSES);
+  ARG_CHECK(K >= 1 && K <= TARGET_MAX_CLASSES, "rise_accumulate: K = %d classes is outside 1 .. %d", K, TARGET_MAX_CLASSES);
   if (int rc = check_masks("rise_accumulate", n_masks)) return rc;
   ARG_CHECK(logits && clean_logits && saliency_sum && coverage && clean_prob && target_used && workspace,
             "rise_accumulate: null argument");

@@ -24,6 +24,7 @@
 #pragma clang fp contract(off)
 
 #include "cam_sample.h"   // axis_tap / make_tap / bilerp / block_minmax, shared with gradcam.hip; compiled here with contraction off
+#include "perturb_tile.h" // tile_pixel / tile_store, shared with rise.hip and faithfulness.hip
 
 namespace {
 
@@ -52,9 +53,10 @@ __global__ __launch_bounds__(NT) void scorecam_minmax_kernel(const float* __rest
 }
 
 // grid = (pixel tiles of NT * PPT, groups of G output rows).  A thread fixes its PPT pixels (taps + the three image values)
-// once and walks the group's channels; per channel and colour plane it stores once.  VEC: the PPT pixels are consecutive and
-// 16-byte aligned in every plane (H * W a multiple of 4): one dwordx4 store; otherwise pixel k of a thread is tile + k * NT +
-// tid and the stores are coalesced dwords.  Rows n .. n_pad of the chunk are written as zeros.
+// once and walks the group's channels; per channel and colour plane it stores once.  The pixels of a thread and the store are
+// perturb_tile.h's.  The loads are not: there is one image and no baseline, it is read once for all the group's channels, by
+// clamped dwords also under VEC (only `out` must be aligned), and the value is a product, not a blend.  Rows n .. n_pad of the
+// chunk are written as zeros.
 template <bool VEC>
 __global__ __launch_bounds__(NT) void scorecam_mask_kernel(const float* __restrict__ fmap, const float* __restrict__ minmax,
                                                            const float* __restrict__ image, int fh, int fw, int H, int W,
@@ -72,13 +74,12 @@ __global__ __launch_bounds__(NT) void scorecam_mask_kernel(const float* __restri
   }
   __syncthreads();
 
-  const int base = blockIdx.x * (NT * PPT);
   int p[PPT];
   Tap tap[PPT];
   float img[3][PPT];
 #pragma unroll
   for (int k = 0; k < PPT; ++k) {
-    p[k] = VEC ? base + tid * PPT + k : base + k * NT + tid;
+    p[k] = tile_pixel<VEC, NT, PPT>(blockIdx.x, tid, k);
     const int pc = min(p[k], HW - 1);          // a pixel past the end computes on the last one and is never stored
     const int y = pc / W, x = pc - y * W;
     tap[k] = make_tap(y, x, fh, fw, scale_h, scale_w);
@@ -98,13 +99,7 @@ __global__ __launch_bounds__(NT) void scorecam_mask_kernel(const float* __restri
       float v[PPT];
 #pragma unroll
       for (int k = 0; k < PPT; ++k) v[k] = is_live ? img[ch][k] * cam[k] : 0.f;
-      if (VEC) {
-        if (p[0] < HW) *reinterpret_cast<float4*>(dst + p[0]) = make_float4(v[0], v[1], v[2], v[3]);
-      } else {
-#pragma unroll
-        for (int k = 0; k < PPT; ++k)
-          if (p[k] < HW) dst[p[k]] = v[k];
-      }
+      tile_store<VEC>(dst, 0, p, HW, v);
     }
   }
 }

@@ -191,6 +191,7 @@ __global__ __launch_bounds__(NT) void risk_coverage_counts_kernel(const double* 
 }
 
 // the fixed-order sum of one value per thread over the workgroup; every thread returns with it
+// (wave sums, then the wave totals in ascending order: not faithfulness.hip's block_tree_sum, whose order differs)
 __device__ __forceinline__ double block_sum_f64(double v, double* s_red) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   v = wave_sum_f64(v);

@@ -21,30 +21,18 @@ maps.  Any other layer that delivers a 4-D map takes the generic route: the whol
 layer, the same kernels.  Out of scope: second-order differentiation (the reference squares and cubes the first-order gradient
 and never differentiates again), DenseNet's `find_last_conv` target, and the MBConv / VGG plans, whose encoders run no hooks.
 """
-from collections.abc import Mapping
-
 import torch
 import torch.nn as nn
 
 from . import ops
+from ._image_explainer import (DEFAULT_CHUNK, check_images, check_rows, check_target_range, chunk_or_default, expand_batch,
+                               model_device, require_eval, target_tensor)
 from ._lib import MMSkinError
 from .backbone import RESNET_DEPTHS, _FlatBackbone
 
 
-def _expand_batch(metadata, n):
-    """metadata of batch 1 -> batch n: a tensor (1, V), or a mapping of such tensors (the tokenizer's BatchEncoding)."""
-    if isinstance(metadata, Mapping):
-        return {k: _expand_batch(v, n) for k, v in metadata.items()}
-    if torch.is_tensor(metadata):
-        if metadata.dim() == 0 or metadata.shape[0] != 1:
-            raise ValueError(f"ScoreCAM: metadata must have batch 1, got shape {tuple(metadata.shape)}")
-        return metadata.expand(n, *metadata.shape[1:]).contiguous()
-    return metadata
-
-
 class ScoreCAM:
-    # Channels per masked forward: the fastest of 64 / 128 / 256 on densenet169 + crossattention at 224x224 (DESIGN.md section 12)
-    default_chunk = 256
+    default_chunk = DEFAULT_CHUNK
 
     def __init__(self, model, target_layer, device, chunk=None):
         """
@@ -57,9 +45,7 @@ class ScoreCAM:
         self.model = model
         self.target_layer = target_layer
         self.device = device
-        self.chunk = int(chunk) if chunk is not None else self.default_chunk
-        if self.chunk < 1:
-            raise ValueError(f"ScoreCAM: chunk must be >= 1, got {chunk}")
+        self.chunk = chunk_or_default(chunk, "ScoreCAM")
         self.features = None
         self.scores = None           # soft-max score of the target class per channel, device tensor [C], after generate_heatmap
         self.hook_handle = self.target_layer.register_forward_hook(self.hook_fn)
@@ -77,11 +63,9 @@ class ScoreCAM:
     def generate_heatmap(self, image, metadata, target_class):
         """image (1, 3, H, W), metadata (1, V) or a mapping of batch-1 tensors -> np.ndarray [H, W] float32 in [0, 1].
         A combined map that is flat comes back as NaN, as in the reference (no zero guard on the last division)."""
-        if image.dim() != 4 or image.shape[0] != 1 or image.shape[1] != 3:
-            raise ValueError(f"ScoreCAM.generate_heatmap: image must have shape (1, 3, H, W), got {tuple(image.shape)}: the "
-                             "per-channel min-max of the reference is only meaningful for one image")
-        if self.model.training:
-            raise MMSkinError("ScoreCAM runs in eval mode: call model.eval() first")
+        check_images(image, "ScoreCAM.generate_heatmap", one=True,
+                     why=": the per-channel min-max of the reference is only meaningful for one image")
+        require_eval(self.model, "ScoreCAM")
         image = image.to(self.device).float().contiguous()
         H, W = image.shape[2:]
 
@@ -97,7 +81,7 @@ class ScoreCAM:
         minmax = ops.scorecam_minmax(fmap, (H, W))
         scores = torch.empty(C, device=fmap.device, dtype=torch.float32)
         chunk = self.chunk
-        meta = _expand_batch(metadata, chunk)
+        meta = expand_batch(metadata, chunk, "ScoreCAM")
         masked = torch.empty((chunk, 3, H, W), device=fmap.device, dtype=torch.float32)
 
         # the masked forwards run without the hook: the encoder then takes its BatchNorm-folded eval plan, not the hooked route
@@ -113,16 +97,6 @@ class ScoreCAM:
             self.hook_handle = self.target_layer.register_forward_hook(self.hook_fn)
         self.scores = scores
         return ops.scorecam_combine(fmap, minmax, scores, (H, W)).cpu().numpy()
-
-
-def _check_rows(metadata, rows, who):
-    """metadata of `rows` rows: a tensor (rows, V), or a mapping of such tensors"""
-    if isinstance(metadata, Mapping):
-        for v in metadata.values():
-            _check_rows(v, rows, who)
-    elif torch.is_tensor(metadata) and (metadata.dim() == 0 or metadata.shape[0] != rows):
-        raise ValueError(f"{who}: metadata must have {rows} rows (images x variants_per_image, image-major), got shape "
-                         f"{tuple(metadata.shape)}")
 
 
 class _GradCAMBase:
@@ -188,19 +162,10 @@ class _GradCAMBase:
             raise MMSkinError(f"{who}: the model must return logits of shape ({rows}, K), got {tuple(logits.shape)}")
         K = logits.shape[1]
         pred = logits.detach().argmax(dim=1)
-        if target_class is None:
+        index = target_tensor(target_class, rows, logits.device, who, torch.long)
+        check_target_range(target_class, K, who)
+        if index is None:
             index = pred
-        elif torch.is_tensor(target_class):
-            if target_class.dim() != 1 or target_class.shape[0] != rows or target_class.is_floating_point():
-                raise ValueError(f"{who}: target_class must be an int, None or an int tensor [{rows}], got "
-                                 f"{target_class.dtype} {tuple(target_class.shape)}")
-            if bool(((target_class < 0) | (target_class >= K)).any()):       # checked where the tensor lives
-                raise ValueError(f"{who}: target_class has entries outside 0 .. {K - 1}")
-            index = target_class.to(logits.device).long()
-        else:
-            if not 0 <= int(target_class) < K:
-                raise ValueError(f"{who}: target_class {target_class} is outside 0 .. {K - 1}")
-            index = torch.full((rows,), int(target_class), device=logits.device, dtype=torch.long)
         return logits.gather(1, index[:, None])[:, 0], pred, torch.softmax(logits.detach().float(), dim=1)
 
     def generate_batch(self, images, metadata, target_class=None, variants_per_image=1):
@@ -213,18 +178,15 @@ class _GradCAMBase:
         self.activations on the object; nothing is copied to the host."""
         who = type(self).__name__
         model = self.model
-        if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != 3 or images.shape[0] < 1:
-            raise ValueError(f"{who}.generate_batch: images must have shape (N, 3, H, W), got "
-                             f"{tuple(images.shape) if torch.is_tensor(images) else type(images).__name__}")
+        check_images(images, f"{who}.generate_batch")
         V = int(variants_per_image)
         if V < 1:
             raise ValueError(f"{who}.generate_batch: variants_per_image must be >= 1, got {variants_per_image}")
-        if model.training:
-            raise MMSkinError(f"{who} runs in eval mode: call model.eval() first")
+        require_eval(model, who)
         N = images.shape[0]
         R = N * V
-        _check_rows(metadata, R, f"{who}.generate_batch")
-        device = getattr(model, "device", None) or next(model.parameters()).device
+        check_rows(metadata, R, f"{who}.generate_batch")
+        device = model_device(model)
         images = images.detach().to(device).float().contiguous()
         H, W = images.shape[2:]
         self.clear()
@@ -258,11 +220,9 @@ class _GradCAMBase:
     def generate(self, image, metadata, target_class):
         """image (1, 3, H, W), metadata of one row, target_class an int -> np.ndarray [H, W] float32 in [0, 1]: the reference's
         call and result; the R = 1 case of generate_batch."""
-        if not torch.is_tensor(image) or image.dim() != 4 or image.shape[0] != 1 or image.shape[1] != 3:
-            raise ValueError(f"{type(self).__name__}.generate: image must have shape (1, 3, H, W), got "
-                             f"{tuple(image.shape) if torch.is_tensor(image) else type(image).__name__}: the min-max of the "
-                             "reference runs over the whole batch and is only meaningful for one image (generate_batch "
-                             "normalises every row on its own)")
+        check_images(image, f"{type(self).__name__}.generate", one=True,
+                     why=": the min-max of the reference runs over the whole batch and is only meaningful for one image "
+                         "(generate_batch normalises every row on its own)")
         return self.generate_batch(image, metadata, target_class)[0].cpu().numpy()
 
 

@@ -18,7 +18,6 @@ target class; areas by the trapezoid rule over x = k / S; average_drop = max(0, 
 
 Eval mode, forward only: nothing here is differentiable.
 """
-from collections.abc import Mapping
 from dataclasses import dataclass, fields
 
 import numpy as np
@@ -26,9 +25,9 @@ import torch
 
 from . import ops
 from ._lib import MMSkinError
-from .cam import GradCAM, GradCAMPlusPlus, ScoreCAM, _check_rows
-
-BASELINES = ("blur", "zero", "mean")
+from ._image_explainer import (BASELINES, Baseline, check_images, check_rows, check_target_range, chunk_or_default,  # noqa: F401
+                               chunked_logits, model_device, require_eval, take_rows, target_tensor)
+from .cam import GradCAM, GradCAMPlusPlus, ScoreCAM
 
 
 @dataclass
@@ -50,15 +49,6 @@ class FaithfulnessResult:
         return FaithfulnessResult(**{f.name: getattr(self, f.name).cpu() for f in fields(self)})
 
 
-def _take_rows(metadata, index):
-    """rows `index` (a long device tensor) of a metadata tensor, or of every tensor of a mapping"""
-    if isinstance(metadata, Mapping):
-        return {k: _take_rows(v, index) for k, v in metadata.items()}
-    if torch.is_tensor(metadata):
-        return metadata.to(index.device).index_select(0, index)
-    return metadata
-
-
 class CamFaithfulness:
     def __init__(self, model, device, steps=32, baseline="blur", blur_ksize=11, blur_sigma=5.0, chunk=None):
         """
@@ -75,21 +65,13 @@ class CamFaithfulness:
         self.steps = int(steps)
         if not 1 <= self.steps <= ops.FAITH_MAX_STEPS:
             raise ValueError(f"CamFaithfulness: steps must be in 1 .. {ops.FAITH_MAX_STEPS}, got {steps}")
-        if baseline not in BASELINES:
-            raise ValueError(f"CamFaithfulness: baseline must be one of {BASELINES}, got {baseline!r}")
-        self.baseline = baseline
-        self.taps = ops.gaussian_taps(blur_ksize, blur_sigma) if baseline == "blur" else None
-        self.chunk = int(chunk) if chunk is not None else ScoreCAM.default_chunk
-        if self.chunk < 1:
-            raise ValueError(f"CamFaithfulness: chunk must be >= 1, got {chunk}")
+        self._baseline = Baseline("CamFaithfulness", baseline, blur_ksize, blur_sigma)
+        self.baseline, self.taps = baseline, self._baseline.taps
+        self.chunk = chunk_or_default(chunk, "CamFaithfulness")
 
     def baseline_images(self, images):
         """images [N, 3, H, W] fp32 on the device -> the baseline of every image, same shape"""
-        if self.baseline == "blur":
-            return ops.faith_blur(images, self.taps)
-        if self.baseline == "mean":
-            return ops.faith_mean(images)
-        return torch.zeros_like(images)
+        return self._baseline.images(images)
 
     def row_table(self, n_images):
         """int32 [N * (2 S + 3), 3] of (image, k, mode), image-major: deletion k = 0 .. S, insertion k = 0 .. S, explanation"""
@@ -106,33 +88,22 @@ class CamFaithfulness:
         tensor or numpy array (any CAM class's output); target_class an int, an int tensor (N,), or None = the argmax of the
         clean forward, taken on the device -> FaithfulnessResult."""
         who = "CamFaithfulness.evaluate"
-        if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != 3 or images.shape[0] < 1:
-            raise ValueError(f"{who}: images must have shape (N, 3, H, W), got "
-                             f"{tuple(images.shape) if torch.is_tensor(images) else type(images).__name__}")
+        check_images(images, who)
         N, _, H, W = images.shape
         if isinstance(saliency, np.ndarray):
             saliency = torch.from_numpy(saliency)
         if not torch.is_tensor(saliency) or not saliency.is_floating_point() or tuple(saliency.shape) != (N, H, W):
             raise ValueError(f"{who}: saliency must be a float tensor or array of shape {(N, H, W)}, got "
                              f"{(saliency.dtype, tuple(saliency.shape)) if torch.is_tensor(saliency) else type(saliency).__name__}")
-        _check_rows(metadata, N, who)
+        check_rows(metadata, N, who)
         S = self.steps
         if S > H * W:
             raise ValueError(f"{who}: {S} steps on an image of {H * W} pixels; steps must be <= H * W")
         if H * W > ops.faith_max_pixels():
             raise MMSkinError(f"{who}: {H}x{W} images are above the rank kernel's cap of {ops.faith_max_pixels()} pixels")
-        if self.model.training:
-            raise MMSkinError("CamFaithfulness runs in eval mode: call model.eval() first")
+        require_eval(self.model, "CamFaithfulness")
         dev = self.device
-        target = None
-        if target_class is not None:
-            if torch.is_tensor(target_class):
-                if target_class.dim() != 1 or target_class.shape[0] != N or target_class.is_floating_point():
-                    raise ValueError(f"{who}: target_class must be an int, None or an int tensor [{N}], got "
-                                     f"{target_class.dtype} {tuple(target_class.shape)}")
-                target = target_class.to(dev).to(torch.int32).contiguous()
-            else:
-                target = torch.full((N,), int(target_class), device=dev, dtype=torch.int32)
+        target = target_tensor(target_class, N, dev, who)
 
         images = images.detach().to(dev).float().contiguous()
         saliency = saliency.detach().to(dev).float().contiguous()
@@ -141,26 +112,15 @@ class CamFaithfulness:
 
         P, chunk = 2 * S + 3, self.chunk
         R = N * P
-        n_chunks = -(-R // chunk)
-        table = np.zeros((n_chunks * chunk, 3), dtype=np.int32)          # the padding rows point at image 0 and are never built
+        table = np.zeros((-(-R // chunk) * chunk, 3), dtype=np.int32)    # the padding rows point at image 0 and are never built
         table[:R] = self.row_table(N)
         rows = torch.from_numpy(table).to(dev)
-        row_image = rows[:, 0].long()
-        masked = torch.empty((chunk, 3, H, W), device=dev, dtype=torch.float32)
-        logits = None
-        with torch.no_grad():
-            for c in range(n_chunks):
-                r0 = c * chunk
-                ops.faith_perturb(images, base, rank, saliency, rows[r0:r0 + chunk], S, min(chunk, R - r0), chunk, out=masked)
-                out = self.model(masked, _take_rows(metadata, row_image[r0:r0 + chunk]))
-                if logits is None:
-                    if out.dim() != 2 or out.shape[0] != chunk:
-                        raise MMSkinError(f"{who}: the model must return logits of shape ({chunk}, K), got {tuple(out.shape)}")
-                    logits = torch.empty((n_chunks * chunk, out.shape[1]), device=dev, dtype=torch.float32)
-                logits[r0:r0 + chunk] = out                              # the padded rows' logits are never read
-        K = logits.shape[1]
-        if target is not None and bool(((target < 0) | (target >= K)).any()):       # checked where the tensor lives
-            raise ValueError(f"{who}: target_class has entries outside 0 .. {K - 1}")
+
+        def write_chunk(r0, n, out):
+            return ops.faith_perturb(images, base, rank, saliency, rows[r0:r0 + chunk], S, n, chunk, out=out)
+
+        logits = chunked_logits(self.model, metadata, rows[:, 0].long(), R, chunk, write_chunk, who)
+        check_target_range(target, logits.shape[1], who)
         curves, scalars, means, used = ops.faith_curves(logits, S, N, target)
         return FaithfulnessResult(deletion=curves[0], insertion=curves[1], deletion_auc=scalars[0], insertion_auc=scalars[1],
                                   average_drop=scalars[2], increase=scalars[3], target=used, mean_deletion_auc=means[0],
@@ -173,7 +133,7 @@ CAM_METHODS = ("gradcam", "gradcam++", "scorecam")
 def cam_maps(model, target_layer, images, metadata, method, target, chunk=None):
     """The maps [N, H, W] (device, fp32) of one method on the existing classes of mmskin.cam; target: int tensor [N] on the
     device.  Score-CAM explains one image per call, so it loops over the images."""
-    device = getattr(model, "device", None) or next(model.parameters()).device
+    device = model_device(model)
     if method in ("gradcam", "gradcam++"):
         cam = (GradCAM if method == "gradcam" else GradCAMPlusPlus)(model, target_layer)
         try:
@@ -185,7 +145,7 @@ def cam_maps(model, target_layer, images, metadata, method, target, chunk=None):
         try:
             classes = target.tolist()
             one = torch.arange(1, device=target.device)
-            heats = [cam.generate_heatmap(images[i:i + 1], _take_rows(metadata, one + i), classes[i]) for i in range(images.shape[0])]
+            heats = [cam.generate_heatmap(images[i:i + 1], take_rows(metadata, one + i), classes[i]) for i in range(images.shape[0])]
         finally:
             cam.remove_hook()
         return torch.from_numpy(np.stack(heats)).to(device)
@@ -198,19 +158,15 @@ def compare_cam_methods(model, target_layer, images, metadata, methods=CAM_METHO
 
     target_class: an int, an int tensor [N], or None = the model's own prediction on the clean images (one forward, shared by
     all methods).  -> {method: {"maps": device tensor [N, H, W], "result": FaithfulnessResult}}"""
-    if model.training:
-        raise MMSkinError("compare_cam_methods runs in eval mode: call model.eval() first")
-    device = getattr(model, "device", None) or next(model.parameters()).device
+    require_eval(model, "compare_cam_methods")
+    device = model_device(model)
     images = images.detach().to(device).float().contiguous()
     N = images.shape[0]
-    _check_rows(metadata, N, "compare_cam_methods")
-    if target_class is None:
+    check_rows(metadata, N, "compare_cam_methods")
+    target = target_tensor(target_class, N, device, "compare_cam_methods", torch.long)
+    if target is None:
         with torch.no_grad():
             target = model(images, metadata).argmax(dim=1)
-    elif torch.is_tensor(target_class):
-        target = target_class.to(device).long()
-    else:
-        target = torch.full((N,), int(target_class), device=device, dtype=torch.long)
     scorer = CamFaithfulness(model, device, **kw)
     out = {}
     for method in methods:

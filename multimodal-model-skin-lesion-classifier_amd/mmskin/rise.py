@@ -23,8 +23,8 @@ import torch
 
 from . import ops
 from ._lib import MMSkinError
-from .cam import ScoreCAM, _check_rows
-from .faithfulness import BASELINES, _take_rows
+from ._image_explainer import (Baseline, check_images, check_rows, check_target_range, chunk_or_default, chunked_logits,
+                               model_device, require_eval, target_tensor)
 
 NORMALIZE = ("expected", "coverage")
 
@@ -61,72 +61,47 @@ class RISE:
         if not 1 <= self.n_masks <= ops.RISE_MAX_MASKS:
             raise ValueError(f"RISE: n_masks must be in 1 .. {ops.RISE_MAX_MASKS}, got {n_masks}")
         self.seed, self.grid, self.p1 = ops._rise_args(seed, grid, p1, "RISE")
-        if baseline not in BASELINES:
-            raise ValueError(f"RISE: baseline must be one of {BASELINES}, got {baseline!r}")
-        self.baseline = baseline
         if normalize not in NORMALIZE:
             raise ValueError(f"RISE: normalize must be one of {NORMALIZE}, got {normalize!r}")
         self.normalize = normalize
-        self.taps = ops.gaussian_taps(blur_ksize, blur_sigma) if baseline == "blur" else None
-        self.chunk = int(chunk) if chunk is not None else ScoreCAM.default_chunk
-        if self.chunk < 1:
-            raise ValueError(f"RISE: chunk must be >= 1, got {chunk}")
+        self._baseline = Baseline("RISE", baseline, blur_ksize, blur_sigma)
+        self.baseline, self.taps = baseline, self._baseline.taps
+        self.chunk = chunk_or_default(chunk, "RISE")
 
     def baseline_images(self, images):
         """images [N, 3, H, W] fp32 on the device -> the baseline of every image, same shape"""
-        if self.baseline == "blur":
-            return ops.faith_blur(images, self.taps)
-        if self.baseline == "mean":
-            return ops.faith_mean(images)
-        return torch.zeros_like(images)
+        return self._baseline.images(images)
 
     def generate_batch(self, images, metadata, target_class=None):
         """images (N, 3, H, W) as the model takes them; metadata (N, V) or a mapping of such tensors; target_class an int, an
         int tensor (N,), or None = the argmax of the clean forward, taken on the device -> RiseResult."""
         who = "RISE.generate_batch"
-        if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != 3 or images.shape[0] < 1:
-            raise ValueError(f"{who}: images must have shape (N, 3, H, W), got "
-                             f"{tuple(images.shape) if torch.is_tensor(images) else type(images).__name__}")
+        check_images(images, who)
         N, _, H, W = images.shape
-        _check_rows(metadata, N, who)
-        if torch.is_tensor(target_class) and (target_class.dim() != 1 or target_class.shape[0] != N or target_class.is_floating_point()):
-            raise ValueError(f"{who}: target_class must be an int, None or an int tensor [{N}], got "
-                             f"{target_class.dtype} {tuple(target_class.shape)}")
-        if self.model.training:
-            raise MMSkinError("RISE runs in eval mode: call model.eval() first")
+        check_rows(metadata, N, who)
+        dev = self.device
+        target = target_tensor(target_class, N, dev, who)
+        require_eval(self.model, "RISE")
         if H * W > ops.faith_max_pixels():
             raise MMSkinError(f"{who}: {H}x{W} images are above the kernels' cap of {ops.faith_max_pixels()} pixels")
-        dev = self.device
-        target = None
-        if target_class is not None:
-            if torch.is_tensor(target_class):
-                target = target_class.to(dev).to(torch.int32).contiguous()
-            else:
-                target = torch.full((N,), int(target_class), device=dev, dtype=torch.int32)
 
         images = images.detach().to(dev).float().contiguous()
         base = self.baseline_images(images)
         n_masks, chunk = self.n_masks, self.chunk
         R = N * n_masks
-        n_chunks = -(-R // chunk)
-        row_image = torch.arange(n_chunks * chunk, device=dev).div_(n_masks, rounding_mode="floor").clamp_(max=N - 1)
-        masked = torch.empty((chunk, 3, H, W), device=dev, dtype=torch.float32)
+        row_image = torch.arange(-(-R // chunk) * chunk, device=dev).div_(n_masks, rounding_mode="floor").clamp_(max=N - 1)
         with torch.no_grad():
             clean = self.model(images, metadata)
-            if clean.dim() != 2 or clean.shape[0] != N:
-                raise MMSkinError(f"{who}: the model must return logits of shape ({N}, K), got {tuple(clean.shape)}")
-            clean = clean.float().contiguous()
-            K = clean.shape[1]
-            logits = torch.empty((n_chunks * chunk, K), device=dev, dtype=torch.float32)
-            for c in range(n_chunks):
-                r0 = c * chunk
-                ops.rise_apply(images, base, self.seed, self.grid, self.p1, n_masks, r0, min(chunk, R - r0), chunk, out=masked)
-                out = self.model(masked, _take_rows(metadata, row_image[r0:r0 + chunk]))
-                if out.dim() != 2 or tuple(out.shape) != (chunk, K):
-                    raise MMSkinError(f"{who}: the model must return logits of shape ({chunk}, {K}), got {tuple(out.shape)}")
-                logits[r0:r0 + chunk] = out                              # the padded rows' logits are never read
-        if target is not None and bool(((target < 0) | (target >= K)).any()):       # checked where the tensor lives
-            raise ValueError(f"{who}: target_class has entries outside 0 .. {K - 1}")
+        if clean.dim() != 2 or clean.shape[0] != N:
+            raise MMSkinError(f"{who}: the model must return logits of shape ({N}, K), got {tuple(clean.shape)}")
+        clean = clean.float().contiguous()
+        K = clean.shape[1]
+
+        def write_chunk(r0, n, out):
+            return ops.rise_apply(images, base, self.seed, self.grid, self.p1, n_masks, r0, n, chunk, out=out)
+
+        logits = chunked_logits(self.model, metadata, row_image, R, chunk, write_chunk, who, K)
+        check_target_range(target, K, who)
         total, coverage, clean_prob, used = ops.rise_accumulate(logits, clean, (H, W), self.seed, self.grid, self.p1, n_masks, target)
         if self.normalize == "expected":
             saliency = total / (n_masks * self.p1)
@@ -137,9 +112,7 @@ class RISE:
     def generate(self, image, metadata, target_class=None):
         """image (1, 3, H, W), metadata of one row -> np.ndarray [H, W] float32, min-max normalised to [0, 1] (+1e-8 in the
         denominator: a flat map gives zeros): the convention of the CAM classes."""
-        if not torch.is_tensor(image) or image.dim() != 4 or image.shape[0] != 1 or image.shape[1] != 3:
-            raise ValueError(f"RISE.generate: image must have shape (1, 3, H, W), got "
-                             f"{tuple(image.shape) if torch.is_tensor(image) else type(image).__name__}")
+        check_images(image, "RISE.generate", one=True)
         sal = self.generate_batch(image, metadata, target_class).saliency[0]
         lo, hi = sal.min(), sal.max()
         return ((sal - lo) / (hi - lo + 1e-8)).cpu().numpy()
@@ -148,5 +121,5 @@ class RISE:
 def rise_maps(model, images, metadata, target=None, **kw):
     """The RISE maps [N, H, W] (device, fp32) of RISE(model, device, **kw) on `target` (an int, an int tensor [N], or None = the
     model's own prediction; device=... for a model without parameters): what CamFaithfulness.evaluate takes as `saliency`, unchanged."""
-    device = kw.pop("device", None) or getattr(model, "device", None) or next(model.parameters()).device
+    device = kw.pop("device", None) or model_device(model)
     return RISE(model, device, **kw).generate_batch(images, metadata, target).saliency

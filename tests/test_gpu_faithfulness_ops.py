@@ -106,6 +106,83 @@ def test_perturb_matches_the_restatement(H, W):
     assert equal_bits(fresh, want)                                                  # a fresh output buffer takes the same path
 
 
+@pytest.mark.parametrize("H,W", [(7, 9), (32, 33), (36, 36)])
+def test_perturb_tile_shared_with_rise_apply(H, W):
+    """The pixel tile and the blend that faith_perturb shares with rise_apply (csrc/perturb_tile.h), at the shapes of
+    test_gpu_rise_ops.test_apply_tile_matches_the_restatement_bit_for_bit.  The test above already holds both paths, a NaN
+    saliency and the zero padding to the restatement; new here: a 16-byte path whose second tile is mostly empty (32x33: 1056
+    pixels) or partly filled (36x36: 1296), a dword path of less than one tile whose pixel count is odd (7x9), an image that is
+    its own baseline (every mode must return it exactly) and a NaN pixel in an image.  Two images, n = 3 rows, n_pad = 5."""
+    N, S, n, n_pad = 2, 4, 3, 5
+    rng = np.random.default_rng(H * W)
+    img = rng.standard_normal((N, 3, H, W)).astype(np.float32)
+    base = rng.standard_normal((N, 3, H, W)).astype(np.float32)
+    base[1] = img[1]
+    img[0, 1, H // 2, W // 3] = np.nan
+    sal = (rng.standard_normal((N, H, W)) * 0.8).astype(np.float32)
+    ranks = fo.rank(sal)
+    rows = np.asarray([(0, 2, fo.DELETION), (0, 0, fo.EXPLANATION), (1, 0, fo.EXPLANATION), (1, 2, fo.INSERTION), (1, 2, fo.DELETION)],
+                      dtype=np.int32)                                                 # the last two are past n: never built
+    dev = [torch.from_numpy(a).to(DEV) for a in (img, base, ranks, sal, rows)]
+    buf = torch.full((n_pad + 2, 3, H, W), SENTINEL, device=DEV)
+    got = ops.faith_perturb(*dev, S, n, n_pad, out=buf[1:1 + n_pad]).cpu().numpy()
+    host = buf.cpu().numpy()
+    assert (host[0] == SENTINEL).all() and (host[-1] == SENTINEL).all(), "bytes outside the n_pad rows were written"
+    want = fo.perturb(img, base, ranks, sal, rows, S, n, n_pad)
+    print(f"{H}x{W}: {int((~((got == want) | (np.isnan(got) & np.isnan(want)))).sum())} of {got.size} values differ")
+    assert equal_bits(got, want)
+    assert not host[1 + n:1 + n_pad].any()                                          # padded rows are exactly zero
+    assert np.array_equal(got[2], img[1])                                           # baseline == image: the blend returns it
+    for mode in (fo.DELETION, fo.INSERTION):                                        # ... and so does the select
+        rows[2, 1:] = (2, mode)
+        assert np.array_equal(ops.faith_perturb(*dev[:4], torch.from_numpy(rows).to(DEV), S, n, n_pad).cpu().numpy()[2], img[1])
+    assert np.isnan(got[1, 1, H // 2, W // 3]) and int(np.isnan(got[1]).sum()) == 1   # the blend keeps the NaN pixel, and only it
+
+
+def first_largest(row):
+    """the arg-max rule of csrc/target_prob.h: the first largest logit, where a NaN is never larger"""
+    t, best = 0, row[0]
+    for c in range(1, len(row)):
+        if row[c] > best or (best != best and row[c] == row[c]):
+            t, best = c, row[c]
+    return t
+
+
+@pytest.mark.parametrize("K", [1, 2, 7])
+def test_target_and_clean_probability_are_the_ones_rise_uses(K):
+    """faith_curves and rise_accumulate take the class and the clean probability from the same two device functions
+    (csrc/target_prob.h): on the same clean logits both must return the same target and bitwise the same probability.  Rows: a
+    tie for the maximum between the first and the last class, a NaN first logit, an all-NaN row, +inf and -inf, an ordinary
+    row.  Faithfulness gets S = 1 with every row of an image equal to its clean row; RISE one mask on an 8x8 image with the
+    masked logits equal to the clean ones.  target None and a given target out of range on both sides (clamped)."""
+    import rise_oracle as ro
+    N, S = 5, 1
+    clean = (np.random.default_rng(K).standard_normal((N, K)) * 3).astype(np.float32)
+    clean[0, 0] = clean[0, -1] = np.abs(clean[0]).max() + 1
+    clean[1, 0] = np.nan
+    clean[2, :] = np.nan
+    clean[3, 0], clean[3, -1] = np.inf, -np.inf
+    cd = torch.from_numpy(clean).to(DEV)
+    rows = torch.from_numpy(np.repeat(clean, 2 * S + 3, axis=0)).to(DEV)
+    for target in (None, [-3, K, K + 5, 0, 100]):
+        td = None if target is None else torch.tensor(target, dtype=torch.int32, device=DEV)
+        curves, _, _, used_f = ops.faith_curves(rows, S, N, td)
+        _, _, clean_prob, used_r = ops.rise_accumulate(cd, cd, (8, 8), 9, 2, 0.5, 1, td)
+        used = used_f.cpu().numpy()
+        assert np.array_equal(used, used_r.cpu().numpy())
+        assert used.tolist() == ([first_largest(r) for r in clean] if target is None else np.clip(target, 0, K - 1).tolist())
+        p_f, p_r = curves[0, :, 0].cpu().numpy(), clean_prob.cpu().numpy()
+        assert equal_bits(p_f, p_r)
+        with np.errstate(all="ignore"):
+            wants = (fo.curves(rows.cpu().numpy(), S, N, used.tolist())["deletion"][:, 0], ro.probabilities(clean, used))
+        for want in wants:
+            assert np.array_equal(np.isnan(p_f), np.isnan(want))
+            err = float(np.nanmax(np.abs(p_f - want), initial=0.0))
+            print(f"K {K} target {'given' if target else 'argmax'}: max |p - restatement| {err:.3e}")
+            assert err == 0.0                    # measured: exact on these rows.  Should a later exp differ in its last ulps, the
+                                                 # bound to fall back on is test_curves_match_the_restatement's 1e-12
+
+
 @pytest.mark.parametrize("N", [1, 3])
 @pytest.mark.parametrize("S", [1, 8])
 @pytest.mark.parametrize("C", [2, 6])

@@ -74,6 +74,33 @@ def test_apply_matches_the_fp64_oracle(H, W, g, mask_sets):
     assert np.array_equal(again, got)                                               # repeatable; a fresh buffer takes the same path
 
 
+@pytest.mark.parametrize("H,W", [(7, 9), (32, 33), (36, 36)])
+def test_apply_tile_matches_the_restatement_bit_for_bit(H, W):
+    """The pixel tile and the blend that rise_apply shares with faith_perturb (csrc/perturb_tile.h), bit for bit against
+    rise_oracle.apply in fp32 (the test above holds the kernel to the fp64 formula only).  7x9: 63 pixels, no multiple of 4 and
+    less than one tile of 1024: the dword path.  32x33: 1056 pixels, the 16-byte path with a second tile that is mostly empty
+    (threads whose first pixel lies past the end).  36x36: 1296 pixels, two tiles of the 16-byte path.  Two images, rows 1 .. 3
+    of two masks each (image 0 once, image 1 twice), two padded rows.  Image 1 is its own baseline, so its rows must come back
+    exactly; image 0 has one NaN pixel."""
+    g, n_masks, r0, n, n_pad = 4, 2, 1, 3, 5
+    rng = np.random.default_rng(H * W)
+    img = rng.standard_normal((2, 3, H, W)).astype(np.float32)
+    base = rng.standard_normal((2, 3, H, W)).astype(np.float32)
+    base[1] = img[1]
+    img[0, 1, H // 2, W // 3] = np.nan
+    want = ro.apply(img, base, SEED, g, P1, n_masks, r0, n, n_pad)
+    buf = torch.full((n_pad + 2, 3, H, W), SENTINEL, device=DEV)
+    got = ops.rise_apply(torch.from_numpy(img).to(DEV), torch.from_numpy(base).to(DEV), SEED, g, P1, n_masks, r0, n, n_pad,
+                         out=buf[1:1 + n_pad]).cpu().numpy()
+    host = buf.cpu().numpy()
+    assert (host[0] == SENTINEL).all() and (host[-1] == SENTINEL).all(), "bytes outside the n_pad rows were written"
+    print(f"{H}x{W}: {int((~((got == want) | (np.isnan(got) & np.isnan(want)))).sum())} of {got.size} values differ")
+    assert got.dtype == want.dtype and np.array_equal(got, want, equal_nan=True)
+    assert not host[1 + n:1 + n_pad].any()                                          # padded rows are exactly zero
+    assert np.array_equal(got[1], img[1]) and np.array_equal(got[2], img[1])        # baseline == image: the blend returns it
+    assert int(np.isnan(got).sum()) == 1 and np.isnan(got[0, 1, H // 2, W // 3])
+
+
 @pytest.mark.parametrize("n_masks", [1, 5, 67])
 @pytest.mark.parametrize("H,W,g", SHAPES)
 def test_accumulate_matches_the_oracle(H, W, g, n_masks, mask_sets):
