@@ -1343,6 +1343,72 @@ int mmskin_risk_coverage(const double* score, const uint8_t* wrong, int N, int32
 int mmskin_risk_coverage_summary(const int32_t* counts, const uint8_t* wrong, int N, double* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Split-conformal prediction sets of a fold (csrc/conformal.hip, mmskin.conformal.ConformalPredictor).  probs [N][C] are soft-max
+ * rows, fp32 or fp64 (probs_fp64 != 0), no NaN (the caller checks); labels int64 [N] in [0, C) (the caller drops other rows; one
+ * outside is never followed as an index and counts nowhere).  2 <= C <= MMSKIN_CONFORMAL_MAX_CLASSES; a study and a fit hold
+ * 1 <= N <= MMSKIN_CONFORMAL_MAX_ROWS rows, score and apply 1 .. 2^24; 1 <= R <= MMSKIN_BOOTSTRAP_MAX_RESAMPLES.
+ *
+ * The order of a row (csrc/conformal_order.h): class a stands above class b iff p_a > p_b, or p_a == p_b and a < b; rank(c) = 1 +
+ * the number of classes above c.  The scores, all fp64 from (double) p, with P(c) = the sum of p over the classes above c added one
+ * by one in rank order, and u the row's number in [0, 1] (below):
+ *   MMSKIN_CONFORMAL_LAC    s(c) = 1 - p_c
+ *   MMSKIN_CONFORMAL_APS    s(c) = P(c) + u p_c
+ *   MMSKIN_CONFORMAL_RAPS   s(c) = (P(c) + u p_c) + lam max(0, rank(c) - k_reg), lam >= 0, k_reg >= 0
+ * randomized == 0: u = 1.  Otherwise, with key = mix64(seed) (mix64 as under LIME above), row i of the call has
+ * u = (mix64(key ^ (0xFFFFFFFF << 32 | (uint32) (row0 + i))) >> 11) 2^-53.  No product or sum is fused.  Class c is in the set
+ * of a row iff s(c) <= qhat[c]; qhat[c] = +inf admits class c always.
+ * conformal_score: score fp64 [N][C], rank uint8 [N][C] (either may be NULL), and, with a workspace, the scores class-major inside
+ * it for conformal_study / conformal_fit (then N <= MMSKIN_CONFORMAL_MAX_ROWS).
+ * conformal_apply: mask uint64 [M] (bit c = class c is in the set) and size int32 [M] = its population, from qhat fp64 [C] on the
+ * device.
+ *
+ * conformal_study, replicates [r0, r1) of R, one workgroup each.  The split of replicate r has exactly n_cal calibration rows,
+ * 1 <= n_cal <= N - 1.  Replicate 0 is the identity order: the rows 0 .. n_cal - 1.  Replicate r >= 1: u_i = mix64(key ^
+ * ((uint64) r << 32 | i)) >> 32, and the calibration rows are the n_cal rows with the smallest (u_i, i) (the 48-bit key u_i << 16 |
+ * i; keys are distinct).  MMSKIN_CONFORMAL_STRATIFIED: the same per class, over the rows of class c (members [N] int32 = the rows
+ * in ascending (label, row) order, class_start [C + 1] int32), taking cal_count[c] of them (int32 [C], the caller's; replicate 0:
+ * the first cal_count[c] members of the class).  mmskin.conformal.cal_counts states the rule: floor(n_cal n_c / N) each, and
+ * one more for the n_cal - sum classes with the largest remainder n_cal n_c mod N, a tie going to the lower class.
+ * The threshold: qhat = the k-th smallest true-label score s_i(y_i) over the n calibration rows, k = ceil((n + 1)(1 - alpha))
+ * evaluated in fp64 as written, 0 < alpha < 1; k > n gives +inf.  An order statistic, never interpolated.  order [N] int32 lists
+ * the rows by ascending (s_i(y_i), i).  MMSKIN_CONFORMAL_MONDRIAN: one qhat[c] per class from the calibration rows of class c
+ * (n = their number; none: +inf); order then lists the rows by ascending (y_i, s_i(y_i), i) and class_start is read.
+ * It WRITES, once per replicate, qhat fp64 [R][C] (the same value C times unless Mondrian) and counts int64 [R][8 + 5 C] over
+ * the test rows: 0 n_test, 1 covered (y in the set), 2 the total set size, 3 empty sets, 4 singleton sets, 5 singleton sets that
+ * are {y}, then hist[C + 1] (sets per size), size_covered[C + 1] (covered rows per set size), class_rows[C] (test rows per true
+ * class), class_covered[C], class_in[C] (the sets that hold class c).  All integer LDS atomics and ballots: bitwise repeatable, and
+ * a function of (inputs, seed, options, r) alone -- not of R, of the range of a call, or of the launch shape.
+ * conformal_fit: qhat fp64 [C] with every row calibrating (n = N; flags: MMSKIN_CONFORMAL_MONDRIAN or 0).
+ * conformal_finalize: metrics fp64 [M][R], M = mmskin_conformal_metric_columns(C) = 6 + 2 C, inside the workspace: 0 coverage =
+ * covered / n_test, 1 mean set size, 2 singleton rate, 3 singleton accuracy (NaN without a singleton), 4 empty rate, 5 the worst
+ * class coverage over the classes with a test row, 6 + c the coverage of class c (NaN without a test row), 6 + C + c qhat[c];
+ * summary fp64 [5][M] is that of bootstrap_finalize above (an infinite qhat gives an infinite mean and a NaN std).
+ * workspace: mmskin_conformal_workspace_bytes(N, C, R) bytes (-1 out of range), one buffer for score, study / fit and finalize.
+ * Errors (nothing is launched, no GPU needed), all MMSKIN_ERR_ARG with the field's name in the message: num_classes, n_rows,
+ * n_resamples, alpha, n_cal, score, k_reg, lam, row0, flags, a range outside [0, R], quantiles out of order, a null argument. */
+#define MMSKIN_CONFORMAL_MAX_ROWS 32768
+#define MMSKIN_CONFORMAL_MAX_CLASSES 64
+#define MMSKIN_CONFORMAL_LAC 0
+#define MMSKIN_CONFORMAL_APS 1
+#define MMSKIN_CONFORMAL_RAPS 2
+#define MMSKIN_CONFORMAL_STRATIFIED 1
+#define MMSKIN_CONFORMAL_MONDRIAN 2
+int mmskin_conformal_count_columns(int C);
+int mmskin_conformal_metric_columns(int C);
+int64_t mmskin_conformal_workspace_bytes(int N, int C, int R);
+int mmskin_conformal_score(const void* probs, int probs_fp64, int64_t N, int C, int kind, int randomized, double lam, int k_reg,
+                           uint64_t seed, int64_t row0, double* score, uint8_t* rank, void* workspace, void* stream);
+int mmskin_conformal_apply(const void* probs, int probs_fp64, int64_t M, int C, int kind, int randomized, double lam, int k_reg,
+                           uint64_t seed, int64_t row0, const double* qhat, uint64_t* mask, int32_t* size, void* stream);
+int mmskin_conformal_study(uint64_t seed, int N, int C, int R, int n_cal, double alpha, int flags, const int64_t* labels,
+                           const int32_t* order, const int32_t* members, const int32_t* class_start, const int32_t* cal_count,
+                           int r0, int r1, const void* workspace, double* qhat, int64_t* counts, void* stream);
+int mmskin_conformal_fit(int N, int C, double alpha, int flags, const int64_t* labels, const int32_t* order,
+                         const int32_t* class_start, const void* workspace, double* qhat, void* stream);
+int mmskin_conformal_finalize(const int64_t* counts, const double* qhat, int N, int C, int R, double q_lo, double q_hi, void* workspace,
+                              double* summary, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * `custom-cnn` image encoder pieces (loadImageModelClassifier.py:50-60): small direct kernels for
  * shapes the MFMA implicit GEMM does not cover (Cin=3, Cout=16).  NCHW fp32. */
 int mmskin_direct_conv2d_forward(const float* x, const float* w, const float* b, float* y, int N, int Cin, int H, int W,

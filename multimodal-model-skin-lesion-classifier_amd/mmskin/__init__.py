@@ -7,6 +7,7 @@ Layout:
 """
 from . import _lib, criterion, evaluate  # noqa: F401
 from .calibration import Calibration, TemperatureScaling  # noqa: F401
+from .conformal import ConformalPredictor, ConformalReport  # noqa: F401
 from .curves import FoldCurves  # noqa: F401
 from .criterion import CrossEntropyLoss, EpochMeter, FocalLoss, SoftTargetCrossEntropy  # noqa: F401
 from .evaluate import evaluate_model  # noqa: F401
@@ -14,4 +15,5 @@ from .permutation import MetadataPermutationImportance  # noqa: F401
 from .uncertainty import PredictiveUncertainty  # noqa: F401
 
 __all__ = ["_lib", "criterion", "evaluate", "CrossEntropyLoss", "FocalLoss", "SoftTargetCrossEntropy", "EpochMeter", "evaluate_model",
-           "MetadataPermutationImportance", "Calibration", "TemperatureScaling", "FoldCurves", "PredictiveUncertainty"]
+           "MetadataPermutationImportance", "Calibration", "TemperatureScaling", "FoldCurves", "PredictiveUncertainty", "ConformalPredictor",
+           "ConformalReport"]

@@ -255,6 +255,14 @@ _SIGNATURES = {
     "mmskin_uncertainty_reduce": (_i, [_P, _i64, _i64, _i, _i, _i] + [_P] * 5 + [_P]),
     "mmskin_risk_coverage": (_i, [_P, _P, _i, _P, _P]),
     "mmskin_risk_coverage_summary": (_i, [_P, _P, _i, _P, _P]),
+    "mmskin_conformal_count_columns": (_i, [_i]),
+    "mmskin_conformal_metric_columns": (_i, [_i]),
+    "mmskin_conformal_workspace_bytes": (_i64, [_i, _i, _i]),
+    "mmskin_conformal_score": (_i, [_P, _i, _i64, _i, _i, _i, _d, _i, _u64, _i64, _P, _P, _P, _P]),
+    "mmskin_conformal_apply": (_i, [_P, _i, _i64, _i, _i, _i, _d, _i, _u64, _i64, _P, _P, _P, _P]),
+    "mmskin_conformal_study": (_i, [_u64, _i, _i, _i, _i, _d, _i] + [_P] * 5 + [_i, _i, _P, _P, _P, _P]),
+    "mmskin_conformal_fit": (_i, [_i, _i, _d, _i] + [_P] * 6),
+    "mmskin_conformal_finalize": (_i, [_P, _P, _i, _i, _i, _d, _d, _P, _P, _P]),
     "mmskin_pool_gap_forward":(_i, [_P] * 3 + [_i] * 5 + [_P]),
     "mmskin_pool_gap_backward": (_i, [_P] * 3 + [_i] * 5 + [_P]),
     "mmskin_star_relu_forward_bf16": (_i, [_P] * 4 + [_i64, _i, _i, _P]),

@@ -156,6 +156,12 @@ def _checked_scores(what, scores, labels, probabilities):
     return s.contiguous(), y.contiguous()
 
 
+def read_fold_dir(path):
+    """(probs fp32 [N, K], labels [N]) from the probabilities.npy and labels.npy that evaluate_model wrote into `path`"""
+    load = lambda name: np.load(os.path.join(path, name))
+    return load("probabilities.npy").astype(np.float32, copy=False), load("labels.npy")
+
+
 def _device_of(t):
     if not torch.cuda.is_available():
         return None
@@ -222,8 +228,7 @@ class Calibration:
 
     def from_fold_dir(self, path, **study):
         """`evaluate` on the probabilities.npy and labels.npy that evaluate_model wrote into `path`"""
-        load = lambda name: np.load(os.path.join(path, name))
-        return self.evaluate(load("probabilities.npy").astype(np.float32, copy=False), load("labels.npy"), **study)
+        return self.evaluate(*read_fold_dir(path), **study)
 
 
 class TemperatureScaling:
