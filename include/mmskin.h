@@ -1113,6 +1113,65 @@ int mmskin_bootstrap_compare(const double* metrics_a, const double* metrics_b, i
                              double* summary, int64_t* sign_counts, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Subgroup audit of a fold (csrc/subgroup.hip, mmskin.subgroup.SubgroupAudit): the bootstrap above scored per group of rows, so
+ * that a group's replicate, another group's and the fold's are ONE resample and their differences are paired.  scores, labels,
+ * preds, modes, the generator, members and class_start are those of the bootstrap section.  groups int32 [N], read in place: the
+ * group of each row; an id outside [0, G) puts the row in no group -- it is still drawn and still carries weight, it is counted
+ * nowhere.  1 <= N <= MMSKIN_SUBGROUP_MAX_ROWS, 2 <= K <= MMSKIN_BOOTSTRAP_MAX_CLASSES, 1 <= G <= MMSKIN_SUBGROUP_MAX_GROUPS,
+ * G K K <= MMSKIN_SUBGROUP_MAX_CELLS, 1 <= B <= MMSKIN_BOOTSTRAP_MAX_RESAMPLES.  (N = 8192, G = 16, K = 8) and (N = 8192, G = 4,
+ * K = 64) lie inside.
+ *
+ * The weights w_b are exactly those of mmskin_bootstrap_weights for the same (seed, mode, N, labels), in all three modes: they
+ * depend neither on groups nor on G (one piece of code draws both).
+ *
+ * The caller's tables, all int32 on the device (mmskin.ops.subgroup_tables builds them with device sorts), with
+ * key(i) = groups[i] if it lies in [0, G), else G:
+ *   order [K][N]        order[c][q] = the row at position q when the rows are sorted by (key, scores[.][c]), ascending
+ *   lo, hi [K][N]       the tie group of position q in that order: the positions lo[c][q] <= x < hi[c][q] hold the rows with the
+ *                       key AND the score of position q, 0 <= lo <= q < hi <= N.  A tie group never crosses a group boundary.
+ *   group_start [G + 1] group g owns the positions group_start[g] .. group_start[g + 1] of every class's order;
+ *                       group_start[0] = 0, and the rows in no group lie from group_start[G] to N
+ *   members, class_start as for the bootstrap (stratified mode only; may be NULL otherwise).
+ * An entry out of range is skipped, never followed: a row index outside [0, N) counts nothing, a position <= 0 is read as "no
+ * negative before it" and a position >= N as "every negative before it".
+ *
+ * subgroup_replicates: for each replicate b of [b0, b1) it WRITES, once, and nothing outside those slices:
+ *   confusion int32 [B][G][K][K]  confusion[b][g][y][p] = the sum of w_b[i] over the rows of group g with label y and prediction p
+ *   counts    int64 [B][G][3 K]   pos[K], neg[K] (weighted row counts within the group), wins2[K]: wins2[c] = the sum over (i with
+ *                                 label c, j with another label, BOTH in group g) of w_b[i] w_b[j] (2 [s[i][c] > s[j][c]] +
+ *                                 [s[i][c] == s[j][c]]), the pair rule of mmskin_ovr_auc_counts below
+ * One workgroup per replicate; one prefix scan per class serves all G groups (a positive of group g at position q adds
+ * w_q (P[lo_q] + P[hi_q] - 2 P[group_start[g]])); integer LDS atomics and single-owner sums: bitwise repeatable and independent
+ * of how [0, B) is cut into calls.  With G = 1 and every row in group 0 the integers are those of mmskin_bootstrap_replicates.
+ *
+ * subgroup_finalize: metrics fp64 [G][M][B], M = mmskin_subgroup_metric_columns(K) = 7 + 4 K, column m of group g and replicate b
+ * at metrics[(g M + m) B + b].  With n_g = sum_c pos[c] the group's weighted row count: columns 0 .. 7 + 2 K - 1 are the bootstrap
+ * columns above on the group's integers (one device function computes both), 7 + 2 K + c the false-positive rate of class c =
+ * (sum_y conf[y][c] - conf[c][c]) / (n_g - pos[c]), 7 + 3 K + c the predicted rate of class c = sum_y conf[y][c] / n_g; a zero
+ * denominator gives NaN.  A group with n_g < min_rows (min_rows >= 1) in replicate b is NaN in every column of that replicate.
+ * summary fp64 [G][5][M]: per group the summary of bootstrap_finalize.
+ *
+ * subgroup_gaps: metrics fp64 [G][M][B] (any M in 1 .. 7 + 4 MMSKIN_BOOTSTRAP_MAX_CLASSES) -> per column m and replicate b, over
+ * the groups that are not NaN there: lowest, highest fp64 [M][B] (NaN when no group is defined), gap = highest - lowest (NaN when
+ * fewer than two groups are defined); lowest_group int64 [M][G] = the number of replicates in which g is the lowest, ties going to
+ * the smallest id; summary fp64 [3][5][M] for lowest, highest and gap.  Differences of two groups, of a group and the fold, or of
+ * two models' gaps are two [M][B] tables through mmskin_bootstrap_compare.
+ * Errors (nothing is launched, no GPU needed): an extent outside its limit is MMSKIN_ERR_UNSUPPORTED with the limit's name in the
+ * message; an unknown mode, a range outside [0, B], quantiles out of order, min_rows < 1, a null argument are MMSKIN_ERR_ARG. */
+#define MMSKIN_SUBGROUP_MAX_ROWS 8192
+#define MMSKIN_SUBGROUP_MAX_GROUPS 64
+#define MMSKIN_SUBGROUP_MAX_CELLS 16384
+int mmskin_subgroup_metric_columns(int K);
+int mmskin_subgroup_replicates(uint64_t seed, int mode, int N, int K, int G, int B, const int64_t* labels, const int64_t* preds,
+                               const int32_t* groups, const int32_t* members, const int32_t* class_start, const int32_t* order,
+                               const int32_t* lo, const int32_t* hi, const int32_t* group_start, int b0, int b1, int32_t* confusion,
+                               int64_t* counts, void* stream);
+int mmskin_subgroup_finalize(const int32_t* confusion, const int64_t* counts, int B, int G, int K, int64_t min_rows, double q_lo,
+                             double q_hi, double* metrics, double* summary, void* stream);
+int mmskin_subgroup_gaps(const double* metrics, int B, int G, int M, double q_lo, double q_hi, double* lowest, double* highest,
+                         double* gap, int64_t* lowest_group, double* summary, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Calibration of a fold's probabilities (csrc/calibration.hip, mmskin.calibration.Calibration / TemperatureScaling): reliability
  * tables as exact integers, ECE / MCE / class-wise ECE, Brier score and NLL, their bootstrap, and post-hoc temperature scaling.
  * probs fp32 [N][K] are soft-max rows (0 <= p <= 1, no NaN: the caller checks); labels int64 [N], read in place, in [0, K) (the

@@ -23,6 +23,7 @@
 //   compare     the same on d = a - b of two metric tables, plus the counts of d <= 0 and d >= 0 (integer LDS atomics).
 #include "../../include/mmskin.h"
 #include "auc_pairs.h"
+#include "bootstrap_core.h"
 #include "column_summary.h"
 #include "common.h"
 
@@ -30,11 +31,7 @@
 
 namespace {
 
-constexpr int MAX_N = MMSKIN_BOOTSTRAP_MAX_ROWS;         // 16384
-constexpr int MAX_K = MMSKIN_BOOTSTRAP_MAX_CLASSES;      // 64
-constexpr int MAX_B = MMSKIN_BOOTSTRAP_MAX_RESAMPLES;    // 8192
-constexpr int MAX_WAVES = 16;                            // 1024 threads
-constexpr int NO_LABEL = 0xFF;
+constexpr int MAX_N = MMSKIN_BOOTSTRAP_MAX_ROWS;         // 16384; MAX_K, MAX_B, MAX_WAVES, NO_LABEL: bootstrap_core.h
 
 // Dynamic LDS of the replicates kernel, in bytes, for N rows (Np = N rounded up to 4):
 //   w      int32 [Np]                      the replicate's weights
@@ -46,52 +43,7 @@ inline size_t p_cells(int N, int K) { return (size_t)(((N + 3) & ~3) > K * K ? (
 inline size_t replicate_lds_bytes(int N, int K) { return ((size_t)((N + 3) & ~3) + p_cells(N, K)) * 4 + (size_t)((N + 3) & ~3); }
 static_assert(((size_t)MAX_N + MAX_N) * 4 + MAX_N + 708 <= 160 * 1024, "the limits must fit one workgroup's LDS");
 
-__device__ __forceinline__ uint32_t draw_u(uint64_t key, uint64_t b, int t) { return (uint32_t)(mix64(key ^ ((b << 32) | (uint64_t)(uint32_t)t)) >> 32); }
-
-__device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, o, 64), hi = __shfl_xor((uint32_t)((uint64_t)v >> 32), o, 64);
-    v += (int64_t)(((uint64_t)hi << 32) | lo);
-  }
-  return v;
-}
-
-// labels -> LDS bytes (NO_LABEL outside [0, K)), class_start -> LDS; ends with a barrier
-__device__ __forceinline__ void stage_labels(const int64_t* __restrict__ labels, const int32_t* __restrict__ class_start, int N, int K,
-                                             int mode, uint8_t* s_lab, int32_t* s_start) {
-  for (int i = threadIdx.x; i < N; i += blockDim.x) {
-    const int64_t y = labels[i];
-    s_lab[i] = (uint8_t)((y >= 0 && y < K) ? (int)y : NO_LABEL);
-  }
-  if (mode == MMSKIN_BOOTSTRAP_STRATIFIED)
-    for (int c = threadIdx.x; c <= K; c += blockDim.x) s_start[c] = class_start[c];
-  __syncthreads();
-}
-
-// phase 1: w[0 .. N) of replicate b; ends with a barrier.  Every index into w is checked: a table entry out of range draws nothing.
-__device__ __forceinline__ void build_weights(uint64_t key, uint64_t b, int mode, int N, const int32_t* __restrict__ members,
-                                              const uint8_t* s_lab, const int32_t* s_start, int32_t* s_w) {
-  const int tid = threadIdx.x, nt = blockDim.x;
-  for (int i = tid; i < N; i += nt) s_w[i] = mode == MMSKIN_BOOTSTRAP_POINT ? 1 : 0;
-  __syncthreads();
-  if (mode == MMSKIN_BOOTSTRAP_PLAIN) {
-    for (int t = tid; t < N; t += nt) {
-      const int row = (int)(((uint64_t)draw_u(key, b, t) * (uint64_t)N) >> 32);       // < N
-      atomicAdd(&s_w[row], 1);
-    }
-  } else if (mode == MMSKIN_BOOTSTRAP_STRATIFIED) {
-    for (int t = tid; t < N; t += nt) {
-      const int c = s_lab[t];
-      if (c == NO_LABEL) continue;
-      const int s = s_start[c], n = s_start[c + 1] - s;
-      if (s < 0 || n < 1 || s + n > N) continue;
-      const int row = members[s + (int)(((uint64_t)draw_u(key, b, t) * (uint64_t)n) >> 32)];
-      if ((unsigned)row < (unsigned)N) atomicAdd(&s_w[row], 1);
-    }
-  }
-  __syncthreads();
-}
+// The generator, stage_labels and build_weights (phase 1), wave_sum_i64 and metric_columns: bootstrap_core.h, shared with subgroup.hip.
 
 // ------------------------------------------------------------------------------------------------ weights
 __global__ __launch_bounds__(1024) void bootstrap_weights_kernel(uint64_t key, int mode, int N, int K, const int64_t* __restrict__ labels,
@@ -220,55 +172,12 @@ __global__ __launch_bounds__(256) void bootstrap_metrics_kernel(const int32_t* _
                                                                 int B, int K, double* __restrict__ metrics) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= B) return;
-  const int32_t* cm = confusion + (int64_t)b * K * K;
-  const int64_t* cnt = counts + (int64_t)b * 3 * K;
-  const double nan = nan64();
-  double* col = metrics + b;                                       // column m of replicate b: col[m B]
-  int64_t n = 0, hits = 0;
-  for (int e = 0; e < K * K; ++e) n += cm[e];
-  double recall_sum = 0.0, wp = 0.0, wr = 0.0, wf = 0.0, p1 = 0.0, r1 = 0.0, f1 = 0.0;
-  int present = 0;
-  for (int c = 0; c < K; ++c) {
-    int64_t true_n = 0, pred_n = 0;
-    for (int k = 0; k < K; ++k) { true_n += cm[c * K + k]; pred_n += cm[k * K + c]; }
-    const double tp = (double)cm[c * K + c];
-    hits += cm[c * K + c];
-    const double prec = pred_n > 0 ? tp / (double)pred_n : 0.0, rec = true_n > 0 ? tp / (double)true_n : 0.0;
-    const double f = true_n + pred_n > 0 ? 2.0 * tp / (double)(true_n + pred_n) : 0.0;
-    if (true_n > 0) { recall_sum += rec; ++present; }
-    wp += prec * (double)true_n; wr += rec * (double)true_n; wf += f * (double)true_n;
-    if (c == 1) { p1 = prec; r1 = rec; f1 = f; }
-    col[(int64_t)(7 + c) * B] = true_n > 0 ? rec : nan;
-  }
-  col[0] = n > 0 ? (double)hits / (double)n : nan;
-  col[(int64_t)1 * B] = present > 0 ? recall_sum / (double)present : nan;
-  if (K == 2) {
-    col[(int64_t)2 * B] = p1; col[(int64_t)3 * B] = r1; col[(int64_t)4 * B] = f1;
-  } else {
-    col[(int64_t)2 * B] = n > 0 ? wp / (double)n : 0.0;
-    col[(int64_t)3 * B] = n > 0 ? wr / (double)n : 0.0;
-    col[(int64_t)4 * B] = n > 0 ? wf / (double)n : 0.0;
-  }
-  double weighted = 0.0, weight = 0.0, plain = 0.0, auc1 = nan;
-  int ranked = 0;
-  for (int c = 0; c < K; ++c) {
-    const double pos = (double)cnt[c], pairs = 2.0 * pos * (double)cnt[K + c];
-    double auc = nan;
-    if (pairs > 0.0) {
-      auc = (double)cnt[2 * K + c] / pairs;
-      weighted += auc * pos; weight += pos; plain += auc; ++ranked;
-    }
-    if (c == 1) auc1 = auc;
-    col[(int64_t)(7 + K + c) * B] = auc;
-  }
-  col[(int64_t)5 * B] = K == 2 ? auc1 : (ranked > 0 ? weighted / weight : nan);
-  col[(int64_t)6 * B] = ranked > 0 ? plain / (double)ranked : nan;
+  metric_columns(confusion + (int64_t)b * K * K, counts + (int64_t)b * 3 * K, K, metrics + b, B);   // column m of replicate b: metrics[m B + b]
 }
 
 // ------------------------------------------------------------------------------------------------ summary
 // n_valid, mean, deviation, the sort and the percentiles of a column: summarize_column of column_summary.h.  Dynamic LDS of a column
-// workgroup: the B values (fp64) and n >= B sort keys (n a power of two, >= 2): at B = 8192, 128 KiB.
-static_assert(((size_t)MAX_B + MAX_B) * 8 + 64 <= 160 * 1024, "a column must fit one workgroup's LDS");
+// workgroup: the B values (fp64) and n >= B sort keys (n a power of two, >= 2): at B = 8192, 128 KiB (asserted in bootstrap_core.h).
 
 __global__ __launch_bounds__(NT_COL) void bootstrap_summary_kernel(const double* __restrict__ metrics, int B, int n, int M, double q_lo,
                                                                    double q_hi, double* __restrict__ summary) {
@@ -307,36 +216,7 @@ __global__ __launch_bounds__(NT_COL) void bootstrap_compare_kernel(const double*
 }
 
 // ------------------------------------------------------------------------------------------------ host
-int study_limits(const char* what, int N, int K, int B) {
-  if (N < 1 || N > MAX_N) {
-    mmskin_set_error("%s: %d rows; a replicate's weights live in LDS, which holds 1 .. MMSKIN_BOOTSTRAP_MAX_ROWS = %d", what, N, MAX_N);
-    return MMSKIN_ERR_UNSUPPORTED;
-  }
-  if (K < 2 || K > MAX_K) {
-    mmskin_set_error("%s: %d classes; the kernels hold 2 .. MMSKIN_BOOTSTRAP_MAX_CLASSES = %d", what, K, MAX_K);
-    return MMSKIN_ERR_UNSUPPORTED;
-  }
-  if (B < 1 || B > MAX_B) {
-    mmskin_set_error("%s: %d replicates; a metric column is sorted in LDS, which holds 1 .. MMSKIN_BOOTSTRAP_MAX_RESAMPLES = %d", what, B,
-                     MAX_B);
-    return MMSKIN_ERR_UNSUPPORTED;
-  }
-  return MMSKIN_OK;
-}
-
-int range_ok(const char* what, int B, int b0, int b1) {
-  ARG_CHECK(b0 >= 0 && b0 <= b1 && b1 <= B, "%s: replicates [%d, %d) are not a range of the study's %d", what, b0, b1, B);
-  return MMSKIN_OK;
-}
-
-int mode_ok(const char* what, int mode) {
-  ARG_CHECK(mode == MMSKIN_BOOTSTRAP_PLAIN || mode == MMSKIN_BOOTSTRAP_STRATIFIED || mode == MMSKIN_BOOTSTRAP_POINT, "%s: unknown mode %d", what,
-            mode);
-  return MMSKIN_OK;
-}
-
-// threads of a replicate's workgroup: more waves where one workgroup fills the CU's LDS alone
-int replicate_threads(int N) { return N <= 4096 ? 256 : (N <= 8192 ? 512 : 1024); }
+// study_limits, range_ok, mode_ok, quantiles_ok, replicate_threads, scan_segment: bootstrap_core.h
 
 }  // namespace
 
@@ -368,20 +248,13 @@ extern "C" int mmskin_bootstrap_replicates(uint64_t seed, int mode, int N, int K
   ARG_CHECK(mode != MMSKIN_BOOTSTRAP_STRATIFIED || (members && class_start), "bootstrap_replicates: stratified resampling needs members and class_start");
   if (b0 == b1) return MMSKIN_OK;
   const int nt = replicate_threads(N), waves = nt / 64;
-  const int seg = ((N + waves - 1) / waves + 63) / 64 * 64;        // positions per wave: a multiple of 64, waves * seg >= N
+  const int seg = scan_segment(N, waves);
   HIP_CHECK_RET(opt_in_dynamic_lds((const void*)bootstrap_replicates_kernel, (int)replicate_lds_bytes(MAX_N, MAX_K)));
   hipLaunchKernelGGL(bootstrap_replicates_kernel, dim3((unsigned)(b1 - b0)), dim3(nt), replicate_lds_bytes(N, K), ST(stream), mix64(seed), mode, N,
                      K, labels, preds, members, class_start, order, lo, hi, b0, seg, confusion, counts);
   HIP_CHECK_RET(hipGetLastError());
   return MMSKIN_OK;
 }
-
-namespace {
-int quantiles_ok(const char* what, double q_lo, double q_hi) {
-  ARG_CHECK(q_lo >= 0.0 && q_lo <= q_hi && q_hi <= 1.0, "%s: the quantiles (%g, %g) must satisfy 0 <= low <= high <= 1", what, q_lo, q_hi);
-  return MMSKIN_OK;
-}
-}  // namespace
 
 extern "C" int mmskin_bootstrap_finalize(const int32_t* confusion, const int64_t* counts, int B, int K, double q_lo, double q_hi,
                                          double* metrics, double* summary, void* stream) {

@@ -12,8 +12,9 @@ from .curves import FoldCurves  # noqa: F401
 from .criterion import CrossEntropyLoss, EpochMeter, FocalLoss, SoftTargetCrossEntropy  # noqa: F401
 from .evaluate import evaluate_model  # noqa: F401
 from .permutation import MetadataPermutationImportance  # noqa: F401
+from .subgroup import SubgroupAudit, group_ids  # noqa: F401
 from .uncertainty import PredictiveUncertainty  # noqa: F401
 
 __all__ = ["_lib", "criterion", "evaluate", "CrossEntropyLoss", "FocalLoss", "SoftTargetCrossEntropy", "EpochMeter", "evaluate_model",
            "MetadataPermutationImportance", "Calibration", "TemperatureScaling", "FoldCurves", "PredictiveUncertainty", "ConformalPredictor",
-           "ConformalReport"]
+           "ConformalReport", "SubgroupAudit", "group_ids"]

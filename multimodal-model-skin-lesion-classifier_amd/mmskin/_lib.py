@@ -234,6 +234,10 @@ _SIGNATURES = {
     "mmskin_bootstrap_replicates": (_i, [_u64, _i, _i, _i, _i] + [_P] * 7 + [_i, _i, _P, _P, _P]),
     "mmskin_bootstrap_finalize": (_i, [_P, _P, _i, _i, _d, _d, _P, _P, _P]),
     "mmskin_bootstrap_compare": (_i, [_P, _P, _i, _i, _d, _d, _P, _P, _P, _P]),
+    "mmskin_subgroup_metric_columns": (_i, [_i]),
+    "mmskin_subgroup_replicates": (_i, [_u64, _i, _i, _i, _i, _i] + [_P] * 9 + [_i, _i, _P, _P, _P]),
+    "mmskin_subgroup_finalize": (_i, [_P, _P, _i, _i, _i, _i64, _d, _d, _P, _P, _P]),
+    "mmskin_subgroup_gaps": (_i, [_P, _i, _i, _i, _d, _d] + [_P] * 6),
     "mmskin_calibration_metric_columns": (_i, [_i]),
     "mmskin_calibration_sums_scratch_doubles": (_i64, [_i, _i]),
     "mmskin_temperature_scratch_doubles": (_i64, [_i, _i]),

@@ -1836,6 +1836,143 @@ def bootstrap_compare(metrics_a, metrics_b, confidence=0.95):
     return delta, summary, sign_counts
 
 
+# ---------------------------------------------------------------------------------------------- subgroup audit of a fold
+SUBGROUP_MAX_ROWS = 8192                                                                     # MMSKIN_SUBGROUP_MAX_* of mmskin.h
+SUBGROUP_MAX_GROUPS = 64
+SUBGROUP_MAX_CELLS = 16384                                                                   # G K K
+SUBGROUP_CLASS_METRICS = BOOTSTRAP_CLASS_METRICS + ("per_class_fpr", "per_class_predicted_rate")   # columns 7 + j K .. 7 + (j + 1) K
+SUBGROUP_GAPS = ("lowest", "highest", "gap")                                                 # the blocks of a gap summary
+
+
+def subgroup_metric_columns(K):
+    return 7 + 4 * int(K)
+
+
+def subgroup_check_limits(what, N=None, K=None, G=None, B=None):
+    """MMSkinError naming the limit that a row, class, group or replicate count breaks (the C entry points check the same)"""
+    if N is not None and not 1 <= N <= SUBGROUP_MAX_ROWS:
+        raise _lib.MMSkinError(f"{what}: {N} rows; a replicate's weights live in LDS, which holds 1 .. SUBGROUP_MAX_ROWS = {SUBGROUP_MAX_ROWS}")
+    bootstrap_check_limits(what, K=K, B=B)
+    if G is not None and not 1 <= G <= SUBGROUP_MAX_GROUPS:
+        raise _lib.MMSkinError(f"{what}: {G} groups; a row's group is a byte in LDS, which holds 1 .. SUBGROUP_MAX_GROUPS = {SUBGROUP_MAX_GROUPS}")
+    if G is not None and K is not None and G * K * K > SUBGROUP_MAX_CELLS:
+        raise _lib.MMSkinError(f"{what}: {G} groups of {K} classes are {G * K * K} confusion cells; LDS holds G K K <= SUBGROUP_MAX_CELLS = "
+                               f"{SUBGROUP_MAX_CELLS}")
+
+
+def subgroup_tables(scores, labels, groups, n_groups, preds=None):
+    """The per-call tables of a grouped fold (mmskin.h): scores, labels and preds as for bootstrap_tables, groups integer [N] on the
+    same device (an id outside [0, n_groups) puts the row in no group).  Returns bootstrap_tables' dict with order, lo, hi int32
+    [K, N] taken over (group, score) -- per class the rows in ascending order of their group, then their score; a tie group ends
+    where the group does -- plus groups int32 [N], group_start int32 [G + 1] and G.  Device sorts, once per call."""
+    _need_gpu(scores, "subgroup_tables")
+    if scores.dim() != 2 or scores.dtype != torch.float32:
+        raise ValueError(f"subgroup_tables: scores must be an fp32 [N, K] tensor, got {scores.dtype} {tuple(scores.shape)}")
+    N, K = scores.shape
+    G = int(n_groups)
+    subgroup_check_limits("subgroup_tables", N=N, K=K, G=G)
+    dev = scores.device
+    for name, t in (("labels", labels), ("groups", groups)) + ((("preds", preds),) if preds is not None else ()):
+        if t is None or tuple(t.shape) != (N,) or t.dtype.is_floating_point or t.dtype == torch.bool or t.device != dev:
+            raise ValueError(f"subgroup_tables: {name} must be an integer {(N,)} tensor on {dev}")
+    labels = labels.detach().long().contiguous()
+    preds = (scores.argmax(dim=1) if preds is None else preds.detach()).long().contiguous()
+    groups = groups.detach().long()
+    key = torch.where((groups >= 0) & (groups < G), groups, torch.full_like(groups, G))      # [N] in 0 .. G
+    vals, order = torch.sort(scores.detach().t().contiguous(), dim=1, stable=True)           # [K, N] by score ...
+    by_group = torch.sort(key[order], dim=1, stable=True)                                    # ... then, stably, by group
+    order, vals, keys = torch.gather(order, 1, by_group.indices), torch.gather(vals, 1, by_group.indices), by_group.values
+    at = torch.arange(N, device=dev, dtype=torch.int64).expand(K, N)
+    edge = torch.ones((K, 1), dtype=torch.bool, device=dev)
+    differs = (vals[:, 1:] != vals[:, :-1]) | (keys[:, 1:] != keys[:, :-1])                  # position q + 1 opens a new tie group
+    lo = torch.cummax(torch.where(torch.cat([edge, differs], dim=1), at, torch.zeros_like(at)), dim=1).values
+    ends = torch.where(torch.cat([differs, edge], dim=1), at + 1, torch.full_like(at, N))
+    hi = torch.cummin(ends.flip(1), dim=1).values.flip(1)
+    group_start = torch.zeros(G + 1, dtype=torch.int64, device=dev)
+    group_start[1:] = torch.cumsum(torch.bincount(key, minlength=G + 1)[:G], dim=0)
+    members = torch.sort(labels, stable=True).indices
+    class_start = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+    class_start[1:] = torch.cumsum(torch.bincount(labels.clamp(0, K - 1), minlength=K), dim=0)
+    i32 = lambda t: t.to(torch.int32).contiguous()
+    return {"labels": labels, "preds": preds, "groups": i32(groups.clamp(-1, G)), "order": i32(order), "lo": i32(lo), "hi": i32(hi),
+            "group_start": i32(group_start), "members": i32(members), "class_start": i32(class_start), "N": int(N), "K": int(K), "G": G}
+
+
+def subgroup_accumulators(B, G, K, device, fill=0):
+    """(confusion int32 [B, G, K, K], counts int64 [B, G, 3 K]) for subgroup_replicates to fill"""
+    subgroup_check_limits("subgroup_accumulators", K=int(K), G=int(G), B=int(B))
+    return (torch.full((B, G, K, K), fill, dtype=torch.int32, device=device), torch.full((B, G, 3 * K), fill, dtype=torch.int64, device=device))
+
+
+def subgroup_replicates(tables, seed, mode, confusion, counts, b0=0, b1=None):
+    """The per-group integers of replicates [b0, b1) written into their slices of confusion int32 [B, G, K, K] and counts int64
+    [B, G, 3 K] (pos, neg, wins2 within the group), one workgroup per replicate (mmskin_subgroup_replicates).  The weights are
+    those of bootstrap_weights for the same seed and mode, whatever the groups are."""
+    N, K, G = tables["N"], tables["K"], tables["G"]
+    _need_gpu(tables["labels"], "subgroup_replicates")
+    if confusion is None or confusion.dim() != 4:
+        raise ValueError("subgroup_replicates: confusion must be an int32 [B, G, K, K] device tensor")
+    B = confusion.shape[0]
+    subgroup_check_limits("subgroup_replicates", N=N, K=K, G=G, B=B)
+    _dev_tensor(confusion, torch.int32, (B, G, K, K), "subgroup_replicates: confusion")
+    _dev_tensor(counts, torch.int64, (B, G, 3 * K), "subgroup_replicates: counts")
+    b0, b1 = _bootstrap_range(B, b0, b1)
+    call("mmskin_subgroup_replicates", int(seed) & (2 ** 64 - 1), int(mode), N, K, G, B, ptr(tables["labels"]), ptr(tables["preds"]),
+         ptr(tables["groups"]), ptr(tables["members"]), ptr(tables["class_start"]), ptr(tables["order"]), ptr(tables["lo"]), ptr(tables["hi"]),
+         ptr(tables["group_start"]), b0, b1, ptr(confusion), ptr(counts), stream())
+
+
+def subgroup_finalize(confusion, counts, confidence=0.95, min_rows=1):
+    """(metrics fp64 [G, 7 + 4 K, B], summary fp64 [G, 5, 7 + 4 K]) on the device from the filled accumulators: per group the
+    columns of bootstrap_finalize, then K false-positive rates and K predicted rates; a group below `min_rows` weighted rows in a
+    replicate is NaN there (mmskin_subgroup_finalize)."""
+    _need_gpu(confusion, "subgroup_finalize")
+    if confusion.dim() != 4:
+        raise ValueError("subgroup_finalize: confusion must be an int32 [B, G, K, K] device tensor")
+    B, G, K = confusion.shape[:3]
+    subgroup_check_limits("subgroup_finalize", K=K, G=G, B=B)
+    _dev_tensor(confusion, torch.int32, (B, G, K, K), "subgroup_finalize: confusion")
+    _dev_tensor(counts, torch.int64, (B, G, 3 * K), "subgroup_finalize: counts")
+    if int(min_rows) < 1:
+        raise ValueError(f"subgroup_finalize: min_rows must be >= 1, got {min_rows}")
+    q_lo, q_hi = bootstrap_quantiles(confidence)
+    M = subgroup_metric_columns(K)
+    metrics = torch.empty((G, M, B), dtype=torch.float64, device=confusion.device)
+    summary = torch.empty((G, 5, M), dtype=torch.float64, device=confusion.device)
+    call("mmskin_subgroup_finalize", ptr(confusion), ptr(counts), B, G, K, int(min_rows), q_lo, q_hi, ptr(metrics), ptr(summary), stream())
+    return metrics, summary
+
+
+def subgroup_gaps(metrics, confidence=0.95):
+    """(lowest, highest, gap fp64 [M, B], lowest_group int64 [M, G], summary fp64 [3, 5, M]) from the metrics fp64 [G, M, B] of
+    subgroup_finalize: per column and replicate the extremes over the groups defined there and their difference
+    (mmskin_subgroup_gaps)."""
+    _need_gpu(metrics, "subgroup_gaps")
+    if metrics.dim() != 3:
+        raise ValueError("subgroup_gaps: metrics must be an fp64 [G, M, B] device tensor")
+    G, M, B = metrics.shape
+    subgroup_check_limits("subgroup_gaps", G=G, B=B)
+    _dev_tensor(metrics, torch.float64, (G, M, B), "subgroup_gaps: metrics")
+    q_lo, q_hi = bootstrap_quantiles(confidence)
+    dev = metrics.device
+    lowest, highest, gap = (torch.empty((M, B), dtype=torch.float64, device=dev) for _ in range(3))
+    lowest_group = torch.empty((M, G), dtype=torch.int64, device=dev)
+    summary = torch.empty((3, 5, M), dtype=torch.float64, device=dev)
+    call("mmskin_subgroup_gaps", ptr(metrics), B, G, M, q_lo, q_hi, ptr(lowest), ptr(highest), ptr(gap), ptr(lowest_group), ptr(summary), stream())
+    return lowest, highest, gap, lowest_group, summary
+
+
+def subgroup_compare(metrics_a, metrics_b, confidence=0.95):
+    """bootstrap_compare on two metric tables fp64 [M, B] of any width: mmskin_bootstrap_compare takes 7 + 2 * 64 columns a call, a
+    subgroup table has up to 7 + 4 * 64, so the rows go through it in blocks.  Returns (delta, summary [5, M], sign_counts [M, 2])."""
+    step = 7 + 2 * BOOTSTRAP_MAX_CLASSES
+    M = metrics_a.shape[0]
+    if M <= step:
+        return bootstrap_compare(metrics_a, metrics_b, confidence)
+    parts = [bootstrap_compare(metrics_a[m:m + step], metrics_b[m:m + step], confidence) for m in range(0, M, step)]
+    return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts], dim=1), torch.cat([p[2] for p in parts])
+
+
 # ---------------------------------------------------------------------------------------------- calibration of a fold's probabilities
 CALIBRATION_MAX_ROWS = 1 << 24                                                               # MMSKIN_CALIBRATION_MAX_* of mmskin.h
 CALIBRATION_MAX_CLASSES = 64
